@@ -6,12 +6,22 @@ bases already resident in HBM, followed -- for N > 1 -- by the all-gather of the
 points over RCCL and the local EC add, so that every rank ends the step holding the final group
 element.  Weak scaling: every rank owns its own 2^20 pairs of one N*2^20-pair MSM.
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints ONE
+JSON line (rank 0) with the contract fields only (metric, value, unit, higher_is_better, dtype, ms_per_step,
+the configuration).  Its timed steps are the bare MSMs; with `--full` the same steps also record HIP events
+around k_acc0 (the roofline's kernel time), which costs a few percent -- so do not compare a plain `value` or
+`ms_per_step` with a `--full` one.  `--full` adds everything else, as one line as well:
   roofline     : the dominant kernel (k_acc0, bucket accumulate) -- algorithmic bytes per launch
                  (128 B per pair x pairs per launch) / its mean duration measured with HIP events on
-                 the library's stream, against the 8 TB/s HBM peak;
+                 the library's stream, against the 8 TB/s HBM peak; stage_ms of every kernel;
   cpu_baseline : the CPU restatement of the reference algorithm (oracle/, kind "port") timed on this
-                 box's host cores on one full 2^20 MSM of the same inputs (rank 0, N = 1 only).
+                 box's host cores on one full 2^20 MSM of the same inputs (rank 0, N = 1 only);
+  and the further legs (fixed-base tables, batch_commit, PCIe, time_prover, psnark, strong scaling),
+  which the --no-* / --*-logn options below select.
+`--dump-outputs DIR` writes what the last timed step computed (rank 0): DIR/msm_result.npy, the MSM's G1
+point as canonical affine coordinates, float64 of shape (2, 12) -- x and y in 32-bit little-endian limbs
+(exact in float64); the point at infinity is all zeros.  The inputs are seeded: the same arguments give
+the same inputs, and so the same file, from run to run.
 """
 import argparse
 import ctypes as C
@@ -88,6 +98,20 @@ def uniform_fr(rng: np.random.Generator, n: int) -> np.ndarray:
             eq &= v[:, k] == r_l[k]
         out[todo[lt]] = v[lt]
         todo = todo[~lt]
+    return out
+
+
+def g1_affine_limbs(jac: np.ndarray) -> np.ndarray:
+    """a Jacobian G1 point (18 u64: X, Y, Z in Montgomery form, as the library returns it) as canonical affine x, y in 32-bit
+    little-endian limbs, float64 (2, 12) -- exact; the point at infinity is all zeros"""
+    q = 0x1A0111EA397FE69A4B1BA7B6434BACD764774B84F38512BF6730D2A0F6B0F6241EABFFFEB153FFFFB9FEFFFFFFFFAAAB
+    r_inv = pow(1 << 384, -1, q)
+    X, Y, Z = (sum(int(v) << (64 * i) for i, v in enumerate(c)) * r_inv % q for c in np.asarray(jac, dtype=np.uint64).reshape(3, 6))
+    out = np.zeros((2, 12), dtype=np.float64)
+    if Z:
+        zi = pow(Z, -1, q)
+        for row, v in enumerate((X * zi * zi % q, Y * zi * zi * zi % q)):
+            out[row] = [(v >> (32 * i)) & 0xFFFFFFFF for i in range(12)]
     return out
 
 
@@ -415,9 +439,12 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--logn", type=int, default=LOG_N, help="pairs per GPU per step = 2^logn (default: BASELINE configs[1])")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/msm_result.npy (rank 0; see the module docstring)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: roofline and stage_ms, the CPU baselines and the further legs "
+                    "(the options below act only with --full)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--headline-only", action="store_true", help="only the timed headline loop (what the rocprofv3 summary under profiles/ is taken "
-                    "from: the extra legs overlap kernels on several streams, which stretches their durations)")
+    ap.add_argument("--headline-only", action="store_true", help="with --full: the timed headline loop and its roofline / stage_ms only (what the rocprofv3 "
+                    "summary under profiles/ is taken from: the extra legs overlap kernels on several streams, which stretches their durations)")
     ap.add_argument("--no-tables", action="store_true", help="skip the extra fixed-base-table measurement")
     ap.add_argument("--cpu-snark-logn", type=int, default=20, help="instance size of the time_prover CPU baseline (0 = skip)")
     ap.add_argument("--no-cpu-snark-top", action="store_true", help="do not run the time_prover CPU baseline at --snark-logn itself (about a minute at 2^24), "
@@ -428,6 +455,10 @@ def main():
     ap.add_argument("--strong-msm-logn", type=int, default=26, help="also time ONE MSM of 2^k pairs in total, split n / g over the ranks (strong scaling; 0 = skip)")
     ap.add_argument("--snark-logn", type=int, default=24, help="also time snark::Proof::new_time on dummy_r1cs(2^k) (N=1 only; 0 = skip)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.headline_only = True  # the plain run: the headline loop alone, without even its roofline pass (below)
     if args.headline_only:
         args.no_cpu_baseline = True
         args.no_tables = True
@@ -532,8 +563,9 @@ def main():
         results[i & 1] = step(i)
     # HIP events around k_acc0 ONLY in the timed steps (mode 2): an event record between two kernels of a call is a ~10 us bubble
     # on the stream, and the dominant kernel is the one the contract wants timed live; the other stages are timed in a short
-    # untimed pass after the loop
-    gm.capi.check(lib.gm_prof_enable(C.c_int(2)))
+    # untimed pass after the loop (--full only: a plain run times the bare steps)
+    if args.full:
+        gm.capi.check(lib.gm_prof_enable(C.c_int(2)))
     barrier()
     throttled0 = cpu_throttled_usec()
     t0 = time.perf_counter()
@@ -545,6 +577,41 @@ def main():
     throttled_in_loop = cpu_throttled_usec() - throttled0
     if world > 1:
         elapsed = float(collective.allgather_host(np.array([elapsed], dtype=np.float64).view(np.uint64)).view(np.float64).max())
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "msm_result.npy"), g1_affine_limbs(r))
+    def config() -> dict:
+        """read when the line is printed: with --full, the routes then count the collectives of every leg, not only the headline's"""
+        return {
+            "workload": f"2^{args.logn} G1 MSM per GPU (BASELINE configs[1]: 2^20 G1 MSM on one MI355X)",
+            "pairs_per_gpu": n,
+            "parallelism": f"pairs sharded over {world} GPU(s), all-gather of 144-byte partial points + local EC add",
+            "collective": None if world == 1 else {"transport": collective.info()[2], "inside_library": "gm_dist_allgather_host_class (gemini_amd/csrc/dist.cpp)",
+                                                   # which route each class of collective took: partial G1 points (the per-MSM reduce) vs field values / barriers
+                                                   "routes": collective.stats_routes(), "note": transport_note},
+        }
+
+    headline = {
+        "metric": "BLS12-381 G1 MSM throughput",
+        "value": round(world * n * args.steps / elapsed / 1e6, 3),
+        "unit": "Mscalar/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u32x12 Montgomery Fq (381-bit integer), u32x8 Fr",
+        "data": "synthetic: uniform random Fr scalars x uniform random G1 affine points (k_i*G), seeded",
+        "config": None,  # config(), filled in when the line is printed
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(dict(headline, config=config())))
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     ms = (C.c_double * 7)()
     cnt = (C.c_uint64 * 7)()
@@ -747,31 +814,11 @@ def main():
     if args.psnark_logn > 0:
         ptp = guarded("psnark_time_prover", lambda: psnark_time_prover(gm, args.psnark_logn, world=world, rank=rank))
     if rank == 0:
-        pairs = world * n * args.steps
-        value = pairs / elapsed / 1e6
         acc0_ms = stages["acc0"]
         achieved = BYTES_PER_PAIR * n / (acc0_ms * 1e-3) / 1e9 if acc0_ms else None
         out = {
-            "metric": "BLS12-381 G1 MSM throughput",
-            "value": round(value, 3),
-            "unit": "Mscalar/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u32x12 Montgomery Fq (381-bit integer), u32x8 Fr",
-            "data": "synthetic: uniform random Fr scalars x uniform random G1 affine points (k_i*G), seeded",
-            "config": {
-                "workload": f"2^{args.logn} G1 MSM per GPU (BASELINE configs[1]: 2^20 G1 MSM on one MI355X)",
-                "pairs_per_gpu": n,
-                "parallelism": f"pairs sharded over {world} GPU(s), all-gather of 144-byte partial points + local EC add",
-                "collective": None if world == 1 else {"transport": collective.info()[2], "inside_library": "gm_dist_allgather_host_class (gemini_amd/csrc/dist.cpp)",
-                                                       # which route each class of collective took: partial G1 points (the per-MSM reduce) vs field values / barriers
-                                                       "routes": collective.stats_routes(), "note": transport_note},
-            },
+            **headline,
+            "config": config(),  # after every leg, as the routes say
             "roofline": {
                 "bound": "hbm",
                 "kernel": "k_acc0 (bucket accumulate)",

@@ -7,7 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from tests.util import jac_to_affine_ints, rand_bases
+from tests.util import check_world, jac_to_affine_ints, rand_bases
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -162,13 +162,14 @@ def test_sharded_provers_from_plain_c_abi_processes(oracle, pyref, tmp_path):
     args = [hexl(ev[0]), hexl(ev[1]), hexl(oracle.g1_generator()), hexl(oracle.ints_to_limbs([tau_i], 4)[0])]
 
     def run(world, mode, cols="local", logn=10):
+        check_world(world)
         out = subprocess.run([exe, str(world), str(logn), mode, cols] + args, capture_output=True, text=True, timeout=600)
         assert out.returncode == 0, out.stderr[-2000:]
         return out.stdout.split()[1]
 
     one = run(1, "cyclic")
     assert run(1, "block") == one
-    for world in (8,):  # (1 / 2 / 4 / 8 of the same prover through Python launchers: tests/test_gpu_dist_native.py)
+    for world in (4,):  # (1 / 2 / 4 of the same prover through Python launchers: tests/test_gpu_dist_native.py; 4 = the largest power of two within tests.util.MAX_RANKS)
         assert run(world, "block") == one, world
     assert run(4, "block", "global") == one
     for world in (3, 5):
@@ -182,6 +183,7 @@ def test_sharded_provers_from_plain_c_abi_processes(oracle, pyref, tmp_path):
     g2_file.write_bytes(G2.serialize_vec_uncompressed([G2.mul(G2.generator(), pow(tau_i, i, R)) for i in range(6)]))
 
     def run_p(world, logn=9):
+        check_world(world)
         out = subprocess.run([exe, str(world), str(logn), "psnark", "global"] + args + [str(g2_file)], capture_output=True, text=True, timeout=600)
         assert out.returncode == 0, out.stderr[-2000:]
         return out.stdout.split()[1]

@@ -16,6 +16,8 @@ import sys
 import numpy as np
 import pytest
 
+from tests.util import check_world
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -32,6 +34,7 @@ def _run(world, extra, tool="run_snark.py", logn=12, transport="shm", env_extra=
     env = dict(os.environ, GM_BENCH_BACKEND="gloo", GM_BENCH_SINGLE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.update(env_extra or {})
     script = [os.path.join(ROOT, "tools", tool), "-i", str(logn), "--repeat", "1"] + list(extra)
+    check_world(world)
     if world == 1 and transport is None:
         cmd = [sys.executable] + script
     else:
@@ -141,13 +144,16 @@ def test_cyclic_key_native_psnark_same_proof(extra):
 
 @pytest.mark.parametrize("tail_log", [4, 6, 8])
 def test_block_sharded_native_prover_same_proof(tail_log):
-    """gm_snark_new_time_sharded, block-diagonal instance (local columns): 1 / 2 / 4 / 8 ranks == gm_snark_new_time.  tail_log = 8 on
-    8 ranks (blocks of 512): the first gathered level is TWO blocks long -- every rank takes its range of the replicated levels in
-    the n / g opening, not rank 0 all of them (found by tests/soak_dist_native.py, which sweeps transports x worlds x tails)"""
-    one = _single()
-    for world in {4: (2,), 6: (4,), 8: (8,)}[tail_log]:
-        many = _run(world, ["--block-sharded", "--tail-log", str(tail_log)], transport="hook" if (tail_log, world) == (4, 2) else "shm")
-        assert many["proof_sha256"] == one["proof_sha256"], (world, tail_log)
+    """gm_snark_new_time_sharded, block-diagonal instance (local columns): 1 / 2 / 4 ranks == gm_snark_new_time.  tail_log = 8 on
+    4 ranks of 2^10 constraints (blocks of 256): the first gathered level is TWO blocks long -- every rank takes its range of the
+    replicated levels in the n / g opening, not rank 0 all of them (found by tests/soak_dist_native.py, which sweeps transports x
+    worlds x tails; 8 ranks of 2^12 there).  4 ranks: the largest power of two within tests.util.MAX_RANKS.  (With 4 ranks a
+    first gathered level two blocks long means no folded level stays block-sharded before it; the sharded levels before the
+    gather are the tail_log = 4 / 6 cases.)"""
+    world, logn = {4: (2, 12), 6: (4, 12), 8: (4, 10)}[tail_log]
+    one = _single(logn=logn)
+    many = _run(world, ["--block-sharded", "--tail-log", str(tail_log)], logn=logn, transport="hook" if (tail_log, world) == (4, 2) else "shm")
+    assert many["proof_sha256"] == one["proof_sha256"], (world, tail_log)
 
 
 def test_block_sharded_native_prover_general_matrices():
@@ -197,13 +203,14 @@ print("ok", rank)
 """ % ROOT
 
 
-@pytest.mark.parametrize("world", [2, 8])
+@pytest.mark.parametrize("world", [2, 4])  # (8 ranks: tests/soak_dist_native.py; tests.util.MAX_RANKS here)
 def test_reblocking_between_ranks_on_the_shared_gpu(world):
     """gm_dist_reblock_vecs over the host transport (N processes share the one GPU): the levels of a folding tree, sharded in
     blocks of m / 2^j, arrive as the blocks [r m, (r + 1) m) of the same global vectors -- what the n / g opening of the
     block-sharded prover needs (src/kzg/time.rs:149-159 opens ONE polynomial; rank r commits ITS coefficient range of its quotient)"""
     name = f"/gm_reblock_{os.getpid()}_{world}"
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    check_world(world)
     procs = [subprocess.Popen([sys.executable, "-c", REBLOCK_WORKER, str(r), str(world), name], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env)
              for r in range(world)]
     outs = [p.communicate(timeout=600) for p in procs]
@@ -238,15 +245,15 @@ def test_sharded_sumcheck_refuses_blocks_that_do_not_tile():
 
 
 # ---- psnark with the FIELD side block-sharded (gm_psnark_new_time_sharded, gemini_amd/csrc/psnark_sharded.cpp) ---------------------
-@pytest.mark.parametrize("world,tail_log,transport", [(1, 4, "shm"), (3, 5, "hook"), (8, 4, "shm")])  # (2, 4, 5, 6, 7, 9 ranks: tests/soak_dist_native.py)
+@pytest.mark.parametrize("world,tail_log,transport", [(1, 4, "shm"), (3, 5, "hook"), (4, 4, "shm")])  # (2, 5, 6, 7, 8, 9 ranks: tests/soak_dist_native.py)
 def test_block_sharded_psnark_same_proof(world, tail_log, transport):
-    """BASELINE configs[4]: psnark::Proof::new_time (src/psnark/time_prover.rs:69-384) with every vector in blocks over 1 / 2 / 3 / 4 / 8 ranks
+    """BASELINE configs[4]: psnark::Proof::new_time (src/psnark/time_prover.rs:69-384) with every vector in blocks over 1 / 3 / 4 ranks
     sharing the test GPU == gm_psnark_new_time byte for byte (dummy_r1cs, src/psnark/tests.rs:14-55): lookups from replicated sources, the suffix
     products with a carry between ranks, the 13-prover batch sumcheck with one all-gather per round, the n / g openings"""
     one = _single(tool="run_psnark.py", logn=10)
     many = _run(world, ["--block-sharded", "--tail-log", str(tail_log)], tool="run_psnark.py", logn=10, transport=transport)
     assert many["n_gpus"] == world and many["proof_sha256"] == one["proof_sha256"], (world, tail_log)
-    if world == 8:  # the layout really has LEVELS here: the ~n-long families in blocks half the size of the ~2n-long ones
+    if world >= 4:  # the layout really has LEVELS here: the ~n-long families in blocks half the size of the ~2n-long ones
         levels = many["layout"]["levels_by_family_length"]
         assert max(levels.values()) >= 1 and min(levels.values()) == 0, levels
 
@@ -280,16 +287,16 @@ def fake_rccl(tmp_path_factory):
     return {"GM_RCCL_LIB": so, "GM_FAKE_RCCL_TIMEOUT_S": "120"}
 
 
-@pytest.mark.parametrize("world,transport", [(2, "rccl"), (8, "rccl-node")])
+@pytest.mark.parametrize("world,transport", [(2, "rccl"), (4, "rccl-node")])  # (8 ranks: tools/r6_final.sh n2; tests.util.MAX_RANKS here)
 def test_rccl_branches_with_n_ranks_snark(fake_rccl, world, transport):
-    """gm_snark_new_time_sharded over the RCCL transport with 2 and 8 ranks: ncclAllGather of host payloads (staged) and of device vectors (the gathered
+    """gm_snark_new_time_sharded over the RCCL transport with 2 and 4 ranks: ncclAllGather of host payloads (staged) and of device vectors (the gathered
     level), the grouped ncclSend / ncclRecv of gm_dist_reblock_vecs; with rccl-node the field payloads take the side segment and the G1 points RCCL"""
     one = _single()
     many = _run(world, ["--block-sharded", "--tail-log", "5"], transport=transport, env_extra=fake_rccl)
     assert many["transport"] == "rccl" and many["proof_sha256"] == one["proof_sha256"], (world, transport)
 
 
-@pytest.mark.parametrize("world,transport", [(2, "rccl-node"), (4, "rccl")])  # (8 ranks over the stand-in: the snark test above and tools/r6_final.sh n2)
+@pytest.mark.parametrize("world,transport", [(2, "rccl-node"), (4, "rccl")])  # (8 ranks over the stand-in: tools/r6_final.sh n2)
 def test_rccl_branches_with_n_ranks_psnark(fake_rccl, world, transport):
     """gm_psnark_new_time_sharded the same way (BASELINE configs[4] over the transport the driver's 8-GPU run will use)"""
     logn = 10 if world == 2 else 8  # (the stand-in stages every payload through the host: 8 ranks of it are slow)

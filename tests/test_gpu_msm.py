@@ -1,6 +1,9 @@
 """GPU parity: G1 MSM through the C ABI vs the CPU restatement of the reference algorithm
 (oracle/gemini_oracle.c, itself pinned in test_oracle_pin.py).  Bit-exact after normalisation."""
 import ctypes as C
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -631,6 +634,46 @@ def test_segmented_srs_and_batch_with_offsets(gm, oracle, pyref):
         plain.free()
 
 
+# ---- the experiments live in a build of their own: build() compiles it beside the product -------------------
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EXPERIMENTS_LIB = os.path.join(ROOT, "gemini_amd", "_experiments", "libgemini_hip.so")
+EXPERIMENT_TESTS = "test_affine_levels_same_results or test_affine_levels_large or test_msm_window_group_split or test_msm_glv_same_results"
+
+
+def _has_experiments(gm) -> bool:
+    lib = gm.capi.load()
+    if lib.gm_set_msm_split(C.c_int(1)) == 0:
+        gm.capi.check(lib.gm_set_msm_split(C.c_int(0)))
+        return True
+    assert b"GM_EXPERIMENTS" in lib.gm_last_error(), lib.gm_last_error()
+    return False
+
+
+@pytest.fixture(scope="module")
+def experiments_run():
+    """the experiment tests of this module, run ONCE in a child process on the experiments build (GM_LIB_PATH): test name -> outcome"""
+    assert os.path.exists(EXPERIMENTS_LIB), f"{EXPERIMENTS_LIB} missing: build() compiles it (make -C gemini_amd/csrc experiments)"
+    env = dict(os.environ, GM_LIB_PATH=EXPERIMENTS_LIB)
+    out = subprocess.run([sys.executable, "-m", "pytest", "-q", "-rA", "-p", "no:cacheprovider", "-m", "gpu", "-k", EXPERIMENT_TESTS,
+                          os.path.join("tests", "test_gpu_msm.py")], env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
+    res = {}
+    for line in out.stdout.splitlines():
+        parts = line.split(" ", 2)
+        if len(parts) >= 2 and parts[0] in ("PASSED", "FAILED", "ERROR", "SKIPPED"):
+            res[parts[1].split("::", 1)[-1]] = (parts[0], out.stdout[-4000:] + out.stderr[-2000:])  # by test name: one module
+    return res
+
+
+def _ran_on_experiments_build(gm, request) -> bool:
+    """False when the loaded library carries the experiments (the test body runs here); otherwise the test has run in the child
+    process on the experiments build, and it must have PASSED there"""
+    if _has_experiments(gm):
+        return False
+    outcome, log = request.getfixturevalue("experiments_run").get(request.node.name, ("NOT RUN", ""))
+    assert outcome == "PASSED", f"{request.node.nodeid} on the experiments build: {outcome}\n{log}"
+    return True
+
+
 def _set_levels(gm, k):
     import ctypes as C
 
@@ -641,11 +684,13 @@ def _set_levels(gm, k):
 
 
 @pytest.mark.parametrize("levels", [1, 2, 3, 5])
-def test_affine_levels_same_results(gm, oracle, levels):
+def test_affine_levels_same_results(gm, oracle, levels, request):
     """gm_set_msm_affine_levels: pairwise affine additions with one shared inversion per level in front of
     the XYZZ accumulation -- the result cannot depend on it.  Inputs hit every exceptional pair: repeated
     bases (P + P), P and -P in one bucket, identity bases, all-equal scalars (one bucket per window), zero
     scalars, and sizes around the lane count."""
+    if _ran_on_experiments_build(gm, request):
+        return
     rng = np.random.default_rng(levels)
     cases = []
     n = 3000
@@ -686,8 +731,10 @@ def test_affine_levels_same_results(gm, oracle, levels):
         _set_window(gm, 0)
 
 
-def test_affine_levels_large(gm, oracle):
+def test_affine_levels_large(gm, oracle, request):
     """2^18 pairs, automatic and fixed level counts against the plain path, also with fixed-base tables"""
+    if _ran_on_experiments_build(gm, request):
+        return
     n = 1 << 18
     ks = oracle.random_fr(61, n)
     b = gm.G1Bases.fixed_base(oracle.g1_generator(), ks)
@@ -753,9 +800,11 @@ def test_msm_rejects_scalars_that_are_not_fr_images(gm, oracle):
     bases.free()
 
 
-def test_msm_window_group_split(gm, oracle):
+def test_msm_window_group_split(gm, oracle, request):
     """gm_set_msm_split: a one-call MSM as two window groups on three streams gives the same group element
     (2^17 + 3 pairs, the smallest size that splits, and the degenerate all-equal-scalars instance)."""
+    if _ran_on_experiments_build(gm, request):
+        return
     lib = gm.capi.load()
     n = (1 << 17) + 3
     bases = gm.G1Bases.fixed_base(oracle.g1_generator(), oracle.random_fr(95, n))
@@ -774,10 +823,12 @@ def test_msm_window_group_split(gm, oracle):
 
 
 @pytest.mark.parametrize("n", [1, 33, 1000, 5000, (1 << 14) + 1, (1 << 17) + 3])
-def test_msm_glv_same_results(gm, oracle, pyref, n):
+def test_msm_glv_same_results(gm, oracle, pyref, n, request):
     """gm_set_msm_glv: bases registered with their images under the curve endomorphism, scalars split as
     s = v1 + v2 lambda with |v1|, |v2| < 2^127 (half the windows, two digit strings per scalar).  Same group element as
     the plain path and as the CPU Pippenger, incl. the scalars that sit on the decomposition's edges."""
+    if _ran_on_experiments_build(gm, request):
+        return
     lib = gm.capi.load()
     R = pyref.R_MOD
     lam = 0xAC45A4010001A40200000000FFFFFFFF

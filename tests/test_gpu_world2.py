@@ -10,6 +10,8 @@ import sys
 
 import pytest
 
+from tests.util import check_world
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -36,6 +38,7 @@ def _single(extra=()):
 def _run(world, extra, tool="run_snark.py", logn=12):
     env = dict(os.environ, GM_BENCH_BACKEND="gloo", GM_BENCH_SINGLE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     script = [os.path.join(ROOT, "tools", tool), "-i", str(logn), "--repeat", "1"] + extra
+    check_world(world)
     if world == 1:
         cmd = [sys.executable] + script
     else:

@@ -7,9 +7,19 @@ with the reference itself, and the two recalled conventions of DESIGN.md section
 append_serializable, Fr::from_random_bytes) stop being recalled.
 
 GM_REFVECTORS_DIR overrides the directory (tools/refvectors/mock_vectors.py uses it to exercise this module's
-plumbing with clearly-labelled NON-reference vectors)."""
+plumbing with clearly-labelled NON-reference vectors).
+
+The two GPU tests at the end do not skip while the files are absent: they then take the same-format vectors that
+tools/refvectors/mock_vectors.py writes from the CPU restatement (oracle/, itself pinned by test_oracle_pin.py and
+the KATs), so the device provers are still checked byte for byte, in both curve crates' encodings -- against the
+restatement, not the reference, until the reference's files are committed; each such pass carries a warning that says so.
+(The mock files hold no psnark fields, so the psnark branch below needs the reference's files; device psnark proofs are
+compared byte for byte with the restatement, in both encodings, in tests/test_gpu_psnark.py.)"""
 import json
 import os
+import subprocess
+import sys
+import warnings
 
 import numpy as np
 import pytest
@@ -36,6 +46,35 @@ def vectors(request):
     crate, fname, enc = request.param
     data = _load(fname)
     assert data["curve_crate"] == crate
+    from gemini_amd import transcript
+
+    transcript.set_curve_crate(crate)
+    yield data, enc
+    transcript.set_curve_crate("ark-test-curves")
+
+
+@pytest.fixture(scope="module")
+def _restatement_vectors_dir(tmp_path_factory):
+    d = str(tmp_path_factory.mktemp("restatement_vectors"))
+    subprocess.run([sys.executable, os.path.join(os.path.dirname(HERE), "tools", "refvectors", "mock_vectors.py"), d, "4"], check=True,
+                   capture_output=True, timeout=600)
+    return d
+
+
+@pytest.fixture(params=CRATES, ids=[c[0] for c in CRATES])
+def device_vectors(request):
+    """the reference's vectors when present, else the restatement's (module docstring)"""
+    crate, fname, enc = request.param
+    path = os.path.join(DIR, fname)
+    if not os.path.exists(path):
+        # said in every report (warnings summary, junit properties): this pass is parity with the restatement, NOT with the reference
+        warnings.warn(UserWarning(f"{fname} absent: the device provers are checked against the CPU restatement's vectors "
+                                  f"(tools/refvectors/mock_vectors.py), not against the reference"))
+        request.node.user_properties.append(("vectors", "restatement, not reference"))
+        path = os.path.join(request.getfixturevalue("_restatement_vectors_dir"), fname)
+    with open(path) as fh:
+        data = json.load(fh)
+    assert data["curve_crate"] == crate and data["cases"]
     from gemini_amd import transcript
 
     transcript.set_curve_crate(crate)
@@ -197,7 +236,7 @@ def _g_mont(case):
 
 
 @pytest.mark.gpu
-def test_device_time_prover_against_the_reference(vectors):
+def test_device_time_prover_against_the_reference(device_vectors):
     import gemini_amd
 
     gemini_amd.capi.init()
@@ -206,7 +245,7 @@ def test_device_time_prover_against_the_reference(vectors):
     from gemini_amd.kzg import CommitterKey
     from gemini_amd.snark import Proof
 
-    data, enc = vectors
+    data, enc = device_vectors
     for case in data["cases"]:
         n = 1 << case["logn"]
         g2 = G2.deserialize_uncompressed(bytes.fromhex(case["g2_uncompressed"]), enc)
@@ -231,7 +270,7 @@ def test_device_time_prover_against_the_reference(vectors):
 
 
 @pytest.mark.gpu
-def test_device_elastic_prover_on_the_generator_key_against_the_reference(vectors):
+def test_device_elastic_prover_on_the_generator_key_against_the_reference(device_vectors):
     """examples/snark.rs:54-66: powers_of_g = n + 1 copies of the generator, max_msm_buffer = 2^20"""
     import gemini_amd
 
@@ -241,7 +280,7 @@ def test_device_elastic_prover_on_the_generator_key_against_the_reference(vector
     from gemini_amd.msm import G1Bases
     from gemini_amd.snark import Proof
 
-    data, enc = vectors
+    data, enc = device_vectors
     for case in data["cases"]:
         n = 1 << case["logn"]
         ones = np.zeros((n + 1, 4), dtype=np.uint64)

@@ -1,6 +1,17 @@
 """Shared helpers for the parity tests (test infrastructure)."""
 import numpy as np
 
+# The GPU suite keeps at most 6 processes with the device open at once -- the pytest process and up to MAX_RANKS ranks it starts:
+# shared test machines refuse more.  Every test that starts rank processes checks its world against this bound (`check_world`), and
+# the block-sharded snark, which needs a power-of-two world, runs at most 4 ranks here; 8 ranks live in the soak scripts
+# (tests/soak_dist_native.py) and in the multi-GPU bench runs.
+MAX_RANKS = 5
+
+
+def check_world(world: int) -> int:
+    assert 1 <= world <= MAX_RANKS, f"{world} rank processes: the suite starts at most MAX_RANKS = {MAX_RANKS} (tests/util.py)"
+    return world
+
 
 def rand_bases(orc, seed: int, n: int) -> np.ndarray:
     """n affine points k_i * G (Montgomery, (n, 12)) from the C oracle's fixed-base routine."""

@@ -20,5 +20,5 @@ tools/_build/fqmul_check > $O/fqmul_check.txt 2>&1
 tools/_build/ubench_regs > $O/ubench_regs.txt 2>&1
 python tools/degenerate_probe.py 20 24 > $O/degenerate_probe.txt 2>&1
 python tools/small_probe.py > $O/small_probe.txt 2>&1
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err
 ls -la $O
