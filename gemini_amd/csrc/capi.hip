@@ -406,7 +406,9 @@ int gm_init(int device) {
     }
   }
   GM_HIP(hipHostMalloc((void**)&C->host_small, 1 << 16, hipHostMallocDefault));
-  GM_HIP(hipHostMalloc((void**)&C->sc_desc_host, 8 << 15, hipHostMallocDefault));
+  GM_HIP(hipHostMalloc((void**)&C->sc_desc_host, SC_DESC_SLOTS * SC_DESC_SLOT, hipHostMallocDefault));
+  GM_HIP(gm::raw_malloc(&C->sc_desc_dev, SC_DESC_SLOTS * SC_DESC_SLOT));
+  for (auto& e : C->sc_desc_copied) GM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   if (const char* e = getenv("GM_ZERO_COPY")) C->zero_copy = atoi(e);
   g_ctx = C;
   return GM_OK;
@@ -462,6 +464,9 @@ void gm_shutdown(void) {
   C->cu_split = 0;
   if (C->host_small) (void)hipHostFree(C->host_small);
   if (C->sc_desc_host) (void)hipHostFree(C->sc_desc_host);
+  if (C->sc_desc_dev) (void)gm::raw_free(C->sc_desc_dev);
+  for (auto& e : C->sc_desc_copied)
+    if (e) (void)hipEventDestroy(e);
   if (C->host_batch) (void)hipHostFree(C->host_batch);
   (void)hipStreamDestroy(C->stream);
   delete C;

@@ -123,6 +123,9 @@ struct Sumcheck {
   std::mutex mu;
 };
 constexpr size_t SC_HOST_TAIL = 256;
+// the descriptor ring of k_sc_round_multi (Context::sc_desc_*): a launch takes as many provers as one slot holds descriptors
+constexpr size_t SC_DESC_SLOT = (size_t)32 << 10;
+constexpr unsigned SC_DESC_SLOTS = 8;
 
 struct SpaceProver {
   // src/subprotocols/sumcheck/space_prover.rs:20-40: the witness streams (big-endian, never modified),
@@ -295,11 +298,14 @@ struct Context {
   bool have_start_ev = false;
   DevBuf fr_scratch;
   uint64_t* host_small = nullptr;  // pinned, 64 KiB, for small results
-  // pinned staging of the descriptor arrays of k_sc_round_multi: a RING of 8 slots of 32 KiB, one per launch.  The copy to the device is
-  // asynchronous and the round is split-phase, so the source must outlive the call (a local vector would not) and must not be rewritten by the
-  // next launch of the same round (a sharded batch makes up to four per round); a slot comes round again after 8 launches, i.e. after at least
-  // one collected round (sc_round_end waits for the stream)
+  // the descriptor arrays of k_sc_round_multi: a RING of SC_DESC_SLOTS slots of SC_DESC_SLOT bytes, one per launch, pinned on the host
+  // and mirrored in a device buffer of their own.  The copy to the device is asynchronous and the round is split-phase, so the source must
+  // outlive the call (a local vector would not) and must not be rewritten by the next launch of the same round (a sharded batch makes up to
+  // four per round).  A slot that comes round again is rewritten only once the event recorded behind its last copy has completed: rounds
+  // enqueued by several threads, or one batch split over more launches than there are slots, never read another launch's descriptors
   uint8_t* sc_desc_host = nullptr;
+  uint8_t* sc_desc_dev = nullptr;
+  hipEvent_t sc_desc_copied[SC_DESC_SLOTS] = {};
   unsigned sc_desc_next = 0;
   uint64_t* host_batch = nullptr;  // pinned, grow-only: partial sums of a batch of evaluations (fr_eval_le_batch)
   size_t host_batch_cap = 0;

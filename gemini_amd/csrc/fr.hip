@@ -827,53 +827,57 @@ static int sc_enqueue(Context* C, Sumcheck* S, bool fold, bool msg, const gmh::F
   if (prof.on && !msg) GM_HIP(hipStreamSynchronize(st));
   return sc_after(C, S, fold, msg, blocks);
 }
-// the same for SEVERAL provers with the same (fold, msg): their descriptors go to the device in one small copy, ONE launch
-static int sc_enqueue_many(Context* C, Sumcheck** S, size_t k, bool fold, bool msg, const gmh::Fr& rho, size_t scratch_slot) {
+// the same for SEVERAL provers with the same (fold, msg): their descriptors go to the device in one small copy per launch, and a launch
+// takes as many provers as one descriptor slot holds (22: psnark's 13-prover batch is ONE launch per round)
+static int sc_enqueue_many(Context* C, Sumcheck** S, size_t k, bool fold, bool msg, const gmh::Fr& rho) {
   if (k == 1) return sc_enqueue(C, S[0], fold, msg, rho);
-  GM_FR_LOCK(C);  // (the descriptors travel through the small-upload area of the vector scratch)
+  GM_FR_LOCK(C);  // (the ring of descriptor slots is the context's)
+  GM_CHECK(C->sc_desc_host && C->sc_desc_dev, GM_ESTATE, "sumcheck: no descriptor ring");
   std::vector<ScMultiDesc> d(k);
-  unsigned max_blocks = 0;
   for (size_t j = 0; j < k; j++) {
     memset(&d[j], 0, sizeof d[j]);
     int rc = sc_prepare(C, S[j], fold, msg, rho, d[j].A, &d[j].blocks, &d[j].partials);
     if (rc) return rc;
     d[j].tw1 = msg && sc_twist_one(d[j].A) ? 1u : 0u;
-    max_blocks = std::max(max_blocks, d[j].blocks);
   }
-  const size_t bytes = k * sizeof(ScMultiDesc), slot = (size_t)32 << 10;
-  GM_CHECK(bytes <= slot && C->sc_desc_host, GM_EINVAL, "sumcheck: %zu provers in one launch", k);
-  (void)scratch_slot;
-  int rc = C->fr_scratch.ensure(1 << 20);
-  if (rc) return rc;
-  // through PINNED memory of the context, one ring slot per launch: the copy is asynchronous and nothing waits before this call returns.  (The
-  // first version used one slot per (fold, message) kind: the two launches of a round in which some provers of a sharded batch leave their
-  // sharded phase shared it, and the first launch read the second one's descriptors -- ranks produced different proofs at 8 ranks.)
-  const unsigned ring = C->sc_desc_next++ & 7u;
-  uint8_t* dd = C->fr_scratch.as<uint8_t>() + ring * slot;
-  uint8_t* hs = C->sc_desc_host + ring * slot;
-  memcpy(hs, d.data(), bytes);
-  GM_HIP(hipMemcpyAsync(dd, hs, bytes, hipMemcpyHostToDevice, C->stream));
+  constexpr size_t per_launch = SC_DESC_SLOT / sizeof(ScMultiDesc);
+  static_assert(per_launch >= 13, "psnark's third sumcheck is one launch per round");
   hipStream_t st = C->stream;
-  const dim3 grid(max_blocks, (unsigned)k);
-  const ScMultiDesc* dp = reinterpret_cast<const ScMultiDesc*>(dd);
   const bool lazy = sc_lazy();
-  if (fold && msg && lazy)
-    hipLaunchKernelGGL((k_sc_round_multi<true, true, true>), grid, dim3(256), 0, st, dp);
-  else if (fold && msg)
-    hipLaunchKernelGGL((k_sc_round_multi<true, true>), grid, dim3(256), 0, st, dp);
-  else if (fold)
-    hipLaunchKernelGGL((k_sc_round_multi<true, false>), grid, dim3(256), 0, st, dp);
-  else if (lazy)
-    hipLaunchKernelGGL((k_sc_round_multi<false, true, true>), grid, dim3(256), 0, st, dp);
-  else
-    hipLaunchKernelGGL((k_sc_round_multi<false, true>), grid, dim3(256), 0, st, dp);
-  GM_HIP(hipGetLastError());
+  for (size_t lo = 0; lo < k; lo += per_launch) {
+    const size_t m = std::min(per_launch, k - lo), bytes = m * sizeof(ScMultiDesc);
+    unsigned max_blocks = 0;
+    for (size_t j = lo; j < lo + m; j++) max_blocks = std::max(max_blocks, d[j].blocks);
+    // through PINNED memory of the context, one ring slot per launch: the copy is asynchronous and nothing waits for the kernel before
+    // this call returns.  The host rewrites a slot only after the copy that last read it has run (the event behind it); its device
+    // mirror is rewritten by a copy on the same stream, so after the kernel that read it.  (The first version used one slot per (fold,
+    // message) kind: the two launches of a round in which some provers of a sharded batch leave their sharded phase shared it, and the
+    // first launch read the second one's descriptors -- ranks produced different proofs at 8 ranks.)
+    const unsigned ring = C->sc_desc_next++ % SC_DESC_SLOTS;
+    uint8_t* dd = C->sc_desc_dev + ring * SC_DESC_SLOT;
+    uint8_t* hs = C->sc_desc_host + ring * SC_DESC_SLOT;
+    GM_HIP(hipEventSynchronize(C->sc_desc_copied[ring]));  // (returns at once for a slot never used)
+    memcpy(hs, d.data() + lo, bytes);
+    GM_HIP(hipMemcpyAsync(dd, hs, bytes, hipMemcpyHostToDevice, st));
+    GM_HIP(hipEventRecord(C->sc_desc_copied[ring], st));
+    const dim3 grid(max_blocks, (unsigned)m);
+    const ScMultiDesc* dp = reinterpret_cast<const ScMultiDesc*>(dd);
+    if (fold && msg && lazy)
+      hipLaunchKernelGGL((k_sc_round_multi<true, true, true>), grid, dim3(256), 0, st, dp);
+    else if (fold && msg)
+      hipLaunchKernelGGL((k_sc_round_multi<true, true>), grid, dim3(256), 0, st, dp);
+    else if (fold)
+      hipLaunchKernelGGL((k_sc_round_multi<true, false>), grid, dim3(256), 0, st, dp);
+    else if (lazy)
+      hipLaunchKernelGGL((k_sc_round_multi<false, true, true>), grid, dim3(256), 0, st, dp);
+    else
+      hipLaunchKernelGGL((k_sc_round_multi<false, true>), grid, dim3(256), 0, st, dp);
+    GM_HIP(hipGetLastError());
+  }
   for (size_t j = 0; j < k; j++) {
-    rc = sc_after(C, S[j], fold, msg, d[j].blocks);
+    int rc = sc_after(C, S[j], fold, msg, d[j].blocks);
     if (rc) return rc;
   }
-  // a fold-only launch has no collect phase that would wait for the stream: wait here, so that its descriptor slot is free for the next launch
-  if (!msg) GM_HIP(hipStreamSynchronize(C->stream));
   return GM_OK;
 }
 
@@ -1138,7 +1142,7 @@ int sc_round_end(Context* C, Sumcheck* S, uint64_t a[4], uint64_t b[4]) {
 }
 
 // the split-phase round of k provers with the same challenge (Sumcheck::prove_batch): provers on the device with the same (fold,
-// message) share ONE launch; the tails on the host step there.  Every prover is collected with sc_round_end as before.
+// message) share a launch (one per 22 provers: sc_enqueue_many); the tails on the host step there.  Every prover is collected with sc_round_end as before.
 int sc_round_begin_many(Context* C, Sumcheck** S, size_t k, const uint64_t* challenge, int* has_msg) {
   const bool fold = challenge != nullptr;
   const gmh::Fr rho = fold ? gmh::Fr::from_limbs(challenge) : gmh::Fr::zero();
@@ -1164,7 +1168,7 @@ int sc_round_begin_many(Context* C, Sumcheck** S, size_t k, const uint64_t* chal
   }
   for (int m = 1; m >= 0; m--)
     if (!dev[m].empty()) {
-      int rc = sc_enqueue_many(C, dev[m].data(), dev[m].size(), fold, m == 1, rho, (size_t)m);
+      int rc = sc_enqueue_many(C, dev[m].data(), dev[m].size(), fold, m == 1, rho);
       if (rc) return rc;
     }
   for (size_t j = 0; j < k; j++)

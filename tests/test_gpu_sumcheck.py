@@ -363,15 +363,21 @@ def test_space_prover_different_lengths(gm, oracle):
 
 
 def test_herring_fmodule_prover(gm, oracle, pyref):
-    """src/herring/time_prover.rs over FModule (module.rs:127-146): twist-free messages, twisted folds"""
+    """src/herring/time_prover.rs over FModule (module.rs:127-146): twist-free messages, twisted folds.  The small shapes step on the
+    host from the first round; 2^10 and 2^11 are the reference's sizes (ipa.rs:691,713: `1 << 8 + 2`, `1 << 9 + 2`) and reach the
+    device kernel, each with a random twist and with twist one."""
     from gemini_amd.herring import FModuleTimeProver
 
     I = lambda a: oracle.limbs_to_ints(oracle.fr_from_mont(np.asarray(a).reshape(-1, 4)))
-    for nf, ng in ((64, 64), (33, 33), (100, 17)):
+    one = _mont(oracle, [1])[0]
+    cases = [(64, 64, None), (33, 33, None), (100, 17, None)]
+    cases += [(nf, ng, tw) for nf, ng in ((1024, 1024), (2048, 2048), (2048, 1500)) for tw in (None, one)]
+    for nf, ng, tw in cases:
         f = oracle.fr_to_mont(oracle.random_fr(1100 + nf, nf))
         g = oracle.fr_to_mont(oracle.random_fr(1200 + ng, ng))
-        tw = oracle.fr_to_mont(oracle.random_fr(1300, 1))[0]
-        ch = oracle.fr_to_mont(oracle.random_fr(1400, 10))
+        if tw is None:
+            tw = oracle.fr_to_mont(oracle.random_fr(1300, 1))[0]
+        ch = oracle.fr_to_mont(oracle.random_fr(1400, 12))
         G = FModuleTimeProver(f, g, tw)
         P = pyref.HerringTimeProver("F", I(f), I(g), I(tw)[0])
         assert G.rounds() == P.tot_rounds

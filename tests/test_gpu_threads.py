@@ -151,3 +151,56 @@ def test_concurrent_batch_commit_and_one_call_msm(gm, oracle):
     for v in vecs:
         v.free()
     bases.free()
+
+
+def _batch_transcript(gm, inputs):
+    """Sumcheck::prove_batch on a transcript of its own: messages, challenges, final foldings and the next challenge, end to end"""
+    t = gm.Transcript()
+    provers = []
+    try:
+        provers = [gm.TimeProver(f, g, tw) for f, g, tw in inputs]
+        sc = gm.Sumcheck.prove_batch(t, provers)
+        out = [np.concatenate(m) for m in sc.messages] + list(sc.challenges) + [np.concatenate(ff) for ff in sc.final_foldings]
+        out.append(t.get_challenge(b"next"))
+    finally:
+        for p in provers:
+            p.free()
+        t.free()
+    return np.concatenate([np.ravel(x) for x in out])
+
+
+def test_concurrent_prove_batch_one_context(gm, oracle):
+    """12 threads run gm_sumcheck_prove_batch on one context, each on its own transcript and provers of 2^12 - 2^15 elements (rounds
+    on the device); one thread's batch has 32 provers, two launches per round, while the others run.  The rounds of all threads draw
+    their k_sc_round_multi descriptors from one ring of slots: every result must equal the serial run."""
+    T = 12
+    jobs = []
+    for t in range(T):
+        k = 32 if t == 7 else 3 + t % 3
+        inputs = []
+        for j in range(k):
+            nf = (1 << (12 + (t + j) % 4)) + 2 * j + 1
+            ng = nf - (t + j) % 3
+            seed = 7000 + 100 * t + 2 * j
+            inputs.append((oracle.fr_to_mont(oracle.random_fr(seed, nf)), oracle.fr_to_mont(oracle.random_fr(seed + 1, ng)),
+                           oracle.fr_to_mont(oracle.random_fr(seed + 50, 1))[0]))
+        jobs.append(inputs)
+    serial = [_batch_transcript(gm, jobs[t]) for t in range(T)]
+    for rep in range(3):
+        got = [None] * T
+        errs = []
+
+        def run(t):
+            try:
+                got[t] = _batch_transcript(gm, jobs[t])
+            except Exception as e:  # noqa: BLE001 -- reported below with the thread index
+                errs.append((t, repr(e)))
+
+        threads = [threading.Thread(target=run, args=(t,)) for t in range(T)]
+        for th in threads:
+            th.start()
+        for th in threads:
+            th.join()
+        assert not errs, errs
+        for t in range(T):
+            assert np.array_equal(got[t], serial[t]), f"thread {t}, repetition {rep}"

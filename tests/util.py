@@ -1,4 +1,7 @@
 """Shared helpers for the parity tests (test infrastructure)."""
+import os
+import re
+
 import numpy as np
 
 # The GPU suite keeps at most 6 processes with the device open at once -- the pytest process and up to MAX_RANKS ranks it starts:
@@ -11,6 +14,15 @@ MAX_RANKS = 5
 def check_world(world: int) -> int:
     assert 1 <= world <= MAX_RANKS, f"{world} rank processes: the suite starts at most MAX_RANKS = {MAX_RANKS} (tests/util.py)"
     return world
+
+
+def sc_host_tail() -> int:
+    """SC_HOST_TAIL of gemini_amd/csrc/ctx.hpp: a sumcheck prover whose vectors are down to this many elements runs its remaining
+    rounds on the host.  Tests that must reach the device kernels size their provers from it."""
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gemini_amd", "csrc", "ctx.hpp")).read()
+    m = re.search(r"constexpr\s+size_t\s+SC_HOST_TAIL\s*=\s*(\d+)\s*;", src)
+    assert m, "SC_HOST_TAIL not found in gemini_amd/csrc/ctx.hpp"
+    return int(m.group(1))
 
 
 def rand_bases(orc, seed: int, n: int) -> np.ndarray:
