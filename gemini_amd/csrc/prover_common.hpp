@@ -4,12 +4,10 @@
 #include <cstring>
 #include <vector>
 
-#include "../../include/gemini_hip.h"
-#include "host_field.hpp"
+#include "sumcheck_driver.hpp"
 
 namespace gmprover {
 
-using gmh::Fr;
 using Clock = std::chrono::steady_clock;
 
 inline double since(Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); }
@@ -44,33 +42,26 @@ struct TranscriptGuard {
   }
 };
 
-#define RC(x)            \
-  do {                   \
-    int rc_ = (x);       \
-    if (rc_) return rc_; \
-  } while (0)
-
-inline const uint8_t* L(const char* s) { return reinterpret_cast<const uint8_t*>(s); }
-
 inline int vec_len(uint64_t v, size_t* n) { return gm_fr_vec_len(v, n); }
 
 // Sumcheck::new_time (proof.rs:125-130): the prover reads f and g in place (the round loop runs inside this call and the
 // callers do not touch the vectors meanwhile), its folds go to buffers of its own
 inline int sumcheck_new_time(uint64_t transcript, uint64_t f, uint64_t g, const uint64_t twist[4], uint64_t* messages, std::vector<uint64_t>& challenges,
                              size_t cap_rounds, uint64_t final_foldings[8], size_t* rounds) {
-  uint64_t prover = 0;
-  RC(gm_sc_new_borrow(f, g, twist, &prover));
-  challenges.assign(cap_rounds * 4, 0);
-  int rc = gm_sumcheck_prove(transcript, prover, messages, challenges.data(), cap_rounds, final_foldings, rounds);
-  (void)gm_sc_free(prover);
-  if (!rc) challenges.resize(*rounds * 4);
-  return rc;
+  ElasticSc S;
+  RC(S.init_resident(f, g, twist));
+  return prove(transcript, S, messages, challenges, cap_rounds, final_foldings, rounds);
+}
+// Sumcheck::new_elastic (proof.rs:145-154): a SpaceProver over the streams that becomes a TimeProver when fewer than
+// SPACE_TIME_THRESHOLD rounds remain
+inline int sumcheck_new_elastic(uint64_t transcript, uint64_t f_stream, uint64_t g_stream, const uint64_t twist[4], uint64_t* messages,
+                                std::vector<uint64_t>& challenges, size_t cap_rounds, uint64_t final_foldings[8], size_t* rounds) {
+  ElasticSc S;
+  RC(S.init(f_stream, g_stream, twist, true));
+  return prove(transcript, S, messages, challenges, cap_rounds, final_foldings, rounds);
 }
 
-
 // ---- shared by snark.cpp / psnark.cpp / psnark_elastic.cpp -------------------------------------------------------------
-constexpr size_t SPACE_TIME_THRESHOLD = 22;  // src/lib.rs:76
-
 // sum over stream positions k < len: stream[k] * power[top - k], flushed every max(chunk, min_chunk) pairs
 // (msm_chunks / ChunkedPippenger composition, src/kzg/space.rs:22-55)
 inline int stream_msm(uint64_t bases, uint64_t stream, size_t len, size_t top, size_t chunk, uint64_t out[18]) {
@@ -85,61 +76,6 @@ inline int stream_msm(uint64_t bases, uint64_t stream, size_t len, size_t top, s
   }
   return gm_g1_sum(parts.data(), parts.size() / 18, out);
 }
-
-// Sumcheck::prove over an ElasticProver: a SpaceProver that becomes a TimeProver when fewer than
-// SPACE_TIME_THRESHOLD rounds remain (elastic_prover.rs:44-57); Prover::next_message folds first.
-inline int sumcheck_new_elastic(uint64_t transcript, uint64_t f_stream, uint64_t g_stream, const uint64_t twist[4], uint64_t* messages,
-                         std::vector<uint64_t>& challenges, size_t cap_rounds, uint64_t final_foldings[8], size_t* rounds) {
-  uint64_t space = 0, time = 0;
-  RC(gm_sp_new_borrow(f_stream, g_stream, twist, &space));
-  struct Guard {
-    uint64_t &s, &t;
-    ~Guard() {
-      if (t) (void)gm_sc_free(t);
-      if (s) (void)gm_sp_free(s);
-    }
-  } guard{space, time};
-  challenges.assign(cap_rounds * 4, 0);
-  size_t k = 0;
-  const uint64_t* vm = nullptr;
-  for (;;) {
-    if (vm && !time) {  // ElasticProver::fold
-      size_t tot = 0, rnd = 0;
-      RC(gm_sp_rounds(space, &tot, &rnd));
-      if (tot - rnd < SPACE_TIME_THRESHOLD) {
-        RC(gm_sp_to_time(space, &time));
-        RC(gm_sc_fold(time, vm));
-        (void)gm_sp_free(space);
-        space = 0;
-      } else {
-        RC(gm_sp_fold(space, vm));
-      }
-      vm = nullptr;
-    }
-    uint64_t a[4], b[4];
-    int has = 0;
-    if (time) RC(gm_sc_round(time, vm, a, b, &has));
-    else RC(gm_sp_round(space, vm, a, b, &has));
-    if (!has) break;
-    if (k >= cap_rounds) return GM_EINVAL;
-    memcpy(messages + 8 * k, a, 32);
-    memcpy(messages + 8 * k + 4, b, 32);
-    RC(gm_transcript_append_fr(transcript, L("evaluations"), 11, messages + 8 * k, 2));
-    RC(gm_transcript_challenge_fr(transcript, L("challenge"), 9, challenges.data() + 4 * k));
-    vm = challenges.data() + 4 * k;
-    k++;
-  }
-  int has = 0;
-  if (time) RC(gm_sc_final(time, final_foldings, final_foldings + 4, &has));
-  else RC(gm_sp_final(space, final_foldings, final_foldings + 4, &has));
-  if (!has) return GM_ESTATE;
-  RC(gm_transcript_append_fr(transcript, L("final-folding"), 13, final_foldings, 1));
-  RC(gm_transcript_append_fr(transcript, L("final-folding"), 13, final_foldings + 4, 1));
-  *rounds = k;
-  challenges.resize(k * 4);
-  return GM_OK;
-}
-
 
 inline Fr fr_pow(Fr base, size_t e) {
   Fr acc = Fr::one();

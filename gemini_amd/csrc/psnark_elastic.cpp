@@ -4,7 +4,8 @@
 //     stream MSMs -- `Reverse(powers_of_g)` + advance_by is the reversed / offset addressing of gm_ck_msm, a flush every
 //     max(max_msm_buffer [/ depth], min_device_chunk) pairs;
 //   * Sumcheck::{new_space, new_elastic} (sumcheck/proof.rs:133-154) and prove_batch (:69-122) over ElasticProvers: a SpaceProver
-//     that becomes a TimeProver once fewer than SPACE_TIME_THRESHOLD rounds remain (elastic_prover.rs:44-57);
+//     that becomes a TimeProver once fewer than SPACE_TIME_THRESHOLD rounds remain (elastic_prover.rs:44-57) -- the prover adapter
+//     and both round loops are those of sumcheck_driver.hpp;
 //   * EntryProduct::new_elastic_batch (entryproduct/elastic_prover.rs:66-127), the plookup streams (:227-232 of the prover) and the
 //     tensor check over FoldedPolynomialTrees (:384-600).
 // Same transcript, same bytes as gm_psnark_new_time (src/psnark/tests.rs:56-124 asserts time == elastic); the sequence is the one
@@ -18,193 +19,6 @@
 namespace {
 
 using namespace gmprover;
-
-// `impl Prover for ElasticProver` (sumcheck/elastic_prover.rs:20-95) with split-phase rounds for prove_batch
-struct ElasticSc {
-  uint64_t space = 0, time = 0;
-  bool allow_switch = true;  // false: Sumcheck::new_space, a SpaceProver to the end
-  // round in flight
-  bool pending_time = false, have_msg = false;
-  uint64_t a[4], b[4];
-  ElasticSc() = default;
-  ElasticSc(const ElasticSc&) = delete;
-  ElasticSc& operator=(const ElasticSc&) = delete;
-  ~ElasticSc() { reset(); }
-  void reset() {
-    if (time) (void)gm_sc_free(time);
-    if (space) (void)gm_sp_free(space);
-    time = space = 0;
-  }
-  int init(uint64_t f_stream, uint64_t g_stream, const uint64_t twist[4], bool elastic) {
-    allow_switch = elastic;
-    // no copy: the space prover reads the caller's streams until it is freed (every caller below keeps them that long)
-    return gm_sp_new_borrow(f_stream, g_stream, twist, &space);
-  }
-  // The RESIDENT schedule: the little-endian vectors behind the streams are in HBM anyway, so the prover is a time prover from
-  // its first round (it reads them in place until its first fold) instead of a space prover that re-derives every message from
-  // the whole streams until SPACE_TIME_THRESHOLD rounds remain.  The messages are the same field elements (sumcheck/tests.rs:42-87:
-  // space == time), and it needs LESS memory than the reversed stream copies a device-side space prover reads (0.75 of them).
-  int init_resident(uint64_t f_le, uint64_t g_le, const uint64_t twist[4]) {
-    allow_switch = true;
-    return gm_sc_new_borrow(f_le, g_le, twist, &time);
-  }
-  int rounds(size_t* tot) const { return time ? gm_sc_rounds(time, tot, nullptr) : gm_sp_rounds(space, tot, nullptr); }
-  // next_message(vm), first half: fold (switching to the time prover when it is time), launch the round
-  int begin(const uint64_t* vm, int* has) {
-    if (vm && !time) {
-      size_t tot = 0, rnd = 0;
-      RC(gm_sp_rounds(space, &tot, &rnd));
-      if (allow_switch && tot - rnd < SPACE_TIME_THRESHOLD) {
-        RC(gm_sp_to_time(space, &time));
-        RC(gm_sc_fold(time, vm));
-        (void)gm_sp_free(space);
-        space = 0;
-      } else {
-        RC(gm_sp_fold(space, vm));
-      }
-      vm = nullptr;
-    }
-    if (time) {
-      RC(gm_sc_round_begin(time, vm, has));
-      pending_time = *has != 0;
-      have_msg = false;
-    } else {
-      RC(gm_sp_round(space, nullptr, a, b, has));
-      pending_time = false;
-      have_msg = *has != 0;
-    }
-    return GM_OK;
-  }
-  // a prover that is a time prover already takes part in the ONE launch of its round (gm_sc_round_begin_many)
-  bool is_time() const { return time != 0; }
-  uint64_t time_handle() const { return time; }
-  void begun_as_time(int has) {
-    pending_time = has != 0;
-    have_msg = false;
-  }
-  int end(uint64_t out_a[4], uint64_t out_b[4]) {
-    if (pending_time) {
-      pending_time = false;
-      return gm_sc_round_end(time, out_a, out_b);
-    }
-    if (!have_msg) return GM_ESTATE;
-    memcpy(out_a, a, 32);
-    memcpy(out_b, b, 32);
-    have_msg = false;
-    return GM_OK;
-  }
-  int final(uint64_t f0[4], uint64_t g0[4], int* has) { return time ? gm_sc_final(time, f0, g0, has) : gm_sp_final(space, f0, g0, has); }
-};
-
-// Sumcheck::prove (proof.rs:36-66) over one ElasticSc
-int prove_one(uint64_t transcript, ElasticSc& S, uint64_t* messages, std::vector<uint64_t>& challenges, size_t cap_rounds, uint64_t final_foldings[8],
-              size_t* rounds) {
-  challenges.assign(cap_rounds * 4, 0);
-  size_t k = 0;
-  const uint64_t* vm = nullptr;
-  for (;;) {
-    int has = 0;
-    RC(S.begin(vm, &has));
-    if (!has) break;
-    if (k >= cap_rounds) return GM_EINVAL;
-    RC(S.end(messages + 8 * k, messages + 8 * k + 4));
-    RC(gm_transcript_append_fr(transcript, L("evaluations"), 11, messages + 8 * k, 2));
-    RC(gm_transcript_challenge_fr(transcript, L("challenge"), 9, challenges.data() + 4 * k));
-    vm = challenges.data() + 4 * k;
-    k++;
-  }
-  int has = 0;
-  RC(S.final(final_foldings, final_foldings + 4, &has));
-  if (!has) return GM_ESTATE;
-  RC(gm_transcript_append_fr(transcript, L("final-folding"), 13, final_foldings, 1));
-  RC(gm_transcript_append_fr(transcript, L("final-folding"), 13, final_foldings + 4, 1));
-  *rounds = k;
-  challenges.resize(k * 4);
-  return GM_OK;
-}
-
-// Sumcheck::prove_batch (proof.rs:69-122) over ElasticProvers: the round of every live prover is enqueued before the first wait
-int prove_batch(uint64_t transcript, std::vector<ElasticSc>& provers, uint64_t* messages, uint64_t* challenges, size_t cap_rounds, uint64_t* final_foldings,
-                size_t* rounds_out) {
-  const size_t k = provers.size();
-  size_t rounds = 0;
-  for (auto& p : provers) {
-    size_t t = 0;
-    RC(p.rounds(&t));
-    rounds = std::max(rounds, t);
-  }
-  rounds += 1;
-  if (rounds > cap_rounds) return GM_EINVAL;
-  std::vector<Fr> coeff(k), final_product(k);
-  for (size_t j = 0; j < k; j++) {
-    uint64_t c[4];
-    RC(gm_transcript_challenge_fr(transcript, L("batch-sumcheck"), 14, c));
-    coeff[j] = Fr::from_limbs(c);
-  }
-  std::vector<char> finished(k, 0), has(k, 0);
-  const uint64_t* vm = nullptr;
-  for (size_t r = 0; r < rounds; r++) {
-    Fr ma = Fr::zero(), mb = Fr::zero();
-    {
-      // the time provers among the live ones share one launch; a space prover (the literal schedule) steps on its own
-      std::vector<uint64_t> th;
-      std::vector<size_t> at;
-      for (size_t j = 0; j < k; j++) {
-        if (finished[j]) continue;
-        if (provers[j].is_time()) {
-          th.push_back(provers[j].time_handle());
-          at.push_back(j);
-          continue;
-        }
-        int h = 0;
-        RC(provers[j].begin(vm, &h));
-        has[j] = (char)h;
-      }
-      std::vector<int> hs(th.size(), 0);
-      RC(gm_sc_round_begin_many(th.data(), th.size(), vm, hs.data()));
-      for (size_t t = 0; t < th.size(); t++) {
-        provers[at[t]].begun_as_time(hs[t]);
-        has[at[t]] = (char)hs[t];
-      }
-    }
-    for (size_t j = 0; j < k; j++) {
-      Fr fa, fb;
-      if (!finished[j] && has[j]) {
-        uint64_t a[4], b[4];
-        RC(provers[j].end(a, b));
-        fa = Fr::from_limbs(a);
-        fb = Fr::from_limbs(b);
-      } else {
-        if (!finished[j]) {
-          uint64_t f0[4], g0[4];
-          int hf = 0;
-          RC(provers[j].final(f0, g0, &hf));
-          if (!hf) return GM_ESTATE;
-          final_product[j] = Fr::from_limbs(f0) * Fr::from_limbs(g0);
-          finished[j] = 1;
-        }
-        fa = final_product[j];
-        fb = Fr::zero();
-      }
-      ma = ma + fa * coeff[j];
-      mb = mb + fb * coeff[j];
-    }
-    ma.to_limbs(messages + 8 * r);
-    mb.to_limbs(messages + 8 * r + 4);
-    RC(gm_transcript_append_fr(transcript, L("evaluations"), 11, messages + 8 * r, 2));
-    RC(gm_transcript_challenge_fr(transcript, L("challenge"), 9, challenges + 4 * r));
-    vm = challenges + 4 * r;
-  }
-  for (size_t j = 0; j < k; j++) {
-    int hf = 0;
-    RC(provers[j].final(final_foldings + 8 * j, final_foldings + 8 * j + 4, &hf));
-    if (!hf) return GM_ESTATE;
-    RC(gm_transcript_append_fr(transcript, L("final-folding-lhs"), 17, final_foldings + 8 * j, 1));
-    RC(gm_transcript_append_fr(transcript, L("final-folding-rhs"), 17, final_foldings + 8 * j + 4, 1));
-  }
-  *rounds_out = rounds;
-  return GM_OK;
-}
 
 struct StreamKey {
   uint64_t ck;
@@ -307,7 +121,7 @@ extern "C" int gm_psnark_new_elastic(const gm_psnark_instance* I, uint64_t z_str
   } else {
     ElasticSc S1;
     RC(S1.init(za_stream, zb_stream, alpha, false));  // Sumcheck::new_space :97
-    RC(prove_one(T.h, S1, P->messages[0], ch1, cap_rounds, P->final_foldings[0], &P->rounds[0]));
+    RC(prove(T.h, S1, P->messages[0], ch1, cap_rounds, P->final_foldings[0], &P->rounds[0]));
   }
   P->spans[1] = since(t0);
 
@@ -373,7 +187,7 @@ extern "C" int gm_psnark_new_elastic(const gm_psnark_instance* I, uint64_t z_str
     RC(reversed(V, rhs, &rs));
     ElasticSc S2;
     RC(S2.init(zs, rs, one, true));  // Sumcheck::new_elastic :195
-    RC(prove_one(T.h, S2, P->messages[1], ch2, cap_rounds, P->final_foldings[1], &P->rounds[1]));
+    RC(prove(T.h, S2, P->messages[1], ch2, cap_rounds, P->final_foldings[1], &P->rounds[1]));
     S2.reset();
     V.release(zs);
     V.release(rs);
@@ -538,7 +352,7 @@ extern "C" int gm_psnark_new_elastic(const gm_psnark_instance* I, uint64_t z_str
   V.release(ep_r);
   t0 = Clock::now();
   std::vector<uint64_t> ch3(cap_rounds * 4, 0);
-  RC(prove_batch(T.h, provers, P->messages[2], ch3.data(), cap_rounds, &P->third_final_foldings[0][0], &P->rounds[2]));  // :380
+  RC(prove_batch(T.h, provers.data(), provers.size(), P->messages[2], ch3.data(), cap_rounds, &P->third_final_foldings[0][0], &P->rounds[2]));  // :380
   provers.clear();
   for (uint64_t v : batch_streams) V.release(v);
   P->spans[9] = since(t0);

@@ -8,7 +8,8 @@
 //                                    handle they are given is a cyclic share (gm_g1_bases_set_cyclic): MSMs sharded, field
 //                                    arithmetic replicated.
 //   * gm_sumcheck_prove_sharded      Sumcheck::prove (src/subprotocols/sumcheck/proof.rs:36-66) over contiguous blocks: per
-//                                    round 64 bytes all-gathered and added mod r; short tails gathered and finished replicated.
+//                                    round 64 bytes all-gathered and added mod r; short tails gathered and finished replicated
+//                                    (the round loop: sumcheck_blocks.hpp, shared with psnark_sharded.cpp).
 //   * gm_snark_new_time_sharded      snark::Proof::new_time (src/snark/time_prover.rs:19-117) with EVERY vector block-sharded
 //                                    (rank r holds elements [r m, (r + 1) m) of z_a, z_b, z_c, abc_tensored, the folding
 //                                    levels) and the key in per-level block slices; general sparse matrices (row blocks with
@@ -20,6 +21,7 @@
 
 #include "ctx.hpp"
 #include "prover_common.hpp"
+#include "sumcheck_blocks.hpp"
 
 namespace {
 
@@ -173,8 +175,9 @@ int gm_ck_msm_batch(uint64_t ck, const uint64_t* vecs, const size_t* ns, size_t 
 // ---- Sumcheck::prove over blocks ---------------------------------------------------------------------------------------
 // This rank holds elements [lo, lo + len) of f and g (global length n_global, lo even).  Rounds are shard-local while the blocks
 // stay longer than TAIL elements and pair-aligned: the rank's partial (a, b) -- 64 bytes -- is all-gathered and summed mod r.
-// Then the blocks are gathered once and every rank finishes the protocol on the whole (short) vectors.  Consumes nothing: f and
-// g are copied into the prover (Sumcheck::new_time copies too, proof.rs:125-130).
+// Then the blocks are gathered once and every rank finishes the protocol on the whole (short) vectors.  Consumes nothing: the
+// prover reads f and g in place until its first fold.  Here: the checks that every rank holds an equal block, in rank order; the
+// round loop itself is sumcheck_blocks (sumcheck_blocks.hpp) with one prover.
 int gm_sumcheck_prove_sharded(uint64_t transcript, uint64_t f_block, uint64_t g_block, const uint64_t twist[4], size_t lo, size_t n_global,
                               uint64_t* messages, uint64_t* challenges, size_t cap_rounds, uint64_t final_foldings[8], size_t* rounds_out) {
   GM_CTX();
@@ -203,81 +206,14 @@ int gm_sumcheck_prove_sharded(uint64_t transcript, uint64_t f_block, uint64_t g_
                  (unsigned long long)all[2 * (size_t)r2 + 1], nf0, n_global);
     }
   }
+  // the round loop is the sharded psnark's (sumcheck_blocks.hpp): ONE prover at level 0 of a layout of equal blocks
+  Sh lay;
+  lay.r = (size_t)rank;
+  lay.g = (size_t)world;
+  lay.M = n_global / (size_t)world;
   constexpr size_t TAIL = (size_t)1 << 10;
-  uint64_t prover = 0;
-  RC(gm_sc_new_borrow(f_block, g_block, twist, &prover));
-  struct Guard {
-    uint64_t& p;
-    ~Guard() {
-      if (p) (void)gm_sc_free(p);
-    }
-  } guard{prover};
-  RC(gm_sc_set_shard(prover, lo / 2));
-  bool replicated = world == 1;
-  size_t cur_n = n_global, k = 0;
-  const uint64_t* vm = nullptr;
-  for (;;) {
-    if (!replicated) {
-      const size_t per = cur_n / (size_t)world;
-      if (!(per > TAIL && per % 4 == 0)) {
-        // apply the pending fold shard-locally, then gather: the replicated prover starts exactly at a message boundary
-        if (vm) {
-          RC(gm_sc_fold(prover, vm));
-          cur_n = (cur_n + 1) / 2;
-          vm = nullptr;
-        }
-        size_t nf = 0, ng = 0;
-        uint64_t tw[4];
-        RC(gm_sc_lens(prover, &nf, &ng, tw));
-        GM_CHECK(nf == ng, GM_ESTATE, "sumcheck_prove_sharded: blocks of different lengths (%zu, %zu)", nf, ng);
-        std::vector<uint64_t> loc(8 * nf), all(8 * nf * (size_t)world);
-        RC(gm_sc_download(prover, loc.data(), loc.data() + 4 * nf));
-        RC(gm_dist_allgather_host(loc.data(), 64 * nf, all.data()));
-        std::vector<uint64_t> fs(4 * nf * (size_t)world), gs(4 * nf * (size_t)world);
-        for (size_t r = 0; r < (size_t)world; r++) {
-          memcpy(fs.data() + 4 * nf * r, all.data() + 8 * nf * r, 32 * nf);
-          memcpy(gs.data() + 4 * nf * r, all.data() + 8 * nf * r + 4 * nf, 32 * nf);
-        }
-        (void)gm_sc_free(prover);
-        prover = 0;
-        RC(gm_sc_new(fs.data(), nf * (size_t)world, gs.data(), nf * (size_t)world, tw, &prover));
-        replicated = true;
-      }
-    }
-    uint64_t a[4], b[4];
-    int has = 0;
-    RC(gm_sc_round(prover, vm, a, b, &has));
-    if (vm) cur_n = (cur_n + 1) / 2;
-    if (!has) break;
-    GM_CHECK(k < cap_rounds, GM_EINVAL, "sumcheck_prove_sharded: more than %zu rounds", cap_rounds);
-    if (!replicated) {
-      uint64_t mine[8];
-      memcpy(mine, a, 32);
-      memcpy(mine + 4, b, 32);
-      std::vector<uint64_t> all(8 * (size_t)world);
-      RC(gm_dist_allgather_host(mine, 64, all.data()));
-      Fr sa = Fr::zero(), sb = Fr::zero();
-      for (int r = 0; r < world; r++) {
-        sa = sa + Fr::from_limbs(all.data() + 8 * r);
-        sb = sb + Fr::from_limbs(all.data() + 8 * r + 4);
-      }
-      sa.to_limbs(a);
-      sb.to_limbs(b);
-    }
-    memcpy(messages + 8 * k, a, 32);
-    memcpy(messages + 8 * k + 4, b, 32);
-    RC(gm_transcript_append_fr(transcript, L("evaluations"), 11, messages + 8 * k, 2));
-    RC(gm_transcript_challenge_fr(transcript, L("challenge"), 9, challenges + 4 * k));
-    vm = challenges + 4 * k;
-    k++;
-  }
-  int has = 0;
-  RC(gm_sc_final(prover, final_foldings, final_foldings + 4, &has));
-  GM_CHECK(has, GM_ESTATE, "sumcheck_prove_sharded: final foldings unavailable");
-  RC(gm_transcript_append_fr(transcript, L("final-folding"), 13, final_foldings, 1));
-  RC(gm_transcript_append_fr(transcript, L("final-folding"), 13, final_foldings + 4, 1));
-  *rounds_out = k;
-  return GM_OK;
+  return sumcheck_blocks(lay, transcript, false, {ShProver{f_block, g_block, twist, n_global, 0}}, TAIL, messages, challenges, cap_rounds, final_foldings,
+                         rounds_out);
 }
 
 // ---- the block-sharded key -----------------------------------------------------------------------------------------------

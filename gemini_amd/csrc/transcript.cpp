@@ -21,12 +21,7 @@
 #include <unordered_map>
 #include <vector>
 
-#include "../../include/gemini_hip.h"
-#include "host_field.hpp"
-
-namespace gm {
-void set_error(const char* fmt, ...);
-}
+#include "sumcheck_driver.hpp"
 
 namespace {
 
@@ -296,126 +291,26 @@ int gm_transcript_challenge_fr(uint64_t handle, const uint8_t* label, size_t lle
   }
 }
 
-// Sumcheck::prove round loop (src/subprotocols/sumcheck/proof.rs:36-66) over a device prover:
-// message -> absorb b"evaluations" -> challenge b"challenge" -> next_message(Some(challenge)) ...
-// then the two b"final-folding" absorbs.  messages: rounds x 8 u64 (a || b), challenges: rounds x 4,
-// final_foldings: 8 u64.  *rounds_out = number of messages produced.
+// Sumcheck::prove (src/subprotocols/sumcheck/proof.rs:36-66) over a device prover the caller keeps: the round loop is
+// gmprover::prove (sumcheck_driver.hpp).  messages: rounds x 8 u64 (a || b), challenges: rounds x 4, final_foldings: 8 u64.
+// *rounds_out = number of messages produced.
 int gm_sumcheck_prove(uint64_t transcript, uint64_t prover, uint64_t* messages, uint64_t* challenges, size_t cap_rounds,
                       uint64_t final_foldings[8], size_t* rounds_out) {
   T_CHECK(messages && challenges && final_foldings && rounds_out, GM_EINVAL, "sumcheck_prove: null pointer");
-  size_t k = 0;
-  const uint64_t* vm = nullptr;
-  for (;;) {
-    uint64_t a[4], b[4];
-    int has = 0;
-    int rc = gm_sc_round(prover, vm, a, b, &has);
-    if (rc) return rc;
-    if (!has) break;
-    T_CHECK(k < cap_rounds, GM_EINVAL, "sumcheck_prove: more than %zu rounds", cap_rounds);
-    memcpy(messages + 8 * k, a, 32);
-    memcpy(messages + 8 * k + 4, b, 32);
-    if ((rc = gm_transcript_append_fr(transcript, (const uint8_t*)"evaluations", 11, messages + 8 * k, 2))) return rc;
-    if ((rc = gm_transcript_challenge_fr(transcript, (const uint8_t*)"challenge", 9, challenges + 4 * k))) return rc;
-    vm = challenges + 4 * k;
-    k++;
-  }
-  int has = 0;
-  int rc = gm_sc_final(prover, final_foldings, final_foldings + 4, &has);
-  if (rc) return rc;
-  T_CHECK(has, GM_ESTATE, "sumcheck_prove: final foldings unavailable");
-  if ((rc = gm_transcript_append_fr(transcript, (const uint8_t*)"final-folding", 13, final_foldings, 1))) return rc;
-  if ((rc = gm_transcript_append_fr(transcript, (const uint8_t*)"final-folding", 13, final_foldings + 4, 1))) return rc;
-  *rounds_out = k;
-  return GM_OK;
+  gmprover::ElasticSc S;
+  S.borrow(prover);
+  return gmprover::prove(transcript, S, messages, challenges, cap_rounds, final_foldings, rounds_out);
 }
 
-// Sumcheck::prove_batch (src/subprotocols/sumcheck/proof.rs:69-122): k provers of possibly different
-// lengths run in lock-step for max(rounds) + 1 rounds; coefficients c_j are drawn first
-// (b"batch-sumcheck"); a prover that has run out contributes (f0 * g0, 0); the round message is
-// sum_j c_j * m_j.  The reference maps provers over rayon (:85); here the rounds of all live provers
-// are ONE kernel launch (k_sc_round_multi).  messages: cap_rounds x 8, challenges: cap_rounds x 4,
-// final_foldings: k x 8 (lhs || rhs per prover).
+// Sumcheck::prove_batch (src/subprotocols/sumcheck/proof.rs:69-122) over k device provers the caller keeps: the round loop is
+// gmprover::prove_batch (sumcheck_driver.hpp), the rounds of all live provers ONE kernel launch (k_sc_round_multi).
+// messages: cap_rounds x 8, challenges: cap_rounds x 4, final_foldings: k x 8 (lhs || rhs per prover).
 int gm_sumcheck_prove_batch(uint64_t transcript, const uint64_t* provers, size_t k, uint64_t* messages, uint64_t* challenges,
                             size_t cap_rounds, uint64_t* final_foldings, size_t* rounds_out) {
   T_CHECK(provers && messages && challenges && final_foldings && rounds_out && k >= 1, GM_EINVAL, "sumcheck_prove_batch: bad arguments");
-  size_t rounds = 0;
-  for (size_t j = 0; j < k; j++) {
-    size_t t = 0;
-    int rc = gm_sc_rounds(provers[j], &t, nullptr);
-    if (rc) return rc;
-    if (t > rounds) rounds = t;
-  }
-  rounds += 1;  // "+1 to get the final foldings"
-  T_CHECK(rounds <= cap_rounds, GM_EINVAL, "sumcheck_prove_batch: %zu rounds exceed capacity %zu", rounds, cap_rounds);
-  std::vector<gmh::Fr> coeff(k);
-  for (size_t j = 0; j < k; j++) {
-    uint64_t c[4];
-    int rc = gm_transcript_challenge_fr(transcript, (const uint8_t*)"batch-sumcheck", 14, c);
-    if (rc) return rc;
-    coeff[j] = gmh::Fr::from_limbs(c);
-  }
-  const uint64_t* vm = nullptr;
-  // a prover that has run out contributes (f0 * g0, 0) in every later round: read its final foldings once
-  std::vector<char> finished(k, 0), has(k, 0);
-  std::vector<gmh::Fr> final_product(k);
-  for (size_t r = 0; r < rounds; r++) {
-    gmh::Fr ma = gmh::Fr::zero(), mb = gmh::Fr::zero();
-    // the round of every live prover is enqueued before the first wait (the reference runs them on rayon threads, :85)
-    {
-      // ONE launch for the live provers of the round (gm_sc_round_begin_many)
-      std::vector<uint64_t> live;
-      std::vector<size_t> at;
-      for (size_t j = 0; j < k; j++)
-        if (!finished[j]) {
-          live.push_back(provers[j]);
-          at.push_back(j);
-        }
-      std::vector<int> hs(live.size(), 0);
-      int rc = gm_sc_round_begin_many(live.data(), live.size(), vm, hs.data());
-      if (rc) return rc;
-      for (size_t t = 0; t < live.size(); t++) has[at[t]] = (char)hs[t];
-    }
-    for (size_t j = 0; j < k; j++) {
-      gmh::Fr fa, fb;
-      if (!finished[j] && has[j]) {
-        uint64_t a[4], b[4];
-        int rc = gm_sc_round_end(provers[j], a, b);
-        if (rc) return rc;
-        fa = gmh::Fr::from_limbs(a);
-        fb = gmh::Fr::from_limbs(b);
-      } else {
-        if (!finished[j]) {
-          uint64_t f0[4], g0[4];
-          int hf = 0;
-          int rc = gm_sc_final(provers[j], f0, g0, &hf);
-          if (rc) return rc;
-          T_CHECK(hf, GM_ESTATE, "If next_message is None, we expect final foldings to be available");
-          final_product[j] = gmh::Fr::from_limbs(f0) * gmh::Fr::from_limbs(g0);
-          finished[j] = 1;
-        }
-        fa = final_product[j];
-        fb = gmh::Fr::zero();
-      }
-      ma = ma + fa * coeff[j];
-      mb = mb + fb * coeff[j];
-    }
-    ma.to_limbs(messages + 8 * r);
-    mb.to_limbs(messages + 8 * r + 4);
-    int rc = gm_transcript_append_fr(transcript, (const uint8_t*)"evaluations", 11, messages + 8 * r, 2);
-    if (rc) return rc;
-    if ((rc = gm_transcript_challenge_fr(transcript, (const uint8_t*)"challenge", 9, challenges + 4 * r))) return rc;
-    vm = challenges + 4 * r;
-  }
-  for (size_t j = 0; j < k; j++) {
-    int has = 0;
-    int rc = gm_sc_final(provers[j], final_foldings + 8 * j, final_foldings + 8 * j + 4, &has);
-    if (rc) return rc;
-    T_CHECK(has, GM_ESTATE, "sumcheck_prove_batch: final foldings unavailable for prover %zu", j);
-    if ((rc = gm_transcript_append_fr(transcript, (const uint8_t*)"final-folding-lhs", 17, final_foldings + 8 * j, 1))) return rc;
-    if ((rc = gm_transcript_append_fr(transcript, (const uint8_t*)"final-folding-rhs", 17, final_foldings + 8 * j + 4, 1))) return rc;
-  }
-  *rounds_out = rounds;
-  return GM_OK;
+  std::vector<gmprover::ElasticSc> S(k);
+  for (size_t j = 0; j < k; j++) S[j].borrow(provers[j]);
+  return gmprover::prove_batch(transcript, S.data(), k, messages, challenges, cap_rounds, final_foldings, rounds_out);
 }
 
 }  // extern "C"

@@ -1,6 +1,8 @@
 """Host mirror of src/subprotocols/sumcheck: `trait Prover` (prover.rs:30-45), `TimeProver`
 (time_prover.rs:42-137) and the `Sumcheck::prove` round loop (proof.rs:36-66).  Each
-next_message is one fused fold+message kernel launch in libgemini_hip.so."""
+next_message is one fused fold+message kernel launch in libgemini_hip.so.  The loops here serve herring and Python-level
+provers; the native ones (gm_sumcheck_prove / _prove_batch and the provers compiled into the library) are stated once in
+csrc/sumcheck_driver.hpp."""
 from __future__ import annotations
 
 import ctypes as C
@@ -220,7 +222,7 @@ class Sumcheck:
 
     @staticmethod
     def prove_native(transcript, prover: "TimeProver") -> "Sumcheck":
-        """the same round loop run inside the library (gm_sumcheck_prove): no Python per round"""
+        """the same round loop run inside the library (gm_sumcheck_prove, csrc/sumcheck_driver.hpp): no Python per round"""
         cap = prover.rounds() + 1
         msgs = np.zeros((cap, 8), dtype=np.uint64)
         chs = np.zeros((cap, 4), dtype=np.uint64)
@@ -252,7 +254,7 @@ class Sumcheck:
 
     @staticmethod
     def prove_batch(transcript, provers) -> "Sumcheck":
-        """proof.rs:69-122 (run inside the library: gm_sumcheck_prove_batch)"""
+        """proof.rs:69-122 (run inside the library: gm_sumcheck_prove_batch, csrc/sumcheck_driver.hpp)"""
         k = len(provers)
         cap = max(p.rounds() for p in provers) + 1
         msgs = np.zeros((cap, 8), dtype=np.uint64)
