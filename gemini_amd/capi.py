@@ -25,7 +25,7 @@ SYMBOLS = [
     "gm_g1_msm_h", "gm_g1_msm_v", "gm_g1_msm_v_batch", "gm_g1_msm_v_batch_partial", "gm_g1_msm_v_batch_at", "gm_g1_msm_d", "gm_g1_msm_d_partial", "gm_g1_sum",
     "gm_g1_msm_stream_new", "gm_g1_msm_stream_new_h", "gm_g1_msm_stream_add", "gm_g1_msm_stream_finalize", "gm_g1_msm_stream_free", "gm_host_alloc", "gm_host_free",
     "gm_g1_fixed_base_register", "gm_g1_srs_register", "gm_g1_srs_register_segments", "gm_set_msm_window", "gm_set_msm_table_min", "gm_set_msm_affine_levels", "gm_set_msm_split", "gm_set_msm_glv", "gm_prof_enable", "gm_prof_read", "gm_prof_read_clock",
-    "gm_idx_register", "gm_idx_free", "gm_fr_gather", "gm_fr_alg_hash", "gm_fr_plookup_set", "gm_fr_add_scalar", "gm_fr_shift_monic",
+    "gm_idx_register", "gm_idx_free", "gm_idx_len", "gm_idx_download", "gm_idx_extend_frequency", "gm_fr_gather", "gm_fr_alg_hash", "gm_fr_plookup_set", "gm_fr_add_scalar", "gm_fr_shift_monic",
     "gm_fr_acc_product", "gm_fr_tensor_range", "gm_fr_tensor_gather", "gm_fr_powers_gather", "gm_fr_alg_hash_from", "gm_fr_powers_range", "gm_fr_plookup_set_block", "gm_fr_shift_block", "gm_fr_product", "gm_fr_acc_product_block",
     "gm_sc_set_shard_rounds", "gm_sc_round_begin_many", "gm_psnark_shard_block", "gm_psnark_shard_level", "gm_psnark_shard_footprint", "gm_psnark_shard_key_new", "gm_psnark_index_sharded", "gm_psnark_new_time_sharded", "gm_snark_new_elastic_sharded",
     "gm_fr_vec_alloc", "gm_fr_vec_free", "gm_fr_vec_len", "gm_fr_vec_upload", "gm_fr_vec_download",
@@ -43,6 +43,7 @@ SYMBOLS = [
     "gm_dist_allgather_vec", "gm_dist_stats", "gm_dist_selftest", "gm_dist_allgather_host_class", "gm_dist_stats_routes", "gm_dist_bench", "gm_dist_reblock_vecs",
     "gm_g1_bases_set_cyclic", "gm_g1_srs_register_cyclic", "gm_ck_len", "gm_ck_msm", "gm_ck_msm_batch", "gm_sumcheck_prove_sharded",
     "gm_snark_shard_key_new", "gm_snark_new_time_sharded",
+    "gm_tensorcheck_new_time", "gm_entryproduct_new_time_batch", "gm_plookup_new_time",
 ]
 
 

@@ -300,6 +300,7 @@ int fr_reverse(Context* C, FrVec* in, FrVec* out);
 int spm_mul(Context* C, SparseMatrix* M, FrVec* x, FrVec* y);
 int fr_div_linear_factors(Context* C, FrVec* f, const uint64_t* points, size_t k, FrVec* q, uint64_t* rem_out);
 int fr_gather(Context* C, FrVec* src, const IdxVec* index, FrVec* out);
+int idx_extend_frequency(Context* C, const IdxVec* index, size_t set_len, IdxVec* out);
 int fr_alg_hash(Context* C, FrVec* v, const IdxVec* index, const uint64_t zeta[4], FrVec* out, uint64_t base = 0);
 int fr_tensor_gather(Context* C, const uint64_t* rhos, size_t k, const IdxVec* index, FrVec* out);
 int fr_powers_gather(Context* C, const uint64_t x[4], size_t k, const IdxVec* index, FrVec* out);
@@ -1358,7 +1359,8 @@ int gm_idx_free(uint64_t handle) {
     I = std::move(it->second);
     C->indices.erase(it);
   }
-  if (I->d) (void)gm::raw_free(I->d);
+  if (I->d && I->pool_cap) C->pool.free(I->d, I->pool_cap);
+  else if (I->d) (void)gm::raw_free(I->d);
   return GM_OK;
 }
 #define GM_IDX(var, h, who)                                                                             \
@@ -1369,6 +1371,37 @@ int gm_idx_free(uint64_t handle) {
     GM_CHECK(it != C->indices.end(), GM_EHANDLE, who ": unknown index handle %llu", (unsigned long long)(h)); \
     var = it->second.get();                                                                             \
   }
+int gm_idx_len(uint64_t handle, size_t* n) {
+  GM_CTX();
+  GM_CHECK(n != nullptr, GM_EINVAL, "idx_len: null pointer");
+  GM_IDX(ix, handle, "idx_len");
+  *n = ix->n;
+  return GM_OK;
+}
+int gm_idx_download(uint64_t handle, uint32_t* out) {
+  GM_CTX();
+  GM_IDX(ix, handle, "idx_download");
+  GM_CHECK(out != nullptr || ix->n == 0, GM_EINVAL, "idx_download: null pointer");
+  if (ix->n) {
+    GM_FR_LOCK(C);
+    GM_HIP(hipMemcpyAsync(out, ix->d, ix->n * 4, hipMemcpyDeviceToHost, C->stream));
+    GM_HIP(hipStreamSynchronize(C->stream));
+  }
+  return GM_OK;
+}
+int gm_idx_extend_frequency(uint64_t index, size_t set_len, uint64_t* ext, size_t* ext_len) {
+  GM_CTX();
+  GM_CHECK(ext != nullptr && ext_len != nullptr, GM_EINVAL, "idx_extend_frequency: null pointer");
+  GM_IDX(ix, index, "idx_extend_frequency");
+  auto E = std::make_unique<IdxVec>();
+  int rc = idx_extend_frequency(C, ix, set_len, E.get());
+  if (rc) return rc;  // nothing registered
+  *ext_len = E->n;
+  std::lock_guard<std::mutex> lk(C->mu);
+  *ext = C->next_handle++;
+  C->indices[*ext] = std::move(E);
+  return GM_OK;
+}
 int gm_fr_gather(uint64_t src, uint64_t index, uint64_t out) {
   GM_CTX();
   GM_VEC(vs, src, "fr_gather");

@@ -95,6 +95,7 @@ struct IdxVec {
   uint32_t* d = nullptr;
   size_t n = 0;
   size_t max_plus_1 = 0;  // 1 + the largest index (0 for an empty vector)
+  size_t pool_cap = 0;    // != 0: d is a block of the vector pool (gm_idx_extend_frequency builds its result on the device)
 };
 
 struct Sumcheck {
@@ -214,7 +215,7 @@ struct MsmWorkspace {
 };
 
 // per-stage kernel timing with HIP events on the library's own stream (bench.py's roofline leg)
-enum ProfStage { PROF_DIGITS = 0, PROF_SCAN, PROF_SCATTER, PROF_ACC0, PROF_MERGE, PROF_REDUCE, PROF_SC_ROUND, PROF_NSTAGES };
+enum ProfStage { PROF_DIGITS = 0, PROF_SCAN, PROF_SCATTER, PROF_ACC0, PROF_MERGE, PROF_REDUCE, PROF_SC_ROUND, PROF_EXTFREQ, PROF_NSTAGES };
 struct Profiler {
   bool on = false;
   int only_stage = -1;  // >= 0: events around that stage only (gm_prof_enable(2): the accumulation; every event record is a ~10 us bubble)

@@ -596,6 +596,211 @@ __global__ __launch_bounds__(256) void k_accp_phase3(const uint8_t* __restrict__
   }
 }
 
+// extend_frequency(compute_frequency(set_len, index)) (plookup/time_prover.rs:65-78): the non-decreasing sequence in which every
+// v < set_len appears 1 + #{j : index[j] = v} times.  Three stages, the blocked scan in the style of the accumulated product above:
+//   count:  cnt[v] (starting at 1) += its occurrences -- 32-bit integer atomics, so any order gives the same bits.  Every entry is range-checked
+//           BEFORE it is used as an address; an entry >= set_len raises *bad and is skipped.  A thread merges the equal neighbours of
+//           its EXF_ITEMS consecutive entries and a wave whose lanes all ended on the same value adds once, so a sorted or constant index
+//           does not queue on one address; when the counters fit in LDS a workgroup counts there first and flushes once.
+//   scan:   exclusive scan of cnt, in place (tile sums, one workgroup over the tile sums, tiles again with their carry)
+//   expand: a workgroup finds the values its tile of the output starts and ends in (two binary searches over the offsets), marks where
+//           each value in between starts -- counts are >= 1, so the offsets are strictly increasing and a tile of T outputs starts at
+//           most T - 1 new values -- and out = first value + inclusive scan of the marks.
+constexpr unsigned EXF_ITEMS = 16;          // index entries / counters of one thread: four 16-byte loads
+constexpr unsigned EXF_LDS_BINS = 16384;    // 64 KiB of counters privatised per workgroup
+constexpr unsigned EXF_SCAN_TILE = 256 * EXF_ITEMS;
+constexpr unsigned EXF_OUT_ITEMS = 8;       // outputs of one thread: two 16-byte stores
+constexpr unsigned EXF_OUT_TILE = 256 * EXF_OUT_ITEMS;
+
+// exclusive scan of one value per thread over a 256-thread workgroup (wave64 shuffles + 4 wave sums in LDS); *total = the sum
+__device__ __forceinline__ uint32_t exf_block_exscan(uint32_t x, uint32_t* wsum, uint32_t* total) {
+  const unsigned lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  uint32_t inc = x;
+#pragma unroll
+  for (unsigned d = 1; d < 64; d <<= 1) {
+    const uint32_t y = __shfl_up(inc, d, 64);
+    if (lane >= d) inc += y;
+  }
+  if (lane == 63) wsum[w] = inc;
+  __syncthreads();
+  uint32_t off = 0, tot = 0;
+#pragma unroll
+  for (unsigned i = 0; i < 4; i++) {
+    const uint32_t s = wsum[i];
+    off += i < w ? s : 0;
+    tot += s;
+  }
+  __syncthreads();  // wsum may be written again
+  *total = tot;
+  return off + inc - x;
+}
+// EXF_ITEMS consecutive words from `p + lo` (lo a multiple of EXF_ITEMS, p 64-byte aligned), `fill` past the end
+__device__ __forceinline__ void exf_load_items(const uint32_t* __restrict__ p, size_t lo, size_t n, uint32_t fill, uint32_t (&x)[EXF_ITEMS]) {
+  if (lo + EXF_ITEMS <= n) {
+    const uint4* q = reinterpret_cast<const uint4*>(p + lo);
+#pragma unroll
+    for (unsigned i = 0; i < EXF_ITEMS / 4; i++) {
+      const uint4 t = q[i];
+      x[4 * i] = t.x;
+      x[4 * i + 1] = t.y;
+      x[4 * i + 2] = t.z;
+      x[4 * i + 3] = t.w;
+    }
+  } else {
+#pragma unroll
+    for (unsigned i = 0; i < EXF_ITEMS; i++) x[i] = lo + i < n ? p[lo + i] : fill;
+  }
+}
+template <bool PRIVATE>
+__global__ __launch_bounds__(256) void k_exf_count(const uint32_t* __restrict__ index, size_t k, uint32_t set_len, uint32_t* __restrict__ cnt,
+                                                   uint32_t* __restrict__ bad) {
+  __shared__ uint32_t bins[PRIVATE ? EXF_LDS_BINS : 1];
+  if (PRIVATE) {
+    for (unsigned i = threadIdx.x; i < set_len; i += 256) bins[i] = 0;
+    __syncthreads();
+  }
+  uint32_t* const tgt = PRIVATE ? bins : cnt;
+  const size_t chunk = (size_t)256 * EXF_ITEMS;
+  for (size_t base = (size_t)blockIdx.x * chunk; base < k; base += (size_t)gridDim.x * chunk) {  // uniform over the workgroup
+    const size_t lo = base + (size_t)threadIdx.x * EXF_ITEMS;
+    uint32_t x[EXF_ITEMS];
+    exf_load_items(index, lo, k, 0xffffffffu, x);  // the filler fails the range check below ...
+    uint32_t run_v = 0xffffffffu, run_c = 0;
+#pragma unroll
+    for (unsigned i = 0; i < EXF_ITEMS; i++) {
+      const uint32_t v = x[i];
+      if (v >= set_len) {
+        if (lo + i < k) *bad = 1;  // ... but only a real entry is an error
+        continue;
+      }
+      if (v == run_v) {
+        run_c++;
+      } else {
+        if (run_c) atomicAdd(&tgt[run_v], run_c);
+        run_v = v;
+        run_c = 1;
+      }
+    }
+    // the last run of every lane: one add for the wave when all 64 ended on the same value (a lane without a valid entry keeps
+    // run_v = 2^32 - 1 and run_c = 0, so a sum s > 0 means the common value is a valid one)
+    const uint32_t v0 = __shfl(run_v, 0, 64);
+    if (__all(run_v == v0)) {
+      uint32_t s = run_c;
+#pragma unroll
+      for (unsigned d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
+      if ((threadIdx.x & 63) == 0 && s) atomicAdd(&tgt[v0], s);
+    } else if (run_c) {
+      atomicAdd(&tgt[run_v], run_c);
+    }
+  }
+  if (PRIVATE) {
+    __syncthreads();
+    for (unsigned i = threadIdx.x; i < set_len; i += 256) {
+      const uint32_t c = bins[i];
+      if (c) atomicAdd(&cnt[i], c);
+    }
+  }
+}
+// sums[t] = the sum of tile t of cnt
+__global__ __launch_bounds__(256) void k_exf_tile_sums(const uint32_t* __restrict__ cnt, size_t n, uint32_t* __restrict__ sums) {
+  __shared__ uint32_t wsum[4];
+  uint32_t x[EXF_ITEMS];
+  exf_load_items(cnt, (size_t)blockIdx.x * EXF_SCAN_TILE + (size_t)threadIdx.x * EXF_ITEMS, n, 0, x);
+  uint32_t s = 0, total;
+#pragma unroll
+  for (unsigned i = 0; i < EXF_ITEMS; i++) s += x[i];
+  (void)exf_block_exscan(s, wsum, &total);
+  if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+// exclusive scan of the tile sums, in place: ONE workgroup, 256 at a time with a running carry
+__global__ __launch_bounds__(256) void k_exf_scan_sums(uint32_t* __restrict__ sums, size_t ntiles) {
+  __shared__ uint32_t wsum[4];
+  uint32_t carry = 0;
+  for (size_t base = 0; base < ntiles; base += 256) {
+    const size_t i = base + threadIdx.x;
+    const uint32_t x = i < ntiles ? sums[i] : 0;
+    uint32_t total;
+    const uint32_t ex = exf_block_exscan(x, wsum, &total);
+    if (i < ntiles) sums[i] = carry + ex;
+    carry += total;
+  }
+}
+// cnt -> its exclusive scan, in place: a thread reads its EXF_ITEMS counters, then writes their offsets
+__global__ __launch_bounds__(256) void k_exf_scan_tiles(uint32_t* __restrict__ cnt, size_t n, const uint32_t* __restrict__ sums) {
+  __shared__ uint32_t wsum[4];
+  const size_t lo = (size_t)blockIdx.x * EXF_SCAN_TILE + (size_t)threadIdx.x * EXF_ITEMS;
+  uint32_t x[EXF_ITEMS];
+  exf_load_items(cnt, lo, n, 0, x);
+  uint32_t s = 0, total;
+#pragma unroll
+  for (unsigned i = 0; i < EXF_ITEMS; i++) {
+    const uint32_t c = x[i];
+    x[i] = s;
+    s += c;
+  }
+  const uint32_t off = sums[blockIdx.x] + exf_block_exscan(s, wsum, &total);
+  if (lo + EXF_ITEMS <= n) {
+    uint4* q = reinterpret_cast<uint4*>(cnt + lo);
+#pragma unroll
+    for (unsigned i = 0; i < EXF_ITEMS / 4; i++) q[i] = make_uint4(off + x[4 * i], off + x[4 * i + 1], off + x[4 * i + 2], off + x[4 * i + 3]);
+  } else {
+#pragma unroll
+    for (unsigned i = 0; i < EXF_ITEMS; i++)
+      if (lo + i < n) cnt[lo + i] = off + x[i];
+  }
+}
+// out[j] = the largest v < set_len with off[v] <= j, j < ext_len (off[0] = 0, off strictly increasing, set_len >= 1)
+__global__ __launch_bounds__(256) void k_exf_expand(const uint32_t* __restrict__ off, uint32_t set_len, size_t ext_len, uint32_t* __restrict__ out) {
+  __shared__ __attribute__((aligned(16))) uint32_t mark[EXF_OUT_TILE];
+  __shared__ uint32_t wsum[4];
+  __shared__ uint32_t vrange[2];
+  for (size_t t0 = (size_t)blockIdx.x * EXF_OUT_TILE; t0 < ext_len; t0 += (size_t)gridDim.x * EXF_OUT_TILE) {  // uniform over the workgroup
+    const size_t t1 = min(t0 + (size_t)EXF_OUT_TILE, ext_len);
+    for (unsigned i = threadIdx.x; i < EXF_OUT_TILE; i += 256) mark[i] = 0;
+    if (threadIdx.x < 2) {
+      const size_t j = threadIdx.x == 0 ? t0 : t1 - 1;
+      uint32_t lo = 0, hi = set_len;  // off[lo] <= j < off[hi] (off[set_len] = infinity)
+      while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if ((size_t)off[mid] <= j) lo = mid;
+        else hi = mid;
+      }
+      vrange[threadIdx.x] = lo;
+    }
+    __syncthreads();
+    const uint32_t v_lo = vrange[0], v_hi = vrange[1];
+    // t0 < off[v] <= t1 - 1 for v_lo < v <= v_hi: inside the tile, and all different
+    for (size_t v = (size_t)v_lo + 1 + threadIdx.x; v <= v_hi; v += 256) {
+      const size_t p = (size_t)off[v] - t0;
+      if (p < EXF_OUT_TILE) mark[p] = 1;
+    }
+    __syncthreads();
+    uint32_t m[EXF_OUT_ITEMS];
+    {
+      const uint4* q = reinterpret_cast<const uint4*>(mark + threadIdx.x * EXF_OUT_ITEMS);
+      const uint4 a = q[0], b = q[1];
+      m[0] = a.x, m[1] = a.y, m[2] = a.z, m[3] = a.w, m[4] = b.x, m[5] = b.y, m[6] = b.z, m[7] = b.w;
+    }
+    uint32_t s = 0, total;
+#pragma unroll
+    for (unsigned i = 0; i < EXF_OUT_ITEMS; i++) {
+      s += m[i];
+      m[i] = s;  // inclusive
+    }
+    const uint32_t base = v_lo + exf_block_exscan(s, wsum, &total);  // (its two barriers also fence `mark` and `vrange` for the next tile)
+    const size_t lo = t0 + (size_t)threadIdx.x * EXF_OUT_ITEMS;
+    if (lo + EXF_OUT_ITEMS <= t1) {
+      uint4* q = reinterpret_cast<uint4*>(out + lo);
+      q[0] = make_uint4(base + m[0], base + m[1], base + m[2], base + m[3]);
+      q[1] = make_uint4(base + m[4], base + m[5], base + m[6], base + m[7]);
+    } else {
+#pragma unroll
+      for (unsigned i = 0; i < EXF_OUT_ITEMS; i++)
+        if (lo + i < t1) out[lo + i] = base + m[i];
+    }
+  }
+}
+
 // y[i] = sum_k vals[k] * x[cols[k]] over row i of a CSR matrix       src/misc.rs:100-110
 // (product_matrix_vector; the reference skips the multiplication when the coefficient is one,
 // which cannot change the value)
@@ -1892,6 +2097,74 @@ int fr_gather(Context* C, FrVec* src, const IdxVec* index, FrVec* out) {
   GM_HIP(hipStreamSynchronize(C->stream));
   out->len = index->n;
   return GM_OK;
+}
+
+// extend_frequency(compute_frequency(set_len, index)) into `out` (k_exf_*): everything on the context's stream, the one wait is for the
+// range-check flag at the end.  out->d and the workspace (counters / offsets, tile sums, flag) are blocks of the vector pool.
+int idx_extend_frequency(Context* C, const IdxVec* index, size_t set_len, IdxVec* out) {
+  GM_FR_LOCK(C);
+  const size_t k = index->n;
+  GM_CHECK(set_len <= 0xffffffffull && k <= 0xffffffffull - set_len, GM_EINVAL, "extend_frequency: %zu + %zu entries do not fit a 32-bit index vector",
+           set_len, k);
+  GM_CHECK(set_len > 0 || k == 0, GM_EINVAL, "extend_frequency: %zu index entries into an empty set", k);
+  const size_t ext_len = set_len + k;
+  out->n = ext_len;
+  out->max_plus_1 = ext_len ? set_len : 0;
+  if (ext_len == 0) return GM_OK;
+  const size_t ntiles = (set_len + EXF_SCAN_TILE - 1) / EXF_SCAN_TILE, cnt_words = ntiles * EXF_SCAN_TILE;
+  void* ws = nullptr;
+  size_t ws_cap = 0;
+  int rc = C->pool.alloc((cnt_words + ntiles + 1) * 4, &ws, &ws_cap);
+  if (rc) return rc;
+  if ((rc = C->pool.alloc(ext_len * 4, (void**)&out->d, &out->pool_cap))) {
+    C->pool.free(ws, ws_cap);
+    return rc;
+  }
+  uint32_t* cnt = static_cast<uint32_t*>(ws);
+  uint32_t* sums = cnt + cnt_words;
+  uint32_t* bad = sums + ntiles;
+  uint32_t* host_bad = reinterpret_cast<uint32_t*>(C->host_small);
+  auto enqueue = [&]() -> int {
+    C->prof.begin(PROF_EXTFREQ, C->stream);
+    GM_HIP(hipMemsetD32Async((hipDeviceptr_t)cnt, 1, set_len, C->stream));
+    GM_HIP(hipMemsetAsync(bad, 0, 4, C->stream));
+    if (k) {
+      const size_t chunks = (k + (size_t)256 * EXF_ITEMS - 1) / ((size_t)256 * EXF_ITEMS);
+      if (set_len <= EXF_LDS_BINS) {
+        // a workgroup flushes up to set_len counters: give it at least four times as many entries to count
+        size_t blocks = k / std::max((size_t)256 * EXF_ITEMS, 4 * set_len);
+        blocks = std::min(std::max(blocks, (size_t)1), std::min(chunks, (size_t)1024));
+        hipLaunchKernelGGL(k_exf_count<true>, dim3((unsigned)blocks), dim3(256), 0, C->stream, index->d, k, (uint32_t)set_len, cnt, bad);
+      } else {
+        hipLaunchKernelGGL(k_exf_count<false>, dim3((unsigned)std::min(chunks, (size_t)2048)), dim3(256), 0, C->stream, index->d, k, (uint32_t)set_len, cnt,
+                           bad);
+      }
+    }
+    hipLaunchKernelGGL(k_exf_tile_sums, dim3((unsigned)ntiles), dim3(256), 0, C->stream, cnt, set_len, sums);
+    hipLaunchKernelGGL(k_exf_scan_sums, dim3(1), dim3(256), 0, C->stream, sums, ntiles);
+    hipLaunchKernelGGL(k_exf_scan_tiles, dim3((unsigned)ntiles), dim3(256), 0, C->stream, cnt, set_len, sums);
+    const size_t out_tiles = (ext_len + EXF_OUT_TILE - 1) / EXF_OUT_TILE;
+    hipLaunchKernelGGL(k_exf_expand, dim3((unsigned)std::min(out_tiles, (size_t)1 << 16)), dim3(256), 0, C->stream, cnt, (uint32_t)set_len, ext_len, out->d);
+    GM_HIP(hipGetLastError());
+    C->prof.end(PROF_EXTFREQ, C->stream);
+    GM_HIP(hipMemcpyAsync(host_bad, bad, 4, hipMemcpyDeviceToHost, C->stream));
+    return GM_OK;
+  };
+  rc = enqueue();
+  const hipError_t e = hipStreamSynchronize(C->stream);  // on every path: the blocks go back to the pool only once nothing reads them
+  if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize", __FILE__, __LINE__);
+  if (!rc) C->prof.collect();
+  if (!rc && *host_bad) {
+    set_error("extend_frequency: an index entry is outside the set of %zu elements", set_len);
+    rc = GM_EINVAL;
+  }
+  C->pool.free(ws, ws_cap);
+  if (rc) {
+    C->pool.free(out->d, out->pool_cap);
+    out->d = nullptr;
+    out->pool_cap = 0;
+  }
+  return rc;
 }
 
 int fr_alg_hash(Context* C, FrVec* v, const IdxVec* index, const uint64_t zeta[4], FrVec* out, uint64_t base) {

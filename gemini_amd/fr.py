@@ -251,7 +251,14 @@ class IdxVec:
         return cls(h.value, len(ix))
 
     def __len__(self) -> int:
-        return self.n
+        n = C.c_size_t()
+        capi.check(capi.load().gm_idx_len(C.c_uint64(self.handle), C.byref(n)))
+        return n.value
+
+    def to_host(self) -> np.ndarray:
+        out = np.empty(len(self), dtype=np.uint32)
+        capi.check(capi.load().gm_idx_download(C.c_uint64(self.handle), capi.ptr(out)))
+        return out
 
     def free(self):
         if self.handle:

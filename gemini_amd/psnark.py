@@ -8,6 +8,7 @@ import time
 import numpy as np
 
 from .circuit import R1cs
+from .entryproduct import EntryProductMsgs  # noqa: F401
 from .fr import (FrVec, IdxVec, R_MOD, accumulated_product_monic, alg_hash, element, evaluate_le, evaluate_le_batch, fr_from_int, fr_to_int, hadamard, ip,
                  linear_combination, lookup, plookup_set, plookup_subset, powers, shift_monic, tensor)
 from .kzg import CommitterKey
@@ -182,14 +183,7 @@ def plookup(subset: FrVec, set_: FrVec, index: IdxVec, ext_fre: IdxVec, y, z, ze
     return [lookup_set, lookup_subset, lookup_sorted]
 
 
-# ---- src/subprotocols/entryproduct -----------------------------------------------------------------------
-class EntryProductMsgs:
-    """entryproduct/mod.rs:21-25"""
-
-    def __init__(self, acc_v_commitments, claimed_sumchecks):
-        self.acc_v_commitments = acc_v_commitments
-        self.claimed_sumchecks = claimed_sumchecks
-
+# ---- src/subprotocols/entryproduct: gemini_amd/entryproduct.py (EntryProductMsgs is part of this module's proof record) --------
 
 # ONE orchestration per prover in the product: the one compiled into the library.  The step-wise statement (and the entry-product argument's,
 # `EntryProduct`) is test infrastructure: tests/stepwise/psnark_steps.py, registered here by `import tests.stepwise`.

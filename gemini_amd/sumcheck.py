@@ -32,6 +32,13 @@ class TimeProver:
             capi.check(capi.load().gm_sc_new(capi.ptr(fm), C.c_size_t(len(fm)), capi.ptr(gm), C.c_size_t(len(gm)), capi.ptr(tw), C.byref(h)))
         self.handle = h.value
 
+    @classmethod
+    def from_handle(cls, handle: int) -> "TimeProver":
+        """a gm_sc_* prover the library created (gm_entryproduct_new_time_batch); this object owns it from here"""
+        p = cls.__new__(cls)
+        p.handle, p._keep = int(handle), None
+        return p
+
     def next_message(self, verifier_message=None):
         a = np.empty(4, dtype=np.uint64)
         b = np.empty(4, dtype=np.uint64)

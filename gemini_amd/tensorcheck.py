@@ -1,8 +1,23 @@
-"""TensorcheckProof (src/subprotocols/tensorcheck/mod.rs:39-46) as data, and foldings_polynomial (:124-133).  The prover (:190-275) runs inside the
-native provers (gemini_amd/csrc/{snark,psnark}.cpp); its step-wise statement is tests/stepwise/tensorcheck_steps.py."""
+"""TensorcheckProof (src/subprotocols/tensorcheck/mod.rs:39-46), foldings_polynomial (:124-133) and the prover `TensorcheckProof.new_time`
+(:190-275) as one call into the library (gm_tensorcheck_new_time, gemini_amd/csrc/subprotocols.cpp).  The whole provers run the same
+sequence inline (gemini_amd/csrc/{snark,psnark}.cpp); its step-wise statement is tests/stepwise/tensorcheck_steps.py."""
 from __future__ import annotations
 
-from .fr import FrVec, fold_polynomial
+import ctypes as C
+
+import numpy as np
+
+from . import capi
+from .fr import FrVec, _as_vec, fold_polynomial
+
+
+class _Body(C.Structure):
+    _fields_ = [("polys", C.c_void_p), ("npolys", C.c_size_t), ("challenges_mont", C.c_void_p), ("nchallenges", C.c_size_t)]
+
+
+class _Proof(C.Structure):
+    _fields_ = [("nfold", C.c_size_t), ("cap_folds", C.c_size_t), ("fold_commitments", C.c_void_p), ("fold_evaluations", C.c_void_p),
+                ("evaluation_proof", C.c_uint64 * 18), ("nbase", C.c_size_t), ("base_evaluations", C.c_void_p)]
 
 
 def foldings_polynomial(polynomial: FrVec, challenges_mont) -> list:
@@ -21,3 +36,39 @@ class TensorcheckProof:
         self.folded_polynomials_evaluations = folded_polynomials_evaluations
         self.evaluation_proof = evaluation_proof
         self.base_polynomials_evaluations = base_polynomials_evaluations
+
+    @staticmethod
+    def new_time(transcript, ck, base_polynomials, body_polynomials, cap_folds: int | None = None) -> "TensorcheckProof":
+        """:190-275.  base_polynomials: device vectors (FrVec) or host arrays; body_polynomials: [(polynomials, challenges)], the
+        challenges Montgomery (k, 4).  cap_folds: room for the foldings (default: exactly sum (len(challenges) - 1))."""
+        tmp = []
+
+        def dev(p):
+            v, t = _as_vec(p)
+            if t:
+                tmp.append(v)
+            return v.handle
+
+        try:
+            bases = np.array([dev(p) for p in base_polynomials], dtype=np.uint64)
+            keep, bodies = [], (_Body * max(len(body_polynomials), 1))()
+            nfold = 0
+            for b, (polys, challenges) in enumerate(body_polynomials):
+                hp = np.array([dev(p) for p in polys], dtype=np.uint64)
+                ch = capi.u64(np.asarray(challenges, dtype=np.uint64).reshape(-1, 4))
+                keep += [hp, ch]
+                bodies[b] = _Body(hp.ctypes.data, len(hp), ch.ctypes.data, len(ch))
+                nfold += max(len(ch) - 1, 0)
+            cap = nfold if cap_folds is None else int(cap_folds)
+            fc = np.zeros((max(cap, 1), 18), dtype=np.uint64)
+            fe = np.zeros((max(cap, 1), 2, 4), dtype=np.uint64)
+            be = np.zeros((max(len(bases), 1), 3, 4), dtype=np.uint64)
+            rec = _Proof(0, cap, fc.ctypes.data, fe.ctypes.data, (C.c_uint64 * 18)(), len(bases), be.ctypes.data)
+            capi.check(capi.load().gm_tensorcheck_new_time(C.c_uint64(transcript.handle), C.c_uint64(ck.powers_of_g.handle), capi.ptr(bases),
+                                                           C.c_size_t(len(bases)), bodies, C.c_size_t(len(body_polynomials)), C.byref(rec)))
+        finally:
+            for v in tmp:
+                v.free()
+        n = rec.nfold
+        return TensorcheckProof([fc[i].copy() for i in range(n)], [fe[i].copy() for i in range(n)], np.array(rec.evaluation_proof, dtype=np.uint64),
+                                [be[i].copy() for i in range(len(bases))])

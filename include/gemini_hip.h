@@ -243,11 +243,11 @@ int gm_set_msm_affine_levels(int levels);
 
 /* Per-stage device timing (HIP events on the library's stream).  Stages, in order:
  * 0 digits+histogram, 1 scan, 2 scatter, 3 bucket accumulate (k_acc0), 4 partial merge,
- * 5 bucket reduce, 6 sumcheck round.  gm_prof_enable(1) resets and starts accumulating; gm_prof_enable(2): stage 3 only (every
+ * 5 bucket reduce, 6 sumcheck round, 7 the kernels of gm_idx_extend_frequency.  gm_prof_enable(1) resets and starts accumulating; gm_prof_enable(2): stage 3 only (every
  * event record between two kernels of a call is a ~10 us bubble on the stream: five stages cost an MSM ~60 us, one ~20 us);
  * gm_prof_read returns total milliseconds and launch-group counts per stage.  No reference
  * counterpart (the reference only has start_timer!/end_timer! spans, src/snark/time_prover.rs:23). */
-#define GM_PROF_NSTAGES 7
+#define GM_PROF_NSTAGES 8
 int gm_prof_enable(int on);
 int gm_prof_read(double* ms_out, uint64_t* count_out, int n);
 /* The shader clock (MHz) the bucket accumulation ran at while profiling was on: clock64() against the constant 100 MHz
@@ -311,6 +311,15 @@ int gm_fr_div_vanishing(uint64_t f, const uint64_t* points_mont, size_t k, uint6
 /* `&[usize]` arguments (row_index, col_index, extended frequencies) copied to HBM once. */
 int gm_idx_register(const uint32_t* index, size_t n, uint64_t* handle);
 int gm_idx_free(uint64_t handle);
+int gm_idx_len(uint64_t handle, size_t* n);
+/* the n entries of an index vector (tests, and a caller's own checks of a vector that was built on the device) */
+int gm_idx_download(uint64_t handle, uint32_t* out);
+/* extend_frequency(compute_frequency(set_len, index))                           plookup/time_prover.rs:65-78
+ * index: a gm_idx handle with k entries, every entry < set_len (else GM_EINVAL and nothing is registered: the entries are range-checked
+ * on the device before they address a counter).  *ext: a NEW gm_idx handle (gm_idx_free) with the non-decreasing sequence in which every
+ * v in [0, set_len) appears 1 + #{j : index[j] == v} times; *ext_len = set_len + k, which must fit the 32-bit index vectors.
+ * Built in HBM -- integer-atomic histogram, exclusive scan, expansion -- with no host pass over the index and no upload. */
+int gm_idx_extend_frequency(uint64_t index, size_t set_len, uint64_t* ext, size_t* ext_len);
 /* out[j] = src[index[j]]: `lookup` and `sorted`        src/subprotocols/plookup/time_prover.rs:5-8,67-74 */
 int gm_fr_gather(uint64_t src, uint64_t index, uint64_t out);
 /* out[i] = v[i] + F::from(index[i]) * zeta; index = 0 means the range 0..len   plookup/time_prover.rs:11-21 */
@@ -473,6 +482,47 @@ int gm_sumcheck_prove(uint64_t transcript, uint64_t prover, uint64_t* messages, 
  * messages: cap_rounds x 8, challenges: cap_rounds x 4, final_foldings: k x 8 (lhs || rhs). */
 int gm_sumcheck_prove_batch(uint64_t transcript, const uint64_t* provers, size_t k, uint64_t* messages, uint64_t* challenges,
                             size_t cap_rounds, uint64_t* final_foldings, size_t* rounds_out);
+
+/* ---- the sub-protocols on their own (gemini_amd/csrc/subprotocols.cpp) ---------------------------------------------------
+ * What the reference exports under subprotocols:: for a caller that composes an argument of its own: the same orchestration over the
+ * entry points above as the whole-prover entries below run inline, the same transcript labels in the same order.
+ *
+ * TensorcheckProof::new_time(transcript, ck, base_polynomials, body_polynomials)        tensorcheck/mod.rs:190-275
+ * A body = the polynomials that are batched with powers of the batch challenge (linear_combination pads to the longest, so unequal
+ * lengths are fine) and the tensor challenges they are folded by; all challenges but the last fold (strip_last, :124-133), so a body
+ * with one challenge contributes no folding.  nbodies = 0 or a body without polynomials: GM_EINVAL (the reference asserts).
+ * The caller sets cap_folds, nbase and the three arrays; nfold = sum_b (nchallenges_b - 1) comes back, GM_EINVAL when it exceeds cap_folds. */
+typedef struct gm_tensorcheck_body {
+  const uint64_t* polys;           /* gm_fr_vec handles */
+  size_t npolys;
+  const uint64_t* challenges_mont; /* 4 limbs each */
+  size_t nchallenges;
+} gm_tensorcheck_body;
+typedef struct gm_tensorcheck_proof {
+  size_t nfold, cap_folds;
+  uint64_t* fold_commitments;  /* caller-owned, cap_folds x 18 */
+  uint64_t* fold_evaluations;  /* caller-owned, cap_folds x 8: at beta, -beta */
+  uint64_t evaluation_proof[18];
+  size_t nbase;
+  uint64_t* base_evaluations;  /* caller-owned, nbase x 12: at beta^2, beta, -beta */
+} gm_tensorcheck_proof;
+int gm_tensorcheck_new_time(uint64_t transcript, uint64_t ck_bases, const uint64_t* base_polys, size_t nbase, const gm_tensorcheck_body* bodies,
+                            size_t nbodies, gm_tensorcheck_proof* proof);
+/* EntryProduct::new_time_batch (entryproduct/time_prover.rs:61-114); k = 1 is new_time (:117-147).
+ * vs: k vectors; acc_vs_or_null: accumulated_product(monic(v_i)) where the caller already holds them, else they are built here.
+ * Out: the commitments to the accumulated vectors (k x 18), the claimed sums chal * acc_v(chal) + product - chal^(len + 1) (k x 4),
+ * the challenge, and k gm_sc_* provers Witness(acc_v, right_rotation(monic(v)), chal) for gm_sumcheck_prove_batch (gm_sc_free each).
+ * The provers OWN their data: gm_sc_new_v semantics, one copy of both vectors (2 x (len + 1) x 32 bytes) per prover, so every input
+ * vector may be freed as soon as this returns. */
+int gm_entryproduct_new_time_batch(uint64_t transcript, uint64_t ck_bases, const uint64_t* vs, const uint64_t* acc_vs_or_null, size_t k,
+                                   const uint64_t* claimed_products_mont, uint64_t* acc_v_commitments, uint64_t* claimed_sumchecks_mont,
+                                   uint64_t chal_mont[4], uint64_t* provers);
+/* plookup(subset, set, index, y, z, zeta) -> out = {lookup_set, lookup_subset, lookup_sorted}       plookup/time_prover.rs:89-112
+ * Three NEW vectors the caller frees.  With zeta != 0 set and subset are hashed first and the subset is cut to min(|subset|, |index|) by
+ * the zip (:11-21); with zeta = 0 neither.  ext_fre_or_0 = 0: the extended frequency of `index` is built on the device
+ * (gm_idx_extend_frequency) and dropped; non-zero: the gm_idx handle of it that the caller keeps across proofs over the same index. */
+int gm_plookup_new_time(uint64_t subset, uint64_t set, uint64_t index, uint64_t ext_fre_or_0, const uint64_t y_mont[4], const uint64_t z_mont[4],
+                        const uint64_t zeta_mont[4], uint64_t out[3]);
 
 /* ---- the whole prover in one call ---------------------------------------------------------------------
  * snark::Proof::new_time (src/snark/time_prover.rs:19-117) with its tensor check (tensorcheck/mod.rs:190-275) and KZG

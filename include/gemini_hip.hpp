@@ -10,6 +10,9 @@
 //   gm::TimeProver (trait Prover)                           src/subprotocols/sumcheck/prover.rs:30-45
 //   gm::Transcript (GeminiTranscript over merlin)           src/transcript.rs:8-34
 //   gm::Sumcheck::{prove, new_time}                         src/subprotocols/sumcheck/proof.rs:36-66,125-130
+//   gm::TensorcheckProof::new_time                          src/subprotocols/tensorcheck/mod.rs:190-275
+//   gm::EntryProduct::{new_time, new_time_batch}            src/subprotocols/entryproduct/time_prover.rs:61-147
+//   gm::plookup, gm::DeviceVec, gm::IdxVec                  src/subprotocols/plookup/time_prover.rs:65-112
 //   gm::R1cs, gm::SnarkProof::{new_time, new_elastic}       src/circuit.rs, src/snark/time_prover.rs:19-117, elastic_prover.rs:174-266
 //   gm::dist::{init_rccl, init_shm, init_hook, ...}         the all-gather between the per-GPU processes (no reference counterpart:
 //                                                           the reference is single-device; gemini_amd/csrc/dist.cpp)
@@ -359,6 +362,13 @@ class TimeProver {
   TimeProver(const std::vector<Fr>& f, const std::vector<Fr>& g, const Fr& twist) {
     check(gm_sc_new(f.empty() ? nullptr : f[0].data(), f.size(), g.empty() ? nullptr : g[0].data(), g.size(), twist.data(), &h_));
   }
+  // a gm_sc_* prover the library created (EntryProduct::new_time_batch); owned from here
+  static TimeProver from_handle(uint64_t handle) {
+    TimeProver p;
+    p.h_ = handle;
+    return p;
+  }
+  TimeProver(TimeProver&& o) noexcept : h_(o.h_) { o.h_ = 0; }
   ~TimeProver() {
     if (h_) gm_sc_free(h_);
   }
@@ -392,6 +402,7 @@ class TimeProver {
   uint64_t handle() const { return h_; }
 
  private:
+  TimeProver() = default;
   uint64_t h_ = 0;
 };
 
@@ -457,6 +468,30 @@ struct Sumcheck {
     TimeProver prover(f, g, twist);
     return prove(transcript, prover);
   }
+  // proof.rs:69-122, the round loop inside the library (gm_sumcheck_prove_batch); final_foldings: one (lhs, rhs) per prover
+  static Sumcheck prove_batch(Transcript& transcript, std::vector<TimeProver>& provers) {
+    size_t cap = 1;
+    std::vector<uint64_t> handles;
+    for (auto& p : provers) {
+      cap = p.rounds() + 1 > cap ? p.rounds() + 1 : cap;
+      handles.push_back(p.handle());
+    }
+    std::vector<uint64_t> msgs(cap * 8), chs(cap * 4), ff(provers.size() * 8 + 8);
+    size_t rounds = 0;
+    check(gm_sumcheck_prove_batch(transcript.handle(), handles.data(), handles.size(), msgs.data(), chs.data(), cap, ff.data(), &rounds));
+    Sumcheck s;
+    s.rounds = rounds;
+    s.messages.resize(rounds);
+    s.challenges.resize(rounds);
+    for (size_t i = 0; i < rounds; i++) {
+      memcpy(s.messages[i].a.data(), msgs.data() + 8 * i, 32);
+      memcpy(s.messages[i].b.data(), msgs.data() + 8 * i + 4, 32);
+      memcpy(s.challenges[i].data(), chs.data() + 4 * i, 32);
+    }
+    s.final_foldings.resize(provers.size());
+    for (size_t j = 0; j < provers.size(); j++) memcpy(s.final_foldings[j].data(), ff.data() + 8 * j, 64);
+    return s;
+  }
 };
 
 // `Matrix<F> = Vec<Vec<(F, usize)>>` (src/circuit.rs:43) resident in HBM as CSR, together with its transpose (the
@@ -520,13 +555,159 @@ class R1cs {
   size_t nz_;
 };
 
+// `Vec<F>` / `&[usize]` resident in HBM: what the stand-alone sub-protocols below take and return
+class DeviceVec {
+ public:
+  explicit DeviceVec(const std::vector<Fr>& v) {
+    check(gm_fr_vec_alloc(v.size(), &h_));
+    if (!v.empty()) {
+      const int rc = gm_fr_vec_upload(h_, 0, v[0].data(), v.size());
+      if (rc) {
+        gm_fr_vec_free(h_);
+        check(rc);
+      }
+    }
+  }
+  static DeviceVec from_handle(uint64_t handle) {  // a vector the library created; owned from here
+    DeviceVec d;
+    d.h_ = handle;
+    return d;
+  }
+  DeviceVec(DeviceVec&& o) noexcept : h_(o.h_) { o.h_ = 0; }
+  DeviceVec(const DeviceVec&) = delete;
+  DeviceVec& operator=(const DeviceVec&) = delete;
+  ~DeviceVec() {
+    if (h_) gm_fr_vec_free(h_);
+  }
+  size_t size() const {
+    size_t n = 0;
+    check(gm_fr_vec_len(h_, &n));
+    return n;
+  }
+  std::vector<Fr> to_host() const {
+    std::vector<Fr> out(size());
+    if (!out.empty()) check(gm_fr_vec_download(h_, 0, out[0].data(), out.size()));
+    return out;
+  }
+  uint64_t handle() const { return h_; }
+
+ private:
+  DeviceVec() = default;
+  uint64_t h_ = 0;
+};
+class IdxVec {
+ public:
+  explicit IdxVec(const std::vector<uint32_t>& index) { check(gm_idx_register(index.data(), index.size(), &h_)); }
+  // extend_frequency(compute_frequency(set_len, index)) built on the device   plookup/time_prover.rs:65-78
+  IdxVec extend_frequency(size_t set_len) const {
+    IdxVec e;
+    size_t n = 0;
+    check(gm_idx_extend_frequency(h_, set_len, &e.h_, &n));
+    return e;
+  }
+  IdxVec(IdxVec&& o) noexcept : h_(o.h_) { o.h_ = 0; }
+  IdxVec(const IdxVec&) = delete;
+  IdxVec& operator=(const IdxVec&) = delete;
+  ~IdxVec() {
+    if (h_) gm_idx_free(h_);
+  }
+  size_t size() const {
+    size_t n = 0;
+    check(gm_idx_len(h_, &n));
+    return n;
+  }
+  std::vector<uint32_t> to_host() const {
+    std::vector<uint32_t> out(size());
+    check(gm_idx_download(h_, out.data()));
+    return out;
+  }
+  uint64_t handle() const { return h_; }
+
+ private:
+  IdxVec() = default;
+  uint64_t h_ = 0;
+};
+
 // src/subprotocols/tensorcheck/mod.rs:110-121
 struct TensorcheckProof {
   std::vector<G1Projective> folded_polynomials_commitments;
   std::vector<std::array<Fr, 2>> folded_polynomials_evaluations;
   G1Projective evaluation_proof;
   std::vector<std::array<Fr, 3>> base_polynomials_evaluations;
+
+  // :190-275 (gm_tensorcheck_new_time).  A body: the polynomials batched together and the tensor challenges they fold by
+  struct Body {
+    std::vector<const DeviceVec*> polynomials;
+    std::vector<Fr> challenges;
+  };
+  static TensorcheckProof new_time(Transcript& transcript, const CommitterKey& ck, const std::vector<const DeviceVec*>& base_polynomials,
+                                   const std::vector<Body>& body_polynomials) {
+    std::vector<uint64_t> bases;
+    for (auto* p : base_polynomials) bases.push_back(p->handle());
+    std::vector<std::vector<uint64_t>> polys(body_polynomials.size());
+    std::vector<gm_tensorcheck_body> bodies(body_polynomials.size());
+    size_t nfold = 0;
+    for (size_t b = 0; b < body_polynomials.size(); b++) {
+      const Body& B = body_polynomials[b];
+      for (auto* p : B.polynomials) polys[b].push_back(p->handle());
+      bodies[b] = gm_tensorcheck_body{polys[b].data(), polys[b].size(), B.challenges.empty() ? nullptr : B.challenges[0].data(), B.challenges.size()};
+      nfold += B.challenges.empty() ? 0 : B.challenges.size() - 1;
+    }
+    TensorcheckProof out;
+    out.folded_polynomials_commitments.resize(nfold);
+    out.folded_polynomials_evaluations.resize(nfold);
+    out.base_polynomials_evaluations.resize(bases.size());
+    gm_tensorcheck_proof p;
+    memset(&p, 0, sizeof p);
+    p.cap_folds = nfold;
+    p.fold_commitments = nfold ? out.folded_polynomials_commitments[0].data() : nullptr;
+    p.fold_evaluations = nfold ? out.folded_polynomials_evaluations[0][0].data() : nullptr;
+    p.nbase = bases.size();
+    p.base_evaluations = bases.empty() ? nullptr : out.base_polynomials_evaluations[0][0].data();
+    check(gm_tensorcheck_new_time(transcript.handle(), ck.handle(), bases.data(), bases.size(), bodies.data(), bodies.size(), &p));
+    memcpy(out.evaluation_proof.data(), p.evaluation_proof, 144);
+    return out;
+  }
 };
+
+// src/subprotocols/entryproduct/mod.rs:21-31 + time_prover.rs:61-147 (gm_entryproduct_new_time_batch): the provers own their data
+struct EntryProduct {
+  struct ProverMsgs {
+    std::vector<G1Projective> acc_v_commitments;
+    std::vector<Fr> claimed_sumchecks;
+  };
+  ProverMsgs msgs;
+  Fr chal;
+  std::vector<TimeProver> provers;
+
+  static EntryProduct new_time_batch(Transcript& transcript, const CommitterKey& ck, const std::vector<const DeviceVec*>& vs,
+                                     const std::vector<Fr>& claimed_products) {
+    if (vs.size() != claimed_products.size()) throw Error(GM_EINVAL, "EntryProduct::new_time_batch: one claimed product per vector");
+    const size_t k = vs.size();
+    std::vector<uint64_t> hv, hp(k, 0);
+    for (auto* v : vs) hv.push_back(v->handle());
+    EntryProduct ep;
+    ep.msgs.acc_v_commitments.resize(k);
+    ep.msgs.claimed_sumchecks.resize(k);
+    check(gm_entryproduct_new_time_batch(transcript.handle(), ck.handle(), hv.data(), nullptr, k, k ? claimed_products[0].data() : nullptr,
+                                         k ? ep.msgs.acc_v_commitments[0].data() : nullptr, k ? ep.msgs.claimed_sumchecks[0].data() : nullptr,
+                                         ep.chal.data(), hp.data()));
+    for (uint64_t h : hp) ep.provers.push_back(TimeProver::from_handle(h));
+    return ep;
+  }
+  static EntryProduct new_time(Transcript& transcript, const CommitterKey& ck, const DeviceVec& v, const Fr& claimed_product) {
+    return new_time_batch(transcript, ck, {&v}, {claimed_product});
+  }
+};
+
+// plookup(subset, set, index, y, z, zeta) -> {lookup_set, lookup_subset, lookup_sorted}   plookup/time_prover.rs:89-112
+// ext_fre: index.extend_frequency(set.size()) when the caller keeps it across proofs; null: built on the device inside the call
+inline std::array<DeviceVec, 3> plookup(const DeviceVec& subset, const DeviceVec& set, const IdxVec& index, const Fr& y, const Fr& z, const Fr& zeta,
+                                        const IdxVec* ext_fre = nullptr) {
+  uint64_t out[3] = {0, 0, 0};
+  check(gm_plookup_new_time(subset.handle(), set.handle(), index.handle(), ext_fre ? ext_fre->handle() : 0, y.data(), z.data(), zeta.data(), out));
+  return {DeviceVec::from_handle(out[0]), DeviceVec::from_handle(out[1]), DeviceVec::from_handle(out[2])};
+}
 
 // src/snark/mod.rs:76-82 + Proof::new_time (src/snark/time_prover.rs:19-117): one call into the library
 struct SnarkProof {
