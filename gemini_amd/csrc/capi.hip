@@ -432,6 +432,9 @@ void gm_shutdown(void) {
   for (auto& kv : C->provers) sc_destroy(kv.second.get());
   for (auto& kv : C->space_provers) sp_destroy(C, kv.second.get());
   for (auto& kv : C->herring_g1) hg1_destroy(C, kv.second.get());
+  for (auto& kv : C->herring_g2) hg2_destroy(C, kv.second.get());
+  for (auto& kv : C->g2_bases)
+    if (kv.second->d) (void)gm::raw_free(kv.second->d);
   C->partial_bufs.release_all();
   for (auto& kv : C->indices)
     if (kv.second->d) (void)gm::raw_free(kv.second->d);
@@ -452,6 +455,7 @@ void gm_shutdown(void) {
     }
   };
   release_ws(C->msm);
+  g2_workspace_release(C->g2);
   release_ws(C->msm_b);
   if (C->stream_b) (void)hipStreamDestroy(C->stream_b);
   for (int k = 0; k < MSM_SMALL_LANES; k++) {
@@ -539,6 +543,7 @@ int gm_mem_stats(uint64_t out[12]) {
   }
   size_t workspaces = msm_workspace_held(C->msm) + msm_workspace_held(C->msm_b);
   for (auto& w : C->msm_small) workspaces += msm_workspace_held(w);
+  for (const DevBuf* d : {&C->g2.buckets, &C->g2.part, &C->g2.red[0], &C->g2.red[1], &C->g2.longs}) workspaces += d->cap;
   MemStats& m = mem_stats();
   std::lock_guard<std::mutex> lk(m.mu);
   out[0] = total_b;
@@ -1761,6 +1766,152 @@ int gm_hg1_free(uint64_t handle) {
     C->herring_g1.erase(it);
   }
   hg1_destroy(C, p.get());
+  return GM_OK;
+}
+
+// ---- G2: MSM and the herring G2Module prover (g2msm.hip) ---------------------------------------------
+static G2Bases* find_g2_bases(Context* C, uint64_t h) {
+  std::lock_guard<std::mutex> lk(C->mu);
+  auto it = C->g2_bases.find(h);
+  return it == C->g2_bases.end() ? nullptr : it->second.get();
+}
+static int g2_msm_host_scalars(Context* C, const G2Bases* b, size_t offset, int reversed, const uint64_t* scalars, size_t n, uint64_t out_jac[36]) {
+  int rc;
+  GM_MSM_LOCK(C);  // held across the upload AND the MSM: another thread must not restage C->msm.scalars in between
+  if ((rc = C->msm.scalars.ensure(n * 32 + 32))) return rc;
+  if (n) GM_HIP(hipMemcpyAsync(C->msm.scalars.p, scalars, n * 32, hipMemcpyHostToDevice, C->stream));
+  return g2_msm_run(C, b, (int64_t)offset, reversed ? -1 : 1, C->msm.scalars.p, 0, n, out_jac);
+}
+int gm_g2_msm(const void* bases, size_t base_stride, const uint64_t* scalars, size_t n, uint64_t out_jac[36]) {
+  GM_CTX();
+  GM_CHECK(out_jac != nullptr && ((bases != nullptr && scalars != nullptr) || n == 0), GM_EINVAL, "g2_msm: null pointer");
+  std::unique_ptr<G2Bases> b;
+  int rc = g2_bases_from_host(C, bases, base_stride, n, b);
+  if (rc) return rc;
+  rc = g2_msm_host_scalars(C, b.get(), 0, 0, scalars, n, out_jac);
+  if (b->d) (void)gm::raw_free(b->d);
+  return rc;
+}
+int gm_g2_bases_register(const void* bases, size_t base_stride, size_t n, uint64_t* handle) {
+  GM_CTX();
+  GM_CHECK(handle != nullptr && (bases != nullptr || n == 0), GM_EINVAL, "g2_bases_register: null pointer");
+  std::unique_ptr<G2Bases> b;
+  int rc = g2_bases_from_host(C, bases, base_stride, n, b);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(C->mu);
+  *handle = C->next_handle++;
+  C->g2_bases[*handle] = std::move(b);
+  return GM_OK;
+}
+int gm_g2_bases_free(uint64_t handle) {
+  GM_CTX();
+  std::unique_ptr<G2Bases> b;
+  {
+    std::lock_guard<std::mutex> lk(C->mu);
+    auto it = C->g2_bases.find(handle);
+    GM_CHECK(it != C->g2_bases.end(), GM_EHANDLE, "g2_bases_free: unknown handle %llu", (unsigned long long)handle);
+    b = std::move(it->second);
+    C->g2_bases.erase(it);
+  }
+  if (b->d) GM_HIP(gm::raw_free(b->d));
+  return GM_OK;
+}
+#define GM_G2B(var, h, who)                 \
+  G2Bases* var = find_g2_bases(C, h);       \
+  GM_CHECK(var != nullptr, GM_EHANDLE, who ": unknown G2 bases handle %llu", (unsigned long long)(h))
+int gm_g2_bases_len(uint64_t handle, size_t* n) {
+  GM_CTX();
+  GM_G2B(b, handle, "g2_bases_len");
+  GM_CHECK(n != nullptr, GM_EINVAL, "g2_bases_len: null pointer");
+  *n = b->n;
+  return GM_OK;
+}
+int gm_g2_bases_download(uint64_t handle, size_t offset, size_t n, void* out192) {
+  GM_CTX();
+  GM_G2B(b, handle, "g2_bases_download");
+  GM_CHECK(out192 != nullptr || n == 0, GM_EINVAL, "g2_bases_download: null pointer");
+  GM_CHECK(offset <= b->n && n <= b->n - offset, GM_EINVAL, "g2_bases_download: range [%zu, %zu) outside %zu bases", offset, offset + n, b->n);
+  GM_MSM_LOCK(C);
+  return g2_bases_export(C, b, offset, n, out192);
+}
+int gm_g2_msm_h(uint64_t handle, size_t offset, int reversed, const uint64_t* scalars, size_t n, uint64_t out_jac[36]) {
+  GM_CTX();
+  GM_G2B(b, handle, "g2_msm_h");
+  GM_CHECK(out_jac != nullptr && (scalars != nullptr || n == 0), GM_EINVAL, "g2_msm_h: null pointer");
+  return g2_msm_host_scalars(C, b, offset, reversed, scalars, n, out_jac);
+}
+int gm_g2_msm_v(uint64_t bases_handle, size_t offset, int reversed, uint64_t vec_handle, size_t voffset, size_t n, uint64_t out_jac[36]) {
+  GM_CTX();
+  GM_G2B(b, bases_handle, "g2_msm_v");
+  FrVec* v = find_vec(vec_handle);
+  GM_CHECK(v != nullptr, GM_EHANDLE, "g2_msm_v: unknown vector handle %llu", (unsigned long long)vec_handle);
+  GM_CHECK(out_jac != nullptr, GM_EINVAL, "g2_msm_v: null pointer");
+  GM_CHECK(voffset <= v->len && n <= v->len - voffset, GM_EINVAL, "g2_msm_v: range [%zu, %zu) outside vector of length %zu", voffset, voffset + n, v->len);
+  return g2_msm_run(C, b, (int64_t)offset, reversed ? -1 : 1, v->d + voffset * 32, 1, n, out_jac);
+}
+int gm_g2_msm_d(uint64_t bases_handle, size_t offset, int reversed, const void* d_scalars, int mont, size_t n, uint64_t out_jac[36]) {
+  GM_CTX();
+  GM_G2B(b, bases_handle, "g2_msm_d");
+  GM_CHECK(out_jac != nullptr && (d_scalars != nullptr || n == 0), GM_EINVAL, "g2_msm_d: null pointer");
+  return g2_msm_run(C, b, (int64_t)offset, reversed ? -1 : 1, d_scalars, mont, n, out_jac);
+}
+int gm_g2_sum(const uint64_t* points_jac, size_t k, uint64_t out_jac[36]) {
+  GM_CHECK(out_jac != nullptr && (points_jac != nullptr || k == 0), GM_EINVAL, "g2_sum: null pointer");
+  gmh::G2 acc = gmh::G2::identity();
+  for (size_t i = 0; i < k; i++) acc = acc.add(gmh::G2::from_limbs(points_jac + 36 * i));
+  acc.normalized().to_limbs(out_jac);
+  return GM_OK;
+}
+static HerringG2* find_hg2(Context* C, uint64_t h) {
+  std::lock_guard<std::mutex> lk(C->mu);
+  auto it = C->herring_g2.find(h);
+  return it == C->herring_g2.end() ? nullptr : it->second.get();
+}
+#define GM_HG2(var, h, who)                   \
+  HerringG2* var = find_hg2(C, h);            \
+  GM_CHECK(var != nullptr, GM_EHANDLE, who ": unknown herring G2 prover handle %llu", (unsigned long long)(h))
+int gm_hg2_new(const uint64_t* f_mont, size_t nf, const void* g_bases, size_t base_stride, size_t ng, const uint64_t twist_mont[4],
+               uint64_t* handle) {
+  GM_CTX();
+  GM_CHECK(f_mont && g_bases && twist_mont && handle, GM_EINVAL, "hg2_new: null pointer");
+  return hg2_create(C, f_mont, nf, g_bases, base_stride, ng, twist_mont, handle);
+}
+int gm_hg2_round(uint64_t handle, const uint64_t* challenge_or_null, uint64_t a_jac[36], uint64_t b_jac[36], int* has_msg) {
+  GM_CTX();
+  GM_HG2(H, handle, "hg2_round");
+  GM_CHECK(a_jac && b_jac && has_msg, GM_EINVAL, "hg2_round: null pointer");
+  return hg2_round(C, H, challenge_or_null, a_jac, b_jac, has_msg);
+}
+int gm_hg2_fold(uint64_t handle, const uint64_t challenge_mont[4]) {
+  GM_CTX();
+  GM_HG2(H, handle, "hg2_fold");
+  GM_CHECK(challenge_mont != nullptr, GM_EINVAL, "hg2_fold: null pointer");
+  return hg2_fold(C, H, challenge_mont);
+}
+int gm_hg2_rounds(uint64_t handle, size_t* tot_rounds, size_t* round) {
+  GM_CTX();
+  GM_HG2(H, handle, "hg2_rounds");
+  if (tot_rounds) *tot_rounds = H->tot_rounds;
+  if (round) *round = H->round;
+  return GM_OK;
+}
+int gm_hg2_final(uint64_t handle, uint64_t f0_mont[4], uint64_t g0_jac[36], int* has) {
+  GM_CTX();
+  GM_HG2(H, handle, "hg2_final");
+  GM_CHECK(f0_mont && g0_jac && has, GM_EINVAL, "hg2_final: null pointer");
+  return hg2_final(C, H, f0_mont, g0_jac, has);
+}
+int gm_hg2_free(uint64_t handle) {
+  GM_CTX();
+  std::unique_ptr<HerringG2> p;
+  {
+    std::lock_guard<std::mutex> lk(C->mu);
+    auto it = C->herring_g2.find(handle);
+    GM_CHECK(it != C->herring_g2.end(), GM_EHANDLE, "hg2_free: unknown handle %llu", (unsigned long long)handle);
+    p = std::move(it->second);
+    C->herring_g2.erase(it);
+  }
+  hg2_destroy(C, p.get());
   return GM_OK;
 }
 

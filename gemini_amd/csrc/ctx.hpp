@@ -160,6 +160,32 @@ struct HerringG1 {
   std::mutex mu;
 };
 
+// G2 bases (g2msm.hip): n x 192 bytes, x.c0 | x.c1 | y.c0 | y.c1 in the device form of g1.cuh; identity = all zero
+struct G2Bases {
+  uint8_t* d = nullptr;
+  size_t n = 0;
+};
+// What a G2 MSM holds beyond the sort buffers it shares with G1 (MsmWorkspace counts / offsets / cursor / entries / ...):
+// buckets and chunk partials in 384-byte XYZZ records, the two ping-pong levels of the bucket reduction, the pinned window sums
+struct G2Workspace {
+  DevBuf buckets, part, red[2], longs;
+  uint64_t* host_out = nullptr;  // pinned: W window sums (48 u64 each) + the scalar-range flag
+  size_t host_out_cap = 0;
+};
+// herring TimeProver over G2Module (Lhs = F, Rhs = G2, Target = G2): src/herring/module.rs:104-125
+struct HerringG2 {
+  uint8_t* f[2] = {nullptr, nullptr};  // Fr
+  uint8_t* g[2] = {nullptr, nullptr};  // affine G2 points, 192 B each
+  size_t fcap[2] = {0, 0};
+  int cur = 0;
+  size_t nf = 0, ng = 0;
+  uint64_t twist[4];
+  size_t round = 0, tot_rounds = 0;
+  uint8_t* tmp = nullptr;  // compacted scalars
+  size_t tmpcap = 0;
+  std::mutex mu;
+};
+
 // ChunkedPippenger / msm_chunks over HOST-resident pairs (src/kzg/msm/stream_pippenger.rs:209-272, src/kzg/space.rs:22-55):
 // the device holds two chunks; chunk i + 1 is copied in while the MSM of chunk i runs (msm.hip: msm_stream_*)
 struct MsmWorkspace;
@@ -276,9 +302,12 @@ struct Context {
   std::unordered_map<uint64_t, std::unique_ptr<SparseMatrix>> matrices;
   std::unordered_map<uint64_t, std::unique_ptr<SpaceProver>> space_provers;
   std::unordered_map<uint64_t, std::unique_ptr<HerringG1>> herring_g1;
+  std::unordered_map<uint64_t, std::unique_ptr<G2Bases>> g2_bases;
+  std::unordered_map<uint64_t, std::unique_ptr<HerringG2>> herring_g2;
   std::unordered_map<uint64_t, std::unique_ptr<MsmStream>> msm_streams;
   std::unordered_map<uint64_t, std::unique_ptr<IdxVec>> indices;
   MsmWorkspace msm;
+  G2Workspace g2;  // single-flight under msm_mu, like msm
   // extra workspaces + streams for the small calls of a batch (msm_run_batch)
   MsmWorkspace msm_small[MSM_SMALL_LANES];
   hipStream_t small_stream[MSM_SMALL_LANES] = {};
@@ -382,5 +411,30 @@ int msm_run_batch(Context* C, const Bases* bases, int64_t first, int64_t step, c
 // call j walks the bases from index pair_offsets[j] (step +1) or DOWN from it (step -1)
 int msm_run_batch_offsets(Context* C, const Bases* bases, const size_t* pair_offsets, int64_t step, const void* const* d_scalars, int mont,
                           const size_t* ns, size_t k, bool normalize, uint64_t* out_jac);
+// The digit and sort stage of ONE plain call (no tables, no GLV, no window groups) for a second group: the digit, sort and scan
+// kernels of msm_enqueue (the direct scatter variants of the block sort) and the same choice between the flat and the block sort,
+// on `ws` and `st`.  Entries are (key << 32 | sign << 31 | pair index),
+// grouped by key = window * B + |digit| - 1; offsets[k] is where key k starts, offsets[nbuckets] the entry count.
+struct MsmSorted {
+  const uint64_t* entries = nullptr;
+  const uint32_t* offsets = nullptr;
+  const uint32_t* err = nullptr;  // != 0 after the sort: a scalar was >= 2^255
+  int W = 0;
+  uint32_t B = 0;
+  size_t nbuckets = 0;
+};
+int msm_sort_plain(Context* C, MsmWorkspace& ws, hipStream_t st, const void* d_scalars, int mont, size_t n, int c, MsmSorted* out);
+int msm_ceil_log2(size_t n);
+
+// G2 engine (g2msm.hip)
+int g2_bases_from_host(Context* C, const void* bases, size_t stride, size_t n, std::unique_ptr<G2Bases>& out);
+int g2_bases_export(Context* C, const G2Bases* b, size_t offset, size_t n, void* out192);
+int g2_msm_run(Context* C, const G2Bases* bases, int64_t first, int64_t step, const void* d_scalars, int mont, size_t n, uint64_t out_jac[36]);
+void g2_workspace_release(G2Workspace& w);
+int hg2_create(Context* C, const uint64_t* f_mont, size_t nf, const void* g_bases, size_t stride, size_t ng, const uint64_t twist[4], uint64_t* handle);
+void hg2_destroy(Context* C, HerringG2* H);
+int hg2_fold(Context* C, HerringG2* H, const uint64_t r[4]);
+int hg2_round(Context* C, HerringG2* H, const uint64_t* challenge, uint64_t a_jac[36], uint64_t b_jac[36], int* has_msg);
+int hg2_final(Context* C, HerringG2* H, uint64_t f0[4], uint64_t g0_jac[36], int* has);
 
 }  // namespace gm

@@ -300,6 +300,99 @@ static inline G1 xyzz_to_jac_dev(const u64* p) {
   return r;
 }
 
+// Fq2 = Fq[u] / (u^2 + 1), c0 + c1 u; memory image c0 | c1 (ark-ff `Fp2`)
+struct Fq2 {
+  Fq c0, c1;
+  static Fq2 zero() { return Fq2{Fq::zero(), Fq::zero()}; }
+  static Fq2 one() { return Fq2{Fq::one(), Fq::zero()}; }
+  static Fq2 from_limbs(const u64* p) { return Fq2{Fq::from_limbs(p), Fq::from_limbs(p + 6)}; }
+  void to_limbs(u64* p) const {
+    c0.to_limbs(p);
+    c1.to_limbs(p + 6);
+  }
+  bool is_zero() const { return c0.is_zero() && c1.is_zero(); }
+  bool operator==(const Fq2& o) const { return c0 == o.c0 && c1 == o.c1; }
+  Fq2 operator+(const Fq2& o) const { return Fq2{c0 + o.c0, c1 + o.c1}; }
+  Fq2 operator-(const Fq2& o) const { return Fq2{c0 - o.c0, c1 - o.c1}; }
+  Fq2 dbl() const { return Fq2{c0.dbl(), c1.dbl()}; }
+  Fq2 operator*(const Fq2& o) const {  // Karatsuba: 3 Fq products
+    const Fq v0 = c0 * o.c0, v1 = c1 * o.c1;
+    return Fq2{v0 - v1, (c0 + c1) * (o.c0 + o.c1) - v0 - v1};
+  }
+  Fq2 sqr() const { return Fq2{(c0 + c1) * (c0 - c1), (c0 * c1).dbl()}; }
+  Fq2 inv() const {  // (c0 - c1 u) / (c0^2 + c1^2); callers never invert zero
+    const Fq ni = (c0.sqr() + c1.sqr()).inv();
+    return Fq2{c0 * ni, (c1 * ni).neg()};
+  }
+};
+
+// Jacobian G2 point, ark-ec `Projective<g2::Config>` layout (X, Y, Z over Fq2, 36 limbs), identity Z = 0.  Same formulas as G1:
+// the curve y^2 = x^3 + 4 (1 + u) has a = 0 too.
+struct G2 {
+  Fq2 x, y, z;
+  static G2 identity() { return G2{Fq2::one(), Fq2::one(), Fq2::zero()}; }
+  bool is_identity() const { return z.is_zero(); }
+  static G2 from_limbs(const u64* p) { return G2{Fq2::from_limbs(p), Fq2::from_limbs(p + 12), Fq2::from_limbs(p + 24)}; }
+  void to_limbs(u64* p) const {
+    x.to_limbs(p);
+    y.to_limbs(p + 12);
+    z.to_limbs(p + 24);
+  }
+  G2 dbl() const {  // dbl-2009-l
+    if (is_identity()) return *this;
+    Fq2 A = x.sqr(), B = y.sqr(), C = B.sqr();
+    Fq2 t = x + B;
+    Fq2 D = (t.sqr() - A - C).dbl();
+    Fq2 E = A.dbl() + A;
+    Fq2 F = E.sqr();
+    G2 r;
+    r.x = F - D.dbl();
+    r.y = E * (D - r.x) - C.dbl().dbl().dbl();
+    r.z = (y * z).dbl();
+    return r;
+  }
+  G2 add(const G2& q) const {  // add-2007-bl with exceptional cases
+    if (is_identity()) return q;
+    if (q.is_identity()) return *this;
+    Fq2 z1z1 = z.sqr(), z2z2 = q.z.sqr();
+    Fq2 u1 = x * z2z2, u2 = q.x * z1z1;
+    Fq2 s1 = y * q.z * z2z2, s2 = q.y * z * z1z1;
+    if (u1 == u2) {
+      if (s1 == s2) return dbl();
+      return identity();
+    }
+    Fq2 h = u2 - u1;
+    Fq2 i = h.dbl().sqr();
+    Fq2 j = h * i;
+    Fq2 rr = (s2 - s1).dbl();
+    Fq2 v = u1 * i;
+    G2 r;
+    r.x = rr.sqr() - j - v.dbl();
+    r.y = rr * (v - r.x) - (s1 * j).dbl();
+    r.z = ((z + q.z).sqr() - z1z1 - z2z2) * h;
+    return r;
+  }
+  // (X/Z^2, Y/Z^3, 1): the unique representative, so equal points give equal bytes
+  G2 normalized() const {
+    if (is_identity()) return identity();
+    if (z == Fq2::one()) return *this;
+    Fq2 zi = z.inv(), zi2 = zi.sqr();
+    return G2{x * zi2, y * zi2 * zi, Fq2::one()};
+  }
+};
+static inline Fq2 fq2_from_device(const u64* p) { return Fq2{fq_from_device(p), fq_from_device(p + 6)}; }
+// 192-byte affine record in device form -> Jacobian in ark-ff form (the all-zero record is the identity)
+static inline G2 g2_affine_to_jac_dev(const u64* p) {
+  if (is_zero<24>(p)) return G2::identity();
+  return G2{fq2_from_device(p), fq2_from_device(p + 12), Fq2::one()};
+}
+// 384-byte XYZZ record in device form -> Jacobian in ark-ff form
+static inline G2 g2_xyzz_to_jac_dev(const u64* p) {
+  const Fq2 ZZ = fq2_from_device(p + 24);
+  if (ZZ.is_zero()) return G2::identity();
+  return G2{fq2_from_device(p) * ZZ, fq2_from_device(p + 12) * fq2_from_device(p + 36), ZZ};
+}
+
 // extended Jacobian (X, Y, ZZ, ZZZ) -> Jacobian, mirrors device xyzz_to_jac
 static inline G1 xyzz_to_jac(const u64* p) {
   Fq X = Fq::from_limbs(p), Y = Fq::from_limbs(p + 6), ZZ = Fq::from_limbs(p + 12), ZZZ = Fq::from_limbs(p + 18);

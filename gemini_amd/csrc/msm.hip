@@ -2710,6 +2710,92 @@ static int msm_finish_parts(Context* C, const MsmPending* parts, int nparts, boo
   return GM_OK;
 }
 
+// ---- the digit + sort stage on its own (ctx.hpp: MsmSorted) ---------------------------------------
+// For the G2 MSM (g2msm.hip): the group-agnostic front of msm_enqueue for one plain call -- the flat three-launch sort up to
+// 2^21 entries, the two-pass block sort above, with the same geometry rules.  The G1 path does not go through here: its dispatch
+// in msm_enqueue (tables, GLV, levels, window groups, profiling stages) stays as it was, so the size rule and the FB / G geometry
+// are stated twice.  Of the block sort this launches the DIRECT scatter kernels k_sort1<true> / k_sort2<true> (G1's GM_MSM_SORT1 /
+// GM_MSM_SORT2 = direct variants), not the LDS-staged ones G1 takes by default: same entries, about twice the sort time at 2^22
+// pairs (profiles/g2_msm.md), 4 % of a G2 call.
+int msm_ceil_log2(size_t n) { return ceil_log2_sz(n); }
+int msm_sort_plain(Context* C, MsmWorkspace& ws, hipStream_t st, const void* d_scalars, int mont, size_t n, int c, MsmSorted* out) {
+  (void)C;
+  GM_CHECK(n >= 1 && n < ((size_t)1 << ENTRY_W_SHIFT), GM_EINVAL, "msm sort: %zu pairs per call (1 .. 2^26 - 1)", n);
+  GM_CHECK(c >= 2 && c <= 22, GM_EINVAL, "msm sort: window width %d out of range [2, 22]", c);
+  const int W = (256 + c - 1) / c;
+  const uint32_t B = 1u << (c - 1);
+  const size_t nbuckets = (size_t)W * B;
+  const uint64_t N = (uint64_t)n * (uint64_t)W;
+  GM_CHECK(N < (1ull << 32), GM_EINVAL, "msm sort: n*W = %llu entries exceed 2^32", (unsigned long long)N);
+  int rc;
+  const size_t counts_words = (nbuckets + 2 + SORT_GMAX + 1 + 63) / 64 * 64;  // [nbuckets + 1]: the scalar-range flag, then the coarse bins
+  if ((rc = ws.counts.ensure(counts_words * 4))) return rc;
+  if ((rc = ws.offsets.ensure((nbuckets + 1) * 4))) return rc;
+  if ((rc = ws.cursor.ensure((nbuckets + 1) * 4))) return rc;
+  if ((rc = ws.misc.ensure((nbuckets / SCAN_PER_BLOCK + 2) * 4))) return rc;
+  if ((rc = ws.entries.ensure(N * 8))) return rc;
+  const uint32_t* sc = reinterpret_cast<const uint32_t*>(d_scalars);
+  GM_HIP(hipMemsetAsync(ws.counts.p, 0, counts_words * 4, st));
+  uint32_t* d_err = ws.counts.as<uint32_t>() + nbuckets + 1;
+  if (N <= ((uint64_t)1 << 21) && nbuckets <= ((size_t)1 << 18)) {
+    FlatGeom fg{};
+    fg.c = c;
+    fg.W = W;
+    fg.B = B;
+    for (int j = 0; j + 1 < W; j++) {
+      const int b = c * j + c - 1;
+      if (b < 256) fg.K[b >> 5] |= 1u << (b & 31);
+    }
+    const dim3 grid((uint32_t)((n + 255) / 256), (uint32_t)W);
+    hipLaunchKernelGGL(k_digits_flat<false>, grid, dim3(256), 0, st, sc, (uint32_t)n, mont, fg, ws.counts.as<uint32_t>(), (uint64_t*)nullptr, d_err);
+    hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1024), 0, st, ws.counts.as<uint32_t>(), (uint32_t)nbuckets, ws.offsets.as<uint32_t>(),
+                       ws.cursor.as<uint32_t>());
+    hipLaunchKernelGGL(k_digits_flat<true>, grid, dim3(256), 0, st, sc, (uint32_t)n, mont, fg, ws.cursor.as<uint32_t>(), ws.entries.as<uint64_t>(), d_err);
+  } else {
+    SortGeom sg;
+    sg.c = c;
+    sg.W = W;
+    sg.w_lo = 0;
+    sg.Wg = W;
+    sg.glv = 0;
+    sg.B = B;
+    sg.shared = 0;
+    sg.FB = std::min<uint32_t>((uint32_t)(c - 1), 10u);
+    while ((nbuckets >> sg.FB) > SORT_GMAX && (1u << sg.FB) < SORT_FMAX) sg.FB++;
+    sg.G = (uint32_t)(nbuckets >> sg.FB);
+    GM_CHECK(sg.G <= SORT_GMAX, GM_EINVAL, "msm sort: %u coarse sort bins exceed %u (window %d too wide for this sort)", sg.G, SORT_GMAX, c);
+    if ((rc = ws.tmp_entries.ensure(N * 8))) return rc;
+    if ((rc = ws.sortmeta.ensure((size_t)(3 * (sg.G + 1)) * 4))) return rc;
+    LevelGeom lg{};
+    uint32_t* gcount = ws.counts.as<uint32_t>() + nbuckets + 2;
+    uint32_t* goff = ws.sortmeta.as<uint32_t>();
+    uint32_t* gcursor = goff + (sg.G + 1);
+    uint32_t* blkoff = gcursor + (sg.G + 1);
+    const uint32_t b1 = (uint32_t)((n + SORT_TS - 1) / SORT_TS);
+    const uint32_t b2 = (uint32_t)(N / SORT_CH + sg.G + 1);
+    const uint32_t nb = (uint32_t)((nbuckets + SCAN_PER_BLOCK - 1) / SCAN_PER_BLOCK);
+    hipLaunchKernelGGL(k_sort1<false>, dim3(b1), dim3(256), 0, st, sc, (uint32_t)n, mont, sg, lg, gcount, (uint64_t*)nullptr, d_err);
+    hipLaunchKernelGGL(k_sort1_scan, dim3(1), dim3(1024), 0, st, gcount, sg.G, goff, gcursor, blkoff);
+    hipLaunchKernelGGL(k_sort1<true>, dim3(b1), dim3(256), 0, st, sc, (uint32_t)n, mont, sg, lg, gcursor, ws.tmp_entries.as<uint64_t>(), d_err);
+    hipLaunchKernelGGL(k_sort2<false>, dim3(b2), dim3(256), 0, st, ws.tmp_entries.as<uint64_t>(), goff, blkoff, sg, ws.counts.as<uint32_t>(),
+                       (uint64_t*)nullptr);
+    hipLaunchKernelGGL(k_scan_block_sums, dim3(nb), dim3(256), 0, st, ws.counts.as<uint32_t>(), (uint32_t)nbuckets, ws.misc.as<uint32_t>());
+    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, st, ws.misc.as<uint32_t>(), nb, ws.offsets.as<uint32_t>() + nbuckets);
+    hipLaunchKernelGGL(k_scan_apply, dim3(nb), dim3(256), 0, st, ws.counts.as<uint32_t>(), (uint32_t)nbuckets, ws.misc.as<uint32_t>(),
+                       ws.offsets.as<uint32_t>(), ws.cursor.as<uint32_t>());
+    hipLaunchKernelGGL(k_sort2<true>, dim3(b2), dim3(256), 0, st, ws.tmp_entries.as<uint64_t>(), goff, blkoff, sg, ws.cursor.as<uint32_t>(),
+                       ws.entries.as<uint64_t>());
+  }
+  GM_HIP(hipGetLastError());
+  out->entries = ws.entries.as<uint64_t>();
+  out->offsets = ws.offsets.as<uint32_t>();
+  out->err = d_err;
+  out->W = W;
+  out->B = B;
+  out->nbuckets = nbuckets;
+  return GM_OK;
+}
+
 // ---- bases management -----------------------------------------------------------------------
 int bases_from_host(Context* C, const void* bases, size_t stride, size_t n, std::unique_ptr<Bases>& out) {
   GM_CHECK(stride >= 96 && (stride % 8) == 0, GM_EINVAL, "bases: stride %zu must be >= 96 and a multiple of 8", stride);

@@ -1,6 +1,7 @@
 """Host mirror of herring's sumcheck over a bilinear module (src/herring): the TimeProver of
-src/herring/time_prover.rs:42-137 for the two module instances that are in scope:
-FModule (F x F -> F) and G1Module (G1 x F -> G1).  G2/GT/pairing modules are out of scope."""
+src/herring/time_prover.rs:42-137 for the three module instances that are in scope:
+FModule (F x F -> F), G1Module (G1 x F -> G1) and G2Module (F x G2 -> G2).  GT, pairings, PModule / GtModule and
+InnerProductProof are out of scope."""
 from __future__ import annotations
 
 import ctypes as C
@@ -62,4 +63,51 @@ class G1ModuleTimeProver:
     def free(self):
         if self.handle:
             capi.check(capi.load().gm_hg1_free(C.c_uint64(self.handle)))
+            self.handle = 0
+
+
+class G2ModuleTimeProver:
+    """TimeProver<G2Module>: f = Fr, g = G2 points ((n, 24) affine Montgomery, or (n, 25) Rust records); messages and the final
+    g are (36,) normalised Jacobian"""
+
+    def __init__(self, f, g_points, twist_mont):
+        capi.ensure_init()
+        fm = capi.u64(f).reshape(-1, 4)
+        gp = capi.u64(g_points)
+        h = C.c_uint64()
+        capi.check(capi.load().gm_hg2_new(capi.ptr(fm), C.c_size_t(len(fm)), capi.ptr(gp), C.c_size_t(gp.shape[1] * 8), C.c_size_t(len(gp)),
+                                          capi.ptr(capi.u64(twist_mont).reshape(4)), C.byref(h)))
+        self.handle = h.value
+
+    def next_message(self, verifier_message=None):
+        a = np.empty(36, dtype=np.uint64)
+        b = np.empty(36, dtype=np.uint64)
+        has = C.c_int()
+        ch = None if verifier_message is None else capi.ptr(capi.u64(verifier_message).reshape(4))
+        capi.check(capi.load().gm_hg2_round(C.c_uint64(self.handle), ch, capi.ptr(a), capi.ptr(b), C.byref(has)))
+        return (a, b) if has.value else None
+
+    def fold(self, challenge):
+        capi.check(capi.load().gm_hg2_fold(C.c_uint64(self.handle), capi.ptr(capi.u64(challenge).reshape(4))))
+
+    def rounds(self) -> int:
+        t = C.c_size_t()
+        capi.check(capi.load().gm_hg2_rounds(C.c_uint64(self.handle), C.byref(t), None))
+        return t.value
+
+    def round(self) -> int:
+        r = C.c_size_t()
+        capi.check(capi.load().gm_hg2_rounds(C.c_uint64(self.handle), None, C.byref(r)))
+        return r.value
+
+    def final_foldings(self):
+        f0 = np.empty(4, dtype=np.uint64)
+        g0 = np.empty(36, dtype=np.uint64)
+        has = C.c_int()
+        capi.check(capi.load().gm_hg2_final(C.c_uint64(self.handle), capi.ptr(f0), capi.ptr(g0), C.byref(has)))
+        return (f0, g0) if has.value else None
+
+    def free(self):
+        if self.handle:
+            capi.check(capi.load().gm_hg2_free(C.c_uint64(self.handle)))
             self.handle = 0

@@ -16,6 +16,12 @@
  *   - G1 results: Jacobian X, Y, Z (18 x u64, Montgomery) = the image of ark-ec
  *     `Projective<g1::Config>`.  Results are normalised (Z = R, or (R, R, 0) for the identity)
  *     so equal group elements always produce equal bytes.
+ *   - G2 affine bases: x.c0 | x.c1 | y.c0 | y.c1, each 6 x u64 Montgomery limbs (192 bytes), an Fq2 element being
+ *     c0 + c1 u with u^2 = -1: the image of ark-ec `Affine<g2::Config>` without its flag.  `stride` >= 192 and a multiple
+ *     of 8 (anything else gives GM_EINVAL); from stride 200 on, byte 192 is ark-ec's `infinity: bool` (the Rust record's stride).  With stride 192 the
+ *     identity is the all-zero record.
+ *   - G2 results: Jacobian X, Y, Z over Fq2 (36 x u64, Montgomery, c0 before c1) = the image of ark-ec
+ *     `Projective<g2::Config>`, normalised like the G1 results (Z = (R, 0), or ((R, 0), (R, 0), 0) for the identity).
  *   - Return value: 0 = ok, negative = GM_E*.  Nothing throws or aborts across the boundary;
  *     gm_last_error() gives a message for the calling thread.
  *   - Ownership: the caller owns every host buffer for the duration of the call only; registered
@@ -24,7 +30,7 @@
  *     different prover handles run concurrently (sumcheck::prove_batch calls next_message on distinct
  *     provers from different rayon threads, src/subprotocols/sumcheck/proof.rs:85; `Prover: Send + Sync`,
  *     prover.rs:30); calls on the SAME prover handle are serialised by a per-handle lock.  MSM calls
- *     (gm_g1_msm*, herring G1 rounds) share the device workspaces and are serialised by one library
+ *     (gm_g1_msm*, gm_g2_msm*, herring G1 / G2 rounds) share the device workspaces and are serialised by one library
  *     lock held from the staging of host scalars to the result (the reference's MSM calls are
  *     sequential too, src/kzg/time.rs:103-106); the vector entry points (gm_fr_*) are serialised by a
  *     second lock because they stage per-call parameters in one scratch buffer.  Results never depend
@@ -451,6 +457,39 @@ int gm_hg1_fold(uint64_t handle, const uint64_t challenge_mont[4]);
 int gm_hg1_rounds(uint64_t handle, size_t* tot_rounds, size_t* round);
 int gm_hg1_final(uint64_t handle, uint64_t f0_jac[18], uint64_t g0_mont[4], int* has);
 int gm_hg1_free(uint64_t handle);
+
+/* ---- BLS12-381 G2: MSM and the herring G2Module prover ------------------------------------------- */
+/* Replaces `P::G2::msm_unchecked` as Crs::commit_g2 / CrsStream::commit_g2 call it (src/herring/ipa.rs:107-118,185-189)
+ * and `G2Module::ip` (src/herring/module.rs:114-124): the signed-digit bucket method over Fq2, same semantics as the G1
+ * entry points of the same names (n = min(lengths); canonical scalars, a scalar >= 2^255 gives GM_EINVAL; results
+ * normalised).  A null pointer or a bad stride (< 192, or not a multiple of 8) gives GM_EINVAL, an unknown handle GM_EHANDLE.
+ * A call of more than 2^25 pairs is cut into 2^25-pair MSMs whose results are added on the host.
+ * OUT OF SCOPE for G2: fixed-base tables, GLV, the streaming form, batches, sharding; GT, pairings, PModule / GtModule
+ * and InnerProductProof. */
+int gm_g2_msm(const void* bases, size_t base_stride, const uint64_t* scalars, size_t n, uint64_t out_jac[36]);
+int gm_g2_bases_register(const void* bases, size_t base_stride, size_t n, uint64_t* handle);
+int gm_g2_bases_free(uint64_t handle);
+int gm_g2_bases_len(uint64_t handle, size_t* n);
+/* Copy registered bases back (192-byte stride). */
+int gm_g2_bases_download(uint64_t handle, size_t offset, size_t n, void* out192);
+/* bases[offset + i] (reversed: bases[offset - i]) against host scalars (canonical), an Fr vector (Montgomery) or device
+ * scalars (mont = 0 canonical, 1 Montgomery) */
+int gm_g2_msm_h(uint64_t handle, size_t offset, int reversed, const uint64_t* scalars, size_t n, uint64_t out_jac[36]);
+int gm_g2_msm_v(uint64_t bases_handle, size_t offset, int reversed, uint64_t vec_handle, size_t voffset, size_t n, uint64_t out_jac[36]);
+int gm_g2_msm_d(uint64_t bases_handle, size_t offset, int reversed, const void* d_scalars, int mont, size_t n, uint64_t out_jac[36]);
+/* Sum of k Jacobian points on the host (no GPU needed, like gm_g1_sum); normalised. */
+int gm_g2_sum(const uint64_t* points_jac, size_t k, uint64_t out_jac[36]);
+/* G2Module (F x G2 -> G2, module.rs:104-125): f is a vector of Fr, g a vector of G2 points (affine records as in
+ * gm_g2_bases_register).  Each message is three device MSMs over the even / odd halves; fold (time_prover.rs:83-88) is
+ * f' = split_fold(f, r * twist) in Fr and g'[i] = g[2i] + r g[2i+1] on the device.  Messages / final g are normalised
+ * Jacobian. */
+int gm_hg2_new(const uint64_t* f_mont, size_t nf, const void* g_bases, size_t base_stride, size_t ng, const uint64_t twist_mont[4],
+               uint64_t* handle);
+int gm_hg2_round(uint64_t handle, const uint64_t* challenge_or_null, uint64_t a_jac[36], uint64_t b_jac[36], int* has_msg);
+int gm_hg2_fold(uint64_t handle, const uint64_t challenge_mont[4]);
+int gm_hg2_rounds(uint64_t handle, size_t* tot_rounds, size_t* round);
+int gm_hg2_final(uint64_t handle, uint64_t f0_mont[4], uint64_t g0_jac[36], int* has);
+int gm_hg2_free(uint64_t handle);
 
 /* ---- Fiat-Shamir transcript (host; no GPU needed) ------------------------------------------------ */
 /* merlin::Transcript::new(label) (merlin 3.0.0, Cargo.lock:606-608); the prover uses

@@ -406,6 +406,121 @@ class TimeProver {
   uint64_t h_ = 0;
 };
 
+// ---- BLS12-381 G2: `P::G2::msm_unchecked` (src/herring/ipa.rs:107-118,185-189) and TimeProver<G2Module> (src/herring) -----------
+using G2Projective = std::array<uint64_t, 36>;  // Jacobian X, Y, Z over Fq2, c0 before c1
+struct G2Affine {                               // Rust layout: x.c0, x.c1, y.c0, y.c1, infinity (200-byte stride)
+  uint64_t x[12], y[12];
+  uint64_t infinity;  // bool at byte 192, padded
+};
+static_assert(sizeof(G2Affine) == 200, "G2Affine must match the 200-byte Rust record");
+
+inline G2Projective g2_zero() {
+  G2Projective z;
+  check(gm_g2_sum(nullptr, 0, z.data()));
+  return z;
+}
+inline G2Projective g2_add(const G2Projective& a, const G2Projective& b) {
+  uint64_t two[72];
+  memcpy(two, a.data(), 288);
+  memcpy(two + 36, b.data(), 288);
+  G2Projective r;
+  check(gm_g2_sum(two, 2, r.data()));
+  return r;
+}
+
+// G2 points resident in HBM (the `g2s` of herring's Crs); commit_g2 is msm_unchecked against them
+class G2Bases {
+ public:
+  explicit G2Bases(const std::vector<G2Affine>& points) : n_(points.size()) { check(gm_g2_bases_register(points.data(), sizeof(G2Affine), n_, &h_)); }
+  G2Bases(G2Bases&& o) noexcept : h_(o.h_), n_(o.n_) { o.h_ = 0; }
+  ~G2Bases() {
+    if (h_) gm_g2_bases_free(h_);
+  }
+  G2Bases(const G2Bases&) = delete;
+  G2Bases& operator=(const G2Bases&) = delete;
+  uint64_t handle() const { return h_; }
+  size_t size() const { return n_; }
+  // 192-byte records x.c0 | x.c1 | y.c0 | y.c1 (the identity all zero), 24 words each
+  std::vector<uint64_t> download(size_t offset, size_t n) const {
+    std::vector<uint64_t> out(n * 24);
+    check(gm_g2_bases_download(h_, offset, n, out.data()));
+    return out;
+  }
+  G2Projective msm_bigint(const std::vector<BigInt>& bigints, size_t offset = 0, bool reversed = false) const {
+    G2Projective out;
+    check(gm_g2_msm_h(h_, offset, reversed ? 1 : 0, bigints.empty() ? nullptr : bigints[0].data(), bigints.size(), out.data()));
+    return out;
+  }
+  // silently truncates to the shorter input, like the reference (src/herring/ipa.rs:117)
+  G2Projective msm_unchecked(const std::vector<Fr>& scalars) const {
+    const size_t n = scalars.size() < n_ ? scalars.size() : n_;
+    if (n == 0) return g2_zero();
+    uint64_t hv = 0;
+    check(gm_fr_vec_alloc(n, &hv));
+    G2Projective out;
+    int rc = gm_fr_vec_upload(hv, 0, scalars[0].data(), n);
+    if (!rc) rc = gm_g2_msm_v(h_, 0, 0, hv, 0, n, out.data());  // into_bigint happens on the device
+    gm_fr_vec_free(hv);
+    check(rc);
+    return out;
+  }
+  G2Projective msm_device(const void* d_scalars, bool mont, size_t n, size_t offset = 0, bool reversed = false) const {
+    G2Projective out;
+    check(gm_g2_msm_d(h_, offset, reversed ? 1 : 0, d_scalars, mont ? 1 : 0, n, out.data()));
+    return out;
+  }
+
+ private:
+  uint64_t h_ = 0;
+  size_t n_ = 0;
+};
+
+struct G2RoundMsg {
+  G2Projective a, b;
+};
+// TimeProver<G2Module> (src/herring/time_prover.rs:42-137, module.rs:104-125): f in Fr, g in G2
+class HerringG2 {
+ public:
+  HerringG2(const std::vector<Fr>& f, const std::vector<G2Affine>& g, const Fr& twist) {
+    check(gm_hg2_new(f.empty() ? nullptr : f[0].data(), f.size(), g.data(), sizeof(G2Affine), g.size(), twist.data(), &h_));
+  }
+  HerringG2(HerringG2&& o) noexcept : h_(o.h_) { o.h_ = 0; }
+  ~HerringG2() {
+    if (h_) gm_hg2_free(h_);
+  }
+  HerringG2(const HerringG2&) = delete;
+  HerringG2& operator=(const HerringG2&) = delete;
+  std::optional<G2RoundMsg> next_message(const std::optional<Fr>& verifier_message) {
+    G2RoundMsg m;
+    int has = 0;
+    check(gm_hg2_round(h_, verifier_message ? verifier_message->data() : nullptr, m.a.data(), m.b.data(), &has));
+    if (!has) return std::nullopt;
+    return m;
+  }
+  void fold(const Fr& challenge) { check(gm_hg2_fold(h_, challenge.data())); }
+  size_t rounds() const {
+    size_t t = 0;
+    check(gm_hg2_rounds(h_, &t, nullptr));
+    return t;
+  }
+  size_t round() const {
+    size_t r = 0;
+    check(gm_hg2_rounds(h_, nullptr, &r));
+    return r;
+  }
+  std::optional<std::pair<Fr, G2Projective>> final_foldings() const {
+    std::pair<Fr, G2Projective> ff;
+    int has = 0;
+    check(gm_hg2_final(h_, ff.first.data(), ff.second.data(), &has));
+    if (!has) return std::nullopt;
+    return ff;
+  }
+  uint64_t handle() const { return h_; }
+
+ private:
+  uint64_t h_ = 0;
+};
+
 // merlin::Transcript + GeminiTranscript, src/transcript.rs
 class Transcript {
  public:
