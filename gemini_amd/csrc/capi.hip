@@ -433,6 +433,7 @@ void gm_shutdown(void) {
   for (auto& kv : C->space_provers) sp_destroy(C, kv.second.get());
   for (auto& kv : C->herring_g1) hg1_destroy(C, kv.second.get());
   for (auto& kv : C->herring_g2) hg2_destroy(C, kv.second.get());
+  for (auto& kv : C->herring_p) hp_destroy(kv.second.get());
   for (auto& kv : C->g2_bases)
     if (kv.second->d) (void)gm::raw_free(kv.second->d);
   C->partial_bufs.release_all();
@@ -456,6 +457,7 @@ void gm_shutdown(void) {
   };
   release_ws(C->msm);
   g2_workspace_release(C->g2);
+  pairing_workspace_release(C->pairing);
   release_ws(C->msm_b);
   if (C->stream_b) (void)hipStreamDestroy(C->stream_b);
   for (int k = 0; k < MSM_SMALL_LANES; k++) {
@@ -543,7 +545,8 @@ int gm_mem_stats(uint64_t out[12]) {
   }
   size_t workspaces = msm_workspace_held(C->msm) + msm_workspace_held(C->msm_b);
   for (auto& w : C->msm_small) workspaces += msm_workspace_held(w);
-  for (const DevBuf* d : {&C->g2.buckets, &C->g2.part, &C->g2.red[0], &C->g2.red[1], &C->g2.longs}) workspaces += d->cap;
+  for (const DevBuf* d : {&C->g2.buckets, &C->g2.part, &C->g2.red[0], &C->g2.red[1], &C->g2.longs, &C->pairing.part[0], &C->pairing.part[1]})
+    workspaces += d->cap;
   MemStats& m = mem_stats();
   std::lock_guard<std::mutex> lk(m.mu);
   out[0] = total_b;
@@ -1912,6 +1915,99 @@ int gm_hg2_free(uint64_t handle) {
     C->herring_g2.erase(it);
   }
   hg2_destroy(C, p.get());
+  return GM_OK;
+}
+
+// ---- pairings: multi-Miller loop, GT helpers, the herring PModule prover (pairing.hip) ----------------
+int gm_pairing_multi(const void* g1, size_t g1_stride, const void* g2, size_t g2_stride, size_t n, uint64_t out_gt[72]) {
+  GM_CTX();
+  GM_CHECK(out_gt != nullptr && ((g1 != nullptr && g2 != nullptr) || n == 0), GM_EINVAL, "pairing_multi: null pointer");
+  if (n == 0) return gm_gt_one(out_gt);
+  return pairing_run_host(C, g1, g1_stride, g2, g2_stride, n, out_gt);
+}
+int gm_pairing_multi_h(uint64_t g1_handle, size_t off1, size_t step1, uint64_t g2_handle, size_t off2, size_t step2, size_t n, uint64_t out_gt[72]) {
+  GM_CTX();
+  Bases* b1 = find_bases(g1_handle);
+  GM_CHECK(b1 != nullptr, GM_EHANDLE, "pairing_multi_h: unknown G1 bases handle %llu", (unsigned long long)g1_handle);
+  GM_G2B(b2, g2_handle, "pairing_multi_h");
+  GM_CHECK(out_gt != nullptr, GM_EINVAL, "pairing_multi_h: null pointer");
+  GM_CHECK(step1 >= 1 && step2 >= 1, GM_EINVAL, "pairing_multi_h: steps %zu / %zu must be >= 1", step1, step2);
+  if (n == 0) return gm_gt_one(out_gt);
+  GM_CHECK(off1 < b1->n && (n - 1) <= (b1->n - 1 - off1) / step1, GM_EINVAL, "pairing_multi_h: G1 range %zu + %zu * [0, %zu) outside %zu bases", off1, step1, n,
+           b1->n);
+  GM_CHECK(off2 < b2->n && (n - 1) <= (b2->n - 1 - off2) / step2, GM_EINVAL, "pairing_multi_h: G2 range %zu + %zu * [0, %zu) outside %zu bases", off2, step2, n,
+           b2->n);
+  return pairing_run(C, b1->d, (int64_t)off1, (int64_t)step1, b2->d, (int64_t)off2, (int64_t)step2, n, out_gt);
+}
+int gm_gt_one(uint64_t out_gt[72]) {
+  GM_CHECK(out_gt != nullptr, GM_EINVAL, "gt_one: null pointer");
+  gmh::Fq12::one().to_limbs(out_gt);
+  return GM_OK;
+}
+int gm_gt_mul(const uint64_t a[72], const uint64_t b[72], uint64_t out_gt[72]) {
+  GM_CHECK(a && b && out_gt, GM_EINVAL, "gt_mul: null pointer");
+  (gmh::Fq12::from_limbs(a) * gmh::Fq12::from_limbs(b)).to_limbs(out_gt);
+  return GM_OK;
+}
+int gm_gt_pow(const uint64_t a[72], const uint64_t scalar_canonical[4], uint64_t out_gt[72]) {
+  GM_CHECK(a && scalar_canonical && out_gt, GM_EINVAL, "gt_pow: null pointer");
+  gmh::Fq12::from_limbs(a).pow(scalar_canonical, 4).to_limbs(out_gt);
+  return GM_OK;
+}
+int gm_gt_final_exp(const uint64_t in[72], uint64_t out_gt[72]) {
+  GM_CHECK(in && out_gt, GM_EINVAL, "gt_final_exp: null pointer");
+  gmh::gt_final_exponentiation(gmh::Fq12::from_limbs(in)).to_limbs(out_gt);
+  return GM_OK;
+}
+static HerringP* find_hp(Context* C, uint64_t h) {
+  std::lock_guard<std::mutex> lk(C->mu);
+  auto it = C->herring_p.find(h);
+  return it == C->herring_p.end() ? nullptr : it->second.get();
+}
+#define GM_HP(var, h, who)                  \
+  HerringP* var = find_hp(C, h);            \
+  GM_CHECK(var != nullptr, GM_EHANDLE, who ": unknown herring P prover handle %llu", (unsigned long long)(h))
+int gm_hp_new(const void* f_g1, size_t g1_stride, size_t nf, const void* g_g2, size_t g2_stride, size_t ng, const uint64_t twist_mont[4], uint64_t* handle) {
+  GM_CTX();
+  GM_CHECK(f_g1 && g_g2 && twist_mont && handle, GM_EINVAL, "hp_new: null pointer");
+  return hp_create(C, f_g1, g1_stride, nf, g_g2, g2_stride, ng, twist_mont, handle);
+}
+int gm_hp_round(uint64_t handle, const uint64_t* challenge_or_null, uint64_t a_gt[72], uint64_t b_gt[72], int* has_msg) {
+  GM_CTX();
+  GM_HP(H, handle, "hp_round");
+  GM_CHECK(a_gt && b_gt && has_msg, GM_EINVAL, "hp_round: null pointer");
+  return hp_round(C, H, challenge_or_null, a_gt, b_gt, has_msg);
+}
+int gm_hp_fold(uint64_t handle, const uint64_t challenge_mont[4]) {
+  GM_CTX();
+  GM_HP(H, handle, "hp_fold");
+  GM_CHECK(challenge_mont != nullptr, GM_EINVAL, "hp_fold: null pointer");
+  return hp_fold(C, H, challenge_mont);
+}
+int gm_hp_rounds(uint64_t handle, size_t* tot_rounds, size_t* round) {
+  GM_CTX();
+  GM_HP(H, handle, "hp_rounds");
+  if (tot_rounds) *tot_rounds = H->tot_rounds;
+  if (round) *round = H->round;
+  return GM_OK;
+}
+int gm_hp_final(uint64_t handle, uint64_t f0_jac[18], uint64_t g0_jac[36], int* has) {
+  GM_CTX();
+  GM_HP(H, handle, "hp_final");
+  GM_CHECK(f0_jac && g0_jac && has, GM_EINVAL, "hp_final: null pointer");
+  return hp_final(C, H, f0_jac, g0_jac, has);
+}
+int gm_hp_free(uint64_t handle) {
+  GM_CTX();
+  std::unique_ptr<HerringP> p;
+  {
+    std::lock_guard<std::mutex> lk(C->mu);
+    auto it = C->herring_p.find(handle);
+    GM_CHECK(it != C->herring_p.end(), GM_EHANDLE, "hp_free: unknown handle %llu", (unsigned long long)handle);
+    p = std::move(it->second);
+    C->herring_p.erase(it);
+  }
+  hp_destroy(p.get());
   return GM_OK;
 }
 

@@ -186,6 +186,24 @@ struct HerringG2 {
   std::mutex mu;
 };
 
+// What a multi-pairing holds (pairing.hip): the two ping-pong levels of Miller partial products (576-byte Fq12 records) and the
+// pinned copy of the last few.  Single-flight under msm_mu
+struct PairingWorkspace {
+  DevBuf part[2];
+  uint64_t* host_out = nullptr;
+};
+// herring TimeProver over PModule (Lhs = G1, Rhs = G2, Target = GT): src/herring/module.rs:60-79
+struct HerringP {
+  uint8_t* f[2] = {nullptr, nullptr};  // affine G1 points, 96 B each
+  uint8_t* g[2] = {nullptr, nullptr};  // affine G2 points, 192 B each
+  int cur = 0;
+  size_t nf = 0, ng = 0;
+  uint64_t twist[4];
+  size_t round = 0, tot_rounds = 0;
+  bool finished = false;  // the call that folded the last challenge has answered "no message": every later one is GM_ESTATE
+  std::mutex mu;
+};
+
 // ChunkedPippenger / msm_chunks over HOST-resident pairs (src/kzg/msm/stream_pippenger.rs:209-272, src/kzg/space.rs:22-55):
 // the device holds two chunks; chunk i + 1 is copied in while the MSM of chunk i runs (msm.hip: msm_stream_*)
 struct MsmWorkspace;
@@ -304,10 +322,12 @@ struct Context {
   std::unordered_map<uint64_t, std::unique_ptr<HerringG1>> herring_g1;
   std::unordered_map<uint64_t, std::unique_ptr<G2Bases>> g2_bases;
   std::unordered_map<uint64_t, std::unique_ptr<HerringG2>> herring_g2;
+  std::unordered_map<uint64_t, std::unique_ptr<HerringP>> herring_p;
   std::unordered_map<uint64_t, std::unique_ptr<MsmStream>> msm_streams;
   std::unordered_map<uint64_t, std::unique_ptr<IdxVec>> indices;
   MsmWorkspace msm;
   G2Workspace g2;  // single-flight under msm_mu, like msm
+  PairingWorkspace pairing;  // likewise
   // extra workspaces + streams for the small calls of a batch (msm_run_batch)
   MsmWorkspace msm_small[MSM_SMALL_LANES];
   hipStream_t small_stream[MSM_SMALL_LANES] = {};
@@ -436,5 +456,15 @@ void hg2_destroy(Context* C, HerringG2* H);
 int hg2_fold(Context* C, HerringG2* H, const uint64_t r[4]);
 int hg2_round(Context* C, HerringG2* H, const uint64_t* challenge, uint64_t a_jac[36], uint64_t b_jac[36], int* has_msg);
 int hg2_final(Context* C, HerringG2* H, uint64_t f0[4], uint64_t g0_jac[36], int* has);
+
+// pairings (pairing.hip): GT values are 72 limbs, 12 Fq in tower order, Montgomery
+int pairing_run(Context* C, const uint8_t* d_g1, int64_t first1, int64_t step1, const uint8_t* d_g2, int64_t first2, int64_t step2, size_t n, uint64_t out_gt[72]);
+int pairing_run_host(Context* C, const void* g1, size_t stride1, const void* g2, size_t stride2, size_t n, uint64_t out_gt[72]);
+void pairing_workspace_release(PairingWorkspace& w);
+int hp_create(Context* C, const void* f_g1, size_t stride1, size_t nf, const void* g_g2, size_t stride2, size_t ng, const uint64_t twist[4], uint64_t* handle);
+void hp_destroy(HerringP* H);
+int hp_fold(Context* C, HerringP* H, const uint64_t r[4]);
+int hp_round(Context* C, HerringP* H, const uint64_t* challenge, uint64_t a_gt[72], uint64_t b_gt[72], int* has_msg);
+int hp_final(Context* C, HerringP* H, uint64_t f0_jac[18], uint64_t g0_jac[36], int* has);
 
 }  // namespace gm

@@ -393,6 +393,100 @@ static inline G2 g2_xyzz_to_jac_dev(const u64* p) {
   return G2{fq2_from_device(p) * ZZ, fq2_from_device(p + 12) * fq2_from_device(p + 36), ZZ};
 }
 
+// ---- GT: Fq12 = Fq6[w] / (w^2 - v), Fq6 = Fq2[v] / (v^3 - xi), xi = 1 + u (ark-ff `Fp12` over `Fp6` over `Fp2` of BLS12-381).
+// Memory image: 12 Fq in tower order c0.c0.c0, c0.c0.c1, c0.c1.c0, ..., c1.c2.c1 (72 limbs).  Used for the tail of a
+// multi-pairing (the last few Miller partials, the conjugation, the final exponentiation) and the gm_gt_* helpers.
+static inline Fq2 fq2_mul_xi(const Fq2& a) { return Fq2{a.c0 - a.c1, a.c0 + a.c1}; }
+static inline Fq2 fq2_neg(const Fq2& a) { return Fq2{a.c0.neg(), a.c1.neg()}; }
+static inline Fq2 fq2_scale(const Fq2& a, const Fq& s) { return Fq2{a.c0 * s, a.c1 * s}; }
+
+struct Fq6 {
+  Fq2 c0, c1, c2;
+  static Fq6 zero() { return Fq6{Fq2::zero(), Fq2::zero(), Fq2::zero()}; }
+  static Fq6 one() { return Fq6{Fq2::one(), Fq2::zero(), Fq2::zero()}; }
+  bool operator==(const Fq6& o) const { return c0 == o.c0 && c1 == o.c1 && c2 == o.c2; }
+  Fq6 operator+(const Fq6& o) const { return Fq6{c0 + o.c0, c1 + o.c1, c2 + o.c2}; }
+  Fq6 operator-(const Fq6& o) const { return Fq6{c0 - o.c0, c1 - o.c1, c2 - o.c2}; }
+  Fq6 neg() const { return Fq6{fq2_neg(c0), fq2_neg(c1), fq2_neg(c2)}; }
+  Fq6 mul_v() const { return Fq6{fq2_mul_xi(c2), c0, c1}; }
+  Fq6 operator*(const Fq6& o) const {  // Karatsuba: 6 Fq2 products
+    const Fq2 v0 = c0 * o.c0, v1 = c1 * o.c1, v2 = c2 * o.c2;
+    return Fq6{v0 + fq2_mul_xi((c1 + c2) * (o.c1 + o.c2) - v1 - v2), (c0 + c1) * (o.c0 + o.c1) - v0 - v1 + fq2_mul_xi(v2),
+               (c0 + c2) * (o.c0 + o.c2) - v0 - v2 + v1};
+  }
+  Fq6 inv() const {  // callers never invert zero
+    const Fq2 t0 = c0.sqr() - fq2_mul_xi(c1 * c2), t1 = fq2_mul_xi(c2.sqr()) - c0 * c1, t2 = c1.sqr() - c0 * c2;
+    const Fq2 di = (c0 * t0 + fq2_mul_xi(c2 * t1 + c1 * t2)).inv();
+    return Fq6{t0 * di, t1 * di, t2 * di};
+  }
+};
+
+struct Fq12 {
+  Fq6 c0, c1;
+  static Fq12 one() { return Fq12{Fq6::one(), Fq6::zero()}; }
+  static Fq12 from_limbs(const u64* p) {
+    Fq12 r;
+    Fq2* c[6] = {&r.c0.c0, &r.c0.c1, &r.c0.c2, &r.c1.c0, &r.c1.c1, &r.c1.c2};
+    for (int k = 0; k < 6; k++) *c[k] = Fq2::from_limbs(p + 12 * k);
+    return r;
+  }
+  // a Miller partial as the device writes it: the same order, every Fq in the device form
+  static Fq12 from_device(const u64* p) {
+    Fq12 r;
+    Fq2* c[6] = {&r.c0.c0, &r.c0.c1, &r.c0.c2, &r.c1.c0, &r.c1.c1, &r.c1.c2};
+    for (int k = 0; k < 6; k++) *c[k] = fq2_from_device(p + 12 * k);
+    return r;
+  }
+  void to_limbs(u64* p) const {
+    const Fq2* c[6] = {&c0.c0, &c0.c1, &c0.c2, &c1.c0, &c1.c1, &c1.c2};
+    for (int k = 0; k < 6; k++) c[k]->to_limbs(p + 12 * k);
+  }
+  bool operator==(const Fq12& o) const { return c0 == o.c0 && c1 == o.c1; }
+  Fq12 operator*(const Fq12& o) const {  // Karatsuba: 3 Fq6 products
+    const Fq6 aa = c0 * o.c0, bb = c1 * o.c1;
+    return Fq12{aa + bb.mul_v(), (c0 + c1) * (o.c0 + o.c1) - aa - bb};
+  }
+  Fq12 sqr() const {  // complex squaring: 2 Fq6 products
+    const Fq6 ab = c0 * c1;
+    return Fq12{(c0 + c1) * (c0 + c1.mul_v()) - ab - ab.mul_v(), ab + ab};
+  }
+  Fq12 conj() const { return Fq12{c0, c1.neg()}; }  // the q^6 Frobenius; the inverse on the cyclotomic subgroup
+  Fq12 inv() const {
+    const Fq6 di = (c0 * c0 - (c1 * c1).mul_v()).inv();
+    return Fq12{c0 * di, (c1 * di).neg()};
+  }
+  // x -> x^(q^2): Fq2 is fixed, v^j w^i picks up delta^(2 j + i) for delta = xi^((q^2 - 1) / 6), a sixth root of unity in Fq
+  Fq12 frobenius2() const {
+    static const u64 DELTA[6] = {0x2e01fffffffeffffULL, 0xde17d813620a0002ULL, 0xddb3a93be6f89688ULL,
+                                 0xba69c6076a0f77eaULL, 0x5f19672fdf76ce51ULL, 0x0000000000000000ULL};  // canonical
+    static const Fq d1 = Fq::from_canonical(DELTA);
+    static const Fq d2 = d1 * d1, d3 = d2 * d1, d4 = d2 * d2, d5 = d4 * d1;
+    return Fq12{Fq6{c0.c0, fq2_scale(c0.c1, d2), fq2_scale(c0.c2, d4)}, Fq6{fq2_scale(c1.c0, d1), fq2_scale(c1.c1, d3), fq2_scale(c1.c2, d5)}};
+  }
+  Fq12 pow(const u64* e, int n) const {
+    Fq12 acc = one();
+    for (int i = n * 64 - 1; i >= 0; i--) {
+      acc = acc.sqr();
+      if ((e[i / 64] >> (i % 64)) & 1) acc = acc * *this;
+    }
+    return acc;
+  }
+};
+
+// f -> f^((q^12 - 1) / r), THE exponent of this library (README: whether ark-ec 0.4.2 carries the extra factor 3 of the
+// Hayashida-Hayasaka-Teruya hard part is not pinned).  Easy part f^((q^6 - 1)(q^2 + 1)) by conjugate, inverse and Frobenius;
+// hard part a plain square-and-multiply by (q^4 - q^2 + 1) / r (1268 bits).  f = 0 (never a Miller value) gives 0.
+static inline Fq12 gt_final_exponentiation(const Fq12& f) {
+  static const u64 HARD[20] = {0xe516c3f438e3ba79ULL, 0xfa9912aae208ccf1ULL, 0x905ce937335d5b68ULL, 0xc71a2629b0dea236ULL, 0x83774940996754c8ULL,
+                               0x21d160aeb6a1e799ULL, 0x2ed0b283ed237db4ULL, 0x915c97f36c6f1821ULL, 0x67f17fcbde783765ULL, 0x2378b9039096d1b7ULL,
+                               0x7988f8761bdc51dcULL, 0x2076995003fc77a1ULL, 0x827eca0ba621315bULL, 0xe5a72bce8d63cb9fULL, 0xf68f7764c28b6f8aULL,
+                               0x2f230063cf081517ULL, 0x94506632528d6a9aULL, 0xd3cde88eeb996ca3ULL, 0xc0bd38c3195c899eULL, 0x000f686b3d807d01ULL};
+  if (f.c0 == Fq6::zero() && f.c1 == Fq6::zero()) return f;
+  const Fq12 a = f.conj() * f.inv();   // f^(q^6 - 1)
+  const Fq12 b = a.frobenius2() * a;   // ^(q^2 + 1)
+  return b.pow(HARD, 20);
+}
+
 // extended Jacobian (X, Y, ZZ, ZZZ) -> Jacobian, mirrors device xyzz_to_jac
 static inline G1 xyzz_to_jac(const u64* p) {
   Fq X = Fq::from_limbs(p), Y = Fq::from_limbs(p + 6), ZZ = Fq::from_limbs(p + 12), ZZZ = Fq::from_limbs(p + 18);

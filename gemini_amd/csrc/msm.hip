@@ -3118,6 +3118,14 @@ static int hg1_fold_locked(Context* C, HerringG1* H, const uint64_t r[4]) {
   return GM_OK;
 }
 
+// the G1 fold for the PModule prover (pairing.hip): out[i] = in[2i] + s in[2i+1], s at d_s8 (canonical, 8 x u32), on C->stream
+int g1_split_fold_launch(Context* C, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out) {
+  const size_t m = (n + 1) / 2;
+  hipLaunchKernelGGL(k_g1_split_fold, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, C->stream, in, n, d_s8, out);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
 int hg1_fold(Context* C, HerringG1* H, const uint64_t r[4]) {
   std::lock_guard<std::mutex> lk(H->mu);
   return hg1_fold_locked(C, H, r);

@@ -1,7 +1,7 @@
 """Host mirror of herring's sumcheck over a bilinear module (src/herring): the TimeProver of
-src/herring/time_prover.rs:42-137 for the three module instances that are in scope:
-FModule (F x F -> F), G1Module (G1 x F -> G1) and G2Module (F x G2 -> G2).  GT, pairings, PModule / GtModule and
-InnerProductProof are out of scope."""
+src/herring/time_prover.rs:42-137 for the four module instances that are in scope:
+FModule (F x F -> F), G1Module (G1 x F -> G1), G2Module (F x G2 -> G2) and PModule (G1 x G2 -> GT; pairings are
+gemini_amd/pairing.py).  GtModule and InnerProductProof are out of scope."""
 from __future__ import annotations
 
 import ctypes as C
@@ -110,4 +110,52 @@ class G2ModuleTimeProver:
     def free(self):
         if self.handle:
             capi.check(capi.load().gm_hg2_free(C.c_uint64(self.handle)))
+            self.handle = 0
+
+
+class PModuleTimeProver:
+    """TimeProver<PModule>: f = G1 points ((n, 12) / (n, 13) records), g = G2 points ((n, 24) / (n, 25) records); messages are
+    pairs of (72,) GT elements (gemini_amd/pairing.py), b one Miller product over both halves with one final exponentiation.
+    A call after the one that returned None raises GM_ESTATE."""
+
+    def __init__(self, f_points, g_points, twist_mont):
+        capi.ensure_init()
+        fp = capi.u64(f_points)
+        gp = capi.u64(g_points)
+        h = C.c_uint64()
+        capi.check(capi.load().gm_hp_new(capi.ptr(fp), C.c_size_t(fp.shape[1] * 8), C.c_size_t(len(fp)), capi.ptr(gp), C.c_size_t(gp.shape[1] * 8),
+                                         C.c_size_t(len(gp)), capi.ptr(capi.u64(twist_mont).reshape(4)), C.byref(h)))
+        self.handle = h.value
+
+    def next_message(self, verifier_message=None):
+        a = np.empty(72, dtype=np.uint64)
+        b = np.empty(72, dtype=np.uint64)
+        has = C.c_int()
+        ch = None if verifier_message is None else capi.ptr(capi.u64(verifier_message).reshape(4))
+        capi.check(capi.load().gm_hp_round(C.c_uint64(self.handle), ch, capi.ptr(a), capi.ptr(b), C.byref(has)))
+        return (a, b) if has.value else None
+
+    def fold(self, challenge):
+        capi.check(capi.load().gm_hp_fold(C.c_uint64(self.handle), capi.ptr(capi.u64(challenge).reshape(4))))
+
+    def rounds(self) -> int:
+        t = C.c_size_t()
+        capi.check(capi.load().gm_hp_rounds(C.c_uint64(self.handle), C.byref(t), None))
+        return t.value
+
+    def round(self) -> int:
+        r = C.c_size_t()
+        capi.check(capi.load().gm_hp_rounds(C.c_uint64(self.handle), None, C.byref(r)))
+        return r.value
+
+    def final_foldings(self):
+        f0 = np.empty(18, dtype=np.uint64)
+        g0 = np.empty(36, dtype=np.uint64)
+        has = C.c_int()
+        capi.check(capi.load().gm_hp_final(C.c_uint64(self.handle), capi.ptr(f0), capi.ptr(g0), C.byref(has)))
+        return (f0, g0) if has.value else None
+
+    def free(self):
+        if self.handle:
+            capi.check(capi.load().gm_hp_free(C.c_uint64(self.handle)))
             self.handle = 0

@@ -1,0 +1,84 @@
+"""Host mirror of the pairing surface herring uses: `P::multi_pairing` behind PModule::ip (src/herring/module.rs:60-79) and the
+multi-pairings of Vrs::from (src/herring/ipa.rs:215-247).  All arithmetic happens in libgemini_hip.so (gm_pairing_*, gm_gt_*).
+
+Data conventions (numpy uint64): G1 records (n, 12) / (n, 13) as in gemini_amd.msm, G2 records (n, 24) / (n, 25) as in
+gemini_amd.g2msm; a GT element is (72,) limbs = 12 Fq values in Montgomery form, tower order c0.c0.c0, c0.c0.c1, c0.c1.c0, ...,
+c1.c2.c1 of Fq12 = Fq6[w] / (w^2 - v), Fq6 = Fq2[v] / (v^3 - (1 + u)), Fq2 = Fq[u] / (u^2 + 1).  GT is written multiplicatively:
+what herring calls "+" on GT is `gt_mul`.  The value is the reduced ate pairing as ark-ec states it for BLS12 with the exponent
+(q^12 - 1) / r; GtModule and InnerProductProof are out of scope.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import capi
+from .g2msm import G2Bases, _fq_int, _fq_limbs, _records as _g2_records
+
+
+def gt_from_ints(coeffs) -> np.ndarray:
+    """12 canonical integers in tower order -> (72,) limbs"""
+    assert len(coeffs) == 12
+    return np.array([w for c in coeffs for w in _fq_limbs(int(c))], dtype=np.uint64)
+
+
+def gt_to_ints(gt) -> list:
+    """(72,) limbs -> 12 canonical integers in tower order"""
+    g = capi.u64(gt).reshape(12, 6)
+    return [_fq_int(row) for row in g]
+
+
+def gt_one() -> np.ndarray:
+    out = np.empty(72, dtype=np.uint64)
+    capi.check(capi.load().gm_gt_one(capi.ptr(out)))
+    return out
+
+
+def gt_mul(a, b) -> np.ndarray:
+    """a b on the host (no GPU needed)"""
+    out = np.empty(72, dtype=np.uint64)
+    capi.check(capi.load().gm_gt_mul(capi.ptr(capi.u64(a).reshape(72)), capi.ptr(capi.u64(b).reshape(72)), capi.ptr(out)))
+    return out
+
+
+def gt_pow(a, scalar: int) -> np.ndarray:
+    """a^scalar for 0 <= scalar < 2^256 on the host (no GPU needed)"""
+    assert 0 <= scalar < (1 << 256)
+    s = np.array([(scalar >> (64 * k)) & 0xFFFFFFFFFFFFFFFF for k in range(4)], dtype=np.uint64)
+    out = np.empty(72, dtype=np.uint64)
+    capi.check(capi.load().gm_gt_pow(capi.ptr(capi.u64(a).reshape(72)), capi.ptr(s), capi.ptr(out)))
+    return out
+
+
+def gt_final_exp(f) -> np.ndarray:
+    """f^((q^12 - 1) / r) for any Fq12 element, no conjugation: a test and integration aid (gm_gt_final_exp)"""
+    out = np.empty(72, dtype=np.uint64)
+    capi.check(capi.load().gm_gt_final_exp(capi.ptr(capi.u64(f).reshape(72)), capi.ptr(out)))
+    return out
+
+
+def _g1_records(bases) -> np.ndarray:
+    bases = capi.u64(bases)
+    assert bases.ndim == 2 and bases.shape[1] in (12, 13)
+    return bases
+
+
+def multi_pairing(g1_records, g2_records) -> np.ndarray:
+    """prod_i e(P_i, Q_i) over the shorter input (zip); records with an infinity flag or all-zero coordinates contribute 1"""
+    capi.ensure_init()
+    g1 = _g1_records(g1_records)
+    g2 = _g2_records(g2_records)
+    n = min(len(g1), len(g2))
+    out = np.empty(72, dtype=np.uint64)
+    capi.check(capi.load().gm_pairing_multi(capi.ptr(g1), C.c_size_t(g1.shape[1] * 8), capi.ptr(g2), C.c_size_t(g2.shape[1] * 8), C.c_size_t(n),
+                                            capi.ptr(out)))
+    return out
+
+
+def multi_pairing_h(g1_bases, g2_bases: G2Bases, n: int, off1: int = 0, step1: int = 1, off2: int = 0, step2: int = 1) -> np.ndarray:
+    """prod_i e(g1[off1 + step1 i], g2[off2 + step2 i]), i < n, over registered bases (gemini_amd.msm.G1Bases, g2msm.G2Bases)"""
+    out = np.empty(72, dtype=np.uint64)
+    capi.check(capi.load().gm_pairing_multi_h(C.c_uint64(g1_bases.handle), C.c_size_t(off1), C.c_size_t(step1), C.c_uint64(g2_bases.handle),
+                                              C.c_size_t(off2), C.c_size_t(step2), C.c_size_t(n), capi.ptr(out)))
+    return out

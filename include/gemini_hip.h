@@ -30,7 +30,7 @@
  *     different prover handles run concurrently (sumcheck::prove_batch calls next_message on distinct
  *     provers from different rayon threads, src/subprotocols/sumcheck/proof.rs:85; `Prover: Send + Sync`,
  *     prover.rs:30); calls on the SAME prover handle are serialised by a per-handle lock.  MSM calls
- *     (gm_g1_msm*, gm_g2_msm*, herring G1 / G2 rounds) share the device workspaces and are serialised by one library
+ *     (gm_g1_msm*, gm_g2_msm*, gm_pairing_*, herring G1 / G2 / P rounds) share the device workspaces and are serialised by one library
  *     lock held from the staging of host scalars to the result (the reference's MSM calls are
  *     sequential too, src/kzg/time.rs:103-106); the vector entry points (gm_fr_*) are serialised by a
  *     second lock because they stage per-call parameters in one scratch buffer.  Results never depend
@@ -464,8 +464,8 @@ int gm_hg1_free(uint64_t handle);
  * entry points of the same names (n = min(lengths); canonical scalars, a scalar >= 2^255 gives GM_EINVAL; results
  * normalised).  A null pointer or a bad stride (< 192, or not a multiple of 8) gives GM_EINVAL, an unknown handle GM_EHANDLE.
  * A call of more than 2^25 pairs is cut into 2^25-pair MSMs whose results are added on the host.
- * OUT OF SCOPE for G2: fixed-base tables, GLV, the streaming form, batches, sharding; GT, pairings, PModule / GtModule
- * and InnerProductProof. */
+ * OUT OF SCOPE for G2: fixed-base tables, GLV, the streaming form, batches, sharding.  Pairings and the PModule prover are
+ * in the next block; GtModule and InnerProductProof stay out of scope. */
 int gm_g2_msm(const void* bases, size_t base_stride, const uint64_t* scalars, size_t n, uint64_t out_jac[36]);
 int gm_g2_bases_register(const void* bases, size_t base_stride, size_t n, uint64_t* handle);
 int gm_g2_bases_free(uint64_t handle);
@@ -490,6 +490,49 @@ int gm_hg2_fold(uint64_t handle, const uint64_t challenge_mont[4]);
 int gm_hg2_rounds(uint64_t handle, size_t* tot_rounds, size_t* round);
 int gm_hg2_final(uint64_t handle, uint64_t f0_mont[4], uint64_t g0_jac[36], int* has);
 int gm_hg2_free(uint64_t handle);
+
+/* ---- pairings: multi-Miller loop, GT, the herring PModule prover ----------------------------------- */
+/* Replaces `P::multi_pairing` behind PModule::ip (src/herring/module.rs:60-79), i.e. the messages of TimeProver<PModule>
+ * (src/herring/ipa.rs:533-685) and the multi-pairings of Vrs::from (ipa.rs:215-247).  e(P, Q) is the reduced ate pairing as
+ * ark-ec 0.4.2 states it for BLS12: Miller loop over |x| = 0xd201000000010000 (f <- f^2 l_{T,T}(P), and l_{T,Q}(P) on the set
+ * bits below the top one), conjugation because x < 0, then f^((q^12 - 1) / r).  A pair with either point at infinity
+ * contributes 1.  NOT PINNED: whether ark-ec's final_exponentiation carries the extra factor 3 of the
+ * Hayashida-Hayasaka-Teruya hard part; this library raises to exactly (q^12 - 1) / r (README).
+ * GT elements: 12 Fq values, 72 x u64 Montgomery limbs (the limb form of the coordinates of out_jac), in tower order
+ * c0.c0.c0, c0.c0.c1, c0.c1.c0, ..., c1.c2.c1 of Fq12 = Fq6[w] / (w^2 - v), Fq6 = Fq2[v] / (v^3 - (1 + u)),
+ * Fq2 = Fq[u] / (u^2 + 1): the image of ark-ff `Fp12`.  GT is written multiplicatively; herring's "+" on GT is gm_gt_mul.
+ * One lane per pair runs the Miller loop; the product is reduced on the device down to a handful of partials, the host
+ * multiplies those and does the conjugation and ONE final exponentiation per call (a few ms, profiles/pairing.md).
+ * Pairing calls share the MSM lock of the Threading paragraph above.
+ * OUT OF SCOPE: GtModule, InnerProductProof, subgroup checks (points are taken as members of G1 / G2, as ark-ec's
+ * pairing takes them). */
+/* host records as gm_g1_bases_register / gm_g2_bases_register accept them (strides >= 96 / >= 192, multiples of 8; the
+ * infinity flag at byte 96 / 192 when the stride has room); n = 0 gives 1 */
+int gm_pairing_multi(const void* g1, size_t g1_stride, const void* g2, size_t g2_stride, size_t n, uint64_t out_gt[72]);
+/* prod_i e(g1[off1 + step1 i], g2[off2 + step2 i]), i < n, over registered bases (steps >= 1: Vrs::from pairs
+ * step_by(2) against take(size)).  A range outside the bases or a zero step gives GM_EINVAL, an unknown handle GM_EHANDLE. */
+int gm_pairing_multi_h(uint64_t g1_handle, size_t off1, size_t step1, uint64_t g2_handle, size_t off2, size_t step2, size_t n,
+                       uint64_t out_gt[72]);
+/* GT on the host (no GPU needed, like gm_g2_sum): a b, a^s for a canonical 256-bit integer s, 1 */
+int gm_gt_mul(const uint64_t a[72], const uint64_t b[72], uint64_t out_gt[72]);
+int gm_gt_pow(const uint64_t a[72], const uint64_t scalar_canonical[4], uint64_t out_gt[72]);
+int gm_gt_one(uint64_t out_gt[72]);
+/* A test and integration aid, not a protocol step: in^((q^12 - 1) / r) for any Fq12 element (no conjugation), the one
+ * host function that holds the exponent.  No GPU needed. */
+int gm_gt_final_exp(const uint64_t in[72], uint64_t out_gt[72]);
+/* PModule (G1 x G2 -> GT, module.rs:60-79) under TimeProver (src/herring/time_prover.rs:55-138): f is a vector of G1
+ * records, g a vector of G2 records.  a = ip(f_e, g_e); b = ip(f_e, g_o) + ip(f_o, g_e) is ONE Miller product over both
+ * halves and ONE final exponentiation.  fold: f'[i] = f[2i] + (r twist) f[2i+1] in G1, g'[i] = g[2i] + r g[2i+1] in G2 (an odd
+ * tail folds against the identity), twist <- twist^2.  rounds = ceil(log2(min(len f, len g))).  gm_hp_round folds by the
+ * challenge first when one is given; the call that folds the last challenge answers has_msg = 0, and any round or fold
+ * after it is GM_ESTATE.  gm_hp_final: f[0] (18 limbs) and g[0] (36 limbs), normalised Jacobian, once the rounds are done. */
+int gm_hp_new(const void* f_g1, size_t g1_stride, size_t nf, const void* g_g2, size_t g2_stride, size_t ng, const uint64_t twist_mont[4],
+              uint64_t* handle);
+int gm_hp_round(uint64_t handle, const uint64_t* challenge_or_null, uint64_t a_gt[72], uint64_t b_gt[72], int* has_msg);
+int gm_hp_fold(uint64_t handle, const uint64_t challenge_mont[4]);
+int gm_hp_rounds(uint64_t handle, size_t* tot_rounds, size_t* round);
+int gm_hp_final(uint64_t handle, uint64_t f0_jac[18], uint64_t g0_jac[36], int* has);
+int gm_hp_free(uint64_t handle);
 
 /* ---- Fiat-Shamir transcript (host; no GPU needed) ------------------------------------------------ */
 /* merlin::Transcript::new(label) (merlin 3.0.0, Cargo.lock:606-608); the prover uses

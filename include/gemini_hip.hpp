@@ -521,6 +521,83 @@ class HerringG2 {
   uint64_t h_ = 0;
 };
 
+// ---- pairings: `P::multi_pairing` behind PModule::ip (src/herring/module.rs:60-79) and TimeProver<PModule> ----------------------
+using Gt = std::array<uint64_t, 72>;  // 12 Fq in tower order c0.c0.c0, c0.c0.c1, ..., c1.c2.c1 (ark-ff Fp12); multiplicative
+
+inline Gt gt_one() {
+  Gt r;
+  check(gm_gt_one(r.data()));
+  return r;
+}
+inline Gt gt_mul(const Gt& a, const Gt& b) {  // herring's "+" on GT
+  Gt r;
+  check(gm_gt_mul(a.data(), b.data(), r.data()));
+  return r;
+}
+inline Gt gt_pow(const Gt& a, const BigInt& scalar) {
+  Gt r;
+  check(gm_gt_pow(a.data(), scalar.data(), r.data()));
+  return r;
+}
+// prod_i e(g1[i], g2[i]) over the shorter input (zip); a pair with a point at infinity contributes 1
+inline Gt multi_pairing(const std::vector<G1Affine>& g1, const std::vector<G2Affine>& g2) {
+  Gt r;
+  check(gm_pairing_multi(g1.data(), sizeof(G1Affine), g2.data(), sizeof(G2Affine), g1.size() < g2.size() ? g1.size() : g2.size(), r.data()));
+  return r;
+}
+// the same over registered bases (handles of gm_g1_bases_register / gm::G2Bases): g1[off1 + step1 i] against g2[off2 + step2 i], i < n
+inline Gt multi_pairing(uint64_t g1_handle, size_t off1, size_t step1, const G2Bases& g2, size_t off2, size_t step2, size_t n) {
+  Gt r;
+  check(gm_pairing_multi_h(g1_handle, off1, step1, g2.handle(), off2, step2, n, r.data()));
+  return r;
+}
+
+struct GtRoundMsg {
+  Gt a, b;
+};
+// TimeProver<PModule> (src/herring/time_prover.rs:55-138, module.rs:60-79): f in G1, g in G2, messages in GT
+class HerringP {
+ public:
+  HerringP(const std::vector<G1Affine>& f, const std::vector<G2Affine>& g, const Fr& twist) {
+    check(gm_hp_new(f.data(), sizeof(G1Affine), f.size(), g.data(), sizeof(G2Affine), g.size(), twist.data(), &h_));
+  }
+  HerringP(HerringP&& o) noexcept : h_(o.h_) { o.h_ = 0; }
+  ~HerringP() {
+    if (h_) gm_hp_free(h_);
+  }
+  HerringP(const HerringP&) = delete;
+  HerringP& operator=(const HerringP&) = delete;
+  std::optional<GtRoundMsg> next_message(const std::optional<Fr>& verifier_message) {
+    GtRoundMsg m;
+    int has = 0;
+    check(gm_hp_round(h_, verifier_message ? verifier_message->data() : nullptr, m.a.data(), m.b.data(), &has));
+    if (!has) return std::nullopt;
+    return m;
+  }
+  void fold(const Fr& challenge) { check(gm_hp_fold(h_, challenge.data())); }
+  size_t rounds() const {
+    size_t t = 0;
+    check(gm_hp_rounds(h_, &t, nullptr));
+    return t;
+  }
+  size_t round() const {
+    size_t r = 0;
+    check(gm_hp_rounds(h_, nullptr, &r));
+    return r;
+  }
+  std::optional<std::pair<G1Projective, G2Projective>> final_foldings() const {
+    std::pair<G1Projective, G2Projective> ff;
+    int has = 0;
+    check(gm_hp_final(h_, ff.first.data(), ff.second.data(), &has));
+    if (!has) return std::nullopt;
+    return ff;
+  }
+  uint64_t handle() const { return h_; }
+
+ private:
+  uint64_t h_ = 0;
+};
+
 // merlin::Transcript + GeminiTranscript, src/transcript.rs
 class Transcript {
  public:
