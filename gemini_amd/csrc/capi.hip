@@ -247,7 +247,6 @@ uint64_t put_prover(std::unique_ptr<Sumcheck> p) {
 }
 
 // implemented in msm.hip / fr.hip
-int bases_from_host(Context* C, const void* bases, size_t stride, size_t n, std::unique_ptr<Bases>& out);
 int fixed_base_generate(Context* C, const uint64_t base_affine[12], const void* d_scalars, int mont, size_t n,
                         std::unique_ptr<Bases>& out);
 int bases_precompute(Context* C, Bases* b, int c);
@@ -255,12 +254,6 @@ void bases_free_tables(Bases* b);
 int bases_export(Context* C, const Bases* b, size_t offset, size_t n, void* out96);
 int bases_build_phi(Context* C, Bases* b);
 int sc_set_herring(Sumcheck* S, int on);
-int hg1_create(Context* C, const void* f_bases, size_t stride, size_t nf, const uint64_t* g_mont, size_t ng, const uint64_t twist[4],
-               uint64_t* handle);
-void hg1_destroy(Context* C, HerringG1* H);
-int hg1_fold(Context* C, HerringG1* H, const uint64_t r[4]);
-int hg1_round(Context* C, HerringG1* H, const uint64_t* challenge, uint64_t a_jac[18], uint64_t b_jac[18], int* has_msg);
-int hg1_final(Context* C, HerringG1* H, uint64_t f0_jac[18], uint64_t g0[4], int* has);
 int sc_create(Context* C, const void* f_src, size_t nf, const void* g_src, size_t ng, bool src_is_device,
               const uint64_t twist[4], uint64_t* handle, bool borrow = false);
 void sc_destroy(Sumcheck* S);
@@ -277,7 +270,6 @@ int sp_fold(Context* C, SpaceProver* S, const uint64_t challenge[4]);
 int sp_round(Context* C, SpaceProver* S, const uint64_t* challenge, uint64_t a[4], uint64_t b[4], int* has_msg);
 int sp_final(Context* C, SpaceProver* S, uint64_t f0[4], uint64_t g0[4], int* has);
 int sp_to_time(Context* C, SpaceProver* S, uint64_t* time_handle);
-int fr_stride_raw(Context* C, const uint8_t* in, size_t start, size_t stride, size_t count, uint8_t* out);
 int msm_stream_create(Context* C, uint64_t bases_handle, size_t offset, int reversed, size_t chunk, size_t stride, int mont, uint64_t* handle);
 void msm_stream_destroy(Context* C, MsmStream* S);
 int msm_stream_add(Context* C, MsmStream* S, const void* bases_host, const void* scalars_host, size_t n);
@@ -431,9 +423,7 @@ void gm_shutdown(void) {
   C->pool.release_all();
   for (auto& kv : C->provers) sc_destroy(kv.second.get());
   for (auto& kv : C->space_provers) sp_destroy(C, kv.second.get());
-  for (auto& kv : C->herring_g1) hg1_destroy(C, kv.second.get());
-  for (auto& kv : C->herring_g2) hg2_destroy(C, kv.second.get());
-  for (auto& kv : C->herring_p) hp_destroy(kv.second.get());
+  for (auto& kv : C->herring) herring_destroy(C, kv.second.get());
   for (auto& kv : C->g2_bases)
     if (kv.second->d) (void)gm::raw_free(kv.second->d);
   C->partial_bufs.release_all();
@@ -1721,58 +1711,65 @@ int gm_sc_set_herring(uint64_t handle, int on) {
   GM_SC(S, handle, "sc_set_herring");
   return sc_set_herring(S, on);
 }
-static HerringG1* find_hg1(Context* C, uint64_t h) {
+// the module provers (herring.hip): one handle table for the three kinds; a handle of another module is unknown to this one's calls
+static HerringProver* find_herring(Context* C, uint64_t h, HerringModule module) {
   std::lock_guard<std::mutex> lk(C->mu);
-  auto it = C->herring_g1.find(h);
-  return it == C->herring_g1.end() ? nullptr : it->second.get();
+  auto it = C->herring.find(h);
+  return it == C->herring.end() || it->second->module != module ? nullptr : it->second.get();
 }
-#define GM_HG1(var, h, who)                   \
-  HerringG1* var = find_hg1(C, h);            \
-  GM_CHECK(var != nullptr, GM_EHANDLE, who ": unknown herring G1 prover handle %llu", (unsigned long long)(h))
-int gm_hg1_new(const void* f_bases, size_t base_stride, size_t nf, const uint64_t* g_mont, size_t ng, const uint64_t twist_mont[4],
-               uint64_t* handle) {
-  GM_CTX();
-  GM_CHECK(f_bases && g_mont && twist_mont && handle, GM_EINVAL, "hg1_new: null pointer");
-  return hg1_create(C, f_bases, base_stride, nf, g_mont, ng, twist_mont, handle);
-}
-int gm_hg1_round(uint64_t handle, const uint64_t* challenge_or_null, uint64_t a_jac[18], uint64_t b_jac[18], int* has_msg) {
-  GM_CTX();
-  GM_HG1(H, handle, "hg1_round");
-  GM_CHECK(a_jac && b_jac && has_msg, GM_EINVAL, "hg1_round: null pointer");
-  return hg1_round(C, H, challenge_or_null, a_jac, b_jac, has_msg);
-}
-int gm_hg1_fold(uint64_t handle, const uint64_t challenge_mont[4]) {
-  GM_CTX();
-  GM_HG1(H, handle, "hg1_fold");
-  return hg1_fold(C, H, challenge_mont);
-}
-int gm_hg1_rounds(uint64_t handle, size_t* tot_rounds, size_t* round) {
-  GM_CTX();
-  GM_HG1(H, handle, "hg1_rounds");
+#define GM_HERRING(var, h, M, who)                        \
+  HerringProver* var = find_herring(C, h, HERRING_##M);   \
+  GM_CHECK(var != nullptr, GM_EHANDLE, who ": unknown herring " #M " prover handle %llu", (unsigned long long)(h))
+static int herring_rounds(const HerringProver* H, size_t* tot_rounds, size_t* round) {
   if (tot_rounds) *tot_rounds = H->tot_rounds;
   if (round) *round = H->round;
   return GM_OK;
 }
+static int herring_free(Context* C, uint64_t handle, HerringModule module, const char* who) {
+  std::unique_ptr<HerringProver> p;
+  {
+    std::lock_guard<std::mutex> lk(C->mu);
+    auto it = C->herring.find(handle);
+    GM_CHECK(it != C->herring.end() && it->second->module == module, GM_EHANDLE, "%s: unknown handle %llu", who, (unsigned long long)handle);
+    p = std::move(it->second);
+    C->herring.erase(it);
+  }
+  herring_destroy(C, p.get());
+  return GM_OK;
+}
+int gm_hg1_new(const void* f_bases, size_t base_stride, size_t nf, const uint64_t* g_mont, size_t ng, const uint64_t twist_mont[4],
+               uint64_t* handle) {
+  GM_CTX();
+  GM_CHECK(f_bases && g_mont && twist_mont && handle, GM_EINVAL, "hg1_new: null pointer");
+  return herring_create(C, HERRING_G1, f_bases, base_stride, nf, g_mont, 32, ng, twist_mont, handle);
+}
+int gm_hg1_round(uint64_t handle, const uint64_t* challenge_or_null, uint64_t a_jac[18], uint64_t b_jac[18], int* has_msg) {
+  GM_CTX();
+  GM_HERRING(H, handle, G1, "hg1_round");
+  GM_CHECK(a_jac && b_jac && has_msg, GM_EINVAL, "hg1_round: null pointer");
+  return herring_round(C, H, challenge_or_null, a_jac, b_jac, has_msg);
+}
+int gm_hg1_fold(uint64_t handle, const uint64_t challenge_mont[4]) {
+  GM_CTX();
+  GM_HERRING(H, handle, G1, "hg1_fold");
+  return herring_fold(C, H, challenge_mont);
+}
+int gm_hg1_rounds(uint64_t handle, size_t* tot_rounds, size_t* round) {
+  GM_CTX();
+  GM_HERRING(H, handle, G1, "hg1_rounds");
+  return herring_rounds(H, tot_rounds, round);
+}
 int gm_hg1_final(uint64_t handle, uint64_t f0_jac[18], uint64_t g0_mont[4], int* has) {
   GM_CTX();
-  GM_HG1(H, handle, "hg1_final");
-  return hg1_final(C, H, f0_jac, g0_mont, has);
+  GM_HERRING(H, handle, G1, "hg1_final");
+  return herring_final(C, H, f0_jac, g0_mont, has);
 }
 int gm_hg1_free(uint64_t handle) {
   GM_CTX();
-  std::unique_ptr<HerringG1> p;
-  {
-    std::lock_guard<std::mutex> lk(C->mu);
-    auto it = C->herring_g1.find(handle);
-    GM_CHECK(it != C->herring_g1.end(), GM_EHANDLE, "hg1_free: unknown handle %llu", (unsigned long long)handle);
-    p = std::move(it->second);
-    C->herring_g1.erase(it);
-  }
-  hg1_destroy(C, p.get());
-  return GM_OK;
+  return herring_free(C, handle, HERRING_G1, "hg1_free");
 }
 
-// ---- G2: MSM and the herring G2Module prover (g2msm.hip) ---------------------------------------------
+// ---- G2: MSM (g2msm.hip) and the herring G2Module prover ---------------------------------------------
 static G2Bases* find_g2_bases(Context* C, uint64_t h) {
   std::lock_guard<std::mutex> lk(C->mu);
   auto it = C->g2_bases.find(h);
@@ -1865,60 +1862,41 @@ int gm_g2_sum(const uint64_t* points_jac, size_t k, uint64_t out_jac[36]) {
   acc.normalized().to_limbs(out_jac);
   return GM_OK;
 }
-static HerringG2* find_hg2(Context* C, uint64_t h) {
-  std::lock_guard<std::mutex> lk(C->mu);
-  auto it = C->herring_g2.find(h);
-  return it == C->herring_g2.end() ? nullptr : it->second.get();
-}
-#define GM_HG2(var, h, who)                   \
-  HerringG2* var = find_hg2(C, h);            \
-  GM_CHECK(var != nullptr, GM_EHANDLE, who ": unknown herring G2 prover handle %llu", (unsigned long long)(h))
 int gm_hg2_new(const uint64_t* f_mont, size_t nf, const void* g_bases, size_t base_stride, size_t ng, const uint64_t twist_mont[4],
                uint64_t* handle) {
   GM_CTX();
   GM_CHECK(f_mont && g_bases && twist_mont && handle, GM_EINVAL, "hg2_new: null pointer");
-  return hg2_create(C, f_mont, nf, g_bases, base_stride, ng, twist_mont, handle);
+  return herring_create(C, HERRING_G2, f_mont, 32, nf, g_bases, base_stride, ng, twist_mont, handle);
 }
 int gm_hg2_round(uint64_t handle, const uint64_t* challenge_or_null, uint64_t a_jac[36], uint64_t b_jac[36], int* has_msg) {
   GM_CTX();
-  GM_HG2(H, handle, "hg2_round");
+  GM_HERRING(H, handle, G2, "hg2_round");
   GM_CHECK(a_jac && b_jac && has_msg, GM_EINVAL, "hg2_round: null pointer");
-  return hg2_round(C, H, challenge_or_null, a_jac, b_jac, has_msg);
+  return herring_round(C, H, challenge_or_null, a_jac, b_jac, has_msg);
 }
 int gm_hg2_fold(uint64_t handle, const uint64_t challenge_mont[4]) {
   GM_CTX();
-  GM_HG2(H, handle, "hg2_fold");
+  GM_HERRING(H, handle, G2, "hg2_fold");
   GM_CHECK(challenge_mont != nullptr, GM_EINVAL, "hg2_fold: null pointer");
-  return hg2_fold(C, H, challenge_mont);
+  return herring_fold(C, H, challenge_mont);
 }
 int gm_hg2_rounds(uint64_t handle, size_t* tot_rounds, size_t* round) {
   GM_CTX();
-  GM_HG2(H, handle, "hg2_rounds");
-  if (tot_rounds) *tot_rounds = H->tot_rounds;
-  if (round) *round = H->round;
-  return GM_OK;
+  GM_HERRING(H, handle, G2, "hg2_rounds");
+  return herring_rounds(H, tot_rounds, round);
 }
 int gm_hg2_final(uint64_t handle, uint64_t f0_mont[4], uint64_t g0_jac[36], int* has) {
   GM_CTX();
-  GM_HG2(H, handle, "hg2_final");
+  GM_HERRING(H, handle, G2, "hg2_final");
   GM_CHECK(f0_mont && g0_jac && has, GM_EINVAL, "hg2_final: null pointer");
-  return hg2_final(C, H, f0_mont, g0_jac, has);
+  return herring_final(C, H, f0_mont, g0_jac, has);
 }
 int gm_hg2_free(uint64_t handle) {
   GM_CTX();
-  std::unique_ptr<HerringG2> p;
-  {
-    std::lock_guard<std::mutex> lk(C->mu);
-    auto it = C->herring_g2.find(handle);
-    GM_CHECK(it != C->herring_g2.end(), GM_EHANDLE, "hg2_free: unknown handle %llu", (unsigned long long)handle);
-    p = std::move(it->second);
-    C->herring_g2.erase(it);
-  }
-  hg2_destroy(C, p.get());
-  return GM_OK;
+  return herring_free(C, handle, HERRING_G2, "hg2_free");
 }
 
-// ---- pairings: multi-Miller loop, GT helpers, the herring PModule prover (pairing.hip) ----------------
+// ---- pairings: multi-Miller loop and GT helpers (pairing.hip), the herring PModule prover ----------------
 int gm_pairing_multi(const void* g1, size_t g1_stride, const void* g2, size_t g2_stride, size_t n, uint64_t out_gt[72]) {
   GM_CTX();
   GM_CHECK(out_gt != nullptr && ((g1 != nullptr && g2 != nullptr) || n == 0), GM_EINVAL, "pairing_multi: null pointer");
@@ -1959,56 +1937,37 @@ int gm_gt_final_exp(const uint64_t in[72], uint64_t out_gt[72]) {
   gmh::gt_final_exponentiation(gmh::Fq12::from_limbs(in)).to_limbs(out_gt);
   return GM_OK;
 }
-static HerringP* find_hp(Context* C, uint64_t h) {
-  std::lock_guard<std::mutex> lk(C->mu);
-  auto it = C->herring_p.find(h);
-  return it == C->herring_p.end() ? nullptr : it->second.get();
-}
-#define GM_HP(var, h, who)                  \
-  HerringP* var = find_hp(C, h);            \
-  GM_CHECK(var != nullptr, GM_EHANDLE, who ": unknown herring P prover handle %llu", (unsigned long long)(h))
 int gm_hp_new(const void* f_g1, size_t g1_stride, size_t nf, const void* g_g2, size_t g2_stride, size_t ng, const uint64_t twist_mont[4], uint64_t* handle) {
   GM_CTX();
   GM_CHECK(f_g1 && g_g2 && twist_mont && handle, GM_EINVAL, "hp_new: null pointer");
-  return hp_create(C, f_g1, g1_stride, nf, g_g2, g2_stride, ng, twist_mont, handle);
+  return herring_create(C, HERRING_P, f_g1, g1_stride, nf, g_g2, g2_stride, ng, twist_mont, handle);
 }
 int gm_hp_round(uint64_t handle, const uint64_t* challenge_or_null, uint64_t a_gt[72], uint64_t b_gt[72], int* has_msg) {
   GM_CTX();
-  GM_HP(H, handle, "hp_round");
+  GM_HERRING(H, handle, P, "hp_round");
   GM_CHECK(a_gt && b_gt && has_msg, GM_EINVAL, "hp_round: null pointer");
-  return hp_round(C, H, challenge_or_null, a_gt, b_gt, has_msg);
+  return herring_round(C, H, challenge_or_null, a_gt, b_gt, has_msg);
 }
 int gm_hp_fold(uint64_t handle, const uint64_t challenge_mont[4]) {
   GM_CTX();
-  GM_HP(H, handle, "hp_fold");
+  GM_HERRING(H, handle, P, "hp_fold");
   GM_CHECK(challenge_mont != nullptr, GM_EINVAL, "hp_fold: null pointer");
-  return hp_fold(C, H, challenge_mont);
+  return herring_fold(C, H, challenge_mont);
 }
 int gm_hp_rounds(uint64_t handle, size_t* tot_rounds, size_t* round) {
   GM_CTX();
-  GM_HP(H, handle, "hp_rounds");
-  if (tot_rounds) *tot_rounds = H->tot_rounds;
-  if (round) *round = H->round;
-  return GM_OK;
+  GM_HERRING(H, handle, P, "hp_rounds");
+  return herring_rounds(H, tot_rounds, round);
 }
 int gm_hp_final(uint64_t handle, uint64_t f0_jac[18], uint64_t g0_jac[36], int* has) {
   GM_CTX();
-  GM_HP(H, handle, "hp_final");
+  GM_HERRING(H, handle, P, "hp_final");
   GM_CHECK(f0_jac && g0_jac && has, GM_EINVAL, "hp_final: null pointer");
-  return hp_final(C, H, f0_jac, g0_jac, has);
+  return herring_final(C, H, f0_jac, g0_jac, has);
 }
 int gm_hp_free(uint64_t handle) {
   GM_CTX();
-  std::unique_ptr<HerringP> p;
-  {
-    std::lock_guard<std::mutex> lk(C->mu);
-    auto it = C->herring_p.find(handle);
-    GM_CHECK(it != C->herring_p.end(), GM_EHANDLE, "hp_free: unknown handle %llu", (unsigned long long)handle);
-    p = std::move(it->second);
-    C->herring_p.erase(it);
-  }
-  hp_destroy(p.get());
-  return GM_OK;
+  return herring_free(C, handle, HERRING_P, "hp_free");
 }
 
 // ---- space prover --------------------------------------------------------------------------------

@@ -16,6 +16,10 @@
 
 #include "../../include/gemini_hip.h"
 
+namespace gmh {
+struct Fq12;  // host_field.hpp
+}
+
 namespace gm {
 
 void set_error(const char* fmt, ...);
@@ -146,17 +150,21 @@ struct SpaceProver {
   std::mutex mu;
 };
 
-// herring TimeProver over G1Module (Lhs = G1, Rhs = F, Target = G1): src/herring/module.rs:81-102
-struct HerringG1 {
-  uint8_t* f[2] = {nullptr, nullptr};  // affine points, 96 B each
-  uint8_t* g[2] = {nullptr, nullptr};  // Fr
-  size_t fcap[2] = {0, 0}, gcap[2] = {0, 0};
+// herring TimeProver over a bilinear module (src/herring/time_prover.rs:42-137; herring.hip): f is the Lhs vector, g the Rhs vector,
+// each an Fr vector (32 B, a block of the vector pool), affine G1 points (96 B) or affine G2 points (192 B)
+enum HerringModule { HERRING_G1 = 0, HERRING_G2, HERRING_P };  // G1 x F -> G1, F x G2 -> G2, G1 x G2 -> GT (module.rs:60-125)
+struct HerringProver {
+  HerringModule module = HERRING_G1;
+  uint8_t* f[2] = {nullptr, nullptr};
+  uint8_t* g[2] = {nullptr, nullptr};
+  size_t fcap[2] = {0, 0}, gcap[2] = {0, 0};  // pooled allocation sizes (Fr sides)
   int cur = 0;
   size_t nf = 0, ng = 0;
-  uint64_t twist[4];
+  uint64_t twist[4];  // Montgomery
   size_t round = 0, tot_rounds = 0;
-  uint8_t* tmp = nullptr;  // compacted scalars
+  uint8_t* tmp = nullptr;  // compacted scalars of the module's messages
   size_t tmpcap = 0;
+  bool finished = false;  // PModule: the call that folded the last challenge has answered "no message", every later one is GM_ESTATE
   std::mutex mu;
 };
 
@@ -172,19 +180,6 @@ struct G2Workspace {
   uint64_t* host_out = nullptr;  // pinned: W window sums (48 u64 each) + the scalar-range flag
   size_t host_out_cap = 0;
 };
-// herring TimeProver over G2Module (Lhs = F, Rhs = G2, Target = G2): src/herring/module.rs:104-125
-struct HerringG2 {
-  uint8_t* f[2] = {nullptr, nullptr};  // Fr
-  uint8_t* g[2] = {nullptr, nullptr};  // affine G2 points, 192 B each
-  size_t fcap[2] = {0, 0};
-  int cur = 0;
-  size_t nf = 0, ng = 0;
-  uint64_t twist[4];
-  size_t round = 0, tot_rounds = 0;
-  uint8_t* tmp = nullptr;  // compacted scalars
-  size_t tmpcap = 0;
-  std::mutex mu;
-};
 
 // What a multi-pairing holds (pairing.hip): the two ping-pong levels of Miller partial products (576-byte Fq12 records) and the
 // pinned copy of the last few.  Single-flight under msm_mu
@@ -192,18 +187,6 @@ struct PairingWorkspace {
   DevBuf part[2];
   uint64_t* host_out = nullptr;
 };
-// herring TimeProver over PModule (Lhs = G1, Rhs = G2, Target = GT): src/herring/module.rs:60-79
-struct HerringP {
-  uint8_t* f[2] = {nullptr, nullptr};  // affine G1 points, 96 B each
-  uint8_t* g[2] = {nullptr, nullptr};  // affine G2 points, 192 B each
-  int cur = 0;
-  size_t nf = 0, ng = 0;
-  uint64_t twist[4];
-  size_t round = 0, tot_rounds = 0;
-  bool finished = false;  // the call that folded the last challenge has answered "no message": every later one is GM_ESTATE
-  std::mutex mu;
-};
-
 // ChunkedPippenger / msm_chunks over HOST-resident pairs (src/kzg/msm/stream_pippenger.rs:209-272, src/kzg/space.rs:22-55):
 // the device holds two chunks; chunk i + 1 is copied in while the MSM of chunk i runs (msm.hip: msm_stream_*)
 struct MsmWorkspace;
@@ -319,10 +302,8 @@ struct Context {
   std::unordered_map<uint64_t, std::unique_ptr<Sumcheck>> provers;
   std::unordered_map<uint64_t, std::unique_ptr<SparseMatrix>> matrices;
   std::unordered_map<uint64_t, std::unique_ptr<SpaceProver>> space_provers;
-  std::unordered_map<uint64_t, std::unique_ptr<HerringG1>> herring_g1;
+  std::unordered_map<uint64_t, std::unique_ptr<HerringProver>> herring;
   std::unordered_map<uint64_t, std::unique_ptr<G2Bases>> g2_bases;
-  std::unordered_map<uint64_t, std::unique_ptr<HerringG2>> herring_g2;
-  std::unordered_map<uint64_t, std::unique_ptr<HerringP>> herring_p;
   std::unordered_map<uint64_t, std::unique_ptr<MsmStream>> msm_streams;
   std::unordered_map<uint64_t, std::unique_ptr<IdxVec>> indices;
   MsmWorkspace msm;
@@ -445,26 +426,47 @@ struct MsmSorted {
 };
 int msm_sort_plain(Context* C, MsmWorkspace& ws, hipStream_t st, const void* d_scalars, int mont, size_t n, int c, MsmSorted* out);
 int msm_ceil_log2(size_t n);
+// pair_offsets[j] (optional): call j starts at base pair_offsets[j] (absolute, whatever the step) and walks step from there
+// firsts[j] (optional): call j starts at base firsts[j] instead of `first` (herring: even / odd halves of one array)
+int msm_run_batch_at(Context* C, const Bases* bases, int64_t first, int64_t step, const size_t* pair_offsets, const void* const* d_scalars,
+                     int mont, const size_t* ns, size_t k, bool normalize, uint64_t* out_jac, const int64_t* firsts = nullptr);
+int bases_from_host(Context* C, const void* bases, size_t stride, size_t n, std::unique_ptr<Bases>& out);
+// out[i] = in[2i] + s in[2i+1] over packed affine records (an odd tail folds against the identity), s at d_s8 (canonical, 8 x u32), on C->stream
+int g1_split_fold_launch(Context* C, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out);
+
+// Fr vectors (fr.hip), on C->stream without a wait
+int fr_stride_raw(Context* C, const uint8_t* in, size_t start, size_t stride, size_t count, uint8_t* out);
+int fr_fold_raw(Context* C, const uint8_t* f, size_t n, const uint64_t r[4], uint8_t* out);  // r is read by an asynchronous copy: the caller waits
 
 // G2 engine (g2msm.hip)
 int g2_bases_from_host(Context* C, const void* bases, size_t stride, size_t n, std::unique_ptr<G2Bases>& out);
 int g2_bases_export(Context* C, const G2Bases* b, size_t offset, size_t n, void* out192);
 int g2_msm_run(Context* C, const G2Bases* bases, int64_t first, int64_t step, const void* d_scalars, int mont, size_t n, uint64_t out_jac[36]);
 void g2_workspace_release(G2Workspace& w);
-int hg2_create(Context* C, const uint64_t* f_mont, size_t nf, const void* g_bases, size_t stride, size_t ng, const uint64_t twist[4], uint64_t* handle);
-void hg2_destroy(Context* C, HerringG2* H);
-int hg2_fold(Context* C, HerringG2* H, const uint64_t r[4]);
-int hg2_round(Context* C, HerringG2* H, const uint64_t* challenge, uint64_t a_jac[36], uint64_t b_jac[36], int* has_msg);
-int hg2_final(Context* C, HerringG2* H, uint64_t f0[4], uint64_t g0_jac[36], int* has);
+int g2_split_fold_launch(Context* C, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out);  // as g1_split_fold_launch
 
 // pairings (pairing.hip): GT values are 72 limbs, 12 Fq in tower order, Montgomery
 int pairing_run(Context* C, const uint8_t* d_g1, int64_t first1, int64_t step1, const uint8_t* d_g2, int64_t first2, int64_t step2, size_t n, uint64_t out_gt[72]);
 int pairing_run_host(Context* C, const void* g1, size_t stride1, const void* g2, size_t stride2, size_t n, uint64_t out_gt[72]);
 void pairing_workspace_release(PairingWorkspace& w);
-int hp_create(Context* C, const void* f_g1, size_t stride1, size_t nf, const void* g_g2, size_t stride2, size_t ng, const uint64_t twist[4], uint64_t* handle);
-void hp_destroy(HerringP* H);
-int hp_fold(Context* C, HerringP* H, const uint64_t r[4]);
-int hp_round(Context* C, HerringP* H, const uint64_t* challenge, uint64_t a_gt[72], uint64_t b_gt[72], int* has_msg);
-int hp_final(Context* C, HerringP* H, uint64_t f0_jac[18], uint64_t g0_jac[36], int* has);
+struct PairSpan {  // n pairs (g1[first1 + step1 i], g2[first2 + step2 i]) of packed device records; ranges checked by the caller
+  const uint8_t* g1 = nullptr;
+  const uint8_t* g2 = nullptr;
+  int64_t first1 = 0, step1 = 1, first2 = 0, step2 = 1;
+  size_t n = 0;
+};
+// The Miller product of both spans, NOT conjugated, not exponentiated.  Caller holds the MSM lock.
+int miller_product(Context* C, const PairSpan& s0, const PairSpan& s1, gmh::Fq12* out);
+// Miller product -> GT: conjugation (the loop parameter is negative), then the one final exponentiation
+void pairing_finish(const gmh::Fq12& miller, uint64_t out_gt[72]);
+
+// herring module provers (herring.hip).  f / g are host arrays: Fr vectors in Montgomery form (the stride is ignored) or point
+// records of f_stride / g_stride bytes; messages and final foldings have the module's limb counts (include/gemini_hip.h)
+int herring_create(Context* C, HerringModule module, const void* f, size_t f_stride, size_t nf, const void* g, size_t g_stride, size_t ng,
+                   const uint64_t twist[4], uint64_t* handle);
+void herring_destroy(Context* C, HerringProver* H);
+int herring_fold(Context* C, HerringProver* H, const uint64_t r[4]);
+int herring_round(Context* C, HerringProver* H, const uint64_t* challenge, uint64_t* a, uint64_t* b, int* has_msg);
+int herring_final(Context* C, HerringProver* H, uint64_t* f0, uint64_t* g0, int* has);
 
 }  // namespace gm

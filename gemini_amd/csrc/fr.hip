@@ -1687,8 +1687,7 @@ int fr_fold_raw(Context* C, const uint8_t* f, size_t n, const uint64_t r[4], uin
   const size_t m = (n + 1) / 2;
   if (m) hipLaunchKernelGGL(k_fold, dim3(grid_for(m)), dim3(256), 0, C->stream, f, n, (const uint32_t*)dr, out);
   GM_HIP(hipGetLastError());
-  GM_HIP(hipStreamSynchronize(C->stream));
-  return GM_OK;
+  return GM_OK;  // no wait: `r` is the caller's until the copy has run (herring.hip: fold_locked waits once for both sides)
 }
 
 // ---- vector helper entry points (called from capi.hip) ---------------------------------------

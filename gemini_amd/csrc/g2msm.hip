@@ -1,7 +1,7 @@
-// G2 multi-scalar multiplication and the herring G2Module time prover for gfx950.
+// G2 multi-scalar multiplication and the G2 fold kernel of the herring provers (herring.hip) for gfx950.
 //
 // Replaces `P::G2::msm_unchecked` (Crs::commit_g2 / CrsStream::commit_g2, src/herring/ipa.rs:107-118,185-189; G2Module::ip,
-// src/herring/module.rs:114-124) and TimeProver<G2Module> (src/herring/time_prover.rs:72-137).  Signed-digit bucket method with
+// src/herring/module.rs:114-124) and the split_fold of TimeProver<G2Module> (src/herring/time_prover.rs:72-76).  Signed-digit bucket method with
 // the semantics of VariableBaseMSM::msm_bigint, as the G1 engine of msm.hip:
 //
 //   1. msm_sort_plain   (msm.hip) scalars -> signed c-bit digits -> entries (bucket, sign, pair index) grouped by bucket: the digit
@@ -28,9 +28,6 @@
 #include "host_field.hpp"
 
 namespace gm {
-
-int fr_stride_raw(Context* C, const uint8_t* in, size_t start, size_t stride, size_t count, uint8_t* out);
-int fr_fold_raw(Context* C, const uint8_t* f, size_t n, const uint64_t r[4], uint8_t* out);
 
 // ------------------------------------------------------------------------------------------
 // bases import / export
@@ -358,127 +355,11 @@ int g2_bases_export(Context* C, const G2Bases* b, size_t offset, size_t n, void*
   return e == hipSuccess ? GM_OK : hip_fail(e, "g2 bases download", __FILE__, __LINE__);
 }
 
-// ---- herring TimeProver over G2Module (src/herring/time_prover.rs:42-137, module.rs:104-125) ------
-// The mirror image of hg1_* (msm.hip): here f is the scalar side and takes the twist, g the point side.
-int hg2_create(Context* C, const uint64_t* f_mont, size_t nf, const void* g_bases, size_t stride, size_t ng, const uint64_t twist[4], uint64_t* handle) {
-  GM_CHECK(nf >= 1 && ng >= 1, GM_EINVAL, "herring G2 prover: empty vectors");
-  std::unique_ptr<G2Bases> b;
-  int rc = g2_bases_from_host(C, g_bases, stride, ng, b);
-  if (rc) return rc;
-  auto H = std::make_unique<HerringG2>();
-  H->nf = nf;
-  H->ng = ng;
-  H->g[0] = b->d;  // take ownership of the packed copy
-  b->d = nullptr;
-  auto fail = [&](int code) {  // what has been allocated so far goes back
-    hg2_destroy(C, H.get());
-    return code;
-  };
-  {
-    hipError_t e = dev_malloc((void**)&H->g[1], ((ng + 1) / 2) * G2_AFF_BYTES);
-    if (e != hipSuccess) return fail(hip_fail(e, "dev_malloc(herring G2 fold buffer)", __FILE__, __LINE__));
-  }
-  if ((rc = C->pool.alloc(nf * 32, (void**)&H->f[0], &H->fcap[0]))) return fail(rc);
-  if ((rc = C->pool.alloc(((nf + 1) / 2) * 32, (void**)&H->f[1], &H->fcap[1]))) return fail(rc);
-  if ((rc = C->pool.alloc(2 * ((((nf + 1) / 2) + 1) * 32), (void**)&H->tmp, &H->tmpcap))) return fail(rc);  // f_even, f_odd compacted
-  {
-    hipError_t e = hipMemcpyAsync(H->f[0], f_mont, nf * 32, hipMemcpyHostToDevice, C->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(C->stream);
-    if (e != hipSuccess) return fail(hip_fail(e, "hipMemcpyAsync(herring G2 scalars)", __FILE__, __LINE__));
-  }
-  memcpy(H->twist, twist, 32);
-  H->tot_rounds = (size_t)msm_ceil_log2(nf < ng ? nf : ng);  // Witness::required_rounds: log2(min(len)) (time_prover.rs:36-39)
-  std::lock_guard<std::mutex> lk(C->mu);
-  *handle = C->next_handle++;
-  C->herring_g2[*handle] = std::move(H);
-  return GM_OK;
-}
-
-void hg2_destroy(Context* C, HerringG2* H) {
-  for (int i = 0; i < 2; i++) {
-    if (H->g[i]) (void)gm::raw_free(H->g[i]);
-    if (C && H->f[i]) C->pool.free(H->f[i], H->fcap[i]);
-    H->g[i] = H->f[i] = nullptr;
-  }
-  if (C && H->tmp) C->pool.free(H->tmp, H->tmpcap);
-  H->tmp = nullptr;
-}
-
-static int hg2_fold_locked(Context* C, HerringG2* H, const uint64_t r[4]) {
-  GM_MSM_LOCK(C);  // the folding scalar is staged in the MSM workspace (C->msm.misc)
-  const gmh::Fr rr = gmh::Fr::from_limbs(r), tw = gmh::Fr::from_limbs(H->twist);
-  uint64_t canon[4], rt[4];
-  rr.to_canonical(canon);  // scalar multiplication wants the integer
-  (rr * tw).to_limbs(rt);
-  int rc = C->msm.misc.ensure(64);
-  if (rc) return rc;
-  GM_HIP(hipMemcpyAsync(C->msm.misc.p, canon, 32, hipMemcpyHostToDevice, C->stream));
-  const size_t m = (H->ng + 1) / 2;
-  hipLaunchKernelGGL(k_g2_split_fold, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, C->stream, H->g[H->cur], H->ng, C->msm.misc.as<uint32_t>(),
-                     H->g[H->cur ^ 1]);
-  GM_HIP(hipGetLastError());
-  if ((rc = fr_fold_raw(C, H->f[H->cur], H->nf, rt, H->f[H->cur ^ 1]))) return rc;
-  GM_HIP(hipStreamSynchronize(C->stream));  // `canon` is read by the copy until here
-  H->cur ^= 1;
-  H->ng = m;
-  H->nf = (H->nf + 1) / 2;
-  tw.sqr().to_limbs(H->twist);
-  return GM_OK;
-}
-
-// the G2 fold for the PModule prover (pairing.hip): out[i] = in[2i] + s in[2i+1], s at d_s8 (canonical, 8 x u32), on C->stream
+// the G2 fold of the herring provers (herring.hip): out[i] = in[2i] + s in[2i+1], s at d_s8 (canonical, 8 x u32), on C->stream
 int g2_split_fold_launch(Context* C, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out) {
   const size_t m = (n + 1) / 2;
   hipLaunchKernelGGL(k_g2_split_fold, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, C->stream, in, n, d_s8, out);
   GM_HIP(hipGetLastError());
-  return GM_OK;
-}
-
-int hg2_fold(Context* C, HerringG2* H, const uint64_t r[4]) {
-  std::lock_guard<std::mutex> lk(H->mu);
-  return hg2_fold_locked(C, H, r);
-}
-
-// next_message: a = <f_even, g_even>, b = <f_even, g_odd> + <f_odd, g_even>, each an MSM (module.rs:114-124)
-int hg2_round(Context* C, HerringG2* H, const uint64_t* challenge, uint64_t a_jac[36], uint64_t b_jac[36], int* has_msg) {
-  std::lock_guard<std::mutex> lk(H->mu);
-  GM_CHECK(H->round <= H->tot_rounds, GM_ESTATE, "More rounds than needed.");
-  int rc;
-  if (challenge && (rc = hg2_fold_locked(C, H, challenge))) return rc;
-  if (H->round == H->tot_rounds) {
-    *has_msg = 0;
-    return GM_OK;
-  }
-  G2Bases gb;
-  gb.d = H->g[H->cur];
-  gb.n = H->ng;
-  const size_t fe = (H->nf + 1) / 2, fo = H->nf / 2, ge = (H->ng + 1) / 2, go = H->ng / 2;
-  uint8_t* f_even = H->tmp;
-  uint8_t* f_odd = H->tmp + (fe + 1) * 32;
-  if ((rc = fr_stride_raw(C, H->f[H->cur], 0, 2, fe, f_even))) return rc;
-  if (fo && (rc = fr_stride_raw(C, H->f[H->cur], 1, 2, fo, f_odd))) return rc;
-  uint64_t b1[36], b2[36];
-  if ((rc = g2_msm_run(C, &gb, 0, 2, f_even, 1, std::min(fe, ge), a_jac))) return rc;   // zip: the shorter side ends the product
-  if ((rc = g2_msm_run(C, &gb, 1, 2, f_even, 1, std::min(fe, go), b1))) return rc;
-  if ((rc = g2_msm_run(C, &gb, 0, 2, f_odd, 1, std::min(fo, ge), b2))) return rc;
-  gmh::G2::from_limbs(b1).add(gmh::G2::from_limbs(b2)).normalized().to_limbs(b_jac);
-  H->round += 1;
-  *has_msg = 1;
-  return GM_OK;
-}
-
-int hg2_final(Context* C, HerringG2* H, uint64_t f0[4], uint64_t g0_jac[36], int* has) {
-  std::lock_guard<std::mutex> lk(H->mu);
-  if (H->round != H->tot_rounds) {
-    *has = 0;
-    return GM_OK;
-  }
-  uint64_t aff[24];
-  GM_HIP(hipMemcpyAsync(aff, H->g[H->cur], G2_AFF_BYTES, hipMemcpyDeviceToHost, C->stream));
-  GM_HIP(hipMemcpyAsync(f0, H->f[H->cur], 32, hipMemcpyDeviceToHost, C->stream));
-  GM_HIP(hipStreamSynchronize(C->stream));
-  gmh::g2_affine_to_jac_dev(aff).to_limbs(g0_jac);
-  *has = 1;
   return GM_OK;
 }
 

@@ -1,0 +1,275 @@
+// herring's TimeProver over a bilinear module (src/herring/time_prover.rs:42-137), stated once for G1Module, G2Module and PModule
+// (src/herring/module.rs:60-125).  FModule rides the field sumcheck kernel (fr.hip: sc_set_herring).
+//
+// The prover keeps the Lhs vector f and the Rhs vector g on the device, each in two ping-pong buffers:
+//   fold(r)          f'[i] = f[2i] + (r twist) f[2i+1], g'[i] = g[2i] + r g[2i+1] (an odd tail folds against zero), twist <- twist^2
+//   next_message(c)  an optional fold, then a = ip(f_even, g_even), b = ip(f_even, g_odd) + ip(f_odd, g_even); ip zips, so the
+//                    shorter side ends a product.  After log2(min(len)) messages the answer is "no message"
+//   final_foldings   (f[0], g[0]) once the last round is behind
+// A SIDE says how a vector of its element type is held, folded and read out -- Fr, affine G1, affine G2 -- and a MODULE is two
+// sides and its inner product `ip`: the only per-module code.  The engines (msm.hip, g2msm.hip, pairing.hip) and the fold kernels
+// stay where they are.
+//
+// Locks: the prover's own mutex outermost; the MSM lock in fold (the canonical scalars of the point folds are staged in
+// C->msm.misc) and wherever the engines take it.
+#include <algorithm>
+#include <cstring>
+
+#include "ctx.hpp"
+#include "host_field.hpp"
+
+namespace gm {
+
+// ---- sides --------------------------------------------------------------------------------------------------------------
+struct HerringSide {
+  size_t elem;  // bytes per element
+  // the host vector on the device (point records are packed from `stride` bytes); *cap != 0: a block of the vector pool
+  int (*upload)(Context* C, const void* host, size_t stride, size_t n, uint8_t** d, size_t* cap);
+  int (*alloc)(Context* C, size_t n, uint8_t** d, size_t* cap);
+  void (*release)(Context* C, uint8_t* d, size_t cap);
+  // out[i] = in[2i] + s in[2i+1] on C->stream, no wait: Fr takes s in Montgomery form, the points the canonical copy on the device
+  int (*split_fold)(Context* C, const uint8_t* in, size_t n, const uint64_t s_mont[4], const uint32_t* d_s_canon, uint8_t* out);
+  void (*read0)(const uint64_t* elem, uint64_t* out);  // element 0 as final_foldings returns it: Fr as it is, points as Jacobian
+};
+
+static int fr_alloc(Context* C, size_t n, uint8_t** d, size_t* cap) { return C->pool.alloc(n * 32, (void**)d, cap); }
+static int fr_upload(Context* C, const void* host, size_t, size_t n, uint8_t** d, size_t* cap) {
+  int rc = fr_alloc(C, n, d, cap);
+  if (rc) return rc;
+  GM_HIP(hipMemcpyAsync(*d, host, n * 32, hipMemcpyHostToDevice, C->stream));
+  GM_HIP(hipStreamSynchronize(C->stream));
+  return GM_OK;
+}
+static void fr_release(Context* C, uint8_t* d, size_t cap) { C->pool.free(d, cap); }
+static int fr_split_fold(Context* C, const uint8_t* in, size_t n, const uint64_t s_mont[4], const uint32_t*, uint8_t* out) {
+  return fr_fold_raw(C, in, n, s_mont, out);
+}
+static void fr_read0(const uint64_t* elem, uint64_t* out) { memcpy(out, elem, 32); }
+
+template <size_t ELEM>
+static int point_alloc(Context*, size_t n, uint8_t** d, size_t* cap) {
+  *cap = 0;
+  GM_HIP(dev_malloc((void**)d, n * ELEM));
+  return GM_OK;
+}
+static void point_release(Context*, uint8_t* d, size_t) {
+  if (d) (void)gm::raw_free(d);
+}
+static int g1_upload(Context* C, const void* host, size_t stride, size_t n, uint8_t** d, size_t* cap) {
+  std::unique_ptr<Bases> b;
+  int rc = bases_from_host(C, host, stride, n, b);
+  if (rc) return rc;
+  *d = b->d;  // take ownership of the packed copy
+  *cap = 0;
+  return GM_OK;
+}
+static int g2_upload(Context* C, const void* host, size_t stride, size_t n, uint8_t** d, size_t* cap) {
+  std::unique_ptr<G2Bases> b;
+  int rc = g2_bases_from_host(C, host, stride, n, b);
+  if (rc) return rc;
+  *d = b->d;
+  *cap = 0;
+  return GM_OK;
+}
+static int g1_split_fold(Context* C, const uint8_t* in, size_t n, const uint64_t*, const uint32_t* d_s_canon, uint8_t* out) {
+  return g1_split_fold_launch(C, in, n, d_s_canon, out);
+}
+static int g2_split_fold(Context* C, const uint8_t* in, size_t n, const uint64_t*, const uint32_t* d_s_canon, uint8_t* out) {
+  return g2_split_fold_launch(C, in, n, d_s_canon, out);
+}
+static void g1_read0(const uint64_t* elem, uint64_t* out) { gmh::g1_affine_to_jac_dev(elem).to_limbs(out); }
+static void g2_read0(const uint64_t* elem, uint64_t* out) { gmh::g2_affine_to_jac_dev(elem).to_limbs(out); }
+
+static const HerringSide FR_SIDE = {32, fr_upload, fr_alloc, fr_release, fr_split_fold, fr_read0};
+static const HerringSide G1_SIDE = {96, g1_upload, point_alloc<96>, point_release, g1_split_fold, g1_read0};
+static const HerringSide G2_SIDE = {192, g2_upload, point_alloc<192>, point_release, g2_split_fold, g2_read0};
+
+// ---- modules ------------------------------------------------------------------------------------------------------------
+struct HerringZip {  // lengths of the even / odd halves, and of the three products a message is made of
+  size_t fe, fo, ge, go;
+  size_t ee, eo, oe;
+};
+
+// G1Module::ip is an MSM (module.rs:91-101): three strided MSMs over the same point array, issued as ONE batch (these are small
+// calls -- 2^10 points in the reference's tests -- and run side by side on the small lanes)
+static int g1_message(Context* C, HerringProver* H, const HerringZip& z, uint64_t* a_jac, uint64_t* b_jac) {
+  Bases fb;
+  fb.d = H->f[H->cur];
+  fb.n = H->nf;
+  const uint8_t* g = H->g[H->cur];
+  const size_t slot = (z.ge + 1) * 32;  // bytes per compacted scalar vector inside H->tmp
+  const int64_t firsts[3] = {0, 0, 1};
+  const size_t g_first[3] = {0, 1, 0};
+  const size_t cnts[3] = {z.ee, z.eo, z.oe};
+  const void* sc[3];
+  int rc;
+  for (int j = 0; j < 3; j++) {
+    uint8_t* dst = H->tmp + (size_t)j * slot;
+    if ((rc = fr_stride_raw(C, g, g_first[j], 2, cnts[j], dst))) return rc;
+    sc[j] = dst;
+  }
+  uint64_t res[3 * 18];
+  if ((rc = msm_run_batch_at(C, &fb, 0, 2, nullptr, sc, 1, cnts, 3, true, res, firsts))) return rc;
+  memcpy(a_jac, res, 18 * sizeof(uint64_t));
+  gmh::G1::from_limbs(res + 18).add(gmh::G1::from_limbs(res + 36)).normalized().to_limbs(b_jac);
+  return GM_OK;
+}
+
+// G2Module::ip(f, g) = msm(g, f) (module.rs:114-124)
+static int g2_message(Context* C, HerringProver* H, const HerringZip& z, uint64_t* a_jac, uint64_t* b_jac) {
+  G2Bases gb;
+  gb.d = H->g[H->cur];
+  gb.n = H->ng;
+  uint8_t* f_even = H->tmp;
+  uint8_t* f_odd = H->tmp + (z.fe + 1) * 32;
+  int rc;
+  if ((rc = fr_stride_raw(C, H->f[H->cur], 0, 2, z.fe, f_even))) return rc;
+  if (z.fo && (rc = fr_stride_raw(C, H->f[H->cur], 1, 2, z.fo, f_odd))) return rc;
+  uint64_t b1[36], b2[36];
+  if ((rc = g2_msm_run(C, &gb, 0, 2, f_even, 1, z.ee, a_jac))) return rc;
+  if ((rc = g2_msm_run(C, &gb, 1, 2, f_even, 1, z.eo, b1))) return rc;
+  if ((rc = g2_msm_run(C, &gb, 0, 2, f_odd, 1, z.oe, b2))) return rc;
+  gmh::G2::from_limbs(b1).add(gmh::G2::from_limbs(b2)).normalized().to_limbs(b_jac);
+  return GM_OK;
+}
+
+// PModule::ip is a multi-pairing (module.rs:70-78) and GT is written multiplicatively: b is ONE Miller product over both halves
+// and ONE final exponentiation
+static int p_message(Context* C, HerringProver* H, const HerringZip& z, uint64_t* a_gt, uint64_t* b_gt) {
+  GM_MSM_LOCK(C);
+  PairSpan ee, eo, oe;
+  ee.g1 = eo.g1 = oe.g1 = H->f[H->cur];
+  ee.g2 = eo.g2 = oe.g2 = H->g[H->cur];
+  ee.step1 = ee.step2 = eo.step1 = eo.step2 = oe.step1 = oe.step2 = 2;
+  ee.n = z.ee;
+  eo.first2 = 1;
+  eo.n = z.eo;
+  oe.first1 = 1;
+  oe.n = z.oe;
+  gmh::Fq12 fa, fb;
+  int rc;
+  if ((rc = miller_product(C, ee, PairSpan(), &fa))) return rc;
+  if ((rc = miller_product(C, eo, oe, &fb))) return rc;
+  pairing_finish(fa, a_gt);
+  pairing_finish(fb, b_gt);
+  return GM_OK;
+}
+
+struct HerringModuleDesc {
+  const char* name;
+  const HerringSide *lhs, *rhs;
+  int (*message)(Context* C, HerringProver* H, const HerringZip& z, uint64_t* a, uint64_t* b);
+  // Two differences between the modules are kept as they were found; making them uniform would change behaviour.
+  size_t tmp_slots;   // compacted copies of halves of the Fr side that `message` builds in H->tmp: three for G1, two for G2, none for P
+  bool ends_for_good;  // P only: after the call that answered "no message", round and fold are sequence errors (GM_ESTATE)
+};
+static const HerringModuleDesc MODULES[] = {  // indexed by HerringModule
+    {"G1", &G1_SIDE, &FR_SIDE, g1_message, 3, false},
+    {"G2", &FR_SIDE, &G2_SIDE, g2_message, 2, false},
+    {"P", &G1_SIDE, &G2_SIDE, p_message, 0, true},
+};
+
+// ---- the prover ---------------------------------------------------------------------------------------------------------
+void herring_destroy(Context* C, HerringProver* H) {
+  const HerringModuleDesc& M = MODULES[H->module];
+  for (int i = 0; i < 2; i++) {
+    M.lhs->release(C, H->f[i], H->fcap[i]);
+    M.rhs->release(C, H->g[i], H->gcap[i]);
+    H->f[i] = H->g[i] = nullptr;
+  }
+  C->pool.free(H->tmp, H->tmpcap);
+  H->tmp = nullptr;
+}
+
+int herring_create(Context* C, HerringModule module, const void* f, size_t f_stride, size_t nf, const void* g, size_t g_stride, size_t ng,
+                   const uint64_t twist[4], uint64_t* handle) {
+  const HerringModuleDesc& M = MODULES[module];
+  GM_CHECK(nf >= 1 && ng >= 1, GM_EINVAL, "herring %s prover: empty vectors", M.name);
+  auto H = std::make_unique<HerringProver>();
+  H->module = module;
+  H->nf = nf;
+  H->ng = ng;
+  const size_t fr_len = M.lhs == &FR_SIDE ? nf : ng;  // of the side `message` compacts (no slot: no side)
+  int rc;
+  if ((rc = M.lhs->upload(C, f, f_stride, nf, &H->f[0], &H->fcap[0])) || (rc = M.rhs->upload(C, g, g_stride, ng, &H->g[0], &H->gcap[0])) ||
+      (rc = M.lhs->alloc(C, (nf + 1) / 2, &H->f[1], &H->fcap[1])) || (rc = M.rhs->alloc(C, (ng + 1) / 2, &H->g[1], &H->gcap[1])) ||
+      (rc = C->pool.alloc(M.tmp_slots * (((fr_len + 1) / 2 + 1) * 32), (void**)&H->tmp, &H->tmpcap))) {
+    herring_destroy(C, H.get());  // what has been allocated so far goes back
+    return rc;
+  }
+  memcpy(H->twist, twist, 32);
+  H->tot_rounds = (size_t)msm_ceil_log2(std::min(nf, ng));  // Witness::required_rounds: log2(min(len)) (time_prover.rs:36-39)
+  std::lock_guard<std::mutex> lk(C->mu);
+  *handle = C->next_handle++;
+  C->herring[*handle] = std::move(H);
+  return GM_OK;
+}
+
+// time_prover.rs:82-88: the Lhs folds by r twist, the Rhs by r
+static int fold_locked(Context* C, HerringProver* H, const uint64_t r[4]) {
+  const HerringModuleDesc& M = MODULES[H->module];
+  GM_MSM_LOCK(C);  // the canonical scalars are staged in the MSM workspace (C->msm.misc)
+  const gmh::Fr rr = gmh::Fr::from_limbs(r), tw = gmh::Fr::from_limbs(H->twist), rt = rr * tw;
+  uint64_t mont[2][4], canon[2][4];  // {Lhs, Rhs}; scalar multiplication wants the integers
+  rt.to_limbs(mont[0]);
+  rr.to_limbs(mont[1]);
+  rt.to_canonical(canon[0]);
+  rr.to_canonical(canon[1]);
+  int rc = C->msm.misc.ensure(64);
+  if (rc) return rc;
+  GM_HIP(hipMemcpyAsync(C->msm.misc.p, canon, 64, hipMemcpyHostToDevice, C->stream));
+  if ((rc = M.lhs->split_fold(C, H->f[H->cur], H->nf, mont[0], C->msm.misc.as<uint32_t>(), H->f[H->cur ^ 1]))) return rc;
+  if ((rc = M.rhs->split_fold(C, H->g[H->cur], H->ng, mont[1], C->msm.misc.as<uint32_t>() + 8, H->g[H->cur ^ 1]))) return rc;
+  GM_HIP(hipStreamSynchronize(C->stream));  // `mont` and `canon` are read by the copies until here
+  H->cur ^= 1;
+  H->nf = (H->nf + 1) / 2;
+  H->ng = (H->ng + 1) / 2;
+  tw.sqr().to_limbs(H->twist);
+  return GM_OK;
+}
+
+int herring_fold(Context* C, HerringProver* H, const uint64_t r[4]) {
+  std::lock_guard<std::mutex> lk(H->mu);
+  GM_CHECK(!H->finished, GM_ESTATE, "herring %s prover: fold after the last round", MODULES[H->module].name);
+  return fold_locked(C, H, r);
+}
+
+// time_prover.rs:91-123
+int herring_round(Context* C, HerringProver* H, const uint64_t* challenge, uint64_t* a, uint64_t* b, int* has_msg) {
+  const HerringModuleDesc& M = MODULES[H->module];
+  std::lock_guard<std::mutex> lk(H->mu);
+  GM_CHECK(!H->finished && H->round <= H->tot_rounds, GM_ESTATE, "More rounds than needed.");
+  int rc;
+  if (challenge && (rc = fold_locked(C, H, challenge))) return rc;
+  if (H->round == H->tot_rounds) {
+    H->finished = M.ends_for_good;
+    *has_msg = 0;
+    return GM_OK;
+  }
+  const size_t fe = (H->nf + 1) / 2, fo = H->nf / 2, ge = (H->ng + 1) / 2, go = H->ng / 2;
+  const HerringZip z = {fe, fo, ge, go, std::min(fe, ge), std::min(fe, go), std::min(fo, ge)};  // zip: the shorter side ends the product
+  if ((rc = M.message(C, H, z, a, b))) return rc;
+  H->round += 1;
+  *has_msg = 1;
+  return GM_OK;
+}
+
+// time_prover.rs:135-137
+int herring_final(Context* C, HerringProver* H, uint64_t* f0, uint64_t* g0, int* has) {
+  const HerringModuleDesc& M = MODULES[H->module];
+  std::lock_guard<std::mutex> lk(H->mu);
+  if (H->round != H->tot_rounds) {
+    *has = 0;
+    return GM_OK;
+  }
+  uint64_t ef[24], eg[24];
+  GM_HIP(hipMemcpyAsync(ef, H->f[H->cur], M.lhs->elem, hipMemcpyDeviceToHost, C->stream));
+  GM_HIP(hipMemcpyAsync(eg, H->g[H->cur], M.rhs->elem, hipMemcpyDeviceToHost, C->stream));
+  GM_HIP(hipStreamSynchronize(C->stream));
+  M.lhs->read0(ef, f0);
+  M.rhs->read0(eg, g0);
+  *has = 1;
+  return GM_OK;
+}
+
+}  // namespace gm

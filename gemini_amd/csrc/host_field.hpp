@@ -299,6 +299,15 @@ static inline G1 xyzz_to_jac_dev(const u64* p) {
   r.z = ZZ;
   return r;
 }
+// 96-byte affine record in device form -> Jacobian in ark-ff form (the all-zero record is the identity)
+static inline G1 g1_affine_to_jac_dev(const u64* p) {
+  if (is_zero<12>(p)) return G1::identity();
+  G1 r;
+  r.x = fq_from_device(p);
+  r.y = fq_from_device(p + 6);
+  r.z = Fq::one();
+  return r;
+}
 
 // Fq2 = Fq[u] / (u^2 + 1), c0 + c1 u; memory image c0 | c1 (ark-ff `Fp2`)
 struct Fq2 {

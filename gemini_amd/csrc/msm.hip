@@ -1554,8 +1554,6 @@ constexpr size_t MSM_SMALL_N = (size_t)1 << 17;
 constexpr size_t MSM_SPLIT_MIN_N = (size_t)1 << 17;  // smaller calls are launch-latency bound: one chain of launches beats two
 static int msm_run_one(Context* C, const Bases* bases, int64_t first, int64_t step, const void* d_scalars, int mont, size_t n,
                        bool normalize, uint64_t out_jac[18]);
-static int msm_run_batch_at(Context* C, const Bases* bases, int64_t first, int64_t step, const size_t* pair_offsets, const void* const* d_scalars,
-                            int mont, const size_t* ns, size_t k, bool normalize, uint64_t* out_jac, const int64_t* firsts = nullptr);
 
 // One MSM is an enqueue (every kernel + the async copy of the window bit-planes to pinned memory, no host
 // wait) and a finish (wait for the copy, Horner over the bit positions on the host).  Splitting them lets
@@ -1671,10 +1669,9 @@ int msm_run_batch_offsets(Context* C, const Bases* bases, const size_t* pair_off
                           const size_t* ns, size_t k, bool normalize, uint64_t* out_jac) {
   return msm_run_batch_at(C, bases, 0, step, pair_offsets, d_scalars, mont, ns, k, normalize, out_jac);
 }
-// pair_offsets[j] (optional): call j starts at base pair_offsets[j] (absolute, whatever the step) and walks step from there
-// firsts[j] (optional): call j starts at base firsts[j] instead of `first` (herring: even / odd halves of one array)
-static int msm_run_batch_at(Context* C, const Bases* bases, int64_t first, int64_t step, const size_t* pair_offsets, const void* const* d_scalars,
-                            int mont, const size_t* ns, size_t k, bool normalize, uint64_t* out_jac, const int64_t* firsts) {
+// (pair_offsets / firsts: ctx.hpp)
+int msm_run_batch_at(Context* C, const Bases* bases, int64_t first, int64_t step, const size_t* pair_offsets, const void* const* d_scalars,
+                     int mont, const size_t* ns, size_t k, bool normalize, uint64_t* out_jac, const int64_t* firsts) {
   const size_t CH = (size_t)1 << 26;
   bool pipelined = !C->prof.on;
   for (size_t j = 0; j < k; j++) pipelined = pipelined && ns[j] <= CH;
@@ -2875,10 +2872,6 @@ static int build_fixed_table(Context* C, const uint64_t base_affine[12], uint8_t
   return GM_OK;
 }
 
-// ---- herring TimeProver over G1Module (src/herring/time_prover.rs:42-137, module.rs:81-102) ------
-int fr_stride_raw(Context* C, const uint8_t* in, size_t start, size_t stride, size_t count, uint8_t* out);
-int fr_fold_raw(Context* C, const uint8_t* f, size_t n, const uint64_t r[4], uint8_t* out);
-
 // ------------------------------------------------------------------------------------------
 // ChunkedPippenger / msm_chunks over HOST-resident pairs: bounded device memory
 //
@@ -3052,145 +3045,11 @@ int msm_stream_finalize(Context* C, MsmStream* S, uint64_t out_jac[18], size_t* 
   return rc;
 }
 
-void hg1_destroy(Context* C, HerringG1* H);
-int hg1_create(Context* C, const void* f_bases, size_t stride, size_t nf, const uint64_t* g_mont, size_t ng, const uint64_t twist[4],
-               uint64_t* handle) {
-  GM_CHECK(nf >= 1 && ng >= 1, GM_EINVAL, "herring G1 prover: empty vectors");
-  std::unique_ptr<Bases> b;
-  int rc = bases_from_host(C, f_bases, stride, nf, b);
-  if (rc) return rc;
-  auto H = std::make_unique<HerringG1>();
-  H->nf = nf;
-  H->ng = ng;
-  H->f[0] = b->d;  // take ownership of the packed copy
-  b->d = nullptr;
-  auto fail = [&](int code) {  // what has been allocated so far goes back
-    hg1_destroy(C, H.get());
-    return code;
-  };
-  {
-    hipError_t e = dev_malloc((void**)&H->f[1], ((nf + 1) / 2) * AFF_BYTES);
-    if (e != hipSuccess) return fail(hip_fail(e, "dev_malloc(herring G1 fold buffer)", __FILE__, __LINE__));
-  }
-  if ((rc = C->pool.alloc(ng * 32, (void**)&H->g[0], &H->gcap[0]))) return fail(rc);
-  if ((rc = C->pool.alloc(((ng + 1) / 2) * 32, (void**)&H->g[1], &H->gcap[1]))) return fail(rc);
-  if ((rc = C->pool.alloc(3 * ((((ng + 1) / 2) + 1) * 32), (void**)&H->tmp, &H->tmpcap))) return fail(rc);  // three compacted scalar vectors
-  {
-    hipError_t e = hipMemcpyAsync(H->g[0], g_mont, ng * 32, hipMemcpyHostToDevice, C->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(C->stream);
-    if (e != hipSuccess) return fail(hip_fail(e, "hipMemcpyAsync(herring G1 scalars)", __FILE__, __LINE__));
-  }
-  memcpy(H->twist, twist, 32);
-  size_t mn = nf < ng ? nf : ng;
-  H->tot_rounds = (size_t)ceil_log2_sz(mn);  // Witness::required_rounds: log2(min(len)) (time_prover.rs:36-39)
-  std::lock_guard<std::mutex> lk(C->mu);
-  *handle = C->next_handle++;
-  C->herring_g1[*handle] = std::move(H);
-  return GM_OK;
-}
-
-void hg1_destroy(Context* C, HerringG1* H) {
-  for (int i = 0; i < 2; i++) {
-    if (H->f[i]) (void)gm::raw_free(H->f[i]);
-    if (C) C->pool.free(H->g[i], H->gcap[i]);
-  }
-  if (C) C->pool.free(H->tmp, H->tmpcap);
-}
-
-static int hg1_fold_locked(Context* C, HerringG1* H, const uint64_t r[4]) {
-  GM_MSM_LOCK(C);  // the folding scalar is staged in the MSM workspace (C->msm.misc)
-  gmh::Fr rr = gmh::Fr::from_limbs(r), tw = gmh::Fr::from_limbs(H->twist);
-  gmh::Fr rt = rr * tw;
-  uint64_t canon[4];
-  rt.to_canonical(canon);  // scalar multiplication wants the integer
-  int rc = C->msm.misc.ensure(64);
-  if (rc) return rc;
-  GM_HIP(hipMemcpyAsync(C->msm.misc.p, canon, 32, hipMemcpyHostToDevice, C->stream));
-  const size_t m = (H->nf + 1) / 2;
-  hipLaunchKernelGGL(k_g1_split_fold, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, C->stream, H->f[H->cur], H->nf,
-                     C->msm.misc.as<uint32_t>(), H->f[H->cur ^ 1]);
-  GM_HIP(hipGetLastError());
-  if ((rc = fr_fold_raw(C, H->g[H->cur], H->ng, r, H->g[H->cur ^ 1]))) return rc;
-  H->cur ^= 1;
-  H->nf = m;
-  H->ng = (H->ng + 1) / 2;
-  tw.sqr().to_limbs(H->twist);
-  return GM_OK;
-}
-
-// the G1 fold for the PModule prover (pairing.hip): out[i] = in[2i] + s in[2i+1], s at d_s8 (canonical, 8 x u32), on C->stream
+// the G1 fold of the herring provers (herring.hip): out[i] = in[2i] + s in[2i+1], s at d_s8 (canonical, 8 x u32), on C->stream
 int g1_split_fold_launch(Context* C, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out) {
   const size_t m = (n + 1) / 2;
   hipLaunchKernelGGL(k_g1_split_fold, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, C->stream, in, n, d_s8, out);
   GM_HIP(hipGetLastError());
-  return GM_OK;
-}
-
-int hg1_fold(Context* C, HerringG1* H, const uint64_t r[4]) {
-  std::lock_guard<std::mutex> lk(H->mu);
-  return hg1_fold_locked(C, H, r);
-}
-
-// next_message: a = <f_even, g_even>, b = <f_even, g_odd> + <f_odd, g_even>, each an MSM (module.rs:91-101)
-int hg1_round(Context* C, HerringG1* H, const uint64_t* challenge, uint64_t a_jac[18], uint64_t b_jac[18], int* has_msg) {
-  std::lock_guard<std::mutex> lk(H->mu);
-  GM_CHECK(H->round <= H->tot_rounds, GM_ESTATE, "More rounds than needed.");
-  int rc;
-  if (challenge && (rc = hg1_fold_locked(C, H, challenge))) return rc;
-  if (H->round == H->tot_rounds) {
-    *has_msg = 0;
-    return GM_OK;
-  }
-  Bases fb;
-  fb.d = H->f[H->cur];
-  fb.n = H->nf;
-  const uint8_t* g = H->g[H->cur];
-  const size_t fe = (H->nf + 1) / 2, fo = H->nf / 2, ge = (H->ng + 1) / 2, go = H->ng / 2;
-  // a = <f_even, g_even>, b = <f_even, g_odd> + <f_odd, g_even>: three strided MSMs over the same point array, issued
-  // as ONE batch (these are small calls -- 2^10 points in the reference's tests -- and run side by side on the small lanes)
-  const size_t slot = (ge + 1) * 32;  // bytes per compacted scalar vector inside H->tmp
-  const int64_t firsts[3] = {0, 0, 1};
-  const size_t g_first[3] = {0, 1, 0};
-  const size_t fcount[3] = {fe, fe, fo}, gcount[3] = {ge, go, ge};
-  size_t cnts[3];
-  const void* sc[3];
-  for (int j = 0; j < 3; j++) {
-    cnts[j] = fcount[j] < gcount[j] ? fcount[j] : gcount[j];  // zip
-    uint8_t* dst = H->tmp + (size_t)j * slot;
-    if ((rc = fr_stride_raw(C, g, g_first[j], 2, cnts[j], dst))) return rc;
-    sc[j] = dst;
-  }
-  uint64_t res[3 * 18];
-  if ((rc = msm_run_batch_at(C, &fb, 0, 2, nullptr, sc, 1, cnts, 3, true, res, firsts))) return rc;
-  memcpy(a_jac, res, 18 * sizeof(uint64_t));
-  const uint64_t *b1 = res + 18, *b2 = res + 36;
-  gmh::G1 bsum = gmh::G1::from_limbs(b1).add(gmh::G1::from_limbs(b2)).normalized();
-  bsum.to_limbs(b_jac);
-  H->round += 1;
-  *has_msg = 1;
-  return GM_OK;
-}
-
-int hg1_final(Context* C, HerringG1* H, uint64_t f0_jac[18], uint64_t g0[4], int* has) {
-  std::lock_guard<std::mutex> lk(H->mu);
-  if (H->round != H->tot_rounds) {
-    *has = 0;
-    return GM_OK;
-  }
-  uint64_t aff[12];
-  GM_HIP(hipMemcpyAsync(aff, H->f[H->cur], AFF_BYTES, hipMemcpyDeviceToHost, C->stream));
-  GM_HIP(hipMemcpyAsync(g0, H->g[H->cur], 32, hipMemcpyDeviceToHost, C->stream));
-  GM_HIP(hipStreamSynchronize(C->stream));
-  gmh::G1 p = gmh::G1::identity();
-  bool zero = true;
-  for (int i = 0; i < 12; i++) zero &= aff[i] == 0;
-  if (!zero) {
-    p.x = gmh::fq_from_device(aff);
-    p.y = gmh::fq_from_device(aff + 6);
-    p.z = gmh::Fq::one();
-  }
-  p.to_limbs(f0_jac);
-  *has = 1;
   return GM_OK;
 }
 

@@ -1,4 +1,4 @@
-// The BLS12-381 pairing on the device: multi-Miller loop, GT product reduction, and the herring PModule time prover (gfx950).
+// The BLS12-381 pairing on the device: multi-Miller loop and GT product reduction (gfx950); the herring PModule prover of herring.hip calls them.
 //
 // Replaces `P::multi_pairing` as PModule::ip calls it (src/herring/module.rs:60-79: G1 x G2 -> GT), i.e. the messages of
 // TimeProver<PModule> (src/herring/time_prover.rs:91-123, two such provers per round of InnerProductProof::new,
@@ -32,10 +32,6 @@
 #include "host_field.hpp"
 
 namespace gm {
-
-int bases_from_host(Context* C, const void* bases, size_t stride, size_t n, std::unique_ptr<Bases>& out);
-int g1_split_fold_launch(Context* C, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out);
-int g2_split_fold_launch(Context* C, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out);
 
 constexpr int PAIR_BLOCK = 64;          // pairs per block of k_miller = partials per block of k_gt_reduce: one wave
 constexpr size_t GT_HOST_MAX = 4;       // partials the host multiplies itself
@@ -188,15 +184,8 @@ void pairing_workspace_release(PairingWorkspace& w) {
   w.host_out = nullptr;
 }
 
-struct PairSpan {  // n pairs (g1[first1 + step1 i], g2[first2 + step2 i]) of packed device records; ranges checked by the caller
-  const uint8_t* g1 = nullptr;
-  const uint8_t* g2 = nullptr;
-  int64_t first1 = 0, step1 = 1, first2 = 0, step2 = 1;
-  size_t n = 0;
-};
-
-// The Miller product of both spans, NOT conjugated, not exponentiated.  Caller holds the MSM lock.
-static int miller_product(Context* C, const PairSpan& s0, const PairSpan& s1, gmh::Fq12* out) {
+// The Miller product of both spans (PairSpan: ctx.hpp), NOT conjugated, not exponentiated.  Caller holds the MSM lock.
+int miller_product(Context* C, const PairSpan& s0, const PairSpan& s1, gmh::Fq12* out) {
   const size_t n = s0.n + s1.n;
   *out = gmh::Fq12::one();
   if (n == 0) return GM_OK;
@@ -235,7 +224,7 @@ static int miller_product(Context* C, const PairSpan& s0, const PairSpan& s1, gm
 }
 
 // Miller product -> GT: conjugation (the loop parameter is negative), then the one final exponentiation
-static void pairing_finish(const gmh::Fq12& miller, uint64_t out_gt[72]) { gmh::gt_final_exponentiation(miller.conj()).to_limbs(out_gt); }
+void pairing_finish(const gmh::Fq12& miller, uint64_t out_gt[72]) { gmh::gt_final_exponentiation(miller.conj()).to_limbs(out_gt); }
 
 // prod_i e(g1[first1 + step1 i], g2[first2 + step2 i]) over packed device records
 int pairing_run(Context* C, const uint8_t* d_g1, int64_t first1, int64_t step1, const uint8_t* d_g2, int64_t first2, int64_t step2, size_t n, uint64_t out_gt[72]) {
@@ -265,127 +254,6 @@ int pairing_run_host(Context* C, const void* g1, size_t stride1, const void* g2,
   if (b1 && b1->d) (void)gm::raw_free(b1->d);
   if (b2 && b2->d) (void)gm::raw_free(b2->d);
   return rc;
-}
-
-// ---- herring TimeProver over PModule (src/herring/time_prover.rs:55-138, module.rs:60-79) ------------------------------
-int hp_create(Context* C, const void* f_g1, size_t stride1, size_t nf, const void* g_g2, size_t stride2, size_t ng, const uint64_t twist[4], uint64_t* handle) {
-  GM_CHECK(nf >= 1 && ng >= 1, GM_EINVAL, "herring P prover: empty vectors");
-  std::unique_ptr<Bases> b1;
-  std::unique_ptr<G2Bases> b2;
-  int rc = bases_from_host(C, f_g1, stride1, nf, b1);
-  if (rc) return rc;
-  auto H = std::make_unique<HerringP>();
-  H->f[0] = b1->d;  // take ownership of the packed copies
-  b1->d = nullptr;
-  H->nf = nf;
-  H->ng = ng;
-  auto fail = [&](int code) {  // what has been allocated so far goes back
-    hp_destroy(H.get());
-    return code;
-  };
-  if ((rc = g2_bases_from_host(C, g_g2, stride2, ng, b2))) return fail(rc);
-  H->g[0] = b2->d;
-  b2->d = nullptr;
-  hipError_t e = dev_malloc((void**)&H->f[1], ((nf + 1) / 2) * G1_AFF_BYTES);
-  if (e == hipSuccess) e = dev_malloc((void**)&H->g[1], ((ng + 1) / 2) * G2_AFF_BYTES);
-  if (e != hipSuccess) return fail(hip_fail(e, "dev_malloc(herring P fold buffers)", __FILE__, __LINE__));
-  memcpy(H->twist, twist, 32);
-  H->tot_rounds = (size_t)msm_ceil_log2(nf < ng ? nf : ng);  // Witness::required_rounds: log2(min(len)) (time_prover.rs:36-39)
-  std::lock_guard<std::mutex> lk(C->mu);
-  *handle = C->next_handle++;
-  C->herring_p[*handle] = std::move(H);
-  return GM_OK;
-}
-
-void hp_destroy(HerringP* H) {
-  for (int i = 0; i < 2; i++) {
-    if (H->f[i]) (void)gm::raw_free(H->f[i]);
-    if (H->g[i]) (void)gm::raw_free(H->g[i]);
-    H->f[i] = H->g[i] = nullptr;
-  }
-}
-
-// f'[i] = f[2i] + (r twist) f[2i+1] in G1, g'[i] = g[2i] + r g[2i+1] in G2 (an odd tail folds against the identity), twist <- twist^2:
-// the fold kernels of the G1Module and G2Module provers
-static int hp_fold_locked(Context* C, HerringP* H, const uint64_t r[4]) {
-  GM_MSM_LOCK(C);  // the two folding scalars are staged in the MSM workspace (C->msm.misc)
-  const gmh::Fr rr = gmh::Fr::from_limbs(r), tw = gmh::Fr::from_limbs(H->twist);
-  uint64_t canon[8];  // scalar multiplication wants the integers
-  (rr * tw).to_canonical(canon);
-  rr.to_canonical(canon + 4);
-  int rc = C->msm.misc.ensure(64);
-  if (rc) return rc;
-  GM_HIP(hipMemcpyAsync(C->msm.misc.p, canon, 64, hipMemcpyHostToDevice, C->stream));
-  if ((rc = g1_split_fold_launch(C, H->f[H->cur], H->nf, C->msm.misc.as<uint32_t>(), H->f[H->cur ^ 1]))) return rc;
-  if ((rc = g2_split_fold_launch(C, H->g[H->cur], H->ng, C->msm.misc.as<uint32_t>() + 8, H->g[H->cur ^ 1]))) return rc;
-  GM_HIP(hipStreamSynchronize(C->stream));  // `canon` is read by the copy until here
-  H->cur ^= 1;
-  H->nf = (H->nf + 1) / 2;
-  H->ng = (H->ng + 1) / 2;
-  tw.sqr().to_limbs(H->twist);
-  return GM_OK;
-}
-
-int hp_fold(Context* C, HerringP* H, const uint64_t r[4]) {
-  std::lock_guard<std::mutex> lk(H->mu);
-  GM_CHECK(!H->finished, GM_ESTATE, "herring P prover: fold after the last round");
-  return hp_fold_locked(C, H, r);
-}
-
-// next_message: a = ip(f_e, g_e), b = ip(f_e, g_o) + ip(f_o, g_e) with GT written multiplicatively: b is ONE Miller product
-// over both halves and ONE final exponentiation.  The call that folds the last challenge answers has_msg = 0; any call
-// after it is a sequence error.
-int hp_round(Context* C, HerringP* H, const uint64_t* challenge, uint64_t a_gt[72], uint64_t b_gt[72], int* has_msg) {
-  std::lock_guard<std::mutex> lk(H->mu);
-  GM_CHECK(!H->finished && H->round <= H->tot_rounds, GM_ESTATE, "More rounds than needed.");
-  int rc;
-  if (challenge && (rc = hp_fold_locked(C, H, challenge))) return rc;
-  if (H->round == H->tot_rounds) {
-    H->finished = true;
-    *has_msg = 0;
-    return GM_OK;
-  }
-  GM_MSM_LOCK(C);
-  const size_t fe = (H->nf + 1) / 2, fo = H->nf / 2, ge = (H->ng + 1) / 2, go = H->ng / 2;
-  PairSpan ee, eo, oe;  // zip: the shorter side ends the product
-  ee.g1 = eo.g1 = oe.g1 = H->f[H->cur];
-  ee.g2 = eo.g2 = oe.g2 = H->g[H->cur];
-  ee.step1 = ee.step2 = eo.step1 = eo.step2 = oe.step1 = oe.step2 = 2;
-  ee.n = std::min(fe, ge);
-  eo.first2 = 1;
-  eo.n = std::min(fe, go);
-  oe.first1 = 1;
-  oe.n = std::min(fo, ge);
-  gmh::Fq12 fa, fb;
-  if ((rc = miller_product(C, ee, PairSpan(), &fa))) return rc;
-  if ((rc = miller_product(C, eo, oe, &fb))) return rc;
-  pairing_finish(fa, a_gt);
-  pairing_finish(fb, b_gt);
-  H->round += 1;
-  *has_msg = 1;
-  return GM_OK;
-}
-
-int hp_final(Context* C, HerringP* H, uint64_t f0_jac[18], uint64_t g0_jac[36], int* has) {
-  std::lock_guard<std::mutex> lk(H->mu);
-  if (H->round != H->tot_rounds) {
-    *has = 0;
-    return GM_OK;
-  }
-  uint64_t a1[12], a2[24];
-  GM_HIP(hipMemcpyAsync(a1, H->f[H->cur], G1_AFF_BYTES, hipMemcpyDeviceToHost, C->stream));
-  GM_HIP(hipMemcpyAsync(a2, H->g[H->cur], G2_AFF_BYTES, hipMemcpyDeviceToHost, C->stream));
-  GM_HIP(hipStreamSynchronize(C->stream));
-  gmh::G1 p = gmh::G1::identity();
-  if (!gmh::is_zero<12>(a1)) {
-    p.x = gmh::fq_from_device(a1);
-    p.y = gmh::fq_from_device(a1 + 6);
-    p.z = gmh::Fq::one();
-  }
-  p.to_limbs(f0_jac);
-  gmh::g2_affine_to_jac_dev(a2).to_limbs(g0_jac);
-  *has = 1;
-  return GM_OK;
 }
 
 }  // namespace gm

@@ -20,8 +20,54 @@ class FModuleTimeProver(_FieldTimeProver):
         capi.check(capi.load().gm_sc_set_herring(C.c_uint64(self.handle), C.c_int(1)))
 
 
-class G1ModuleTimeProver:
+class _ModuleTimeProver:
+    """what the module provers share; a subclass sets the prefix of its C functions (gm_<prefix>_round, ...) and the limb counts of
+    a message element and of the two final foldings, and creates `self.handle`"""
+
+    _prefix = ""
+    _msg = _final_f = _final_g = 0
+
+    def _call(self, name, *args):
+        capi.check(getattr(capi.load(), f"gm_{self._prefix}_{name}")(C.c_uint64(self.handle), *args))
+
+    def next_message(self, verifier_message=None):
+        a = np.empty(self._msg, dtype=np.uint64)
+        b = np.empty(self._msg, dtype=np.uint64)
+        has = C.c_int()
+        ch = None if verifier_message is None else capi.ptr(capi.u64(verifier_message).reshape(4))
+        self._call("round", ch, capi.ptr(a), capi.ptr(b), C.byref(has))
+        return (a, b) if has.value else None
+
+    def fold(self, challenge):
+        self._call("fold", capi.ptr(capi.u64(challenge).reshape(4)))
+
+    def rounds(self) -> int:
+        t = C.c_size_t()
+        self._call("rounds", C.byref(t), None)
+        return t.value
+
+    def round(self) -> int:
+        r = C.c_size_t()
+        self._call("rounds", None, C.byref(r))
+        return r.value
+
+    def final_foldings(self):
+        f0 = np.empty(self._final_f, dtype=np.uint64)
+        g0 = np.empty(self._final_g, dtype=np.uint64)
+        has = C.c_int()
+        self._call("final", capi.ptr(f0), capi.ptr(g0), C.byref(has))
+        return (f0, g0) if has.value else None
+
+    def free(self):
+        if self.handle:
+            self._call("free")
+            self.handle = 0
+
+
+class G1ModuleTimeProver(_ModuleTimeProver):
     """TimeProver<G1Module>: f = G1 points ((n, 12) affine Montgomery, or (n, 13) Rust records), g = Fr"""
+
+    _prefix, _msg, _final_f, _final_g = "hg1", 18, 18, 4
 
     def __init__(self, f_points, g, twist_mont):
         capi.ensure_init()
@@ -32,43 +78,12 @@ class G1ModuleTimeProver:
                                           capi.ptr(capi.u64(twist_mont).reshape(4)), C.byref(h)))
         self.handle = h.value
 
-    def next_message(self, verifier_message=None):
-        a = np.empty(18, dtype=np.uint64)
-        b = np.empty(18, dtype=np.uint64)
-        has = C.c_int()
-        ch = None if verifier_message is None else capi.ptr(capi.u64(verifier_message).reshape(4))
-        capi.check(capi.load().gm_hg1_round(C.c_uint64(self.handle), ch, capi.ptr(a), capi.ptr(b), C.byref(has)))
-        return (a, b) if has.value else None
 
-    def fold(self, challenge):
-        capi.check(capi.load().gm_hg1_fold(C.c_uint64(self.handle), capi.ptr(capi.u64(challenge).reshape(4))))
-
-    def rounds(self) -> int:
-        t = C.c_size_t()
-        capi.check(capi.load().gm_hg1_rounds(C.c_uint64(self.handle), C.byref(t), None))
-        return t.value
-
-    def round(self) -> int:
-        r = C.c_size_t()
-        capi.check(capi.load().gm_hg1_rounds(C.c_uint64(self.handle), None, C.byref(r)))
-        return r.value
-
-    def final_foldings(self):
-        f0 = np.empty(18, dtype=np.uint64)
-        g0 = np.empty(4, dtype=np.uint64)
-        has = C.c_int()
-        capi.check(capi.load().gm_hg1_final(C.c_uint64(self.handle), capi.ptr(f0), capi.ptr(g0), C.byref(has)))
-        return (f0, g0) if has.value else None
-
-    def free(self):
-        if self.handle:
-            capi.check(capi.load().gm_hg1_free(C.c_uint64(self.handle)))
-            self.handle = 0
-
-
-class G2ModuleTimeProver:
+class G2ModuleTimeProver(_ModuleTimeProver):
     """TimeProver<G2Module>: f = Fr, g = G2 points ((n, 24) affine Montgomery, or (n, 25) Rust records); messages and the final
     g are (36,) normalised Jacobian"""
+
+    _prefix, _msg, _final_f, _final_g = "hg2", 36, 4, 36
 
     def __init__(self, f, g_points, twist_mont):
         capi.ensure_init()
@@ -79,44 +94,13 @@ class G2ModuleTimeProver:
                                           capi.ptr(capi.u64(twist_mont).reshape(4)), C.byref(h)))
         self.handle = h.value
 
-    def next_message(self, verifier_message=None):
-        a = np.empty(36, dtype=np.uint64)
-        b = np.empty(36, dtype=np.uint64)
-        has = C.c_int()
-        ch = None if verifier_message is None else capi.ptr(capi.u64(verifier_message).reshape(4))
-        capi.check(capi.load().gm_hg2_round(C.c_uint64(self.handle), ch, capi.ptr(a), capi.ptr(b), C.byref(has)))
-        return (a, b) if has.value else None
 
-    def fold(self, challenge):
-        capi.check(capi.load().gm_hg2_fold(C.c_uint64(self.handle), capi.ptr(capi.u64(challenge).reshape(4))))
-
-    def rounds(self) -> int:
-        t = C.c_size_t()
-        capi.check(capi.load().gm_hg2_rounds(C.c_uint64(self.handle), C.byref(t), None))
-        return t.value
-
-    def round(self) -> int:
-        r = C.c_size_t()
-        capi.check(capi.load().gm_hg2_rounds(C.c_uint64(self.handle), None, C.byref(r)))
-        return r.value
-
-    def final_foldings(self):
-        f0 = np.empty(4, dtype=np.uint64)
-        g0 = np.empty(36, dtype=np.uint64)
-        has = C.c_int()
-        capi.check(capi.load().gm_hg2_final(C.c_uint64(self.handle), capi.ptr(f0), capi.ptr(g0), C.byref(has)))
-        return (f0, g0) if has.value else None
-
-    def free(self):
-        if self.handle:
-            capi.check(capi.load().gm_hg2_free(C.c_uint64(self.handle)))
-            self.handle = 0
-
-
-class PModuleTimeProver:
+class PModuleTimeProver(_ModuleTimeProver):
     """TimeProver<PModule>: f = G1 points ((n, 12) / (n, 13) records), g = G2 points ((n, 24) / (n, 25) records); messages are
     pairs of (72,) GT elements (gemini_amd/pairing.py), b one Miller product over both halves with one final exponentiation.
     A call after the one that returned None raises GM_ESTATE."""
+
+    _prefix, _msg, _final_f, _final_g = "hp", 72, 18, 36
 
     def __init__(self, f_points, g_points, twist_mont):
         capi.ensure_init()
@@ -126,36 +110,3 @@ class PModuleTimeProver:
         capi.check(capi.load().gm_hp_new(capi.ptr(fp), C.c_size_t(fp.shape[1] * 8), C.c_size_t(len(fp)), capi.ptr(gp), C.c_size_t(gp.shape[1] * 8),
                                          C.c_size_t(len(gp)), capi.ptr(capi.u64(twist_mont).reshape(4)), C.byref(h)))
         self.handle = h.value
-
-    def next_message(self, verifier_message=None):
-        a = np.empty(72, dtype=np.uint64)
-        b = np.empty(72, dtype=np.uint64)
-        has = C.c_int()
-        ch = None if verifier_message is None else capi.ptr(capi.u64(verifier_message).reshape(4))
-        capi.check(capi.load().gm_hp_round(C.c_uint64(self.handle), ch, capi.ptr(a), capi.ptr(b), C.byref(has)))
-        return (a, b) if has.value else None
-
-    def fold(self, challenge):
-        capi.check(capi.load().gm_hp_fold(C.c_uint64(self.handle), capi.ptr(capi.u64(challenge).reshape(4))))
-
-    def rounds(self) -> int:
-        t = C.c_size_t()
-        capi.check(capi.load().gm_hp_rounds(C.c_uint64(self.handle), C.byref(t), None))
-        return t.value
-
-    def round(self) -> int:
-        r = C.c_size_t()
-        capi.check(capi.load().gm_hp_rounds(C.c_uint64(self.handle), None, C.byref(r)))
-        return r.value
-
-    def final_foldings(self):
-        f0 = np.empty(18, dtype=np.uint64)
-        g0 = np.empty(36, dtype=np.uint64)
-        has = C.c_int()
-        capi.check(capi.load().gm_hp_final(C.c_uint64(self.handle), capi.ptr(f0), capi.ptr(g0), C.byref(has)))
-        return (f0, g0) if has.value else None
-
-    def free(self):
-        if self.handle:
-            capi.check(capi.load().gm_hp_free(C.c_uint64(self.handle)))
-            self.handle = 0

@@ -478,40 +478,41 @@ class G2Bases {
 struct G2RoundMsg {
   G2Projective a, b;
 };
-// TimeProver<G2Module> (src/herring/time_prover.rs:42-137, module.rs:104-125): f in Fr, g in G2
-class HerringG2 {
+namespace detail {
+// TimeProver<M> of herring over a bilinear module (src/herring/time_prover.rs:42-137).  T names the module: the vector, message and
+// final-pair types, `create`, and the five C functions behind the other members
+template <class T>
+class HerringModuleProver {
  public:
-  HerringG2(const std::vector<Fr>& f, const std::vector<G2Affine>& g, const Fr& twist) {
-    check(gm_hg2_new(f.empty() ? nullptr : f[0].data(), f.size(), g.data(), sizeof(G2Affine), g.size(), twist.data(), &h_));
+  HerringModuleProver(const typename T::Lhs& f, const typename T::Rhs& g, const Fr& twist) { check(T::create(f, g, twist, &h_)); }
+  HerringModuleProver(HerringModuleProver&& o) noexcept : h_(o.h_) { o.h_ = 0; }
+  ~HerringModuleProver() {
+    if (h_) T::free(h_);
   }
-  HerringG2(HerringG2&& o) noexcept : h_(o.h_) { o.h_ = 0; }
-  ~HerringG2() {
-    if (h_) gm_hg2_free(h_);
-  }
-  HerringG2(const HerringG2&) = delete;
-  HerringG2& operator=(const HerringG2&) = delete;
-  std::optional<G2RoundMsg> next_message(const std::optional<Fr>& verifier_message) {
-    G2RoundMsg m;
+  HerringModuleProver(const HerringModuleProver&) = delete;
+  HerringModuleProver& operator=(const HerringModuleProver&) = delete;
+  std::optional<typename T::Msg> next_message(const std::optional<Fr>& verifier_message) {
+    typename T::Msg m;
     int has = 0;
-    check(gm_hg2_round(h_, verifier_message ? verifier_message->data() : nullptr, m.a.data(), m.b.data(), &has));
+    check(T::round(h_, verifier_message ? verifier_message->data() : nullptr, m.a.data(), m.b.data(), &has));
     if (!has) return std::nullopt;
     return m;
   }
-  void fold(const Fr& challenge) { check(gm_hg2_fold(h_, challenge.data())); }
+  void fold(const Fr& challenge) { check(T::fold(h_, challenge.data())); }
   size_t rounds() const {
     size_t t = 0;
-    check(gm_hg2_rounds(h_, &t, nullptr));
+    check(T::rounds(h_, &t, nullptr));
     return t;
   }
   size_t round() const {
     size_t r = 0;
-    check(gm_hg2_rounds(h_, nullptr, &r));
+    check(T::rounds(h_, nullptr, &r));
     return r;
   }
-  std::optional<std::pair<Fr, G2Projective>> final_foldings() const {
-    std::pair<Fr, G2Projective> ff;
+  std::optional<typename T::Final> final_foldings() const {
+    typename T::Final ff;
     int has = 0;
-    check(gm_hg2_final(h_, ff.first.data(), ff.second.data(), &has));
+    check(T::final_foldings(h_, ff.first.data(), ff.second.data(), &has));
     if (!has) return std::nullopt;
     return ff;
   }
@@ -520,6 +521,23 @@ class HerringG2 {
  private:
   uint64_t h_ = 0;
 };
+// TimeProver<G2Module> (module.rs:104-125): f in Fr, g in G2
+struct HerringG2Module {
+  using Lhs = std::vector<Fr>;
+  using Rhs = std::vector<G2Affine>;
+  using Msg = G2RoundMsg;
+  using Final = std::pair<Fr, G2Projective>;
+  static int create(const Lhs& f, const Rhs& g, const Fr& twist, uint64_t* h) {
+    return gm_hg2_new(f.empty() ? nullptr : f[0].data(), f.size(), g.data(), sizeof(G2Affine), g.size(), twist.data(), h);
+  }
+  static constexpr auto round = gm_hg2_round;
+  static constexpr auto fold = gm_hg2_fold;
+  static constexpr auto rounds = gm_hg2_rounds;
+  static constexpr auto final_foldings = gm_hg2_final;
+  static constexpr auto free = gm_hg2_free;
+};
+}  // namespace detail
+using HerringG2 = detail::HerringModuleProver<detail::HerringG2Module>;
 
 // ---- pairings: `P::multi_pairing` behind PModule::ip (src/herring/module.rs:60-79) and TimeProver<PModule> ----------------------
 using Gt = std::array<uint64_t, 72>;  // 12 Fq in tower order c0.c0.c0, c0.c0.c1, ..., c1.c2.c1 (ark-ff Fp12); multiplicative
@@ -555,48 +573,24 @@ inline Gt multi_pairing(uint64_t g1_handle, size_t off1, size_t step1, const G2B
 struct GtRoundMsg {
   Gt a, b;
 };
-// TimeProver<PModule> (src/herring/time_prover.rs:55-138, module.rs:60-79): f in G1, g in G2, messages in GT
-class HerringP {
- public:
-  HerringP(const std::vector<G1Affine>& f, const std::vector<G2Affine>& g, const Fr& twist) {
-    check(gm_hp_new(f.data(), sizeof(G1Affine), f.size(), g.data(), sizeof(G2Affine), g.size(), twist.data(), &h_));
+namespace detail {
+// TimeProver<PModule> (module.rs:60-79): f in G1, g in G2, messages in GT
+struct HerringPModule {
+  using Lhs = std::vector<G1Affine>;
+  using Rhs = std::vector<G2Affine>;
+  using Msg = GtRoundMsg;
+  using Final = std::pair<G1Projective, G2Projective>;
+  static int create(const Lhs& f, const Rhs& g, const Fr& twist, uint64_t* h) {
+    return gm_hp_new(f.data(), sizeof(G1Affine), f.size(), g.data(), sizeof(G2Affine), g.size(), twist.data(), h);
   }
-  HerringP(HerringP&& o) noexcept : h_(o.h_) { o.h_ = 0; }
-  ~HerringP() {
-    if (h_) gm_hp_free(h_);
-  }
-  HerringP(const HerringP&) = delete;
-  HerringP& operator=(const HerringP&) = delete;
-  std::optional<GtRoundMsg> next_message(const std::optional<Fr>& verifier_message) {
-    GtRoundMsg m;
-    int has = 0;
-    check(gm_hp_round(h_, verifier_message ? verifier_message->data() : nullptr, m.a.data(), m.b.data(), &has));
-    if (!has) return std::nullopt;
-    return m;
-  }
-  void fold(const Fr& challenge) { check(gm_hp_fold(h_, challenge.data())); }
-  size_t rounds() const {
-    size_t t = 0;
-    check(gm_hp_rounds(h_, &t, nullptr));
-    return t;
-  }
-  size_t round() const {
-    size_t r = 0;
-    check(gm_hp_rounds(h_, nullptr, &r));
-    return r;
-  }
-  std::optional<std::pair<G1Projective, G2Projective>> final_foldings() const {
-    std::pair<G1Projective, G2Projective> ff;
-    int has = 0;
-    check(gm_hp_final(h_, ff.first.data(), ff.second.data(), &has));
-    if (!has) return std::nullopt;
-    return ff;
-  }
-  uint64_t handle() const { return h_; }
-
- private:
-  uint64_t h_ = 0;
+  static constexpr auto round = gm_hp_round;
+  static constexpr auto fold = gm_hp_fold;
+  static constexpr auto rounds = gm_hp_rounds;
+  static constexpr auto final_foldings = gm_hp_final;
+  static constexpr auto free = gm_hp_free;
 };
+}  // namespace detail
+using HerringP = detail::HerringModuleProver<detail::HerringPModule>;
 
 // merlin::Transcript + GeminiTranscript, src/transcript.rs
 class Transcript {
