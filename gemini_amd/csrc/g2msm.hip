@@ -33,7 +33,7 @@ namespace gm {
 // bases import / export
 // ------------------------------------------------------------------------------------------
 // staging (stride >= 192, optional infinity flag at byte 192, ark-ff Montgomery form) -> packed 192-byte records in the
-// device form (g1.cuh: a * 2^390 with GM_FQ30)
+// device form (g1.cuh: a * 2^390)
 __global__ void k_g2_pack_bases(const uint8_t* __restrict__ src, size_t stride, size_t n, uint8_t* __restrict__ dst) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(64) void k_g2_merge(const uint32_t* __restrict__ of
 GM_DEV Fq2 fq2_shfl_xor(const Fq2& a, int m) {
   Fq2 r;
 #pragma unroll
-  for (int i = 0; i < FQE_LIMBS; i++) {
+  for (int i = 0; i < Fq::N; i++) {
     r.c0.l[i] = __shfl_xor(a.c0.l[i], m);
     r.c1.l[i] = __shfl_xor(a.c1.l[i], m);
   }

@@ -1276,7 +1276,7 @@ __global__ __launch_bounds__(256) void k_group_sum(GroupSumJobs J) {
 // bases import / generation
 // ------------------------------------------------------------------------------------------
 // staging (stride >= 96, optional infinity flag at byte 96, ark-ff Montgomery form) -> packed 96-byte
-// records in the device form (see g1.cuh: a * 2^390 with GM_FQ30)
+// records in the device form (see g1.cuh: a * 2^390)
 __global__ void k_pack_bases(const uint8_t* __restrict__ src, size_t stride, size_t n, uint8_t* __restrict__ dst) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -1307,22 +1307,13 @@ __global__ void k_phi_bases(const uint8_t* __restrict__ src, size_t n, uint8_t* 
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   G1Affine a = g1_load_affine(src + i * AFF_BYTES);
-  // beta in the device's Montgomery form (a * 2^390 with the radix-2^30 product core, a * 2^384 otherwise)
-#if GM_FQ30
+  // beta in the device's Montgomery form (a * 2^390)
   constexpr uint32_t BETA[12] = {0x9c907181u, 0xef2f7921u, 0xb26574c3u, 0x1bcc91d7u, 0x191c3ebcu, 0x856e7b9au,
                                  0x67fd6ffau, 0xbd16b0d2u, 0xeb0c0550u, 0x18c86532u, 0x6567dd7du, 0x09c6d485u};
-#else
-  constexpr uint32_t BETA[12] = {0x8671f071u, 0xcd03c9e4u, 0x1fcda5d2u, 0x5dab2246u, 0xd3851b95u, 0x587042afu,
-                                 0x01bacb9eu, 0x8eb60ebeu, 0x83d050d2u, 0x03f97d6eu, 0x54638741u, 0x18f02065u};
-#endif
   Fq b;
 #pragma unroll
   for (int k = 0; k < 12; k++) b.l[k] = BETA[k];
-#if GM_FQ30 == 1
-  a.x = fq_mul(a.x, fq30_unpack(b));
-#else
   a.x = fq_mul(a.x, b);
-#endif
   g1_store_affine(dst + i * AFF_BYTES, a);  // the identity (0, 0) maps to itself
 }
 
@@ -1390,7 +1381,7 @@ __global__ __launch_bounds__(256) void k_xyzz_to_affine_batch(const uint8_t* __r
   for (int k = 0; k < m; k++) {
     const uint8_t* rec = in + (i0 + k) * XYZZ_BYTES;
     const FqE zz = fqe_load(rec + 96);
-    if (!fq_is_exact_zero(zz)) run = fq_mul(run, fq_mul(zz, fqe_load(rec + 144)));
+    if (!fq_is_zero(zz)) run = fq_mul(run, fq_mul(zz, fqe_load(rec + 144)));
     pre[k] = run;
   }
   FqE inv = fq_inv(run);
@@ -1398,7 +1389,7 @@ __global__ __launch_bounds__(256) void k_xyzz_to_affine_batch(const uint8_t* __r
     const uint8_t* rec = in + (i0 + k) * XYZZ_BYTES;
     const FqE zz = fqe_load(rec + 96);
     G1Affine a;
-    if (fq_is_exact_zero(zz)) {
+    if (fq_is_zero(zz)) {
       a.x = fqe_zero();
       a.y = fqe_zero();
     } else {

@@ -69,15 +69,15 @@ GM_DEV G1Affine lvl_point(const uint8_t* ptr, bool negate) {
 // The common case (distinct non-zero x) is decided from the x coordinates alone; only equal or zero x
 // coordinates load the y's.  Passes A and C call this with the same inputs, so they agree.
 GM_DEV int lvl_mode(const FqE& x0, const FqE& x1, const uint8_t* p0, bool n0, const uint8_t* p1, bool n1, FqE& d) {
-  d = fq_sub<1>(x1, x0);
-  const bool dz = fq_is_zero_mod(d);
-  if (!dz && !fq_is_exact_zero(x0) && !fq_is_exact_zero(x1)) return 3;
+  d = fq_sub(x1, x0);
+  const bool dz = fq_is_zero(d);
+  if (!dz && !fq_is_zero(x0) && !fq_is_zero(x1)) return 3;
   const G1Affine p = lvl_point(p0, n0), q = lvl_point(p1, n1);
   if (q.is_identity()) return 0;
   if (p.is_identity()) return 1;
   if (!dz) return 3;  // x = 0 on a real point
   const FqE sy = fq_add(p.y, q.y);
-  if (fq_is_zero_mod(sy)) return 2;
+  if (fq_is_zero(sy)) return 2;
   d = sy;
   return 4;
 }
@@ -146,14 +146,14 @@ __global__ __launch_bounds__(256) void k_lvl_c(LvlArgs A) {
         if (mode == 3) {
           FqE y1 = fqe_load(p1 + 48);
           if (n1) y1 = fq_neg_canonical(y1);
-          num = fq_sub<1>(y1, y0);
+          num = fq_sub(y1, y0);
         } else {
           const FqE xx = fq_sqr(x0);
           num = fq_add(fq_dbl(xx), xx);
         }
         const FqE lam = fq_mul(num, inv_d);
-        r.x = fq_sub<1>(fq_sub<1>(fq_sqr(lam), x0), x1);
-        r.y = fq_sub<1>(fq_mul(lam, fq_sub<1>(x0, r.x)), y0);
+        r.x = fq_sub(fq_sub(fq_sqr(lam), x0), x1);
+        r.y = fq_sub(fq_mul(lam, fq_sub(x0, r.x)), y0);
       } else if (mode == 0) {
         r = lvl_point(p0, n0);
       } else if (mode == 1) {

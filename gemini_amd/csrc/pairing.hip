@@ -36,7 +36,7 @@ namespace gm {
 constexpr int PAIR_BLOCK = 64;          // pairs per block of k_miller = partials per block of k_gt_reduce: one wave
 constexpr size_t GT_HOST_MAX = 4;       // partials the host multiplies itself
 constexpr int G1_AFF_BYTES = 96;
-constexpr int GT_WORDS = 12 * FQE_LIMBS;
+constexpr int GT_WORDS = 12 * Fq::N;
 constexpr uint64_t ATE_LOOP = 0xd201000000010000ull;
 
 // ---- f in LDS: limb j of lane l at sh[j * PAIR_BLOCK + l] (conflict-free: a wave reads 64 consecutive words) ----------------
@@ -45,7 +45,7 @@ GM_DEV void gt_lds_store(uint32_t* sh, int lane, const Fq12& a) {
 #pragma unroll
   for (int k = 0; k < 12; k++) {
 #pragma unroll
-    for (int i = 0; i < FQE_LIMBS; i++) sh[(k * FQE_LIMBS + i) * PAIR_BLOCK + lane] = e[k].l[i];
+    for (int i = 0; i < Fq::N; i++) sh[(k * Fq::N + i) * PAIR_BLOCK + lane] = e[k].l[i];
   }
 }
 GM_DEV Fq12 gt_lds_load(const uint32_t* sh, int lane) {
@@ -54,7 +54,7 @@ GM_DEV Fq12 gt_lds_load(const uint32_t* sh, int lane) {
 #pragma unroll
   for (int k = 0; k < 12; k++) {
 #pragma unroll
-    for (int i = 0; i < FQE_LIMBS; i++) e[k].l[i] = sh[(k * FQE_LIMBS + i) * PAIR_BLOCK + lane];
+    for (int i = 0; i < Fq::N; i++) e[k].l[i] = sh[(k * Fq::N + i) * PAIR_BLOCK + lane];
   }
   return a;
 }
@@ -67,50 +67,50 @@ GM_DEV void gt_block_product(uint32_t* sh, int lane) {
   __syncthreads();
 }
 
-// ---- the point of the twist, homogeneous projective (x = X / Z, y = Y / Z); X, Y, Z < 2 ----------------------------------
+// ---- the point of the twist, homogeneous projective (x = X / Z, y = Y / Z) -----------------------------------------------
 struct G2Proj {
   Fq2 x, y, z;
 };
 struct Line {
-  Fq2 l0, l1, l4;  // < 2
+  Fq2 l0, l1, l4;
 };
 // T <- 2 T and the tangent at T evaluated at P: (3 b' Z^2 - Y^2, 3 X^2 x_P, -2 Y Z y_P), b' = 4 xi.  3 M + 6 S + 4 Fq products.
 GM_DEV Line miller_dbl_step(G2Proj& T, const G1Affine& P) {
-  const Fq2 a = fq2_mul_t(T.x, T.y);                                           // X Y
-  const Fq2 b = fq2_tighten(fq2_sqr<2>(T.y));
-  const Fq2 c = fq2_tighten(fq2_sqr<2>(T.z));
-  const Fq2 e = fq2_mul12(fq2_tighten(fq2_mul_xi(c)));                         // 3 b' Z^2 = 12 xi Z^2
-  const Fq2 f = fq2_add(fq2_dbl(e), e);                                        // < 6
-  const Fq2 g = fq2_add(b, f);                                                 // < 8
-  const Fq2 h = fq2_tighten(fq2_sub<2>(fq2_sub<2>(fq2_sqr<4>(fq2_add(T.y, T.z)), b), c));  // 2 Y Z: 4 + 2 + 2
-  const Fq2 j = fq2_tighten(fq2_sqr<2>(T.x));
+  const Fq2 a = fq2_mul(T.x, T.y);                                     // X Y
+  const Fq2 b = fq2_sqr(T.y);
+  const Fq2 c = fq2_sqr(T.z);
+  const Fq2 e = fq2_mul12(fq2_mul_xi(c));                              // 3 b' Z^2 = 12 xi Z^2
+  const Fq2 f = fq2_add(fq2_dbl(e), e);                                // 9 b' Z^2
+  const Fq2 g = fq2_add(b, f);                                         // Y^2 + 9 b' Z^2
+  const Fq2 h = fq2_sub(fq2_sub(fq2_sqr(fq2_add(T.y, T.z)), b), c);    // 2 Y Z
+  const Fq2 j = fq2_sqr(T.x);
   Line l;
-  l.l0 = fq2_tighten(fq2_sub<2>(e, b));
-  l.l1 = fq2_mul_fq(fq2_add(fq2_dbl(j), j), P.x);                              // 6 * 1
+  l.l0 = fq2_sub(e, b);
+  l.l1 = fq2_mul_fq(fq2_add(fq2_dbl(j), j), P.x);
   l.l4 = fq2_mul_fq(fq2_neg(h), P.y);
-  T.x = fq2_tighten(fq2_dbl(fq2_mul(a, fq2_sub<8>(b, f))));                    // 2 X Y (Y^2 - 9 b' Z^2): 2 * 10 -> 12
-  T.y = fq2_tighten(fq2_sub<2>(fq2_sqr<8>(g), fq2_mul12(fq2_tighten(fq2_sqr<2>(e)))));  // (Y^2 + 9 b' Z^2)^2 - 12 (3 b' Z^2)^2
-  T.z = fq2_tighten(fq2_dbl(fq2_dbl(fq2_mul(b, h))));                          // 4 Y^2 (2 Y Z): 24
+  T.x = fq2_dbl(fq2_mul(a, fq2_sub(b, f)));                            // 2 X Y (Y^2 - 9 b' Z^2)
+  T.y = fq2_sub(fq2_sqr(g), fq2_mul12(fq2_sqr(e)));                    // (Y^2 + 9 b' Z^2)^2 - 12 (3 b' Z^2)^2
+  T.z = fq2_dbl(fq2_dbl(fq2_mul(b, h)));                               // 4 Y^2 (2 Y Z)
   return l;
 }
 // T <- T + Q (Q affine, T != +-Q: T is a multiple k Q with 1 < k < r) and the chord evaluated at P:
 // (theta x_Q - lambda y_Q, -theta x_P, lambda y_P).  11 M + 2 S + 4 Fq products.
 GM_DEV Line miller_add_step(G2Proj& T, const G2Affine& Q, const G1Affine& P) {
-  const Fq2 theta = fq2_tighten(fq2_sub<2>(T.y, fq2_mul_t(Q.y, T.z)));
-  const Fq2 lambda = fq2_tighten(fq2_sub<2>(T.x, fq2_mul_t(Q.x, T.z)));
-  const Fq2 c = fq2_tighten(fq2_sqr<2>(theta));
-  const Fq2 d = fq2_tighten(fq2_sqr<2>(lambda));
-  const Fq2 e = fq2_mul_t(lambda, d);
-  const Fq2 f = fq2_mul_t(T.z, c);
-  const Fq2 g = fq2_mul_t(T.x, d);
-  const Fq2 h = fq2_tighten(fq2_sub<4>(fq2_add(e, f), fq2_dbl(g)));           // 4 + 4
+  const Fq2 theta = fq2_sub(T.y, fq2_mul(Q.y, T.z));
+  const Fq2 lambda = fq2_sub(T.x, fq2_mul(Q.x, T.z));
+  const Fq2 c = fq2_sqr(theta);
+  const Fq2 d = fq2_sqr(lambda);
+  const Fq2 e = fq2_mul(lambda, d);
+  const Fq2 f = fq2_mul(T.z, c);
+  const Fq2 g = fq2_mul(T.x, d);
+  const Fq2 h = fq2_sub(fq2_add(e, f), fq2_dbl(g));
   Line l;
-  l.l0 = fq2_tighten(fq2_sub<2>(fq2_mul(theta, Q.x), fq2_mul_t(lambda, Q.y)));
+  l.l0 = fq2_sub(fq2_mul(theta, Q.x), fq2_mul(lambda, Q.y));
   l.l1 = fq2_mul_fq(fq2_neg(theta), P.x);
   l.l4 = fq2_mul_fq(lambda, P.y);
-  T.y = fq2_tighten(fq2_sub<2>(fq2_mul(theta, fq2_sub<2>(g, h)), fq2_mul_t(e, T.y)));  // 2 * 4; 6 + 2
-  T.x = fq2_mul_t(lambda, h);
-  T.z = fq2_mul_t(T.z, e);
+  T.y = fq2_sub(fq2_mul(theta, fq2_sub(g, h)), fq2_mul(e, T.y));
+  T.x = fq2_mul(lambda, h);
+  T.z = fq2_mul(T.z, e);
   return l;
 }
 

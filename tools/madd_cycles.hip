@@ -1,6 +1,6 @@
 // Real issue cycles of the generated group law (g1_madd30_asm / g1_add30_asm, gen_madd30.py) with operands in registers:
 // clock64() around N statements, two waves per SIMD as in k_acc0, against the constant-rate wall clock for the MHz.
-//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -DGM_FQ30=2 tools/madd_cycles.hip -o /tmp/madd_cycles && /tmp/madd_cycles
+//   hipcc -O3 -std=c++17 --offload-arch=gfx950 tools/madd_cycles.hip -o /tmp/madd_cycles && /tmp/madd_cycles
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
