@@ -48,6 +48,9 @@ SYMBOLS = [
     "gm_g1_bases_set_cyclic", "gm_g1_srs_register_cyclic", "gm_ck_len", "gm_ck_msm", "gm_ck_msm_batch", "gm_sumcheck_prove_sharded",
     "gm_snark_shard_key_new", "gm_snark_new_time_sharded",
     "gm_tensorcheck_new_time", "gm_entryproduct_new_time_batch", "gm_plookup_new_time",
+    "gm_crs_new", "gm_crs_free", "gm_crs_len", "gm_crs_commit_g1", "gm_crs_commit_g2", "gm_vrs_from_crs", "gm_vrs_levels", "gm_vrs_get", "gm_vrs_free",
+    "gm_ipa_new", "gm_ipa_rounds", "gm_ipa_messages", "gm_ipa_challenges", "gm_ipa_batch_challenges", "gm_ipa_final_foldings", "gm_ipa_foldings_ff",
+    "gm_ipa_foldings_fg1", "gm_ipa_foldings_fg2", "gm_ipa_free", "gm_ipa_host_times", "gm_ipa_from_fields", "gm_ipa_verify", "gm_transcript_append_gt",
 ]
 
 

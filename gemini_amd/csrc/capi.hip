@@ -426,6 +426,7 @@ void gm_shutdown(void) {
   for (auto& kv : C->herring) herring_destroy(C, kv.second.get());
   for (auto& kv : C->g2_bases)
     if (kv.second->d) (void)gm::raw_free(kv.second->d);
+  for (auto& kv : C->crs) crs_destroy(kv.second.get());
   C->partial_bufs.release_all();
   for (auto& kv : C->indices)
     if (kv.second->d) (void)gm::raw_free(kv.second->d);
@@ -1968,6 +1969,187 @@ int gm_hp_final(uint64_t handle, uint64_t f0_jac[18], uint64_t g0_jac[36], int* 
 int gm_hp_free(uint64_t handle) {
   GM_CTX();
   return herring_free(C, handle, HERRING_P, "hp_free");
+}
+
+// ---- herring's inner-product argument: Crs, Vrs, InnerProductProof (ipa.hip) --------------------------------
+#define GM_IPA_FIND(var, table, h, who, what)  \
+  auto* var = find_in(C, C->table, h);          \
+  GM_CHECK(var != nullptr, GM_EHANDLE, who ": unknown " what " handle %llu", (unsigned long long)(h))
+
+int gm_crs_new(const void* g1, size_t g1_stride, size_t n1, const void* g2, size_t g2_stride, size_t n2, uint64_t* handle) {
+  GM_CTX();
+  GM_CHECK(g1 && g2 && handle, GM_EINVAL, "crs_new: null pointer");
+  GM_CHECK(n1 >= 1 && n2 >= 1, GM_EINVAL, "crs_new: empty CRS");
+  return crs_create(C, g1, g1_stride, n1, g2, g2_stride, n2, handle);
+}
+int gm_crs_free(uint64_t handle) {
+  GM_CTX();
+  std::unique_ptr<Crs> c = take_from(C, C->crs, handle);
+  GM_CHECK(c != nullptr, GM_EHANDLE, "crs_free: unknown handle %llu", (unsigned long long)handle);
+  crs_destroy(c.get());
+  return GM_OK;
+}
+int gm_crs_len(uint64_t handle, size_t* n1, size_t* n2) {
+  GM_CTX();
+  GM_IPA_FIND(c, crs, handle, "crs_len", "CRS");
+  if (n1) *n1 = c->n1;
+  if (n2) *n2 = c->n2;
+  return GM_OK;
+}
+int gm_crs_commit_g1(uint64_t handle, const uint64_t* scalars_mont, size_t n, uint64_t out_jac[18]) {
+  GM_CTX();
+  GM_IPA_FIND(c, crs, handle, "crs_commit_g1", "CRS");
+  GM_CHECK(out_jac && (scalars_mont || n == 0), GM_EINVAL, "crs_commit_g1: null pointer");
+  return crs_commit(C, c, 1, scalars_mont, n, out_jac);
+}
+int gm_crs_commit_g2(uint64_t handle, const uint64_t* scalars_mont, size_t n, uint64_t out_jac[36]) {
+  GM_CTX();
+  GM_IPA_FIND(c, crs, handle, "crs_commit_g2", "CRS");
+  GM_CHECK(out_jac && (scalars_mont || n == 0), GM_EINVAL, "crs_commit_g2: null pointer");
+  return crs_commit(C, c, 2, scalars_mont, n, out_jac);
+}
+int gm_vrs_from_crs(uint64_t crs, uint64_t* vrs) {
+  GM_CTX();
+  GM_IPA_FIND(c, crs, crs, "vrs_from_crs", "CRS");
+  GM_CHECK(vrs != nullptr, GM_EINVAL, "vrs_from_crs: null pointer");
+  auto v = std::make_unique<Vrs>();
+  int rc = vrs_from_crs(C, c, v.get());
+  if (rc) return rc;
+  *vrs = put_in(C, C->vrs, std::move(v));
+  return GM_OK;
+}
+int gm_vrs_levels(uint64_t vrs, size_t* levels) {
+  GM_CTX();
+  GM_IPA_FIND(v, vrs, vrs, "vrs_levels", "Vrs");
+  GM_CHECK(levels != nullptr, GM_EINVAL, "vrs_levels: null pointer");
+  *levels = v->levels;
+  return GM_OK;
+}
+int gm_vrs_get(uint64_t vrs, size_t level, uint64_t vk1_even_odd[144], uint64_t vk2_even_odd[144]) {
+  GM_CTX();
+  GM_IPA_FIND(v, vrs, vrs, "vrs_get", "Vrs");
+  GM_CHECK(vk1_even_odd && vk2_even_odd, GM_EINVAL, "vrs_get: null pointer");
+  GM_CHECK(level < v->levels, GM_EINVAL, "vrs_get: level %zu of %zu", level, v->levels);
+  memcpy(vk1_even_odd, v->vk1.data() + 144 * level, 144 * 8);
+  memcpy(vk2_even_odd, v->vk2.data() + 144 * level, 144 * 8);
+  return GM_OK;
+}
+int gm_vrs_free(uint64_t vrs) {
+  GM_CTX();
+  GM_CHECK(take_from(C, C->vrs, vrs) != nullptr, GM_EHANDLE, "vrs_free: unknown handle %llu", (unsigned long long)vrs);
+  return GM_OK;
+}
+int gm_ipa_new(uint64_t transcript, uint64_t crs, const uint64_t* a_mont, const uint64_t* b_mont, size_t d, uint64_t* proof) {
+  GM_CTX();
+  GM_IPA_FIND(c, crs, crs, "ipa_new", "CRS");
+  GM_CHECK(a_mont && b_mont && proof, GM_EINVAL, "ipa_new: null pointer");
+  auto p = std::make_unique<IpaProof>();
+  int rc = ipa_prove(C, transcript, c, a_mont, b_mont, d, p.get());
+  if (rc) return rc;
+  *proof = put_in(C, C->ipa, std::move(p));
+  return GM_OK;
+}
+int gm_ipa_from_fields(size_t rounds, const uint64_t* messages, const uint64_t* challenges, const uint64_t* batch_challenges, const uint64_t* final_lhs_jac,
+                       const uint64_t* final_rhs_jac, const uint64_t foldings_ff[8], const uint64_t foldings_fg1[22], const uint64_t foldings_fg2[40], uint64_t* proof) {
+  GM_CTX();
+  GM_CHECK(rounds >= 1 && rounds <= 64, GM_EINVAL, "ipa_from_fields: %zu rounds", rounds);
+  const size_t k = 2 * (rounds - 1);
+  GM_CHECK(messages && challenges && batch_challenges && (k == 0 || (final_lhs_jac && final_rhs_jac)) && foldings_ff && foldings_fg1 && foldings_fg2 && proof, GM_EINVAL,
+           "ipa_from_fields: null pointer");
+  auto p = std::make_unique<IpaProof>();
+  p->rounds = rounds;
+  p->messages.assign(messages, messages + rounds * 144);
+  p->challenges.assign(challenges, challenges + rounds * 4);
+  p->batch_challenges.assign(batch_challenges, batch_challenges + (3 + k) * 4);
+  if (k) {
+    p->final_g1.assign(final_lhs_jac, final_lhs_jac + k * 18);
+    p->final_g2.assign(final_rhs_jac, final_rhs_jac + k * 36);
+  }
+  memcpy(p->foldings_ff, foldings_ff, sizeof p->foldings_ff);
+  memcpy(p->foldings_fg1, foldings_fg1, sizeof p->foldings_fg1);
+  memcpy(p->foldings_fg2, foldings_fg2, sizeof p->foldings_fg2);
+  *proof = put_in(C, C->ipa, std::move(p));
+  return GM_OK;
+}
+int gm_ipa_rounds(uint64_t proof, size_t* rounds) {
+  GM_CTX();
+  GM_IPA_FIND(p, ipa, proof, "ipa_rounds", "proof");
+  GM_CHECK(rounds != nullptr, GM_EINVAL, "ipa_rounds: null pointer");
+  *rounds = p->rounds;
+  return GM_OK;
+}
+int gm_ipa_messages(uint64_t proof, uint64_t* messages) {
+  GM_CTX();
+  GM_IPA_FIND(p, ipa, proof, "ipa_messages", "proof");
+  GM_CHECK(messages != nullptr, GM_EINVAL, "ipa_messages: null pointer");
+  memcpy(messages, p->messages.data(), p->messages.size() * 8);
+  return GM_OK;
+}
+int gm_ipa_challenges(uint64_t proof, uint64_t* challenges) {
+  GM_CTX();
+  GM_IPA_FIND(p, ipa, proof, "ipa_challenges", "proof");
+  GM_CHECK(challenges != nullptr, GM_EINVAL, "ipa_challenges: null pointer");
+  memcpy(challenges, p->challenges.data(), p->challenges.size() * 8);
+  return GM_OK;
+}
+int gm_ipa_batch_challenges(uint64_t proof, uint64_t* batch_challenges) {
+  GM_CTX();
+  GM_IPA_FIND(p, ipa, proof, "ipa_batch_challenges", "proof");
+  GM_CHECK(batch_challenges != nullptr, GM_EINVAL, "ipa_batch_challenges: null pointer");
+  memcpy(batch_challenges, p->batch_challenges.data(), p->batch_challenges.size() * 8);
+  return GM_OK;
+}
+int gm_ipa_final_foldings(uint64_t proof, uint64_t* lhs_jac, uint64_t* rhs_jac) {
+  GM_CTX();
+  GM_IPA_FIND(p, ipa, proof, "ipa_final_foldings", "proof");
+  GM_CHECK(p->final_g1.empty() || (lhs_jac && rhs_jac), GM_EINVAL, "ipa_final_foldings: null pointer");
+  if (!p->final_g1.empty()) {
+    memcpy(lhs_jac, p->final_g1.data(), p->final_g1.size() * 8);
+    memcpy(rhs_jac, p->final_g2.data(), p->final_g2.size() * 8);
+  }
+  return GM_OK;
+}
+int gm_ipa_foldings_ff(uint64_t proof, uint64_t lhs_rhs_mont[8]) {
+  GM_CTX();
+  GM_IPA_FIND(p, ipa, proof, "ipa_foldings_ff", "proof");
+  GM_CHECK(lhs_rhs_mont != nullptr, GM_EINVAL, "ipa_foldings_ff: null pointer");
+  memcpy(lhs_rhs_mont, p->foldings_ff, sizeof p->foldings_ff);
+  return GM_OK;
+}
+int gm_ipa_foldings_fg1(uint64_t proof, uint64_t lhs_jac[18], uint64_t rhs_mont[4]) {
+  GM_CTX();
+  GM_IPA_FIND(p, ipa, proof, "ipa_foldings_fg1", "proof");
+  GM_CHECK(lhs_jac && rhs_mont, GM_EINVAL, "ipa_foldings_fg1: null pointer");
+  memcpy(lhs_jac, p->foldings_fg1, 18 * 8);
+  memcpy(rhs_mont, p->foldings_fg1 + 18, 4 * 8);
+  return GM_OK;
+}
+int gm_ipa_foldings_fg2(uint64_t proof, uint64_t lhs_mont[4], uint64_t rhs_jac[36]) {
+  GM_CTX();
+  GM_IPA_FIND(p, ipa, proof, "ipa_foldings_fg2", "proof");
+  GM_CHECK(lhs_mont && rhs_jac, GM_EINVAL, "ipa_foldings_fg2: null pointer");
+  memcpy(lhs_mont, p->foldings_fg2, 4 * 8);
+  memcpy(rhs_jac, p->foldings_fg2 + 4, 36 * 8);
+  return GM_OK;
+}
+int gm_ipa_host_times(uint64_t proof, double ms[3]) {
+  GM_CTX();
+  GM_IPA_FIND(p, ipa, proof, "ipa_host_times", "proof");
+  GM_CHECK(ms != nullptr, GM_EINVAL, "ipa_host_times: null pointer");
+  memcpy(ms, p->host_ms, sizeof p->host_ms);
+  return GM_OK;
+}
+int gm_ipa_free(uint64_t proof) {
+  GM_CTX();
+  GM_CHECK(take_from(C, C->ipa, proof) != nullptr, GM_EHANDLE, "ipa_free: unknown handle %llu", (unsigned long long)proof);
+  return GM_OK;
+}
+int gm_ipa_verify(uint64_t proof, uint64_t vrs, const uint64_t comm_a_jac[18], const uint64_t comm_b_jac[36], const uint64_t y_mont[4], int* ok) {
+  GM_CTX();
+  GM_IPA_FIND(p, ipa, proof, "ipa_verify", "proof");
+  GM_IPA_FIND(v, vrs, vrs, "ipa_verify", "Vrs");
+  GM_CHECK(comm_a_jac && comm_b_jac && y_mont && ok, GM_EINVAL, "ipa_verify: null pointer");
+  return ipa_verify(C, p, v, comm_a_jac, comm_b_jac, y_mont, ok);
 }
 
 // ---- space prover --------------------------------------------------------------------------------

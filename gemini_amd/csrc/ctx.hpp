@@ -168,6 +168,27 @@ struct HerringProver {
   std::mutex mu;
 };
 
+// herring's inner-product argument (src/herring/ipa.rs; ipa.hip).  Crs: the two point vectors resident on the device, packed as
+// Bases / G2Bases hold them.  Vrs and a proof are host values: GT elements are 72 limbs (gemini_hip.h), points normalised Jacobian
+struct Crs {
+  uint8_t* g1 = nullptr;  // n1 x 96 bytes
+  uint8_t* g2 = nullptr;  // n2 x 192 bytes
+  size_t n1 = 0, n2 = 0;
+};
+struct Vrs {
+  std::vector<uint64_t> vk1, vk2;  // levels x (even || odd), 144 limbs per level
+  size_t levels = 0;
+};
+struct IpaProof {
+  size_t rounds = 0;
+  std::vector<uint64_t> messages;          // rounds x (a || b), 144 limbs each
+  std::vector<uint64_t> challenges;        // rounds x 4, Montgomery
+  std::vector<uint64_t> batch_challenges;  // (2 rounds + 1) x 4
+  std::vector<uint64_t> final_g1, final_g2;  // 2 (rounds - 1) x 18 / x 36: Sumcheck::final_foldings
+  uint64_t foldings_ff[8], foldings_fg1[22], foldings_fg2[40];  // (lhs || rhs) of the three initial provers
+  double host_ms[3] = {0, 0, 0};  // of gm_ipa_new: host GT multi-exponentiations, host final exponentiations, the whole call (gm_ipa_host_times)
+};
+
 // G2 bases (g2msm.hip): n x 192 bytes, x.c0 | x.c1 | y.c0 | y.c1 in the device form of g1.cuh; identity = all zero
 struct G2Bases {
   uint8_t* d = nullptr;
@@ -186,6 +207,10 @@ struct G2Workspace {
 struct PairingWorkspace {
   DevBuf part[2];
   uint64_t* host_out = nullptr;
+  // the segmented form (miller_products): the span and segment tables of a call, and the pinned copy of its S results
+  DevBuf seg_tab;
+  uint64_t* host_seg = nullptr;
+  size_t host_seg_cap = 0;  // in GT elements
 };
 // ChunkedPippenger / msm_chunks over HOST-resident pairs (src/kzg/msm/stream_pippenger.rs:209-272, src/kzg/space.rs:22-55):
 // the device holds two chunks; chunk i + 1 is copied in while the MSM of chunk i runs (msm.hip: msm_stream_*)
@@ -303,6 +328,9 @@ struct Context {
   std::unordered_map<uint64_t, std::unique_ptr<SparseMatrix>> matrices;
   std::unordered_map<uint64_t, std::unique_ptr<SpaceProver>> space_provers;
   std::unordered_map<uint64_t, std::unique_ptr<HerringProver>> herring;
+  std::unordered_map<uint64_t, std::unique_ptr<Crs>> crs;
+  std::unordered_map<uint64_t, std::unique_ptr<Vrs>> vrs;
+  std::unordered_map<uint64_t, std::unique_ptr<IpaProof>> ipa;
   std::unordered_map<uint64_t, std::unique_ptr<G2Bases>> g2_bases;
   std::unordered_map<uint64_t, std::unique_ptr<MsmStream>> msm_streams;
   std::unordered_map<uint64_t, std::unique_ptr<IdxVec>> indices;
@@ -386,6 +414,30 @@ uint64_t put_bases(std::unique_ptr<Bases> b);
 uint64_t put_vec(std::unique_ptr<FrVec> v);
 uint64_t put_prover(std::unique_ptr<Sumcheck> p);
 
+// a handle table of the context: look up, take out, put in (under C->mu)
+template <class T>
+inline T* find_in(Context* C, std::unordered_map<uint64_t, std::unique_ptr<T>>& table, uint64_t h) {
+  std::lock_guard<std::mutex> lk(C->mu);
+  auto it = table.find(h);
+  return it == table.end() ? nullptr : it->second.get();
+}
+template <class T>
+inline std::unique_ptr<T> take_from(Context* C, std::unordered_map<uint64_t, std::unique_ptr<T>>& table, uint64_t h) {
+  std::lock_guard<std::mutex> lk(C->mu);
+  auto it = table.find(h);
+  if (it == table.end()) return nullptr;
+  std::unique_ptr<T> p = std::move(it->second);
+  table.erase(it);
+  return p;
+}
+template <class T>
+inline uint64_t put_in(Context* C, std::unordered_map<uint64_t, std::unique_ptr<T>>& table, std::unique_ptr<T> p) {
+  std::lock_guard<std::mutex> lk(C->mu);
+  const uint64_t h = C->next_handle++;
+  table[h] = std::move(p);
+  return h;
+}
+
 #define GM_FR_LOCK(C) std::lock_guard<std::recursive_mutex> gm_fr_lock_((C)->fr_mu)
 // (the guard also counts the MSM scopes that are open: release_spare_tables must not free a table an MSM in flight reads)
 struct MsmBusyGuard {
@@ -457,16 +509,30 @@ struct PairSpan {  // n pairs (g1[first1 + step1 i], g2[first2 + step2 i]) of pa
 };
 // The Miller product of both spans, NOT conjugated, not exponentiated.  Caller holds the MSM lock.
 int miller_product(Context* C, const PairSpan& s0, const PairSpan& s1, gmh::Fq12* out);
+// S independent products in one launch per level of the reduction, however many products there are (pairing.hip: k_miller_seg)
+struct PairProduct {
+  PairSpan s0, s1;
+};
+int miller_products(Context* C, const PairProduct* prods, size_t S, gmh::Fq12* out);
 // Miller product -> GT: conjugation (the loop parameter is negative), then the one final exponentiation
 void pairing_finish(const gmh::Fq12& miller, uint64_t out_gt[72]);
 
 // herring module provers (herring.hip).  f / g are host arrays: Fr vectors in Montgomery form (the stride is ignored) or point
-// records of f_stride / g_stride bytes; messages and final foldings have the module's limb counts (include/gemini_hip.h)
+// records of f_stride / g_stride bytes; messages and final foldings have the module's limb counts (include/gemini_hip.h).
+// on_device: bit 0 / bit 1 say that f / g is a packed DEVICE vector of the side's element size, which is copied (ipa.hip: the CRS)
 int herring_create(Context* C, HerringModule module, const void* f, size_t f_stride, size_t nf, const void* g, size_t g_stride, size_t ng,
-                   const uint64_t twist[4], uint64_t* handle);
+                   const uint64_t twist[4], uint64_t* handle, int on_device = 0);
 void herring_destroy(Context* C, HerringProver* H);
 int herring_fold(Context* C, HerringProver* H, const uint64_t r[4]);
 int herring_round(Context* C, HerringProver* H, const uint64_t* challenge, uint64_t* a, uint64_t* b, int* has_msg);
 int herring_final(Context* C, HerringProver* H, uint64_t* f0, uint64_t* g0, int* has);
+
+// herring's inner-product argument (ipa.hip)
+int crs_create(Context* C, const void* g1, size_t stride1, size_t n1, const void* g2, size_t stride2, size_t n2, uint64_t* handle);
+void crs_destroy(Crs* c);
+int crs_commit(Context* C, const Crs* crs, int group, const uint64_t* scalars_mont, size_t n, uint64_t* out_jac);
+int vrs_from_crs(Context* C, const Crs* crs, Vrs* out);
+int ipa_prove(Context* C, uint64_t transcript, const Crs* crs, const uint64_t* a_mont, const uint64_t* b_mont, size_t d, IpaProof* proof);
+int ipa_verify(Context* C, const IpaProof* proof, const Vrs* vrs, const uint64_t comm_a[18], const uint64_t comm_b[36], const uint64_t y_mont[4], int* ok);
 
 }  // namespace gm

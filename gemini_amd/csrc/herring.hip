@@ -84,6 +84,16 @@ static const HerringSide FR_SIDE = {32, fr_upload, fr_alloc, fr_release, fr_spli
 static const HerringSide G1_SIDE = {96, g1_upload, point_alloc<96>, point_release, g1_split_fold, g1_read0};
 static const HerringSide G2_SIDE = {192, g2_upload, point_alloc<192>, point_release, g2_split_fold, g2_read0};
 
+// a vector where the prover keeps it: a host vector goes through the side's upload, a packed device vector (the CRS of ipa.hip) is copied
+static int side_put(Context* C, const HerringSide* S, const void* src, size_t stride, size_t n, bool on_device, uint8_t** d, size_t* cap) {
+  if (!on_device) return S->upload(C, src, stride, n, d, cap);
+  int rc = S->alloc(C, n, d, cap);
+  if (rc) return rc;
+  GM_HIP(hipMemcpyAsync(*d, src, n * S->elem, hipMemcpyDeviceToDevice, C->stream));
+  GM_HIP(hipStreamSynchronize(C->stream));
+  return GM_OK;
+}
+
 // ---- modules ------------------------------------------------------------------------------------------------------------
 struct HerringZip {  // lengths of the even / odd halves, and of the three products a message is made of
   size_t fe, fo, ge, go;
@@ -182,7 +192,7 @@ void herring_destroy(Context* C, HerringProver* H) {
 }
 
 int herring_create(Context* C, HerringModule module, const void* f, size_t f_stride, size_t nf, const void* g, size_t g_stride, size_t ng,
-                   const uint64_t twist[4], uint64_t* handle) {
+                   const uint64_t twist[4], uint64_t* handle, int on_device) {
   const HerringModuleDesc& M = MODULES[module];
   GM_CHECK(nf >= 1 && ng >= 1, GM_EINVAL, "herring %s prover: empty vectors", M.name);
   auto H = std::make_unique<HerringProver>();
@@ -191,7 +201,7 @@ int herring_create(Context* C, HerringModule module, const void* f, size_t f_str
   H->ng = ng;
   const size_t fr_len = M.lhs == &FR_SIDE ? nf : ng;  // of the side `message` compacts (no slot: no side)
   int rc;
-  if ((rc = M.lhs->upload(C, f, f_stride, nf, &H->f[0], &H->fcap[0])) || (rc = M.rhs->upload(C, g, g_stride, ng, &H->g[0], &H->gcap[0])) ||
+  if ((rc = side_put(C, M.lhs, f, f_stride, nf, on_device & 1, &H->f[0], &H->fcap[0])) || (rc = side_put(C, M.rhs, g, g_stride, ng, on_device & 2, &H->g[0], &H->gcap[0])) ||
       (rc = M.lhs->alloc(C, (nf + 1) / 2, &H->f[1], &H->fcap[1])) || (rc = M.rhs->alloc(C, (ng + 1) / 2, &H->g[1], &H->gcap[1])) ||
       (rc = C->pool.alloc(M.tmp_slots * (((fr_len + 1) / 2 + 1) * 32), (void**)&H->tmp, &H->tmpcap))) {
     herring_destroy(C, H.get());  // what has been allocated so far goes back

@@ -15,6 +15,13 @@
 //   2. k_gt_reduce   64 partials -> 1 per block, repeated while more than GT_HOST_MAX remain
 //   3. host          the last <= GT_HOST_MAX partials, the conjugation, the final exponentiation (host_field.hpp)
 //
+// The SEGMENTED form (k_miller_seg, k_gt_reduce_seg; miller_products) computes S independent products in one launch per level: the
+// rounds of InnerProductProof::new ask 2 j + 2 PModule provers for a message each, all over vectors of the same short length
+// (ipa.hip), and Vrs::from asks for 4 (log2 len - 1) products.  Lanes map to (segment, pair) through a table of segment starts,
+// the per-lane loop is k_miller's, the block product multiplies only neighbours of the same segment and every segment that
+// touches a block writes one partial.  Partials of a segment are consecutive, so the next level is the same reduction over a
+// table of its own; the launch count depends on the longest segment only, never on S.
+//
 // Registers and LDS: f is 144 VGPRs, T 72, a line 36, and an Fq6 product keeps ~10 Fq2 alive: too much for the 512 registers of
 // a lane at one wave per SIMD if f stayed resident.  f therefore lives in LDS ([coefficient limb][lane], 576 B per lane, 36 KiB per
 // wave: four waves per CU, one per SIMD) and is in registers only from the load in front of f^2 to the store behind f * line;
@@ -26,6 +33,7 @@
 // (C->msm.misc) and the partial buffers (C->pairing) are single-flight like it.
 #include <algorithm>
 #include <cstring>
+#include <vector>
 
 #include "ctx.hpp"
 #include "gt.cuh"
@@ -114,6 +122,30 @@ GM_DEV Line miller_add_step(G2Proj& T, const G2Affine& Q, const G1Affine& P) {
   return l;
 }
 
+// The loop of one lane: f_{|x|, Q}(P) into the lane's column of sh (1 when the pair is not live).  Shared by k_miller and k_miller_seg.
+GM_DEV void miller_lane(uint32_t* sh, int lane, bool live, const G1Affine& P, const G2Affine& Q) {
+  gt_lds_store(sh, lane, fq12_one());
+  if (live) {
+    G2Proj T;
+    T.x = Q.x;
+    T.y = Q.y;
+    T.z = fq2_one();
+    // the loop bits are those of a constant: the branch below is the same for every lane of every wave (a scalar branch),
+    // and the body is stated once -- unrolling 63 steps of ~100 out-of-line Fq products each buys nothing
+#pragma unroll 1
+    for (int bit = 62; bit >= 0; bit--) {
+      Line l = miller_dbl_step(T, P);
+      Fq12 f = fq12_mul_014(fq12_sqr(gt_lds_load(sh, lane)), l.l0, l.l1, l.l4);
+      if ((ATE_LOOP >> bit) & 1ull) {
+        gt_lds_store(sh, lane, f);
+        l = miller_add_step(T, Q, P);
+        f = fq12_mul_014(gt_lds_load(sh, lane), l.l0, l.l1, l.l4);
+      }
+      gt_lds_store(sh, lane, f);
+    }
+  }
+}
+
 // Two ranges of pairs per launch (the second may be empty): pair i < n0 is (g1[first1 + step1 i], g2[first2 + step2 i]) of
 // range 0, the others of range 1 -- the b message of the PModule prover is ONE product over (f_e, g_o) and (f_o, g_e).
 struct PairRange {
@@ -141,26 +173,7 @@ __global__ __launch_bounds__(PAIR_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1
     Q = g2_load_affine((second ? r1.g2 : r0.g2) + (size_t)i2 * G2_AFF_BYTES);
     live = !(P.is_identity() || Q.is_identity());  // a point at infinity never enters the product
   }
-  gt_lds_store(sh, lane, fq12_one());
-  if (live) {
-    G2Proj T;
-    T.x = Q.x;
-    T.y = Q.y;
-    T.z = fq2_one();
-    // the loop bits are those of a constant: the branch below is the same for every lane of every wave (a scalar branch),
-    // and the body is stated once -- unrolling 63 steps of ~100 out-of-line Fq products each buys nothing
-#pragma unroll 1
-    for (int bit = 62; bit >= 0; bit--) {
-      Line l = miller_dbl_step(T, P);
-      Fq12 f = fq12_mul_014(fq12_sqr(gt_lds_load(sh, lane)), l.l0, l.l1, l.l4);
-      if ((ATE_LOOP >> bit) & 1ull) {
-        gt_lds_store(sh, lane, f);
-        l = miller_add_step(T, Q, P);
-        f = fq12_mul_014(gt_lds_load(sh, lane), l.l0, l.l1, l.l4);
-      }
-      gt_lds_store(sh, lane, f);
-    }
-  }
+  miller_lane(sh, lane, live, P, Q);
   gt_block_product(sh, lane);
   if (lane == 0) fq12_store(partials + (size_t)blockIdx.x * GT_BYTES, gt_lds_load(sh, 0));
 }
@@ -175,6 +188,85 @@ __global__ __launch_bounds__(PAIR_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1
   if (lane == 0) fq12_store(out + (size_t)blockIdx.x * GT_BYTES, gt_lds_load(sh, 0));
 }
 
+// ---- the segmented form: S independent products per launch ------------------------------------------------------------------
+// Segment s owns the lanes [start, start + count) of a level and writes its partials from index `out` on, one per block it touches.
+// The host (seg_levels) lays the segments out so that one of at most PAIR_BLOCK lanes never crosses a block; lanes between two
+// segments belong to none.
+struct SegMap {
+  unsigned long long start, count, out;
+};
+struct PairSeg {
+  PairRange r0, r1;
+};
+constexpr uint32_t NO_SEG = 0xffffffffu;
+
+// the segment of lane i, NO_SEG between segments: the last entry that starts at or below i (starts ascend)
+GM_DEV uint32_t seg_find(const SegMap* __restrict__ map, unsigned nseg, unsigned long long i) {
+  if (i < map[0].start) return NO_SEG;
+  unsigned lo = 0, hi = nseg;  // map[lo].start <= i < map[hi].start (map[nseg]: past the end)
+  while (hi - lo > 1) {
+    const unsigned mid = (lo + hi) >> 1;
+    if (map[mid].start <= i) lo = mid;
+    else hi = mid;
+  }
+  return i - map[lo].start < map[lo].count ? lo : NO_SEG;
+}
+
+// The block's accumulators multiplied segment by segment: after the step of stride s a lane holds the product of the lanes
+// [lane, lane + 2 s) of its segment, so the first lane of every segment ends with all of it -- at most 6 levels, fewer when the
+// segments are short (the loop ends with the first stride no lane can use).  That lane writes the segment's partial of this block.
+GM_DEV void gt_block_product_seg(uint32_t* sh, uint32_t* seg, int lane, uint32_t sid, const SegMap* __restrict__ map, uint8_t* __restrict__ out) {
+  seg[lane] = sid;
+  __syncthreads();
+  for (int s = 1; s < PAIR_BLOCK; s <<= 1) {
+    const bool take = sid != NO_SEG && lane + s < PAIR_BLOCK && seg[lane + s] == sid;
+    if (!__syncthreads_or(take)) break;
+    Fq12 p;
+    if (take) p = fq12_mul(gt_lds_load(sh, lane), gt_lds_load(sh, lane + s));
+    __syncthreads();
+    if (take) gt_lds_store(sh, lane, p);
+  }
+  __syncthreads();
+  if (sid != NO_SEG && (lane == 0 || seg[lane - 1] != sid))
+    fq12_store(out + (size_t)(map[sid].out + (blockIdx.x - map[sid].start / PAIR_BLOCK)) * GT_BYTES, gt_lds_load(sh, lane));
+}
+
+// k_miller over a table of products: lane -> (segment, pair), the loop of miller_lane, one partial per (block, segment)
+__global__ __launch_bounds__(PAIR_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_miller_seg(const PairSeg* __restrict__ spans, const SegMap* __restrict__ map, unsigned nseg,
+                                                                                                         uint8_t* __restrict__ partials) {
+  __shared__ uint32_t sh[GT_WORDS * PAIR_BLOCK];
+  __shared__ uint32_t seg[PAIR_BLOCK];
+  const int lane = threadIdx.x;
+  const unsigned long long i = (unsigned long long)blockIdx.x * PAIR_BLOCK + lane;
+  const uint32_t sid = seg_find(map, nseg, i);
+  G1Affine P;
+  G2Affine Q;
+  bool live = false;
+  if (sid != NO_SEG) {
+    const unsigned long long k0 = i - map[sid].start;
+    const bool second = k0 >= spans[sid].r0.n;
+    const PairRange r = second ? spans[sid].r1 : spans[sid].r0;
+    const long long k = (long long)(second ? k0 - spans[sid].r0.n : k0);
+    P = g1_load_affine(r.g1 + (size_t)(r.first1 + r.step1 * k) * G1_AFF_BYTES);
+    Q = g2_load_affine(r.g2 + (size_t)(r.first2 + r.step2 * k) * G2_AFF_BYTES);
+    live = !(P.is_identity() || Q.is_identity());
+  }
+  miller_lane(sh, lane, live, P, Q);
+  gt_block_product_seg(sh, seg, lane, sid, map, partials);
+}
+
+// one level of the reduction behind it: lane i holds partial i of the level below
+__global__ __launch_bounds__(PAIR_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_gt_reduce_seg(const uint8_t* __restrict__ in, const SegMap* __restrict__ map, unsigned nseg,
+                                                                                                            uint8_t* __restrict__ out) {
+  __shared__ uint32_t sh[GT_WORDS * PAIR_BLOCK];
+  __shared__ uint32_t seg[PAIR_BLOCK];
+  const int lane = threadIdx.x;
+  const unsigned long long i = (unsigned long long)blockIdx.x * PAIR_BLOCK + lane;
+  const uint32_t sid = seg_find(map, nseg, i);
+  gt_lds_store(sh, lane, sid != NO_SEG ? fq12_load(in + (size_t)i * GT_BYTES) : fq12_one());
+  gt_block_product_seg(sh, seg, lane, sid, map, out);
+}
+
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
@@ -182,6 +274,10 @@ void pairing_workspace_release(PairingWorkspace& w) {
   for (DevBuf& b : w.part) b.release();
   if (w.host_out) (void)hipHostFree(w.host_out);
   w.host_out = nullptr;
+  w.seg_tab.release();
+  if (w.host_seg) (void)hipHostFree(w.host_seg);
+  w.host_seg = nullptr;
+  w.host_seg_cap = 0;
 }
 
 // The Miller product of both spans (PairSpan: ctx.hpp), NOT conjugated, not exponentiated.  Caller holds the MSM lock.
@@ -220,6 +316,106 @@ int miller_product(Context* C, const PairSpan& s0, const PairSpan& s1, gmh::Fq12
   gmh::Fq12 f = gmh::Fq12::from_device(ws.host_out);
   for (size_t k = 1; k < m; k++) f = f * gmh::Fq12::from_device(ws.host_out + k * (GT_BYTES / 8));
   *out = f;
+  return GM_OK;
+}
+
+// One level of the segmented layout: segment s has counts[s] >= 1 lanes.  Fills start / count / out and returns the number of
+// lanes of the level; counts becomes the partials per segment (the next level's lanes), *partials their total.  A segment of at
+// most PAIR_BLOCK lanes is moved to the next block rather than split, so it yields ONE partial and the levels end: a longer one
+// yields at most count / 64 + 2 < count.
+static unsigned long long seg_level(std::vector<unsigned long long>& counts, const std::vector<unsigned long long>& starts_or_empty, SegMap* map,
+                                    unsigned long long* partials) {
+  unsigned long long lane = 0, out = 0;
+  for (size_t s = 0; s < counts.size(); s++) {
+    const unsigned long long n = counts[s];
+    if (!starts_or_empty.empty()) lane = starts_or_empty[s];  // a reduction level reads where the level below wrote
+    else if (n <= PAIR_BLOCK && lane % PAIR_BLOCK + n > PAIR_BLOCK) lane = (lane / PAIR_BLOCK + 1) * PAIR_BLOCK;
+    const unsigned long long nb = (lane + n - 1) / PAIR_BLOCK - lane / PAIR_BLOCK + 1;
+    if (nb <= PAIR_BLOCK && out % PAIR_BLOCK + nb > PAIR_BLOCK) out = (out / PAIR_BLOCK + 1) * PAIR_BLOCK;
+    map[s] = SegMap{lane, n, out};
+    lane += n;
+    out += nb;
+    counts[s] = nb;
+  }
+  *partials = out;
+  return lane;
+}
+
+// S independent Miller products in one launch per level (NOT conjugated, not exponentiated): out[s] is the product over both spans
+// of prods[s], 1 for an empty one.  Caller holds the MSM lock.
+int miller_products(Context* C, const PairProduct* prods, size_t S, gmh::Fq12* out) {
+  std::vector<size_t> idx;
+  std::vector<unsigned long long> counts;
+  std::vector<PairSeg> spans;
+  for (size_t s = 0; s < S; s++) {
+    out[s] = gmh::Fq12::one();
+    const PairSpan &a = prods[s].s0, &b = prods[s].s1;
+    if (a.n + b.n == 0) continue;
+    GM_CHECK(a.n + b.n <= ((size_t)1 << 36), GM_EINVAL, "pairing: %zu pairs in one product (at most 2^36)", a.n + b.n);
+    idx.push_back(s);
+    counts.push_back(a.n + b.n);
+    spans.push_back(PairSeg{PairRange{a.g1, a.g2, (long long)a.first1, (long long)a.step1, (long long)a.first2, (long long)a.step2, (unsigned long long)a.n},
+                            PairRange{b.g1, b.g2, (long long)b.first1, (long long)b.step1, (long long)b.first2, (long long)b.step2, (unsigned long long)b.n}});
+  }
+  const size_t nseg = idx.size();
+  if (nseg == 0) return GM_OK;
+  GM_CHECK(nseg < ((size_t)1 << 24), GM_EINVAL, "pairing: %zu products in one call (at most 2^24)", nseg);
+  // every level's table, then ONE copy: level 0 maps pairs, the others the partials of the level below
+  struct Level {
+    unsigned long long lanes, partials;
+  };
+  std::vector<Level> levels;
+  std::vector<SegMap> maps;
+  std::vector<unsigned long long> starts;
+  for (;;) {
+    maps.resize(maps.size() + nseg);
+    SegMap* m = maps.data() + maps.size() - nseg;
+    Level l;
+    l.lanes = seg_level(counts, starts, m, &l.partials);
+    levels.push_back(l);
+    GM_CHECK(l.lanes <= ((unsigned long long)1 << 37), GM_EINVAL, "pairing: %llu lanes in one segmented launch (at most 2^37)", l.lanes);
+    if (l.partials == nseg) break;  // one partial per segment, back to back
+    starts.resize(nseg);
+    for (size_t s = 0; s < nseg; s++) starts[s] = m[s].out;
+  }
+  hipStream_t st = C->stream;
+  PairingWorkspace& ws = C->pairing;
+  Profiler& pf = C->prof;
+  int rc;
+  const size_t span_bytes = nseg * sizeof(PairSeg), map_bytes = maps.size() * sizeof(SegMap);
+  if ((rc = ws.seg_tab.ensure(span_bytes + map_bytes))) return rc;
+  for (size_t l = 0; l < levels.size(); l++)  // level l writes its partials into part[l & 1]
+    if ((rc = ws.part[l & 1].ensure(levels[l].partials * GT_BYTES))) return rc;
+  if (ws.host_seg_cap < nseg) {
+    if (ws.host_seg) (void)hipHostFree(ws.host_seg);
+    ws.host_seg = nullptr;
+    ws.host_seg_cap = 0;
+    const size_t cap = std::max<size_t>(2 * nseg, 64);
+    GM_HIP(hipHostMalloc((void**)&ws.host_seg, cap * GT_BYTES, hipHostMallocDefault));
+    ws.host_seg_cap = cap;
+  }
+  uint8_t* d_tab = ws.seg_tab.as<uint8_t>();
+  GM_HIP(hipMemcpyAsync(d_tab, spans.data(), span_bytes, hipMemcpyHostToDevice, st));
+  GM_HIP(hipMemcpyAsync(d_tab + span_bytes, maps.data(), map_bytes, hipMemcpyHostToDevice, st));
+  const SegMap* d_map = reinterpret_cast<const SegMap*>(d_tab + span_bytes);
+  pf.begin(PROF_ACC0, st);
+  hipLaunchKernelGGL(k_miller_seg, dim3((unsigned)((levels[0].lanes + PAIR_BLOCK - 1) / PAIR_BLOCK)), dim3(PAIR_BLOCK), 0, st, reinterpret_cast<const PairSeg*>(d_tab), d_map,
+                     (unsigned)nseg, ws.part[0].as<uint8_t>());
+  pf.end(PROF_ACC0, st);
+  GM_HIP(hipGetLastError());
+  int cur = 0;
+  pf.begin(PROF_REDUCE, st);
+  for (size_t l = 1; l < levels.size(); l++) {
+    hipLaunchKernelGGL(k_gt_reduce_seg, dim3((unsigned)((levels[l].lanes + PAIR_BLOCK - 1) / PAIR_BLOCK)), dim3(PAIR_BLOCK), 0, st, ws.part[cur].as<uint8_t>(), d_map + l * nseg,
+                       (unsigned)nseg, ws.part[cur ^ 1].as<uint8_t>());
+    cur ^= 1;
+  }
+  pf.end(PROF_REDUCE, st);
+  GM_HIP(hipGetLastError());
+  GM_HIP(hipMemcpyAsync(ws.host_seg, ws.part[cur].p, nseg * GT_BYTES, hipMemcpyDeviceToHost, st));
+  GM_HIP(hipStreamSynchronize(st));  // the tables above are read by their copies until here
+  pf.collect();
+  for (size_t s = 0; s < nseg; s++) out[idx[s]] = gmh::Fq12::from_device(ws.host_seg + s * (GT_BYTES / 8));
   return GM_OK;
 }
 

@@ -12,6 +12,8 @@
 //   Fr            32 bytes little-endian canonical
 //   G1 (uncompr.) x (48 B LE) || y (48 B LE), flags in the top bits of the last byte:
 //                 bit 7 = y is the lexicographically larger root, bit 6 = point at infinity
+//   GT            PairingOutput serialises its Fp12: the 12 Fq coefficients in tower order (c0.c0.c0, c0.c0.c1, c0.c1.c0, ...,
+//                 c1.c2.c1), 48 bytes little-endian canonical each, 576 bytes, no flags
 // These are recalled from the crates' sources (not checkable in this image); they are isolated in
 // this file so that a correction is local.
 #include <cstdint>
@@ -254,6 +256,23 @@ int gm_transcript_append_g1(uint64_t handle, const uint8_t* label, size_t llen, 
       if (!gmh::geq<6>(ny, y)) enc[95] |= 1u << 7;  // y > -y
     }
     buf.insert(buf.end(), enc, enc + 96);
+  }
+  t->append_message(label, llen, buf.data(), buf.size());
+  return GM_OK;
+}
+
+// append_serializable for `count` GT elements laid out consecutively (72 Montgomery limbs each): one PairingOutput, or a
+// SumcheckMsg<PairingOutput> (a || b: the derive of src/herring/prover.rs:11-12 writes its two fields in order, count = 2)
+int gm_transcript_append_gt(uint64_t handle, const uint8_t* label, size_t llen, const uint64_t* gt, size_t count) {
+  Transcript* t = find(handle);
+  T_CHECK(t, GM_EHANDLE, "transcript_append_gt: unknown handle %llu", (unsigned long long)handle);
+  T_CHECK(gt != nullptr || count == 0, GM_EINVAL, "transcript_append_gt: null pointer");
+  std::vector<uint8_t> buf(576 * count);
+  for (size_t i = 0; i < 12 * count; i++) {
+    uint64_t c[6];
+    gmh::Fq::from_limbs(gt + 6 * i).to_canonical(c);
+    for (int k = 0; k < 6; k++)
+      for (int b = 0; b < 8; b++) buf[48 * i + 8 * k + b] = (uint8_t)(c[k] >> (8 * b));
   }
   t->append_message(label, llen, buf.data(), buf.size());
   return GM_OK;

@@ -1,7 +1,8 @@
 """Host mirror of herring's sumcheck over a bilinear module (src/herring): the TimeProver of
 src/herring/time_prover.rs:42-137 for the four module instances that are in scope:
 FModule (F x F -> F), G1Module (G1 x F -> G1), G2Module (F x G2 -> G2) and PModule (G1 x G2 -> GT; pairings are
-gemini_amd/pairing.py).  GtModule and InnerProductProof are out of scope."""
+gemini_amd/pairing.py).  The inner-product argument built on them is gemini_amd/ipa.py (its PModule provers are batched inside the library,
+not instances of the classes here); a GtModule prover of its own, InnerProductProof::generic and CrsStream are out of scope."""
 from __future__ import annotations
 
 import ctypes as C

@@ -1,0 +1,158 @@
+"""Host mirror of herring's inner-product argument (src/herring/ipa.rs): `Crs` (:172-213), `Vrs` (:215-247) and
+`InnerProductProof` with `new` (:533-685) and `verify_transcript` (:250-343).  All arithmetic happens in libgemini_hip.so
+(gm_crs_*, gm_vrs_*, gm_ipa_*; gemini_amd/csrc/ipa.hip): the prover keeps every vector on the device and the round loop is the
+library's, with the transcript inside it.
+
+Data conventions (numpy uint64): G1 records (n, 12) / (n, 13) as in gemini_amd.msm, G2 records (n, 24) / (n, 25) as in
+gemini_amd.g2msm, scalars (n, 4) Montgomery, points (18,) / (36,) normalised Jacobian, GT elements (72,) as in gemini_amd.pairing.
+The reference defines no wire format for this proof and none is claimed here.  `InnerProductProof::generic` (pub(crate), called
+by one test of the reference) and `CrsStream` (its fold is a todo!() in the reference) are out of scope.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import capi
+from .g2msm import _records as _g2_records
+from .pairing import _g1_records
+
+
+class Crs:
+    """`Crs`: G1 and G2 points resident in HBM"""
+
+    def __init__(self, g1_records, g2_records):
+        capi.ensure_init()
+        g1, g2 = _g1_records(g1_records), _g2_records(g2_records)
+        h = C.c_uint64()
+        capi.check(capi.load().gm_crs_new(capi.ptr(g1), C.c_size_t(g1.shape[1] * 8), C.c_size_t(len(g1)), capi.ptr(g2), C.c_size_t(g2.shape[1] * 8),
+                                          C.c_size_t(len(g2)), C.byref(h)))
+        self.handle = h.value
+        self.n1, self.n2 = len(g1), len(g2)
+
+    def commit_g1(self, scalars_mont) -> np.ndarray:
+        """Crs::commit_g1: the CRS must be longer than the scalars"""
+        sc = capi.u64(scalars_mont).reshape(-1, 4)
+        out = np.empty(18, dtype=np.uint64)
+        capi.check(capi.load().gm_crs_commit_g1(C.c_uint64(self.handle), capi.ptr(sc), C.c_size_t(len(sc)), capi.ptr(out)))
+        return out
+
+    def commit_g2(self, scalars_mont) -> np.ndarray:
+        sc = capi.u64(scalars_mont).reshape(-1, 4)
+        out = np.empty(36, dtype=np.uint64)
+        capi.check(capi.load().gm_crs_commit_g2(C.c_uint64(self.handle), capi.ptr(sc), C.c_size_t(len(sc)), capi.ptr(out)))
+        return out
+
+    def free(self):
+        if self.handle:
+            capi.check(capi.load().gm_crs_free(C.c_uint64(self.handle)))
+            self.handle = 0
+
+
+class Vrs:
+    """`Vrs::from(&crs)`: per level the (even, odd) multi-pairings of each group against the other, one segmented launch for all"""
+
+    def __init__(self, crs: Crs):
+        h = C.c_uint64()
+        capi.check(capi.load().gm_vrs_from_crs(C.c_uint64(crs.handle), C.byref(h)))
+        self.handle = h.value
+
+    @property
+    def levels(self) -> int:
+        n = C.c_size_t()
+        capi.check(capi.load().gm_vrs_levels(C.c_uint64(self.handle), C.byref(n)))
+        return n.value
+
+    def level(self, l: int):
+        """-> (vk1, vk2), each (2, 72): even, odd"""
+        vk1, vk2 = np.empty((2, 72), dtype=np.uint64), np.empty((2, 72), dtype=np.uint64)
+        capi.check(capi.load().gm_vrs_get(C.c_uint64(self.handle), C.c_size_t(l), capi.ptr(vk1), capi.ptr(vk2)))
+        return vk1, vk2
+
+    def free(self):
+        if self.handle:
+            capi.check(capi.load().gm_vrs_free(C.c_uint64(self.handle)))
+            self.handle = 0
+
+
+@dataclass
+class IpaFields:
+    """the fields of `InnerProductProof` (and of its `Sumcheck<PModule>`)"""
+
+    rounds: int
+    messages: np.ndarray          # (rounds, 2, 72)
+    challenges: np.ndarray        # (rounds, 4)
+    batch_challenges: np.ndarray  # (2 rounds + 1, 4)
+    final_lhs: np.ndarray         # (2 (rounds - 1), 18)
+    final_rhs: np.ndarray         # (2 (rounds - 1), 36)
+    foldings_ff: np.ndarray       # (2, 4)
+    foldings_fg1: tuple           # ((18,), (4,))
+    foldings_fg2: tuple           # ((4,), (36,))
+
+
+class InnerProductProof:
+    def __init__(self, handle: int):
+        self.handle = handle
+
+    @classmethod
+    def new(cls, transcript, crs: Crs, a_mont, b_mont) -> "InnerProductProof":
+        """InnerProductProof::new(transcript, crs, (a, b)); d = len(a) = len(b) >= 2 and the CRS holds max(d + 1, 2^rounds) points"""
+        a, b = capi.u64(a_mont).reshape(-1, 4), capi.u64(b_mont).reshape(-1, 4)
+        assert len(a) == len(b)
+        h = C.c_uint64()
+        capi.check(capi.load().gm_ipa_new(C.c_uint64(transcript.handle), C.c_uint64(crs.handle), capi.ptr(a), capi.ptr(b), C.c_size_t(len(a)), C.byref(h)))
+        return cls(h.value)
+
+    @classmethod
+    def from_fields(cls, f: IpaFields) -> "InnerProductProof":
+        capi.ensure_init()
+        k = 2 * (f.rounds - 1)
+        fg1 = np.concatenate([capi.u64(f.foldings_fg1[0]).reshape(18), capi.u64(f.foldings_fg1[1]).reshape(4)])
+        fg2 = np.concatenate([capi.u64(f.foldings_fg2[0]).reshape(4), capi.u64(f.foldings_fg2[1]).reshape(36)])
+        lhs, rhs = capi.u64(f.final_lhs).reshape(k, 18), capi.u64(f.final_rhs).reshape(k, 36)
+        h = C.c_uint64()
+        capi.check(capi.load().gm_ipa_from_fields(C.c_size_t(f.rounds), capi.ptr(capi.u64(f.messages).reshape(f.rounds, 144)),
+                                                  capi.ptr(capi.u64(f.challenges).reshape(f.rounds, 4)),
+                                                  capi.ptr(capi.u64(f.batch_challenges).reshape(2 * f.rounds + 1, 4)), capi.ptr(lhs) if k else None,
+                                                  capi.ptr(rhs) if k else None, capi.ptr(capi.u64(f.foldings_ff).reshape(8)), capi.ptr(fg1), capi.ptr(fg2),
+                                                  C.byref(h)))
+        return cls(h.value)
+
+    def fields(self) -> IpaFields:
+        lib, h = capi.load(), C.c_uint64(self.handle)
+        n = C.c_size_t()
+        capi.check(lib.gm_ipa_rounds(h, C.byref(n)))
+        r = n.value
+        k = 2 * (r - 1)
+        msgs, ch, bch = np.empty((r, 2, 72), dtype=np.uint64), np.empty((r, 4), dtype=np.uint64), np.empty((2 * r + 1, 4), dtype=np.uint64)
+        lhs, rhs = np.empty((k, 18), dtype=np.uint64), np.empty((k, 36), dtype=np.uint64)
+        ff = np.empty((2, 4), dtype=np.uint64)
+        g1f, g1s, g2s, g2g = (np.empty(w, dtype=np.uint64) for w in (18, 4, 4, 36))
+        capi.check(lib.gm_ipa_messages(h, capi.ptr(msgs)))
+        capi.check(lib.gm_ipa_challenges(h, capi.ptr(ch)))
+        capi.check(lib.gm_ipa_batch_challenges(h, capi.ptr(bch)))
+        capi.check(lib.gm_ipa_final_foldings(h, capi.ptr(lhs) if k else None, capi.ptr(rhs) if k else None))
+        capi.check(lib.gm_ipa_foldings_ff(h, capi.ptr(ff)))
+        capi.check(lib.gm_ipa_foldings_fg1(h, capi.ptr(g1f), capi.ptr(g1s)))
+        capi.check(lib.gm_ipa_foldings_fg2(h, capi.ptr(g2s), capi.ptr(g2g)))
+        return IpaFields(r, msgs, ch, bch, lhs, rhs, ff, (g1f, g1s), (g2s, g2g))
+
+    def verify_transcript(self, vrs: Vrs, comm_a, comm_b, y_mont) -> bool:
+        """InnerProductProof::verify_transcript(vrs, comm_a, comm_b, y): True for Ok(())"""
+        ok = C.c_int()
+        capi.check(capi.load().gm_ipa_verify(C.c_uint64(self.handle), C.c_uint64(vrs.handle), capi.ptr(capi.u64(comm_a).reshape(18)),
+                                             capi.ptr(capi.u64(comm_b).reshape(36)), capi.ptr(capi.u64(y_mont).reshape(4)), C.byref(ok)))
+        return bool(ok.value)
+
+    def host_times(self) -> dict:
+        """what gm_ipa_new spent on the host making this proof, ms (a measurement aid: tools/ipa_bench.py)"""
+        ms = (C.c_double * 3)()
+        capi.check(capi.load().gm_ipa_host_times(C.c_uint64(self.handle), ms))
+        return {"gt_multi_pow_ms": ms[0], "final_exp_ms": ms[1], "call_ms": ms[2]}
+
+    def free(self):
+        if self.handle:
+            capi.check(capi.load().gm_ipa_free(C.c_uint64(self.handle)))
+            self.handle = 0

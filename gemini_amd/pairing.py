@@ -5,7 +5,7 @@ Data conventions (numpy uint64): G1 records (n, 12) / (n, 13) as in gemini_amd.m
 gemini_amd.g2msm; a GT element is (72,) limbs = 12 Fq values in Montgomery form, tower order c0.c0.c0, c0.c0.c1, c0.c1.c0, ...,
 c1.c2.c1 of Fq12 = Fq6[w] / (w^2 - v), Fq6 = Fq2[v] / (v^3 - (1 + u)), Fq2 = Fq[u] / (u^2 + 1).  GT is written multiplicatively:
 what herring calls "+" on GT is `gt_mul`.  The value is the reduced ate pairing as ark-ec states it for BLS12 with the exponent
-(q^12 - 1) / r; GtModule and InnerProductProof are out of scope.
+(q^12 - 1) / r.  InnerProductProof with Crs and Vrs is gemini_amd/ipa.py; InnerProductProof::generic and CrsStream are out of scope.
 """
 from __future__ import annotations
 

@@ -58,6 +58,11 @@ class Transcript:
         j = capi.u64(jac).reshape(-1, 18)
         capi.check(capi.load().gm_transcript_append_g1(C.c_uint64(self.handle), _b(label), C.c_size_t(len(label)), capi.ptr(j), C.c_size_t(len(j)), C.c_int(int(with_len))))
 
+    def append_gt(self, label: bytes, gt):
+        """one PairingOutput or herring's SumcheckMsg<PairingOutput> (a || b): (k, 72) limbs, 576 bytes per element"""
+        g = capi.u64(gt).reshape(-1, 72)
+        capi.check(capi.load().gm_transcript_append_gt(C.c_uint64(self.handle), _b(label), C.c_size_t(len(label)), capi.ptr(g), C.c_size_t(len(g))))
+
     def set_g1_encoding(self, encoding: int):
         """0: ark-ec default framing (ark-test-curves); 1: zcash framing (ark-bls12-381).  See gemini_amd/wire.py."""
         capi.check(capi.load().gm_transcript_set_g1_encoding(C.c_uint64(self.handle), C.c_int(int(encoding))))

@@ -465,7 +465,7 @@ int gm_hg1_free(uint64_t handle);
  * normalised).  A null pointer or a bad stride (< 192, or not a multiple of 8) gives GM_EINVAL, an unknown handle GM_EHANDLE.
  * A call of more than 2^25 pairs is cut into 2^25-pair MSMs whose results are added on the host.
  * OUT OF SCOPE for G2: fixed-base tables, GLV, the streaming form, batches, sharding.  Pairings and the PModule prover are
- * in the next block; GtModule and InnerProductProof stay out of scope. */
+ * in the next block, InnerProductProof in the one after it. */
 int gm_g2_msm(const void* bases, size_t base_stride, const uint64_t* scalars, size_t n, uint64_t out_jac[36]);
 int gm_g2_bases_register(const void* bases, size_t base_stride, size_t n, uint64_t* handle);
 int gm_g2_bases_free(uint64_t handle);
@@ -504,8 +504,8 @@ int gm_hg2_free(uint64_t handle);
  * One lane per pair runs the Miller loop; the product is reduced on the device down to a handful of partials, the host
  * multiplies those and does the conjugation and ONE final exponentiation per call (a few ms, profiles/pairing.md).
  * Pairing calls share the MSM lock of the Threading paragraph above.
- * OUT OF SCOPE: GtModule, InnerProductProof, subgroup checks (points are taken as members of G1 / G2, as ark-ec's
- * pairing takes them). */
+ * OUT OF SCOPE: subgroup checks (points are taken as members of G1 / G2, as ark-ec's pairing takes them); of herring's
+ * InnerProductProof (next block) the pub(crate) `generic` and CrsStream. */
 /* host records as gm_g1_bases_register / gm_g2_bases_register accept them (strides >= 96 / >= 192, multiples of 8; the
  * infinity flag at byte 96 / 192 when the stride has room); n = 0 gives 1 */
 int gm_pairing_multi(const void* g1, size_t g1_stride, const void* g2, size_t g2_stride, size_t n, uint64_t out_gt[72]);
@@ -534,6 +534,65 @@ int gm_hp_rounds(uint64_t handle, size_t* tot_rounds, size_t* round);
 int gm_hp_final(uint64_t handle, uint64_t f0_jac[18], uint64_t g0_jac[36], int* has);
 int gm_hp_free(uint64_t handle);
 
+/* ---- herring's inner-product argument: Crs, Vrs, InnerProductProof (gemini_amd/csrc/ipa.hip) -------------------------
+ * src/herring/ipa.rs: InnerProductProof::new (:533-685) proves <a, b> = y together with comm_a = <a, crs.g1> and
+ * comm_b = <b, crs.g2> in one batched sumcheck over GT; verify_transcript (:250-343) checks it against the Vrs of the CRS.
+ * The three claims run on the FModule / G1Module / G2Module provers above.  The PModule provers the rounds add (two per round,
+ * every live one asked for a message in every round) live in one device arena per group: per round ONE G1 and ONE G2 fold launch
+ * and ONE segmented Miller launch (plus its reduction levels) whatever the number of live provers; the GT multi-exponentiation
+ * of SumcheckMsg::ip runs on the host over the Miller values, so each half of a round message takes one final exponentiation
+ * (profiles/herring_ipa.md).  Values are bit for bit those of the composition of gm_sc_* / gm_hg1_* / gm_hg2_* / gm_hp_* with
+ * gm_gt_mul / gm_gt_pow (tests/test_gpu_ipa_stepwise.py).
+ * Scalars are Montgomery limbs, points normalised Jacobian, GT elements 72 limbs as in the pairing block.  The reference defines no
+ * wire format for this proof and none is claimed: the getters return the fields.
+ * OUT OF SCOPE: InnerProductProof::generic (pub(crate), called by one test of the reference only) and CrsStream (its fold is a
+ * todo!() in the reference, ipa.rs:143-145). */
+/* Crs over resident G1 and G2 arrays; records and strides as gm_g1_bases_register / gm_g2_bases_register take them */
+int gm_crs_new(const void* g1, size_t g1_stride, size_t n1, const void* g2, size_t g2_stride, size_t n2, uint64_t* handle);
+int gm_crs_free(uint64_t handle);
+int gm_crs_len(uint64_t handle, size_t* n1, size_t* n2);
+/* Crs::commit_g1 / commit_g2 (ipa.rs:179-189): the MSM of the first n points.  The reference asserts that the CRS is LONGER
+ * than the scalars; n >= the CRS length gives GM_EINVAL. */
+int gm_crs_commit_g1(uint64_t handle, const uint64_t* scalars_mont, size_t n, uint64_t out_jac[18]);
+int gm_crs_commit_g2(uint64_t handle, const uint64_t* scalars_mont, size_t n, uint64_t out_jac[36]);
+/* Vrs::from(&crs) (ipa.rs:215-247): levels = ceil(log2(n1)) - 1; level l holds, for size = 2^(l + 1), vk1 = (ip(g1 even, g2), ip(g1 odd, g2))
+ * and vk2 = (ip(g1, g2 even), ip(g1, g2 odd)) over the first `size` pairs (zips end with the shorter side).  All 4 levels
+ * Miller products are one segmented launch.  gm_vrs_get: even || odd, 144 limbs each. */
+int gm_vrs_from_crs(uint64_t crs, uint64_t* vrs);
+int gm_vrs_levels(uint64_t vrs, size_t* levels);
+int gm_vrs_get(uint64_t vrs, size_t level, uint64_t vk1_even_odd[144], uint64_t vk2_even_odd[144]);
+int gm_vrs_free(uint64_t vrs);
+/* InnerProductProof::new(transcript, crs, (a, b)) for two vectors of d scalars; rounds = ceil(log2(d)).  The transcript (a
+ * gm_transcript handle) absorbs and answers under the reference's labels in its order: batch-chal, prover_message, then per round
+ * sumcheck-chal, batch-chal, sumcheck-round, and the last sumcheck-chal; it is the caller's to hand on.
+ * GM_EINVAL for d < 2 (the reference's round loop underflows at rounds - 1) and for a CRS with fewer than max(d + 1, 2^rounds)
+ * points in either group (commitments need d + 1, the truncation of ipa.rs:581 needs 2^rounds). */
+int gm_ipa_new(uint64_t transcript, uint64_t crs, const uint64_t* a_mont, const uint64_t* b_mont, size_t d, uint64_t* proof);
+/* The fields of the proof.  messages: rounds x (a || b) = 144 limbs; challenges: rounds x 4; batch_challenges: (2 rounds + 1) x 4;
+ * final_foldings (Sumcheck::final_foldings): 2 (rounds - 1) x 18 limbs (Lhs, G1) and x 36 limbs (Rhs, G2);
+ * foldings_ff: lhs || rhs; foldings_fg1: (G1, Fr); foldings_fg2: (Fr, G2). */
+int gm_ipa_rounds(uint64_t proof, size_t* rounds);
+int gm_ipa_messages(uint64_t proof, uint64_t* messages);
+int gm_ipa_challenges(uint64_t proof, uint64_t* challenges);
+int gm_ipa_batch_challenges(uint64_t proof, uint64_t* batch_challenges);
+int gm_ipa_final_foldings(uint64_t proof, uint64_t* lhs_jac, uint64_t* rhs_jac);
+int gm_ipa_foldings_ff(uint64_t proof, uint64_t lhs_rhs_mont[8]);
+int gm_ipa_foldings_fg1(uint64_t proof, uint64_t lhs_jac[18], uint64_t rhs_mont[4]);
+int gm_ipa_foldings_fg2(uint64_t proof, uint64_t lhs_mont[4], uint64_t rhs_jac[36]);
+int gm_ipa_free(uint64_t proof);
+/* A measurement aid (tools/ipa_bench.py, profiles/herring_ipa.md): what gm_ipa_new spent on the HOST making this proof, in
+ * milliseconds -- ms[0] the GT multi-exponentiations, ms[1] the final exponentiations -- and ms[2] the whole call.  Zeros for a
+ * proof that came from gm_ipa_from_fields. */
+int gm_ipa_host_times(uint64_t proof, double ms[3]);
+/* A proof object from its fields, laid out as the getters return them (a verifier that did not run the prover);
+ * foldings_fg1 = lhs_jac || rhs_mont (22 limbs), foldings_fg2 = lhs_mont || rhs_jac (40 limbs). */
+int gm_ipa_from_fields(size_t rounds, const uint64_t* messages, const uint64_t* challenges, const uint64_t* batch_challenges, const uint64_t* final_lhs_jac,
+                       const uint64_t* final_rhs_jac, const uint64_t foldings_ff[8], const uint64_t foldings_fg1[22], const uint64_t foldings_fg2[40],
+                       uint64_t* proof);
+/* InnerProductProof::verify_transcript(vrs, comm_a, comm_b, y): *ok = 1 iff the proof verifies.  Its pairings are one segmented
+ * launch on the device.  A Vrs with fewer than rounds - 1 levels gives GM_EINVAL. */
+int gm_ipa_verify(uint64_t proof, uint64_t vrs, const uint64_t comm_a_jac[18], const uint64_t comm_b_jac[36], const uint64_t y_mont[4], int* ok);
+
 /* ---- Fiat-Shamir transcript (host; no GPU needed) ------------------------------------------------ */
 /* merlin::Transcript::new(label) (merlin 3.0.0, Cargo.lock:606-608); the prover uses
  * Transcript::new(PROTOCOL_NAME) with PROTOCOL_NAME = b"GEMINI-v0" (src/lib.rs:74). */
@@ -547,6 +606,10 @@ int gm_transcript_challenge_bytes(uint64_t handle, const uint8_t* label, size_t 
  * u64 length like Vec<Commitment>). */
 int gm_transcript_append_fr(uint64_t handle, const uint8_t* label, size_t llen, const uint64_t* mont, size_t count);
 int gm_transcript_append_g1(uint64_t handle, const uint8_t* label, size_t llen, const uint64_t* jac, size_t count, int with_len);
+/* append_serializable for `count` consecutive GT elements (72 limbs each): a PairingOutput, or herring's
+ * SumcheckMsg<PairingOutput> (a || b, count = 2).  576 bytes per element: the 12 Fq coefficients in tower order, 48 bytes
+ * little-endian canonical each (ark-serialize of Fp12; a recalled convention like the other two, README). */
+int gm_transcript_append_gt(uint64_t handle, const uint8_t* label, size_t llen, const uint64_t* gt, size_t count);
 /* The ark-serialize framing gm_transcript_append_g1 uses, fixed by the curve crate of the build: 0 (default) =
  * ark-ec's short-Weierstrass default as in ark-test-curves' bls12_381 -- what the reference's examples and tests
  * link (x || y little-endian, flags in the top bits of the last byte); 1 = the zcash framing that ark-bls12-381

@@ -614,10 +614,151 @@ class Transcript {
   void append_serializable(const std::string& label, const G1Projective& c) {
     check(gm_transcript_append_g1(h_, (const uint8_t*)label.data(), label.size(), c.data(), 1, 0));
   }
+  void append_serializable(const std::string& label, const Gt& x) { check(gm_transcript_append_gt(h_, (const uint8_t*)label.data(), label.size(), x.data(), 1)); }
+  void append_serializable(const std::string& label, const GtRoundMsg& m) {  // SumcheckMsg<PairingOutput>: a || b
+    uint64_t ab[144];
+    memcpy(ab, m.a.data(), 576);
+    memcpy(ab + 72, m.b.data(), 576);
+    check(gm_transcript_append_gt(h_, (const uint8_t*)label.data(), label.size(), ab, 2));
+  }
   Fr get_challenge(const std::string& label) {
     Fr r;
     check(gm_transcript_challenge_fr(h_, (const uint8_t*)label.data(), label.size(), r.data()));
     return r;
+  }
+  uint64_t handle() const { return h_; }
+
+ private:
+  uint64_t h_ = 0;
+};
+
+// ---- herring's inner-product argument (src/herring/ipa.rs): Crs, Vrs, InnerProductProof ------------------------------------------
+// `InnerProductProof::generic` (pub(crate)) and `CrsStream` (its fold is a todo!() in the reference) are out of scope.
+class Crs {  // ipa.rs:62-66,172-213: G1 and G2 points resident in HBM
+ public:
+  Crs(const std::vector<G1Affine>& g1s, const std::vector<G2Affine>& g2s) {
+    check(gm_crs_new(g1s.data(), sizeof(G1Affine), g1s.size(), g2s.data(), sizeof(G2Affine), g2s.size(), &h_));
+  }
+  Crs(Crs&& o) noexcept : h_(o.h_) { o.h_ = 0; }
+  ~Crs() {
+    if (h_) gm_crs_free(h_);
+  }
+  Crs(const Crs&) = delete;
+  Crs& operator=(const Crs&) = delete;
+  // the CRS must be longer than the scalars (ipa.rs:180,186)
+  G1Projective commit_g1(const std::vector<Fr>& scalars) const {
+    G1Projective out;
+    check(gm_crs_commit_g1(h_, scalars.empty() ? nullptr : scalars[0].data(), scalars.size(), out.data()));
+    return out;
+  }
+  G2Projective commit_g2(const std::vector<Fr>& scalars) const {
+    G2Projective out;
+    check(gm_crs_commit_g2(h_, scalars.empty() ? nullptr : scalars[0].data(), scalars.size(), out.data()));
+    return out;
+  }
+  uint64_t handle() const { return h_; }
+
+ private:
+  uint64_t h_ = 0;
+};
+
+class Vrs {  // ipa.rs:68-71,215-247
+ public:
+  explicit Vrs(const Crs& crs) { check(gm_vrs_from_crs(crs.handle(), &h_)); }
+  Vrs(Vrs&& o) noexcept : h_(o.h_) { o.h_ = 0; }
+  ~Vrs() {
+    if (h_) gm_vrs_free(h_);
+  }
+  Vrs(const Vrs&) = delete;
+  Vrs& operator=(const Vrs&) = delete;
+  size_t levels() const {
+    size_t n = 0;
+    check(gm_vrs_levels(h_, &n));
+    return n;
+  }
+  // (vk1, vk2) of a level, each (even, odd)
+  std::pair<std::pair<Gt, Gt>, std::pair<Gt, Gt>> level(size_t l) const {
+    uint64_t a[144], b[144];
+    check(gm_vrs_get(h_, l, a, b));
+    std::pair<std::pair<Gt, Gt>, std::pair<Gt, Gt>> r;
+    memcpy(r.first.first.data(), a, 576);
+    memcpy(r.first.second.data(), a + 72, 576);
+    memcpy(r.second.first.data(), b, 576);
+    memcpy(r.second.second.data(), b + 72, 576);
+    return r;
+  }
+  uint64_t handle() const { return h_; }
+
+ private:
+  uint64_t h_ = 0;
+};
+
+class InnerProductProof {  // ipa.rs:54-60
+ public:
+  // InnerProductProof::new(transcript, crs, (a, b)): |a| = |b| >= 2, the CRS holds max(|a| + 1, 2^rounds) points
+  InnerProductProof(Transcript& transcript, const Crs& crs, const std::vector<Fr>& a, const std::vector<Fr>& b) {
+    if (a.size() != b.size()) throw Error(GM_EINVAL, "InnerProductProof: |a| != |b|");
+    check(gm_ipa_new(transcript.handle(), crs.handle(), a.empty() ? nullptr : a[0].data(), b.empty() ? nullptr : b[0].data(), a.size(), &h_));
+  }
+  InnerProductProof(InnerProductProof&& o) noexcept : h_(o.h_) { o.h_ = 0; }
+  ~InnerProductProof() {
+    if (h_) gm_ipa_free(h_);
+  }
+  InnerProductProof(const InnerProductProof&) = delete;
+  InnerProductProof& operator=(const InnerProductProof&) = delete;
+  size_t rounds() const {
+    size_t r = 0;
+    check(gm_ipa_rounds(h_, &r));
+    return r;
+  }
+  std::vector<GtRoundMsg> messages() const {  // sumcheck.messages
+    std::vector<GtRoundMsg> m(rounds());
+    static_assert(sizeof(GtRoundMsg) == 1152, "GtRoundMsg is a || b");
+    check(gm_ipa_messages(h_, (uint64_t*)m.data()));
+    return m;
+  }
+  std::vector<Fr> challenges() const {  // sumcheck.challenges
+    std::vector<Fr> c(rounds());
+    check(gm_ipa_challenges(h_, c[0].data()));
+    return c;
+  }
+  std::vector<Fr> batch_challenges() const {
+    std::vector<Fr> c(2 * rounds() + 1);
+    check(gm_ipa_batch_challenges(h_, c[0].data()));
+    return c;
+  }
+  std::vector<std::pair<G1Projective, G2Projective>> final_foldings() const {  // sumcheck.final_foldings
+    const size_t k = 2 * (rounds() - 1);
+    std::vector<G1Projective> l(k);
+    std::vector<G2Projective> r(k);
+    check(gm_ipa_final_foldings(h_, k ? l[0].data() : nullptr, k ? r[0].data() : nullptr));
+    std::vector<std::pair<G1Projective, G2Projective>> out(k);
+    for (size_t i = 0; i < k; i++) out[i] = {l[i], r[i]};
+    return out;
+  }
+  std::pair<Fr, Fr> foldings_ff() const {
+    uint64_t v[8];
+    check(gm_ipa_foldings_ff(h_, v));
+    std::pair<Fr, Fr> r;
+    memcpy(r.first.data(), v, 32);
+    memcpy(r.second.data(), v + 4, 32);
+    return r;
+  }
+  std::pair<G1Projective, Fr> foldings_fg1() const {
+    std::pair<G1Projective, Fr> r;
+    check(gm_ipa_foldings_fg1(h_, r.first.data(), r.second.data()));
+    return r;
+  }
+  std::pair<Fr, G2Projective> foldings_fg2() const {
+    std::pair<Fr, G2Projective> r;
+    check(gm_ipa_foldings_fg2(h_, r.first.data(), r.second.data()));
+    return r;
+  }
+  // verify_transcript (ipa.rs:250-343): true for Ok(())
+  bool verify_transcript(const Vrs& vrs, const G1Projective& comm_a, const G2Projective& comm_b, const Fr& y) const {
+    int ok = 0;
+    check(gm_ipa_verify(h_, vrs.handle(), comm_a.data(), comm_b.data(), y.data(), &ok));
+    return ok != 0;
   }
   uint64_t handle() const { return h_; }
 
