@@ -50,6 +50,13 @@ class SparseMatrix:
         capi.check(capi.load().gm_spm_mul(C.c_uint64(self.handle), C.c_uint64(x.handle), C.c_uint64(y.handle)))
         return y
 
+    def bilinear_pm(self, powers: FrVec, weights: FrVec):
+        """gm_spm_bilinear_pm: (weights^T M powers, the same with (-1)^c powers[c]) in one pass, no intermediate vector -- the snark
+        verifier's product_matrix_vector + ip at powers(beta) and powers(-beta) (src/snark/verifier.rs:63-88)"""
+        pos, neg = np.zeros(4, dtype=np.uint64), np.zeros(4, dtype=np.uint64)
+        capi.check(capi.load().gm_spm_bilinear_pm(C.c_uint64(self.handle), C.c_uint64(powers.handle), C.c_uint64(weights.handle), capi.ptr(pos), capi.ptr(neg)))
+        return pos, neg
+
     def free(self):
         if self.handle:
             capi.check(capi.load().gm_spm_free(C.c_uint64(self.handle)))

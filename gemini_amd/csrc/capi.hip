@@ -290,6 +290,7 @@ int fr_add_at(Context* C, FrVec* v, const size_t* idx, const uint64_t* vals, siz
 int fr_fill(Context* C, FrVec* v, const uint64_t val[4]);
 int fr_reverse(Context* C, FrVec* in, FrVec* out);
 int spm_mul(Context* C, SparseMatrix* M, FrVec* x, FrVec* y);
+int spm_bilinear_pm(Context* C, SparseMatrix* M, FrVec* p, FrVec* w, uint64_t pos[4], uint64_t neg[4]);
 int fr_div_linear_factors(Context* C, FrVec* f, const uint64_t* points, size_t k, FrVec* q, uint64_t* rem_out);
 int fr_gather(Context* C, FrVec* src, const IdxVec* index, FrVec* out);
 int idx_extend_frequency(Context* C, const IdxVec* index, size_t set_len, IdxVec* out);
@@ -1591,6 +1592,15 @@ int gm_spm_mul(uint64_t matrix, uint64_t x, uint64_t y) {
   GM_VEC(vx, x, "spm_mul");
   GM_VEC(vy, y, "spm_mul");
   return spm_mul(C, M, vx, vy);
+}
+int gm_spm_bilinear_pm(uint64_t matrix, uint64_t powers, uint64_t weights, uint64_t out_pos_mont[4], uint64_t out_neg_mont[4]) {
+  GM_CTX();
+  GM_CHECK(out_pos_mont && out_neg_mont, GM_EINVAL, "spm_bilinear_pm: null pointer");
+  SparseMatrix* M = find_in(C, C->matrices, matrix);
+  GM_CHECK(M != nullptr, GM_EHANDLE, "spm_bilinear_pm: unknown matrix handle %llu", (unsigned long long)matrix);
+  GM_VEC(vp, powers, "spm_bilinear_pm");
+  GM_VEC(vw, weights, "spm_bilinear_pm");
+  return spm_bilinear_pm(C, M, vp, vw, out_pos_mont, out_neg_mont);
 }
 
 // ---- sumcheck ---------------------------------------------------------------------------------

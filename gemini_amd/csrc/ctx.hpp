@@ -189,6 +189,13 @@ struct IpaProof {
   double host_ms[3] = {0, 0, 0};  // of gm_ipa_new: host GT multi-exponentiations, host final exponentiations, the whole call (gm_ipa_host_times)
 };
 
+// kzg::VerifierKey (src/kzg/mod.rs:141-149; verifier.cpp): host records, Montgomery, identity = all zero
+struct VerifierKey {
+  std::vector<uint64_t> g1;  // n1 x 12 limbs: the first max_eval_points powers of g
+  std::vector<uint64_t> g2;  // n2 x 24 limbs: max_eval_points + 1 powers of g2
+  size_t n1 = 0, n2 = 0;
+};
+
 // G2 bases (g2msm.hip): n x 192 bytes, x.c0 | x.c1 | y.c0 | y.c1 in the device form of g1.cuh; identity = all zero
 struct G2Bases {
   uint8_t* d = nullptr;
@@ -332,6 +339,7 @@ struct Context {
   std::unordered_map<uint64_t, std::unique_ptr<Vrs>> vrs;
   std::unordered_map<uint64_t, std::unique_ptr<IpaProof>> ipa;
   std::unordered_map<uint64_t, std::unique_ptr<G2Bases>> g2_bases;
+  std::unordered_map<uint64_t, std::unique_ptr<VerifierKey>> vks;
   std::unordered_map<uint64_t, std::unique_ptr<MsmStream>> msm_streams;
   std::unordered_map<uint64_t, std::unique_ptr<IdxVec>> indices;
   MsmWorkspace msm;

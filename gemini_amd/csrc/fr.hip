@@ -817,6 +817,37 @@ __global__ __launch_bounds__(256) void k_spmv(const uint64_t* __restrict__ rowpt
   }
 }
 
+// The bilinear form w^T M p of the snark verifier (src/snark/verifier.rs:63-88: product_matrix_vector against powers(beta) and
+// powers(-beta), then ip against a weight vector) in ONE pass over the CSR matrix, with no n-element intermediate:
+// powers(-beta)[c] = (-1)^c beta^c, so the products of a row are summed by the parity of their column and
+//   pos = sum_r w[r] (even_r + odd_r),  neg = sum_r w[r] (even_r - odd_r)
+// come from one gather and one product per entry.  Row-per-lane like k_spmv; per block the partial (pos, neg).
+__global__ __launch_bounds__(256) void k_spm_bilinear_pm(const uint64_t* __restrict__ rowptr, const uint32_t* __restrict__ cols,
+                                                         const uint8_t* __restrict__ vals, size_t nrows, const uint8_t* __restrict__ p,
+                                                         size_t np, const uint8_t* __restrict__ w, uint8_t* __restrict__ partials) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds[4 * 2 * FR_BYTES];
+  Fr acc[2] = {Fr::zero(), Fr::zero()};  // sum_r w[r] even_r, sum_r w[r] odd_r
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nrows; i += (size_t)gridDim.x * blockDim.x) {
+    Fr even = Fr::zero(), odd = Fr::zero();
+    for (uint64_t k = rowptr[i]; k < rowptr[i + 1]; k++) {
+      const uint32_t c = cols[k];
+      const Fr t = fr_mul(fp_load<FrParams>(vals + k * FR_BYTES), fr_load_or_zero(p, c, np));
+      if (c & 1)
+        odd = fr_add(odd, t);
+      else
+        even = fr_add(even, t);
+    }
+    const Fr wi = fp_load<FrParams>(w + i * FR_BYTES);
+    acc[0] = fr_add(acc[0], fr_mul(wi, even));
+    acc[1] = fr_add(acc[1], fr_mul(wi, odd));
+  }
+  block_sum<2>(acc, lds);
+  if (threadIdx.x == 0) {
+    fp_store<FrParams>(partials + (size_t)blockIdx.x * 2 * FR_BYTES, fr_add(acc[0], acc[1]));
+    fp_store<FrParams>(partials + ((size_t)blockIdx.x * 2 + 1) * FR_BYTES, fr_sub(acc[0], acc[1]));
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // space prover (src/subprotocols/sumcheck/space_prover.rs): nothing but the ORIGINAL big-endian
 // streams and the challenges is kept; every message is recomputed from the streams.
@@ -2082,6 +2113,30 @@ int spm_mul(Context* C, SparseMatrix* M, FrVec* x, FrVec* y) {
   GM_HIP(hipGetLastError());
   GM_HIP(hipStreamSynchronize(C->stream));
   y->len = M->nrows;
+  return GM_OK;
+}
+
+// pos = w^T M p, neg = w^T M p' with p'[c] = (-1)^c p[c]; w may be longer than the rows (tensor(rho) has 2^k >= n entries and
+// the reference's ip_unsafe zip-truncates), never shorter.  The last reduction is fr_ip's
+int spm_bilinear_pm(Context* C, SparseMatrix* M, FrVec* p, FrVec* w, uint64_t pos[4], uint64_t neg[4]) {
+  GM_FR_LOCK(C);
+  GM_CHECK(w->len >= M->nrows, GM_EINVAL, "spm_bilinear_pm: %zu weights for %zu rows", w->len, M->nrows);
+  gmh::Fr s[2] = {gmh::Fr::zero(), gmh::Fr::zero()};
+  if (M->nrows && M->nnz) {
+    const unsigned blocks = grid_for(M->nrows, 512);
+    int rc = C->fr_scratch.ensure(1 << 20);
+    if (rc) return rc;
+    const bool zc = (C->zero_copy & 1) != 0;
+    hipLaunchKernelGGL(k_spm_bilinear_pm, dim3(blocks), dim3(256), 0, C->stream, M->rowptr, M->cols, M->vals, M->nrows, p->d, p->len, w->d,
+                       zc ? reinterpret_cast<uint8_t*>(C->host_small) : C->fr_scratch.as<uint8_t>());
+    GM_HIP(hipGetLastError());
+    if (!zc) GM_HIP(hipMemcpyAsync(C->host_small, C->fr_scratch.p, (size_t)blocks * 2 * FR_BYTES, hipMemcpyDeviceToHost, C->stream));
+    GM_HIP(hipStreamSynchronize(C->stream));
+    for (unsigned i = 0; i < blocks; i++)
+      for (int k = 0; k < 2; k++) s[k] = s[k] + gmh::Fr::from_limbs(C->host_small + ((size_t)i * 2 + k) * 4);
+  }
+  s[0].to_limbs(pos);
+  s[1].to_limbs(neg);
   return GM_OK;
 }
 

@@ -33,8 +33,8 @@ def _warn_truncated(poly_len: int, key_len: int):
 
 
 class CommitterKey:
-    """src/kzg/time.rs:24-27.  powers_of_g lives on the GPU; powers_of_g2 is only used by the
-    verifier (out of scope) so just its length (max_eval_points + 1) is kept."""
+    """src/kzg/time.rs:24-27.  powers_of_g lives on the GPU; powers_of_g2 (max_eval_points + 1 affine points) is the
+    verifier's half: VerifierKey.from_committer_key takes it from here."""
 
     def __init__(self, powers_of_g: G1Bases, max_eval_points: int, powers_of_g2=None):
         self.powers_of_g = powers_of_g
@@ -139,6 +139,109 @@ class CommitterKey:
             return self.open_multi_points(batched, pts)
         finally:
             batched.free()
+
+
+class VerificationError(Exception):
+    """`VerificationError` of src/errors.rs: what every `verify` of this package raises on a rejected proof"""
+
+
+def _fq_mont(v: int) -> list:
+    return [(((v << 384) % _Q) >> (64 * i)) & (2**64 - 1) for i in range(6)]
+
+
+def g2_records(points) -> np.ndarray:
+    """affine G2 points as gemini_amd.g2 holds them (((x0, x1), (y0, y1)) or None) -> the 192-byte records of the C ABI"""
+    out = np.zeros((len(points), 24), dtype=np.uint64)
+    for i, p in enumerate(points):
+        if p is not None:
+            out[i] = np.array(_fq_mont(p[0][0]) + _fq_mont(p[0][1]) + _fq_mont(p[1][0]) + _fq_mont(p[1][1]), dtype=np.uint64)
+    return out
+
+
+class VerifierKey:
+    """src/kzg/mod.rs:141-149: the first max_eval_points powers of g and max_eval_points + 1 powers of g2, held by the library
+    (gm_vk_*, gemini_amd/csrc/verifier.cpp).  verify / verify_multi_points return normally or raise VerificationError."""
+
+    def __init__(self, handle: int):
+        self.handle = handle
+
+    @classmethod
+    def from_powers(cls, powers_of_g: np.ndarray, powers_of_g2: np.ndarray) -> "VerifierKey":
+        """host records: (n1, 12) and (n2, 24) Montgomery limbs (96- and 192-byte strides)"""
+        import ctypes as C
+
+        capi.ensure_init()
+        g1 = capi.u64(powers_of_g).reshape(-1, 12)
+        g2 = capi.u64(powers_of_g2).reshape(-1, 24)
+        h = C.c_uint64()
+        capi.check(capi.load().gm_vk_new(capi.ptr(g1), C.c_size_t(96), C.c_size_t(len(g1)), capi.ptr(g2), C.c_size_t(192), C.c_size_t(len(g2)), C.byref(h)))
+        return cls(h.value)
+
+    @classmethod
+    def from_committer_key(cls, ck: "CommitterKey") -> "VerifierKey":
+        """`From<&CommitterKey>` (src/kzg/time.rs:29-40)"""
+        assert ck.powers_of_g2 is not None, "this key was built without its G2 half"
+        n1 = min(ck.max_eval_points(), len(ck.powers_of_g))
+        return cls.from_powers(ck.powers_of_g.download(0, n1), g2_records(ck.powers_of_g2))
+
+    @classmethod
+    def from_trapdoor(cls, tau_canonical: np.ndarray, max_eval_points: int, g_affine: np.ndarray | None = None, g2_affine: np.ndarray | None = None) -> "VerifierKey":
+        """gm_vk_from_trapdoor: the setup aid that pairs with CommitterKey.new (g, g2 default to the standard generators;
+        g2_affine: a 24-limb record)"""
+        import ctypes as C
+
+        from . import g2 as G2
+
+        capi.ensure_init()
+        g = capi.u64(g1_generator_mont() if g_affine is None else g_affine).reshape(12)
+        g2 = capi.u64(g2_records([G2.generator()])[0] if g2_affine is None else g2_affine).reshape(24)
+        h = C.c_uint64()
+        capi.check(capi.load().gm_vk_from_trapdoor(capi.ptr(g), capi.ptr(g2), capi.ptr(capi.u64(tau_canonical).reshape(4)), C.c_size_t(max_eval_points), C.byref(h)))
+        return cls(h.value)
+
+    def powers_of_g2_bytes(self, enc: int | None = None) -> bytes:
+        """gm_vk_g2_bytes: equals CommitterKey.powers_of_g2_bytes() of the key this one came from"""
+        import ctypes as C
+
+        from .transcript import default_group_encoding
+
+        enc = default_group_encoding() if enc is None else enc
+        n = C.c_size_t()
+        capi.check(capi.load().gm_vk_g2_bytes(C.c_uint64(self.handle), C.c_int(enc), None, C.c_size_t(0), C.byref(n)))
+        buf = (C.c_uint8 * n.value)()
+        capi.check(capi.load().gm_vk_g2_bytes(C.c_uint64(self.handle), C.c_int(enc), buf, C.c_size_t(n.value), C.byref(n)))
+        return bytes(buf)
+
+    def verify(self, commitment, alpha_mont, evaluation_mont, proof) -> None:
+        """src/kzg/mod.rs:155-175"""
+        import ctypes as C
+
+        ok = C.c_int()
+        capi.check(capi.load().gm_kzg_verify(C.c_uint64(self.handle), capi.ptr(capi.u64(commitment).reshape(18)), capi.ptr(capi.u64(alpha_mont).reshape(4)),
+                                             capi.ptr(capi.u64(evaluation_mont).reshape(4)), capi.ptr(capi.u64(proof).reshape(18)), C.byref(ok)))
+        if not ok.value:
+            raise VerificationError("verify: pairing check failed")
+
+    def verify_multi_points(self, commitments, eval_points_mont, evaluations_mont, proof, open_chal_mont) -> None:
+        """src/kzg/mod.rs:181-244.  evaluations: one row of len(eval_points) values per commitment"""
+        import ctypes as C
+
+        cm = capi.u64(np.asarray(commitments, dtype=np.uint64).reshape(-1, 18))
+        pts = capi.u64(np.asarray(eval_points_mont, dtype=np.uint64).reshape(-1, 4))
+        ev = capi.u64(np.asarray(evaluations_mont, dtype=np.uint64).reshape(-1, len(pts), 4))
+        ok = C.c_int()
+        capi.check(capi.load().gm_kzg_verify_multi_points(C.c_uint64(self.handle), capi.ptr(cm), C.c_size_t(len(cm)), capi.ptr(pts), C.c_size_t(len(pts)), capi.ptr(ev),
+                                                          C.c_size_t(len(ev)), capi.ptr(capi.u64(proof).reshape(18)), capi.ptr(capi.u64(open_chal_mont).reshape(4)),
+                                                          C.byref(ok)))
+        if not ok.value:
+            raise VerificationError("verify_multi_points: pairing check failed")
+
+    def free(self):
+        import ctypes as C
+
+        if self.handle:
+            capi.check(capi.load().gm_vk_free(C.c_uint64(self.handle)))
+            self.handle = 0
 
 
 class FoldedPolynomialTree:

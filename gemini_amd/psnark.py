@@ -244,6 +244,25 @@ class Proof:
             return _new_time_native(ck, r1cs_stream.r1cs, index, elastic=(ck, r1cs_stream, max_msm_buffer))
         return _stepwise("new_elastic")(ck, r1cs_stream, index, max_msm_buffer)
 
+    def verify(self, r1cs: R1cs, vk, index: list, num_non_zero: int | None = None) -> None:
+        """src/psnark/verifier.rs:88-565 (gm_psnark_verify): returns normally or raises VerificationError.  `vk`: a kzg.VerifierKey of
+        max_eval_points >= 3; num_non_zero: entries of the joint support of A, B, C (default: computed from the instance)."""
+        import ctypes as C
+
+        from . import capi
+        from .kzg import VerificationError
+        from .transcript import default_group_encoding
+
+        if num_non_zero is None:
+            num_non_zero = len(_joint_device(r1cs).row_index)
+        P, keep = _pack_proof(self)
+        idx = np.ascontiguousarray(np.stack(index), dtype=np.uint64).reshape(5, 18)
+        ok = C.c_int()
+        capi.check(capi.load().gm_psnark_verify(C.c_uint64(r1cs.x.handle if r1cs.x is not None else 0), C.c_size_t(len(r1cs.z)), C.c_size_t(num_non_zero),
+                                                capi.ptr(idx), C.c_uint64(vk.handle), C.c_int(int(default_group_encoding())), C.byref(P), C.byref(ok)))
+        if not ok.value:
+            raise VerificationError("psnark: rejected")
+
     def serialize(self, compress: bool = True, enc=0) -> bytes:
         """derive(CanonicalSerialize) of src/psnark/mod.rs:29-51 (formats: gemini_amd/wire.py)"""
         from . import wire
@@ -350,6 +369,65 @@ def _unpack_proof(P, bufs) -> "Proof":
         ralpha_star_acc_mu_evals=[A(P.ralpha_star_acc_mu_evals[k]) for k in range(10)], ralpha_star_acc_mu_proof=A(P.ralpha_star_acc_mu_proof),
         rstars_vals=[A(P.rstars_vals[0]), A(P.rstars_vals[1])], third_sumcheck_msgs=(msgs(2), third_ff), tensorcheck_proof=tc)
     return proof
+
+
+def _pack_proof(proof: "Proof"):
+    """the gm_psnark_proof record of `proof` (from a prover or from Proof.deserialize) and the arrays it points into: the inverse of
+    _unpack_proof (the products of the three sorted vectors, which the proof does not carry, stay zero)"""
+    import ctypes as C
+
+    from . import capi
+
+    _, ProofRec = _psnark_ctypes()
+    U = C.POINTER(C.c_uint64)
+    A = lambda x, shape: capi.u64(np.asarray(x, dtype=np.uint64).reshape(shape))  # noqa: E731
+    put = lambda dst, x: C.memmove(dst, A(x, -1).ctypes.data, C.sizeof(dst))  # noqa: E731
+    pair = lambda f: np.concatenate([A(f[0], 4), A(f[1], 4)])  # noqa: E731
+    P = ProofRec()
+    keep = []
+    sumchecks = (proof.first_sumcheck_msgs, proof.second_sumcheck_msgs, proof.third_sumcheck_msgs)
+    for k, (msgs, ff) in enumerate(sumchecks):
+        m = A([pair(x) for x in msgs], (-1, 8))
+        keep.append(m)
+        P.rounds[k] = len(m)
+        P.messages[k] = m.ctypes.data_as(U)
+        if k < 2:
+            put(P.final_foldings[k], pair(ff[0]))
+    third = sumchecks[2][1]
+    if len(third) != 13 or len(proof.r_star_commitments) != 3 or len(proof.ep_msgs.acc_v_commitments) != 9 or len(proof.ep_msgs.claimed_sumchecks) != 9 \
+            or len(proof.ralpha_star_acc_mu_evals) != 10 or len(proof.rstars_vals) != 2 or len(proof.tensorcheck_proof.base_polynomials_evaluations) != 22:
+        from .kzg import VerificationError
+
+        raise VerificationError("psnark: the proof does not have the shape of a psnark::Proof")
+    for j in range(13):
+        put(P.third_final_foldings[j], pair(third[j]))
+    put(P.witness_commitment, proof.witness_commitment)
+    put(P.zc_alpha, proof.zc_alpha)
+    for k in range(3):
+        put(P.r_star_commitments[k], proof.r_star_commitments[k])
+    put(P.z_star_commitment, proof.z_star_commitment)
+    for k, c in enumerate((proof.sorted_r_commitment, proof.sorted_alpha_commitment, proof.sorted_z_commitment)):
+        put(P.sorted_commitments[k], c)
+    for k, v in ((0, proof.set_r_ep), (1, proof.subset_r_ep), (3, proof.set_alpha_ep), (4, proof.subset_alpha_ep), (6, proof.set_z_ep), (7, proof.subset_z_ep)):
+        put(P.products[k], v)
+    for k in range(9):
+        put(P.acc_v_commitments[k], proof.ep_msgs.acc_v_commitments[k])
+        put(P.claimed_sumchecks[k], proof.ep_msgs.claimed_sumchecks[k])
+    for k in range(10):
+        put(P.ralpha_star_acc_mu_evals[k], proof.ralpha_star_acc_mu_evals[k])
+    put(P.ralpha_star_acc_mu_proof, proof.ralpha_star_acc_mu_proof)
+    for k in range(2):
+        put(P.rstars_vals[k], proof.rstars_vals[k])
+    tc = proof.tensorcheck_proof
+    nf = len(tc.folded_polynomials_commitments)
+    fc, fe = A(tc.folded_polynomials_commitments, (nf, 18)), A(tc.folded_polynomials_evaluations, (nf, 8))
+    keep += [fc, fe]
+    P.nfold = P.cap_folds = nf
+    P.fold_commitments, P.fold_evaluations = fc.ctypes.data_as(U), fe.ctypes.data_as(U)
+    put(P.evaluation_proof, tc.evaluation_proof)
+    for k in range(22):
+        put(P.base_evaluations[k], tc.base_polynomials_evaluations[k])
+    return P, keep
 
 
 def _new_time_native(ck: CommitterKey, r1cs: R1cs, index: list, preprocess_in_library: bool = False, elastic=None) -> "Proof":

@@ -130,6 +130,57 @@ def _new_elastic_native(r1cs_stream, ck_stream, max_msm_buffer: int) -> "Proof":
     return _unpack_native(P, m, fc, fe, _ELASTIC_SPAN_NAMES)
 
 
+def _pack_native(proof: "Proof"):
+    """a gm_snark_proof record of `proof` (from a prover or from Proof.deserialize) and the arrays it points into"""
+    import ctypes as C
+
+    from . import capi
+
+    U = C.POINTER(C.c_uint64)
+    A = lambda x, shape: capi.u64(np.asarray(x, dtype=np.uint64).reshape(shape))  # noqa: E731
+    P = _GmSnarkProof()
+    keep = []
+    for k, (msgs, ff) in enumerate((proof.first_sumcheck_msgs, proof.second_sumcheck_msgs)):
+        m = A([np.concatenate([A(a, 4), A(b, 4)]) for a, b in msgs], (-1, 8))
+        keep.append(m)
+        P.rounds[k] = len(m)
+        P.messages[k] = m.ctypes.data_as(U)
+        P.final_foldings[k] = (C.c_uint64 * 8)(*[int(v) for v in np.concatenate([A(ff[0][0], 4), A(ff[0][1], 4)])])
+    tc = proof.tensorcheck_proof
+    nf = len(tc.folded_polynomials_commitments)
+    fc, fe = A(tc.folded_polynomials_commitments, (nf, 18)), A(tc.folded_polynomials_evaluations, (nf, 8))
+    keep += [fc, fe]
+    P.nfold = nf
+    P.fold_commitments, P.fold_evaluations = fc.ctypes.data_as(U), fe.ctypes.data_as(U)
+    P.witness_commitment = (C.c_uint64 * 18)(*[int(v) for v in A(proof.witness_commitment, 18)])
+    P.zc_alpha = (C.c_uint64 * 4)(*[int(v) for v in A(proof.zc_alpha, 4)])
+    P.evaluation_proof = (C.c_uint64 * 18)(*[int(v) for v in A(tc.evaluation_proof, 18)])
+    P.base_evaluations = (C.c_uint64 * 12)(*[int(v) for v in A(tc.base_polynomials_evaluations[0], 12)])
+    return P, keep
+
+
+def _proof_verify(self, r1cs: R1cs, vk) -> None:
+    """src/snark/verifier.rs:19-119 (gm_snark_verify): returns normally or raises VerificationError.  `vk`: a kzg.VerifierKey"""
+    import ctypes as C
+
+    from . import capi
+    from .kzg import VerificationError
+    from .transcript import default_group_encoding
+
+    if len(self.tensorcheck_proof.base_polynomials_evaluations) != 1:
+        raise VerificationError("snark: one base polynomial (the witness) expected")
+    P, keep = _pack_native(self)
+    mats = (C.c_uint64 * 3)(r1cs.a.handle, r1cs.b.handle, r1cs.c.handle)
+    ok = C.c_int()
+    capi.check(capi.load().gm_snark_verify(mats, C.c_uint64(r1cs.x.handle if r1cs.x is not None else 0), C.c_uint64(vk.handle), C.c_int(int(default_group_encoding())),
+                                           C.byref(P), C.byref(ok)))
+    if not ok.value:
+        raise VerificationError("snark: rejected")
+
+
+Proof.verify = _proof_verify
+
+
 # ---- CanonicalSerialize of the proof (src/snark/mod.rs:75-82): gemini_amd/wire.py holds the formats ------------
 def _proof_serialize(self, compress: bool = True, enc=0) -> bytes:
     from . import wire

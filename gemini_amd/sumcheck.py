@@ -316,3 +316,42 @@ class Sumcheck:
             return Sumcheck.prove_native(transcript, prover) if native else Sumcheck.prove(transcript, prover)
         finally:
             prover.free()
+
+
+class Subclaim:
+    """src/subprotocols/sumcheck/subclaim.rs:10-21: the verifier's view of a sumcheck -- the challenges it drew and the final
+    foldings it accepted (gm_sumcheck_subclaim / gm_sumcheck_subclaim_batch, gemini_amd/csrc/verifier.cpp)."""
+
+    def __init__(self, challenges, final_foldings):
+        self.challenges = challenges
+        self.final_foldings = final_foldings
+
+    @staticmethod
+    def _run(transcript, messages, final_foldings, asserted, batch: bool) -> "Subclaim":
+        from .kzg import VerificationError
+
+        msgs = capi.u64(np.asarray([np.concatenate([capi.u64(a).reshape(4), capi.u64(b).reshape(4)]) for a, b in messages], dtype=np.uint64).reshape(-1, 8))
+        ff = capi.u64(np.asarray([np.concatenate([capi.u64(a).reshape(4), capi.u64(b).reshape(4)]) for a, b in final_foldings], dtype=np.uint64).reshape(-1, 8))
+        sums = capi.u64(np.asarray(asserted, dtype=np.uint64).reshape(-1, 4))
+        chs = np.zeros((max(len(msgs), 1), 4), dtype=np.uint64)
+        ok = C.c_int()
+        if batch:
+            assert len(ff) == len(sums), "one pair of final foldings per asserted sum"
+            capi.check(capi.load().gm_sumcheck_subclaim_batch(C.c_uint64(transcript.handle), capi.ptr(msgs), C.c_size_t(len(msgs)), capi.ptr(ff), capi.ptr(sums),
+                                                              C.c_size_t(len(sums)), capi.ptr(chs), C.byref(ok)))
+        else:
+            capi.check(capi.load().gm_sumcheck_subclaim(C.c_uint64(transcript.handle), capi.ptr(msgs), C.c_size_t(len(msgs)), capi.ptr(ff), capi.ptr(sums), capi.ptr(chs),
+                                                        C.byref(ok)))
+        if not ok.value:
+            raise VerificationError("sumcheck: the final foldings do not meet the reduced claim")
+        return Subclaim([chs[i].copy() for i in range(len(msgs))], list(final_foldings))
+
+    @staticmethod
+    def new(transcript, messages, final_foldings, asserted_sum_mont) -> "Subclaim":
+        """:23-43.  final_foldings: [(f0, g0)] as Sumcheck.final_foldings holds them"""
+        return Subclaim._run(transcript, messages, final_foldings[:1], asserted_sum_mont, False)
+
+    @staticmethod
+    def new_batch(transcript, messages, final_foldings, asserted_sums_mont) -> "Subclaim":
+        """:45-75"""
+        return Subclaim._run(transcript, messages, final_foldings, asserted_sums_mont, True)

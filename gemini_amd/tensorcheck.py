@@ -20,6 +20,11 @@ class _Proof(C.Structure):
                 ("evaluation_proof", C.c_uint64 * 18), ("nbase", C.c_size_t), ("base_evaluations", C.c_void_p)]
 
 
+class _Claim(C.Structure):
+    _fields_ = [("asserted_res_mont", C.c_void_p), ("nasserted", C.c_size_t), ("fold_randomness_mont", C.c_void_p), ("nrandomness", C.c_size_t),
+                ("direct_base_evals_mont", C.c_uint64 * 8)]
+
+
 def foldings_polynomial(polynomial: FrVec, challenges_mont) -> list:
     """:124-133  successive folds with all challenges but the last (strip_last)"""
     out = []
@@ -72,3 +77,36 @@ class TensorcheckProof:
         n = rec.nfold
         return TensorcheckProof([fc[i].copy() for i in range(n)], [fe[i].copy() for i in range(n)], np.array(rec.evaluation_proof, dtype=np.uint64),
                                 [be[i].copy() for i in range(len(bases))])
+
+    def _record(self):
+        """the gm_tensorcheck_proof record of this proof and the arrays it points into (keep them alive)"""
+        n = len(self.folded_polynomials_commitments)
+        fc = capi.u64(np.asarray(self.folded_polynomials_commitments, dtype=np.uint64).reshape(n, 18))
+        fe = capi.u64(np.asarray(self.folded_polynomials_evaluations, dtype=np.uint64).reshape(n, 8))
+        nb = len(self.base_polynomials_evaluations)
+        be = capi.u64(np.asarray(self.base_polynomials_evaluations, dtype=np.uint64).reshape(nb, 12))
+        ep = (C.c_uint64 * 18)(*[int(v) for v in capi.u64(self.evaluation_proof).reshape(18)])
+        return _Proof(n, n, fc.ctypes.data, fe.ctypes.data, ep, nb, be.ctypes.data), (fc, fe, be)
+
+    def verify(self, transcript, vk, asserted_res_vec, base_polynomials_commitments, direct_base_polynomials_evaluations, fold_randomness, eval_chal,
+               batch_challenge) -> None:
+        """:286-385 (gm_tensorcheck_verify): one entry of asserted_res_vec / direct_base_polynomials_evaluations / fold_randomness per
+        tensor-check instance, all Montgomery.  Raises VerificationError on a rejected proof."""
+        from .kzg import VerificationError
+
+        rec, keep = self._record()
+        k = len(fold_randomness)
+        assert len(asserted_res_vec) == k and len(direct_base_polynomials_evaluations) == k
+        claims = (_Claim * max(k, 1))()
+        for i in range(k):
+            ar = capi.u64(np.asarray(asserted_res_vec[i], dtype=np.uint64).reshape(-1, 4))
+            fr_ = capi.u64(np.asarray(fold_randomness[i], dtype=np.uint64).reshape(-1, 4))
+            de = capi.u64(np.asarray(direct_base_polynomials_evaluations[i], dtype=np.uint64).reshape(8))
+            keep += (ar, fr_)
+            claims[i] = _Claim(ar.ctypes.data, len(ar), fr_.ctypes.data, len(fr_), (C.c_uint64 * 8)(*[int(v) for v in de]))
+        bc = capi.u64(np.asarray(base_polynomials_commitments, dtype=np.uint64).reshape(-1, 18))
+        ok = C.c_int()
+        capi.check(capi.load().gm_tensorcheck_verify(C.c_uint64(transcript.handle), C.c_uint64(vk.handle), C.byref(rec), capi.ptr(bc), C.c_size_t(len(bc)), claims,
+                                                     C.c_size_t(k), capi.ptr(capi.u64(eval_chal).reshape(4)), capi.ptr(capi.u64(batch_challenge).reshape(4)), C.byref(ok)))
+        if not ok.value:
+            raise VerificationError("tensorcheck: rejected")

@@ -370,6 +370,14 @@ int gm_spm_register(const uint64_t* rowptr, const uint32_t* cols, const uint64_t
                     size_t nnz, uint64_t* handle);
 int gm_spm_free(uint64_t handle);
 int gm_spm_mul(uint64_t matrix, uint64_t x, uint64_t y);
+/* The bilinear form of the snark verifier (src/snark/verifier.rs:63-88: product_matrix_vector against powers(beta) and powers(-beta),
+ * then ip against a weight vector) in ONE pass over the matrix, no n-element intermediate:
+ *   out_pos = sum_r weights[r] * sum_{(v, c) in row r} v * powers[c],   out_neg = the same with (-1)^c * powers[c]
+ * (powers(-beta)[c] = (-1)^c beta^c: the row sums are kept by the parity of the column).  Bit for bit the values of gm_fr_powers ->
+ * gm_spm_mul -> gm_fr_ip with +-beta.  A column index >= len(powers) contributes zero (as in gm_spm_mul); weights may be LONGER than
+ * the rows (tensor(rho) has 2^k >= n entries and the reference's ip_unsafe zip-truncates), shorter is GM_EINVAL; no rows or no
+ * entries give (0, 0). */
+int gm_spm_bilinear_pm(uint64_t matrix, uint64_t powers, uint64_t weights, uint64_t out_pos_mont[4], uint64_t out_neg_mont[4]);
 int gm_spm_shape(uint64_t matrix, size_t* nrows_or_null, size_t* ncols_or_null, size_t* nnz_or_null);
 /* The CSR arrays back on the host (rowptr: nrows + 1, cols: nnz, vals: nnz x 4 Montgomery limbs; any pointer may be NULL). */
 int gm_spm_download(uint64_t matrix, uint64_t* rowptr, uint32_t* cols, uint64_t* vals_mont);
@@ -780,6 +788,59 @@ int gm_psnark_preprocess(uint64_t a, uint64_t b, uint64_t c, size_t num_variable
 int gm_psnark_preprocess_free(gm_psnark_instance* instance);
 /* psnark::Proof::index (src/psnark/time_prover.rs:49-64): commitments to row, col, val_a, val_b, val_c; out = 5 x 18 limbs */
 int gm_psnark_index(const gm_psnark_instance* instance, uint64_t ck_bases, uint64_t* out_jac);
+
+/* ---- the verifiers (gemini_amd/csrc/verifier.cpp) ---------------------------------------------------------------------------
+ * What replaces `proof.verify(&r1cs, &vk)`: the reference's verifiers as host orchestration over the entry points above.  Every
+ * group operation is a device MSM, every KZG check ONE multi-pairing of two pairs with one final exponentiation compared with 1
+ * (so the check is indifferent to the factor-3 question of the pairing block), the O(n) part of the snark verifier is
+ * gm_fr_powers / gm_fr_tensor / gm_fr_hadamard, three gm_spm_bilinear_pm and one gm_fr_eval_le.
+ * Scalars are Montgomery limbs, G1 elements Jacobian (18 limbs, any representative).  *ok = 1: accepted, 0: REJECTED -- a rejected proof
+ * is a result (return value GM_OK), negative codes are for misuse only.  The transcripts are replayed with the framings of the
+ * transcript block (NOT PINNED, README).  OUT OF SCOPE: subgroup and on-curve checks of proof elements (the reference makes none), a
+ * sharded verifier. */
+/* kzg::VerifierKey (src/kzg/mod.rs:141-149): the first max_eval_points powers of g and max_eval_points + 1 powers of g2, records and
+ * strides as gm_g1_bases_register / gm_g2_bases_register take them (copied to the host side of the library). */
+int gm_vk_new(const void* g1, size_t g1_stride, size_t n1, const void* g2, size_t g2_stride, size_t n2, uint64_t* vk);
+/* `VerifierKey::from(&CommitterKey::new(..))` from the trapdoor (src/kzg/time.rs:29-72), the setup aid that pairs with
+ * gm_g1_srs_register: powers tau^i g, i < max_eval_points, and tau^i g2, i <= max_eval_points (tau canonical). */
+int gm_vk_from_trapdoor(const uint64_t g1_affine[12], const uint64_t g2_affine[24], const uint64_t tau[4], size_t max_eval_points, uint64_t* vk);
+int gm_vk_free(uint64_t vk);
+int gm_vk_len(uint64_t vk, size_t* n1_or_null, size_t* n2_or_null);
+/* serialize_uncompressed(&powers_of_g2) -- u64 length, 192 bytes per point, framing as gm_transcript_set_g1_encoding -- what psnark
+ * absorbs as b"ck".  out = NULL: *len only. */
+int gm_vk_g2_bytes(uint64_t vk, int encoding, uint8_t* out, size_t cap, size_t* len);
+/* VerifierKey::verify (src/kzg/mod.rs:155-175): e(C - [evaluation] g, g2) == e(proof, [tau - alpha] g2) */
+int gm_kzg_verify(uint64_t vk, const uint64_t commitment_jac[18], const uint64_t alpha_mont[4], const uint64_t evaluation_mont[4], const uint64_t proof_jac[18],
+                  int* ok);
+/* VerifierKey::verify_multi_points (:181-244): evaluations = nrows x npoints.  More points than the key holds powers for is GM_EINVAL;
+ * ncommitments != nrows is a rejection (the reference's msm(..).unwrap() fails). */
+int gm_kzg_verify_multi_points(uint64_t vk, const uint64_t* commitments_jac, size_t ncommitments, const uint64_t* eval_points_mont, size_t npoints,
+                               const uint64_t* evaluations_mont, size_t nrows, const uint64_t proof_jac[18], const uint64_t open_chal_mont[4], int* ok);
+/* Subclaim::new / new_batch (src/subprotocols/sumcheck/subclaim.rs:23-97) over a gm_transcript handle: messages = rounds x (a || b),
+ * final_foldings = lhs || rhs (k of them for the batch); challenges_mont receives rounds x 4 limbs. */
+int gm_sumcheck_subclaim(uint64_t transcript, const uint64_t* messages, size_t rounds, const uint64_t final_foldings[8], const uint64_t asserted_sum_mont[4],
+                         uint64_t* challenges_mont, int* ok);
+int gm_sumcheck_subclaim_batch(uint64_t transcript, const uint64_t* messages, size_t rounds, const uint64_t* final_foldings, const uint64_t* asserted_sums_mont, size_t k,
+                               uint64_t* challenges_mont, int* ok);
+/* TensorcheckProof::verify (src/subprotocols/tensorcheck/mod.rs:286-385): one claim per tensor-check instance -- the asserted results
+ * that are batched with powers of the batch challenge, the folding randomness (two challenges or more, else GM_EINVAL) and the
+ * evaluations of the instance's base combination at beta and -beta.  base_commitments_jac: ncommitments x 18. */
+typedef struct gm_tensorcheck_claim {
+  const uint64_t* asserted_res_mont;
+  size_t nasserted;
+  const uint64_t* fold_randomness_mont;
+  size_t nrandomness;
+  uint64_t direct_base_evals_mont[8];
+} gm_tensorcheck_claim;
+int gm_tensorcheck_verify(uint64_t transcript, uint64_t vk, const gm_tensorcheck_proof* proof, const uint64_t* base_commitments_jac, size_t ncommitments,
+                          const gm_tensorcheck_claim* claims, size_t nclaims, const uint64_t eval_chal_mont[4], const uint64_t batch_challenge_mont[4], int* ok);
+/* snark::Proof::verify (src/snark/verifier.rs:19-119).  matrices = {A, B, C} (gm_spm handles), x_vec the public input (a vector
+ * handle; 0 = empty), the proof's arrays filled by a prover or from deserialised bytes (spans are not read). */
+int gm_snark_verify(const uint64_t matrices[3], uint64_t x_vec, uint64_t vk, int g1_encoding, const gm_snark_proof* proof, int* ok);
+/* psnark::Proof::verify (src/psnark/verifier.rs:88-565): O(log n) host field arithmetic around two KZG checks.  index_commitments:
+ * 5 x 18 limbs (gm_psnark_index).  The key must hold max_eval_points >= 3. */
+int gm_psnark_verify(uint64_t x_vec, size_t num_variables, size_t nnz, const uint64_t* index_commitments, uint64_t vk, int g1_encoding,
+                     const gm_psnark_proof* proof, int* ok);
 
 /* ---- Multi-GPU: the collective layer (gemini_amd/csrc/dist.cpp) ------------------------------------------------------
  * One process per GPU (gm_init(LOCAL_RANK)).  The reference has no multi-device code: what shards is its own loop structure --

@@ -1036,6 +1036,58 @@ inline std::array<DeviceVec, 3> plookup(const DeviceVec& subset, const DeviceVec
   return {DeviceVec::from_handle(out[0]), DeviceVec::from_handle(out[1]), DeviceVec::from_handle(out[2])};
 }
 
+// kzg::VerifierKey (src/kzg/mod.rs:141-149) held by the library: the first max_eval_points powers of g and max_eval_points + 1 of g2.
+// verify / verify_multi_points answer true (accepted) or false (rejected); misuse throws gm::Error like everything else here
+class VerifierKey {
+ public:
+  VerifierKey(const std::vector<G1Affine>& powers_of_g, const std::vector<G2Affine>& powers_of_g2) {
+    check(gm_vk_new(powers_of_g.data(), sizeof(G1Affine), powers_of_g.size(), powers_of_g2.data(), sizeof(G2Affine), powers_of_g2.size(), &h_));
+  }
+  // the setup aid that pairs with gm_g1_srs_register: tau canonical, g and g2 as 12 / 24 Montgomery limbs
+  static VerifierKey from_trapdoor(const uint64_t g_affine[12], const uint64_t g2_affine[24], const BigInt& tau, size_t max_eval_points) {
+    VerifierKey k;
+    check(gm_vk_from_trapdoor(g_affine, g2_affine, tau.data(), max_eval_points, &k.h_));
+    return k;
+  }
+  VerifierKey(VerifierKey&& o) noexcept : h_(o.h_) { o.h_ = 0; }
+  ~VerifierKey() {
+    if (h_) gm_vk_free(h_);
+  }
+  VerifierKey(const VerifierKey&) = delete;
+  VerifierKey& operator=(const VerifierKey&) = delete;
+  uint64_t handle() const { return h_; }
+  // serialize_uncompressed(&powers_of_g2): what psnark absorbs as b"ck" (PsnarkProof::new_time's ck_g2_bytes)
+  std::vector<uint8_t> g2_bytes(int encoding = 0) const {
+    size_t n = 0;
+    check(gm_vk_g2_bytes(h_, encoding, nullptr, 0, &n));
+    std::vector<uint8_t> out(n);
+    check(gm_vk_g2_bytes(h_, encoding, out.data(), n, &n));
+    return out;
+  }
+  bool verify(const G1Projective& commitment, const Fr& alpha, const Fr& evaluation, const G1Projective& proof) const {  // src/kzg/mod.rs:155-175
+    int ok = 0;
+    check(gm_kzg_verify(h_, commitment.data(), alpha.data(), evaluation.data(), proof.data(), &ok));
+    return ok != 0;
+  }
+  // :181-244; evaluations: one row of eval_points.size() values per commitment
+  bool verify_multi_points(const std::vector<G1Projective>& commitments, const std::vector<Fr>& eval_points, const std::vector<std::vector<Fr>>& evaluations,
+                           const G1Projective& proof, const Fr& open_chal) const {
+    std::vector<Fr> flat;
+    for (auto& row : evaluations) {
+      if (row.size() != eval_points.size()) throw Error(GM_EINVAL, "verify_multi_points: one value per evaluation point in every row");
+      flat.insert(flat.end(), row.begin(), row.end());
+    }
+    int ok = 0;
+    check(gm_kzg_verify_multi_points(h_, commitments.empty() ? nullptr : commitments[0].data(), commitments.size(), eval_points.empty() ? nullptr : eval_points[0].data(),
+                                     eval_points.size(), flat.empty() ? nullptr : flat[0].data(), evaluations.size(), proof.data(), open_chal.data(), &ok));
+    return ok != 0;
+  }
+
+ private:
+  VerifierKey() = default;
+  uint64_t h_ = 0;
+};
+
 // src/snark/mod.rs:76-82 + Proof::new_time (src/snark/time_prover.rs:19-117): one call into the library
 struct SnarkProof {
   G1Projective witness_commitment;
@@ -1080,6 +1132,68 @@ struct SnarkProof {
     check(gm_snark_new_elastic(mats_t, z_be.h, w_be.h, za.h, zb.h, zc.h, ck.handle(), max_msm_buffer, min_device_chunk, g1_encoding, b.cap, &b.p));
     return b.unpack();
   }
+
+  // Proof::verify(&r1cs, &vk) (src/snark/verifier.rs:19-119): true = accepted.  The proof may come from a prover or from its fields
+  bool verify(const R1cs& r1cs, const VerifierKey& vk, int g1_encoding = 0) const {
+    if (tensorcheck_proof.base_polynomials_evaluations.size() != 1) return false;
+    const auto& tc = tensorcheck_proof;
+    const size_t nf = tc.folded_polynomials_commitments.size();
+    if (tc.folded_polynomials_evaluations.size() != nf) return false;
+    gm_snark_proof p;
+    memset(&p, 0, sizeof p);
+    memcpy(p.witness_commitment, witness_commitment.data(), 144);
+    memcpy(p.zc_alpha, zc_alpha.data(), 32);
+    std::vector<uint64_t> m[2], fc(18 * nf + 1), fe(8 * nf + 1);
+    const std::vector<RoundMsg>* msgs[2] = {&first_sumcheck_msgs, &second_sumcheck_msgs};
+    for (int k = 0; k < 2; k++) {
+      m[k].resize(8 * msgs[k]->size() + 1);
+      for (size_t i = 0; i < msgs[k]->size(); i++) {
+        memcpy(m[k].data() + 8 * i, (*msgs[k])[i].a.data(), 32);
+        memcpy(m[k].data() + 8 * i + 4, (*msgs[k])[i].b.data(), 32);
+      }
+      p.rounds[k] = msgs[k]->size();
+      p.messages[k] = m[k].data();
+    }
+    memcpy(p.final_foldings[0], first_final_foldings.data(), 64);
+    memcpy(p.final_foldings[1], second_final_foldings.data(), 64);
+    for (size_t i = 0; i < nf; i++) {
+      memcpy(fc.data() + 18 * i, tc.folded_polynomials_commitments[i].data(), 144);
+      memcpy(fe.data() + 8 * i, tc.folded_polynomials_evaluations[i].data(), 64);
+    }
+    p.nfold = nf;
+    p.fold_commitments = fc.data();
+    p.fold_evaluations = fe.data();
+    memcpy(p.evaluation_proof, tc.evaluation_proof.data(), 144);
+    memcpy(p.base_evaluations, tc.base_polynomials_evaluations[0].data(), 96);
+    const PublicInput x(r1cs);
+    const uint64_t mats[3] = {r1cs.a_.handle(), r1cs.b_.handle(), r1cs.c_.handle()};
+    int ok = 0;
+    check(gm_snark_verify(mats, x.h, vk.handle(), g1_encoding, &p, &ok));
+    return ok != 0;
+  }
+
+  // x = the entries of z in front of the witness (src/circuit.rs: z = x || w), as a vector of its own for the verifiers
+  struct PublicInput {
+    uint64_t h = 0;
+    explicit PublicInput(const R1cs& r1cs) {
+      size_t nw = 0;
+      check(gm_fr_vec_len(r1cs.w_, &nw));
+      const size_t nx = r1cs.nz_ > nw ? r1cs.nz_ - nw : 0;
+      check(gm_fr_vec_alloc(nx, &h));
+      if (nx) {
+        const int rc = gm_fr_stride(r1cs.z_, 0, 1, nx, h);
+        if (rc) {
+          gm_fr_vec_free(h);
+          check(rc);
+        }
+      }
+    }
+    ~PublicInput() {
+      if (h) gm_fr_vec_free(h);
+    }
+    PublicInput(const PublicInput&) = delete;
+    PublicInput& operator=(const PublicInput&) = delete;
+  };
 
  private:
   // the plain-C proof record of the library and its caller-owned arrays
@@ -1232,6 +1346,53 @@ struct PsnarkProof {
     tc.base_polynomials_evaluations.resize(22);
     memcpy(tc.base_polynomials_evaluations[0].data(), p.base_evaluations, sizeof p.base_evaluations);
     return out;
+  }
+
+  // Proof::verify(&r1cs, &vk, &index, num_non_zero) (src/psnark/verifier.rs:88-565): true = accepted.  The key needs max_eval_points >= 3
+  bool verify(const R1cs& r1cs, const VerifierKey& vk, const std::array<G1Projective, 5>& index, size_t num_non_zero, int g1_encoding = 0) const {
+    const TensorcheckProof& tc = tensorcheck_proof;
+    const size_t nf = tc.folded_polynomials_commitments.size();
+    if (tc.base_polynomials_evaluations.size() != 22 || tc.folded_polynomials_evaluations.size() != nf) return false;
+    gm_psnark_proof p;
+    memset(&p, 0, sizeof p);
+    std::vector<uint64_t> m[3], fc(18 * nf + 1), fe(8 * nf + 1);
+    const std::vector<RoundMsg>* msgs[3] = {&first_sumcheck_msgs, &second_sumcheck_msgs, &third_sumcheck_msgs};
+    for (int k = 0; k < 3; k++) {
+      m[k].resize(8 * msgs[k]->size() + 1);
+      for (size_t i = 0; i < msgs[k]->size(); i++) {
+        memcpy(m[k].data() + 8 * i, (*msgs[k])[i].a.data(), 32);
+        memcpy(m[k].data() + 8 * i + 4, (*msgs[k])[i].b.data(), 32);
+      }
+      p.rounds[k] = msgs[k]->size();
+      p.messages[k] = m[k].data();
+    }
+    memcpy(p.witness_commitment, witness_commitment.data(), 144);
+    memcpy(p.zc_alpha, zc_alpha.data(), 32);
+    memcpy(p.final_foldings[0], first_final_foldings.data(), 64);
+    memcpy(p.final_foldings[1], second_final_foldings.data(), 64);
+    memcpy(p.third_final_foldings, third_final_foldings.data(), sizeof p.third_final_foldings);
+    memcpy(p.r_star_commitments, r_star_commitments.data(), sizeof p.r_star_commitments);
+    memcpy(p.z_star_commitment, z_star_commitment.data(), 144);
+    memcpy(p.sorted_commitments, sorted_commitments.data(), sizeof p.sorted_commitments);
+    memcpy(p.products, products.data(), sizeof p.products);
+    memcpy(p.acc_v_commitments, acc_v_commitments.data(), sizeof p.acc_v_commitments);
+    memcpy(p.claimed_sumchecks, claimed_sumchecks.data(), sizeof p.claimed_sumchecks);
+    memcpy(p.ralpha_star_acc_mu_evals, ralpha_star_acc_mu_evals.data(), sizeof p.ralpha_star_acc_mu_evals);
+    memcpy(p.ralpha_star_acc_mu_proof, ralpha_star_acc_mu_proof.data(), 144);
+    memcpy(p.rstars_vals, rstars_vals.data(), sizeof p.rstars_vals);
+    for (size_t i = 0; i < nf; i++) {
+      memcpy(fc.data() + 18 * i, tc.folded_polynomials_commitments[i].data(), 144);
+      memcpy(fe.data() + 8 * i, tc.folded_polynomials_evaluations[i].data(), 64);
+    }
+    p.nfold = p.cap_folds = nf;
+    p.fold_commitments = fc.data();
+    p.fold_evaluations = fe.data();
+    memcpy(p.evaluation_proof, tc.evaluation_proof.data(), 144);
+    memcpy(p.base_evaluations, tc.base_polynomials_evaluations[0].data(), sizeof p.base_evaluations);
+    const SnarkProof::PublicInput x(r1cs);
+    int ok = 0;
+    check(gm_psnark_verify(x.h, r1cs.nz_, num_non_zero, index[0].data(), vk.handle(), g1_encoding, &p, &ok));
+    return ok != 0;
   }
 };
 

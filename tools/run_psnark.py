@@ -29,6 +29,9 @@ def main():
     ap.add_argument("--tail-log", type=int, default=10, help="--block-sharded: blocks shorter than 2^k elements are gathered")
     ap.add_argument("--random-r1cs", type=int, default=None, metavar="SEED", help="a satisfied random GENERAL R1CS (1-3 entries per row of A and B in random "
                     "columns, C diagonal: tools/run_snark.py random_rows) instead of dummy_r1cs")
+    ap.add_argument("--verify", action="store_true", help="check the last proof with Proof::verify on the device (gm_psnark_verify; one GPU) and report `verified` "
+                    "and `verify_s`.  With the example's key the verdict is FALSE -- the key is one power short of what the proof commits to -- pass "
+                    "--verifiable-key for a proof that verifies")
     ap.add_argument("--verifiable-key", action="store_true", help="one more power than examples/psnark.rs:76 asks for: the reference's "
                     "time-prover key (2n + 1 powers) is one short of the longest committed polynomial (2n + 2 coefficients), so the proof "
                     "of the example's configuration does not verify (tests/test_oracle_verifier.py::test_reference_example_key_is_one_power_short)")
@@ -38,6 +41,8 @@ def main():
 
     import gemini_amd as gm
     from gemini_amd.circuit import dummy_r1cs
+    if args.verify and (args.block_sharded or args.transport or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        raise SystemExit("--verify: one GPU (there is no sharded verifier)")
     from gemini_amd.kzg import CommitterKey
     from gemini_amd.psnark import Proof
 
@@ -144,6 +149,18 @@ def main():
         stamps[-1]["t1"] = clocks()
         out["runs"].append({k: round(v, 4) for k, v in proof.spans.items()})
         out["proof_size_B"] = proof.compressed_size()
+    if args.verify:
+        from gemini_amd.kzg import VerificationError, VerifierKey
+
+        vk = VerifierKey.from_committer_key(ck)
+        t0 = time.perf_counter()
+        try:
+            proof.verify(r1cs, vk, index)
+            out["verified"] = True
+        except VerificationError:
+            out["verified"] = False
+        out["verify_s"] = round(time.perf_counter() - t0, 6)
+        vk.free()
     out["mem_GB"] = {k: round(v / 1e9, 3) for k, v in gm.capi.mem_stats().items() if k != "spare_table_releases"}
     out["spare_table_releases"] = gm.capi.mem_stats()["spare_table_releases"]
     out["stamps"] = stamps

@@ -58,12 +58,16 @@ def main():
                     "global column indices, z whole on every rank) instead of block-diagonal")
     ap.add_argument("--random-r1cs", type=int, default=None, metavar="SEED", help="a satisfied random GENERAL R1CS (1-3 entries per row of A and B in "
                     "random columns, C diagonal) instead of dummy_r1cs: single GPU, or --block-sharded --transport (row blocks, global columns)")
+    ap.add_argument("--verify", action="store_true", help="check the last proof with Proof::verify on the device (gm_snark_verify; one GPU, a key with its G2 "
+                    "half: not --dummy-srs) and report `verified` and `verify_s`")
     ap.add_argument("--elastic", action="store_true", help="Proof::new_elastic over device-resident streams, max_msm_buffer = 2^20 "
                     "(examples/snark.rs elastic_snark_main) instead of --time-prover")
     args = ap.parse_args()
     import tests.stepwise  # noqa: F401 -- registers the step-wise cross-check (what --stepwise and the Python-level sharded keys use)
     import gemini_amd as gm
     from gemini_amd.circuit import dummy_r1cs
+    if args.verify and (args.dummy_srs or args.block_sharded or args.transport or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        raise SystemExit("--verify: one GPU and a key built from a trapdoor (the generator-copies key has no G2 half here; there is no sharded verifier)")
     from gemini_amd.kzg import CommitterKey
     from gemini_amd.snark import Proof
 
@@ -195,6 +199,19 @@ def main():
         if getattr(proof, "fr_work", None):
             out["fr_work"] = proof.fr_work  # field elements this rank's device passes read + wrote (tests/stepwise/dist_prover.py)
         out["proof_size_B"] = proof.compressed_size()  # examples/snark.rs:96 "proof-size {}B"
+    if args.verify:
+        # Proof::verify(&r1cs, &vk) on the device (gm_snark_verify): the key's G2 half comes from the committer key
+        from gemini_amd.kzg import VerificationError, VerifierKey
+
+        vk = VerifierKey.from_committer_key(ck)
+        t0 = time.perf_counter()
+        try:
+            proof.verify(r1cs, vk)
+            out["verified"] = True
+        except VerificationError:
+            out["verified"] = False
+        out["verify_s"] = round(time.perf_counter() - t0, 6)
+        vk.free()
     key = "ark_gemini::snark::elastic_prover" if args.elastic else "ark_gemini::snark::time_prover"
     out["elastic_prover_s" if args.elastic else "time_prover_s"] = min(r[key] for r in out["runs"])
     if lib_dist:
