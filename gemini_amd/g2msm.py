@@ -139,6 +139,12 @@ class G2Bases:
                                            C.c_size_t(voffset), C.c_size_t(n), capi.ptr(out)))
         return out
 
+    def check(self, offset: int = 0, n: int | None = None):
+        """curve and subgroup check of the resident points (gm_g2_bases_check); a points.CheckResult"""
+        from .points import check_g2_bases
+
+        return check_g2_bases(self, offset, n)
+
     def free(self):
         if self.handle:
             capi.check(capi.load().gm_g2_bases_free(C.c_uint64(self.handle)))

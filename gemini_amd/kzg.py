@@ -73,6 +73,26 @@ class CommitterKey:
     def max_eval_points(self) -> int:  # :75-78
         return self._max_eval_points
 
+    def check(self, vk: "VerifierKey | None" = None, rho=None) -> bool:
+        """Is this a key to commit against?  Every power is on the curve and in G1 (gm_g1_bases_check), and the powers are
+        consecutive powers of the tau of powers_of_g2[0], powers_of_g2[1] (gm_g1_powers_check; rho is drawn with `secrets` when
+        not given).  The G2 pair is the verifier key's when one is passed -- the party that will check the openings -- else this
+        key's own.  A WHOLE key only: on a cyclic share (gemini_amd.sharded) the library refuses the powers check with GM_EINVAL, which
+        is raised here -- a share holds powers of tau^world, and sharded checks are not built.  The reference has no counterpart: its
+        keys come from its own setup."""
+        from . import g2 as G2
+        from .points import check_g2, check_powers
+
+        if vk is not None:
+            raw = vk.powers_of_g2_bytes(enc=0)
+            g2s = [G2.deserialize_uncompressed(raw[8 + 192 * i: 8 + 192 * (i + 1)], 0) for i in range(2)]
+        else:
+            assert self.powers_of_g2 is not None and len(self.powers_of_g2) >= 2, "this key was built without its G2 half"
+            g2s = list(self.powers_of_g2[:2])
+        if not self.powers_of_g.check().ok or not check_g2(g2_records(g2s)).ok:
+            return False
+        return check_powers(self.powers_of_g, g2s[0], g2s[1], rho)
+
     def num_powers(self) -> int:
         """len(powers_of_g) of the whole key (a sharded key holds only a slice of it)"""
         return len(self.powers_of_g)

@@ -131,6 +131,12 @@ class G1Bases:
                                                     C.c_int(int(partial)), capi.ptr(out)))
         return out
 
+    def check(self, offset: int = 0, n: int | None = None):
+        """curve and subgroup check of the resident points (gm_g1_bases_check); a points.CheckResult"""
+        from .points import check_g1_bases
+
+        return check_g1_bases(self, offset, n)
+
     def free(self):
         if self.handle:
             capi.check(capi.load().gm_g1_bases_free(C.c_uint64(self.handle)))

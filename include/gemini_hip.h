@@ -512,7 +512,8 @@ int gm_hg2_free(uint64_t handle);
  * One lane per pair runs the Miller loop; the product is reduced on the device down to a handful of partials, the host
  * multiplies those and does the conjugation and ONE final exponentiation per call (a few ms, profiles/pairing.md).
  * Pairing calls share the MSM lock of the Threading paragraph above.
- * OUT OF SCOPE: subgroup checks (points are taken as members of G1 / G2, as ark-ec's pairing takes them); of herring's
+ * OUT OF SCOPE here: subgroup checks (points are taken as members of G1 / G2, as ark-ec's pairing takes them) -- a caller with
+ * points it has no reason to trust runs them through the point-validation block (gm_g1_check / gm_g2_check) first; of herring's
  * InnerProductProof (next block) the pub(crate) `generic` and CrsStream. */
 /* host records as gm_g1_bases_register / gm_g2_bases_register accept them (strides >= 96 / >= 192, multiples of 8; the
  * infinity flag at byte 96 / 192 when the stride has room); n = 0 gives 1 */
@@ -796,8 +797,9 @@ int gm_psnark_index(const gm_psnark_instance* instance, uint64_t ck_bases, uint6
  * gm_fr_powers / gm_fr_tensor / gm_fr_hadamard, three gm_spm_bilinear_pm and one gm_fr_eval_le.
  * Scalars are Montgomery limbs, G1 elements Jacobian (18 limbs, any representative).  *ok = 1: accepted, 0: REJECTED -- a rejected proof
  * is a result (return value GM_OK), negative codes are for misuse only.  The transcripts are replayed with the framings of the
- * transcript block (NOT PINNED, README).  OUT OF SCOPE: subgroup and on-curve checks of proof elements (the reference makes none), a
- * sharded verifier. */
+ * transcript block (NOT PINNED, README).  OUT OF SCOPE: subgroup and on-curve checks of proof elements (the reference makes none) --
+ * the verifiers do NOT call the point-validation block below; a caller that wants them checks the proof's points and the key itself
+ * (gm_g1_check, gm_g1_bases_check, gm_g1_powers_check) --, a sharded verifier. */
 /* kzg::VerifierKey (src/kzg/mod.rs:141-149): the first max_eval_points powers of g and max_eval_points + 1 powers of g2, records and
  * strides as gm_g1_bases_register / gm_g2_bases_register take them (copied to the host side of the library). */
 int gm_vk_new(const void* g1, size_t g1_stride, size_t n1, const void* g2, size_t g2_stride, size_t n2, uint64_t* vk);
@@ -1025,6 +1027,50 @@ int gm_psnark_index_sharded(const gm_psnark_shard* shard, uint64_t* out_jac);
  * what gm_psnark_new_time_sharded does before its first allocation.  z (whole on every rank) and the instance's blocks are the caller's. */
 int gm_psnark_shard_footprint(uint64_t key, size_t num_constraints, size_t num_variables, size_t nnz, size_t block, int world, int admit, uint64_t out[4]);
 int gm_psnark_new_time_sharded(const gm_psnark_shard* shard, int g1_encoding, size_t cap_rounds, gm_psnark_proof* proof);
+
+/* ---- point validation: untrusted G1 / G2 points and an SRS (gemini_amd/csrc/points.hip) ------------------------------------------
+ * What `deserialize_with_mode(.., Validate::Yes)` of ark-ec does per point, for whole keys on the device: canonical coordinates,
+ * the curve equation (y^2 = x^3 + 4, on the twist y^2 = x^3 + 4 (1 + u)) and membership of the prime-order subgroup by the
+ * endomorphism tests ark-bls12-381 uses -- G1: (beta x, y) == -[x^2] P, G2: psi(Q) == [x] Q, x = -0xd201000000010000 -- one lane
+ * per point, no inversion (DESIGN.md "Point validation").  The identity is a valid point.  Nothing else in this header calls
+ * these checks: registration, the pairings and the verifiers keep taking their points on trust.
+ * Every point gets ONE status, the FIRST check that fails in the order below.  A bad point is a result, not an error: the return
+ * value is GM_OK, *ok = 0 and *first_bad the smallest bad index; when every point passes *ok = 1 and *first_bad = n.  status_or_null
+ * (n bytes) and first_bad may be null.  Negative codes are for misuse only: null pointers, a bad stride, a range outside the handle
+ * (GM_EINVAL), an unknown handle (GM_EHANDLE), no gm_init (GM_ENOTINIT).  Every entry writes *ok = 0 (and gm_g1_bases_from_bytes
+ * *handle = 0) before it does anything else, gm_init or not, so a negative return value always comes with *ok = 0: the checks fail
+ * closed.  Only status bytes and one word per block of points come back from the device.  The calls share the MSM lock of the Threading paragraph above. */
+enum { GM_PT_OK = 0, GM_PT_BAD_ENCODING = 1, GM_PT_NONCANONICAL = 2, GM_PT_NOT_ON_CURVE = 3, GM_PT_NOT_IN_SUBGROUP = 4 };
+/* Host records as gm_g1_bases_register / gm_g2_bases_register take them (ark-ff Montgomery limbs, stride >= 96 / 192 and a multiple
+ * of 8, the infinity byte at 96 / 192 when the stride has room).  A record is the identity exactly when registration reads it as
+ * the identity: the infinity byte is set (whatever the coordinates hold) or every coordinate limb is zero.  GM_PT_NONCANONICAL: the
+ * limbs of a coordinate are >= q. */
+int gm_g1_check(const void* points, size_t stride, size_t n, uint8_t* status_or_null, size_t* first_bad, int* ok);
+int gm_g2_check(const void* points, size_t stride, size_t n, uint8_t* status_or_null, size_t* first_bad, int* ok);
+/* The same over bases[offset .. offset + n) of a registered handle.  What is resident is canonical by construction, so these report
+ * curve and subgroup failures only. */
+int gm_g1_bases_check(uint64_t handle, size_t offset, size_t n, uint8_t* status_or_null, size_t* first_bad, int* ok);
+int gm_g2_bases_check(uint64_t handle, size_t offset, size_t n, uint8_t* status_or_null, size_t* first_bad, int* ok);
+/* n G1 points from bytes, decoded on the device: 48 (compressed != 0) or 96 bytes each, back to back, in the framing `encoding`
+ * names (the values of gm_transcript_set_g1_encoding: 0 ark-ec little-endian with the flags in the last byte, 1 zcash big-endian
+ * with the flags in the first).  A compressed point costs one square root, y = (x^3 + 4)^((q + 1) / 4), its sign chosen by the flag.
+ * validate != 0 adds the curve equation (uncompressed points; a decompressed one is on the curve by construction) and the subgroup
+ * test, in the same pass.  Acceptance is the canonical encoding only, point for point that of gemini_amd/wire.py's
+ * g1_deserialize(strict = True): flag errors, a y-sign flag that does not match y, and infinity with non-zero coordinate bytes are
+ * GM_PT_BAD_ENCODING; a coordinate >= q GM_PT_NONCANONICAL; an x whose x^3 + 4 is no square, or a point off the curve,
+ * GM_PT_NOT_ON_CURVE.  On *ok = 0 nothing stays registered and *handle = 0; on success the handle is one of gm_g1_bases_register
+ * (no tables are built here either; gm_g1_bases_precompute(handle, -1) asks for them). */
+int gm_g1_bases_from_bytes(const uint8_t* bytes, size_t n, int compressed, int encoding, int validate, uint64_t* handle, uint8_t* status_or_null,
+                           size_t* first_bad, int* ok);
+/* Do bases[offset .. offset + n) hold consecutive powers of ONE tau -- bases[offset + i + 1] = tau bases[offset + i] for i < n - 1 --,
+ * the tau of (g2, tau g2)?  With A = sum rho^i P_i and B = sum rho^i P_{i+1} over i < n - 1 the test is e(A, tau g2) e(-B, g2) == 1:
+ * gm_fr_powers, two gm_g1_msm_v and ONE two-pair multi-pairing.  g2_affine / tau_g2_affine: 192-byte records as
+ * gm_g2_bases_register takes them.  A key that fails some pair passes with probability at most (n - 2) / r over rho, so rho MUST be
+ * unpredictable to whoever made the key (draw it after the key is fixed); rho = 0 is GM_EINVAL, and so is a cyclic share
+ * (gm_g1_bases_set_cyclic: it holds powers of tau^world; sharded checks are out of scope).  n <= 1 gives *ok = 1.  The points
+ * are taken as members of their groups: run gm_g1_bases_check first. */
+int gm_g1_powers_check(uint64_t handle, size_t offset, size_t n, const uint64_t g2_affine[24], const uint64_t tau_g2_affine[24],
+                       const uint64_t rho_mont[4], int* ok);
 
 #ifdef __cplusplus
 }

@@ -17,6 +17,9 @@
 //   gm::dist::{init_rccl, init_shm, init_hook, ...}         the all-gather between the per-GPU processes (no reference counterpart:
 //                                                           the reference is single-device; gemini_amd/csrc/dist.cpp)
 //   gm::CommitterKey::cyclic_share                          CommitterKey::new (src/kzg/time.rs:49-72), every rank its powers i = rank (mod world)
+//   gm::check_g1 / check_g2, CommitterKey::{check_points, check_powers, from_bytes}, G2Bases::check_points
+//                                                           deserialize_with_mode(.., Validate::Yes) of ark-ec for whole keys, on the
+//                                                           device (gemini_amd/csrc/points.hip); the powers check has no counterpart
 #pragma once
 #include <array>
 #include <cstdint>
@@ -118,6 +121,39 @@ struct G1Affine {                          // Rust layout: x, y, infinity (104-b
   uint64_t infinity;  // bool at byte 96, padded
 };
 static_assert(sizeof(G1Affine) == 104, "G1Affine must match the 104-byte Rust record");
+
+// ---- point validation (the block of the same name in gemini_hip.h).  A bad point is a result, never an exception ---------------
+enum class PointStatus : uint8_t { Ok = GM_PT_OK, BadEncoding = GM_PT_BAD_ENCODING, NonCanonical = GM_PT_NONCANONICAL, NotOnCurve = GM_PT_NOT_ON_CURVE, NotInSubgroup = GM_PT_NOT_IN_SUBGROUP };
+struct PointCheck {
+  bool ok = false;
+  size_t first_bad = 0;         // the smallest bad index; n when every point passes
+  std::vector<uint8_t> status;  // PointStatus values, one per point
+  explicit operator bool() const { return ok; }
+};
+namespace detail {
+template <class F>
+inline PointCheck point_check(size_t n, F&& call) {
+  PointCheck r;
+  r.status.assign(n, 0);
+  int ok = 0;
+  check(call(r.status.data(), &r.first_bad, &ok));
+  r.ok = ok != 0;
+  return r;
+}
+}  // namespace detail
+inline PointCheck check_g1(const std::vector<G1Affine>& points) {
+  return detail::point_check(points.size(), [&](uint8_t* st, size_t* fb, int* ok) { return gm_g1_check(points.data(), sizeof(G1Affine), points.size(), st, fb, ok); });
+}
+inline PointCheck check_g1_bases(uint64_t handle, size_t offset, size_t n) {
+  return detail::point_check(n, [&](uint8_t* st, size_t* fb, int* ok) { return gm_g1_bases_check(handle, offset, n, st, fb, ok); });
+}
+// bases[offset + i + 1] = tau bases[offset + i] for the tau of (g2, tau g2): 24 Montgomery limbs each.  rho must be unpredictable to
+// whoever made the key
+inline bool check_powers(uint64_t handle, size_t offset, size_t n, const uint64_t g2_affine[24], const uint64_t tau_g2_affine[24], const Fr& rho) {
+  int ok = 0;
+  check(gm_g1_powers_check(handle, offset, n, g2_affine, tau_g2_affine, rho.data(), &ok));
+  return ok != 0;
+}
 
 inline G1Projective g1_zero() {
   G1Projective z;
@@ -307,6 +343,25 @@ class CommitterKey {
     check(gm_g1_srs_register_cyclic(g_affine, tau.data(), k.n_, dist::rank(), dist::world(), &k.h_));
     return k;
   }
+  // n points of 48 (compressed) or 96 bytes in the framing `encoding` (0 ark-ec, 1 zcash), decoded -- and with `validate` checked --
+  // on the device (gm_g1_bases_from_bytes).  No key when a point is rejected: *report says which and why
+  static std::optional<CommitterKey> from_bytes(const std::vector<uint8_t>& bytes, size_t n, bool compressed, int encoding, bool validate = true,
+                                                PointCheck* report = nullptr) {
+    if (bytes.size() != n * (compressed ? 48 : 96)) throw Error(GM_EINVAL, "CommitterKey::from_bytes: the byte count does not match n");
+    CommitterKey k;
+    PointCheck r = detail::point_check(n, [&](uint8_t* st, size_t* fb, int* ok) {
+      return gm_g1_bases_from_bytes(bytes.data(), n, compressed ? 1 : 0, encoding, validate ? 1 : 0, &k.h_, st, fb, ok);
+    });
+    const bool ok = r.ok;
+    if (report) *report = std::move(r);
+    if (ok != (k.h_ != 0)) throw Error(GM_ESTATE, "CommitterKey::from_bytes: the library hands out a handle exactly when every point is accepted");
+    if (!ok) return std::nullopt;
+    k.n_ = n;
+    return std::optional<CommitterKey>(std::move(k));
+  }
+  PointCheck check_points() const { return check_g1_bases(h_, 0, n_); }  // every power on the curve and in G1
+  bool check_powers(const uint64_t g2_affine[24], const uint64_t tau_g2_affine[24], const Fr& rho) const { return gm::check_powers(h_, 0, n_, g2_affine, tau_g2_affine, rho); }
+  size_t size() const { return n_; }
   CommitterKey(CommitterKey&& o) noexcept : h_(o.h_), n_(o.n_) { o.h_ = 0; }
   ~CommitterKey() {
     if (h_) gm_g1_bases_free(h_);
@@ -414,6 +469,10 @@ struct G2Affine {                               // Rust layout: x.c0, x.c1, y.c0
 };
 static_assert(sizeof(G2Affine) == 200, "G2Affine must match the 200-byte Rust record");
 
+inline PointCheck check_g2(const std::vector<G2Affine>& points) {
+  return detail::point_check(points.size(), [&](uint8_t* st, size_t* fb, int* ok) { return gm_g2_check(points.data(), sizeof(G2Affine), points.size(), st, fb, ok); });
+}
+
 inline G2Projective g2_zero() {
   G2Projective z;
   check(gm_g2_sum(nullptr, 0, z.data()));
@@ -440,6 +499,10 @@ class G2Bases {
   G2Bases& operator=(const G2Bases&) = delete;
   uint64_t handle() const { return h_; }
   size_t size() const { return n_; }
+  PointCheck check_points(size_t offset, size_t n) const {
+    return detail::point_check(n, [&](uint8_t* st, size_t* fb, int* ok) { return gm_g2_bases_check(h_, offset, n, st, fb, ok); });
+  }
+  PointCheck check_points() const { return check_points(0, n_); }
   // 192-byte records x.c0 | x.c1 | y.c0 | y.c1 (the identity all zero), 24 words each
   std::vector<uint64_t> download(size_t offset, size_t n) const {
     std::vector<uint64_t> out(n * 24);
