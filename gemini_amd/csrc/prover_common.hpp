@@ -1,4 +1,5 @@
-// Helpers shared by the provers compiled into the library (snark.cpp, psnark.cpp): pure orchestration over the library's own C ABI.
+// Helpers shared by the provers compiled into the library, single-device and sharded: pure orchestration over the library's own C ABI.
+// The committer keys and the tensor check of the single-device provers are in tensorcheck.hpp.
 #pragma once
 #include <chrono>
 #include <cstring>
@@ -61,7 +62,6 @@ inline int sumcheck_new_elastic(uint64_t transcript, uint64_t f_stream, uint64_t
   return prove(transcript, S, messages, challenges, cap_rounds, final_foldings, rounds);
 }
 
-// ---- shared by snark.cpp / psnark.cpp / psnark_elastic.cpp -------------------------------------------------------------
 // sum over stream positions k < len: stream[k] * power[top - k], flushed every max(chunk, min_chunk) pairs
 // (msm_chunks / ChunkedPippenger composition, src/kzg/space.rs:22-55)
 inline int stream_msm(uint64_t bases, uint64_t stream, size_t len, size_t top, size_t chunk, uint64_t out[18]) {
@@ -85,49 +85,6 @@ inline Fr fr_pow(Fr base, size_t e) {
     e >>= 1;
   }
   return acc;
-}
-
-// ck.commit(v): msm_unchecked truncates to the shorter side (src/kzg/time.rs:82)
-inline int commit(uint64_t ck, size_t nck, uint64_t v, uint64_t out[18]) {
-  size_t n = 0;
-  RC(vec_len(v, &n));
-  return gm_ck_msm(ck, 0, 0, v, 0, n < nck ? n : nck, out);
-}
-inline int batch_commit(uint64_t ck, size_t nck, const std::vector<uint64_t>& vs, uint64_t* out) {
-  std::vector<size_t> ns(vs.size());
-  for (size_t k = 0; k < vs.size(); k++) {
-    RC(vec_len(vs[k], &ns[k]));
-    if (ns[k] > nck) ns[k] = nck;
-  }
-  return gm_ck_msm_batch(ck, vs.data(), ns.data(), vs.size(), out);
-}
-
-// batch_open_multi_points (src/kzg/time.rs:149-159): commit((sum_i chal^i p_i) / prod (x - point_j))
-inline int batch_open(Vecs& V, uint64_t ck, size_t nck, const std::vector<uint64_t>& polys, const uint64_t* pts, size_t npts, const uint64_t chal[4],
-               uint64_t out[18]) {
-  std::vector<uint64_t> etas(4 * polys.size());
-  Fr acc = Fr::one();
-  const Fr c = Fr::from_limbs(chal);
-  size_t longest = 0;
-  for (size_t k = 0; k < polys.size(); k++) {
-    acc.to_limbs(etas.data() + 4 * k);
-    acc = acc * c;
-    size_t l = 0;
-    RC(vec_len(polys[k], &l));
-    longest = l > longest ? l : longest;
-  }
-  uint64_t combined, quotient;
-  RC(V.alloc(longest, &combined));
-  RC(gm_fr_lincomb(polys.data(), etas.data(), polys.size(), combined));
-  size_t lc = 0;
-  RC(vec_len(combined, &lc));
-  RC(V.alloc(lc ? lc - 1 : 0, &quotient));
-  uint64_t rem[12];
-  RC(gm_fr_div_vanishing(combined, pts, npts, quotient, rem));
-  V.release(combined);
-  const int rc = commit(ck, nck, quotient, out);
-  V.release(quotient);
-  return rc;
 }
 
 // plookup (plookup/time_prover.rs:89-112) -> lookup_set, lookup_subset, lookup_sorted
@@ -159,6 +116,5 @@ inline int plookup(Vecs& V, uint64_t subset, uint64_t set_, uint64_t index, size
   if (subset_h != subset) V.release(subset_h);
   return GM_OK;
 }
-
 
 }  // namespace gmprover

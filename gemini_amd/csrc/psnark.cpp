@@ -1,16 +1,14 @@
 // psnark::Proof::new_time (src/psnark/time_prover.rs:69-384) with EntryProduct::new_time_batch
 // (src/subprotocols/entryproduct/time_prover.rs:53-114), the plookup vector builders
-// (src/subprotocols/plookup/time_prover.rs:89-112), Sumcheck::{new_time, prove_batch} (sumcheck/proof.rs:69-130),
-// TensorcheckProof::new_time (tensorcheck/mod.rs:190-275) and CommitterKey::{commit, batch_commit,
-// batch_open_multi_points} (src/kzg/time.rs:81-159) as ONE entry point of the library.
+// (src/subprotocols/plookup/time_prover.rs:89-112) and Sumcheck::{new_time, prove_batch} (sumcheck/proof.rs:69-130) as ONE entry
+// point of the library.  TensorcheckProof::new_time (tensorcheck/mod.rs:190-275), the entry product's claims and CommitterKey::{commit,
+// batch_commit, batch_open_multi_points} (src/kzg/time.rs:81-159) are the statements of tensorcheck.hpp, here over a TimeKey.
 //
 // Pure orchestration over the library's own C ABI, like snark.cpp: every O(n) step is a gm_* call, the sequence is the
 // one of gemini_amd/psnark.py::Proof.new_time (the tests hold the two byte for byte equal).  Driven from Python the
 // prover makes ~1000 FFI round trips per proof, most of which wait for the device; here the GPU is fed from one thread
 // that never leaves the library.
-#include <algorithm>
-
-#include "prover_common.hpp"
+#include "tensorcheck.hpp"
 
 namespace {
 
@@ -23,11 +21,12 @@ extern "C" int gm_psnark_new_time(const gm_psnark_instance* I, uint64_t ck_bases
     return GM_EINVAL;
   const auto t_all = Clock::now();
   Vecs V;
-  size_t nz = 0, nck = 0;
+  TimeKey K{ck_bases, 0};
+  size_t nz = 0;
   RC(vec_len(I->z, &nz));
-  RC(gm_ck_len(ck_bases, &nck));
+  RC(gm_ck_len(ck_bases, &K.nck));
   const size_t nnz = I->nnz;
-  if (nck < nnz || nck < I->ext_fre_row_len || nck < I->ext_fre_col_len) return GM_EINVAL;  // index_by zips need as many powers as indices (:119-127,179-183)
+  if (K.nck < nnz || K.nck < I->ext_fre_row_len || K.nck < I->ext_fre_col_len) return GM_EINVAL;  // index_by zips need as many powers as indices (:119-127,179-183)
   RC(gm_footprint_admit(1, ck_bases, nz, nnz, 0));  // room for the whole proof, or GM_ENOMEM with the numbers, before the first allocation
   uint64_t one[4];
   Fr::one().to_limbs(one);
@@ -48,7 +47,7 @@ extern "C" int gm_psnark_new_time(const gm_psnark_instance* I, uint64_t ck_bases
   if (g1_encoding) RC(gm_transcript_set_g1_encoding(T.h, g1_encoding));
 
   auto t0 = Clock::now();
-  RC(commit(ck_bases, nck, I->w, P->witness_commitment));  // :79
+  RC(K.commit(V, I->w, P->witness_commitment));  // :79
   P->spans[0] = since(t0);
   RC(gm_transcript_append_g1(T.h, L("witness"), 7, P->witness_commitment, 1, 0));  // :82-86
   RC(gm_transcript_append_message(T.h, L("ck"), 2, I->ck_g2_bytes, I->ck_g2_len));
@@ -91,8 +90,8 @@ extern "C" int gm_psnark_new_time(const gm_psnark_instance* I, uint64_t ck_bases
   RC(gm_fr_gather(I->z, I->col_index, z_star));
 
   t0 = Clock::now();
-  RC(batch_commit(ck_bases, nck, {ralpha_star, r_star, alpha_star}, &P->r_star_commitments[0][0]));  // :119-127
-  RC(commit(ck_bases, nck, z_star, P->z_star_commitment));
+  RC(K.commit_many(V, {ralpha_star, r_star, alpha_star}, &P->r_star_commitments[0][0]));  // :119-127
+  RC(K.commit(V, z_star, P->z_star_commitment));
   P->spans[3] = since(t0);
   RC(gm_transcript_append_g1(T.h, L("ra*"), 3, P->r_star_commitments[0], 1, 0));  // :129-132
   RC(gm_transcript_append_g1(T.h, L("rb*"), 3, P->r_star_commitments[1], 1, 0));
@@ -144,7 +143,7 @@ extern "C" int gm_psnark_new_time(const gm_psnark_instance* I, uint64_t ck_bases
   RC(V.alloc(I->ext_fre_col_len, &sorted[2]));
   RC(gm_fr_gather(ahp[2], I->ext_fre_col, sorted[2]));
   for (int k = 0; k < 3; k++) V.release(ahp[k]);
-  RC(batch_commit(ck_bases, nck, {sorted[0], sorted[1], sorted[2]}, &P->sorted_commitments[0][0]));  // :179-183
+  RC(K.commit_many(V, {sorted[0], sorted[1], sorted[2]}, &P->sorted_commitments[0][0]));  // :179-183
   P->spans[5] = since(t0);
   RC(gm_transcript_append_g1(T.h, L("sorted_alpha_commitment"), 23, P->sorted_commitments[1], 1, 0));  // :186-188
   RC(gm_transcript_append_g1(T.h, L("sorted_r_commitment"), 19, P->sorted_commitments[0], 1, 0));
@@ -160,7 +159,7 @@ extern "C" int gm_psnark_new_time(const gm_psnark_instance* I, uint64_t ck_bases
   RC(plookup(V, z_star, I->z, I->col_index, nnz, I->ext_fre_col, I->ext_fre_col_len, gamma, chi, zeta, lookup_vec + 6));
   V.release(b_ch);
   V.release(c_ch);
-  uint64_t acc_vec[9];  // accumulated_product(monic(v))   :211-214
+  std::vector<uint64_t> acc_vec(9);  // accumulated_product(monic(v))   :211-214
   // the right rotation of every lookup vector (shift_monic) is needed twice -- as the g side of the entry-product sumchecks (:223-239)
   // and as a body of the tensor check (:323-326) -- and the lookup vectors themselves for nothing else: build it here, once, and let
   // the 12 n elements of the lookup vectors go
@@ -193,23 +192,11 @@ extern "C" int gm_psnark_new_time(const gm_psnark_instance* I, uint64_t ck_bases
     }
   } prover_guard{provers};
   uint64_t psi[4];
-  {
-    RC(batch_commit(ck_bases, nck, std::vector<uint64_t>(acc_vec, acc_vec + 9), &P->acc_v_commitments[0][0]));
-    for (int k = 0; k < 9; k++) RC(gm_transcript_append_g1(T.h, L("acc_v"), 5, P->acc_v_commitments[k], 1, 0));
-    RC(gm_transcript_challenge_fr(T.h, L("ep-chal"), 7, psi));
-    for (int k = 0; k < 9; k++) {
-      uint64_t h = 0;
-      RC(gm_sc_new_borrow(acc_vec[k], shift_lookup[k], psi, &h));  // both read in place until the first fold, never written
-      provers.push_back(h);
-    }
-    uint64_t acc_chal[9][4];
-    RC(gm_fr_eval_le_batch(acc_vec, 9, psi, 1, &acc_chal[0][0]));
-    const Fr ci = Fr::from_limbs(psi);
-    for (int k = 0; k < 9; k++) {
-      size_t l = 0;
-      RC(vec_len(acc_vec[k], &l));
-      (Fr::from_limbs(acc_chal[k]) * ci + Fr::from_limbs(P->products[k]) - fr_pow(ci, l)).to_limbs(P->claimed_sumchecks[k]);
-    }
+  RC(entry_product_claims(K, T.h, V, acc_vec, &P->products[0][0], &P->acc_v_commitments[0][0], psi, &P->claimed_sumchecks[0][0]));
+  for (int k = 0; k < 9; k++) {
+    uint64_t h = 0;
+    RC(gm_sc_new_borrow(acc_vec[k], shift_lookup[k], psi, &h));  // both read in place until the first fold, never written
+    provers.push_back(h);
   }
   P->spans[7] = since(t0);
 
@@ -217,8 +204,8 @@ extern "C" int gm_psnark_new_time(const gm_psnark_instance* I, uint64_t ck_bases
   RC(gm_transcript_challenge_fr(T.h, L("open-chal"), 9, open_chal));  // :241-242
   t0 = Clock::now();
   std::vector<uint64_t> polys = {ralpha_star};  // :244-251
-  polys.insert(polys.end(), acc_vec, acc_vec + 9);
-  RC(batch_open(V, ck_bases, nck, polys, psi, 1, open_chal, P->ralpha_star_acc_mu_proof));
+  polys.insert(polys.end(), acc_vec.begin(), acc_vec.end());
+  RC(K.open(V, polys, psi, 1, open_chal, P->ralpha_star_acc_mu_proof));
   RC(gm_fr_eval_le_batch(polys.data(), 10, psi, 1, &P->ralpha_star_acc_mu_evals[0][0]));
   P->spans[8] = since(t0);
   {
@@ -257,93 +244,10 @@ extern "C" int gm_psnark_new_time(const gm_psnark_instance* I, uint64_t ck_bases
   for (uint64_t v : borrowed_tmp) V.release(v);
   P->spans[9] = since(t0);
 
-  // ---- TensorcheckProof::new_time(transcript, ck, 22 base polynomials, 4 bodies)   :296-367, tensorcheck/mod.rs:190-275
+  // ---- TensorcheckProof::new_time(transcript, ck, 22 base polynomials, 4 bodies)   :296-367
   t0 = Clock::now();
-  std::vector<uint64_t> base = {I->w, ralpha_star, r_star, alpha_star, z_star, I->row, I->col, I->val_a, I->val_b, I->val_c, sorted[0], sorted[1], sorted[2]};
-  base.insert(base.end(), acc_vec, acc_vec + 9);
-  const size_t n3 = P->rounds[2], n2 = P->rounds[1];
-  struct Body {
-    std::vector<uint64_t> polys;
-    std::vector<uint64_t> challenges;  // 4 limbs each
-  };
-  std::vector<Body> bodies(4);
-  {
-    bodies[0].polys.assign(acc_vec, acc_vec + 9);  // accumulated_vec + [r_star], challenges third_ch[j] * psi^(2^j)   :334-349
-    bodies[0].polys.push_back(r_star);
-    bodies[0].challenges.resize(4 * n3);
-    Fr tw = Fr::from_limbs(psi);
-    for (size_t j = 0; j < n3; j++) {
-      (Fr::from_limbs(ch3.data() + 4 * j) * tw).to_limbs(bodies[0].challenges.data() + 4 * j);
-      tw = tw.sqr();
-    }
-    bodies[1].polys = shift_lookup;  // shift_monic_lookup_vec + [val_a, val_b, val_c, alpha_star], challenges third_ch
-    bodies[1].polys.insert(bodies[1].polys.end(), {I->val_a, I->val_b, I->val_c, alpha_star});
-    bodies[1].challenges.assign(ch3.begin(), ch3.begin() + 4 * n3);
-    bodies[2].polys = {z_star};  // challenges second_ch
-    bodies[2].challenges.assign(ch2.begin(), ch2.begin() + 4 * n2);
-    bodies[3].polys = {ralpha_star, r_star, alpha_star};  // challenges second_ch[j] * third_ch[j]
-    const size_t nh = n2 < n3 ? n2 : n3;
-    bodies[3].challenges.resize(4 * nh);
-    for (size_t j = 0; j < nh; j++)
-      (Fr::from_limbs(ch2.data() + 4 * j) * Fr::from_limbs(ch3.data() + 4 * j)).to_limbs(bodies[3].challenges.data() + 4 * j);
-  }
-  uint64_t batch_challenge[4];
-  RC(gm_transcript_challenge_fr(T.h, L("batch_challenge"), 15, batch_challenge));
-  size_t max_group = 0;
-  for (auto& b : bodies) max_group = b.polys.size() > max_group ? b.polys.size() : max_group;
-  std::vector<uint64_t> bc(4 * max_group);  // powers(batch_challenge, max_len)
-  {
-    Fr acc = Fr::one();
-    const Fr c = Fr::from_limbs(batch_challenge);
-    for (size_t k = 0; k < max_group; k++) {
-      acc.to_limbs(bc.data() + 4 * k);
-      acc = acc * c;
-    }
-  }
-  std::vector<uint64_t> foldings;
-  for (auto& b : bodies) {
-    size_t longest = 0;
-    for (uint64_t p : b.polys) {
-      size_t l = 0;
-      RC(vec_len(p, &l));
-      longest = l > longest ? l : longest;
-    }
-    uint64_t batched;
-    RC(V.alloc(longest, &batched));
-    RC(gm_fr_lincomb(b.polys.data(), bc.data(), b.polys.size(), batched));
-    size_t len = 0;
-    RC(vec_len(batched, &len));
-    const size_t nch = b.challenges.size() / 4, first_level = foldings.size();
-    for (size_t k = 0; k + 1 < nch; k++) {  // foldings_polynomial: all challenges but the last (:124-133)
-      uint64_t nxt;
-      len = (len + 1) / 2;
-      RC(V.alloc(len, &nxt));
-      foldings.push_back(nxt);
-    }
-    RC(gm_fr_fold_chain(batched, b.challenges.data(), foldings.size() - first_level, foldings.data() + first_level));  // one wait per tree
-  }
-  P->nfold = foldings.size();
-  if (P->nfold > P->cap_folds) return GM_EINVAL;
-  if (P->nfold) RC(batch_commit(ck_bases, nck, foldings, P->fold_commitments));
-  for (size_t k = 0; k < P->nfold; k++) RC(gm_transcript_append_g1(T.h, L("commitment"), 10, P->fold_commitments + 18 * k, 1, 0));
-  uint64_t pts[12];  // beta^2, beta, -beta
-  RC(gm_transcript_challenge_fr(T.h, L("evaluation-chal"), 15, pts + 4));
-  {
-    const Fr beta = Fr::from_limbs(pts + 4);
-    beta.sqr().to_limbs(pts);
-    beta.neg().to_limbs(pts + 8);
-  }
-  RC(gm_fr_eval_le_batch(base.data(), base.size(), pts, 3, &P->base_evaluations[0][0]));
-  RC(gm_fr_eval_le_batch(foldings.data(), P->nfold, pts + 4, 2, P->fold_evaluations));
-  for (size_t k = 0; k < 3 * base.size(); k++) RC(gm_transcript_append_fr(T.h, L("eval"), 4, &P->base_evaluations[0][0] + 4 * k, 1));
-  for (size_t k = 0; k < 2 * P->nfold; k++) RC(gm_transcript_append_fr(T.h, L("eval"), 4, P->fold_evaluations + 4 * k, 1));
-  uint64_t open_chal2[4];
-  RC(gm_transcript_challenge_fr(T.h, L("open-chal"), 9, open_chal2));
-  {
-    std::vector<uint64_t> all = base;
-    all.insert(all.end(), foldings.begin(), foldings.end());
-    RC(batch_open(V, ck_bases, nck, all, pts, 3, open_chal2, P->evaluation_proof));
-  }
+  const uint64_t star[4] = {ralpha_star, r_star, alpha_star, z_star};
+  RC(psnark_tensorcheck(K, T.h, V, I, I->w, star, sorted, acc_vec, shift_lookup, psi, ch2, ch3, P));
   P->spans[10] = since(t0);
   P->spans[11] = since(t_all);
   return GM_OK;
@@ -487,5 +391,6 @@ extern "C" int gm_psnark_index(const gm_psnark_instance* I, uint64_t ck_bases, u
   if (!I || !out_jac) return GM_EINVAL;
   size_t nck = 0;
   RC(gm_ck_len(ck_bases, &nck));
-  return batch_commit(ck_bases, nck, {I->row, I->col, I->val_a, I->val_b, I->val_c}, out_jac);
+  Vecs V;
+  return TimeKey{ck_bases, nck}.commit_many(V, {I->row, I->col, I->val_a, I->val_b, I->val_c}, out_jac);
 }

@@ -1,59 +1,21 @@
 // psnark::Proof::new_elastic (src/psnark/elastic_prover.rs:60-634) as ONE entry point of the library: the preprocessing SNARK over
 // device-resident STREAMS (big-endian reversed vectors), with
-//   * CommitterKeyStream::{commit, open, open_multi_points, commit_folding, open_folding} (src/kzg/space.rs:95-285) as chunked
-//     stream MSMs -- `Reverse(powers_of_g)` + advance_by is the reversed / offset addressing of gm_ck_msm, a flush every
-//     max(max_msm_buffer [/ depth], min_device_chunk) pairs;
+//   * CommitterKeyStream::{commit, open, open_multi_points, commit_folding, open_folding} (src/kzg/space.rs:95-285) as the StreamKey
+//     of tensorcheck.hpp: chunked stream MSMs, a flush every max(max_msm_buffer [/ depth], min_device_chunk) pairs;
 //   * Sumcheck::{new_space, new_elastic} (sumcheck/proof.rs:133-154) and prove_batch (:69-122) over ElasticProvers: a SpaceProver
 //     that becomes a TimeProver once fewer than SPACE_TIME_THRESHOLD rounds remain (elastic_prover.rs:44-57) -- the prover adapter
 //     and both round loops are those of sumcheck_driver.hpp;
 //   * EntryProduct::new_elastic_batch (entryproduct/elastic_prover.rs:66-127), the plookup streams (:227-232 of the prover) and the
-//     tensor check over FoldedPolynomialTrees (:384-600).
+//     tensor check over FoldedPolynomialTrees (:384-600): the claims and the tensorcheck of tensorcheck.hpp, over the StreamKey.
 // Same transcript, same bytes as gm_psnark_new_time (src/psnark/tests.rs:56-124 asserts time == elastic); the sequence is the one
 // of gemini_amd/psnark.py::Proof.new_elastic, which the tests hold byte for byte equal to this.  Pure orchestration over the
 // library's own C ABI, like snark.cpp / psnark.cpp.  The reference re-streams every vector from its source to stay in O(log n)
 // memory; with the streams resident in HBM they are materialised once.
-#include <algorithm>
-
-#include "prover_common.hpp"
+#include "tensorcheck.hpp"
 
 namespace {
 
 using namespace gmprover;
-
-struct StreamKey {
-  uint64_t ck;
-  size_t nck, max_msm_buffer, min_chunk;
-  size_t flush(size_t wanted) const { return std::max<size_t>(std::max<size_t>(wanted, 1), min_chunk); }
-  // ck.commit(stream of a little-endian vector): msm_chunks of 2^20 (space.rs:169-177).  The vector is reversed into its stream
-  // and walked against Reverse(powers_of_g)
-  int commit_le(Vecs& V, uint64_t le, uint64_t out[18]) const { return msm_le(V, le, (size_t)1 << 20, out); }
-  int msm_le(Vecs& V, uint64_t le, size_t wanted_flush, uint64_t out[18]) const {
-    size_t n = 0;
-    RC(vec_len(le, &n));
-    if (n > nck) return GM_EINVAL;  // the streaming committer insists on a key as long as the stream (space.rs:169-175)
-    if (n == 0) return gm_g1_sum(nullptr, 0, out);
-    uint64_t s;
-    RC(V.alloc(n, &s));
-    RC(gm_fr_reverse(le, s));
-    const int rc = stream_msm(ck, s, n, n - 1, flush(wanted_flush), out);
-    V.release(s);
-    return rc;
-  }
-  // several commitments: when no vector is cut by the flush size they are sum_i v[i] tau^i g whichever way the pairs are walked
-  // -- one pipelined batch; otherwise stream by stream
-  int commit_many(Vecs& V, const std::vector<uint64_t>& les, size_t wanted_flush, uint64_t* out) const {
-    bool cut = false;
-    std::vector<size_t> ns(les.size());
-    for (size_t k = 0; k < les.size(); k++) {
-      RC(vec_len(les[k], &ns[k]));
-      if (ns[k] > nck) return GM_EINVAL;
-      cut = cut || ns[k] > flush(wanted_flush);
-    }
-    if (!cut) return gm_ck_msm_batch(ck, les.data(), ns.data(), les.size(), out);
-    for (size_t k = 0; k < les.size(); k++) RC(msm_le(V, les[k], wanted_flush, out + 18 * k));
-    return GM_OK;
-  }
-};
 
 int reversed(Vecs& V, uint64_t v, uint64_t* out) {
   size_t n = 0;
@@ -153,7 +115,7 @@ extern "C" int gm_psnark_new_elastic(const gm_psnark_instance* I, uint64_t z_str
   t0 = Clock::now();
   {
     uint64_t four[4 * 18];
-    RC(K.commit_many(V, {ralpha_star, r_star, alpha_star, z_star}, (size_t)1 << 20, four));  // :164-172
+    RC(K.commit_many(V, {ralpha_star, r_star, alpha_star, z_star}, four));  // :164-172
     memcpy(P->r_star_commitments, four, 3 * 144);
     memcpy(P->z_star_commitment, four + 54, 144);
   }
@@ -212,7 +174,7 @@ extern "C" int gm_psnark_new_elastic(const gm_psnark_instance* I, uint64_t z_str
   RC(V.alloc(I->ext_fre_col_len, &sorted[2]));
   RC(gm_fr_gather(ahp[2], I->ext_fre_col, sorted[2]));
   for (int k = 0; k < 3; k++) V.release(ahp[k]);
-  RC(K.commit_many(V, {sorted[0], sorted[1], sorted[2]}, (size_t)1 << 20, &P->sorted_commitments[0][0]));
+  RC(K.commit_many(V, {sorted[0], sorted[1], sorted[2]}, &P->sorted_commitments[0][0]));
   P->spans[5] = since(t0);
   RC(gm_transcript_append_g1(T.h, L("sorted_alpha_commitment"), 23, P->sorted_commitments[1], 1, 0));  // :220-222
   RC(gm_transcript_append_g1(T.h, L("sorted_r_commitment"), 19, P->sorted_commitments[0], 1, 0));
@@ -222,7 +184,8 @@ extern "C" int gm_psnark_new_elastic(const gm_psnark_instance* I, uint64_t z_str
   RC(gm_transcript_challenge_fr(T.h, L("chi"), 3, chi));
 
   t0 = Clock::now();
-  uint64_t pls[9], accs[9], shifts[9];  // plookup streams, ProductStream, RightRotationStreamer   :227-243
+  uint64_t pls[9];
+  std::vector<uint64_t> accs(9), shifts(9);  // plookup streams, ProductStream, RightRotationStreamer   :227-243
   RC(plookup(V, r_star, b_ch, I->row_index, nnz, I->ext_fre_row, I->ext_fre_row_len, gamma, chi, zeta, pls));
   RC(plookup(V, alpha_star, c_ch, I->row_index, nnz, I->ext_fre_row, I->ext_fre_row_len, gamma, chi, zeta, pls + 3));
   RC(plookup(V, z_star, z_le, I->col_index, nnz, I->ext_fre_col, I->ext_fre_col_len, gamma, chi, zeta, pls + 6));
@@ -257,28 +220,18 @@ extern "C" int gm_psnark_new_elastic(const gm_psnark_instance* I, uint64_t z_str
   std::vector<ElasticSc> provers(13);
   std::vector<uint64_t> batch_streams;  // reversed streams the 13 provers read in place
   uint64_t psi[4];
-  {
-    RC(K.commit_many(V, std::vector<uint64_t>(accs, accs + 9), (size_t)1 << 20, &P->acc_v_commitments[0][0]));
-    for (int k = 0; k < 9; k++) RC(gm_transcript_append_g1(T.h, L("acc_v"), 5, P->acc_v_commitments[k], 1, 0));
-    RC(gm_transcript_challenge_fr(T.h, L("ep-chal"), 7, psi));
-    uint64_t acc_chal[9][4];
-    RC(gm_fr_eval_le_batch(accs, 9, psi, 1, &acc_chal[0][0]));  // evaluate_be of the streams
-    const Fr ci = Fr::from_limbs(psi);
-    for (int k = 0; k < 9; k++) {
-      size_t l = 0;
-      RC(vec_len(accs[k], &l));
-      (Fr::from_limbs(acc_chal[k]) * ci + Fr::from_limbs(P->products[k]) - fr_pow(ci, l)).to_limbs(P->claimed_sumchecks[k]);
-      if (resident) {
-        RC(provers[k].init_resident(accs[k], shifts[k], psi));
-        continue;
-      }
-      uint64_t as, ss;
-      RC(reversed(V, accs[k], &as));
-      RC(reversed(V, shifts[k], &ss));
-      RC(provers[k].init(as, ss, psi, true));  // the provers read their streams in place: released after the batch
-      batch_streams.push_back(as);
-      batch_streams.push_back(ss);
+  RC(entry_product_claims(K, T.h, V, accs, &P->products[0][0], &P->acc_v_commitments[0][0], psi, &P->claimed_sumchecks[0][0]));
+  for (int k = 0; k < 9; k++) {
+    if (resident) {
+      RC(provers[k].init_resident(accs[k], shifts[k], psi));
+      continue;
     }
+    uint64_t as, ss;
+    RC(reversed(V, accs[k], &as));
+    RC(reversed(V, shifts[k], &ss));
+    RC(provers[k].init(as, ss, psi, true));  // the provers read their streams in place: released after the batch
+    batch_streams.push_back(as);
+    batch_streams.push_back(ss);
   }
   P->spans[7] = since(t0);
 
@@ -287,29 +240,8 @@ extern "C" int gm_psnark_new_elastic(const gm_psnark_instance* I, uint64_t z_str
   t0 = Clock::now();
   {
     std::vector<uint64_t> polys = {ralpha_star};
-    polys.insert(polys.end(), accs, accs + 9);
-    std::vector<uint64_t> oc(40);
-    Fr acc = Fr::one();
-    size_t longest = 0;
-    for (int k = 0; k < 10; k++) {
-      acc.to_limbs(oc.data() + 4 * k);
-      acc = acc * Fr::from_limbs(open_chal);
-      size_t l = 0;
-      RC(vec_len(polys[k], &l));
-      longest = std::max(longest, l);
-    }
-    uint64_t poly, q;
-    RC(V.alloc(longest, &poly));
-    RC(gm_fr_lincomb(polys.data(), oc.data(), 10, poly));
-    size_t lp = 0;
-    RC(vec_len(poly, &lp));
-    // CommitterKeyStream::open (space.rs:95-125): the quotient by (x - psi), committed as a stream
-    RC(V.alloc(lp ? lp - 1 : 0, &q));
-    uint64_t rem[4];
-    RC(gm_fr_div_vanishing(poly, psi, 1, q, rem));
-    RC(K.msm_le(V, q, max_msm_buffer, P->ralpha_star_acc_mu_proof));
-    V.release(q);
-    V.release(poly);
+    polys.insert(polys.end(), accs.begin(), accs.end());
+    RC(K.open(V, polys, psi, 1, open_chal, P->ralpha_star_acc_mu_proof));  // CommitterKeyStream::open (space.rs:95-125): the quotient by (x - psi)
     RC(gm_fr_eval_le_batch(polys.data(), 10, psi, 1, &P->ralpha_star_acc_mu_evals[0][0]));  // :332-343
   }
   P->spans[8] = since(t0);
@@ -357,145 +289,11 @@ extern "C" int gm_psnark_new_elastic(const gm_psnark_instance* I, uint64_t z_str
   for (uint64_t v : batch_streams) V.release(v);
   P->spans[9] = since(t0);
 
-  // ---- tensorcheck (:384-600)
+  // ---- tensorcheck (:384-600): 22 base polynomials, 4 FoldedPolynomialTrees
   t0 = Clock::now();
-  const size_t n3 = P->rounds[2], n2 = P->rounds[1];
-  uint64_t tc_chal[4];
-  RC(gm_transcript_challenge_fr(T.h, L("batch_challenge"), 15, tc_chal));
-  std::vector<uint64_t> tcc(4 * 13);
-  {
-    Fr acc = Fr::one();
-    for (int k = 0; k < 13; k++) {
-      acc.to_limbs(tcc.data() + 4 * k);
-      acc = acc * Fr::from_limbs(tc_chal);
-    }
-  }
-  struct Tree {
-    uint64_t body;
-    std::vector<uint64_t> challenges;  // every challenge but the last
-    std::vector<uint64_t> levels;
-  };
-  std::vector<Tree> trees(4);
-  {
-    auto lincomb = [&](std::vector<uint64_t> polys, uint64_t* out) -> int {
-      size_t longest = 0;
-      for (uint64_t p : polys) {
-        size_t l = 0;
-        RC(vec_len(p, &l));
-        longest = std::max(longest, l);
-      }
-      RC(V.alloc(longest, out));
-      return gm_fr_lincomb(polys.data(), tcc.data(), polys.size(), *out);
-    };
-    std::vector<uint64_t> g0(accs, accs + 9), g1(shifts, shifts + 9);
-    g0.push_back(r_star);
-    g1.insert(g1.end(), {I->val_a, I->val_b, I->val_c, alpha_star});
-    RC(lincomb(g0, &trees[0].body));
-    RC(lincomb(g1, &trees[1].body));
-    trees[2].body = z_star;
-    RC(lincomb({ralpha_star, r_star, alpha_star}, &trees[3].body));
-    if (n3 == 0 || n2 == 0) return GM_EINVAL;
-    Fr tw = Fr::from_limbs(psi);
-    trees[0].challenges.resize(4 * (n3 - 1));
-    for (size_t j = 0; j + 1 < n3; j++) {
-      (Fr::from_limbs(ch3.data() + 4 * j) * tw).to_limbs(trees[0].challenges.data() + 4 * j);
-      tw = tw.sqr();
-    }
-    trees[1].challenges.assign(ch3.begin(), ch3.begin() + 4 * (n3 - 1));
-    trees[2].challenges.assign(ch2.begin(), ch2.begin() + 4 * (n2 - 1));
-    const size_t nh = std::min(n2, n3);  // zip(ch2, ch3[:len(ch2)]) without its last element
-    trees[3].challenges.resize(4 * (nh - 1));
-    for (size_t j = 0; j + 1 < nh; j++)
-      (Fr::from_limbs(ch2.data() + 4 * j) * Fr::from_limbs(ch3.data() + 4 * j)).to_limbs(trees[3].challenges.data() + 4 * j);
-  }
-  for (int k = 0; k < 9; k++) V.release(shifts[k]);
-  size_t nfold = 0;
-  for (auto& t : trees) {  // FoldedPolynomialTree: the levels, little-endian
-    size_t len = 0;
-    RC(vec_len(t.body, &len));
-    for (size_t k = 0; k < t.challenges.size() / 4; k++) {
-      uint64_t nxt;
-      len = (len + 1) / 2;
-      RC(V.alloc(len, &nxt));
-      t.levels.push_back(nxt);
-    }
-    RC(gm_fr_fold_chain(t.body, t.challenges.data(), t.levels.size(), t.levels.data()));
-    nfold += t.levels.size();
-  }
-  P->nfold = nfold;
-  if (nfold > P->cap_folds) return GM_EINVAL;
-  std::vector<uint64_t> all_levels;
-  for (auto& t : trees) all_levels.insert(all_levels.end(), t.levels.begin(), t.levels.end());
-  {
-    // commit_folding (space.rs:192-223): one ChunkedPippenger of max_msm_buffer / depth per level of a tree.  When no level of any
-    // tree is cut by its flush size every commitment is sum_i level[i] tau^i g whichever way the pairs are walked: the levels of
-    // all four trees go through ONE pipelined batch; otherwise tree by tree, level by level, as streams
-    bool cut = false;
-    for (auto& t : trees)
-      for (uint64_t lv : t.levels) {
-        size_t l = 0;
-        RC(vec_len(lv, &l));
-        cut = cut || l > K.flush(max_msm_buffer / t.levels.size());
-      }
-    if (!cut) {
-      if (nfold) RC(K.commit_many(V, all_levels, (size_t)1 << 62, P->fold_commitments));
-    } else {
-      size_t at = 0;
-      for (auto& t : trees) {
-        const size_t depth = t.levels.size();
-        if (depth) RC(K.commit_many(V, t.levels, max_msm_buffer / depth, P->fold_commitments + 18 * at));
-        at += depth;
-      }
-    }
-  }
-  for (size_t k = 0; k < nfold; k++) RC(gm_transcript_append_g1(T.h, L("commitment"), 10, P->fold_commitments + 18 * k, 1, 0));
-  uint64_t pts[12];  // beta^2, beta, -beta
-  RC(gm_transcript_challenge_fr(T.h, L("evaluation-chal"), 15, pts + 4));
-  {
-    const Fr beta = Fr::from_limbs(pts + 4);
-    beta.sqr().to_limbs(pts);
-    beta.neg().to_limbs(pts + 8);
-  }
-  RC(gm_fr_eval_le_batch(all_levels.data(), nfold, pts + 4, 2, P->fold_evaluations));  // evaluate_folding, tree by tree
-  std::vector<uint64_t> base = {w_le, ralpha_star, r_star, alpha_star, z_star, I->row, I->col, I->val_a, I->val_b, I->val_c, sorted[0], sorted[1], sorted[2]};
-  base.insert(base.end(), accs, accs + 9);
-  RC(gm_fr_eval_le_batch(base.data(), base.size(), pts, 3, &P->base_evaluations[0][0]));
-  for (size_t k = 0; k < 3 * base.size(); k++) RC(gm_transcript_append_fr(T.h, L("eval"), 4, &P->base_evaluations[0][0] + 4 * k, 1));
-  for (size_t k = 0; k < 2 * nfold; k++) RC(gm_transcript_append_fr(T.h, L("eval"), 4, P->fold_evaluations + 4 * k, 1));
-  uint64_t open_chal2[4];
-  RC(gm_transcript_challenge_fr(T.h, L("open-chal"), 9, open_chal2));
-  {
-    const Fr oc = Fr::from_limbs(open_chal2);
-    std::vector<uint64_t> ocs(4 * (base.size() + nfold));
-    Fr acc = Fr::one();
-    for (size_t k = 0; k < base.size() + nfold; k++) {
-      acc.to_limbs(ocs.data() + 4 * k);
-      acc = acc * oc;
-    }
-    // The reference sums five openings: open_multi_points(partial_eval) (space.rs:128-166) and one open_folding per tree (:229-285),
-    // each sum_i eta_i commit(p_i div Z), the HashMapPippenger of open_folding merging the scalars of equal bases.  Division by the
-    // same Z is linear and all five walk the same key, so the merge extends over all of them: ONE linear combination of the 22 base
-    // polynomials and every level, ONE division, one stream MSM (flushed every max_msm_buffer pairs) -- instead of a division
-    // per level (~100 latency-bound three-phase scans)
-    std::vector<uint64_t> all = base;
-    all.insert(all.end(), all_levels.begin(), all_levels.end());
-    size_t longest = 0;
-    for (uint64_t p : all) {
-      size_t l = 0;
-      RC(vec_len(p, &l));
-      longest = std::max(longest, l);
-    }
-    uint64_t pe, q, rem[12];
-    RC(V.alloc(longest, &pe));
-    RC(gm_fr_lincomb(all.data(), ocs.data(), all.size(), pe));
-    size_t lp = 0;
-    RC(vec_len(pe, &lp));
-    RC(V.alloc(lp ? lp - 1 : 0, &q));
-    RC(gm_fr_div_vanishing(pe, pts, 3, q, rem));
-    V.release(pe);
-    RC(K.msm_le(V, q, max_msm_buffer, P->evaluation_proof));
-    V.release(q);
-  }
+  if (P->rounds[1] == 0 || P->rounds[2] == 0) return GM_EINVAL;  // a sumcheck of no rounds: no challenge to fold a tree with
+  const uint64_t star[4] = {ralpha_star, r_star, alpha_star, z_star};
+  RC(psnark_tensorcheck(K, T.h, V, I, w_le, star, sorted, accs, shifts, psi, ch2, ch3, P));
   P->spans[10] = since(t0);
   P->spans[11] = since(t_all);
   return GM_OK;

@@ -1,12 +1,12 @@
-// snark::Proof::new_time (src/snark/time_prover.rs:19-117) with TensorcheckProof::new_time
-// (src/subprotocols/tensorcheck/mod.rs:190-275), CommitterKey::{commit, batch_commit, batch_open_multi_points}
-// (src/kzg/time.rs:81-159) and Sumcheck::new_time (sumcheck/proof.rs:125-130) as ONE entry point of the library.
+// snark::Proof::new_time (src/snark/time_prover.rs:19-117) with Sumcheck::new_time (sumcheck/proof.rs:125-130) as ONE entry point
+// of the library.  TensorcheckProof::new_time (src/subprotocols/tensorcheck/mod.rs:190-275) and CommitterKey::{commit, batch_commit,
+// batch_open_multi_points} (src/kzg/time.rs:81-159) are the tensorcheck and TimeKey of tensorcheck.hpp.
 //
 // The reference's prover is compiled host code that drives its kernels (MSM, sumcheck rounds, vector passes); so is
 // this: pure orchestration over the library's own C ABI (every O(n) step below is a gm_* call that a Rust / C++
 // embedder could make itself -- gemini_amd/snark.py is the same sequence in Python and the tests hold the two byte for
 // byte equal).  What a shim gains is one FFI call per proof: `Proof::new_time(&r1cs, &ck)` -> gm_snark_new_time.
-#include "prover_common.hpp"
+#include "tensorcheck.hpp"
 
 namespace {
 
@@ -97,93 +97,21 @@ extern "C" int gm_snark_new_time(const uint64_t matrices[6], uint64_t z, uint64_
   RC(sumcheck_new_time(T.h, abc, z, one, P->messages[1], ch2, cap_rounds, P->final_foldings[1], &P->rounds[1]));  // :84-89
   P->spans[4] = since(t0);
 
-  // ---- TensorcheckProof::new_time(transcript, ck, [w], [([abc_tensored, z], challenges)])   tensorcheck/mod.rs:190-275
+  // ---- TensorcheckProof::new_time(transcript, ck, [w], [([abc_tensored, z], challenges)]); abc_tensored is last read when the body is batched
   t0 = Clock::now();
-  uint64_t batch_challenge[4];
-  RC(gm_transcript_challenge_fr(T.h, L("batch_challenge"), 15, batch_challenge));
-  uint64_t lc_coeffs[8];
-  Fr::one().to_limbs(lc_coeffs);  // powers(batch_challenge, max_len)[0..2]
-  memcpy(lc_coeffs + 4, batch_challenge, 32);
-  const uint64_t body[2] = {abc, z};
-  uint64_t batched;
-  RC(V.alloc(nz, &batched));
-  RC(gm_fr_lincomb(body, lc_coeffs, 2, batched));
-  // foldings_polynomial (:124-133): successive folds with every challenge but the last
-  std::vector<uint64_t> foldings;
-  std::vector<size_t> fold_len;
-  {
-    size_t len = 0;
-    RC(vec_len(batched, &len));
-    for (size_t k = 0; k + 1 < P->rounds[1]; k++) {
-      uint64_t nxt;
-      len = (len + 1) / 2;
-      RC(V.alloc(len, &nxt));
-      foldings.push_back(nxt);
-      fold_len.push_back(len);
-    }
-    RC(gm_fr_fold_chain(batched, ch2.data(), foldings.size(), foldings.data()));  // one wait for the whole tree
-  }
-  V.release(batched);
-  V.release(abc);
-  P->nfold = foldings.size();
-  if (P->nfold > cap_rounds) return GM_EINVAL;
-  if (P->nfold) {
-    std::vector<size_t> ns(P->nfold);
-    for (size_t k = 0; k < P->nfold; k++) ns[k] = fold_len[k] < nck ? fold_len[k] : nck;
-    RC(gm_ck_msm_batch(ck_bases, foldings.data(), ns.data(), P->nfold, P->fold_commitments));  // batch_commit :98-107
-  }
-  for (size_t k = 0; k < P->nfold; k++) RC(gm_transcript_append_g1(T.h, L("commitment"), 10, P->fold_commitments + 18 * k, 1, 0));
-  uint64_t pts[12];  // beta^2, beta, -beta
-  RC(gm_transcript_challenge_fr(T.h, L("evaluation-chal"), 15, pts + 4));
-  {
-    const Fr beta = Fr::from_limbs(pts + 4);
-    beta.sqr().to_limbs(pts);
-    beta.neg().to_limbs(pts + 8);
-  }
-  RC(gm_fr_eval_le(w, pts, 3, P->base_evaluations));
-  RC(gm_fr_eval_le_batch(foldings.data(), P->nfold, pts + 4, 2, P->fold_evaluations));  // one wait for all levels
-  RC(gm_transcript_append_fr(T.h, L("eval"), 4, P->base_evaluations, 1));
-  RC(gm_transcript_append_fr(T.h, L("eval"), 4, P->base_evaluations + 4, 1));
-  RC(gm_transcript_append_fr(T.h, L("eval"), 4, P->base_evaluations + 8, 1));
-  for (size_t k = 0; k < 2 * P->nfold; k++) RC(gm_transcript_append_fr(T.h, L("eval"), 4, P->fold_evaluations + 4 * k, 1));
-  uint64_t open_chal[4];
-  RC(gm_transcript_challenge_fr(T.h, L("open-chal"), 9, open_chal));
-  // batch_open_multi_points (:149-159): commit((sum_i open_chal^i p_i) / ((x - beta^2)(x - beta)(x + beta)))
-  {
-    const size_t npoly = 1 + P->nfold;
-    std::vector<uint64_t> polys(npoly), etas(4 * npoly);
-    polys[0] = w;
-    for (size_t k = 0; k < P->nfold; k++) polys[1 + k] = foldings[k];
-    Fr acc = Fr::one();
-    const Fr oc = Fr::from_limbs(open_chal);
-    for (size_t k = 0; k < npoly; k++) {
-      acc.to_limbs(etas.data() + 4 * k);
-      acc = acc * oc;
-    }
-    size_t longest = nw;
-    for (size_t l : fold_len) longest = l > longest ? l : longest;
-    uint64_t combined, quotient;
-    RC(V.alloc(longest, &combined));
-    RC(gm_fr_lincomb(polys.data(), etas.data(), npoly, combined));
-    size_t lc = 0;
-    RC(vec_len(combined, &lc));
-    RC(V.alloc(lc ? lc - 1 : 0, &quotient));
-    uint64_t rem[12];
-    RC(gm_fr_div_vanishing(combined, pts, 3, quotient, rem));
-    V.release(combined);
-    size_t lq = 0;
-    RC(vec_len(quotient, &lq));
-    RC(gm_ck_msm(ck_bases, 0, 0, quotient, 0, lq < nck ? lq : nck, P->evaluation_proof));
-  }
+  const uint64_t body_polys[2] = {abc, z};
+  const gm_tensorcheck_body body{body_polys, 2, ch2.data(), P->rounds[1]};
+  RC(tensorcheck(TimeKey{ck_bases, nck}, T.h, V, {w}, {body}, {abc}, cap_rounds, P->fold_commitments, P->base_evaluations, P->fold_evaluations,
+                 P->evaluation_proof, &P->nfold));
   P->spans[5] = since(t0);
   P->spans[6] = since(t_all);
   return GM_OK;
 }
 
 // =====================================================================================================================
-// snark::Proof::new_elastic (src/snark/elastic_prover.rs:174-266) with its `tensorcheck` (:105-168),
-// CommitterKeyStream::{commit, commit_folding, open_multi_points, open_folding} (src/kzg/space.rs:95-285) and
-// Sumcheck::new_elastic (sumcheck/proof.rs:145-154, elastic_prover.rs:44-57) as ONE entry point.
+// snark::Proof::new_elastic (src/snark/elastic_prover.rs:174-266) with Sumcheck::new_elastic (sumcheck/proof.rs:145-154,
+// elastic_prover.rs:44-57) as ONE entry point.  Its `tensorcheck` (:105-168) is the tensorcheck of tensorcheck.hpp over a StreamKey:
+// CommitterKeyStream::{commit_folding, open_multi_points, open_folding} (src/kzg/space.rs:95-285).
 //
 // The streams of the reference (`Reverse(..)` views, big-endian) are device-resident reversed vectors; the key stays in
 // time order in HBM and the stream view `Reverse(powers_of_g)` + advance_by is the reversed / offset addressing of the MSM
@@ -203,19 +131,19 @@ extern "C" int gm_snark_new_elastic(const uint64_t matrices_t[3], uint64_t z_str
   if (!matrices_t || !P || !P->messages[0] || !P->messages[1] || !P->fold_commitments || !P->fold_evaluations) return GM_EINVAL;
   const auto t_all = Clock::now();
   Vecs V;
-  size_t nz = 0, nw = 0, nck = 0, nzc = 0;
+  StreamKey K{ck_bases, 0, max_msm_buffer, min_device_chunk};
+  size_t nz = 0, nw = 0, nzc = 0;
   RC(vec_len(z_stream, &nz));
   RC(vec_len(w_stream, &nw));
   RC(vec_len(zc_stream, &nzc));
-  RC(gm_ck_len(ck_bases, &nck));
-  if (nw > nck || nz > nck) return GM_EINVAL;  // the streaming committer insists on a key as long as every stream (space.rs:169-175)
+  RC(gm_ck_len(ck_bases, &K.nck));
+  if (nw > K.nck || nz > K.nck) return GM_EINVAL;  // the streaming committer insists on a key as long as every stream (space.rs:169-175)
   for (int k = 0; k < 3; k++) {
     size_t rows = 0;
     RC(gm_spm_shape(matrices_t[k], &rows, nullptr, nullptr));
     if (rows != nz) return GM_EINVAL;
   }
   RC(gm_footprint_admit(0, ck_bases, nz, 0, min_device_chunk > 1 ? 1 : 2));  // (2: the literal schedule holds the reversed copies as well)
-  const size_t flush = max_msm_buffer > min_device_chunk ? max_msm_buffer : min_device_chunk;
   TranscriptGuard T;
   static const char protocol[] = "GEMINI-v0";
   RC(gm_transcript_new(L(protocol), sizeof protocol - 1, &T.h));
@@ -223,8 +151,7 @@ extern "C" int gm_snark_new_elastic(const uint64_t matrices_t[3], uint64_t z_str
   P->spans[0] = 0.0;  // the matrix products z_a, z_b, z_c belong to the stream construction (R1csStream), not to the prover
 
   auto t0 = Clock::now();
-  RC(stream_msm(ck_bases, w_stream, nw, nw - 1, (size_t)1 << 20 > min_device_chunk ? (size_t)1 << 20 : min_device_chunk,
-                P->witness_commitment));  // ck.commit(witness): msm_chunks of 2^20 (:209, space.rs:169-177)
+  RC(stream_msm(ck_bases, w_stream, nw, nw - 1, K.flush((size_t)1 << 20), P->witness_commitment));  // ck.commit(witness): msm_chunks of 2^20 (:209, space.rs:169-177)
   P->spans[1] = since(t0);
   RC(gm_transcript_append_g1(T.h, L("witness"), 7, P->witness_commitment, 1, 0));
   uint64_t alpha[4];
@@ -307,109 +234,15 @@ extern "C" int gm_snark_new_elastic(const uint64_t matrices_t[3], uint64_t z_str
   }
   P->spans[4] = since(t0);
 
-  // ---- tensorcheck (:105-168) over the folded polynomial tree of body = lhs + batch_challenge * z
+  // ---- tensorcheck(transcript, ck, [w], [([lhs, z], challenges)])   :105-168; lhs and z are last read when the body is batched
   t0 = Clock::now();
-  uint64_t batch_challenge[4];
-  RC(gm_transcript_challenge_fr(T.h, L("batch_challenge"), 15, batch_challenge));
-  uint64_t body_le;
-  uint64_t lc_coeffs[8];
-  Fr::one().to_limbs(lc_coeffs);
-  memcpy(lc_coeffs + 4, batch_challenge, 32);
-  const uint64_t body[2] = {lhs_le, z_le};
-  RC(V.alloc(nz, &body_le));
-  RC(gm_fr_lincomb(body, lc_coeffs, 2, body_le));
-  std::vector<uint64_t> levels;
-  std::vector<size_t> level_len;
-  {
-    size_t len = 0;
-    RC(vec_len(body_le, &len));
-    for (size_t k = 0; k + 1 < P->rounds[1]; k++) {  // strip_last
-      uint64_t nxt;
-      len = (len + 1) / 2;
-      RC(V.alloc(len, &nxt));
-      levels.push_back(nxt);
-      level_len.push_back(len);
-    }
-    RC(gm_fr_fold_chain(body_le, ch2.data(), levels.size(), levels.data()));
-  }
-  for (uint64_t v : {body_le, lhs_le, z_le}) V.release(v);
-  P->nfold = levels.size();
-  if (P->nfold > cap_rounds) return GM_EINVAL;
-  if (P->nfold) {  // commit_folding (space.rs:192-223): one ChunkedPippenger of max_msm_buffer / depth per level
-    const size_t per = max_msm_buffer / P->nfold ? max_msm_buffer / P->nfold : 1;
-    const size_t lvl_flush = per > min_device_chunk ? per : min_device_chunk;
-    bool cut = false;
-    for (size_t l : level_len) cut = cut || l > lvl_flush;
-    if (!cut) {  // no level is cut: the commitments are sum_i level[i] * tau^i g whichever way the pairs are walked
-      RC(gm_ck_msm_batch(ck_bases, levels.data(), level_len.data(), P->nfold, P->fold_commitments));
-    } else {
-      for (size_t k = 0; k < P->nfold; k++) {
-        uint64_t s;
-        RC(V.alloc(level_len[k], &s));
-        RC(gm_fr_reverse(levels[k], s));
-        RC(stream_msm(ck_bases, s, level_len[k], level_len[k] - 1, lvl_flush, P->fold_commitments + 18 * k));
-        V.release(s);
-      }
-    }
-  }
-  for (size_t k = 0; k < P->nfold; k++) RC(gm_transcript_append_g1(T.h, L("commitment"), 10, P->fold_commitments + 18 * k, 1, 0));
-  uint64_t pts[12];  // beta^2, beta, -beta
-  RC(gm_transcript_challenge_fr(T.h, L("evaluation-chal"), 15, pts + 4));
-  {
-    const Fr beta = Fr::from_limbs(pts + 4);
-    beta.sqr().to_limbs(pts);
-    beta.neg().to_limbs(pts + 8);
-  }
-  RC(gm_fr_eval_le_batch(levels.data(), P->nfold, pts + 4, 2, P->fold_evaluations));  // evaluate_folding, tensorcheck/mod.rs:73-88
   uint64_t w_le;
   RC(V.alloc(nw, &w_le));
   RC(gm_fr_reverse(w_stream, w_le));
-  RC(gm_fr_eval_le(w_le, pts, 3, P->base_evaluations));
-  RC(gm_transcript_append_fr(T.h, L("eval"), 4, P->base_evaluations, 1));
-  RC(gm_transcript_append_fr(T.h, L("eval"), 4, P->base_evaluations + 4, 1));
-  RC(gm_transcript_append_fr(T.h, L("eval"), 4, P->base_evaluations + 8, 1));
-  for (size_t k = 0; k < 2 * P->nfold; k++) RC(gm_transcript_append_fr(T.h, L("eval"), 4, P->fold_evaluations + 4 * k, 1));
-  uint64_t open_chal[4];
-  RC(gm_transcript_challenge_fr(T.h, L("open-chal"), 9, open_chal));
-  {
-    // The reference adds two openings: open_multi_points(w) (space.rs:128-166) and open_folding (:229-285) = sum_i open_chal^(i + 1)
-    // commit(quotient of level i), the HashMapPippenger of the latter merging the scalars of equal bases.  Both walk the same key
-    // and division by the same Z is linear, so the merge extends over both: the quotient of  w + sum_i open_chal^(i + 1) level_i
-    // -- one linear combination, ONE division (instead of one latency-bound scan per level), one stream MSM flushed every
-    // max_msm_buffer pairs.  (It is the polynomial the time prover opens: time_prover.rs:98-107 -> kzg/time.rs:149-159.)
-    std::vector<uint64_t> polys(1 + P->nfold), etas(4 * (1 + P->nfold));
-    polys[0] = w_le;
-    Fr acc = Fr::one();
-    const Fr oc = Fr::from_limbs(open_chal);
-    size_t longest = nw;
-    for (size_t k = 0; k <= P->nfold; k++) {
-      acc.to_limbs(etas.data() + 4 * k);
-      acc = acc * oc;
-      if (k) {
-        polys[k] = levels[k - 1];
-        longest = level_len[k - 1] > longest ? level_len[k - 1] : longest;
-      }
-    }
-    size_t lb = 0;
-    if (longest > 3) {
-      uint64_t combined, q, bs, rem[12];
-      RC(V.alloc(longest, &combined));
-      RC(gm_fr_lincomb(polys.data(), etas.data(), polys.size(), combined));
-      size_t lc = 0;
-      RC(vec_len(combined, &lc));
-      RC(V.alloc(lc ? lc - 1 : 0, &q));
-      RC(gm_fr_div_vanishing(combined, pts, 3, q, rem));
-      V.release(combined);
-      RC(vec_len(q, &lb));
-      if (lb) {
-        RC(V.alloc(lb, &bs));
-        RC(gm_fr_reverse(q, bs));
-        V.release(q);
-        RC(stream_msm(ck_bases, bs, lb, lb - 1, flush, P->evaluation_proof));
-      }
-    }
-    if (lb == 0) RC(gm_g1_sum(nullptr, 0, P->evaluation_proof));
-  }
+  const uint64_t body_polys[2] = {lhs_le, z_le};
+  const gm_tensorcheck_body body{body_polys, 2, ch2.data(), P->rounds[1]};
+  RC(tensorcheck(K, T.h, V, {w_le}, {body}, {lhs_le, z_le}, cap_rounds, P->fold_commitments, P->base_evaluations, P->fold_evaluations, P->evaluation_proof,
+                 &P->nfold));
   P->spans[5] = since(t0);
   P->spans[6] = since(t_all);
   return GM_OK;

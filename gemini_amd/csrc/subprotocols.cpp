@@ -4,11 +4,9 @@
 //   plookup                                    src/subprotocols/plookup/time_prover.rs:89-112
 // for a caller that builds an argument of its own from them (a grand product over its own vector, a lookup into its own table).
 //
-// Pure orchestration over the library's own C ABI, like snark.cpp / psnark.cpp, with the transcript labels of the reference in the
-// reference's order.  The whole-prover entries keep their own inlined statements of the same sequences (the tests hold the two equal).
-#include <algorithm>
-
-#include "prover_common.hpp"
+// Pure orchestration over the library's own C ABI, like snark.cpp / psnark.cpp.  The tensor check and the entry product's claims are
+// the statements of tensorcheck.hpp that the whole provers call as well: the entries here add their argument checks.
+#include "tensorcheck.hpp"
 
 namespace {
 
@@ -30,72 +28,19 @@ extern "C" int gm_tensorcheck_new_time(uint64_t transcript, uint64_t ck_bases, c
   size_t nck = 0;
   RC(gm_ck_len(ck_bases, &nck));
   SC_CHECK(nbodies != 0, GM_EINVAL, "tensorcheck_new_time: no body polynomials");  // assert_ne!(batch_challenges.len(), 0)   :203
-  size_t max_group = 0, nfold = 0;
+  size_t nfold = 0;
   for (size_t b = 0; b < nbodies; b++) {
     SC_CHECK(bodies[b].npolys != 0 && bodies[b].polys, GM_EINVAL, "tensorcheck_new_time: body %zu has no polynomials", b);  // :204-206
     SC_CHECK(bodies[b].challenges_mont || bodies[b].nchallenges == 0, GM_EINVAL, "tensorcheck_new_time: body %zu: null challenges", b);
-    max_group = std::max(max_group, bodies[b].npolys);
     nfold += bodies[b].nchallenges ? bodies[b].nchallenges - 1 : 0;
   }
   SC_CHECK(nfold <= P->cap_folds, GM_EINVAL, "tensorcheck_new_time: %zu foldings, room for %zu", nfold, P->cap_folds);
   SC_CHECK(P->nbase == nbase && (nbase == 0 || P->base_evaluations) && (nfold == 0 || (P->fold_commitments && P->fold_evaluations)), GM_EINVAL,
            "tensorcheck_new_time: the proof record does not match the call (%zu bases, record %zu) or lacks an array", nbase, P->nbase);
   Vecs V;
-  uint64_t batch_challenge[4];
-  RC(gm_transcript_challenge_fr(transcript, L("batch_challenge"), 15, batch_challenge));  // :201
-  std::vector<uint64_t> bc(4 * max_group);  // powers(batch_challenge, max_len)   :202
-  {
-    Fr acc = Fr::one();
-    const Fr c = Fr::from_limbs(batch_challenge);
-    for (size_t k = 0; k < max_group; k++) {
-      acc.to_limbs(bc.data() + 4 * k);
-      acc = acc * c;
-    }
-  }
-  std::vector<uint64_t> foldings;
-  for (size_t b = 0; b < nbodies; b++) {  // :208-217
-    const gm_tensorcheck_body& B = bodies[b];
-    size_t longest = 0;
-    for (size_t k = 0; k < B.npolys; k++) {
-      size_t l = 0;
-      RC(vec_len(B.polys[k], &l));
-      longest = std::max(longest, l);
-    }
-    if (B.nchallenges < 2) continue;  // no folding: the batched polynomial is not needed
-    uint64_t batched;
-    RC(V.alloc(longest, &batched));
-    RC(gm_fr_lincomb(B.polys, bc.data(), B.npolys, batched));
-    size_t len = 0;
-    RC(vec_len(batched, &len));
-    const size_t first_level = foldings.size();
-    for (size_t k = 0; k + 1 < B.nchallenges; k++) {  // foldings_polynomial: all challenges but the last   :124-133
-      uint64_t nxt;
-      len = (len + 1) / 2;
-      RC(V.alloc(len, &nxt));
-      foldings.push_back(nxt);
-    }
-    RC(gm_fr_fold_chain(batched, B.challenges_mont, foldings.size() - first_level, foldings.data() + first_level));
-    V.release(batched);
-  }
-  P->nfold = nfold;
-  if (nfold) RC(batch_commit(ck_bases, nck, foldings, P->fold_commitments));  // ONE batch over every folding   :218
-  for (size_t k = 0; k < nfold; k++) RC(gm_transcript_append_g1(transcript, L("commitment"), 10, P->fold_commitments + 18 * k, 1, 0));
-  uint64_t pts[12];  // beta^2, beta, -beta   :224-226
-  RC(gm_transcript_challenge_fr(transcript, L("evaluation-chal"), 15, pts + 4));
-  {
-    const Fr beta = Fr::from_limbs(pts + 4);
-    beta.sqr().to_limbs(pts);
-    beta.neg().to_limbs(pts + 8);
-  }
-  if (nbase) RC(gm_fr_eval_le_batch(base_polys, nbase, pts, 3, P->base_evaluations));           // :228-237
-  if (nfold) RC(gm_fr_eval_le_batch(foldings.data(), nfold, pts + 4, 2, P->fold_evaluations));  // :239-247
-  for (size_t k = 0; k < 3 * nbase; k++) RC(gm_transcript_append_fr(transcript, L("eval"), 4, P->base_evaluations + 4 * k, 1));
-  for (size_t k = 0; k < 2 * nfold; k++) RC(gm_transcript_append_fr(transcript, L("eval"), 4, P->fold_evaluations + 4 * k, 1));
-  uint64_t open_chal[4];
-  RC(gm_transcript_challenge_fr(transcript, L("open-chal"), 9, open_chal));  // :261
-  std::vector<uint64_t> all(base_polys, base_polys + nbase);
-  all.insert(all.end(), foldings.begin(), foldings.end());
-  return batch_open(V, ck_bases, nck, all, pts, 3, open_chal, P->evaluation_proof);  // :263-267
+  return tensorcheck(TimeKey{ck_bases, nck}, transcript, V, std::vector<uint64_t>(base_polys, base_polys + nbase),
+                     std::vector<gm_tensorcheck_body>(bodies, bodies + nbodies), {}, P->cap_folds, P->fold_commitments, P->base_evaluations,
+                     P->fold_evaluations, P->evaluation_proof, &P->nfold);
 }
 
 extern "C" int gm_entryproduct_new_time_batch(uint64_t transcript, uint64_t ck_bases, const uint64_t* vs, const uint64_t* acc_vs_or_null, size_t k,
@@ -107,11 +52,9 @@ extern "C" int gm_entryproduct_new_time_batch(uint64_t transcript, uint64_t ck_b
   RC(gm_ck_len(ck_bases, &nck));
   Vecs V;
   std::vector<uint64_t> acc(k), rrot(k);
-  std::vector<size_t> acc_len(k);
   for (size_t i = 0; i < k; i++) {  // monic, right_rotation, accumulated_product   :70-78
     size_t l = 0;
     RC(vec_len(vs[i], &l));
-    acc_len[i] = l + 1;
     if (acc_vs_or_null) {
       size_t la = 0;
       RC(vec_len(acc_vs_or_null[i], &la));
@@ -124,21 +67,12 @@ extern "C" int gm_entryproduct_new_time_batch(uint64_t transcript, uint64_t ck_b
     RC(V.alloc(l + 1, &rrot[i]));
     RC(gm_fr_shift_monic(vs[i], rrot[i]));
   }
-  if (k) RC(batch_commit(ck_bases, nck, acc, acc_v_commitments));  // :79 (:128 for one vector)
-  for (size_t i = 0; i < k; i++) RC(gm_transcript_append_g1(transcript, L("acc_v"), 5, acc_v_commitments + 18 * i, 1, 0));
-  RC(gm_transcript_challenge_fr(transcript, L("ep-chal"), 7, chal_mont));  // :84
+  RC(entry_product_claims(TimeKey{ck_bases, nck}, transcript, V, acc, claimed_products_mont, acc_v_commitments, chal_mont, claimed_sumchecks_mont));  // :79-102
   Provers made;
   for (size_t i = 0; i < k; i++) {  // Witness::new(acc_v, rrot_v, chal) copies both   :86-93
     uint64_t h = 0;
     RC(gm_sc_new_v(acc[i], rrot[i], chal_mont, &h));
     made.h.push_back(h);
-  }
-  if (k) {  // chal * acc_v(chal) + claimed_product - chal^|acc_v|   :94-102
-    std::vector<uint64_t> acc_chal(4 * k);
-    RC(gm_fr_eval_le_batch(acc.data(), k, chal_mont, 1, acc_chal.data()));
-    const Fr c = Fr::from_limbs(chal_mont);
-    for (size_t i = 0; i < k; i++)
-      (Fr::from_limbs(acc_chal.data() + 4 * i) * c + Fr::from_limbs(claimed_products_mont + 4 * i) - fr_pow(c, acc_len[i])).to_limbs(claimed_sumchecks_mont + 4 * i);
   }
   std::copy(made.h.begin(), made.h.end(), provers);
   made.h.clear();  // the caller's from here

@@ -1,6 +1,6 @@
 """TensorcheckProof (src/subprotocols/tensorcheck/mod.rs:39-46), foldings_polynomial (:124-133) and the prover `TensorcheckProof.new_time`
-(:190-275) as one call into the library (gm_tensorcheck_new_time, gemini_amd/csrc/subprotocols.cpp).  The whole provers run the same
-sequence inline (gemini_amd/csrc/{snark,psnark}.cpp); its step-wise statement is tests/stepwise/tensorcheck_steps.py."""
+(:190-275) as one call into the library (gm_tensorcheck_new_time, gemini_amd/csrc/subprotocols.cpp).  The whole provers call the same
+statement (gemini_amd/csrc/tensorcheck.hpp); its step-wise statement is tests/stepwise/tensorcheck_steps.py."""
 from __future__ import annotations
 
 import ctypes as C

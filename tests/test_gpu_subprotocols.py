@@ -273,9 +273,12 @@ def _tensorcheck_shape(oracle, shape):
     if shape == "a":  # tensorcheck/tests.rs:16-86: d = 8, one base, one body
         polys = [_rand_ints(oracle, 5100, 8)]
         bodies = [([0], _rand_ints(oracle, 5101, 3))]
-    else:  # three bases of unequal lengths, two bodies: 7 + 5 foldings
+    elif shape == "b":  # three bases of unequal lengths, two bodies: 7 + 5 foldings
         polys = [_rand_ints(oracle, 5200 + i, n) for i, n in enumerate((256, 200, 64))]
         bodies = [([0, 1], _rand_ints(oracle, 5210, 8)), ([2], _rand_ints(oracle, 5211, 6))]
+    else:  # a body that folds nothing (one challenge: no batched polynomial, no level) in front of one that folds twice
+        polys = [_rand_ints(oracle, 5400, 8), _rand_ints(oracle, 5401, 5)]
+        bodies = [([0], _rand_ints(oracle, 5410, 1)), ([0, 1], _rand_ints(oracle, 5411, 3))]
     return polys, bodies
 
 
@@ -288,7 +291,7 @@ def _tc_to_ints(gm, oracle, tc):
             "base_polynomials_evaluations": [[F(x) for x in e3] for e3 in tc.base_polynomials_evaluations]}
 
 
-@pytest.mark.parametrize("shape", ["a", "b"])
+@pytest.mark.parametrize("shape", ["a", "b", "c"])
 def test_tensorcheck_prove_verify(gm, oracle, pyref, key, shape):
     from gemini_amd import capi, wire
     from gemini_amd.fr import FrVec
@@ -303,7 +306,7 @@ def test_tensorcheck_prove_verify(gm, oracle, pyref, key, shape):
     dpolys = [FrVec.from_host(_M(oracle, p)) for p in polys]
     dbodies = [([dpolys[i] for i in idx], _M(oracle, ch)) for idx, ch in bodies]
     nfold = sum(len(ch) - 1 for _, ch in bodies)
-    assert nfold == (2 if shape == "a" else 12)
+    assert nfold == {"a": 2, "b": 12, "c": 2}[shape]
     t = Transcript(PROTOCOL)
     tc = TensorcheckProof.new_time(t, ck, dpolys, dbodies)
     tr = pyref.GeminiTranscript(PROTOCOL)
@@ -313,25 +316,27 @@ def test_tensorcheck_prove_verify(gm, oracle, pyref, key, shape):
         assert got[field] == want[field], field
     assert gm.fr.fr_to_int(t.get_challenge(b"next")) == tr.get_challenge(b"next")
     t.free()
-    # the verifier (tensorcheck/mod.rs:286-392, pairing check included), driven as tensorcheck/tests.rs:45-85 drives it
-    vk = V.VerifierKey.from_trapdoor(tau, 5)
-    trv = pyref.GeminiTranscript(PROTOCOL)
-    batch_challenge = trv.get_challenge(b"batch_challenge")
-    for c in got["folded_polynomials_commitments"]:
-        trv.append_message(b"commitment", pyref.g1_serialize_uncompressed(c))
-    eval_chal = trv.get_challenge(b"evaluation-chal")
-    asserted, direct = [], []
-    for idx, ch in bodies:
-        tensor = pyref.tensor(ch)
-        asserted.append([pyref.ip(polys[i], tensor[:len(polys[i])]) for i in idx])
-        e0 = e1 = 0
-        for j, i in enumerate(idx):
-            w = pow(batch_challenge, j, R)
-            e0 = (e0 + w * got["base_polynomials_evaluations"][i][1]) % R
-            e1 = (e1 + w * got["base_polynomials_evaluations"][i][2]) % R
-        direct.append([e0, e1])
-    base_commitments = [sr.commit(srs, p) for p in polys]
-    V.tensorcheck_verify(got, trv, vk, asserted, base_commitments, direct, [ch for _, ch in bodies], eval_chal, batch_challenge)
+    # (shape c is the prover's path alone: its first body pairs 8 coefficients with the tensor of ONE challenge, which no verifier is handed)
+    if shape != "c":
+        # the verifier (tensorcheck/mod.rs:286-392, pairing check included), driven as tensorcheck/tests.rs:45-85 drives it
+        vk = V.VerifierKey.from_trapdoor(tau, 5)
+        trv = pyref.GeminiTranscript(PROTOCOL)
+        batch_challenge = trv.get_challenge(b"batch_challenge")
+        for c in got["folded_polynomials_commitments"]:
+            trv.append_message(b"commitment", pyref.g1_serialize_uncompressed(c))
+        eval_chal = trv.get_challenge(b"evaluation-chal")
+        asserted, direct = [], []
+        for idx, ch in bodies:
+            tensor = pyref.tensor(ch)
+            asserted.append([pyref.ip(polys[i], tensor[:len(polys[i])]) for i in idx])
+            e0 = e1 = 0
+            for j, i in enumerate(idx):
+                w = pow(batch_challenge, j, R)
+                e0 = (e0 + w * got["base_polynomials_evaluations"][i][1]) % R
+                e1 = (e1 + w * got["base_polynomials_evaluations"][i][2]) % R
+            direct.append([e0, e1])
+        base_commitments = [sr.commit(srs, p) for p in polys]
+        V.tensorcheck_verify(got, trv, vk, asserted, base_commitments, direct, [ch for _, ch in bodies], eval_chal, batch_challenge)
     # the proof record round-trips through the wire schema
     for compress in (True, False):
         back = wire.deserialize(wire.TENSORCHECK_PROOF, wire.serialize(wire.TENSORCHECK_PROOF, tc, compress=compress), compress=compress)
