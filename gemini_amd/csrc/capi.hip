@@ -756,6 +756,25 @@ int gm_set_msm_glv(int on) {
   return GM_OK;
 }
 
+int gm_set_msm_sort_group(int mode, size_t cap) {
+  GM_CTX();
+  GM_CHECK(mode == 0 || mode == 1, GM_EINVAL, "gm_set_msm_sort_group: mode = %d not in {0, 1}", mode);
+  GM_CHECK(cap == 0 || (cap >= MSM_SORT_GROUP_CAP_MIN && cap <= MSM_SORT_GROUP_CAP_MAX), GM_EINVAL,
+           "gm_set_msm_sort_group: a block stages %zu .. %zu entries in its LDS (0 = the most), not %zu", MSM_SORT_GROUP_CAP_MIN, MSM_SORT_GROUP_CAP_MAX, cap);
+  std::lock_guard<std::recursive_mutex> lk(C->msm_mu);
+  C->msm_sort_group = mode;
+  C->msm_sort_group_cap = cap;
+  return GM_OK;
+}
+
+int gm_debug_msm_sort_path(int* out) {
+  GM_CTX();
+  GM_CHECK(out != nullptr, GM_EINVAL, "gm_debug_msm_sort_path: null output");
+  std::lock_guard<std::recursive_mutex> lk(C->msm_mu);
+  *out = C->msm_sort_path_last;
+  return GM_OK;
+}
+
 int gm_set_msm_split(int on) {
   GM_CTX();
 #ifndef GM_EXPERIMENTS

@@ -222,6 +222,10 @@ struct PairingWorkspace {
 // ChunkedPippenger / msm_chunks over HOST-resident pairs (src/kzg/msm/stream_pippenger.rs:209-272, src/kzg/space.rs:22-55):
 // the device holds two chunks; chunk i + 1 is copied in while the MSM of chunk i runs (msm.hip: msm_stream_*)
 struct MsmWorkspace;
+// k_sort2_group (msm.hip): 4-byte entries one block stages in its 160 KiB of LDS beside three arrays of 1024 counters and the
+// wave sums of its scan; at least one entry per thread
+constexpr size_t MSM_SORT_GROUP_CAP_MAX = (160 * 1024 - 3 * 1024 * 4 - 64) / 4;
+constexpr size_t MSM_SORT_GROUP_CAP_MIN = 1024;
 // One MSM between its enqueue (all kernels + the async copy of the window bit-planes) and its finish (host Horner)
 struct MsmPending {
   MsmWorkspace* ws = nullptr;  // the workspace (and stream) the call was enqueued on
@@ -233,6 +237,7 @@ struct MsmPending {
   size_t plane_count = 0;
   int multi_levels = 0;  // > 0: several small MSMs in ONE pass (msm.hip: MsmMulti); bucket sets [l W, (l + 1) W) belong to call l
   int multi_W = 0;
+  bool sort_compact = false;  // the block sort took the 4-byte pass-1 entries + k_sort2_group (gm_debug_msm_sort_path)
 };
 struct MsmStreamSlot {
   uint8_t *raw = nullptr, *packed = nullptr, *scalars = nullptr;  // staged records, device-form bases, scalars
@@ -380,6 +385,11 @@ struct Context {
   int msm_glv = 0;            // build phi(P) at registration and split scalars by the GLV endomorphism (gm_set_msm_glv)
   int msm_split = 0;          // one-call MSMs as two window groups over three streams (gm_set_msm_split)
   int msm_affine_levels = 0;  // affine tree levels in front of the XYZZ accumulation; -1 = automatic
+  // block sort of a plain call (gm_set_msm_sort_group): 1 = 4-byte pass-1 entries and one block per coarse group where that
+  // applies, 0 = the 8-byte passes; cap = entries a block of k_sort2_group loads at once (0 = all that fits beside its counters)
+  int msm_sort_group = 1;
+  size_t msm_sort_group_cap = 0;
+  int msm_sort_path_last = 0;  // what the last finished call took: 0 old, 1 compact, 2 compact with a chunked group
   size_t msm_table_min = (size_t)1 << 17;  // smallest MSM that uses fixed-base tables when present
   // small results (per-block partial sums, the bit-plane sums of an MSM) are written by their kernels straight into pinned host
   // memory instead of a device buffer that a blit kernel then copies (GM_ZERO_COPY=0 restores the copies; bit 0 field paths, bit 1 MSM planes.  Two A/B runs on one box: snark -i 20 14.9 -> 14.5 ms, -i 24 117.8 -> 117.0, psnark -i 20 129 -> 127, same proof bytes: profiles/r4_zero_copy_probe.txt)

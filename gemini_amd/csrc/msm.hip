@@ -404,7 +404,7 @@ __global__ __launch_bounds__(1024) void k_sort1_staged(const uint32_t* __restric
 // exclusive scan of the G coarse counters + prefix of the pass-2 block counts (one block)
 __global__ __launch_bounds__(1024) void k_sort1_scan(const uint32_t* __restrict__ gcount, uint32_t G,
                                                      uint32_t* __restrict__ goff, uint32_t* __restrict__ gcursor,
-                                                     uint32_t* __restrict__ blkoff) {
+                                                     uint32_t* __restrict__ blkoff, uint32_t* __restrict__ total_out) {
   __shared__ uint32_t a[1024], b[1024];
   const uint32_t tid = threadIdx.x;
   const uint32_t per = (G + 1023u) / 1024u;  // <= 4
@@ -440,6 +440,7 @@ __global__ __launch_bounds__(1024) void k_sort1_scan(const uint32_t* __restrict_
   if (tid == 1023) {
     goff[G] = a[1023];
     blkoff[G] = b[1023];
+    if (total_out) *total_out = a[1023];  // the entry count k_acc0 reads, where no later scan of the bucket counters writes it
   }
 }
 
@@ -577,6 +578,242 @@ __global__ __launch_bounds__(1024) void k_sort2_staged(const uint64_t* __restric
     const uint64_t v = buf[i];
     const uint32_t f = (uint32_t)(v >> 32) & mask;
     entries[base[f] + (i - lst[f])] = v;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// The block sort of a PLAIN call with 4-byte pass-1 entries (msm_enqueue: sort_compact).
+//
+// After pass 1 the coarse bin of an entry is implied by its position (goff), so the intermediate entry only carries
+//   fine key bits : FB | sign : 1 | pair index : 31 - FB          (10 | 1 | 21 at c = 16: up to 2^21 pairs)
+// and a whole coarse group of a 2^20-pair call (<= 36.6 Ki entries) fits the LDS of ONE block.  Pass 2 is then one kernel, one
+// block per group, that reads its group once, ranks it in LDS and streams the final 8-byte entries out contiguously: no count
+// pass, no global scan, no second read of the intermediate array.
+// ------------------------------------------------------------------------------------------
+GM_DEV uint32_t sort_entry_expand_hi(uint32_t v, uint32_t g, uint32_t FB) { return (g << FB) | (v >> (32u - FB)); }
+GM_DEV uint64_t sort_entry_expand(uint32_t v, uint32_t g, uint32_t FB) {
+  const uint32_t ib = 31u - FB;
+  return ((uint64_t)sort_entry_expand_hi(v, g, FB) << 32) | (uint64_t)(((v >> ib) & 1u) << 31) | (uint64_t)(v & ((1u << ib) - 1u));
+}
+
+// k_sort1_staged for those entries: the same 1024 scalars per block, the LDS image is 4 bytes per entry (2048 scalars per block,
+// which would keep the byte length of the runs, measured the same: profiles/msm_group_sort.md).  Plain calls only (no levels,
+// tables or GLV).  The image leaves by coarse bin, one half-wave per bin, as one contiguous run.
+__global__ __launch_bounds__(1024) void k_sort1_staged_c(const uint32_t* __restrict__ scalars, uint32_t n, int mont, SortGeom sg,
+                                                         uint32_t* __restrict__ gcursor, uint32_t* __restrict__ tmp) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  uint32_t* buf = reinterpret_cast<uint32_t*>(smem);
+  uint32_t* cnt = buf + (size_t)SORT_TS * sg.Wg;
+  uint32_t* base = cnt + sg.G;
+  uint32_t* lst = base + sg.G;
+  uint32_t* scan = lst + sg.G;
+  const uint32_t tid = threadIdx.x;
+  for (uint32_t g = tid; g < sg.G; g += 1024) cnt[g] = 0;
+  __syncthreads();
+  const uint32_t i = blockIdx.x * SORT_TS + tid;
+  const bool active = i < n;
+  uint32_t ks[SORT1_STAGE_WMAX];  // key | sign << 31 per window; ~0 = no entry
+  {
+    DigitIter it;
+    it.init(scalars + 8 * (size_t)(active ? i : 0), active, mont);
+#pragma unroll
+    for (int j = 0; j < SORT1_STAGE_WMAX; j++) {
+      uint32_t k = ~0u;
+      if (j < sg.Wg) {
+        const int32_t d = j == sg.W - 1 ? it.last(sg.c) : it.next(sg.c);
+        if (active && d != 0) k = ((uint32_t)j * sg.B + ((uint32_t)(d < 0 ? -d : d) - 1u)) | (d < 0 ? 0x80000000u : 0u);
+      }
+      ks[j] = k;
+      wave_atomic_inc(cnt, k != ~0u ? (k & 0x7fffffffu) >> sg.FB : KEY_INV);
+    }
+  }
+  __syncthreads();
+  const uint32_t per = (sg.G + 1023u) / 1024u;
+  uint32_t s = 0;
+  for (uint32_t k = 0; k < per; k++) {
+    const uint32_t g = tid * per + k;
+    if (g < sg.G) {
+      const uint32_t c = cnt[g];
+      base[g] = c ? atomicAdd(gcursor + g, c) : 0u;
+      s += c;
+    }
+  }
+  scan[tid] = s;
+  __syncthreads();
+  for (uint32_t d = 1; d < 1024; d <<= 1) {
+    const uint32_t x = tid >= d ? scan[tid - d] : 0;
+    __syncthreads();
+    scan[tid] += x;
+    __syncthreads();
+  }
+  uint32_t run = scan[tid] - s;
+  for (uint32_t k = 0; k < per; k++) {
+    const uint32_t g = tid * per + k;
+    if (g < sg.G) {
+      lst[g] = run;
+      run += cnt[g];
+    }
+  }
+  __syncthreads();
+  for (uint32_t g = tid; g < sg.G; g += 1024) cnt[g] = 0;
+  __syncthreads();
+  const uint32_t ib = 31u - sg.FB, fmask = (1u << sg.FB) - 1u;
+#pragma unroll
+  for (int j = 0; j < SORT1_STAGE_WMAX; j++) {
+    const uint32_t k = ks[j];
+    const bool live = k != ~0u;
+    const uint32_t key = k & 0x7fffffffu, g = key >> sg.FB;
+    const uint32_t r = wave_atomic_inc(cnt, live ? g : KEY_INV);
+    if (live) buf[lst[g] + r] = ((key & fmask) << (ib + 1u)) | ((k >> 31) << ib) | i;
+  }
+  __syncthreads();
+  // (the bins a half-wave serves are rotated against the window: equal scalars put one bin of EVERY window, often the same
+  // bin number, on the block -- those 16 long runs then leave through 16 different half-waves)
+  const uint32_t hw = tid >> 5, hl = tid & 31u;
+  for (uint32_t k = 0; k * 32u < sg.G; k++) {
+    const uint32_t g = k * 32u + ((hw + k) & 31u);
+    if (g >= sg.G) continue;
+    const uint32_t c = cnt[g], l0 = lst[g], b0 = base[g];
+    for (uint32_t o = hl; o < c; o += 32u) tmp[b0 + o] = buf[l0 + o];
+  }
+}
+
+// inclusive scan over the 1024 threads of a block: shuffles inside a wave, the 16 wave sums through LDS
+GM_DEV uint32_t block_inclusive_scan_1024(uint32_t v, uint32_t* wsum /* 16 */) {
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (uint32_t d = 1; d < 64; d <<= 1) {
+    const uint32_t x = __shfl_up(v, d);
+    if (lane >= d) v += x;
+  }
+  __syncthreads();  // the previous use of wsum has been read
+  if (lane == 63) wsum[wv] = v;
+  __syncthreads();
+  uint32_t add = 0;
+  for (uint32_t k = 0; k < wv; k++) add += wsum[k];
+  return v + add;
+}
+
+// Pass 2 of that sort: block g owns coarse group g = tmp[goff[g] .. goff[g + 1]).  A group of at most `cap` entries is loaded
+// ONCE (16-byte loads into registers), counted and ranked by fine bin in LDS, and the sorted image streamed out as final 8-byte
+// entries -- lane j writes entries[goff[g] + j].  A larger group (n near 2^21, skewed or all-equal scalars) takes the same block
+// two sweeps: a counting sweep over the whole group, then the chunks of `cap` entries one after the other, each to its bins'
+// next free ranges.  The block writes counts[] and offsets[] of its 2^FB buckets; blocks do not depend on one another.
+// Dynamic LDS: three arrays of 1024 counters, 16 wave sums, cap entries.
+constexpr uint32_t SORT2G_QPT = 10;  // 16-byte loads per thread: 40 Ki entries >= MSM_SORT_GROUP_CAP_MAX + 3
+static_assert(SORT2G_QPT * 4096 >= MSM_SORT_GROUP_CAP_MAX + 3, "k_sort2_group: a chunk must fit the registers of its block");
+// entries [s0, s0 + mc) of tmp in the registers of a block: the 16-byte words that cover them -- up to 3 entries before and after
+// belong to neighbours (tmp is allocated past its last entry) and are masked out; element 4 q + t of the words is entry
+// 4 q + t - off of the chunk
+template <uint32_t QPT>
+struct Sort2gChunk {
+  uint32_t v[4 * QPT];
+  uint32_t off, nq, mc;
+  GM_DEV void load(const uint32_t* __restrict__ tmp, uint32_t s0, uint32_t mc_) {
+    mc = mc_;
+    off = s0 & 3u;
+    nq = (off + mc + 3u) >> 2;
+    const uint4* t4 = reinterpret_cast<const uint4*>(tmp) + (s0 >> 2);
+#pragma unroll
+    for (uint32_t kq = 0; kq < QPT; kq++) {
+      const uint32_t q = kq * 1024 + threadIdx.x;
+      uint4 x = make_uint4(0, 0, 0, 0);
+      if (q < nq) x = t4[q];
+      v[4 * kq] = x.x;
+      v[4 * kq + 1] = x.y;
+      v[4 * kq + 2] = x.z;
+      v[4 * kq + 3] = x.w;
+    }
+  }
+  // entry index of register 4 kq + t inside the chunk; wraps (>= mc) for the entries before the chunk
+  GM_DEV uint32_t at(uint32_t kq, uint32_t t) const { return 4u * (kq * 1024 + threadIdx.x) + t - off; }
+  // histogram of the fine bins; whole waves enter wave_atomic_inc together
+  GM_DEV void count(uint32_t* cnt, uint32_t fsh) const {
+#pragma unroll
+    for (uint32_t kq = 0; kq < QPT; kq++) {
+      if (kq * 1024 < nq) {  // block-uniform
+#pragma unroll
+        for (uint32_t t = 0; t < 4; t++) wave_atomic_inc(cnt, at(kq, t) < mc ? v[4 * kq + t] >> fsh : KEY_INV);
+      }
+    }
+  }
+};
+__global__ __launch_bounds__(1024) void k_sort2_group(const uint32_t* __restrict__ tmp, const uint32_t* __restrict__ goff, SortGeom sg, uint32_t cap,
+                                                      uint32_t* __restrict__ counts, uint32_t* __restrict__ offsets, uint64_t* __restrict__ entries,
+                                                      uint32_t* __restrict__ chunked) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  uint32_t* ccnt = reinterpret_cast<uint32_t*>(smem);  // counts of the chunk per fine bin
+  uint32_t* clst = ccnt + 1024;                        // ... and their exclusive scan
+  uint32_t* glst = clst + 1024;                        // chunked groups: where each bin's next entries go, relative to goff[g]
+  uint32_t* wsum = glst + 1024;
+  uint32_t* buf = wsum + 16;
+  const uint32_t tid = threadIdx.x, g = blockIdx.x;
+  const uint32_t nf = 1u << sg.FB, fsh = 32u - sg.FB, b0 = g << sg.FB;
+  const uint32_t lo = goff[g], m = goff[g + 1] - lo;
+  if (m == 0) {  // counts[] are zero from the call's memset
+    if (tid < nf) offsets[b0 + tid] = lo;
+    return;
+  }
+  const bool single = m <= cap;
+  if (!single) {
+    glst[tid] = 0;
+    __syncthreads();
+    constexpr uint32_t CQ = 4;  // (steps of 16 Ki entries: the chunks' 40 registers per thread here as well would spill)
+    for (uint32_t c0 = 0; c0 < m; c0 += CQ * 4096 - 3) {
+      Sort2gChunk<CQ> ch;
+      ch.load(tmp, lo + c0, min(CQ * 4096 - 3, m - c0));
+      ch.count(glst, fsh);
+    }
+    __syncthreads();
+    const uint32_t c = glst[tid];
+    const uint32_t ex = block_inclusive_scan_1024(c, wsum) - c;
+    if (tid < nf) {
+      counts[b0 + tid] = c;
+      offsets[b0 + tid] = lo + ex;
+    }
+    glst[tid] = ex;
+    if (tid == 0) *chunked = 1u;
+  }
+  for (uint32_t c0 = 0; c0 < m; c0 += cap) {
+    const uint32_t mc = min(cap, m - c0);
+    ccnt[tid] = 0;
+    __syncthreads();
+    Sort2gChunk<SORT2G_QPT> ch;
+    ch.load(tmp, lo + c0, mc);
+    ch.count(ccnt, fsh);
+    __syncthreads();
+    const uint32_t c = ccnt[tid];
+    const uint32_t ex = block_inclusive_scan_1024(c, wsum) - c;
+    clst[tid] = ex;
+    if (single && tid < nf) {
+      counts[b0 + tid] = c;
+      offsets[b0 + tid] = lo + ex;
+    }
+    ccnt[tid] = 0;
+    __syncthreads();
+#pragma unroll
+    for (uint32_t kq = 0; kq < SORT2G_QPT; kq++) {
+      if (kq * 1024 < ch.nq) {
+#pragma unroll
+        for (uint32_t t = 0; t < 4; t++) {
+          const bool live = ch.at(kq, t) < mc;
+          const uint32_t x = ch.v[4 * kq + t], f = x >> fsh;
+          const uint32_t r = wave_atomic_inc(ccnt, live ? f : KEY_INV);
+          if (live) buf[clst[f] + r] = x;
+        }
+      }
+    }
+    __syncthreads();
+    if (single) {
+      for (uint32_t j = tid; j < mc; j += 1024) entries[lo + j] = sort_entry_expand(buf[j], g, sg.FB);
+    } else {
+      for (uint32_t j = tid; j < mc; j += 1024) {
+        const uint32_t x = buf[j], f = x >> fsh;
+        entries[lo + glst[f] + (j - clst[f])] = sort_entry_expand(x, g, sg.FB);
+      }
+      __syncthreads();
+      glst[tid] += ccnt[tid];  // ordered against the next chunk's readers by the barrier at the top of the loop
+    }
   }
 }
 
@@ -1201,6 +1438,7 @@ struct GroupSumJobs {
   const uint32_t* err_src;  // last launch of a call: forward the scalar-range flag behind the plane sums
   uint32_t* err_dst;         // ... and the clock readings of the call's k_acc0 (two 64-bit words at err_dst + 2)
   const unsigned long long* clk_src;
+  const uint32_t* chunked_src;  // ... and k_sort2_group's "a group was chunked" word, to err_dst[1]
 };
 
 // up to three independent jobs per launch so that passes of the same level overlap instead of
@@ -1209,6 +1447,7 @@ struct GroupSumJobs {
 __global__ __launch_bounds__(256) void k_group_sum(GroupSumJobs J) {
   if (J.err_dst && blockIdx.x == 0 && threadIdx.x == 0) {
     *J.err_dst = *J.err_src;
+    J.err_dst[1] = J.chunked_src ? *J.chunked_src : 0u;
     if (J.clk_src) {
       unsigned long long* d = reinterpret_cast<unsigned long long*>(J.err_dst + 2);
       d[0] = J.clk_src[0];
@@ -1978,6 +2217,7 @@ static int msm_enqueue(Context* C, MsmWorkspace& ws, MsmStreams sts, const Bases
   P->ws = &ws;
   P->slot = slot;
   P->multi_levels = 0;
+  P->sort_compact = false;
   if (multi) {
     GM_CHECK(multi->levels >= 1 && multi->levels <= MULTI_MAX_LEVELS && nparts == 1, GM_EINVAL, "msm: %d fused calls (1 .. %d)", multi->levels, MULTI_MAX_LEVELS);
     // the entries of a fused pass carry ABSOLUTE base indices in 30 bits (bit 30: the GLV half, bit 31: the sign)
@@ -2101,8 +2341,9 @@ static int msm_enqueue(Context* C, MsmWorkspace& ws, MsmStreams sts, const Bases
   const uint64_t E1 = 2 * T0pad;
 
   int rc;
-  // [nbuckets + 1] = scalar-range flag; behind it the coarse-bin counters of the block sort, so that ONE memset clears both
-  const size_t counts_words = (nbuckets + 2 + SORT_GMAX + 1 + 63) / 64 * 64;
+  // [nbuckets + 1] = scalar-range flag; behind it the coarse-bin counters of the block sort and the word k_sort2_group sets when
+  // it chunks a group, so that ONE memset clears them all
+  const size_t counts_words = (nbuckets + 2 + SORT_GMAX + 2 + 63) / 64 * 64;
   if ((rc = ws.counts.ensure(counts_words * 4))) return rc;
   if ((rc = ws.offsets.ensure((nbuckets + 1) * 4))) return rc;
   if ((rc = ws.cursor.ensure((nbuckets + 1) * 4))) return rc;
@@ -2118,6 +2359,7 @@ static int msm_enqueue(Context* C, MsmWorkspace& ws, MsmStreams sts, const Bases
   const uint32_t* sc = reinterpret_cast<const uint32_t*>(d_scalars);
   GM_HIP(hipMemsetAsync(ws.counts.p, 0, counts_words * 4, st));
   uint32_t* d_err = ws.counts.as<uint32_t>() + nbuckets + 1;
+  uint32_t* d_chunked = ws.counts.as<uint32_t>() + nbuckets + 2 + SORT_GMAX + 1;
   // levels (an experiment build) rewrite the entry lists, so the counts no longer say which buckets get written: clear there
   const bool bucket_counts_valid = levels == 0;
   if (!bucket_counts_valid) GM_HIP(hipMemsetAsync(ws.buckets.p, 0, nbuckets * bucket_bytes, st));
@@ -2235,12 +2477,30 @@ static int msm_enqueue(Context* C, MsmWorkspace& ws, MsmStreams sts, const Bases
     uint32_t* blkoff = gcursor + (sg.G + 1);
     const uint32_t b1 = (uint32_t)((n + SORT_TS - 1) / SORT_TS);
     const uint32_t b2 = (uint32_t)(N / SORT_CH + sg.G + 1);
+    static const bool sort1_staged_env = !(getenv("GM_MSM_SORT1") && !strcmp(getenv("GM_MSM_SORT1"), "direct"));
+    static const bool sort_staged = !(getenv("GM_MSM_SORT2") && !strcmp(getenv("GM_MSM_SORT2"), "direct"));
+    // a plain call whose pair index, sign and fine key bits fit 32 bits: 4-byte pass-1 entries, pass 2 in one kernel (k_sort2_group)
+    const size_t stage1c_lds = (size_t)SORT_TS * sg.Wg * 4 + (size_t)3 * sg.G * 4 + 1024 * 4;
+    const bool sort_compact = C->msm_sort_group == 1 && !use_table && !use_glv && !multi && nparts == 1 && N > ((uint64_t)1 << 21) &&
+                              sg.FB <= 10 && ceil_log2_sz(n) + (int)sg.FB + 1 <= 32 && sort1_staged_env && sort_staged &&
+                              sg.Wg <= SORT1_STAGE_WMAX && stage1c_lds <= 160 * 1024;
+    P->sort_compact = sort_compact;
+    uint32_t* tmp32 = ws.tmp_entries.as<uint32_t>();
     pf.begin(part, PROF_DIGITS, st);
     hipLaunchKernelGGL(k_sort1<false>, dim3(b1), dim3(256), 0, st, sc, (uint32_t)n, mont, sg, lg, gcount, (uint64_t*)nullptr, d_err);
-    hipLaunchKernelGGL(k_sort1_scan, dim3(1), dim3(1024), 0, st, gcount, sg.G, goff, gcursor, blkoff);
+    // (k_sort2_group writes the buckets' offsets itself: the entry count k_acc0 reads behind them comes from the coarse scan)
+    hipLaunchKernelGGL(k_sort1_scan, dim3(1), dim3(1024), 0, st, gcount, sg.G, goff, gcursor, blkoff,
+                       sort_compact ? ws.offsets.as<uint32_t>() + nbuckets : (uint32_t*)nullptr);
     const size_t stage1_lds = (size_t)SORT_TS * sg.Wg * (use_glv ? 2 : 1) * 8 + (size_t)3 * sg.G * 4 + 1024 * 4;
-    static const bool sort1_staged_env = !(getenv("GM_MSM_SORT1") && !strcmp(getenv("GM_MSM_SORT1"), "direct"));
-    if (sort1_staged_env && sg.Wg * (use_glv ? 2 : 1) <= SORT1_STAGE_WMAX && stage1_lds <= 160 * 1024) {
+    if (sort_compact) {
+      static bool attr_set = false;
+      if (!attr_set) {
+        GM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sort1_staged_c), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        GM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sort2_group), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        attr_set = true;
+      }
+      hipLaunchKernelGGL(k_sort1_staged_c, dim3(b1), dim3(1024), stage1c_lds, st, sc, (uint32_t)n, mont, sg, gcursor, tmp32);
+    } else if (sort1_staged_env && sg.Wg * (use_glv ? 2 : 1) <= SORT1_STAGE_WMAX && stage1_lds <= 160 * 1024) {
       static bool attr_set = false;
       if (!attr_set) {
         GM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sort1_staged), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -2252,16 +2512,21 @@ static int msm_enqueue(Context* C, MsmWorkspace& ws, MsmStreams sts, const Bases
     }
     pf.end(part, PROF_DIGITS, st);
     pf.begin(part, PROF_SCATTER, st);
-    hipLaunchKernelGGL(k_sort2<false>, dim3(b2), dim3(256), 0, st, ws.tmp_entries.as<uint64_t>(), goff, blkoff, sg,
-                       ws.counts.as<uint32_t>(), (uint64_t*)nullptr);
-    run_scan();
-    static const bool sort_staged = !(getenv("GM_MSM_SORT2") && !strcmp(getenv("GM_MSM_SORT2"), "direct"));
-    if (sort_staged && (1u << sg.FB) <= SORT_STAGE_FMAX)
-      hipLaunchKernelGGL(k_sort2_staged, dim3(b2), dim3(1024), 0, st, ws.tmp_entries.as<uint64_t>(), goff, blkoff, sg,
-                         ws.cursor.as<uint32_t>(), ws.entries.as<uint64_t>());
-    else
-      hipLaunchKernelGGL(k_sort2<true>, dim3(b2), dim3(256), 0, st, ws.tmp_entries.as<uint64_t>(), goff, blkoff, sg,
-                         ws.cursor.as<uint32_t>(), ws.entries.as<uint64_t>());
+    if (sort_compact) {
+      const uint32_t cap = (uint32_t)(C->msm_sort_group_cap ? C->msm_sort_group_cap : MSM_SORT_GROUP_CAP_MAX);
+      hipLaunchKernelGGL(k_sort2_group, dim3(sg.G), dim3(1024), (size_t)(3 * 1024 + 16 + cap) * 4, st, tmp32, goff, sg, cap, ws.counts.as<uint32_t>(),
+                         ws.offsets.as<uint32_t>(), ws.entries.as<uint64_t>(), d_chunked);
+    } else {
+      hipLaunchKernelGGL(k_sort2<false>, dim3(b2), dim3(256), 0, st, ws.tmp_entries.as<uint64_t>(), goff, blkoff, sg,
+                         ws.counts.as<uint32_t>(), (uint64_t*)nullptr);
+      run_scan();
+      if (sort_staged && (1u << sg.FB) <= SORT_STAGE_FMAX)
+        hipLaunchKernelGGL(k_sort2_staged, dim3(b2), dim3(1024), 0, st, ws.tmp_entries.as<uint64_t>(), goff, blkoff, sg,
+                           ws.cursor.as<uint32_t>(), ws.entries.as<uint64_t>());
+      else
+        hipLaunchKernelGGL(k_sort2<true>, dim3(b2), dim3(256), 0, st, ws.tmp_entries.as<uint64_t>(), goff, blkoff, sg,
+                           ws.cursor.as<uint32_t>(), ws.entries.as<uint64_t>());
+    }
     pf.end(part, PROF_SCATTER, st);
   }
   const uint64_t* acc_entries = ws.entries.as<uint64_t>();
@@ -2388,6 +2653,7 @@ static int msm_enqueue(Context* C, MsmWorkspace& ws, MsmStreams sts, const Bases
       J.err_src = d_err;
       J.err_dst = reinterpret_cast<uint32_t*>(planes + plane_count * XYZZ_BYTES);
       J.clk_src = ws.clk.as<unsigned long long>();
+      J.chunked_src = d_chunked;
     }
     uint32_t tot = 0;
     int k = 0;
@@ -2406,7 +2672,7 @@ static int msm_enqueue(Context* C, MsmWorkspace& ws, MsmStreams sts, const Bases
     plane_off[k] = plane_count;
     plane_count += (size_t)Wb * (wf[k] + 1);
   }
-  const size_t plane_bytes = plane_count * XYZZ_BYTES + 24;  // + the scalar-range flag + k_acc0's clock readings
+  const size_t plane_bytes = plane_count * XYZZ_BYTES + 24;  // + the scalar-range flag, the sort's chunked word + k_acc0's clock readings
   if (ws.host_planes_cap[slot] < plane_bytes) {
     if (ws.host_planes[slot]) (void)hipHostFree(ws.host_planes[slot]);
     ws.host_planes[slot] = nullptr;
@@ -2632,6 +2898,7 @@ static int msm_finish_parts(Context* C, const MsmPending* parts, int nparts, boo
     if (P.Wb > 1 && use_pool) HornerPool::get().prewake();
     GM_HIP(hipEventSynchronize(ws.done_ev[P.slot]));
     const uint64_t* hp = ws.host_planes[P.slot];
+    C->msm_sort_path_last = P.sort_compact ? 1 + (int)((hp[P.plane_count * 24] >> 32) != 0) : 0;
     if ((uint32_t)hp[P.plane_count * 24] != 0) {
       set_error("msm: a scalar passed as a canonical integer is >= 2^255 (not the BigInt image of an Fr element)");
       rc = GM_EINVAL;  // keep draining: every part's copy-out must have completed before the workspaces are reused
@@ -2763,7 +3030,7 @@ int msm_sort_plain(Context* C, MsmWorkspace& ws, hipStream_t st, const void* d_s
     const uint32_t b2 = (uint32_t)(N / SORT_CH + sg.G + 1);
     const uint32_t nb = (uint32_t)((nbuckets + SCAN_PER_BLOCK - 1) / SCAN_PER_BLOCK);
     hipLaunchKernelGGL(k_sort1<false>, dim3(b1), dim3(256), 0, st, sc, (uint32_t)n, mont, sg, lg, gcount, (uint64_t*)nullptr, d_err);
-    hipLaunchKernelGGL(k_sort1_scan, dim3(1), dim3(1024), 0, st, gcount, sg.G, goff, gcursor, blkoff);
+    hipLaunchKernelGGL(k_sort1_scan, dim3(1), dim3(1024), 0, st, gcount, sg.G, goff, gcursor, blkoff, (uint32_t*)nullptr);
     hipLaunchKernelGGL(k_sort1<true>, dim3(b1), dim3(256), 0, st, sc, (uint32_t)n, mont, sg, lg, gcursor, ws.tmp_entries.as<uint64_t>(), d_err);
     hipLaunchKernelGGL(k_sort2<false>, dim3(b2), dim3(256), 0, st, ws.tmp_entries.as<uint64_t>(), goff, blkoff, sg, ws.counts.as<uint32_t>(),
                        (uint64_t*)nullptr);

@@ -237,6 +237,15 @@ int gm_set_msm_table_min(size_t n);
  * the base memory.  Same results; no net gain on MI355X as measured.  A round-3 EXPERIMENT: the code
  * (gemini_amd/csrc/msm_glv.inc) is only in builds with -DGM_EXPERIMENTS; otherwise on != 0 returns GM_EINVAL. */
 int gm_set_msm_glv(int on);
+/* The bucket sort of a plain one-call MSM (no tables) above 2^21 entries whose pair index, sign and 10 fine key bits fit 32 bits
+ * (2^17 < n <= 2^21 pairs at c = 16).  mode 1 (default): the first pass writes 4-byte entries and ONE block finishes each coarse
+ * group of the second; mode 0: the 8-byte passes every other call takes.  cap: entries such a block loads at once -- 0 = all its
+ * LDS holds (37 872); a smaller value (>= 1024) makes ordinary inputs take the chunked branch that oversized groups take.
+ * GM_EINVAL for a cap outside that range.  The result does not depend on either.  Test / A-B knob. */
+int gm_set_msm_sort_group(int mode, size_t cap);
+/* Which sort the last finished MSM call took: 0 = the 8-byte passes (or no block sort at all), 1 = 4-byte entries with every
+ * coarse group loaded once, 2 = 4-byte entries with at least one group chunked.  Travels with the call's result: no extra sync. */
+int gm_debug_msm_sort_path(int* out);
 /* Tuning knob (default 0): run one-call MSMs of >= 2^17 pairs as two window groups pipelined over three streams.
  * Same results; slower on MI355X as measured.  Builds with -DGM_EXPERIMENTS only; otherwise on != 0 returns GM_EINVAL. */
 int gm_set_msm_split(int on);
