@@ -53,6 +53,8 @@ SYMBOLS = [
     "gm_spm_bilinear_pm", "gm_vk_new", "gm_vk_from_trapdoor", "gm_vk_free", "gm_vk_len", "gm_vk_g2_bytes", "gm_kzg_verify", "gm_kzg_verify_multi_points",
     "gm_sumcheck_subclaim", "gm_sumcheck_subclaim_batch", "gm_tensorcheck_verify", "gm_snark_verify", "gm_psnark_verify",
     "gm_g1_check", "gm_g2_check", "gm_g1_bases_check", "gm_g2_bases_check", "gm_g1_bases_from_bytes", "gm_g1_powers_check",
+    "gm_g2_bases_from_bytes", "gm_g1_bases_to_bytes", "gm_g2_bases_to_bytes", "gm_crs_from_bases", "gm_crs_check", "gm_vk_check",
+    "gm_snark_proof_check", "gm_psnark_proof_check", "gm_ipa_check", "gm_debug_fq2_sqrt",
     "gm_ipa_foldings_fg1", "gm_ipa_foldings_fg2", "gm_ipa_free", "gm_ipa_host_times", "gm_ipa_from_fields", "gm_ipa_verify", "gm_transcript_append_gt",
 ]
 

@@ -1,5 +1,6 @@
 // Validation and decoding of UNTRUSTED G1 / G2 points on the device (gfx950): canonical coordinates, the curve equation, membership
-// of the prime-order subgroup, the two G1 byte framings of gemini_amd/wire.py, and the powers-of-tau structure of a committer key.
+// of the prime-order subgroup, the two byte framings of gemini_amd/wire.py (G1) and gemini_amd/g2.py (G2) in both directions, the
+// powers-of-tau structure of a committer key, and the check entries of what a verifier consumes (a CRS, a verifier key, a proof).
 //
 // Replaces, for whole keys, what `CanonicalDeserialize::deserialize_with_mode(.., Validate::Yes)` of ark-ec 0.4.2 does per point
 // (is_on_curve, then is_in_correct_subgroup_assuming_on_curve); gemini_amd/wire.py states the same on Python integers with [r] P
@@ -14,7 +15,8 @@
 //   G2   psi(Q) = (conj(x) c_x, conj(y) c_y) == [x] Q = -[|x|] Q     one double-and-add by |x| over Fq2
 //
 // Fq products per point as written (a square counts as a product): G1 check 5 (import + curve) + 126 x 9 + 5 x 10 + 5 x 14 + 3
-// = 1262; G2 check 11 (import + curve) + 63 x 24 + 5 x 28 + 11 = 1674; a compressed decode adds the square root, 378 squares + 228 products.
+// = 1262; G2 check 11 (import + curve) + 63 x 24 + 5 x 28 + 11 = 1674; a compressed G1 decode adds the square root, 378 squares + 228 products, a compressed G2 decode
+// the one in Fq2, 1221 products (pt_fq2_sqrt).
 //
 // Reporting: ONE status byte per point (the first check that fails, gemini_hip.h: GM_PT_*), written with ordinary stores, and one
 // u32 per block holding the block's first bad lane.  The host reads the block summaries (and the status bytes when the caller asks
@@ -48,6 +50,9 @@ __device__ constexpr uint32_t PT_PSI_CY0[12] = {0x57305ee1u, 0x79f31769u, 0x99dc
                                                 0xadfc665fu, 0x49c73136u, 0x7fa999feu, 0xdc319445u, 0xdd1a928cu, 0x0345b796u};
 __device__ constexpr uint32_t PT_PSI_CY1[12] = {0xa8cf4bcau, 0x400be896u, 0x17779f28u, 0xf31fb077u, 0x102f0baau, 0x0da77cbau,
                                                 0x4588ac60u, 0x1ab01a4eu, 0xc3a212d9u, 0x6eea1370u, 0x5c65540du, 0x16bb5a53u};
+// 1 / 2 = 2^389 mod q
+__device__ constexpr uint32_t PT_HALF[12] = {0x0068ff97u, 0x233b0000u, 0xcda40056u, 0x425c019bu, 0x7441218eu, 0x06ecd3f0u,
+                                             0x5b41ee7cu, 0x61361368u, 0x31e252f7u, 0x94f8a2bbu, 0x3f9f4025u, 0x00aef4cbu};
 // 2^780 mod q: the product of a canonical INTEGER with it is that integer in the device form
 __device__ constexpr uint32_t PT_R2[12] = {0x4510070fu, 0xaec641c3u, 0xa0132243u, 0x6ea66ec3u, 0x1df507afu, 0x5efee07bu,
                                            0xeed21b14u, 0x41442921u, 0x2d32f70au, 0x97900177u, 0x4acd918cu, 0x0f696ee0u};
@@ -128,11 +133,13 @@ GM_DEV uint8_t pt_g1_status(const G1Affine& P, bool check_curve) {
 }
 
 // ---- G2 ---------------------------------------------------------------------------------------------------------------------
-GM_DEV uint8_t pt_g2_status(const G2Affine& Q) {
-  Fq2 four_xi;  // 4 (1 + u)
-  four_xi.c0 = pt_four();
-  four_xi.c1 = four_xi.c0;
-  if (!fq2_is_zero(fq2_sub(fq2_sqr(Q.y), fq2_add(fq2_mul(fq2_sqr(Q.x), Q.x), four_xi)))) return GM_PT_NOT_ON_CURVE;
+GM_DEV uint8_t pt_g2_status(const G2Affine& Q, bool check_curve) {
+  if (check_curve) {
+    Fq2 four_xi;  // 4 (1 + u)
+    four_xi.c0 = pt_four();
+    four_xi.c1 = four_xi.c0;
+    if (!fq2_is_zero(fq2_sub(fq2_sqr(Q.y), fq2_add(fq2_mul(fq2_sqr(Q.x), Q.x), four_xi)))) return GM_PT_NOT_ON_CURVE;
+  }
   G2Xyzz T = G2Xyzz::from_affine(Q);
 #pragma unroll 1
   for (int bit = 62; bit >= 0; bit--) {
@@ -233,7 +240,7 @@ __global__ __launch_bounds__(PT_G2_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 
         Q.x.c1 = c[1];
         Q.y.c0 = c[2];
         Q.y.c1 = c[3];
-        st = pt_g2_status(Q);
+        st = pt_g2_status(Q, true);
       }
     }
   }
@@ -331,6 +338,208 @@ __global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))
   pt_report(i, n, st, status, summary);
 }
 
+// ---- G2 from bytes: a square root in Fq2 ---------------------------------------------------------------------------------------
+// a^((q - 3) / 4): bit i of the exponent is bit i + 2 of q - 3, which is q with its two low bits cleared -- pt_sqrt_candidate's loop
+// without the bit it sets at i = 2.  t = a^((q - 3) / 4) gives both a root candidate t a and its inverse +-t.
+GM_DEV FqE pt_pow_q3_4(const FqE& a) {
+  FqE acc = a;  // the top bit, 380
+#pragma unroll 1
+  for (int i = 379; i >= 2; i--) {
+    acc = fq_sqr(acc);
+    if ((FqParams::MOD[i >> 5] >> (i & 31)) & 1u) acc = fq_mul(acc, a);
+  }
+  return acc;
+}
+
+// A root of a = a0 + a1 u when a is a square of Fq2 = Fq[u] / (u^2 + 1); *is_square says whether it is.  The norm method
+// (gemini_amd/g2.py: f2_sqrt states it on integers): n = a0^2 + a1^2 is a square of Fq exactly when a is one of Fq2; with s^2 = n and
+// delta = (a0 + s) / 2, exactly one of delta and (a0 - s) / 2 is a square, their product being -(a1 / 2)^2.  t = delta^((q - 3) / 4),
+// w = t delta: w^2 = +-delta and 1 / w = +-t with the same sign, so the root is (w, a1 t / 2) or (-a1 t / 2, w).  a1 = 0 takes
+// delta = a0 and is always a square.  Two Fq exponentiations and no data-dependent third: 2 + (378 + 228) + 1 + 1 + (378 + 227) + 4 + 2
+// = 1221 Fq products (the last two are the square that decides the flag), against ~2 700 for two Fq2 exponentiations.
+GM_DEV Fq2 pt_fq2_sqrt(const Fq2& a, bool* is_square) {
+  const FqE half = pt_const(PT_HALF);
+  FqE delta = a.c0;
+  bool norm_ok = true;
+  if (!fq_is_zero(a.c1)) {
+    const FqE n = fq_add(fq_sqr(a.c0), fq_sqr(a.c1));
+    const FqE s = pt_sqrt_candidate(n);
+    norm_ok = fq_sqr(s) == n;
+    delta = fq_mul(fq_add(a.c0, s), half);
+  }
+  const FqE t = pt_pow_q3_4(delta);
+  const FqE w = fq_mul(t, delta);
+  const FqE h = fq_mul(fq_mul(a.c1, t), half);
+  Fq2 r;
+  if (fq_sqr(w) == delta) {
+    r.c0 = w;
+    r.c1 = h;
+  } else {
+    r.c0 = fq_neg_canonical(h);
+    r.c1 = w;
+  }
+  const Fq2 rr = fq2_sqr(r);
+  *is_square = norm_ok && rr.c0 == a.c0 && rr.c1 == a.c1;
+  return r;
+}
+
+// ark-ff's QuadExtField order on fully reduced integers: y > -y compares c1 first, c0 when c1 = 0 (c = -c only for c = 0)
+GM_DEV bool pt_y2_is_larger(const Fq& y0_int, const Fq& y1_int) { return y1_int.is_zero() ? pt_y_is_larger(y0_int) : pt_y_is_larger(y1_int); }
+
+// one 48-byte coordinate of either framing -> the integer it spells (flag bits still in place)
+GM_DEV Fq pt_load_coord(const uint8_t* p, int zcash) {
+  Fq v = fp_load<FqParams>(p);
+  if (zcash) {  // big-endian: limb k is word 11 - k, byte-swapped
+    const Fq t = v;
+#pragma unroll
+    for (int k = 0; k < 12; k++) v.l[k] = pt_bswap(t.l[11 - k]);
+  }
+  return v;
+}
+GM_DEV void pt_store_coord(uint8_t* p, const Fq& v, int zcash) {
+  Fq o = v;
+  if (zcash) {
+#pragma unroll
+    for (int k = 0; k < 12; k++) o.l[k] = pt_bswap(v.l[11 - k]);
+  }
+  fp_store<FqParams>(p, o);
+}
+
+// 96- / 192-byte encodings -> packed device records (192 bytes; the identity and every rejected point are the all-zero record).
+// Acceptance and the order of the checks are those of gemini_amd/g2.py: deserialize(.., strict = True, validate), the image of
+// k_g1_decode over Fq2.  On the wire enc 0 holds c0 | c1 and enc 1 c1 | c0; c[] below is x.c0, x.c1, y.c0, y.c1.
+__global__ __launch_bounds__(PT_G2_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_g2_decode(const uint8_t* __restrict__ bytes, size_t n, int compressed, int zcash, int validate,
+                                                                                                       uint8_t* __restrict__ dst, uint8_t* __restrict__ status, uint32_t* __restrict__ summary) {
+  const size_t i = (size_t)blockIdx.x * PT_G2_BLOCK + threadIdx.x;
+  uint8_t st = GM_PT_OK;
+  if (i < n) {
+    const int k = compressed ? 2 : 4;
+    const uint8_t* src = bytes + i * (size_t)(48 * k);
+    Fq c[4];
+#pragma unroll
+    for (int e = 0; e < 4; e++) c[e] = e < k ? pt_load_coord(src + 48 * (zcash ? e ^ 1 : e), zcash) : Fq::zero();
+    bool inf, larger;
+    if (zcash) {  // flags in the three top bits of the first byte = the top bits of x.c1
+      const uint32_t f = c[1].l[11] >> 29;
+      c[1].l[11] &= 0x1fffffffu;
+      inf = (f >> 1) & 1u;
+      larger = f & 1u;
+      if ((int)(f >> 2) != (compressed ? 1 : 0) || (larger && (!compressed || inf))) st = GM_PT_BAD_ENCODING;
+    } else {  // flags in the two top bits of the last byte = the top bits of the last coordinate's c1
+      const uint32_t f = (compressed ? c[1].l[11] : c[3].l[11]) >> 30;
+      if (compressed) c[1].l[11] &= 0x3fffffffu;
+      else c[3].l[11] &= 0x3fffffffu;
+      inf = f == 1;
+      larger = f == 2;
+      if (f == 3) st = GM_PT_BAD_ENCODING;
+    }
+    G2Affine P;
+    P.x = fq2_zero();
+    P.y = fq2_zero();
+    if (st == GM_PT_OK) {
+      const bool x_ge = pt_raw_ge_q(c[0]) || pt_raw_ge_q(c[1]);
+      if (inf) {
+        if (!c[0].is_zero() || !c[1].is_zero() || !c[2].is_zero() || !c[3].is_zero()) st = GM_PT_BAD_ENCODING;  // infinity with non-zero coordinates
+      } else if (compressed) {
+        if (x_ge) {
+          st = GM_PT_NONCANONICAL;
+        } else {
+          P.x.c0 = pt_from_int(c[0]);
+          P.x.c1 = pt_from_int(c[1]);
+          Fq2 rhs = fq2_mul(fq2_sqr(P.x), P.x);
+          rhs.c0 = fq_add(rhs.c0, pt_four());
+          rhs.c1 = fq_add(rhs.c1, pt_four());
+          bool square;
+          P.y = pt_fq2_sqrt(rhs, &square);
+          if (!square) {
+            st = GM_PT_NOT_ON_CURVE;  // x^3 + 4 (1 + u) is no square
+          } else {
+            if (pt_y2_is_larger(pt_to_int(P.y.c0), pt_to_int(P.y.c1)) != larger) P.y = fq2_neg_canonical(P.y);
+            if (validate) st = pt_g2_status(P, false);  // on the twist by construction
+          }
+        }
+      } else {
+        const bool y0_ge = pt_raw_ge_q(c[2]), y1_ge = pt_raw_ge_q(c[3]);
+        // g2.py compares the sign flag BEFORE the canonical check, against (-y) mod q: a component >= q is larger than its negative
+        const bool y_larger = y1_ge || (c[3].is_zero() ? (y0_ge || pt_y_is_larger(c[2])) : pt_y_is_larger(c[3]));
+        if (!zcash && y_larger != larger) {
+          st = GM_PT_BAD_ENCODING;
+        } else if (x_ge || y0_ge || y1_ge) {
+          st = GM_PT_NONCANONICAL;
+        } else {
+          P.x.c0 = pt_from_int(c[0]);
+          P.x.c1 = pt_from_int(c[1]);
+          P.y.c0 = pt_from_int(c[2]);
+          P.y.c1 = pt_from_int(c[3]);
+          if (validate) st = pt_g2_status(P, true);
+        }
+      }
+    }
+    if (st != GM_PT_OK) {
+      P.x = fq2_zero();
+      P.y = fq2_zero();
+    }
+    g2_store_affine(dst + i * G2_AFF_BYTES, P);
+  }
+  pt_report(i, n, st, status, summary);
+}
+
+// ---- resident records -> bytes: one Montgomery exit per coordinate and the y > -y compare, no inversion (the bases are affine) ------
+constexpr int PT_ENC_BLOCK = 256;
+__global__ __launch_bounds__(PT_ENC_BLOCK) void k_g1_encode(const uint8_t* __restrict__ src, size_t n, int compressed, int zcash, uint8_t* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * PT_ENC_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const G1Affine P = g1_load_affine(src + i * 96);
+  const bool inf = P.is_identity();
+  Fq x = pt_to_int(P.x), y = pt_to_int(P.y);  // 0 for the identity
+  const bool larger = !inf && pt_y_is_larger(y);
+  if (zcash) {
+    x.l[11] |= (compressed ? 0x80000000u : 0u) | (inf ? 0x40000000u : 0u) | (compressed && larger ? 0x20000000u : 0u);
+  } else {
+    const uint32_t f = (inf ? 0x40000000u : 0u) | (larger ? 0x80000000u : 0u);
+    if (compressed) x.l[11] |= f;
+    else y.l[11] |= f;
+  }
+  uint8_t* o = out + i * (size_t)(compressed ? 48 : 96);
+  pt_store_coord(o, x, zcash);
+  if (!compressed) pt_store_coord(o + 48, y, zcash);
+}
+__global__ __launch_bounds__(PT_ENC_BLOCK) void k_g2_encode(const uint8_t* __restrict__ src, size_t n, int compressed, int zcash, uint8_t* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * PT_ENC_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const G2Affine P = g2_load_affine(src + i * G2_AFF_BYTES);
+  const bool inf = P.is_identity();
+  Fq c[4] = {pt_to_int(P.x.c0), pt_to_int(P.x.c1), pt_to_int(P.y.c0), pt_to_int(P.y.c1)};
+  const bool larger = !inf && pt_y2_is_larger(c[2], c[3]);
+  if (zcash) {  // the first byte is the top of x.c1
+    c[1].l[11] |= (compressed ? 0x80000000u : 0u) | (inf ? 0x40000000u : 0u) | (compressed && larger ? 0x20000000u : 0u);
+  } else {  // the last byte is the top of the last coordinate's c1
+    const uint32_t f = (inf ? 0x40000000u : 0u) | (larger ? 0x80000000u : 0u);
+    if (compressed) c[1].l[11] |= f;
+    else c[3].l[11] |= f;
+  }
+  const int k = compressed ? 2 : 4;
+  uint8_t* o = out + i * (size_t)(48 * k);
+#pragma unroll
+  for (int e = 0; e < 4; e++)
+    if (e < k) pt_store_coord(o + 48 * (zcash ? e ^ 1 : e), c[e], zcash);
+}
+
+// gm_debug_fq2_sqrt: pt_fq2_sqrt on ark-ff Montgomery elements, one lane each
+__global__ __launch_bounds__(PT_G2_BLOCK) void k_fq2_sqrt(const uint8_t* __restrict__ src, size_t n, uint8_t* __restrict__ root, uint8_t* __restrict__ is_square) {
+  const size_t i = (size_t)blockIdx.x * PT_G2_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  Fq2 a = fq2_load(src + i * 96);
+  a.c0 = fqe_import(a.c0);
+  a.c1 = fqe_import(a.c1);
+  bool square;
+  Fq2 r = pt_fq2_sqrt(a, &square);
+  r.c0 = fqe_export(r.c0);
+  r.c1 = fqe_export(r.c1);
+  fq2_store(root + i * 96, r);
+  is_square[i] = square ? 1 : 0;
+}
+
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
@@ -409,6 +618,83 @@ int check_host(int group, const void* points, size_t stride, size_t n, uint8_t* 
   return check_run(C, group, static_cast<const uint8_t*>(stage.p), stride, 1, n, status_or_null, first_bad, ok);
 }
 
+// ---- the group elements of a proof: Jacobian, any representative -> host records for ONE check launch per group ----------------
+bool limbs_lt_q(const uint64_t* p) {
+  uint64_t t[6];
+  return gmh::sub_n<6>(t, p, gmh::FqP::MOD) != 0;
+}
+// a coordinate >= q has no value to normalise: its record gets all-ones limbs, which k_g1_check / k_g2_check report as NONCANONICAL
+void proof_g1_record(const uint64_t jac[18], uint64_t out[12]) {
+  for (int c = 0; c < 3; c++)
+    if (!limbs_lt_q(jac + 6 * c)) {
+      memset(out, 0xff, 96);
+      return;
+    }
+  memset(out, 0, 96);
+  const gmh::G1 a = gmh::G1::from_limbs(jac).normalized();
+  if (a.is_identity()) return;
+  a.x.to_limbs(out);
+  a.y.to_limbs(out + 6);
+}
+void proof_g2_record(const uint64_t jac[36], uint64_t out[24]) {
+  for (int c = 0; c < 6; c++)
+    if (!limbs_lt_q(jac + 6 * c)) {
+      memset(out, 0xff, 192);
+      return;
+    }
+  memset(out, 0, 192);
+  const gmh::G2 a = gmh::G2::from_limbs(jac).normalized();
+  if (a.is_identity()) return;
+  a.x.to_limbs(out);
+  a.y.to_limbs(out + 12);
+}
+// host records of both groups (either may be empty) -> the first bad index of each; one launch per non-empty group.  Caller holds the lock
+int check_records(Context* C, const std::vector<uint64_t>& r1, const std::vector<uint64_t>& r2, size_t* bad1, size_t* bad2, int* ok) {
+  const size_t n1 = r1.size() / 12, n2 = r2.size() / 24;
+  DevTmp stage;
+  if (n1 + n2) {
+    GM_HIP(dev_malloc(&stage.p, n1 * 96 + n2 * 192));
+    if (n1) GM_HIP(hipMemcpyAsync(stage.p, r1.data(), n1 * 96, hipMemcpyHostToDevice, C->stream));
+    if (n2) GM_HIP(hipMemcpyAsync(static_cast<uint8_t*>(stage.p) + n1 * 96, r2.data(), n2 * 192, hipMemcpyHostToDevice, C->stream));
+  }
+  int ok1 = 0, ok2 = 0;
+  int rc = check_run(C, 1, static_cast<const uint8_t*>(stage.p), 96, 1, n1, nullptr, bad1, &ok1);
+  if (!rc) rc = check_run(C, 2, static_cast<const uint8_t*>(stage.p) + n1 * 96, 192, 1, n2, nullptr, bad2, &ok2);
+  if (rc) return rc;
+  *ok = ok1 && ok2;
+  return GM_OK;
+}
+// the G1 elements of a proof, in the order the header lists them
+int proof_check(const std::vector<const uint64_t*>& g1, size_t* first_bad, int* ok) {
+  GM_CTX();
+  std::vector<uint64_t> r1(g1.size() * 12), none;
+  for (size_t i = 0; i < g1.size(); i++) proof_g1_record(g1[i], r1.data() + 12 * i);
+  GM_MSM_LOCK(C);
+  size_t b1 = 0, b2 = 0;
+  int rc = check_records(C, r1, none, &b1, &b2, ok);
+  if (rc) return rc;
+  if (first_bad) *first_bad = b1;
+  return GM_OK;
+}
+
+// bases[offset .. offset + n) of either group -> bytes on the host
+int encode_run(Context* C, int group, const uint8_t* d_src, size_t n, int compressed, int encoding, uint8_t* out) {
+  if (n == 0) return GM_OK;
+  const size_t sz = (group == 1 ? 48 : 96) * (compressed ? 1 : 2);
+  const size_t blocks = (n + PT_ENC_BLOCK - 1) / PT_ENC_BLOCK;
+  GM_CHECK(blocks <= 0x7fffffffu && n <= SIZE_MAX / sz, GM_EINVAL, "g%d_bases_to_bytes: %zu points in one call", group, n);
+  DevTmp tmp;
+  GM_HIP(dev_malloc(&tmp.p, n * sz));
+  if (group == 1)
+    hipLaunchKernelGGL(k_g1_encode, dim3((unsigned)blocks), dim3(PT_ENC_BLOCK), 0, C->stream, d_src, n, compressed ? 1 : 0, encoding, static_cast<uint8_t*>(tmp.p));
+  else
+    hipLaunchKernelGGL(k_g2_encode, dim3((unsigned)blocks), dim3(PT_ENC_BLOCK), 0, C->stream, d_src, n, compressed ? 1 : 0, encoding, static_cast<uint8_t*>(tmp.p));
+  GM_HIP(hipGetLastError());
+  GM_HIP(hipMemcpyAsync(out, tmp.p, n * sz, hipMemcpyDeviceToHost, C->stream));
+  GM_HIP(hipStreamSynchronize(C->stream));
+  return GM_OK;
+}
+
 }  // namespace
 }  // namespace gm
 
@@ -481,6 +767,185 @@ int gm_g1_bases_from_bytes(const uint8_t* bytes, size_t n, int compressed, int e
   }
   *handle = put_bases(std::move(b));  // as gm_g1_bases_register: no tables here, gm_g1_bases_precompute(handle, -1) builds them
   *ok = 1;
+  return GM_OK;
+}
+
+int gm_g2_bases_from_bytes(const uint8_t* bytes, size_t n, int compressed, int encoding, int validate, uint64_t* handle, uint8_t* status_or_null, size_t* first_bad,
+                           int* ok) {
+  if (ok) *ok = 0;
+  if (handle) *handle = 0;
+  GM_CTX();
+  GM_CHECK(handle != nullptr && ok != nullptr && (bytes != nullptr || n == 0), GM_EINVAL, "g2_bases_from_bytes: null pointer");
+  GM_CHECK(encoding == 0 || encoding == 1, GM_EINVAL, "g2_bases_from_bytes: encoding %d (0 arkworks, 1 zcash)", encoding);
+  GM_CHECK(n <= SIZE_MAX / G2_AFF_BYTES, GM_EINVAL, "g2_bases_from_bytes: %zu points do not fit a size_t", n);
+  auto b = std::make_unique<G2Bases>();
+  b->n = n;
+  int rc = GM_OK;
+  if (first_bad) *first_bad = 0;
+  if (n) {
+    GM_MSM_LOCK(C);
+    const size_t sz = compressed ? 96 : 192;
+    DevTmp stage, out;
+    Report rep;
+    if ((rc = rep.alloc(n, PT_G2_BLOCK))) return rc;
+    GM_HIP(dev_malloc(&stage.p, n * sz));
+    GM_HIP(dev_malloc(&out.p, n * G2_AFF_BYTES));
+    GM_HIP(hipMemcpyAsync(stage.p, bytes, n * sz, hipMemcpyHostToDevice, C->stream));
+    hipLaunchKernelGGL(k_g2_decode, dim3((unsigned)rep.blocks), dim3(PT_G2_BLOCK), 0, C->stream, static_cast<const uint8_t*>(stage.p), n, compressed ? 1 : 0, encoding,
+                       validate ? 1 : 0, static_cast<uint8_t*>(out.p), rep.status(), rep.summary());
+    if ((rc = rep.read(C, status_or_null, first_bad, ok))) return rc;
+    if (!*ok) return GM_OK;  // a bad point is a result: nothing stays registered
+    b->d = static_cast<uint8_t*>(out.p);
+    out.p = nullptr;
+  }
+  *handle = put_in(C, C->g2_bases, std::move(b));
+  *ok = 1;
+  return GM_OK;
+}
+
+// A cyclic share (gm_g1_bases_set_cyclic) is encoded as it is held: the n points of the share, not the key they were cut from.
+int gm_g1_bases_to_bytes(uint64_t handle, size_t offset, size_t n, int compressed, int encoding, uint8_t* out, size_t cap) {
+  GM_CTX();
+  Bases* b = find_bases(handle);
+  GM_CHECK(b != nullptr, GM_EHANDLE, "g1_bases_to_bytes: unknown handle %llu", (unsigned long long)handle);
+  GM_CHECK(out != nullptr || n == 0, GM_EINVAL, "g1_bases_to_bytes: null pointer");
+  GM_CHECK(encoding == 0 || encoding == 1, GM_EINVAL, "g1_bases_to_bytes: encoding %d (0 arkworks, 1 zcash)", encoding);
+  GM_CHECK(offset <= b->n && n <= b->n - offset, GM_EINVAL, "g1_bases_to_bytes: range [%zu, %zu) outside %zu bases", offset, offset + n, b->n);
+  GM_CHECK(cap / (compressed ? 48 : 96) >= n, GM_EINVAL, "g1_bases_to_bytes: %zu bytes do not hold %zu points", cap, n);
+  GM_MSM_LOCK(C);
+  return encode_run(C, 1, b->d + offset * 96, n, compressed, encoding, out);
+}
+int gm_g2_bases_to_bytes(uint64_t handle, size_t offset, size_t n, int compressed, int encoding, uint8_t* out, size_t cap) {
+  GM_CTX();
+  G2Bases* b = find_in(C, C->g2_bases, handle);
+  GM_CHECK(b != nullptr, GM_EHANDLE, "g2_bases_to_bytes: unknown G2 bases handle %llu", (unsigned long long)handle);
+  GM_CHECK(out != nullptr || n == 0, GM_EINVAL, "g2_bases_to_bytes: null pointer");
+  GM_CHECK(encoding == 0 || encoding == 1, GM_EINVAL, "g2_bases_to_bytes: encoding %d (0 arkworks, 1 zcash)", encoding);
+  GM_CHECK(offset <= b->n && n <= b->n - offset, GM_EINVAL, "g2_bases_to_bytes: range [%zu, %zu) outside %zu bases", offset, offset + n, b->n);
+  GM_CHECK(cap / (compressed ? 96 : 192) >= n, GM_EINVAL, "g2_bases_to_bytes: %zu bytes do not hold %zu points", cap, n);
+  GM_MSM_LOCK(C);
+  return encode_run(C, 2, b->d + offset * G2_AFF_BYTES, n, compressed, encoding, out);
+}
+
+int gm_crs_from_bases(uint64_t g1_handle, uint64_t g2_handle, uint64_t* crs) {
+  if (crs) *crs = 0;
+  GM_CTX();
+  Bases* b1 = find_bases(g1_handle);
+  GM_CHECK(b1 != nullptr, GM_EHANDLE, "crs_from_bases: unknown handle %llu", (unsigned long long)g1_handle);
+  G2Bases* b2 = find_in(C, C->g2_bases, g2_handle);
+  GM_CHECK(b2 != nullptr, GM_EHANDLE, "crs_from_bases: unknown G2 bases handle %llu", (unsigned long long)g2_handle);
+  GM_CHECK(crs != nullptr, GM_EINVAL, "crs_from_bases: null pointer");
+  GM_CHECK(b1->n >= 1 && b2->n >= 1, GM_EINVAL, "crs_from_bases: empty CRS");
+  GM_MSM_LOCK(C);
+  DevTmp d1, d2;
+  GM_HIP(dev_malloc(&d1.p, b1->n * 96));
+  GM_HIP(dev_malloc(&d2.p, b2->n * G2_AFF_BYTES));
+  GM_HIP(hipMemcpyAsync(d1.p, b1->d, b1->n * 96, hipMemcpyDeviceToDevice, C->stream));
+  GM_HIP(hipMemcpyAsync(d2.p, b2->d, b2->n * G2_AFF_BYTES, hipMemcpyDeviceToDevice, C->stream));
+  GM_HIP(hipStreamSynchronize(C->stream));
+  auto c = std::make_unique<Crs>();
+  c->g1 = static_cast<uint8_t*>(d1.p);
+  c->n1 = b1->n;
+  c->g2 = static_cast<uint8_t*>(d2.p);
+  c->n2 = b2->n;
+  d1.p = d2.p = nullptr;
+  *crs = put_in(C, C->crs, std::move(c));
+  return GM_OK;
+}
+
+int gm_crs_check(uint64_t crs, size_t* first_bad_g1, size_t* first_bad_g2, int* ok) {
+  if (ok) *ok = 0;
+  GM_CTX();
+  Crs* c = find_in(C, C->crs, crs);
+  GM_CHECK(c != nullptr, GM_EHANDLE, "crs_check: unknown CRS handle %llu", (unsigned long long)crs);
+  GM_CHECK(ok != nullptr, GM_EINVAL, "crs_check: null pointer");
+  GM_MSM_LOCK(C);
+  int ok1 = 0, ok2 = 0;
+  int rc = check_run(C, 1, c->g1, 96, 0, c->n1, nullptr, first_bad_g1, &ok1);
+  if (!rc) rc = check_run(C, 2, c->g2, G2_AFF_BYTES, 0, c->n2, nullptr, first_bad_g2, &ok2);
+  if (rc) return rc;
+  *ok = ok1 && ok2;
+  return GM_OK;
+}
+
+int gm_vk_check(uint64_t vk, size_t* first_bad_g1, size_t* first_bad_g2, int* ok) {
+  if (ok) *ok = 0;
+  GM_CTX();
+  VerifierKey* K = find_in(C, C->vks, vk);
+  GM_CHECK(K != nullptr, GM_EHANDLE, "vk_check: unknown verifier key handle %llu", (unsigned long long)vk);
+  GM_CHECK(ok != nullptr, GM_EINVAL, "vk_check: null pointer");
+  GM_MSM_LOCK(C);
+  size_t b1 = 0, b2 = 0;
+  int rc = check_records(C, K->g1, K->g2, &b1, &b2, ok);
+  if (rc) return rc;
+  if (first_bad_g1) *first_bad_g1 = b1;
+  if (first_bad_g2) *first_bad_g2 = b2;
+  return GM_OK;
+}
+
+int gm_snark_proof_check(const gm_snark_proof* proof, size_t* first_bad, int* ok) {
+  if (ok) *ok = 0;
+  GM_CHECK(proof != nullptr && ok != nullptr && (proof->fold_commitments != nullptr || proof->nfold == 0), GM_EINVAL, "snark_proof_check: null pointer");
+  std::vector<const uint64_t*> g1{proof->witness_commitment};
+  for (size_t i = 0; i < proof->nfold; i++) g1.push_back(proof->fold_commitments + 18 * i);
+  g1.push_back(proof->evaluation_proof);
+  return proof_check(g1, first_bad, ok);
+}
+
+int gm_psnark_proof_check(const gm_psnark_proof* proof, size_t* first_bad, int* ok) {
+  if (ok) *ok = 0;
+  GM_CHECK(proof != nullptr && ok != nullptr && (proof->fold_commitments != nullptr || proof->nfold == 0), GM_EINVAL, "psnark_proof_check: null pointer");
+  std::vector<const uint64_t*> g1{proof->witness_commitment};
+  for (int i = 0; i < 3; i++) g1.push_back(proof->r_star_commitments[i]);
+  g1.push_back(proof->z_star_commitment);
+  for (int i = 0; i < 3; i++) g1.push_back(proof->sorted_commitments[i]);
+  for (int i = 0; i < 9; i++) g1.push_back(proof->acc_v_commitments[i]);
+  g1.push_back(proof->ralpha_star_acc_mu_proof);
+  for (size_t i = 0; i < proof->nfold; i++) g1.push_back(proof->fold_commitments + 18 * i);
+  g1.push_back(proof->evaluation_proof);
+  return proof_check(g1, first_bad, ok);
+}
+
+int gm_ipa_check(uint64_t proof, size_t* first_bad, int* ok) {
+  if (ok) *ok = 0;
+  GM_CTX();
+  IpaProof* p = find_in(C, C->ipa, proof);
+  GM_CHECK(p != nullptr, GM_EHANDLE, "ipa_check: unknown proof handle %llu", (unsigned long long)proof);
+  GM_CHECK(ok != nullptr, GM_EINVAL, "ipa_check: null pointer");
+  const size_t k = p->final_g1.size() / 18;
+  GM_CHECK(p->final_g2.size() == k * 36, GM_EINVAL, "ipa_check: %zu Lhs final foldings and %zu Rhs ones", k, p->final_g2.size() / 36);
+  std::vector<uint64_t> r1((1 + k) * 12), r2((1 + k) * 24);
+  proof_g1_record(p->foldings_fg1, r1.data());
+  proof_g2_record(p->foldings_fg2 + 4, r2.data());
+  for (size_t i = 0; i < k; i++) {
+    proof_g1_record(p->final_g1.data() + 18 * i, r1.data() + 12 * (1 + i));
+    proof_g2_record(p->final_g2.data() + 36 * i, r2.data() + 24 * (1 + i));
+  }
+  GM_MSM_LOCK(C);
+  size_t b1 = 0, b2 = 0;
+  int rc = check_records(C, r1, r2, &b1, &b2, ok);
+  if (rc) return rc;
+  if (first_bad) *first_bad = b1 <= k ? b1 : 1 + k + b2;  // the G1 elements come first
+  return GM_OK;
+}
+
+int gm_debug_fq2_sqrt(const uint64_t* a_mont, size_t n, uint64_t* root_mont, uint8_t* is_square) {
+  GM_CTX();
+  GM_CHECK((a_mont && root_mont && is_square) || n == 0, GM_EINVAL, "debug_fq2_sqrt: null pointer");
+  GM_CHECK(n <= (size_t)1 << 30, GM_EINVAL, "debug_fq2_sqrt: %zu elements in one call", n);
+  if (n == 0) return GM_OK;
+  GM_MSM_LOCK(C);
+  DevTmp in, out;
+  GM_HIP(dev_malloc(&in.p, n * 96));
+  GM_HIP(dev_malloc(&out.p, n * 96 + n));
+  GM_HIP(hipMemcpyAsync(in.p, a_mont, n * 96, hipMemcpyHostToDevice, C->stream));
+  uint8_t* d_out = static_cast<uint8_t*>(out.p);
+  hipLaunchKernelGGL(k_fq2_sqrt, dim3((unsigned)((n + PT_G2_BLOCK - 1) / PT_G2_BLOCK)), dim3(PT_G2_BLOCK), 0, C->stream, static_cast<const uint8_t*>(in.p), n, d_out,
+                     d_out + n * 96);
+  GM_HIP(hipGetLastError());
+  GM_HIP(hipMemcpyAsync(root_mont, d_out, n * 96, hipMemcpyDeviceToHost, C->stream));
+  GM_HIP(hipMemcpyAsync(is_square, d_out + n * 96, n, hipMemcpyDeviceToHost, C->stream));
+  GM_HIP(hipStreamSynchronize(C->stream));
   return GM_OK;
 }
 

@@ -156,3 +156,134 @@ def deserialize_uncompressed(b: bytes, enc: int = 0):
 def serialize_vec_uncompressed(points, enc: int | None = None) -> bytes:
     """Vec<G2Affine>: u64 length + items"""
     return len(points).to_bytes(8, "little") + b"".join(serialize_uncompressed(p, enc) for p in points)
+
+
+# ---- the canonical encodings, both framings and both modes ---------------------------------------------------------------------
+# The image of wire.g1_serialize / wire.g1_deserialize over Fq2: the same flag rules and the same ORDER of rejections.  This is the
+# definition k_g2_decode / k_g2_encode (gemini_amd/csrc/points.hip) follow point for point; a rejected encoding raises a WireError
+# whose `status` is the GM_PT_* value the device reports for it.
+PT_BAD_ENCODING, PT_NONCANONICAL, PT_NOT_ON_CURVE, PT_NOT_IN_SUBGROUP = 1, 2, 3, 4
+
+
+def _reject(status: int, what: str):
+    from .wire import WireError
+
+    e = WireError(what)
+    e.status = status
+    return e
+
+
+def g2_size(compress: bool) -> int:
+    return 96 if compress else 192
+
+
+def fq_sqrt(a: int):
+    """q = 3 mod 4"""
+    s = pow(a, (Q + 1) // 4, Q)
+    return s if s * s % Q == a % Q else None
+
+
+def f2_sqrt(a):
+    """A square root of a = a0 + a1 u or None, by the norm method pt_fq2_sqrt runs: two Fq exponentiations, no inversion.
+    n = a0^2 + a1^2 is a square of Fq exactly when a is one of Fq2; with s^2 = n and delta = (a0 + s) / 2, the product of delta and
+    (a0 - s) / 2 is -(a1 / 2)^2, a non-residue, so exactly one of them is a square.  t = delta^((q - 3) / 4), w = t delta:
+    w^2 = +-delta and t w = +-1 with the same sign, which gives 1 / w = +-t.  a1 = 0 takes delta = a0."""
+    a0, a1 = a[0] % Q, a[1] % Q
+    if a1:
+        n = (a0 * a0 + a1 * a1) % Q
+        s = pow(n, (Q + 1) // 4, Q)
+        if s * s % Q != n:
+            return None
+        delta = (a0 + s) * pow(2, -1, Q) % Q
+    else:
+        delta = a0
+    t = pow(delta, (Q - 3) // 4, Q)
+    w = t * delta % Q
+    h = a1 * t * pow(2, -1, Q) % Q
+    r = (w, h) if w * w % Q == delta else ((-h) % Q, w)
+    assert f2_mul(r, r) == (a0, a1)
+    return r
+
+
+def in_prime_order_subgroup(p) -> bool:
+    """[r] P == O by the ladder (`mul` reduces its scalar mod r and cannot tell)"""
+    acc = (ONE2, ONE2, ZERO2)
+    for bit in bin(R_ORDER)[2:]:
+        acc = _jdbl(acc)
+        if bit == "1":
+            acc = _jadd_affine(acc, p)
+    return acc[2] == ZERO2
+
+
+def serialize_compressed(p, enc: int | None = None) -> bytes:
+    """Compress::Yes: x alone, the sign of y in a flag.  enc 0: x.c0 | x.c1 little-endian, bit 7 of the last byte = y > -y, bit 6 =
+    infinity.  enc 1: x.c1 | x.c0 big-endian, bit 7 of the first byte set (compressed), bit 6 = infinity, bit 5 = y > -y."""
+    if enc is None:
+        from .transcript import default_group_encoding
+
+        enc = default_group_encoding()
+    if enc == 1:
+        if p is None:
+            return bytes([0xC0]) + bytes(95)
+        x, y = p
+        out = bytearray(x[1].to_bytes(48, "big") + x[0].to_bytes(48, "big"))
+        out[0] |= 0x80 | (0x20 if _f2_gt(y, f2_neg(y)) else 0)
+        return bytes(out)
+    if p is None:
+        return bytes(95) + bytes([0x40])
+    x, y = p
+    out = bytearray(x[0].to_bytes(48, "little") + x[1].to_bytes(48, "little"))
+    if _f2_gt(y, f2_neg(y)):
+        out[-1] |= 0x80
+    return bytes(out)
+
+
+def deserialize(buf: bytes, pos: int, compress: bool, enc: int = 0, validate: bool = True, strict: bool = True):
+    """One G2 point at buf[pos:] -> (affine point or None, the next position).  strict / validate as wire.g1_deserialize: strict
+    accepts the canonical encoding only; validate adds the curve equation (uncompressed points) and the subgroup ladder."""
+    n = g2_size(compress)
+    if pos + n > len(buf):
+        raise _reject(PT_BAD_ENCODING, "not enough bytes for a G2 point")
+    raw = bytearray(buf[pos: pos + n])
+    k = n // 48
+    if enc == 0:
+        flags = raw[n - 1] >> 6
+        raw[n - 1] &= 0x3F
+        if flags == 3:
+            raise _reject(PT_BAD_ENCODING, "G2 flags: infinity together with the y sign")
+        inf, larger = flags == 1, flags == 2
+        c = [int.from_bytes(raw[48 * i: 48 * i + 48], "little") for i in range(k)]
+    else:
+        if bool(raw[0] >> 7) != compress:
+            raise _reject(PT_BAD_ENCODING, "G2 compression flag does not match the requested mode")
+        inf, larger = bool((raw[0] >> 6) & 1), bool((raw[0] >> 5) & 1)
+        if larger and (not compress or inf):
+            raise _reject(PT_BAD_ENCODING, "G2 flags: unexpected sort flag")
+        raw[0] &= 0x1F
+        c = [int.from_bytes(raw[48 * i: 48 * i + 48], "big") for i in range(k)]
+        c = [c[i ^ 1] for i in range(k)]  # c1 comes first on this wire
+    if inf:
+        if strict and any(c):
+            raise _reject(PT_BAD_ENCODING, "G2 point at infinity with non-zero coordinates")
+        return None, pos + n
+    x = (c[0], c[1])
+    if compress:
+        if x[0] >= Q or x[1] >= Q:
+            raise _reject(PT_NONCANONICAL, "G2 coordinate is not a canonical field element")
+        y = f2_sqrt(f2_add(f2_mul(f2_mul(x, x), x), (4, 4)))
+        if y is None:
+            raise _reject(PT_NOT_ON_CURVE, "G2 x coordinate is not on the curve")
+        if _f2_gt(y, f2_neg(y)) != larger:
+            y = f2_neg(y)
+    else:
+        y = (c[2], c[3])
+        if enc == 0 and strict and _f2_gt(y, f2_neg(y)) != larger:  # before the canonical test, as for G1
+            raise _reject(PT_BAD_ENCODING, "G2 y-sign flag does not match y")
+        if max(c) >= Q:
+            raise _reject(PT_NONCANONICAL, "G2 coordinate is not a canonical field element")
+    if validate:
+        if not on_curve((x, y)):
+            raise _reject(PT_NOT_ON_CURVE, "G2 point is not on the curve")
+        if not in_prime_order_subgroup((x, y)):
+            raise _reject(PT_NOT_IN_SUBGROUP, "G2 point is not in the prime-order subgroup")
+    return (x, y), pos + n

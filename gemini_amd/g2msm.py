@@ -145,6 +145,19 @@ class G2Bases:
 
         return check_g2_bases(self, offset, n)
 
+    @classmethod
+    def from_bytes(cls, data: bytes, n: int, compress: bool, enc: int = 0, validate: bool = True):
+        """gm_g2_bases_from_bytes -> (G2Bases or None, points.CheckResult); the definition is g2.deserialize(strict=True)"""
+        from .points import g2_bases_from_bytes
+
+        return g2_bases_from_bytes(data, n, compress, enc, validate)
+
+    def to_bytes(self, compress: bool, enc: int = 0, offset: int = 0, n: int | None = None) -> bytes:
+        """the canonical encodings of the resident points, n x 96 / 192 bytes (gm_g2_bases_to_bytes)"""
+        from .points import g2_bases_to_bytes
+
+        return g2_bases_to_bytes(self, compress, enc, offset, n)
+
     def free(self):
         if self.handle:
             capi.check(capi.load().gm_g2_bases_free(C.c_uint64(self.handle)))

@@ -32,6 +32,41 @@ class Crs:
         self.handle = h.value
         self.n1, self.n2 = len(g1), len(g2)
 
+    @classmethod
+    def from_bases(cls, g1, g2) -> "Crs":
+        """gm_crs_from_bases: a CRS from two registered handles (G1Bases, G2Bases) by device-to-device copy; the handles stay the caller's"""
+        h = C.c_uint64()
+        capi.check(capi.load().gm_crs_from_bases(C.c_uint64(g1.handle), C.c_uint64(g2.handle), C.byref(h)))
+        crs = cls.__new__(cls)
+        crs.handle, crs.n1, crs.n2 = h.value, len(g1), len(g2)
+        return crs
+
+    @classmethod
+    def from_bytes(cls, g1_bytes: bytes, n1: int, g2_bytes: bytes, n2: int, compress: bool, enc: int = 0, validate: bool = True):
+        """A CRS that arrives as bytes, decoded (and with `validate` checked) on the device without visiting the host as points.
+        -> (Crs or None, the points.CheckResult of the G1 half, that of the G2 half or None when the G1 half was rejected)"""
+        from .points import g1_bases_from_bytes, g2_bases_from_bytes
+
+        b1, r1 = g1_bases_from_bytes(g1_bytes, n1, compress, enc, validate)
+        if b1 is None:
+            return None, r1, None
+        try:
+            b2, r2 = g2_bases_from_bytes(g2_bytes, n2, compress, enc, validate)
+            if b2 is None:
+                return None, r1, r2
+            try:
+                return cls.from_bases(b1, b2), r1, r2
+            finally:
+                b2.free()
+        finally:
+            b1.free()
+
+    def check(self):
+        """gm_crs_check: curve and subgroup over both arrays; a points.KeyCheckResult"""
+        from .points import check_crs
+
+        return check_crs(self)
+
     def commit_g1(self, scalars_mont) -> np.ndarray:
         """Crs::commit_g1: the CRS must be longer than the scalars"""
         sc = capi.u64(scalars_mont).reshape(-1, 4)
@@ -145,6 +180,13 @@ class InnerProductProof:
         capi.check(capi.load().gm_ipa_verify(C.c_uint64(self.handle), C.c_uint64(vrs.handle), capi.ptr(capi.u64(comm_a).reshape(18)),
                                              capi.ptr(capi.u64(comm_b).reshape(36)), capi.ptr(capi.u64(y_mont).reshape(4)), C.byref(ok)))
         return bool(ok.value)
+
+    def check_points(self):
+        """gm_ipa_check: every G1 and G2 element verify_transcript reads from the proof (the G1 ones first); a points.ProofCheckResult.
+        The GT elements of the messages are NOT checked for membership."""
+        from .points import check_proof
+
+        return check_proof(capi.load().gm_ipa_check, C.c_uint64(self.handle))
 
     def host_times(self) -> dict:
         """what gm_ipa_new spent on the host making this proof, ms (a measurement aid: tools/ipa_bench.py)"""

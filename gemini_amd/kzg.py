@@ -93,6 +93,10 @@ class CommitterKey:
             return False
         return check_powers(self.powers_of_g, g2s[0], g2s[1], rho)
 
+    def to_bytes(self, compress: bool = True, enc: int = 0) -> bytes:
+        """powers_of_g as n x 48 / 96 bytes, encoded on the device: what G1Bases / CommitterKey from_bytes read back"""
+        return self.powers_of_g.to_bytes(compress, enc)
+
     def num_powers(self) -> int:
         """len(powers_of_g) of the whole key (a sharded key holds only a slice of it)"""
         return len(self.powers_of_g)
@@ -184,6 +188,13 @@ class VerifierKey:
 
     def __init__(self, handle: int):
         self.handle = handle
+
+    def check(self):
+        """gm_vk_check: every power of both halves canonical, on its curve and in its subgroup; a points.KeyCheckResult.  Run it on a
+        key from elsewhere BEFORE verify: the verifiers take their points on trust."""
+        from .points import check_vk
+
+        return check_vk(self)
 
     @classmethod
     def from_powers(cls, powers_of_g: np.ndarray, powers_of_g2: np.ndarray) -> "VerifierKey":

@@ -137,6 +137,12 @@ class G1Bases:
 
         return check_g1_bases(self, offset, n)
 
+    def to_bytes(self, compress: bool, enc: int = 0, offset: int = 0, n: int | None = None) -> bytes:
+        """the canonical encodings of the resident points, n x 48 / 96 bytes (gm_g1_bases_to_bytes); a cyclic share is encoded as held"""
+        from .points import g1_bases_to_bytes
+
+        return g1_bases_to_bytes(self, compress, enc, offset, n)
+
     def free(self):
         if self.handle:
             capi.check(capi.load().gm_g1_bases_free(C.c_uint64(self.handle)))

@@ -1,5 +1,6 @@
 """Host mirror of the point-validation block of include/gemini_hip.h (gemini_amd/csrc/points.hip): untrusted G1 / G2 points and a
-committer key checked -- and G1 byte encodings decoded -- on the device.
+committer key checked, G1 and G2 byte encodings decoded and resident keys encoded on the device, and the check entries of what a
+verifier consumes (a CRS, a verifier key, the group elements of a proof).
 
 What `CanonicalDeserialize::deserialize_with_mode(.., Validate::Yes)` of ark-ec does per point, for whole keys: gemini_amd/wire.py
 states the same on Python integers, one point at a time, which suits the O(log n) points of a proof and not a 2^26-point key.
@@ -130,3 +131,90 @@ def check_powers(bases: G1Bases, g2, tau_g2, rho=None, offset: int = 0, n: int |
     capi.check(capi.load().gm_g1_powers_check(C.c_uint64(bases.handle), C.c_size_t(offset), C.c_size_t(n), capi.ptr(_g2_record(g2)), capi.ptr(_g2_record(tau_g2)),
                                               capi.ptr(fr_from_int(int(rho) % R_MOD)), C.byref(ok)))
     return bool(ok.value)
+
+
+# ---- G2 keys from bytes, keys back to bytes, and the checks of what a verifier consumes ----------------------------------------------
+def g2_bases_from_bytes(data: bytes, n: int, compress: bool, enc: int = 0, validate: bool = True):
+    """gm_g2_bases_from_bytes: n points of 96 (compress) or 192 bytes, decoded -- and with `validate` checked -- on the device.
+    Returns (G2Bases or None, CheckResult): acceptance is that of g2.deserialize(strict=True, validate=validate) point for point."""
+    capi.ensure_init()
+    size = 96 if compress else 192
+    assert len(data) == n * size, f"{len(data)} bytes for {n} points of {size}"
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    status = np.zeros(n, dtype=np.uint8)
+    h, first_bad, ok = C.c_uint64(0), C.c_size_t(0), C.c_int(0)
+    capi.check(capi.load().gm_g2_bases_from_bytes(capi.ptr(buf), C.c_size_t(n), C.c_int(int(bool(compress))), C.c_int(int(enc)), C.c_int(int(bool(validate))),
+                                                  C.byref(h), capi.ptr(status), C.byref(first_bad), C.byref(ok)))
+    res = CheckResult(bool(ok.value), first_bad.value, status)
+    assert (h.value != 0) == res.ok, "gm_g2_bases_from_bytes: a handle exactly when every point was accepted"
+    return (G2Bases(h.value, n) if res.ok else None), res
+
+
+def _to_bytes(fn, handle: int, size: int, compress: bool, offset: int, n: int, enc: int) -> bytes:
+    out = np.zeros(n * size, dtype=np.uint8)
+    capi.check(fn(C.c_uint64(handle), C.c_size_t(offset), C.c_size_t(n), C.c_int(int(bool(compress))), C.c_int(int(enc)), capi.ptr(out) if n else None,
+                  C.c_size_t(len(out))))
+    return out.tobytes()
+
+
+def g1_bases_to_bytes(bases: G1Bases, compress: bool, enc: int = 0, offset: int = 0, n: int | None = None) -> bytes:
+    """gm_g1_bases_to_bytes: bases[offset : offset + n] as n x 48 / 96 bytes, what wire.g1_serialize writes point by point"""
+    n = len(bases) - offset if n is None else n
+    return _to_bytes(capi.load().gm_g1_bases_to_bytes, bases.handle, 48 if compress else 96, compress, offset, n, enc)
+
+
+def g2_bases_to_bytes(bases: G2Bases, compress: bool, enc: int = 0, offset: int = 0, n: int | None = None) -> bytes:
+    """gm_g2_bases_to_bytes: n x 96 / 192 bytes, what g2.serialize_compressed / serialize_uncompressed write point by point"""
+    n = len(bases) - offset if n is None else n
+    return _to_bytes(capi.load().gm_g2_bases_to_bytes, bases.handle, 96 if compress else 192, compress, offset, n, enc)
+
+
+@dataclasses.dataclass
+class KeyCheckResult:
+    ok: bool
+    first_bad_g1: int       # the smallest bad index of each group; its length when every point passes
+    first_bad_g2: int
+
+    def __bool__(self):
+        return self.ok
+
+
+def _key_check(fn, handle: int) -> KeyCheckResult:
+    b1, b2, ok = C.c_size_t(0), C.c_size_t(0), C.c_int(0)
+    capi.check(fn(C.c_uint64(handle), C.byref(b1), C.byref(b2), C.byref(ok)))
+    return KeyCheckResult(bool(ok.value), b1.value, b2.value)
+
+
+def check_crs(crs) -> KeyCheckResult:
+    """gm_crs_check: curve and subgroup over both arrays of an ipa.Crs"""
+    return _key_check(capi.load().gm_crs_check, crs.handle)
+
+
+def check_vk(vk) -> KeyCheckResult:
+    """gm_vk_check: canonical limbs, curve and subgroup over both arrays of a kzg.VerifierKey"""
+    return _key_check(capi.load().gm_vk_check, vk.handle)
+
+
+@dataclasses.dataclass
+class ProofCheckResult:
+    ok: bool
+    first_bad: int          # in the order include/gemini_hip.h lists the elements; their number when every one passes
+
+    def __bool__(self):
+        return self.ok
+
+
+def check_proof(fn, proof_arg) -> ProofCheckResult:
+    """gm_snark_proof_check / gm_psnark_proof_check (a byref to the packed record) / gm_ipa_check (the handle)"""
+    fb, ok = C.c_size_t(0), C.c_int(0)
+    capi.check(fn(proof_arg, C.byref(fb), C.byref(ok)))
+    return ProofCheckResult(bool(ok.value), fb.value)
+
+
+def debug_fq2_sqrt(a_mont):
+    """gm_debug_fq2_sqrt: (n, 12) ark-ff Montgomery limbs (c0 | c1) -> (roots (n, 12), is_square (n,) uint8)"""
+    capi.ensure_init()
+    a = capi.u64(a_mont).reshape(-1, 12)
+    root, sq = np.zeros_like(a), np.zeros(len(a), dtype=np.uint8)
+    capi.check(capi.load().gm_debug_fq2_sqrt(capi.ptr(a), C.c_size_t(len(a)), capi.ptr(root), capi.ptr(sq)))
+    return root, sq

@@ -263,6 +263,18 @@ class Proof:
         if not ok.value:
             raise VerificationError("psnark: rejected")
 
+    def check_points(self):
+        """gm_psnark_proof_check: every G1 element the verifier reads is canonical, on the curve and in G1; a points.ProofCheckResult
+        (the order of first_bad: include/gemini_hip.h).  verify() does not call it."""
+        import ctypes as C
+
+        from . import capi
+        from .points import check_proof
+
+        capi.ensure_init()
+        P, keep = _pack_proof(self)
+        return check_proof(capi.load().gm_psnark_proof_check, C.byref(P))
+
     def serialize(self, compress: bool = True, enc=0) -> bytes:
         """derive(CanonicalSerialize) of src/psnark/mod.rs:29-51 (formats: gemini_amd/wire.py)"""
         from . import wire

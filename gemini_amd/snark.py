@@ -178,7 +178,21 @@ def _proof_verify(self, r1cs: R1cs, vk) -> None:
         raise VerificationError("snark: rejected")
 
 
+def _proof_check_points(self):
+    """gm_snark_proof_check: every G1 element the verifier reads is canonical, on the curve and in G1; a points.ProofCheckResult whose
+    first_bad counts witness_commitment, the folded commitments, evaluation_proof.  verify() does not call it."""
+    import ctypes as C
+
+    from . import capi
+    from .points import check_proof
+
+    capi.ensure_init()
+    P, keep = _pack_native(self)
+    return check_proof(capi.load().gm_snark_proof_check, C.byref(P))
+
+
 Proof.verify = _proof_verify
+Proof.check_points = _proof_check_points
 
 
 # ---- CanonicalSerialize of the proof (src/snark/mod.rs:75-82): gemini_amd/wire.py holds the formats ------------

@@ -808,7 +808,7 @@ int gm_psnark_index(const gm_psnark_instance* instance, uint64_t ck_bases, uint6
  * is a result (return value GM_OK), negative codes are for misuse only.  The transcripts are replayed with the framings of the
  * transcript block (NOT PINNED, README).  OUT OF SCOPE: subgroup and on-curve checks of proof elements (the reference makes none) --
  * the verifiers do NOT call the point-validation block below; a caller that wants them checks the proof's points and the key itself
- * (gm_g1_check, gm_g1_bases_check, gm_g1_powers_check) --, a sharded verifier. */
+ * first (gm_snark_proof_check, gm_psnark_proof_check, gm_ipa_check, gm_vk_check, gm_crs_check, gm_g1_powers_check) --, a sharded verifier. */
 /* kzg::VerifierKey (src/kzg/mod.rs:141-149): the first max_eval_points powers of g and max_eval_points + 1 powers of g2, records and
  * strides as gm_g1_bases_register / gm_g2_bases_register take them (copied to the host side of the library). */
 int gm_vk_new(const void* g1, size_t g1_stride, size_t n1, const void* g2, size_t g2_stride, size_t n2, uint64_t* vk);
@@ -1042,7 +1042,9 @@ int gm_psnark_new_time_sharded(const gm_psnark_shard* shard, int g1_encoding, si
  * the curve equation (y^2 = x^3 + 4, on the twist y^2 = x^3 + 4 (1 + u)) and membership of the prime-order subgroup by the
  * endomorphism tests ark-bls12-381 uses -- G1: (beta x, y) == -[x^2] P, G2: psi(Q) == [x] Q, x = -0xd201000000010000 -- one lane
  * per point, no inversion (DESIGN.md "Point validation").  The identity is a valid point.  Nothing else in this header calls
- * these checks: registration, the pairings and the verifiers keep taking their points on trust.
+ * these checks: registration, the pairings and the verifiers keep taking their points on trust.  A caller whose inputs it did not
+ * make runs, BEFORE the verifier: gm_vk_check on the key, gm_snark_proof_check / gm_psnark_proof_check / gm_ipa_check on the proof,
+ * gm_crs_check on a CRS (or builds key and CRS with the two _from_bytes decoders and validate != 0).
  * Every point gets ONE status, the FIRST check that fails in the order below.  A bad point is a result, not an error: the return
  * value is GM_OK, *ok = 0 and *first_bad the smallest bad index; when every point passes *ok = 1 and *first_bad = n.  status_or_null
  * (n bytes) and first_bad may be null.  Negative codes are for misuse only: null pointers, a bad stride, a range outside the handle
@@ -1071,6 +1073,43 @@ int gm_g2_bases_check(uint64_t handle, size_t offset, size_t n, uint8_t* status_
  * (no tables are built here either; gm_g1_bases_precompute(handle, -1) asks for them). */
 int gm_g1_bases_from_bytes(const uint8_t* bytes, size_t n, int compressed, int encoding, int validate, uint64_t* handle, uint8_t* status_or_null,
                            size_t* first_bad, int* ok);
+/* The G2 twin: 96 (compressed) or 192 bytes per point; enc 0 x.c0 | x.c1 [| y.c0 | y.c1] little-endian, enc 1 x.c1 | x.c0 [| y.c1 |
+ * y.c0] big-endian, flags as for G1 (the last byte is the top of the last c1, the first byte the top of x.c1).  y > -y is ark-ff's
+ * order of Fq2: c1 first, then c0.  A compressed point costs one square root in Fq2 by the norm method -- two Fq exponentiations,
+ * 1221 Fq products (DESIGN.md "Point validation").  Acceptance is point for point that of gemini_amd/g2.py's deserialize(strict =
+ * True), statuses as above with x^3 + 4 (1 + u) in the place of x^3 + 4.  On success the handle is one of gm_g2_bases_register. */
+int gm_g2_bases_from_bytes(const uint8_t* bytes, size_t n, int compressed, int encoding, int validate, uint64_t* handle, uint8_t* status_or_null,
+                           size_t* first_bad, int* ok);
+/* bases[offset .. offset + n) of a registered handle as n x {48 | 96} (G1) or n x {96 | 192} (G2) bytes in the canonical encoding
+ * the decoders accept, back to back, no length prefix; encoded on the device (one Montgomery exit per coordinate and the y > -y
+ * compare).  cap: the bytes `out` holds.  A range outside the handle, an unknown encoding or a cap too small is GM_EINVAL.  A cyclic
+ * share (gm_g1_bases_set_cyclic) is encoded as it is held: the points of the share, not the key it was cut from. */
+int gm_g1_bases_to_bytes(uint64_t handle, size_t offset, size_t n, int compressed, int encoding, uint8_t* out, size_t cap);
+int gm_g2_bases_to_bytes(uint64_t handle, size_t offset, size_t n, int compressed, int encoding, uint8_t* out, size_t cap);
+/* A gm_crs from two registered handles by device-to-device copy: a CRS decoded by the two _from_bytes calls never visits the host.
+ * The handles stay the caller's (free them, or keep them).  *crs = 0 is written first. */
+int gm_crs_from_bases(uint64_t g1_handle, uint64_t g2_handle, uint64_t* crs);
+/* The curve and subgroup checks over both arrays of a CRS / over the host records of a verifier key (there also the canonical
+ * test).  first_bad_g1 / first_bad_g2 (either may be null): the smallest bad index of each group, its length when all pass. */
+int gm_crs_check(uint64_t crs, size_t* first_bad_g1, size_t* first_bad_g2, int* ok);
+int gm_vk_check(uint64_t vk, size_t* first_bad_g1, size_t* first_bad_g2, int* ok);
+/* Every group element the corresponding verifier reads from a proof: canonical limbs, on the curve, in the subgroup.  The elements
+ * are Jacobian, any representative: they are normalised on the host (a handful of points; a coordinate >= q counts as
+ * GM_PT_NONCANONICAL) and checked in ONE launch per group and call.  *first_bad (may be null) indexes the elements in this order,
+ * and is their number when all pass:
+ *   snark    witness_commitment, fold_commitments[0 .. nfold), evaluation_proof
+ *   psnark   witness_commitment, r_star_commitments[3], z_star_commitment, sorted_commitments[3], acc_v_commitments[9],
+ *            ralpha_star_acc_mu_proof, fold_commitments[0 .. nfold), evaluation_proof
+ *   ipa      G1: foldings_fg1's lhs, the Lhs final foldings; then G2: foldings_fg2's rhs, the Rhs final foldings
+ * The commitments a caller passes to gm_ipa_verify beside the proof are its own to check (gm_g1_check, gm_g2_check).  The GT
+ * elements of an IPA proof (its messages) are NOT checked for membership: that needs a cyclotomic or order-r test this library does
+ * not have. */
+int gm_snark_proof_check(const gm_snark_proof* proof, size_t* first_bad, int* ok);
+int gm_psnark_proof_check(const gm_psnark_proof* proof, size_t* first_bad, int* ok);
+int gm_ipa_check(uint64_t proof, size_t* first_bad, int* ok);
+/* A test aid: the Fq2 square root of the G2 decoder, one lane per element, on inputs no curve point produces.  a_mont: n x 12 limbs
+ * (c0 | c1, ark-ff Montgomery); root_mont the same; is_square[i] = 1 when a_i is a square, and then root_i^2 = a_i. */
+int gm_debug_fq2_sqrt(const uint64_t* a_mont, size_t n, uint64_t* root_mont, uint8_t* is_square);
 /* Do bases[offset .. offset + n) hold consecutive powers of ONE tau -- bases[offset + i + 1] = tau bases[offset + i] for i < n - 1 --,
  * the tau of (g2, tau g2)?  With A = sum rho^i P_i and B = sum rho^i P_{i+1} over i < n - 1 the test is e(A, tau g2) e(-B, g2) == 1:
  * gm_fr_powers, two gm_g1_msm_v and ONE two-pair multi-pairing.  g2_affine / tau_g2_affine: 192-byte records as

@@ -17,7 +17,8 @@
 //   gm::dist::{init_rccl, init_shm, init_hook, ...}         the all-gather between the per-GPU processes (no reference counterpart:
 //                                                           the reference is single-device; gemini_amd/csrc/dist.cpp)
 //   gm::CommitterKey::cyclic_share                          CommitterKey::new (src/kzg/time.rs:49-72), every rank its powers i = rank (mod world)
-//   gm::check_g1 / check_g2, CommitterKey::{check_points, check_powers, from_bytes}, G2Bases::check_points
+//   gm::check_g1 / check_g2, CommitterKey::{check_points, check_powers, from_bytes, to_bytes}, G2Bases::{check_points, from_bytes,
+//   to_bytes}, Crs::{from_bases, check}, VerifierKey::check, check_points of SnarkProof / PsnarkProof / InnerProductProof
 //                                                           deserialize_with_mode(.., Validate::Yes) of ark-ec for whole keys, on the
 //                                                           device (gemini_amd/csrc/points.hip); the powers check has no counterpart
 #pragma once
@@ -128,6 +129,18 @@ struct PointCheck {
   bool ok = false;
   size_t first_bad = 0;         // the smallest bad index; n when every point passes
   std::vector<uint8_t> status;  // PointStatus values, one per point
+  explicit operator bool() const { return ok; }
+};
+// gm_crs_check / gm_vk_check: the smallest bad index of each group (its length when every point passes)
+struct KeyCheck {
+  bool ok = false;
+  size_t first_bad_g1 = 0, first_bad_g2 = 0;
+  explicit operator bool() const { return ok; }
+};
+// gm_snark_proof_check / gm_psnark_proof_check / gm_ipa_check: first_bad in the order gemini_hip.h lists the elements
+struct ProofCheck {
+  bool ok = false;
+  size_t first_bad = 0;
   explicit operator bool() const { return ok; }
 };
 namespace detail {
@@ -360,6 +373,13 @@ class CommitterKey {
     return std::optional<CommitterKey>(std::move(k));
   }
   PointCheck check_points() const { return check_g1_bases(h_, 0, n_); }  // every power on the curve and in G1
+  // the canonical encodings of powers [offset, offset + n), 48 / 96 bytes each, made on the device (gm_g1_bases_to_bytes)
+  std::vector<uint8_t> to_bytes(bool compressed, int encoding, size_t offset, size_t n) const {
+    std::vector<uint8_t> out(n * (compressed ? 48 : 96));
+    check(gm_g1_bases_to_bytes(h_, offset, n, compressed ? 1 : 0, encoding, out.data(), out.size()));
+    return out;
+  }
+  std::vector<uint8_t> to_bytes(bool compressed, int encoding = 0) const { return to_bytes(compressed, encoding, 0, n_); }
   bool check_powers(const uint64_t g2_affine[24], const uint64_t tau_g2_affine[24], const Fr& rho) const { return gm::check_powers(h_, 0, n_, g2_affine, tau_g2_affine, rho); }
   size_t size() const { return n_; }
   CommitterKey(CommitterKey&& o) noexcept : h_(o.h_), n_(o.n_) { o.h_ = 0; }
@@ -503,6 +523,27 @@ class G2Bases {
     return detail::point_check(n, [&](uint8_t* st, size_t* fb, int* ok) { return gm_g2_bases_check(h_, offset, n, st, fb, ok); });
   }
   PointCheck check_points() const { return check_points(0, n_); }
+  // n points of 96 (compressed) or 192 bytes in the framing `encoding`, decoded -- and with `validate` checked -- on the device
+  // (gm_g2_bases_from_bytes).  No bases when a point is rejected: *report says which and why
+  static std::optional<G2Bases> from_bytes(const std::vector<uint8_t>& bytes, size_t n, bool compressed, int encoding, bool validate = true, PointCheck* report = nullptr) {
+    if (bytes.size() != n * (compressed ? 96 : 192)) throw Error(GM_EINVAL, "G2Bases::from_bytes: the byte count does not match n");
+    G2Bases b;
+    PointCheck r = detail::point_check(n, [&](uint8_t* st, size_t* fb, int* ok) {
+      return gm_g2_bases_from_bytes(bytes.data(), n, compressed ? 1 : 0, encoding, validate ? 1 : 0, &b.h_, st, fb, ok);
+    });
+    const bool ok = r.ok;
+    if (report) *report = std::move(r);
+    if (ok != (b.h_ != 0)) throw Error(GM_ESTATE, "G2Bases::from_bytes: the library hands out a handle exactly when every point is accepted");
+    if (!ok) return std::nullopt;
+    b.n_ = n;
+    return std::optional<G2Bases>(std::move(b));
+  }
+  std::vector<uint8_t> to_bytes(bool compressed, int encoding, size_t offset, size_t n) const {
+    std::vector<uint8_t> out(n * (compressed ? 96 : 192));
+    check(gm_g2_bases_to_bytes(h_, offset, n, compressed ? 1 : 0, encoding, out.data(), out.size()));
+    return out;
+  }
+  std::vector<uint8_t> to_bytes(bool compressed, int encoding = 0) const { return to_bytes(compressed, encoding, 0, n_); }
   // 192-byte records x.c0 | x.c1 | y.c0 | y.c1 (the identity all zero), 24 words each
   std::vector<uint64_t> download(size_t offset, size_t n) const {
     std::vector<uint64_t> out(n * 24);
@@ -534,6 +575,7 @@ class G2Bases {
   }
 
  private:
+  G2Bases() = default;
   uint64_t h_ = 0;
   size_t n_ = 0;
 };
@@ -700,7 +742,21 @@ class Transcript {
 class Crs {  // ipa.rs:62-66,172-213: G1 and G2 points resident in HBM
  public:
   Crs(const std::vector<G1Affine>& g1s, const std::vector<G2Affine>& g2s) {
-    check(gm_crs_new(g1s.data(), sizeof(G1Affine), g1s.size(), g2s.data(), sizeof(G2Affine), g2s.size(), &h_));
+    gm::check(gm_crs_new(g1s.data(), sizeof(G1Affine), g1s.size(), g2s.data(), sizeof(G2Affine), g2s.size(), &h_));
+  }
+  // from two registered keys by device-to-device copy (gm_crs_from_bases): a CRS decoded by the two from_bytes never visits the
+  // host; the keys stay the caller's
+  static Crs from_bases(const CommitterKey& g1s, const G2Bases& g2s) {
+    Crs c;
+    gm::check(gm_crs_from_bases(g1s.handle(), g2s.handle(), &c.h_));
+    return c;
+  }
+  KeyCheck check() const {  // curve and subgroup over both arrays (gm_crs_check)
+    KeyCheck r;
+    int ok = 0;
+    gm::check(gm_crs_check(h_, &r.first_bad_g1, &r.first_bad_g2, &ok));
+    r.ok = ok != 0;
+    return r;
   }
   Crs(Crs&& o) noexcept : h_(o.h_) { o.h_ = 0; }
   ~Crs() {
@@ -711,17 +767,18 @@ class Crs {  // ipa.rs:62-66,172-213: G1 and G2 points resident in HBM
   // the CRS must be longer than the scalars (ipa.rs:180,186)
   G1Projective commit_g1(const std::vector<Fr>& scalars) const {
     G1Projective out;
-    check(gm_crs_commit_g1(h_, scalars.empty() ? nullptr : scalars[0].data(), scalars.size(), out.data()));
+    gm::check(gm_crs_commit_g1(h_, scalars.empty() ? nullptr : scalars[0].data(), scalars.size(), out.data()));
     return out;
   }
   G2Projective commit_g2(const std::vector<Fr>& scalars) const {
     G2Projective out;
-    check(gm_crs_commit_g2(h_, scalars.empty() ? nullptr : scalars[0].data(), scalars.size(), out.data()));
+    gm::check(gm_crs_commit_g2(h_, scalars.empty() ? nullptr : scalars[0].data(), scalars.size(), out.data()));
     return out;
   }
   uint64_t handle() const { return h_; }
 
  private:
+  Crs() = default;
   uint64_t h_ = 0;
 };
 
@@ -815,6 +872,14 @@ class InnerProductProof {  // ipa.rs:54-60
   std::pair<Fr, G2Projective> foldings_fg2() const {
     std::pair<Fr, G2Projective> r;
     check(gm_ipa_foldings_fg2(h_, r.first.data(), r.second.data()));
+    return r;
+  }
+  // every G1 and G2 element verify_transcript reads from the proof, the G1 ones first (gm_ipa_check); GT elements are NOT checked
+  ProofCheck check_points() const {
+    ProofCheck r;
+    int ok = 0;
+    check(gm_ipa_check(h_, &r.first_bad, &ok));
+    r.ok = ok != 0;
     return r;
   }
   // verify_transcript (ipa.rs:250-343): true for Ok(())
@@ -1104,12 +1169,12 @@ inline std::array<DeviceVec, 3> plookup(const DeviceVec& subset, const DeviceVec
 class VerifierKey {
  public:
   VerifierKey(const std::vector<G1Affine>& powers_of_g, const std::vector<G2Affine>& powers_of_g2) {
-    check(gm_vk_new(powers_of_g.data(), sizeof(G1Affine), powers_of_g.size(), powers_of_g2.data(), sizeof(G2Affine), powers_of_g2.size(), &h_));
+    gm::check(gm_vk_new(powers_of_g.data(), sizeof(G1Affine), powers_of_g.size(), powers_of_g2.data(), sizeof(G2Affine), powers_of_g2.size(), &h_));
   }
   // the setup aid that pairs with gm_g1_srs_register: tau canonical, g and g2 as 12 / 24 Montgomery limbs
   static VerifierKey from_trapdoor(const uint64_t g_affine[12], const uint64_t g2_affine[24], const BigInt& tau, size_t max_eval_points) {
     VerifierKey k;
-    check(gm_vk_from_trapdoor(g_affine, g2_affine, tau.data(), max_eval_points, &k.h_));
+    gm::check(gm_vk_from_trapdoor(g_affine, g2_affine, tau.data(), max_eval_points, &k.h_));
     return k;
   }
   VerifierKey(VerifierKey&& o) noexcept : h_(o.h_) { o.h_ = 0; }
@@ -1119,17 +1184,25 @@ class VerifierKey {
   VerifierKey(const VerifierKey&) = delete;
   VerifierKey& operator=(const VerifierKey&) = delete;
   uint64_t handle() const { return h_; }
+  // every power of both halves canonical, on its curve and in its subgroup (gm_vk_check): run it on a key from elsewhere BEFORE verify
+  KeyCheck check() const {
+    KeyCheck r;
+    int ok = 0;
+    gm::check(gm_vk_check(h_, &r.first_bad_g1, &r.first_bad_g2, &ok));
+    r.ok = ok != 0;
+    return r;
+  }
   // serialize_uncompressed(&powers_of_g2): what psnark absorbs as b"ck" (PsnarkProof::new_time's ck_g2_bytes)
   std::vector<uint8_t> g2_bytes(int encoding = 0) const {
     size_t n = 0;
-    check(gm_vk_g2_bytes(h_, encoding, nullptr, 0, &n));
+    gm::check(gm_vk_g2_bytes(h_, encoding, nullptr, 0, &n));
     std::vector<uint8_t> out(n);
-    check(gm_vk_g2_bytes(h_, encoding, out.data(), n, &n));
+    gm::check(gm_vk_g2_bytes(h_, encoding, out.data(), n, &n));
     return out;
   }
   bool verify(const G1Projective& commitment, const Fr& alpha, const Fr& evaluation, const G1Projective& proof) const {  // src/kzg/mod.rs:155-175
     int ok = 0;
-    check(gm_kzg_verify(h_, commitment.data(), alpha.data(), evaluation.data(), proof.data(), &ok));
+    gm::check(gm_kzg_verify(h_, commitment.data(), alpha.data(), evaluation.data(), proof.data(), &ok));
     return ok != 0;
   }
   // :181-244; evaluations: one row of eval_points.size() values per commitment
@@ -1141,7 +1214,7 @@ class VerifierKey {
       flat.insert(flat.end(), row.begin(), row.end());
     }
     int ok = 0;
-    check(gm_kzg_verify_multi_points(h_, commitments.empty() ? nullptr : commitments[0].data(), commitments.size(), eval_points.empty() ? nullptr : eval_points[0].data(),
+    gm::check(gm_kzg_verify_multi_points(h_, commitments.empty() ? nullptr : commitments[0].data(), commitments.size(), eval_points.empty() ? nullptr : eval_points[0].data(),
                                      eval_points.size(), flat.empty() ? nullptr : flat[0].data(), evaluations.size(), proof.data(), open_chal.data(), &ok));
     return ok != 0;
   }
@@ -1194,6 +1267,25 @@ struct SnarkProof {
     const uint64_t mats_t[3] = {r1cs.at_.handle(), r1cs.bt_.handle(), r1cs.ct_.handle()};
     check(gm_snark_new_elastic(mats_t, z_be.h, w_be.h, za.h, zb.h, zc.h, ck.handle(), max_msm_buffer, min_device_chunk, g1_encoding, b.cap, &b.p));
     return b.unpack();
+  }
+
+  // every G1 element the verifier reads is canonical, on the curve and in G1 (gm_snark_proof_check); verify() does not call it
+  ProofCheck check_points() const {
+    const auto& tc = tensorcheck_proof;
+    const size_t nf = tc.folded_polynomials_commitments.size();
+    gm_snark_proof p;
+    memset(&p, 0, sizeof p);
+    std::vector<uint64_t> fc(18 * nf + 1);
+    memcpy(p.witness_commitment, witness_commitment.data(), 144);
+    for (size_t i = 0; i < nf; i++) memcpy(fc.data() + 18 * i, tc.folded_polynomials_commitments[i].data(), 144);
+    p.nfold = nf;
+    p.fold_commitments = fc.data();
+    memcpy(p.evaluation_proof, tc.evaluation_proof.data(), 144);
+    ProofCheck r;
+    int ok = 0;
+    check(gm_snark_proof_check(&p, &r.first_bad, &ok));
+    r.ok = ok != 0;
+    return r;
   }
 
   // Proof::verify(&r1cs, &vk) (src/snark/verifier.rs:19-119): true = accepted.  The proof may come from a prover or from its fields
@@ -1409,6 +1501,30 @@ struct PsnarkProof {
     tc.base_polynomials_evaluations.resize(22);
     memcpy(tc.base_polynomials_evaluations[0].data(), p.base_evaluations, sizeof p.base_evaluations);
     return out;
+  }
+
+  // every G1 element the verifier reads is canonical, on the curve and in G1 (gm_psnark_proof_check); verify() does not call it
+  ProofCheck check_points() const {
+    const TensorcheckProof& tc = tensorcheck_proof;
+    const size_t nf = tc.folded_polynomials_commitments.size();
+    gm_psnark_proof p;
+    memset(&p, 0, sizeof p);
+    std::vector<uint64_t> fc(18 * nf + 1);
+    memcpy(p.witness_commitment, witness_commitment.data(), 144);
+    memcpy(p.r_star_commitments, r_star_commitments.data(), sizeof p.r_star_commitments);
+    memcpy(p.z_star_commitment, z_star_commitment.data(), 144);
+    memcpy(p.sorted_commitments, sorted_commitments.data(), sizeof p.sorted_commitments);
+    memcpy(p.acc_v_commitments, acc_v_commitments.data(), sizeof p.acc_v_commitments);
+    memcpy(p.ralpha_star_acc_mu_proof, ralpha_star_acc_mu_proof.data(), 144);
+    for (size_t i = 0; i < nf; i++) memcpy(fc.data() + 18 * i, tc.folded_polynomials_commitments[i].data(), 144);
+    p.nfold = p.cap_folds = nf;
+    p.fold_commitments = fc.data();
+    memcpy(p.evaluation_proof, tc.evaluation_proof.data(), 144);
+    ProofCheck r;
+    int ok = 0;
+    check(gm_psnark_proof_check(&p, &r.first_bad, &ok));
+    r.ok = ok != 0;
+    return r;
   }
 
   // Proof::verify(&r1cs, &vk, &index, num_non_zero) (src/psnark/verifier.rs:88-565): true = accepted.  The key needs max_eval_points >= 3
