@@ -249,6 +249,8 @@ uint64_t put_prover(std::unique_ptr<Sumcheck> p) {
 // implemented in msm.hip / fr.hip
 int fixed_base_generate(Context* C, const uint64_t base_affine[12], const void* d_scalars, int mont, size_t n,
                         std::unique_ptr<Bases>& out);
+int g2_fixed_base_generate(Context* C, const uint64_t base_affine[24], const void* d_scalars, int mont, size_t n, std::unique_ptr<G2Bases>& out);
+int crs_fold(Context* C, const Crs* in, const uint64_t challenge_mont[4], Crs* out);  // ipa.hip
 int bases_precompute(Context* C, Bases* b, int c);
 void bases_free_tables(Bases* b);
 int bases_export(Context* C, const Bases* b, size_t offset, size_t n, void* out96);
@@ -1833,6 +1835,47 @@ int gm_g2_bases_register(const void* bases, size_t base_stride, size_t n, uint64
   C->g2_bases[*handle] = std::move(b);
   return GM_OK;
 }
+// the G2 twins of gm_g1_fixed_base_register / gm_g1_srs_register (g2msm.hip: g2_fixed_base_generate)
+int gm_g2_fixed_base_register(const uint64_t base_affine[24], const uint64_t* scalars, size_t n, uint64_t* handle) {
+  GM_CTX();
+  GM_CHECK(base_affine && handle && (scalars || n == 0), GM_EINVAL, "g2_fixed_base_register: null pointer");
+  GM_CHECK(n <= SIZE_MAX / 32, GM_EINVAL, "g2_fixed_base_register: %zu scalars do not fit a size_t", n);
+  GM_MSM_LOCK(C);  // across the upload and the launches that read it
+  uint8_t* d_sc = nullptr;
+  if (n) {
+    GM_HIP(dev_malloc((void**)&d_sc, n * 32));
+    GM_HIP(hipMemcpyAsync(d_sc, scalars, n * 32, hipMemcpyHostToDevice, C->stream));
+  }
+  std::unique_ptr<G2Bases> b;
+  int rc = g2_fixed_base_generate(C, base_affine, d_sc, 0, n, b);
+  if (d_sc) {
+    if (rc) (void)hipStreamSynchronize(C->stream);  // the copy may still be in flight
+    (void)gm::raw_free(d_sc);
+  }
+  if (rc) return rc;
+  *handle = put_in(C, C->g2_bases, std::move(b));
+  return GM_OK;
+}
+int gm_g2_srs_register(const uint64_t base_affine[24], const uint64_t tau[4], size_t n, uint64_t* handle) {
+  GM_CTX();
+  GM_CHECK(base_affine && tau && handle, GM_EINVAL, "g2_srs_register: null pointer");
+  GM_CHECK(n <= SIZE_MAX / 32, GM_EINVAL, "g2_srs_register: %zu powers do not fit a size_t", n);
+  // powers of tau on the device (Montgomery), then the fixed-base multiplication
+  auto v = std::make_unique<FrVec>();
+  v->cap = n;
+  if (n) GM_HIP(dev_malloc((void**)&v->d, n * 32));
+  gmh::Fr t = gmh::Fr::from_canonical(tau);
+  uint64_t tm[4];
+  t.to_limbs(tm);
+  int rc = fr_powers(C, tm, n, v.get());
+  std::unique_ptr<G2Bases> b;
+  if (!rc) rc = g2_fixed_base_generate(C, base_affine, v->d, 1, n, b);
+  if (v->d) (void)gm::raw_free(v->d);
+  v->d = nullptr;
+  if (rc) return rc;
+  *handle = put_in(C, C->g2_bases, std::move(b));
+  return GM_OK;
+}
 int gm_g2_bases_free(uint64_t handle) {
   GM_CTX();
   std::unique_ptr<G2Bases> b;
@@ -2023,6 +2066,84 @@ int gm_crs_len(uint64_t handle, size_t* n1, size_t* n2) {
   GM_IPA_FIND(c, crs, handle, "crs_len", "CRS");
   if (n1) *n1 = c->n1;
   if (n2) *n2 = c->n2;
+  return GM_OK;
+}
+// device copies of the first k1 / k2 points of a CRS (either pointer may be null); freed by the caller
+static int crs_copy_prefix(Context* C, const Crs* c, size_t k1, size_t k2, uint8_t** g1, uint8_t** g2) {
+  GM_MSM_LOCK(C);
+  uint8_t *d1 = nullptr, *d2 = nullptr;
+  hipError_t e = hipSuccess;
+  if (g1 && k1) e = dev_malloc((void**)&d1, k1 * 96);
+  if (e == hipSuccess && g2 && k2) e = dev_malloc((void**)&d2, k2 * 192);
+  if (e == hipSuccess && d1) e = hipMemcpyAsync(d1, c->g1, k1 * 96, hipMemcpyDeviceToDevice, C->stream);
+  if (e == hipSuccess && d2) e = hipMemcpyAsync(d2, c->g2, k2 * 192, hipMemcpyDeviceToDevice, C->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(C->stream);
+  if (e != hipSuccess) {
+    if (d1) (void)gm::raw_free(d1);
+    if (d2) (void)gm::raw_free(d2);
+    return hip_fail(e, "crs copy", __FILE__, __LINE__);
+  }
+  if (g1) *g1 = d1;
+  if (g2) *g2 = d2;
+  return GM_OK;
+}
+static int crs_prefix(Context* C, const Crs* c, size_t k1, size_t k2, uint64_t* out) {
+  auto r = std::make_unique<Crs>();
+  int rc = crs_copy_prefix(C, c, k1, k2, &r->g1, &r->g2);
+  if (rc) return rc;
+  r->n1 = k1;
+  r->n2 = k2;
+  *out = put_in(C, C->crs, std::move(r));
+  return GM_OK;
+}
+// Crs::truncate (ipa.rs:191-196): 1 << rounds points of each group, or all of them
+int gm_crs_truncate(uint64_t crs, size_t rounds, uint64_t* out) {
+  if (out) *out = 0;
+  GM_CTX();
+  GM_IPA_FIND(c, crs, crs, "crs_truncate", "CRS");
+  GM_CHECK(out != nullptr, GM_EINVAL, "crs_truncate: null pointer");
+  const size_t cut = rounds < 8 * sizeof(size_t) ? (size_t)1 << rounds : SIZE_MAX;
+  return crs_prefix(C, c, std::min(c->n1, cut), std::min(c->n2, cut), out);
+}
+// Crs::halve (ipa.rs:198-203)
+int gm_crs_halve(uint64_t crs, uint64_t* out) {
+  if (out) *out = 0;
+  GM_CTX();
+  GM_IPA_FIND(c, crs, crs, "crs_halve", "CRS");
+  GM_CHECK(out != nullptr, GM_EINVAL, "crs_halve: null pointer");
+  return crs_prefix(C, c, (c->n1 + 1) / 2, (c->n2 + 1) / 2, out);
+}
+// Crs::fold (ipa.rs:205-212)
+int gm_crs_fold(uint64_t crs, const uint64_t challenge_mont[4], uint64_t* out) {
+  if (out) *out = 0;
+  GM_CTX();
+  GM_IPA_FIND(c, crs, crs, "crs_fold", "CRS");
+  GM_CHECK(out != nullptr && challenge_mont != nullptr, GM_EINVAL, "crs_fold: null pointer");
+  GM_CHECK(c->n1 == c->n2, GM_EINVAL, "crs_fold: %zu G1 and %zu G2 points (the reference folds g2s over g1s' length, ipa.rs:205-212)", c->n1, c->n2);
+  auto r = std::make_unique<Crs>();
+  int rc = crs_fold(C, c, challenge_mont, r.get());
+  if (rc) return rc;
+  *out = put_in(C, C->crs, std::move(r));
+  return GM_OK;
+}
+int gm_crs_to_bases(uint64_t crs, uint64_t* g1_handle, uint64_t* g2_handle) {
+  if (g1_handle) *g1_handle = 0;
+  if (g2_handle) *g2_handle = 0;
+  GM_CTX();
+  GM_IPA_FIND(c, crs, crs, "crs_to_bases", "CRS");
+  auto b1 = std::make_unique<Bases>();
+  auto b2 = std::make_unique<G2Bases>();
+  int rc = crs_copy_prefix(C, c, c->n1, c->n2, g1_handle ? &b1->d : nullptr, g2_handle ? &b2->d : nullptr);
+  if (rc) return rc;
+  b1->n = c->n1;
+  b2->n = c->n2;
+  if (g1_handle && (rc = bases_build_phi(C, b1.get()))) {
+    if (b1->d) (void)gm::raw_free(b1->d);
+    if (b2->d) (void)gm::raw_free(b2->d);
+    return rc;
+  }
+  if (g1_handle) *g1_handle = put_bases(std::move(b1));  // as gm_g1_bases_register: no tables
+  if (g2_handle) *g2_handle = put_in(C, C->g2_bases, std::move(b2));
   return GM_OK;
 }
 int gm_crs_commit_g1(uint64_t handle, const uint64_t* scalars_mont, size_t n, uint64_t out_jac[18]) {

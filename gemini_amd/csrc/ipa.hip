@@ -180,6 +180,29 @@ int crs_commit(Context* C, const Crs* crs, int group, const uint64_t* scalars_mo
   return g2_msm_run(C, &b, 0, 1, C->msm.scalars.p, 1, n, out_jac);
 }
 
+// Crs::fold (ipa.rs:205-212): g[i] = g[2i] + c g[2i+1] in both groups, one launch of the module provers' split-fold kernel each (an
+// odd tail folds against the identity); the caller has checked n1 == n2.  `out` owns two new arrays of ceil(n / 2) points.
+int crs_fold(Context* C, const Crs* in, const uint64_t challenge_mont[4], Crs* out) {
+  const size_t m1 = (in->n1 + 1) / 2, m2 = (in->n2 + 1) / 2;
+  const Scalar c = canonical(gmh::Fr::from_limbs(challenge_mont));
+  GM_MSM_LOCK(C);
+  int rc;
+  if ((rc = C->msm.misc.ensure(64))) return rc;
+  Scratch tmp;
+  uint8_t *d1 = nullptr, *d2 = nullptr;
+  if ((rc = tmp.get(m1 * 96, &d1)) || (rc = tmp.get(m2 * 192, &d2))) return rc;
+  GM_HIP(hipMemcpyAsync(C->msm.misc.p, c.data(), 32, hipMemcpyHostToDevice, C->stream));
+  if ((rc = g1_split_fold_launch(C, in->g1, in->n1, C->msm.misc.as<uint32_t>(), d1))) return rc;
+  if ((rc = g2_split_fold_launch(C, in->g2, in->n2, C->msm.misc.as<uint32_t>(), d2))) return rc;
+  GM_HIP(hipStreamSynchronize(C->stream));  // `c` is read by its copy until here
+  tmp.p.clear();  // the arrays are the result's from here
+  out->g1 = d1;
+  out->n1 = m1;
+  out->g2 = d2;
+  out->n2 = m2;
+  return GM_OK;
+}
+
 // Vrs::from (ipa.rs:215-247): for size = 2, 4, ... below the CRS length the four products of the even / odd points of one group
 // against the first `size` of the other -- all 4 levels products in ONE segmented launch, then one final exponentiation each
 int vrs_from_crs(Context* C, const Crs* crs, Vrs* out) {

@@ -21,6 +21,7 @@
 // Reporting: ONE status byte per point (the first check that fails, gemini_hip.h: GM_PT_*), written with ordinary stores, and one
 // u32 per block holding the block's first bad lane.  The host reads the block summaries (and the status bytes when the caller asks
 // for them); no coordinate crosses back.  Launches go on the library's stream under the MSM lock, as the pairing entries do.
+#include <algorithm>
 #include <cstring>
 #include <vector>
 
@@ -540,6 +541,172 @@ __global__ __launch_bounds__(PT_G2_BLOCK) void k_fq2_sqrt(const uint8_t* __restr
   is_square[i] = square ? 1 : 0;
 }
 
+// ---- points without a known logarithm: candidates -> cofactor-cleared points (gm_g1_bases_from_candidates, gm_g2_...) -----------
+// A candidate is an x (and one bit that chooses between y and -y); it survives when its coordinates are < q, x^3 + b is a square and
+// the cleared point is not the identity (include/gemini_hip.h has the format; tests/keygen_ref.py states all of it on integers).
+// Three launches, dense lanes in each, the host compacting in between from status bytes (a wave runs as long as its slowest lane:
+// one kernel from bytes to cleared point took 2.4 x as long, every wave paying root AND clearing for its few survivors):
+//   root    one lane per candidate: rules 1 and 2, the curve point (affine) into slot i, one status byte
+//   clear   one lane per candidate ON THE CURVE, in order and only as many as the key still needs: the cleared point (XYZZ) over the
+//           slot, one status byte (rule 3)
+//   gather  the survivors normalised into the key, eight to an inversion
+// Fq products: root G1 5 + 606, G2 9 + 1 221; clearing G1 63 x 9 + 6 x 10 = 627, G2 2 x 63 x 24 + 6 x 28 (mixed) + 5 x 37 (full) +
+// 135 (the tail: one mixed and two full additions, psi three times, [2] P) = 3 512.
+constexpr uint8_t PT_CAND_OK = 0, PT_CAND_GE_Q = 1, PT_CAND_NO_SQUARE = 2, PT_CAND_IDENTITY = 3;
+constexpr uint32_t PT_CAND_X_MASK = 0x1fffffffu;  // bits 381 and 382 are ignored, bit 383 is the choice of y
+
+__global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_g1_cand_root(const uint8_t* __restrict__ cand, size_t m, uint8_t* __restrict__ slots,
+                                                                                                      uint8_t* __restrict__ status) {
+  const size_t i = (size_t)blockIdx.x * PT_BLOCK + threadIdx.x;
+  if (i >= m) return;
+  Fq x = fp_load<FqParams>(cand + i * 48);
+  const bool larger = (x.l[11] >> 31) != 0;
+  x.l[11] &= PT_CAND_X_MASK;
+  uint8_t st = PT_CAND_OK;
+  if (pt_raw_ge_q(x)) {
+    st = PT_CAND_GE_Q;
+  } else {
+    G1Affine P;
+    P.x = pt_from_int(x);
+    const FqE rhs = fq_add(fq_mul(fq_sqr(P.x), P.x), pt_four());
+    P.y = pt_sqrt_candidate(rhs);
+    if (!(fq_sqr(P.y) == rhs)) {
+      st = PT_CAND_NO_SQUARE;
+    } else {
+      if (pt_y_is_larger(pt_to_int(P.y)) != larger) P.y = fq_neg_canonical(P.y);
+      g1_store_affine(slots + i * 192, P);
+    }
+  }
+  status[i] = st;
+}
+// lane j clears the curve point in slot idx[j]: [1 - x] P = [|x|] P + P
+__global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_g1_cand_clear(uint8_t* __restrict__ slots, const uint32_t* __restrict__ idx, size_t n,
+                                                                                                       uint8_t* __restrict__ status) {
+  const size_t j = (size_t)blockIdx.x * PT_BLOCK + threadIdx.x;
+  if (j >= n) return;
+  uint8_t* slot = slots + (size_t)idx[j] * 192;
+  const G1Affine P = g1_load_affine(slot);
+  G1Xyzz T = pt_g1_mul_x(P);
+  xyzz_madd(T, P);
+  g1_store_xyzz(slot, T);
+  status[j] = T.is_identity() ? PT_CAND_IDENTITY : PT_CAND_OK;
+}
+
+// psi on XYZZ coordinates: conjugation is a field automorphism, so (X, Y, ZZ, ZZZ) -> (conj(X) c_x, conj(Y) c_y, conj(ZZ), conj(ZZZ))
+// is psi of the point they stand for.  The constants are those of pt_g2_status; the identity maps to itself.
+GM_DEV Fq2 pt_fq2_conj(const Fq2& a) {
+  Fq2 r;
+  r.c0 = a.c0;
+  r.c1 = fq_neg_canonical(a.c1);
+  return r;
+}
+GM_DEV G2Xyzz pt_g2_psi(const G2Xyzz& T) {
+  const FqE cx1 = pt_const(PT_PSI_CX1);
+  Fq2 cy;
+  cy.c0 = pt_const(PT_PSI_CY0);
+  cy.c1 = pt_const(PT_PSI_CY1);
+  G2Xyzz r;
+  r.x.c0 = fq_mul(T.x.c1, cx1);  // conj(x) (0 + c u) = x1 c + x0 c u
+  r.x.c1 = fq_mul(T.x.c0, cx1);
+  r.y = fq2_mul(pt_fq2_conj(T.y), cy);
+  r.zz = pt_fq2_conj(T.zz);
+  r.zzz = pt_fq2_conj(T.zzz);
+  return r;
+}
+// [x^2 - x - 1] P + [x - 1] psi(P) + psi^2([2] P) (Budroni, Pintore: "Efficient hash maps to G2 on BLS curves"), x = -|x|: with
+// U = [|x| + 1] P it is [|x|] U - P - psi(U) + psi^2([2] P) -- two |x| ladders.  U waits in the lane's slot between the five
+// additions of the second ladder.  k_g2_cand_clear still spills: 560 bytes of scratch a lane at one wave per SIMD -- the accumulator,
+// P and a full XYZZ + XYZZ addition over Fq2 are more than 512 registers, as in k_g2_reduce (profiles/keygen_kernel_resources.txt).
+GM_DEV G2Xyzz pt_g2_clear(const G2Affine& P, uint8_t* slot) {
+  G2Xyzz acc = G2Xyzz::from_affine(P);
+#pragma unroll 1
+  for (int bit = 62; bit >= 0; bit--) {
+    acc = g2_dbl(acc);
+    if ((BLS_X_ABS >> bit) & 1ull) g2_madd(acc, P);
+  }
+  g2_madd(acc, P);
+  g2_store_xyzz(slot, acc);  // U
+#pragma unroll 1
+  for (int bit = 62; bit >= 0; bit--) {
+    acc = g2_dbl(acc);
+    if ((BLS_X_ABS >> bit) & 1ull) g2_add(acc, g2_load_xyzz(slot));
+  }
+  g2_madd(acc, g2_neg_affine(P));
+  G2Xyzz pu = pt_g2_psi(g2_load_xyzz(slot));
+  pu.y = fq2_neg_canonical(pu.y);
+  g2_add(acc, pu);
+  g2_add(acc, pt_g2_psi(pt_g2_psi(g2_dbl_affine(P))));
+  return acc;
+}
+
+__global__ __launch_bounds__(PT_G2_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_g2_cand_root(const uint8_t* __restrict__ cand, size_t m, uint8_t* __restrict__ slots, uint8_t* __restrict__ status) {
+  const size_t i = (size_t)blockIdx.x * PT_G2_BLOCK + threadIdx.x;
+  if (i >= m) return;
+  Fq c0 = fp_load<FqParams>(cand + i * 96), c1 = fp_load<FqParams>(cand + i * 96 + 48);
+  const bool larger = (c1.l[11] >> 31) != 0;
+  c0.l[11] &= PT_CAND_X_MASK;
+  c1.l[11] &= PT_CAND_X_MASK;
+  uint8_t st = PT_CAND_OK;
+  if (pt_raw_ge_q(c0) || pt_raw_ge_q(c1)) {
+    st = PT_CAND_GE_Q;
+  } else {
+    G2Affine P;
+    P.x.c0 = pt_from_int(c0);
+    P.x.c1 = pt_from_int(c1);
+    Fq2 rhs = fq2_mul(fq2_sqr(P.x), P.x);
+    rhs.c0 = fq_add(rhs.c0, pt_four());
+    rhs.c1 = fq_add(rhs.c1, pt_four());
+    bool square;
+    P.y = pt_fq2_sqrt(rhs, &square);
+    if (!square) {
+      st = PT_CAND_NO_SQUARE;
+    } else {
+      if (pt_y2_is_larger(pt_to_int(P.y.c0), pt_to_int(P.y.c1)) != larger) P.y = fq2_neg_canonical(P.y);
+      g2_store_affine(slots + i * G2_XYZZ_BYTES, P);
+    }
+  }
+  status[i] = st;
+}
+// lane j clears the curve point in slot idx[j] (its first 192 bytes); the slot then serves pt_g2_clear, and takes the result
+__global__ __launch_bounds__(PT_G2_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_g2_cand_clear(uint8_t* slots, const uint32_t* __restrict__ idx, size_t n, uint8_t* __restrict__ status) {
+  const size_t j = (size_t)blockIdx.x * PT_G2_BLOCK + threadIdx.x;
+  if (j >= n) return;
+  uint8_t* slot = slots + (size_t)idx[j] * G2_XYZZ_BYTES;
+  const G2Affine P = g2_load_affine(slot);
+  const G2Xyzz R = pt_g2_clear(P, slot);
+  g2_store_xyzz(slot, R);
+  status[j] = R.is_identity() ? PT_CAND_IDENTITY : PT_CAND_OK;
+}
+
+// The slots idx[0 .. n) -> packed affine records, Montgomery's trick over eight points a lane; the prefix products wait in the
+// group's own output records (k_g2_xyzz_to_affine_batch, g2msm.hip, is the same over Fq2).  No slot holds the identity.
+constexpr int PT_NORM_K = 8;
+__global__ __launch_bounds__(PT_BLOCK) void k_g1_gather_affine(const uint8_t* __restrict__ slots, const uint32_t* __restrict__ idx, size_t n, uint8_t* out) {
+  const size_t t = (size_t)blockIdx.x * PT_BLOCK + threadIdx.x;
+  const size_t i0 = t * PT_NORM_K;
+  if (i0 >= n) return;
+  const int m = (int)min((size_t)PT_NORM_K, n - i0);
+  FqE run = fqe_one();
+  for (int k = 0; k < m; k++) {
+    const uint8_t* rec = slots + (size_t)idx[i0 + k] * 192;
+    run = fq_mul(run, fq_mul(fqe_load(rec + 96), fqe_load(rec + 144)));
+    fqe_store(out + (i0 + k) * 96, run);
+  }
+  FqE inv = g2_fq_inv(run);
+  for (int k = m - 1; k >= 0; k--) {
+    const uint8_t* rec = slots + (size_t)idx[i0 + k] * 192;
+    const FqE zz = fqe_load(rec + 96), zzz = fqe_load(rec + 144);
+    const FqE ti = k ? fq_mul(inv, fqe_load(out + (i0 + k - 1) * 96)) : inv;  // 1 / (zz zzz)
+    inv = fq_mul(inv, fq_mul(zz, zzz));
+    G1Affine a;
+    a.x = fq_mul(fqe_load(rec), fq_mul(ti, zzz));
+    a.y = fq_mul(fqe_load(rec + 48), fq_mul(ti, zz));
+    g1_store_affine(out + (i0 + k) * 96, a);
+  }
+}
+
+int g2_normalise_launch(Context* C, const uint8_t* in, const uint32_t* d_idx, size_t n, uint8_t* out);  // g2msm.hip
+
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
@@ -695,6 +862,88 @@ int encode_run(Context* C, int group, const uint8_t* d_src, size_t n, int compre
   return GM_OK;
 }
 
+// The first n survivors of m candidates, normalised, into a new array of n records (*d_out; nullptr on a shortfall).  A candidate
+// is on the curve with probability p = (q / 2^381)^k / 2 -- k = 1, 2 coordinates below q = 0.8125 x 2^381, half of all x give a
+// square -- = 0.406 for G1 and 0.330 for G2.  The stream is read in pieces of (n - have) x 5 / 2 (G1), x 13 / 4 (G2) + 64 candidates,
+// a little over 1 / p each, so that one piece is expected to finish the key and few roots are taken for nothing; and of at most 2^20
+// (the slots of a piece: 192 / 384 MB).  Of a piece's curve points only as many as the key still needs are cleared, in order; one
+// that clears to the identity (rule 3) makes the loop take the next ones.  *found counts the survivors among the candidates [0, *used).
+constexpr size_t PT_CAND_PIECE = (size_t)1 << 20;
+size_t cand_piece(int group, size_t want) { return group == 1 ? want / 2 * 5 + 64 : want / 4 * 13 + 64; }
+int candidates_run(Context* C, int group, const uint8_t* cand, size_t m, size_t n, uint8_t** d_out, size_t* used, size_t* found) {
+  const size_t csz = group == 1 ? 48 : 96, xsz = group == 1 ? 192 : G2_XYZZ_BYTES, asz = group == 1 ? 96 : G2_AFF_BYTES;
+  const unsigned block = group == 1 ? PT_BLOCK : PT_G2_BLOCK;
+  *d_out = nullptr;
+  *used = m;
+  *found = 0;
+  GM_MSM_LOCK(C);
+  const size_t cap = std::min({m, PT_CAND_PIECE, cand_piece(group, n)});
+  DevTmp out, stage, slots_, st_, idx_;
+  GM_HIP(dev_malloc(&out.p, n * asz));
+  GM_HIP(dev_malloc(&stage.p, cap * csz));
+  GM_HIP(dev_malloc(&slots_.p, cap * xsz));
+  GM_HIP(dev_malloc(&st_.p, cap));
+  GM_HIP(dev_malloc(&idx_.p, cap * 4));
+  uint8_t *slots = static_cast<uint8_t*>(slots_.p), *st = static_cast<uint8_t*>(st_.p);
+  uint32_t* idx = static_cast<uint32_t*>(idx_.p);
+  std::vector<uint8_t> h_st(cap);
+  std::vector<uint32_t> on_curve, good;
+  size_t pos = 0, have = 0;
+  while (have < n && pos < m) {
+    const size_t k = std::min({m - pos, cap, cand_piece(group, n - have)});
+    GM_HIP(hipMemcpyAsync(stage.p, cand + pos * csz, k * csz, hipMemcpyHostToDevice, C->stream));
+    if (group == 1)
+      hipLaunchKernelGGL(k_g1_cand_root, dim3((unsigned)((k + block - 1) / block)), dim3(block), 0, C->stream, static_cast<const uint8_t*>(stage.p), k, slots, st);
+    else
+      hipLaunchKernelGGL(k_g2_cand_root, dim3((unsigned)((k + block - 1) / block)), dim3(block), 0, C->stream, static_cast<const uint8_t*>(stage.p), k, slots, st);
+    GM_HIP(hipGetLastError());
+    GM_HIP(hipMemcpyAsync(h_st.data(), st, k, hipMemcpyDeviceToHost, C->stream));
+    GM_HIP(hipStreamSynchronize(C->stream));
+    on_curve.clear();
+    for (size_t j = 0; j < k; j++)
+      if (h_st[j] == PT_CAND_OK) on_curve.push_back((uint32_t)j);
+    size_t end = k;  // candidates of this piece that count as read
+    for (size_t at = 0; at < on_curve.size() && have < n;) {
+      const size_t c = std::min(on_curve.size() - at, n - have);
+      GM_HIP(hipMemcpyAsync(idx, on_curve.data() + at, c * 4, hipMemcpyHostToDevice, C->stream));
+      if (group == 1)
+        hipLaunchKernelGGL(k_g1_cand_clear, dim3((unsigned)((c + block - 1) / block)), dim3(block), 0, C->stream, slots, idx, c, st);
+      else
+        hipLaunchKernelGGL(k_g2_cand_clear, dim3((unsigned)((c + block - 1) / block)), dim3(block), 0, C->stream, slots, idx, c, st);
+      GM_HIP(hipGetLastError());
+      GM_HIP(hipMemcpyAsync(h_st.data(), st, c, hipMemcpyDeviceToHost, C->stream));
+      GM_HIP(hipStreamSynchronize(C->stream));
+      good.clear();
+      for (size_t j = 0; j < c; j++)
+        if (h_st[j] == PT_CAND_OK) good.push_back(on_curve[at + j]);
+      if (!good.empty()) {
+        uint8_t* dst = static_cast<uint8_t*>(out.p) + have * asz;
+        if (good.size() != c) GM_HIP(hipMemcpyAsync(idx, good.data(), good.size() * 4, hipMemcpyHostToDevice, C->stream));  // else idx holds them already
+        if (group == 1) {
+          const size_t groups = (good.size() + PT_NORM_K - 1) / PT_NORM_K;
+          hipLaunchKernelGGL(k_g1_gather_affine, dim3((unsigned)((groups + PT_BLOCK - 1) / PT_BLOCK)), dim3(PT_BLOCK), 0, C->stream, slots, idx, good.size(), dst);
+          GM_HIP(hipGetLastError());
+        } else {
+          int rc = g2_normalise_launch(C, slots, idx, good.size(), dst);
+          if (rc) return rc;
+        }
+        GM_HIP(hipStreamSynchronize(C->stream));  // idx, the slots and the host lists are rewritten from here on
+        have += good.size();
+        if (have == n) end = (size_t)good.back() + 1;
+      }
+      at += c;
+    }
+    pos += end;
+  }
+  *found = have;
+  if (have == n) {
+    *used = pos;
+    *d_out = static_cast<uint8_t*>(out.p);
+    out.p = nullptr;
+  }
+  return GM_OK;
+}
+
 }  // namespace
 }  // namespace gm
 
@@ -825,6 +1074,45 @@ int gm_g2_bases_to_bytes(uint64_t handle, size_t offset, size_t n, int compresse
   GM_CHECK(cap / (compressed ? 96 : 192) >= n, GM_EINVAL, "g2_bases_to_bytes: %zu bytes do not hold %zu points", cap, n);
   GM_MSM_LOCK(C);
   return encode_run(C, 2, b->d + offset * G2_AFF_BYTES, n, compressed, encoding, out);
+}
+
+int gm_g1_bases_from_candidates(const uint8_t* cand, size_t m, size_t n, uint64_t* handle, size_t* used, size_t* found) {
+  if (handle) *handle = 0;
+  GM_CTX();
+  GM_CHECK(handle && used && found && (cand || m == 0), GM_EINVAL, "g1_bases_from_candidates: null pointer");
+  GM_CHECK(m <= SIZE_MAX / 48 && n <= SIZE_MAX / 192, GM_EINVAL, "g1_bases_from_candidates: %zu candidates for %zu points do not fit a size_t", m, n);
+  auto b = std::make_unique<Bases>();
+  b->n = n;
+  *used = n == 0 ? 0 : m;
+  *found = 0;
+  int rc;
+  if (n && m) {
+    if ((rc = candidates_run(C, 1, cand, m, n, &b->d, used, found))) return rc;
+  }
+  if (*found < n) return GM_OK;  // a shortfall is a result: nothing stays registered
+  if ((rc = bases_build_phi(C, b.get()))) {
+    if (b->d) (void)raw_free(b->d);
+    return rc;
+  }
+  *handle = put_bases(std::move(b));  // as gm_g1_bases_register: no tables here
+  return GM_OK;
+}
+int gm_g2_bases_from_candidates(const uint8_t* cand, size_t m, size_t n, uint64_t* handle, size_t* used, size_t* found) {
+  if (handle) *handle = 0;
+  GM_CTX();
+  GM_CHECK(handle && used && found && (cand || m == 0), GM_EINVAL, "g2_bases_from_candidates: null pointer");
+  GM_CHECK(m <= SIZE_MAX / 96 && n <= SIZE_MAX / G2_XYZZ_BYTES, GM_EINVAL, "g2_bases_from_candidates: %zu candidates for %zu points do not fit a size_t", m, n);
+  auto b = std::make_unique<G2Bases>();
+  b->n = n;
+  *used = n == 0 ? 0 : m;
+  *found = 0;
+  if (n && m) {
+    int rc = candidates_run(C, 2, cand, m, n, &b->d, used, found);
+    if (rc) return rc;
+  }
+  if (*found < n) return GM_OK;
+  *handle = put_in(C, C->g2_bases, std::move(b));
+  return GM_OK;
 }
 
 int gm_crs_from_bases(uint64_t g1_handle, uint64_t g2_handle, uint64_t* crs) {

@@ -113,6 +113,33 @@ class G2Bases:
         capi.check(capi.load().gm_g2_bases_register(capi.ptr(bases), C.c_size_t(bases.shape[1] * 8), C.c_size_t(len(bases)), C.byref(h)))
         return cls(h.value, len(bases))
 
+    @classmethod
+    def fixed_base(cls, base_affine: np.ndarray, scalars_canonical: np.ndarray) -> "G2Bases":
+        """[s_i * base] generated on the device (gm_g2_fixed_base_register): base a 24-limb record, scalars (n, 4) canonical --
+        any 256-bit value, taken as that integer; a zero scalar gives the identity record"""
+        capi.ensure_init()
+        sc = capi.u64(scalars_canonical).reshape(-1, 4)
+        h = C.c_uint64()
+        capi.check(capi.load().gm_g2_fixed_base_register(capi.ptr(capi.u64(base_affine).reshape(24)), capi.ptr(sc), C.c_size_t(len(sc)), C.byref(h)))
+        return cls(h.value, len(sc))
+
+    @classmethod
+    def srs(cls, base_affine: np.ndarray, tau_canonical: np.ndarray, n: int) -> "G2Bases":
+        """powers_of_g2[i] = tau^i * g2 (src/kzg/time.rs:60-67), generated on the device (gm_g2_srs_register)"""
+        capi.ensure_init()
+        h = C.c_uint64()
+        capi.check(capi.load().gm_g2_srs_register(capi.ptr(capi.u64(base_affine).reshape(24)), capi.ptr(capi.u64(tau_canonical).reshape(4)), C.c_size_t(n),
+                                                  C.byref(h)))
+        return cls(h.value, n)
+
+    @classmethod
+    def from_candidates(cls, cand: bytes, n: int):
+        """gm_g2_bases_from_candidates: the first n surviving candidates (96 bytes each), cofactor-cleared on the device
+        -> (G2Bases or None on a shortfall, used, found)"""
+        from .points import bases_from_candidates
+
+        return bases_from_candidates(2, cand, n)
+
     def download(self, offset: int = 0, n: int | None = None) -> np.ndarray:
         n = self.n - offset if n is None else n
         out = np.empty((n, 24), dtype=np.uint64)

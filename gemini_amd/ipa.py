@@ -61,6 +61,83 @@ class Crs:
         finally:
             b1.free()
 
+    @classmethod
+    def from_scalars(cls, a_canonical, b_canonical, g1_affine=None, g2_affine=None) -> "Crs":
+        """g1s[i] = a_i g1, g2s[i] = b_i g2, both generated on the device (gm_g1_fixed_base_register, gm_g2_fixed_base_register).
+        FOR TESTS AND BENCHMARKS ONLY: whoever knows a and b knows every discrete logarithm of this CRS and can break the binding
+        of the commitments, and with it the soundness of the inner-product argument.  `Crs.new` draws points nobody has the logarithms of."""
+        from .g2 import generator
+        from .g2msm import G2Bases, g2_points_to_affine
+        from .kzg import g1_generator_mont
+        from .msm import G1Bases
+
+        g1 = g1_generator_mont() if g1_affine is None else g1_affine
+        g2 = g2_points_to_affine([generator()])[0] if g2_affine is None else g2_affine
+        b1 = G1Bases.fixed_base(g1, a_canonical)
+        try:
+            b2 = G2Bases.fixed_base(g2, b_canonical)
+            try:
+                return cls.from_bases(b1, b2)
+            finally:
+                b2.free()
+        finally:
+            b1.free()
+
+    @classmethod
+    def new(cls, seed: bytes, d: int) -> "Crs":
+        """`Crs::new(rng, d)` (ipa.rs:173-177) with a seed in the place of the rng: d points of each group whose logarithms nobody
+        knows, the survivors of the SHAKE-256 candidate stream of (seed, group) cleared of their cofactors on the device
+        (points.bases_from_seed).  The stream and the map from candidates to points are this package's own: no parity with the
+        draws of arkworks' `rand` is claimed."""
+        from .points import bases_from_seed
+
+        assert d >= 1
+        b1 = bases_from_seed(1, seed, d)
+        try:
+            b2 = bases_from_seed(2, seed, d)
+            try:
+                return cls.from_bases(b1, b2)
+            finally:
+                b2.free()
+        finally:
+            b1.free()
+
+    @classmethod
+    def _of(cls, handle: int) -> "Crs":
+        n1, n2 = C.c_size_t(), C.c_size_t()
+        capi.check(capi.load().gm_crs_len(C.c_uint64(handle), C.byref(n1), C.byref(n2)))
+        crs = cls.__new__(cls)
+        crs.handle, crs.n1, crs.n2 = handle, n1.value, n2.value
+        return crs
+
+    def truncate(self, rounds: int) -> "Crs":
+        """Crs::truncate (ipa.rs:191-196) as a NEW Crs: the first min(len, 2^rounds) points of each group; this one stays valid"""
+        h = C.c_uint64()
+        capi.check(capi.load().gm_crs_truncate(C.c_uint64(self.handle), C.c_size_t(rounds), C.byref(h)))
+        return self._of(h.value)
+
+    def halve(self) -> "Crs":
+        """Crs::halve (ipa.rs:198-203) as a new Crs: the first ceil(len / 2) points of each group"""
+        h = C.c_uint64()
+        capi.check(capi.load().gm_crs_halve(C.c_uint64(self.handle), C.byref(h)))
+        return self._of(h.value)
+
+    def fold(self, challenge_mont) -> "Crs":
+        """Crs::fold (ipa.rs:205-212) as a new Crs: g[i] = g[2i] + c g[2i+1] in both groups on the device, an odd tail against the
+        identity.  Groups of different lengths are refused (GM_EINVAL)."""
+        h = C.c_uint64()
+        capi.check(capi.load().gm_crs_fold(C.c_uint64(self.handle), capi.ptr(capi.u64(challenge_mont).reshape(4)), C.byref(h)))
+        return self._of(h.value)
+
+    def bases(self):
+        """gm_crs_to_bases: device copies of both arrays -> (G1Bases, G2Bases), the caller's to free; the inverse of from_bases"""
+        from .g2msm import G2Bases
+        from .msm import G1Bases
+
+        h1, h2 = C.c_uint64(), C.c_uint64()
+        capi.check(capi.load().gm_crs_to_bases(C.c_uint64(self.handle), C.byref(h1), C.byref(h2)))
+        return G1Bases(h1.value, self.n1), G2Bases(h2.value, self.n2)
+
     def check(self):
         """gm_crs_check: curve and subgroup over both arrays; a points.KeyCheckResult"""
         from .points import check_crs

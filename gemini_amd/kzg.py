@@ -47,11 +47,16 @@ class CommitterKey:
         ark_std::test_rng() is not reproducible without Rust): g, g2 default to the standard generators, or are the
         draws a reference run recorded (tools/refvectors)."""
         from . import g2 as G2
+        from .g2msm import G2Bases, g2_affine_to_points
 
         g = g1_generator_mont() if g_affine is None else g_affine
-        tau = sum(int(v) << (64 * i) for i, v in enumerate(np.asarray(tau_canonical, dtype=np.uint64).reshape(4)))
         g2 = G2.generator() if g2_affine is None else g2_affine
-        powers_of_g2 = [G2.mul(g2, pow(tau, i, R_MOD)) for i in range(max_eval_points + 1)]  # :60-67
+        # :60-67 -- tau^i g2 generated on the device (gm_g2_srs_register) and read back: the verifier's half lives on the host
+        key2 = G2Bases.srs(g2_records([g2])[0], tau_canonical, max_eval_points + 1)
+        try:
+            powers_of_g2 = g2_affine_to_points(key2.download())
+        finally:
+            key2.free()
         return cls(G1Bases.srs(g, tau_canonical, max_degree + 1), max_eval_points, powers_of_g2)
 
     @classmethod

@@ -143,6 +143,14 @@ class G1Bases:
 
         return g1_bases_to_bytes(self, compress, enc, offset, n)
 
+    @classmethod
+    def from_candidates(cls, cand: bytes, n: int):
+        """gm_g1_bases_from_candidates: the first n surviving candidates (48 bytes each), cofactor-cleared on the device
+        -> (G1Bases or None on a shortfall, used, found)"""
+        from .points import bases_from_candidates
+
+        return bases_from_candidates(1, cand, n)
+
     def free(self):
         if self.handle:
             capi.check(capi.load().gm_g1_bases_free(C.c_uint64(self.handle)))

@@ -150,6 +150,64 @@ def g2_bases_from_bytes(data: bytes, n: int, compress: bool, enc: int = 0, valid
     return (G2Bases(h.value, n) if res.ok else None), res
 
 
+# ---- points without a known logarithm ------------------------------------------------------------------------------------------------
+CANDIDATE_BYTES = {1: 48, 2: 96}
+CANDIDATE_DOMAIN = b"gemini_amd candidates v1"
+
+
+def bases_from_candidates(group: int, cand: bytes, n: int):
+    """gm_g1_bases_from_candidates / gm_g2_bases_from_candidates: `cand` holds m candidates of 48 (G1: x and, in bit 383, the choice
+    of y) or 96 bytes (G2: x.c0 | x.c1); the first n whose x is < q and on the curve and whose cofactor-cleared point is not the
+    identity are registered, in candidate order.  -> (G1Bases / G2Bases, or None on a shortfall; used; found): `used` is the index
+    after the n-th survivor (m on a shortfall), `found` the survivors among the candidates before it."""
+    capi.ensure_init()
+    size = CANDIDATE_BYTES[group]
+    assert len(cand) % size == 0, f"{len(cand)} bytes are no whole number of {size}-byte candidates"
+    m = len(cand) // size
+    buf = np.frombuffer(bytes(cand), dtype=np.uint8)
+    h, used, found = C.c_uint64(0), C.c_size_t(0), C.c_size_t(0)
+    fn = capi.load().gm_g1_bases_from_candidates if group == 1 else capi.load().gm_g2_bases_from_candidates
+    capi.check(fn(capi.ptr(buf) if m else None, C.c_size_t(m), C.c_size_t(n), C.byref(h), C.byref(used), C.byref(found)))
+    assert (h.value != 0) == (found.value >= n), "from_candidates: a handle exactly when n candidates survived"
+    return ((G1Bases if group == 1 else G2Bases)(h.value, n) if h.value else None), used.value, found.value
+
+
+def candidate_stream(seed: bytes, group: int, start: int, count: int) -> bytes:
+    """candidates [start, start + count) of the stream of (seed, group): SHAKE-256 over the domain string, the group byte and the
+    seed, cut into 48- / 96-byte candidates.  This stream is this package's own convention: NO parity with the draws of an
+    arkworks `rand` is claimed (README, "Unpinned conventions")."""
+    import hashlib
+
+    size = CANDIDATE_BYTES[group]
+    return hashlib.shake_256(CANDIDATE_DOMAIN + bytes([group]) + bytes(seed)).digest((start + count) * size)[start * size:]
+
+
+def bases_from_seed(group: int, seed: bytes, n: int):
+    """n points of G1 / G2 whose logarithms nobody knows, from the candidate stream of `seed`: 4 n + 64 candidates first (about
+    half of all x are on the curve), and the same stream continued from `used` on a shortfall"""
+    if n == 0:
+        return bases_from_candidates(group, b"", 0)[0]
+    parts, start, count = [], 0, 4 * n + 64
+    try:
+        while True:
+            got = sum(len(p) for p in parts)
+            b, used, found = bases_from_candidates(group, candidate_stream(seed, group, start, count), n - got)
+            if b is not None:
+                parts.append(b)
+                break
+            if found:  # keep what this stretch gave: the survivors of [start, start + count), all of them
+                part, _, _ = bases_from_candidates(group, candidate_stream(seed, group, start, count), found)
+                parts.append(part)
+            start += used
+        if len(parts) == 1:
+            return parts.pop()
+        rec = np.concatenate([p.download() for p in parts])  # (a shortfall of 4 n + 64 candidates has probability ~2^-n: not a hot path)
+        return (G1Bases if group == 1 else G2Bases).register(rec)
+    finally:
+        for p in parts:
+            p.free()
+
+
 def _to_bytes(fn, handle: int, size: int, compress: bool, offset: int, n: int, enc: int) -> bytes:
     out = np.zeros(n * size, dtype=np.uint8)
     capi.check(fn(C.c_uint64(handle), C.c_size_t(offset), C.c_size_t(n), C.c_int(int(bool(compress))), C.c_int(int(enc)), capi.ptr(out) if n else None,

@@ -1120,6 +1120,41 @@ int gm_debug_fq2_sqrt(const uint64_t* a_mont, size_t n, uint64_t* root_mont, uin
 int gm_g1_powers_check(uint64_t handle, size_t offset, size_t n, const uint64_t g2_affine[24], const uint64_t tau_g2_affine[24],
                        const uint64_t rho_mont[4], int* ok);
 
+/* ---- key generation: G2 fixed-base keys, points without a known logarithm, Crs operations (g2msm.hip, points.hip, ipa.hip) --------
+ * The G2 twins of gm_g1_fixed_base_register / gm_g1_srs_register: out[i] = scalars[i] * base, resp. tau^i * base, i < n, through a
+ * table of 32 windows x 256 affine multiples of the base, one lane per scalar (at most 32 mixed additions over Fq2), normalised by
+ * Montgomery's trick over Fq2 -- one Fq inversion per 8 points -- in slabs of at most 2^22 points.  base_affine: a 192-byte record
+ * as gm_g2_bases_register takes it.  Scalars are canonical, n x 4 u64 on the host; ANY 256-bit value is accepted and multiplies as
+ * that integer.  A zero scalar gives the all-zero identity record, n = 0 an empty handle.  The handle is one of
+ * gm_g2_bases_register.  No tables are kept: G2 MSMs have none. */
+int gm_g2_fixed_base_register(const uint64_t base_affine[24], const uint64_t* scalars, size_t n, uint64_t* handle);
+int gm_g2_srs_register(const uint64_t base_affine[24], const uint64_t tau[4], size_t n, uint64_t* handle);
+/* Points whose discrete logarithms nobody knows (what Crs::new(rng, d) draws, ipa.rs:173-177): the first n of m CANDIDATES that
+ * survive, in candidate order, cofactor-cleared and normalised on the device.
+ *   G1 candidate   48 bytes, one little-endian integer: bits 0 .. 380 are x, bits 381 and 382 are ignored, bit 383 chooses the
+ *                  larger of y and -y (ark-ff's order: y > q - y as integers)
+ *   G2 candidate   96 bytes, x.c0 | x.c1, each 48 bytes masked the same way; the choice bit is bit 383 of the c1 half, the order
+ *                  that of Fq2 (c1 first, c0 when c1 = 0)
+ * A candidate is SKIPPED when, in this order, (1) a coordinate is >= q, (2) x^3 + 4 -- on the twist x^3 + 4 (1 + u) -- is no
+ * square, (3) the cleared point is the identity.  Clearing: G1 P -> [1 - x] P = [|x|] P + P; G2 P -> [x^2 - x - 1] P +
+ * [x - 1] psi(P) + psi^2([2] P) (Budroni-Pintore), x = -0xd201000000010000.  *found: the survivors among the candidates read;
+ * *used: the index after the n-th survivor, or m -- a caller continues its stream from there.  Fewer than n survivors is a
+ * result, not an error: GM_OK, *handle = 0, *found < n.  *handle = 0 is written first.  n = 0 gives an empty handle and
+ * *used = 0.  The handles are those of gm_g1_bases_register (no tables built) / gm_g2_bases_register.
+ * NO parity with an arkworks `rand` is claimed: the candidate format and the skip rules are this library's own. */
+int gm_g1_bases_from_candidates(const uint8_t* cand, size_t m, size_t n, uint64_t* handle, size_t* used, size_t* found);
+int gm_g2_bases_from_candidates(const uint8_t* cand, size_t m, size_t n, uint64_t* handle, size_t* used, size_t* found);
+/* Crs::truncate / halve / fold (ipa.rs:191-212).  Each call returns a NEW handle (*out = 0 is written first); the input stays the
+ * caller's.  truncate: the first min(len, 2^rounds) points of each group; halve: the first ceil(len / 2).  fold: g[i] = g[2i] +
+ * c g[2i+1] in both groups (the split-fold kernels of the module provers), an odd tail folds against the identity; c in Montgomery
+ * form.  The reference indexes g2s[2i] over g1s' length: n1 != n2 is GM_EINVAL. */
+int gm_crs_truncate(uint64_t crs, size_t rounds, uint64_t* out);
+int gm_crs_halve(uint64_t crs, uint64_t* out);
+int gm_crs_fold(uint64_t crs, const uint64_t challenge_mont[4], uint64_t* out);
+/* The inverse of gm_crs_from_bases: device copies of both arrays as a G1 and a G2 bases handle (either pointer may be null: that
+ * half is not copied).  Both handles are written 0 first. */
+int gm_crs_to_bases(uint64_t crs, uint64_t* g1_handle, uint64_t* g2_handle);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,11 @@
 //   to_bytes}, Crs::{from_bases, check}, VerifierKey::check, check_points of SnarkProof / PsnarkProof / InnerProductProof
 //                                                           deserialize_with_mode(.., Validate::Yes) of ark-ec for whole keys, on the
 //                                                           device (gemini_amd/csrc/points.hip); the powers check has no counterpart
+//   gm::G2Bases::{fixed_base, srs}                          the powers_of_g2 loop of CommitterKey::new (src/kzg/time.rs:60-67)
+//   gm::CommitterKey::from_candidates, G2Bases::from_candidates, Crs::{from_scalars, from_candidates, truncate, halve, fold, bases}
+//                                                           Crs::{new, truncate, halve, fold} (src/herring/ipa.rs:173-212); the points
+//                                                           come from candidate bytes, not from an arkworks rng (no SHAKE here: the
+//                                                           caller brings the bytes)
 #pragma once
 #include <array>
 #include <cstdint>
@@ -372,6 +377,27 @@ class CommitterKey {
     k.n_ = n;
     return std::optional<CommitterKey>(std::move(k));
   }
+  // n points of G1 whose logarithms nobody knows: the first n of the 48-byte candidates in `cand` that survive, cofactor-cleared on
+  // the device (gm_g1_bases_from_candidates; the header has the candidate format).  *used: the index after the n-th survivor, or
+  // the number of candidates; *found: the survivors before it.  No key on a shortfall (found < n).  No tables are built.
+  static std::optional<CommitterKey> from_candidates(const std::vector<uint8_t>& cand, size_t n, size_t* used = nullptr, size_t* found = nullptr) {
+    if (cand.size() % 48) throw Error(GM_EINVAL, "CommitterKey::from_candidates: a G1 candidate is 48 bytes");
+    CommitterKey k;
+    size_t u = 0, f = 0;
+    check(gm_g1_bases_from_candidates(cand.data(), cand.size() / 48, n, &k.h_, &u, &f));
+    if (used) *used = u;
+    if (found) *found = f;
+    if ((f >= n) != (k.h_ != 0)) throw Error(GM_ESTATE, "CommitterKey::from_candidates: the library hands out a handle exactly when n candidates survive");
+    if (!k.h_) return std::nullopt;
+    k.n_ = n;
+    return std::optional<CommitterKey>(std::move(k));
+  }
+  // 96-byte records x | y (the identity all zero), 12 words each
+  std::vector<uint64_t> download(size_t offset, size_t n) const {
+    std::vector<uint64_t> out(n * 12);
+    check(gm_g1_bases_download(h_, offset, n, out.data()));
+    return out;
+  }
   PointCheck check_points() const { return check_g1_bases(h_, 0, n_); }  // every power on the curve and in G1
   // the canonical encodings of powers [offset, offset + n), 48 / 96 bytes each, made on the device (gm_g1_bases_to_bytes)
   std::vector<uint8_t> to_bytes(bool compressed, int encoding, size_t offset, size_t n) const {
@@ -422,6 +448,7 @@ class CommitterKey {
   }
 
  private:
+  friend class Crs;  // Crs::bases hands out device copies of its arrays
   CommitterKey() = default;
   uint64_t h_ = 0;
   size_t n_ = 0;  // powers of the WHOLE key
@@ -544,6 +571,34 @@ class G2Bases {
     return out;
   }
   std::vector<uint8_t> to_bytes(bool compressed, int encoding = 0) const { return to_bytes(compressed, encoding, 0, n_); }
+  // [s_i base], generated on the device (gm_g2_fixed_base_register): base a 192-byte record, scalars canonical -- any 256-bit value,
+  // taken as that integer; a zero scalar gives the identity record
+  static G2Bases fixed_base(const uint64_t base_affine[24], const std::vector<BigInt>& scalars) {
+    G2Bases b;
+    check(gm_g2_fixed_base_register(base_affine, scalars.empty() ? nullptr : scalars[0].data(), scalars.size(), &b.h_));
+    b.n_ = scalars.size();
+    return b;
+  }
+  // tau^i base, i < n: the powers_of_g2 of CommitterKey::new (src/kzg/time.rs:60-67), tau canonical (gm_g2_srs_register)
+  static G2Bases srs(const uint64_t base_affine[24], const BigInt& tau, size_t n) {
+    G2Bases b;
+    check(gm_g2_srs_register(base_affine, tau.data(), n, &b.h_));
+    b.n_ = n;
+    return b;
+  }
+  // the G2 twin of CommitterKey::from_candidates: 96-byte candidates x.c0 | x.c1 (gm_g2_bases_from_candidates)
+  static std::optional<G2Bases> from_candidates(const std::vector<uint8_t>& cand, size_t n, size_t* used = nullptr, size_t* found = nullptr) {
+    if (cand.size() % 96) throw Error(GM_EINVAL, "G2Bases::from_candidates: a G2 candidate is 96 bytes");
+    G2Bases b;
+    size_t u = 0, f = 0;
+    check(gm_g2_bases_from_candidates(cand.data(), cand.size() / 96, n, &b.h_, &u, &f));
+    if (used) *used = u;
+    if (found) *found = f;
+    if ((f >= n) != (b.h_ != 0)) throw Error(GM_ESTATE, "G2Bases::from_candidates: the library hands out a handle exactly when n candidates survive");
+    if (!b.h_) return std::nullopt;
+    b.n_ = n;
+    return std::optional<G2Bases>(std::move(b));
+  }
   // 192-byte records x.c0 | x.c1 | y.c0 | y.c1 (the identity all zero), 24 words each
   std::vector<uint64_t> download(size_t offset, size_t n) const {
     std::vector<uint64_t> out(n * 24);
@@ -575,6 +630,7 @@ class G2Bases {
   }
 
  private:
+  friend class Crs;
   G2Bases() = default;
   uint64_t h_ = 0;
   size_t n_ = 0;
@@ -750,6 +806,54 @@ class Crs {  // ipa.rs:62-66,172-213: G1 and G2 points resident in HBM
     Crs c;
     gm::check(gm_crs_from_bases(g1s.handle(), g2s.handle(), &c.h_));
     return c;
+  }
+  // g1s[i] = a_i g1, g2s[i] = b_i g2 (canonical scalars), generated on the device.  FOR TESTS AND BENCHMARKS ONLY: whoever knows a
+  // and b knows every logarithm of this CRS and can break the binding of its commitments; from_candidates is the one to use
+  static Crs from_scalars(const uint64_t g1_affine[12], const std::vector<BigInt>& a, const uint64_t g2_affine[24], const std::vector<BigInt>& b) {
+    CommitterKey k1;
+    gm::check(gm_g1_fixed_base_register(g1_affine, a.empty() ? nullptr : a[0].data(), a.size(), &k1.h_));
+    k1.n_ = a.size();
+    return from_bases(k1, G2Bases::fixed_base(g2_affine, b));
+  }
+  // `Crs::new(rng, d)` (ipa.rs:173-177) with candidate bytes in the place of the rng: the first d survivors of each stream
+  // (CommitterKey::from_candidates, G2Bases::from_candidates); no Crs when either stream runs short
+  static std::optional<Crs> from_candidates(const std::vector<uint8_t>& g1_cand, const std::vector<uint8_t>& g2_cand, size_t d) {
+    std::optional<CommitterKey> k1 = CommitterKey::from_candidates(g1_cand, d);
+    if (!k1) return std::nullopt;
+    std::optional<G2Bases> k2 = G2Bases::from_candidates(g2_cand, d);
+    if (!k2) return std::nullopt;
+    return std::optional<Crs>(from_bases(*k1, *k2));
+  }
+  std::pair<size_t, size_t> len() const {
+    std::pair<size_t, size_t> n{0, 0};
+    gm::check(gm_crs_len(h_, &n.first, &n.second));
+    return n;
+  }
+  // Crs::truncate / halve / fold (ipa.rs:191-212), each as a NEW Crs: this one stays valid
+  Crs truncate(size_t rounds) const {
+    Crs c;
+    gm::check(gm_crs_truncate(h_, rounds, &c.h_));
+    return c;
+  }
+  Crs halve() const {
+    Crs c;
+    gm::check(gm_crs_halve(h_, &c.h_));
+    return c;
+  }
+  Crs fold(const Fr& challenge) const {  // groups of different lengths are refused (GM_EINVAL)
+    Crs c;
+    gm::check(gm_crs_fold(h_, challenge.data(), &c.h_));
+    return c;
+  }
+  // device copies of both arrays (gm_crs_to_bases), the inverse of from_bases
+  std::pair<CommitterKey, G2Bases> bases() const {
+    const std::pair<size_t, size_t> n = len();
+    CommitterKey k1;
+    G2Bases k2;
+    gm::check(gm_crs_to_bases(h_, &k1.h_, &k2.h_));
+    k1.n_ = n.first;
+    k2.n_ = n.second;
+    return std::pair<CommitterKey, G2Bases>(std::move(k1), std::move(k2));
   }
   KeyCheck check() const {  // curve and subgroup over both arrays (gm_crs_check)
     KeyCheck r;
