@@ -1743,7 +1743,7 @@ int gm_sc_set_herring(uint64_t handle, int on) {
   GM_SC(S, handle, "sc_set_herring");
   return sc_set_herring(S, on);
 }
-// the module provers (herring.hip): one handle table for the three kinds; a handle of another module is unknown to this one's calls
+// the module provers (herring.hip): one handle table for the four kinds; a handle of another module is unknown to this one's calls
 static HerringProver* find_herring(Context* C, uint64_t h, HerringModule module) {
   std::lock_guard<std::mutex> lk(C->mu);
   auto it = C->herring.find(h);
@@ -2041,6 +2041,46 @@ int gm_hp_final(uint64_t handle, uint64_t f0_jac[18], uint64_t g0_jac[36], int* 
 int gm_hp_free(uint64_t handle) {
   GM_CTX();
   return herring_free(C, handle, HERRING_P, "hp_free");
+}
+
+// ---- GtModule: GT multi-exponentiation on the device (pairing.hip) and the herring GtModule prover ----------------
+int gm_gt_multi_pow(const uint64_t* x, size_t n, const uint64_t* scalars_canonical, uint64_t out_gt[72]) {
+  GM_CTX();
+  GM_CHECK(out_gt != nullptr && ((x != nullptr && scalars_canonical != nullptr) || n == 0), GM_EINVAL, "gt_multi_pow: null pointer");
+  if (n == 0) return gm_gt_one(out_gt);
+  return gt_multi_pow_host(C, x, scalars_canonical, n, out_gt);
+}
+int gm_hgt_new(const uint64_t* f_gt, size_t nf, const uint64_t* g_mont, size_t ng, const uint64_t twist_mont[4], uint64_t* handle) {
+  GM_CTX();
+  GM_CHECK(f_gt && g_mont && twist_mont && handle, GM_EINVAL, "hgt_new: null pointer");
+  return herring_create(C, HERRING_GT, f_gt, 576, nf, g_mont, 32, ng, twist_mont, handle);
+}
+int gm_hgt_round(uint64_t handle, const uint64_t* challenge_or_null, uint64_t a_gt[72], uint64_t b_gt[72], int* has_msg) {
+  GM_CTX();
+  GM_HERRING(H, handle, GT, "hgt_round");
+  GM_CHECK(a_gt && b_gt && has_msg, GM_EINVAL, "hgt_round: null pointer");
+  return herring_round(C, H, challenge_or_null, a_gt, b_gt, has_msg);
+}
+int gm_hgt_fold(uint64_t handle, const uint64_t challenge_mont[4]) {
+  GM_CTX();
+  GM_HERRING(H, handle, GT, "hgt_fold");
+  GM_CHECK(challenge_mont != nullptr, GM_EINVAL, "hgt_fold: null pointer");
+  return herring_fold(C, H, challenge_mont);
+}
+int gm_hgt_rounds(uint64_t handle, size_t* tot_rounds, size_t* round) {
+  GM_CTX();
+  GM_HERRING(H, handle, GT, "hgt_rounds");
+  return herring_rounds(H, tot_rounds, round);
+}
+int gm_hgt_final(uint64_t handle, uint64_t f0_gt[72], uint64_t g0_mont[4], int* has) {
+  GM_CTX();
+  GM_HERRING(H, handle, GT, "hgt_final");
+  GM_CHECK(f0_gt && g0_mont && has, GM_EINVAL, "hgt_final: null pointer");
+  return herring_final(C, H, f0_gt, g0_mont, has);
+}
+int gm_hgt_free(uint64_t handle) {
+  GM_CTX();
+  return herring_free(C, handle, HERRING_GT, "hgt_free");
 }
 
 // ---- herring's inner-product argument: Crs, Vrs, InnerProductProof (ipa.hip) --------------------------------

@@ -151,8 +151,8 @@ struct SpaceProver {
 };
 
 // herring TimeProver over a bilinear module (src/herring/time_prover.rs:42-137; herring.hip): f is the Lhs vector, g the Rhs vector,
-// each an Fr vector (32 B, a block of the vector pool), affine G1 points (96 B) or affine G2 points (192 B)
-enum HerringModule { HERRING_G1 = 0, HERRING_G2, HERRING_P };  // G1 x F -> G1, F x G2 -> G2, G1 x G2 -> GT (module.rs:60-125)
+// each an Fr vector (32 B, a block of the vector pool), affine G1 points (96 B), affine G2 points (192 B) or GT elements (576 B)
+enum HerringModule { HERRING_G1 = 0, HERRING_G2, HERRING_P, HERRING_GT };  // G1 x F -> G1, F x G2 -> G2, G1 x G2 -> GT, GT x F -> GT (module.rs:49-125)
 struct HerringProver {
   HerringModule module = HERRING_G1;
   uint8_t* f[2] = {nullptr, nullptr};
@@ -218,6 +218,8 @@ struct PairingWorkspace {
   DevBuf seg_tab;
   uint64_t* host_seg = nullptr;
   size_t host_seg_cap = 0;  // in GT elements
+  // GtModule (k_gt_multi_pow, k_gt_split_fold): the window table x, x^2, x^3 of every lane of a launch, [block][entry][limb][lane]
+  DevBuf gt_tab;
 };
 // ChunkedPippenger / msm_chunks over HOST-resident pairs (src/kzg/msm/stream_pippenger.rs:209-272, src/kzg/space.rs:22-55):
 // the device holds two chunks; chunk i + 1 is copied in while the MSM of chunk i runs (msm.hip: msm_stream_*)
@@ -534,6 +536,21 @@ struct PairProduct {
 int miller_products(Context* C, const PairProduct* prods, size_t S, gmh::Fq12* out);
 // Miller product -> GT: conjugation (the loop parameter is negative), then the one final exponentiation
 void pairing_finish(const gmh::Fq12& miller, uint64_t out_gt[72]);
+
+// GtModule (pairing.hip): GT elements on the device are 576-byte records, 12 Fq in tower order in the device form of g1.cuh
+struct GtSpan {  // n terms x[first_x + step_x i] ^ e[first_e + step_e i]: 576-byte elements, 32-byte exponents; ranges checked by the caller
+  const uint8_t* x = nullptr;
+  const uint8_t* e = nullptr;
+  int64_t first_x = 0, step_x = 1, first_e = 0, step_e = 1;
+  size_t n = 0;
+};
+// The product over three spans in one launch, no final exponentiation and no conjugation.  mont: the exponents are Fr in Montgomery
+// form (the canonical integer is taken on the device); else 8 canonical words as they are, not reduced.  Caller holds the MSM lock.
+int gt_multi_pow(Context* C, const GtSpan spans[3], int mont, gmh::Fq12* out);
+int gt_multi_pow_host(Context* C, const uint64_t* x, const uint64_t* scalars_canonical, size_t n, uint64_t out_gt[72]);
+int gt_from_host(Context* C, const uint64_t* x, size_t n, uint8_t** d);  // n x 72 limbs -> a dev_malloc block of device records
+// out[i] = in[2i] in[2i+1]^s (an odd tail is in[2i]), s at d_s8 (canonical, 8 x u32), on C->stream; caller holds the MSM lock
+int gt_split_fold_launch(Context* C, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out);
 
 // herring module provers (herring.hip).  f / g are host arrays: Fr vectors in Montgomery form (the stride is ignored) or point
 // records of f_stride / g_stride bytes; messages and final foldings have the module's limb counts (include/gemini_hip.h).

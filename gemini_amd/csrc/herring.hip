@@ -1,12 +1,12 @@
-// herring's TimeProver over a bilinear module (src/herring/time_prover.rs:42-137), stated once for G1Module, G2Module and PModule
-// (src/herring/module.rs:60-125).  FModule rides the field sumcheck kernel (fr.hip: sc_set_herring).
+// herring's TimeProver over a bilinear module (src/herring/time_prover.rs:42-137), stated once for G1Module, G2Module, PModule and
+// GtModule (src/herring/module.rs:49-125).  FModule rides the field sumcheck kernel (fr.hip: sc_set_herring).
 //
 // The prover keeps the Lhs vector f and the Rhs vector g on the device, each in two ping-pong buffers:
 //   fold(r)          f'[i] = f[2i] + (r twist) f[2i+1], g'[i] = g[2i] + r g[2i+1] (an odd tail folds against zero), twist <- twist^2
 //   next_message(c)  an optional fold, then a = ip(f_even, g_even), b = ip(f_even, g_odd) + ip(f_odd, g_even); ip zips, so the
 //                    shorter side ends a product.  After log2(min(len)) messages the answer is "no message"
 //   final_foldings   (f[0], g[0]) once the last round is behind
-// A SIDE says how a vector of its element type is held, folded and read out -- Fr, affine G1, affine G2 -- and a MODULE is two
+// A SIDE says how a vector of its element type is held, folded and read out -- Fr, affine G1, affine G2, GT -- and a MODULE is two
 // sides and its inner product `ip`: the only per-module code.  The engines (msm.hip, g2msm.hip, pairing.hip) and the fold kernels
 // stay where they are.
 //
@@ -80,9 +80,20 @@ static int g2_split_fold(Context* C, const uint8_t* in, size_t n, const uint64_t
 static void g1_read0(const uint64_t* elem, uint64_t* out) { gmh::g1_affine_to_jac_dev(elem).to_limbs(out); }
 static void g2_read0(const uint64_t* elem, uint64_t* out) { gmh::g2_affine_to_jac_dev(elem).to_limbs(out); }
 
+// GT elements: host records of 72 x u64, 576-byte device records (gt.cuh); "+" is the product, the fold out[i] = f[2i] f[2i+1]^s
+static int gt_upload(Context* C, const void* host, size_t, size_t n, uint8_t** d, size_t* cap) {
+  *cap = 0;
+  return gt_from_host(C, static_cast<const uint64_t*>(host), n, d);
+}
+static int gt_split_fold(Context* C, const uint8_t* in, size_t n, const uint64_t*, const uint32_t* d_s_canon, uint8_t* out) {
+  return gt_split_fold_launch(C, in, n, d_s_canon, out);
+}
+static void gt_read0(const uint64_t* elem, uint64_t* out) { gmh::Fq12::from_device(elem).to_limbs(out); }
+
 static const HerringSide FR_SIDE = {32, fr_upload, fr_alloc, fr_release, fr_split_fold, fr_read0};
 static const HerringSide G1_SIDE = {96, g1_upload, point_alloc<96>, point_release, g1_split_fold, g1_read0};
 static const HerringSide G2_SIDE = {192, g2_upload, point_alloc<192>, point_release, g2_split_fold, g2_read0};
+static const HerringSide GT_SIDE = {576, gt_upload, point_alloc<576>, point_release, gt_split_fold, gt_read0};
 
 // a vector where the prover keeps it: a host vector goes through the side's upload, a packed device vector (the CRS of ipa.hip) is copied
 static int side_put(Context* C, const HerringSide* S, const void* src, size_t stride, size_t n, bool on_device, uint8_t** d, size_t* cap) {
@@ -165,18 +176,43 @@ static int p_message(Context* C, HerringProver* H, const HerringZip& z, uint64_t
   return GM_OK;
 }
 
+// GtModule::ip is a multi-exponentiation (module.rs:49-58, the default ip; GT is written multiplicatively): the exponents are the
+// canonical integers of the Fr side, read strided and taken out of Montgomery form by the kernel itself -- no compacted copy --
+// and b is ONE launch over both halves
+static int gt_message(Context* C, HerringProver* H, const HerringZip& z, uint64_t* a_gt, uint64_t* b_gt) {
+  GM_MSM_LOCK(C);
+  GtSpan ee, eo, oe;
+  ee.x = eo.x = oe.x = H->f[H->cur];
+  ee.e = eo.e = oe.e = H->g[H->cur];
+  ee.step_x = ee.step_e = eo.step_x = eo.step_e = oe.step_x = oe.step_e = 2;
+  ee.n = z.ee;
+  eo.first_e = 1;
+  eo.n = z.eo;
+  oe.first_x = 1;
+  oe.n = z.oe;
+  const GtSpan sa[3] = {ee, GtSpan(), GtSpan()}, sb[3] = {eo, oe, GtSpan()};
+  gmh::Fq12 fa, fb;
+  int rc;
+  if ((rc = gt_multi_pow(C, sa, 1, &fa))) return rc;
+  if ((rc = gt_multi_pow(C, sb, 1, &fb))) return rc;
+  fa.to_limbs(a_gt);
+  fb.to_limbs(b_gt);
+  return GM_OK;
+}
+
 struct HerringModuleDesc {
   const char* name;
   const HerringSide *lhs, *rhs;
   int (*message)(Context* C, HerringProver* H, const HerringZip& z, uint64_t* a, uint64_t* b);
   // Two differences between the modules are kept as they were found; making them uniform would change behaviour.
-  size_t tmp_slots;   // compacted copies of halves of the Fr side that `message` builds in H->tmp: three for G1, two for G2, none for P
+  size_t tmp_slots;   // compacted copies of halves of the Fr side that `message` builds in H->tmp: three for G1, two for G2, none for P and Gt
   bool ends_for_good;  // P only: after the call that answered "no message", round and fold are sequence errors (GM_ESTATE)
 };
 static const HerringModuleDesc MODULES[] = {  // indexed by HerringModule
     {"G1", &G1_SIDE, &FR_SIDE, g1_message, 3, false},
     {"G2", &FR_SIDE, &G2_SIDE, g2_message, 2, false},
     {"P", &G1_SIDE, &G2_SIDE, p_message, 0, true},
+    {"Gt", &GT_SIDE, &FR_SIDE, gt_message, 0, false},
 };
 
 // ---- the prover ---------------------------------------------------------------------------------------------------------
@@ -231,6 +267,7 @@ static int fold_locked(Context* C, HerringProver* H, const uint64_t r[4]) {
   if ((rc = M.lhs->split_fold(C, H->f[H->cur], H->nf, mont[0], C->msm.misc.as<uint32_t>(), H->f[H->cur ^ 1]))) return rc;
   if ((rc = M.rhs->split_fold(C, H->g[H->cur], H->ng, mont[1], C->msm.misc.as<uint32_t>() + 8, H->g[H->cur ^ 1]))) return rc;
   GM_HIP(hipStreamSynchronize(C->stream));  // `mont` and `canon` are read by the copies until here
+  C->prof.collect();                        // the GT fold books its launch (gt_split_fold_launch)
   H->cur ^= 1;
   H->nf = (H->nf + 1) / 2;
   H->ng = (H->ng + 1) / 2;
@@ -272,7 +309,7 @@ int herring_final(Context* C, HerringProver* H, uint64_t* f0, uint64_t* g0, int*
     *has = 0;
     return GM_OK;
   }
-  uint64_t ef[24], eg[24];
+  uint64_t ef[72], eg[72];  // the largest element: GT, 576 bytes
   GM_HIP(hipMemcpyAsync(ef, H->f[H->cur], M.lhs->elem, hipMemcpyDeviceToHost, C->stream));
   GM_HIP(hipMemcpyAsync(eg, H->g[H->cur], M.rhs->elem, hipMemcpyDeviceToHost, C->stream));
   GM_HIP(hipStreamSynchronize(C->stream));

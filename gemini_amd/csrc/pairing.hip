@@ -1,4 +1,5 @@
 // The BLS12-381 pairing on the device: multi-Miller loop and GT product reduction (gfx950); the herring PModule prover of herring.hip calls them.
+// Also here, on the same LDS parking and block product: GtModule's kernels (k_gt_multi_pow, k_gt_split_fold; "GtModule" below).
 //
 // Replaces `P::multi_pairing` as PModule::ip calls it (src/herring/module.rs:60-79: G1 x G2 -> GT), i.e. the messages of
 // TimeProver<PModule> (src/herring/time_prover.rs:91-123, two such provers per round of InnerProductProof::new,
@@ -188,6 +189,121 @@ __global__ __launch_bounds__(PAIR_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1
   if (lane == 0) fq12_store(out + (size_t)blockIdx.x * GT_BYTES, gt_lds_load(sh, 0));
 }
 
+// ---- GtModule: powers of GT elements (GT x Fr -> GT, src/herring/module.rs; ip = prod x_i^e_i) --------------------------------
+// One lane per element, acc <- x^e for the 256-bit integer e as given (not reduced mod r), plain fq12_sqr / fq12_mul on any 12
+// reduced coefficients: the value of gmh::Fq12::pow.  The exponent is walked in fixed windows of GT_WINDOW bits from the top:
+// GT_WINDOW squarings, then ONE product by table[digit] with table[0] = 1 selected in registers, so the 64 lanes of a wave run
+// the same instructions whatever their exponents are.  The accumulator is parked in LDS as k_miller parks f; the table x, x^2,
+// x^3 of a lane is a [limb][lane] slice of a device workspace (PairingWorkspace::gt_tab), read coalesced.
+// GT_WINDOW = 2: 256 squarings x 36 + 128 products x 54 + 108 for the table = 16 236 Fq products per lane.  A window of 4 would
+// take 256 x 36 + 64 x 54 + 756 = 13 428 (-17 %) for a table of 15 entries, 8640 B per lane instead of 1728 -- at 2^14 elements
+// 141 MB instead of 28 MB of workspace that the table build writes and the loop reads back with per-lane entry indices -- and the
+// loop body is the same two operands of 144 registers either way (profiles/gt_module_kernel_resources.txt: the body spills as
+// k_gt_reduce's product does).  Measured, the kernel runs at k_miller's time per Fq product (profiles/gt_module.md: 26.6 ms per
+// launch), so the wider window would buy its 17 % and nothing else, ~4.5 ms per launch; the narrow one is kept for its footprint.
+constexpr int GT_WINDOW = 2;
+constexpr int GT_TABLE = (1 << GT_WINDOW) - 1;                      // entries per lane: x^1 .. x^(2^w - 1)
+constexpr size_t GT_TAB_BLOCK = (size_t)GT_TABLE * GT_WORDS * PAIR_BLOCK;  // words of table per block
+static_assert(256 % GT_WINDOW == 0 && GT_WINDOW < 32, "the window walks 8 x 32-bit words");
+
+// table[d] of the lane, 1 for d = 0 (tab: the block's slice, entry t = x^(t+1) at tab + t * GT_WORDS * PAIR_BLOCK)
+GM_DEV Fq12 gt_tab_load(const uint32_t* tab, int lane, uint32_t d) {
+  const Fq12 one = fq12_one();
+  const FqE* o = reinterpret_cast<const FqE*>(&one);
+  const uint32_t* p = tab + (size_t)(d ? d - 1 : 0) * GT_WORDS * PAIR_BLOCK;
+  Fq12 a;
+  FqE* e = reinterpret_cast<FqE*>(&a);
+#pragma unroll
+  for (int k = 0; k < 12; k++) {
+#pragma unroll
+    for (int i = 0; i < Fq::N; i++) {
+      const uint32_t v = p[(k * Fq::N + i) * PAIR_BLOCK + lane];
+      e[k].l[i] = d ? v : o[k].l[i];
+    }
+  }
+  return a;
+}
+
+// x^e into the lane's column of sh (1 when the lane is not live); e: 8 words, least significant first, consumed
+GM_DEV void gt_pow_lane(uint32_t* sh, uint32_t* tab, int lane, bool live, const Fq12& x, uint32_t e[8]) {
+  gt_lds_store(sh, lane, fq12_one());
+  if (live) {
+    Fq12 p = x;
+    gt_lds_store(tab, lane, p);
+#pragma unroll 1
+    for (int t = 1; t < GT_TABLE; t++) {  // x^(t+1) = x^t x (x^2 as a product: one code path, 18 Fq products of 16 236)
+      p = fq12_mul(p, gt_lds_load(tab, lane));
+      gt_lds_store(tab + (size_t)t * GT_WORDS * PAIR_BLOCK, lane, p);
+    }
+#pragma unroll 1
+    for (int w = 0; w < 256 / GT_WINDOW; w++) {
+      const uint32_t d = e[7] >> (32 - GT_WINDOW);  // the top digit, then the exponent moves up by one window
+#pragma unroll
+      for (int i = 7; i > 0; i--) e[i] = (e[i] << GT_WINDOW) | (e[i - 1] >> (32 - GT_WINDOW));
+      e[0] <<= GT_WINDOW;
+      Fq12 f = gt_lds_load(sh, lane);
+#pragma unroll 1
+      for (int k = 0; k < GT_WINDOW; k++) f = fq12_sqr(f);
+      gt_lds_store(sh, lane, fq12_mul(f, gt_tab_load(tab, lane, d)));
+    }
+  }
+}
+
+// Up to three ranges of (element, exponent) per launch: term i of a range is x[first_x + step_x i] (576-byte device records)
+// to the power e[first_e + step_e i] (32-byte records: Fr in Montgomery form when `mont`, else 8 canonical words as they are)
+struct GtRange {
+  const uint8_t* x;
+  const uint8_t* e;
+  long long first_x, step_x, first_e, step_e;
+  unsigned long long n;
+};
+
+__global__ __launch_bounds__(PAIR_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_gt_multi_pow(GtRange r0, GtRange r1, GtRange r2, int mont, uint32_t* __restrict__ tab,
+                                                                                                           uint8_t* __restrict__ partials) {
+  __shared__ uint32_t sh[GT_WORDS * PAIR_BLOCK];
+  const int lane = threadIdx.x;
+  const unsigned long long i = (unsigned long long)blockIdx.x * PAIR_BLOCK + lane;
+  const bool live = i < r0.n + r1.n + r2.n;
+  Fq12 x = fq12_one();
+  uint32_t e[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (live) {
+    const GtRange r = i < r0.n ? r0 : i < r0.n + r1.n ? r1 : r2;
+    const long long k = (long long)(i < r0.n ? i : i < r0.n + r1.n ? i - r0.n : i - r0.n - r1.n);
+    x = fq12_load(r.x + (size_t)(r.first_x + r.step_x * k) * GT_BYTES);
+    Fr s = fp_load<FrParams>(r.e + (size_t)(r.first_e + r.step_e * k) * 32);
+    if (mont) s = fp_from_mont<FrParams>(s);
+#pragma unroll
+    for (int j = 0; j < 8; j++) e[j] = s.l[j];
+  }
+  gt_pow_lane(sh, tab + (size_t)blockIdx.x * GT_TAB_BLOCK, lane, live, x, e);
+  gt_block_product(sh, lane);
+  if (lane == 0) fq12_store(partials + (size_t)blockIdx.x * GT_BYTES, gt_lds_load(sh, 0));
+}
+
+// herring split_fold over GT (src/herring/time_prover.rs:72-76, multiplicative): out[i] = f[2i] f[2i+1]^s, an odd tail is
+// out[i] = f[2i].  s8: the canonical scalar, 8 x u32 -- the same in every lane.  One lane per output.
+__global__ __launch_bounds__(PAIR_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_gt_split_fold(const uint8_t* __restrict__ in, size_t n, const uint32_t* __restrict__ s8,
+                                                                                                            uint32_t* __restrict__ tab, uint8_t* __restrict__ out) {
+  __shared__ uint32_t sh[GT_WORDS * PAIR_BLOCK];
+  const int lane = threadIdx.x;
+  const size_t i = (size_t)blockIdx.x * PAIR_BLOCK + lane, m = (n + 1) / 2;
+  const bool live = 2 * i + 1 < n;
+  uint32_t e[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) e[j] = s8[j];
+  gt_pow_lane(sh, tab + (size_t)blockIdx.x * GT_TAB_BLOCK, lane, live, live ? fq12_load(in + (2 * i + 1) * GT_BYTES) : fq12_one(), e);
+  if (i < m) {
+    const Fq12 lo = fq12_load(in + (2 * i) * GT_BYTES);
+    fq12_store(out + i * GT_BYTES, live ? fq12_mul(lo, gt_lds_load(sh, lane)) : lo);
+  }
+}
+
+// host records (12 Fq in ark-ff's Montgomery form, 2^384) -> device records (2^390), in place: one thread per coefficient
+__global__ __launch_bounds__(256) void k_gt_import(uint8_t* __restrict__ d, size_t ncoef) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < ncoef) fqe_store(d + i * 48, fqe_import(fqe_load(d + i * 48)));
+}
+
 // ---- the segmented form: S independent products per launch ------------------------------------------------------------------
 // Segment s owns the lanes [start, start + count) of a level and writes its partials from index `out` on, one per block it touches.
 // The host (seg_levels) lays the segments out so that one of at most PAIR_BLOCK lanes never crosses a block; lanes between two
@@ -275,10 +391,21 @@ void pairing_workspace_release(PairingWorkspace& w) {
   if (w.host_out) (void)hipHostFree(w.host_out);
   w.host_out = nullptr;
   w.seg_tab.release();
+  w.gt_tab.release();
   if (w.host_seg) (void)hipHostFree(w.host_seg);
   w.host_seg = nullptr;
   w.host_seg_cap = 0;
 }
+
+// room for the m partials of a launch (part[0]), the level behind them and the pinned copy of the last few
+static int gt_partials_ensure(PairingWorkspace& ws, size_t m) {
+  int rc;
+  if ((rc = ws.part[0].ensure(m * GT_BYTES))) return rc;
+  if ((rc = ws.part[1].ensure(((m + PAIR_BLOCK - 1) / PAIR_BLOCK) * GT_BYTES))) return rc;
+  if (!ws.host_out) GM_HIP(hipHostMalloc((void**)&ws.host_out, GT_HOST_MAX * GT_BYTES, hipHostMallocDefault));
+  return GM_OK;
+}
+static int gt_reduce_partials(Context* C, size_t m, gmh::Fq12* out);
 
 // The Miller product of both spans (PairSpan: ctx.hpp), NOT conjugated, not exponentiated.  Caller holds the MSM lock.
 int miller_product(Context* C, const PairSpan& s0, const PairSpan& s1, gmh::Fq12* out) {
@@ -289,17 +416,24 @@ int miller_product(Context* C, const PairSpan& s0, const PairSpan& s1, gmh::Fq12
   hipStream_t st = C->stream;
   PairingWorkspace& ws = C->pairing;
   Profiler& pf = C->prof;
-  size_t m = (n + PAIR_BLOCK - 1) / PAIR_BLOCK;
+  const size_t m = (n + PAIR_BLOCK - 1) / PAIR_BLOCK;
   int rc;
-  if ((rc = ws.part[0].ensure(m * GT_BYTES))) return rc;
-  if ((rc = ws.part[1].ensure(((m + PAIR_BLOCK - 1) / PAIR_BLOCK) * GT_BYTES))) return rc;
-  if (!ws.host_out) GM_HIP(hipHostMalloc((void**)&ws.host_out, GT_HOST_MAX * GT_BYTES, hipHostMallocDefault));
+  if ((rc = gt_partials_ensure(ws, m))) return rc;
   const PairRange r0{s0.g1, s0.g2, (long long)s0.first1, (long long)s0.step1, (long long)s0.first2, (long long)s0.step2, (unsigned long long)s0.n};
   const PairRange r1{s1.g1, s1.g2, (long long)s1.first1, (long long)s1.step1, (long long)s1.first2, (long long)s1.step2, (unsigned long long)s1.n};
   pf.begin(PROF_ACC0, st);
   hipLaunchKernelGGL(k_miller, dim3((unsigned)m), dim3(PAIR_BLOCK), 0, st, r0, r1, ws.part[0].as<uint8_t>());
   pf.end(PROF_ACC0, st);
   GM_HIP(hipGetLastError());
+  return gt_reduce_partials(C, m, out);
+}
+
+// The product of the m partials that a launch left in part[0] (both levels and the pinned copy are there): k_gt_reduce levels,
+// the copy of the last few, their product on the host.  Behind k_miller and k_gt_multi_pow alike.
+static int gt_reduce_partials(Context* C, size_t m, gmh::Fq12* out) {
+  hipStream_t st = C->stream;
+  PairingWorkspace& ws = C->pairing;
+  Profiler& pf = C->prof;
   int cur = 0;
   pf.begin(PROF_REDUCE, st);
   while (m > GT_HOST_MAX) {
@@ -317,6 +451,94 @@ int miller_product(Context* C, const PairSpan& s0, const PairSpan& s1, gmh::Fq12
   for (size_t k = 1; k < m; k++) f = f * gmh::Fq12::from_device(ws.host_out + k * (GT_BYTES / 8));
   *out = f;
   return GM_OK;
+}
+
+// ---- GtModule on the host side: prod x_i^e_i over up to three spans (GtSpan: ctx.hpp).  Caller holds the MSM lock. ------------------
+int gt_multi_pow(Context* C, const GtSpan spans[3], int mont, gmh::Fq12* out) {
+  const size_t n = spans[0].n + spans[1].n + spans[2].n;
+  *out = gmh::Fq12::one();
+  if (n == 0) return GM_OK;
+  GM_CHECK(spans[0].n <= ((size_t)1 << 36) && spans[1].n <= ((size_t)1 << 36) && spans[2].n <= ((size_t)1 << 36), GM_EINVAL,
+           "gt_multi_pow: %zu terms in one call (at most 2^36 per span)", n);
+  hipStream_t st = C->stream;
+  PairingWorkspace& ws = C->pairing;
+  Profiler& pf = C->prof;
+  const size_t m = (n + PAIR_BLOCK - 1) / PAIR_BLOCK;
+  int rc;
+  if ((rc = gt_partials_ensure(ws, m))) return rc;
+  if ((rc = ws.gt_tab.ensure(m * GT_TAB_BLOCK * sizeof(uint32_t)))) return rc;
+  GtRange r[3];
+  for (int j = 0; j < 3; j++)
+    r[j] = GtRange{spans[j].x, spans[j].e, (long long)spans[j].first_x, (long long)spans[j].step_x, (long long)spans[j].first_e, (long long)spans[j].step_e,
+                   (unsigned long long)spans[j].n};
+  pf.begin(PROF_ACC0, st);
+  hipLaunchKernelGGL(k_gt_multi_pow, dim3((unsigned)m), dim3(PAIR_BLOCK), 0, st, r[0], r[1], r[2], mont, ws.gt_tab.as<uint32_t>(), ws.part[0].as<uint8_t>());
+  pf.end(PROF_ACC0, st);
+  GM_HIP(hipGetLastError());
+  return gt_reduce_partials(C, m, out);
+}
+
+// out[i] = in[2i] in[2i+1]^s over device records, s at d_s8 (canonical, 8 x u32), on C->stream without a wait.  Caller holds the
+// MSM lock (the table workspace) and collects the profiler after its wait.
+int gt_split_fold_launch(Context* C, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out) {
+  const size_t blocks = ((n + 1) / 2 + PAIR_BLOCK - 1) / PAIR_BLOCK;
+  if (blocks == 0) return GM_OK;
+  int rc = C->pairing.gt_tab.ensure(blocks * GT_TAB_BLOCK * sizeof(uint32_t));
+  if (rc) return rc;
+  C->prof.begin(PROF_ACC0, C->stream);
+  hipLaunchKernelGGL(k_gt_split_fold, dim3((unsigned)blocks), dim3(PAIR_BLOCK), 0, C->stream, in, n, d_s8, C->pairing.gt_tab.as<uint32_t>(), out);
+  C->prof.end(PROF_ACC0, C->stream);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+// n host records of 72 x u64 (ark-ff's Montgomery form) as a device vector of 576-byte records: a dev_malloc block the caller frees
+int gt_from_host(Context* C, const uint64_t* x, size_t n, uint8_t** d) {
+  *d = nullptr;
+  uint8_t* p = nullptr;
+  GM_HIP(dev_malloc((void**)&p, n * GT_BYTES));
+  const size_t ncoef = n * 12;
+  hipError_t e = hipMemcpyAsync(p, x, n * GT_BYTES, hipMemcpyHostToDevice, C->stream);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_gt_import, dim3((unsigned)((ncoef + 255) / 256)), dim3(256), 0, C->stream, p, ncoef);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(C->stream);  // `x` is read by the copy until here
+  if (e != hipSuccess) {
+    (void)gm::raw_free(p);
+    GM_HIP(e);
+  }
+  *d = p;
+  return GM_OK;
+}
+
+// gm_gt_multi_pow: host elements and canonical 256-bit exponents (n x 4 u64, as they are)
+static int gt_multi_pow_staged(Context* C, const uint8_t* dx, uint8_t* de, const uint64_t* scalars_canonical, size_t n, uint64_t out_gt[72]) {
+  GM_HIP(hipMemcpyAsync(de, scalars_canonical, n * 32, hipMemcpyHostToDevice, C->stream));
+  GtSpan s[3];
+  s[0].x = dx;
+  s[0].e = de;
+  s[0].n = n;
+  gmh::Fq12 f;
+  int rc = gt_multi_pow(C, s, 0, &f);  // ends in a wait: the scalars have been copied
+  if (rc) return rc;
+  f.to_limbs(out_gt);
+  return GM_OK;
+}
+int gt_multi_pow_host(Context* C, const uint64_t* x, const uint64_t* scalars_canonical, size_t n, uint64_t out_gt[72]) {
+  GM_MSM_LOCK(C);
+  uint8_t *dx = nullptr, *de = nullptr;
+  int rc = gt_from_host(C, x, n, &dx);
+  if (rc) return rc;
+  const hipError_t e = dev_malloc((void**)&de, n * 32);
+  if (e == hipSuccess) {
+    rc = gt_multi_pow_staged(C, dx, de, scalars_canonical, n, out_gt);
+    if (rc) (void)hipStreamSynchronize(C->stream);  // nothing in flight reads the two vectors once they go
+    (void)gm::raw_free(de);
+  }
+  (void)gm::raw_free(dx);
+  GM_HIP(e);
+  return rc;
 }
 
 // One level of the segmented layout: segment s has counts[s] >= 1 lanes.  Fills start / count / out and returns the number of

@@ -1,8 +1,9 @@
 """Host mirror of herring's sumcheck over a bilinear module (src/herring): the TimeProver of
-src/herring/time_prover.rs:42-137 for the four module instances that are in scope:
-FModule (F x F -> F), G1Module (G1 x F -> G1), G2Module (F x G2 -> G2) and PModule (G1 x G2 -> GT; pairings are
-gemini_amd/pairing.py).  The inner-product argument built on them is gemini_amd/ipa.py (its PModule provers are batched inside the library,
-not instances of the classes here); a GtModule prover of its own, InnerProductProof::generic and CrsStream are out of scope."""
+src/herring/time_prover.rs:42-137 for the five module instances of src/herring/module.rs:
+FModule (F x F -> F), G1Module (G1 x F -> G1), G2Module (F x G2 -> G2), PModule (G1 x G2 -> GT; pairings are
+gemini_amd/pairing.py) and GtModule (GT x F -> GT; the device multi-exponentiation is pairing.gt_multi_pow).  The inner-product
+argument built on them is gemini_amd/ipa.py (its PModule provers are batched inside the library, not instances of the classes here, and
+its GT multi-exponentiations stay on the host); InnerProductProof::generic and CrsStream are out of scope."""
 from __future__ import annotations
 
 import ctypes as C
@@ -110,4 +111,21 @@ class PModuleTimeProver(_ModuleTimeProver):
         h = C.c_uint64()
         capi.check(capi.load().gm_hp_new(capi.ptr(fp), C.c_size_t(fp.shape[1] * 8), C.c_size_t(len(fp)), capi.ptr(gp), C.c_size_t(gp.shape[1] * 8),
                                          C.c_size_t(len(gp)), capi.ptr(capi.u64(twist_mont).reshape(4)), C.byref(h)))
+        self.handle = h.value
+
+
+class GtModuleTimeProver(_ModuleTimeProver):
+    """TimeProver<GtModule>: f = GT elements ((n, 72) limbs, gemini_amd/pairing.py; any reduced coefficients are taken on trust),
+    g = Fr; messages are pairs of (72,) GT elements, a = prod f[2i]^g[2i], b = prod f[2i]^g[2i+1] * prod f[2i+1]^g[2i] in one
+    launch; the fold is f'[i] = f[2i] * f[2i+1]^(r twist).  Calls after the one that returned None go on as G1/G2 do."""
+
+    _prefix, _msg, _final_f, _final_g = "hgt", 72, 72, 4
+
+    def __init__(self, f_gt, g, twist_mont):
+        capi.ensure_init()
+        fg = capi.u64(f_gt).reshape(-1, 72)
+        gm_ = capi.u64(g).reshape(-1, 4)
+        h = C.c_uint64()
+        capi.check(capi.load().gm_hgt_new(capi.ptr(fg), C.c_size_t(len(fg)), capi.ptr(gm_), C.c_size_t(len(gm_)),
+                                          capi.ptr(capi.u64(twist_mont).reshape(4)), C.byref(h)))
         self.handle = h.value

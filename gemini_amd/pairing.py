@@ -51,6 +51,24 @@ def gt_pow(a, scalar: int) -> np.ndarray:
     return out
 
 
+def gt_multi_pow(x, scalars) -> np.ndarray:
+    """prod_i x_i^scalars_i on the device (gm_gt_multi_pow): x is (n, 72) limbs, scalars n integers 0 <= s < 2^256 taken as they
+    are (not reduced mod r) or an (n, 4) uint64 array of canonical limbs; the shorter input ends the product, n = 0 gives 1.
+    No final exponentiation, no membership check: bit for bit the composition of gt_pow / gt_mul on any reduced coefficients."""
+    capi.ensure_init()
+    xs = capi.u64(x).reshape(-1, 72)
+    if isinstance(scalars, np.ndarray) and scalars.dtype == np.uint64:
+        sc = capi.u64(scalars).reshape(-1, 4)
+    else:
+        ints = [int(s) for s in scalars]
+        assert all(0 <= s < (1 << 256) for s in ints)
+        sc = np.array([[(s >> (64 * k)) & 0xFFFFFFFFFFFFFFFF for k in range(4)] for s in ints], dtype=np.uint64).reshape(-1, 4)
+    n = min(len(xs), len(sc))
+    out = np.empty(72, dtype=np.uint64)
+    capi.check(capi.load().gm_gt_multi_pow(capi.ptr(xs), C.c_size_t(n), capi.ptr(sc), capi.ptr(out)))
+    return out
+
+
 def gt_final_exp(f) -> np.ndarray:
     """f^((q^12 - 1) / r) for any Fq12 element, no conjugation: a test and integration aid (gm_gt_final_exp)"""
     out = np.empty(72, dtype=np.uint64)

@@ -552,6 +552,29 @@ int gm_hp_rounds(uint64_t handle, size_t* tot_rounds, size_t* round);
 int gm_hp_final(uint64_t handle, uint64_t f0_jac[18], uint64_t g0_jac[36], int* has);
 int gm_hp_free(uint64_t handle);
 
+/* ---- GtModule: GT multi-exponentiation on the device and the herring GtModule prover (gemini_amd/csrc/pairing.hip) ------
+ * GtModule (GT x Fr -> GT, src/herring/module.rs:49-58): p(a, b) = a^b in the multiplicative notation of this header,
+ * ip = prod_i a_i^b_i.  One lane per element raises it by a fixed 2-bit window (no branch on exponent bits), the block
+ * multiplies its 64 powers, the reduction levels of the pairing block and the host finish the product.  There is no final
+ * exponentiation, no conjugation and no membership check: the entries take any 12 reduced Fq coefficients on trust and agree
+ * bit for bit with the composition of gm_gt_pow / gm_gt_mul on every such input.  A launch is tens of milliseconds deep whatever
+ * n is (profiles/gt_module.md gives the n from which it beats the host loop).  Calls share the MSM lock.
+ * gm_gt_multi_pow: prod_i x_i^e_i for host elements and exponents that are 256-bit integers AS GIVEN (4 x u64, least
+ * significant first, not reduced mod r), like gm_gt_pow; n = 0 gives 1.
+ * gm_hgt_*: TimeProver<GtModule>: f is a vector of GT elements (nf x 72 limbs), g a vector of Fr (Montgomery).
+ * a = prod_{i} f[2i]^g[2i]; b = prod f[2i]^g[2i+1] * prod f[2i+1]^g[2i] is ONE launch over both halves (a zip: the shorter
+ * side ends a product).  fold: f'[i] = f[2i] * f[2i+1]^(r twist) (an odd tail is f[2i]), g'[i] = g[2i] + r g[2i+1], twist <- twist^2.
+ * rounds = ceil(log2(min(nf, ng))).  gm_hgt_round folds by the challenge first when one is given; after the call that answered
+ * has_msg = 0 further rounds answer has_msg = 0 and folds are applied, as for gm_hg1_* / gm_hg2_*.  gm_hgt_final: f[0] (72 limbs)
+ * and g[0] (4 limbs) once the rounds are done.  A handle of another module is GM_EHANDLE. */
+int gm_gt_multi_pow(const uint64_t* x /* n x 72 */, size_t n, const uint64_t* scalars_canonical /* n x 4 */, uint64_t out_gt[72]);
+int gm_hgt_new(const uint64_t* f_gt /* nf x 72 */, size_t nf, const uint64_t* g_mont, size_t ng, const uint64_t twist_mont[4], uint64_t* handle);
+int gm_hgt_round(uint64_t handle, const uint64_t* challenge_or_null, uint64_t a_gt[72], uint64_t b_gt[72], int* has_msg);
+int gm_hgt_fold(uint64_t handle, const uint64_t challenge_mont[4]);
+int gm_hgt_rounds(uint64_t handle, size_t* tot_rounds, size_t* round);
+int gm_hgt_final(uint64_t handle, uint64_t f0_gt[72], uint64_t g0_mont[4], int* has);
+int gm_hgt_free(uint64_t handle);
+
 /* ---- herring's inner-product argument: Crs, Vrs, InnerProductProof (gemini_amd/csrc/ipa.hip) -------------------------
  * src/herring/ipa.rs: InnerProductProof::new (:533-685) proves <a, b> = y together with comm_a = <a, crs.g1> and
  * comm_b = <b, crs.g2> in one batched sumcheck over GT; verify_transcript (:250-343) checks it against the Vrs of the CRS.

@@ -753,6 +753,33 @@ struct HerringPModule {
 }  // namespace detail
 using HerringP = detail::HerringModuleProver<detail::HerringPModule>;
 
+// ---- GtModule (src/herring/module.rs:49-58): prod_i x_i^e_i on the device and TimeProver<GtModule> ------------------------------
+// exponents are 256-bit integers as given (not reduced mod r), like gt_pow; the shorter input ends the product, none gives 1
+inline Gt gt_multi_pow(const std::vector<Gt>& x, const std::vector<BigInt>& scalars) {
+  Gt r;
+  const size_t n = x.size() < scalars.size() ? x.size() : scalars.size();
+  check(gm_gt_multi_pow(n ? x[0].data() : nullptr, n, n ? scalars[0].data() : nullptr, r.data()));
+  return r;
+}
+namespace detail {
+// TimeProver<GtModule>: f in GT, g in Fr, messages in GT
+struct HerringGtModule {
+  using Lhs = std::vector<Gt>;
+  using Rhs = std::vector<Fr>;
+  using Msg = GtRoundMsg;
+  using Final = std::pair<Gt, Fr>;
+  static int create(const Lhs& f, const Rhs& g, const Fr& twist, uint64_t* h) {
+    return gm_hgt_new(f.empty() ? nullptr : f[0].data(), f.size(), g.empty() ? nullptr : g[0].data(), g.size(), twist.data(), h);
+  }
+  static constexpr auto round = gm_hgt_round;
+  static constexpr auto fold = gm_hgt_fold;
+  static constexpr auto rounds = gm_hgt_rounds;
+  static constexpr auto final_foldings = gm_hgt_final;
+  static constexpr auto free = gm_hgt_free;
+};
+}  // namespace detail
+using HerringGt = detail::HerringModuleProver<detail::HerringGtModule>;
+
 // merlin::Transcript + GeminiTranscript, src/transcript.rs
 class Transcript {
  public:
