@@ -2083,6 +2083,53 @@ int gm_hgt_free(uint64_t handle) {
   return herring_free(C, handle, HERRING_GT, "hgt_free");
 }
 
+// ---- GT element by element on the device (pairing.hip): final exponentiation, pairings, the membership check ----------------
+int gm_gt_final_exp_many(const uint64_t* in, size_t n, uint64_t* out) {
+  GM_CTX();
+  GM_CHECK((in != nullptr && out != nullptr) || n == 0, GM_EINVAL, "gt_final_exp_many: null pointer");
+  if (n == 0) return GM_OK;
+  return gt_final_exp_many(C, in, n, out);
+}
+int gm_pairing_each(const void* g1, size_t g1_stride, const void* g2, size_t g2_stride, size_t n, uint64_t* out_gt) {
+  GM_CTX();
+  GM_CHECK((g1 != nullptr && g2 != nullptr && out_gt != nullptr) || n == 0, GM_EINVAL, "pairing_each: null pointer");
+  if (n == 0) return GM_OK;
+  return pairing_each_host(C, g1, g1_stride, g2, g2_stride, n, out_gt);
+}
+int gm_pairing_each_h(uint64_t g1_handle, size_t off1, size_t step1, uint64_t g2_handle, size_t off2, size_t step2, size_t n, uint64_t* out_gt) {
+  GM_CTX();
+  Bases* b1 = find_bases(g1_handle);
+  GM_CHECK(b1 != nullptr, GM_EHANDLE, "pairing_each_h: unknown G1 bases handle %llu", (unsigned long long)g1_handle);
+  GM_G2B(b2, g2_handle, "pairing_each_h");
+  GM_CHECK(out_gt != nullptr || n == 0, GM_EINVAL, "pairing_each_h: null pointer");
+  GM_CHECK(step1 >= 1 && step2 >= 1, GM_EINVAL, "pairing_each_h: steps %zu / %zu must be >= 1", step1, step2);
+  if (n == 0) return GM_OK;
+  GM_CHECK(off1 < b1->n && (n - 1) <= (b1->n - 1 - off1) / step1, GM_EINVAL, "pairing_each_h: G1 range %zu + %zu * [0, %zu) outside %zu bases", off1, step1, n,
+           b1->n);
+  GM_CHECK(off2 < b2->n && (n - 1) <= (b2->n - 1 - off2) / step2, GM_EINVAL, "pairing_each_h: G2 range %zu + %zu * [0, %zu) outside %zu bases", off2, step2, n,
+           b2->n);
+  return pairing_each_run(C, b1->d, (int64_t)off1, (int64_t)step1, b2->d, (int64_t)off2, (int64_t)step2, n, out_gt);
+}
+int gm_gt_check(const uint64_t* x, size_t n, uint8_t* status_or_null, size_t* first_bad, int* ok) {
+  if (ok) *ok = 0;  // fails closed, as the point-validation block does
+  GM_CTX();
+  GM_CHECK(ok != nullptr && (x != nullptr || n == 0), GM_EINVAL, "gt_check: null pointer");
+  return gt_check_host(C, x, n, status_or_null, first_bad, ok);
+}
+int gm_hgt_check(uint64_t handle, size_t* first_bad, int* ok) {
+  if (ok) *ok = 0;
+  GM_CTX();
+  GM_HERRING(H, handle, GT, "hgt_check");
+  GM_CHECK(ok != nullptr, GM_EINVAL, "hgt_check: null pointer");
+  return herring_gt_check(C, H, first_bad, ok);
+}
+int gm_debug_gt_op(int op, const uint64_t* in, size_t n, uint64_t* out) {
+  GM_CTX();
+  GM_CHECK((in != nullptr && out != nullptr) || n == 0, GM_EINVAL, "debug_gt_op: null pointer");
+  if (n == 0) return GM_OK;
+  return gt_debug_op(C, op, in, n, out);
+}
+
 // ---- herring's inner-product argument: Crs, Vrs, InnerProductProof (ipa.hip) --------------------------------
 #define GM_IPA_FIND(var, table, h, who, what)  \
   auto* var = find_in(C, C->table, h);          \
@@ -2260,6 +2307,15 @@ int gm_ipa_from_fields(size_t rounds, const uint64_t* messages, const uint64_t* 
   memcpy(p->foldings_fg2, foldings_fg2, sizeof p->foldings_fg2);
   *proof = put_in(C, C->ipa, std::move(p));
   return GM_OK;
+}
+// the 2 rounds GT messages of a proof through k_gt_check: a of round i is index 2 i, b is 2 i + 1 (the layout of `messages`)
+int gm_ipa_check_gt(uint64_t proof, size_t* first_bad, int* ok) {
+  if (ok) *ok = 0;
+  GM_CTX();
+  GM_IPA_FIND(p, ipa, proof, "ipa_check_gt", "proof");
+  GM_CHECK(ok != nullptr, GM_EINVAL, "ipa_check_gt: null pointer");
+  GM_CHECK(p->messages.size() == p->rounds * 144, GM_EINVAL, "ipa_check_gt: %zu message limbs for %zu rounds", p->messages.size(), p->rounds);
+  return gt_check_host(C, p->messages.data(), 2 * p->rounds, nullptr, first_bad, ok);
 }
 int gm_ipa_rounds(uint64_t proof, size_t* rounds) {
   GM_CTX();

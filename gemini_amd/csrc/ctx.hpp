@@ -534,6 +534,8 @@ struct PairProduct {
   PairSpan s0, s1;
 };
 int miller_products(Context* C, const PairProduct* prods, size_t S, gmh::Fq12* out);
+// the same S products as GT elements (S x 72 limbs): conjugation and ONE k_gt_final_exp launch over the Miller values on the device
+int pairing_products(Context* C, const PairProduct* prods, size_t S, uint64_t* out_gt);
 // Miller product -> GT: conjugation (the loop parameter is negative), then the one final exponentiation
 void pairing_finish(const gmh::Fq12& miller, uint64_t out_gt[72]);
 
@@ -551,6 +553,15 @@ int gt_multi_pow_host(Context* C, const uint64_t* x, const uint64_t* scalars_can
 int gt_from_host(Context* C, const uint64_t* x, size_t n, uint8_t** d);  // n x 72 limbs -> a dev_malloc block of device records
 // out[i] = in[2i] in[2i+1]^s (an odd tail is in[2i]), s at d_s8 (canonical, 8 x u32), on C->stream; caller holds the MSM lock
 int gt_split_fold_launch(Context* C, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out);
+// GT element by element (pairing.hip: k_gt_final_exp, k_miller_each, k_gt_check).  The *_launch / *_run forms work on device records
+// under the caller's MSM lock; the others take it.
+int gt_final_exp_launch(Context* C, const uint8_t* in, size_t n, int conj, uint8_t* out);  // out[i] = (conj ? conj(in[i]) : in[i])^((q^12 - 1) / r), no wait
+int gt_final_exp_many(Context* C, const uint64_t* in, size_t n, uint64_t* out);
+int pairing_each_run(Context* C, const uint8_t* d_g1, int64_t first1, int64_t step1, const uint8_t* d_g2, int64_t first2, int64_t step2, size_t n, uint64_t* out_gt);
+int pairing_each_host(Context* C, const void* g1, size_t stride1, const void* g2, size_t stride2, size_t n, uint64_t* out_gt);
+int gt_check_run(Context* C, const uint8_t* d_src, int host_form, size_t n, uint8_t* status_or_null, size_t* first_bad, int* ok);
+int gt_check_host(Context* C, const uint64_t* x, size_t n, uint8_t* status_or_null, size_t* first_bad, int* ok);
+int gt_debug_op(Context* C, int op, const uint64_t* in, size_t n, uint64_t* out);
 
 // herring module provers (herring.hip).  f / g are host arrays: Fr vectors in Montgomery form (the stride is ignored) or point
 // records of f_stride / g_stride bytes; messages and final foldings have the module's limb counts (include/gemini_hip.h).
@@ -561,6 +572,7 @@ void herring_destroy(Context* C, HerringProver* H);
 int herring_fold(Context* C, HerringProver* H, const uint64_t r[4]);
 int herring_round(Context* C, HerringProver* H, const uint64_t* challenge, uint64_t* a, uint64_t* b, int* has_msg);
 int herring_final(Context* C, HerringProver* H, uint64_t* f0, uint64_t* g0, int* has);
+int herring_gt_check(Context* C, HerringProver* H, size_t* first_bad, int* ok);  // GtModule: k_gt_check over the current f
 
 // herring's inner-product argument (ipa.hip)
 int crs_create(Context* C, const void* g1, size_t stride1, size_t n1, const void* g2, size_t stride2, size_t n2, uint64_t* handle);

@@ -44,6 +44,17 @@ GM_DEV FqE fq_dbl(const FqE& a) { return fp_add<FqParams>(a, a); }
 GM_DEV FqE fq_sub(const FqE& a, const FqE& b) { return fp_sub<FqParams>(a, b); }
 GM_DEV FqE fq_neg_canonical(const FqE& y) { return fp_neg<FqParams>(y); }
 GM_DEV bool fq_is_zero(const FqE& a) { return a.is_zero(); }
+// the limbs as an integer: >= q?  (untrusted host input: the point checks of points.hip, the GT check of pairing.hip)
+GM_DEV bool pt_raw_ge_q(const Fq& a) {
+  uint32_t borrow = 0;
+#pragma unroll
+  for (int i = 0; i < 12; i++) {
+    uint32_t b;
+    (void)__builtin_subc(a.l[i], FqParams::MOD[i], borrow, &b);
+    borrow = b;
+  }
+  return borrow == 0;
+}
 GM_DEV FqE fqe_zero() { return Fq::zero(); }
 GM_DEV FqE fqe_one() { return fq30_pack(fq30_const(Fq30Consts::ONE)); }  // 2^390 mod q -- NOT Fq::one(), which is 2^384 mod q
 GM_DEV FqE fqe_load(const void* p) { return fp_load<FqParams>(p); }

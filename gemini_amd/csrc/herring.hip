@@ -301,6 +301,13 @@ int herring_round(Context* C, HerringProver* H, const uint64_t* challenge, uint6
   return GM_OK;
 }
 
+// gm_hgt_check: the membership test over the current f vector of a GtModule prover, where it lies (*ok was cleared by the entry)
+int herring_gt_check(Context* C, HerringProver* H, size_t* first_bad, int* ok) {
+  std::lock_guard<std::mutex> lk(H->mu);
+  GM_MSM_LOCK(C);
+  return gt_check_run(C, H->f[H->cur], 0, H->nf, nullptr, first_bad, ok);
+}
+
 // time_prover.rs:135-137
 int herring_final(Context* C, HerringProver* H, uint64_t* f0, uint64_t* g0, int* has) {
   const HerringModuleDesc& M = MODULES[H->module];

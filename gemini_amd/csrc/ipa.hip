@@ -219,19 +219,18 @@ int vrs_from_crs(Context* C, const Crs* crs, Vrs* out) {
     p[3].s0 = span(crs->g1, 0, 1, crs->g2, 1, 2, std::min({size, crs->n1, o2}));
     prods.insert(prods.end(), p, p + 4);
   }
-  std::vector<gmh::Fq12> m(prods.size());
+  // the 4 levels Miller values stay on the device and go through ONE k_gt_final_exp launch (profiles/gt_device.md)
+  std::vector<uint64_t> gt(prods.size() * 72);
   {
     GM_MSM_LOCK(C);
-    int rc = miller_products(C, prods.data(), prods.size(), m.data());
+    int rc = pairing_products(C, prods.data(), prods.size(), gt.data());
     if (rc) return rc;
   }
   out->vk1.resize(out->levels * 144);
   out->vk2.resize(out->levels * 144);
   for (size_t l = 0; l < out->levels; l++) {
-    pairing_finish(m[4 * l], out->vk1.data() + 144 * l);
-    pairing_finish(m[4 * l + 1], out->vk1.data() + 144 * l + 72);
-    pairing_finish(m[4 * l + 2], out->vk2.data() + 144 * l);
-    pairing_finish(m[4 * l + 3], out->vk2.data() + 144 * l + 72);
+    memcpy(out->vk1.data() + 144 * l, gt.data() + 72 * (4 * l), 144 * sizeof(uint64_t));      // even || odd
+    memcpy(out->vk2.data() + 144 * l, gt.data() + 72 * (4 * l + 2), 144 * sizeof(uint64_t));
   }
   return GM_OK;
 }

@@ -23,6 +23,10 @@
 // touches a block writes one partial.  Partials of a segment are consecutive, so the next level is the same reduction over a
 // table of its own; the launch count depends on the longest segment only, never on S.
 //
+// ELEMENT BY ELEMENT (k_miller_each, k_gt_final_exp, k_gt_check; "GT element by element" below): one lane per element and no block
+// product -- out[i] = e(P_i, Q_i) as one launch of Miller loops and one of final exponentiations by an exact x-chain over the
+// cyclotomic squarings of gt.cuh, and the GT membership test.  Vrs::from finishes its Miller values through the same launch.
+//
 // Registers and LDS: f is 144 VGPRs, T 72, a line 36, and an Fq6 product keeps ~10 Fq2 alive: too much for the 512 registers of
 // a lane at one wave per SIMD if f stayed resident.  f therefore lives in LDS ([coefficient limb][lane], 576 B per lane, 36 KiB per
 // wave: four waves per CU, one per SIMD) and is in registers only from the load in front of f^2 to the store behind f * line;
@@ -304,6 +308,148 @@ __global__ __launch_bounds__(256) void k_gt_import(uint8_t* __restrict__ d, size
   if (i < ncoef) fqe_store(d + i * 48, fqe_import(fqe_load(d + i * 48)));
 }
 
+// device records -> host records (ark-ff's Montgomery form), in place
+__global__ __launch_bounds__(256) void k_gt_export(uint8_t* __restrict__ d, size_t ncoef) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < ncoef) fqe_store(d + i * 48, fqe_export(fqe_load(d + i * 48)));
+}
+
+// ---- GT element by element: final exponentiation, pairings, membership (one lane per element, no block product) ----------------
+// The lane's running value is parked in its LDS column, as k_miller parks f.  LDS holds ONE Fq12 per lane (36 KiB per block, four
+// blocks per CU); every other value that has to survive a power -- the base of fq12_pow_x, the saved m and c of the chain -- lies
+// in a [limb][lane] column of the block's slice of PairingWorkspace::gt_tab (GT_SLOTS columns per lane, the table of
+// k_gt_multi_pow reused), read coalesced.
+constexpr int GT_SLOTS = 3;
+static_assert(GT_SLOTS <= GT_TABLE, "the slots are the table entries of k_gt_multi_pow's workspace");
+GM_DEV uint32_t* gt_slot(uint32_t* tab, int t, int lane) { return tab + (size_t)t * GT_WORDS * PAIR_BLOCK + lane; }
+
+// f^((q^12 - 1) / r) for the lane: f in registers, the result in registers.  With x = -|x| and h = (q^4 - q^2 + 1) / r,
+//   (q^12 - 1) / r = (q^6 - 1)(q^2 + 1) h,   h = ((x - 1)^2 / 3)(x + q)(x^2 + q^2 - 1) + 1   (exact; (x - 1)^2 / 3 = ((|x| + 1) / 3)(|x| + 1))
+// so the value is gmh::gt_final_exponentiation's on ANY 12 reduced coefficients (the easy part lands in the cyclotomic subgroup
+// whatever f is, 0 stays 0).  Fq products as written: easy part 837, 614 of them the one Fermat inversion in Fq; powers 62 x 18 +
+// 27 x 54 and 4 x (63 x 18 + 5 x 54); 6 products, 3 Frobenius maps: 9322 in all (tools/gt_device_bench.py counts them the same way).
+GM_DEV Fq12 gt_final_exp_lane(uint32_t* sh, uint32_t* tab, int lane, const Fq12& f) {
+  uint32_t* acc = sh + lane;
+  uint32_t *s0 = gt_slot(tab, 0, lane), *s1 = gt_slot(tab, 1, lane), *s2 = gt_slot(tab, 2, lane);
+  {
+    const Fq12 a = fq12_mul(fq12_conj(f), fq12_inv(f));  // f^(q^6 - 1)
+    const Fq12 m = fq12_mul(fq12_frobenius2(a), a);      // ^(q^2 + 1): cyclotomic from here on, the inverse is the conjugate
+    fq12_col_store(s0, PAIR_BLOCK, m);
+    fq12_col_store(s1, PAIR_BLOCK, m);
+  }
+  fq12_pow_const(acc, s0, PAIR_BLOCK, BLS_X_ABS_P1_DIV3);  // a = m^((|x| + 1) / 3)
+  fq12_col_store(s0, PAIR_BLOCK, fq12_col_load(acc, PAIR_BLOCK));
+  fq12_pow_x(acc, s0, PAIR_BLOCK);
+  fq12_col_store(s0, PAIR_BLOCK, fq12_mul(fq12_col_load(acc, PAIR_BLOCK), fq12_col_load(s0, PAIR_BLOCK)));  // b = a^(|x| + 1) = m^((x - 1)^2 / 3)
+  fq12_pow_x(acc, s0, PAIR_BLOCK);
+  {
+    const Fq12 c = fq12_mul(fq12_conj(fq12_col_load(acc, PAIR_BLOCK)), fq12_frobenius1(fq12_col_load(s0, PAIR_BLOCK)));  // b^(x + q)
+    fq12_col_store(s0, PAIR_BLOCK, c);
+    fq12_col_store(s2, PAIR_BLOCK, c);
+  }
+  fq12_pow_x(acc, s0, PAIR_BLOCK);
+  fq12_col_store(s0, PAIR_BLOCK, fq12_col_load(acc, PAIR_BLOCK));
+  fq12_pow_x(acc, s0, PAIR_BLOCK);  // c^(x^2): the two signs cancel
+  Fq12 d = fq12_mul(fq12_col_load(acc, PAIR_BLOCK), fq12_frobenius2(fq12_col_load(s2, PAIR_BLOCK)));
+  d = fq12_mul(d, fq12_conj(fq12_col_load(s2, PAIR_BLOCK)));  // c^(x^2 + q^2 - 1)
+  return fq12_mul(d, fq12_col_load(s1, PAIR_BLOCK));          // ... + 1
+}
+
+// out[i] = in[i]^((q^12 - 1) / r) over device records, conjugated first when `conj` (Miller values: x < 0); in == out is fine
+__global__ __launch_bounds__(PAIR_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_gt_final_exp(const uint8_t* in, size_t n, int conj, uint32_t* __restrict__ tab, uint8_t* out) {
+  __shared__ uint32_t sh[GT_WORDS * PAIR_BLOCK];
+  const int lane = threadIdx.x;
+  const size_t i = (size_t)blockIdx.x * PAIR_BLOCK + lane;
+  Fq12 f = i < n ? fq12_load(in + i * GT_BYTES) : fq12_one();
+  if (conj) f = fq12_conj(f);
+  f = gt_final_exp_lane(sh, tab + (size_t)blockIdx.x * GT_TAB_BLOCK, lane, f);
+  if (i < n) fq12_store(out + i * GT_BYTES, f);
+}
+
+// out[i] = f_{|x|, Q_i}(P_i), the lane's own Miller value (1 when either point is the identity): the loop of k_miller, no product
+__global__ __launch_bounds__(PAIR_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_miller_each(PairRange r, uint8_t* __restrict__ out) {
+  __shared__ uint32_t sh[GT_WORDS * PAIR_BLOCK];
+  const int lane = threadIdx.x;
+  const unsigned long long i = (unsigned long long)blockIdx.x * PAIR_BLOCK + lane;
+  G1Affine P;
+  G2Affine Q;
+  bool live = false;
+  if (i < r.n) {
+    P = g1_load_affine(r.g1 + (size_t)(r.first1 + r.step1 * (long long)i) * G1_AFF_BYTES);
+    Q = g2_load_affine(r.g2 + (size_t)(r.first2 + r.step2 * (long long)i) * G2_AFF_BYTES);
+    live = !(P.is_identity() || Q.is_identity());
+  }
+  miller_lane(sh, lane, live, P, Q);
+  if (i < r.n) fq12_store(out + (size_t)i * GT_BYTES, gt_lds_load(sh, lane));
+}
+
+// GT membership, one status byte per element: the first test that fails of
+//   1. a coefficient >= q                    GM_PT_NONCANONICAL    (host_form only: resident records are reduced by construction)
+//   2. f = 0 or f^(q^4) f != f^(q^2)         GM_PT_NOT_CYCLOTOMIC  (two Frobenius maps and a product: valid for any f)
+//   3. f^q != conj(f^|x|), i.e. f^q != f^x   GM_PT_NOT_IN_SUBGROUP (cyclotomic squarings, licensed by 2.)
+// 2. and 3. give f^(x^4 - x^2 + 1) = f^r = 1: q^4 - q^2 + 1 = 0 on f by 2., q = x on f by 3., r = x^4 - x^2 + 1 for BLS12.
+// Every lane runs every test and selects its status at the end; summary[block] is the block's first bad lane (GT_NO_BAD: none).
+// Fq products as written: 2 x 10 + 54 + 1404 + 15 = ~1500.
+constexpr uint32_t GT_NO_BAD = 0xffffffffu;
+__global__ __launch_bounds__(PAIR_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_gt_check(const uint8_t* __restrict__ src, int host_form, size_t n, uint32_t* __restrict__ tab,
+                                                                                                       uint8_t* __restrict__ status, uint32_t* __restrict__ summary) {
+  __shared__ uint32_t sh[GT_WORDS * PAIR_BLOCK];
+  const int lane = threadIdx.x;
+  const size_t i = (size_t)blockIdx.x * PAIR_BLOCK + lane;
+  Fq12 f = fq12_one();
+  bool canonical = true;
+  if (i < n) {
+    f = fq12_load(src + i * GT_BYTES);
+    if (host_form) {
+      FqE* e = reinterpret_cast<FqE*>(&f);
+#pragma unroll
+      for (int k = 0; k < 12; k++) canonical = canonical && !pt_raw_ge_q(e[k]);
+      if (!canonical) f = fq12_one();  // no value to go on with; the lane still runs the tests
+#pragma unroll
+      for (int k = 0; k < 12; k++) e[k] = canonical ? fqe_import(e[k]) : e[k];
+    }
+  }
+  uint32_t* s0 = gt_slot(tab + (size_t)blockIdx.x * GT_TAB_BLOCK, 0, lane);
+  fq12_col_store(s0, PAIR_BLOCK, f);
+  bool cyclotomic;
+  {
+    const Fq12 f2 = fq12_frobenius2(f);
+    cyclotomic = !fq12_is_zero(f) && fq12_eq(fq12_mul(fq12_frobenius2(f2), f), f2);
+  }
+  fq12_pow_x(sh + lane, s0, PAIR_BLOCK);
+  const bool member = fq12_eq(fq12_frobenius1(fq12_col_load(s0, PAIR_BLOCK)), fq12_conj(fq12_col_load(sh + lane, PAIR_BLOCK)));
+  const uint8_t st = !canonical ? GM_PT_NONCANONICAL : !cyclotomic ? GM_PT_NOT_CYCLOTOMIC : !member ? GM_PT_NOT_IN_SUBGROUP : GM_PT_OK;
+  const bool bad = i < n && st != GM_PT_OK;
+  if (i < n) status[i] = st;
+  const unsigned long long m = __ballot(bad);  // one wave per block
+  if (lane == 0) summary[blockIdx.x] = m ? (uint32_t)__ffsll((long long)m) - 1u : GT_NO_BAD;
+}
+
+// gm_debug_gt_op: ONE of the device functions of gt.cuh per lane, over device records
+enum { GT_OP_FROBENIUS1 = 0, GT_OP_FROBENIUS2 = 1, GT_OP_INVERSE = 2, GT_OP_CYCLOTOMIC_SQR = 3, GT_OP_POW_X = 4 };
+__global__ __launch_bounds__(PAIR_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_gt_debug_op(int op, const uint8_t* in, size_t n, uint32_t* __restrict__ tab, uint8_t* out) {
+  __shared__ uint32_t sh[GT_WORDS * PAIR_BLOCK];
+  const int lane = threadIdx.x;
+  const size_t i = (size_t)blockIdx.x * PAIR_BLOCK + lane;
+  const Fq12 f = i < n ? fq12_load(in + i * GT_BYTES) : fq12_one();
+  Fq12 r;
+  if (op == GT_OP_FROBENIUS1) {
+    r = fq12_frobenius1(f);
+  } else if (op == GT_OP_FROBENIUS2) {
+    r = fq12_frobenius2(f);
+  } else if (op == GT_OP_INVERSE) {
+    r = fq12_inv(f);
+  } else if (op == GT_OP_CYCLOTOMIC_SQR) {
+    r = fq12_cyclotomic_sqr(f);
+  } else {
+    uint32_t* s0 = gt_slot(tab + (size_t)blockIdx.x * GT_TAB_BLOCK, 0, lane);
+    fq12_col_store(s0, PAIR_BLOCK, f);
+    fq12_pow_x(sh + lane, s0, PAIR_BLOCK);
+    r = fq12_col_load(sh + lane, PAIR_BLOCK);
+  }
+  if (i < n) fq12_store(out + i * GT_BYTES, r);
+}
+
 // ---- the segmented form: S independent products per launch ------------------------------------------------------------------
 // Segment s owns the lanes [start, start + count) of a level and writes its partials from index `out` on, one per block it touches.
 // The host (seg_levels) lays the segments out so that one of at most PAIR_BLOCK lanes never crosses a block; lanes between two
@@ -406,6 +552,7 @@ static int gt_partials_ensure(PairingWorkspace& ws, size_t m) {
   return GM_OK;
 }
 static int gt_reduce_partials(Context* C, size_t m, gmh::Fq12* out);
+static int gt_to_host(Context* C, uint8_t* d, size_t n, uint64_t* out);
 
 // The Miller product of both spans (PairSpan: ctx.hpp), NOT conjugated, not exponentiated.  Caller holds the MSM lock.
 int miller_product(Context* C, const PairSpan& s0, const PairSpan& s1, gmh::Fq12* out) {
@@ -563,14 +710,21 @@ static unsigned long long seg_level(std::vector<unsigned long long>& counts, con
   return lane;
 }
 
-// S independent Miller products in one launch per level (NOT conjugated, not exponentiated): out[s] is the product over both spans
-// of prods[s], 1 for an empty one.  Caller holds the MSM lock.
-int miller_products(Context* C, const PairProduct* prods, size_t S, gmh::Fq12* out) {
+// The launches of S independent Miller products, one per level (NOT conjugated, not exponentiated), on C->stream without a wait:
+// the products of the non-empty prods[idx[k]], k < idx.size(), end as consecutive device records at *d_out (a level buffer of the
+// workspace).  Caller holds the MSM lock and keeps `t` until it has waited for the stream: the copies of the tables read it.
+struct SegTables {
   std::vector<size_t> idx;
-  std::vector<unsigned long long> counts;
   std::vector<PairSeg> spans;
+  std::vector<SegMap> maps;
+};
+static int miller_products_launch(Context* C, const PairProduct* prods, size_t S, SegTables& t, uint8_t** d_out) {
+  std::vector<unsigned long long> counts;
+  std::vector<size_t>& idx = t.idx;
+  std::vector<PairSeg>& spans = t.spans;
+  std::vector<SegMap>& maps = t.maps;
+  *d_out = nullptr;
   for (size_t s = 0; s < S; s++) {
-    out[s] = gmh::Fq12::one();
     const PairSpan &a = prods[s].s0, &b = prods[s].s1;
     if (a.n + b.n == 0) continue;
     GM_CHECK(a.n + b.n <= ((size_t)1 << 36), GM_EINVAL, "pairing: %zu pairs in one product (at most 2^36)", a.n + b.n);
@@ -587,7 +741,6 @@ int miller_products(Context* C, const PairProduct* prods, size_t S, gmh::Fq12* o
     unsigned long long lanes, partials;
   };
   std::vector<Level> levels;
-  std::vector<SegMap> maps;
   std::vector<unsigned long long> starts;
   for (;;) {
     maps.resize(maps.size() + nseg);
@@ -608,14 +761,6 @@ int miller_products(Context* C, const PairProduct* prods, size_t S, gmh::Fq12* o
   if ((rc = ws.seg_tab.ensure(span_bytes + map_bytes))) return rc;
   for (size_t l = 0; l < levels.size(); l++)  // level l writes its partials into part[l & 1]
     if ((rc = ws.part[l & 1].ensure(levels[l].partials * GT_BYTES))) return rc;
-  if (ws.host_seg_cap < nseg) {
-    if (ws.host_seg) (void)hipHostFree(ws.host_seg);
-    ws.host_seg = nullptr;
-    ws.host_seg_cap = 0;
-    const size_t cap = std::max<size_t>(2 * nseg, 64);
-    GM_HIP(hipHostMalloc((void**)&ws.host_seg, cap * GT_BYTES, hipHostMallocDefault));
-    ws.host_seg_cap = cap;
-  }
   uint8_t* d_tab = ws.seg_tab.as<uint8_t>();
   GM_HIP(hipMemcpyAsync(d_tab, spans.data(), span_bytes, hipMemcpyHostToDevice, st));
   GM_HIP(hipMemcpyAsync(d_tab + span_bytes, maps.data(), map_bytes, hipMemcpyHostToDevice, st));
@@ -634,10 +779,54 @@ int miller_products(Context* C, const PairProduct* prods, size_t S, gmh::Fq12* o
   }
   pf.end(PROF_REDUCE, st);
   GM_HIP(hipGetLastError());
-  GM_HIP(hipMemcpyAsync(ws.host_seg, ws.part[cur].p, nseg * GT_BYTES, hipMemcpyDeviceToHost, st));
-  GM_HIP(hipStreamSynchronize(st));  // the tables above are read by their copies until here
-  pf.collect();
-  for (size_t s = 0; s < nseg; s++) out[idx[s]] = gmh::Fq12::from_device(ws.host_seg + s * (GT_BYTES / 8));
+  *d_out = ws.part[cur].as<uint8_t>();
+  return GM_OK;
+}
+
+// S independent Miller products (NOT conjugated, not exponentiated): out[s] is the product over both spans of prods[s], 1 for an
+// empty one.  Caller holds the MSM lock.
+int miller_products(Context* C, const PairProduct* prods, size_t S, gmh::Fq12* out) {
+  for (size_t s = 0; s < S; s++) out[s] = gmh::Fq12::one();
+  SegTables t;
+  uint8_t* d = nullptr;
+  int rc = miller_products_launch(C, prods, S, t, &d);
+  const size_t nseg = t.idx.size();
+  if (rc || nseg == 0) {
+    if (rc) (void)hipStreamSynchronize(C->stream);
+    return rc;
+  }
+  PairingWorkspace& ws = C->pairing;
+  if (ws.host_seg_cap < nseg) {
+    if (ws.host_seg) (void)hipHostFree(ws.host_seg);
+    ws.host_seg = nullptr;
+    ws.host_seg_cap = 0;
+    const size_t cap = std::max<size_t>(2 * nseg, 64);
+    GM_HIP(hipHostMalloc((void**)&ws.host_seg, cap * GT_BYTES, hipHostMallocDefault));
+    ws.host_seg_cap = cap;
+  }
+  GM_HIP(hipMemcpyAsync(ws.host_seg, d, nseg * GT_BYTES, hipMemcpyDeviceToHost, C->stream));
+  GM_HIP(hipStreamSynchronize(C->stream));  // the tables of `t` are read by their copies until here
+  C->prof.collect();
+  for (size_t s = 0; s < nseg; s++) out[t.idx[s]] = gmh::Fq12::from_device(ws.host_seg + s * (GT_BYTES / 8));
+  return GM_OK;
+}
+
+// The same products as GT elements: conjugated and raised to (q^12 - 1) / r by ONE k_gt_final_exp launch over the S Miller values
+// where the reduction left them (Vrs::from: 4 (log2 len - 1) of them); out_gt: S x 72 limbs.  Caller holds the MSM lock.
+int pairing_products(Context* C, const PairProduct* prods, size_t S, uint64_t* out_gt) {
+  SegTables t;
+  uint8_t* d = nullptr;
+  int rc = miller_products_launch(C, prods, S, t, &d);
+  const size_t nseg = t.idx.size();
+  std::vector<uint64_t> got(nseg * 72);
+  if (!rc && nseg) rc = gt_final_exp_launch(C, d, nseg, 1, d);
+  if (!rc && nseg) rc = gt_to_host(C, d, nseg, got.data());  // ends in a wait
+  if (rc) {
+    (void)hipStreamSynchronize(C->stream);
+    return rc;
+  }
+  for (size_t s = 0; s < S; s++) gmh::Fq12::one().to_limbs(out_gt + 72 * s);
+  for (size_t s = 0; s < nseg; s++) memcpy(out_gt + 72 * t.idx[s], got.data() + 72 * s, GT_BYTES);
   return GM_OK;
 }
 
@@ -672,6 +861,145 @@ int pairing_run_host(Context* C, const void* g1, size_t stride1, const void* g2,
   if (b1 && b1->d) (void)gm::raw_free(b1->d);
   if (b2 && b2->d) (void)gm::raw_free(b2->d);
   return rc;
+}
+
+// ---- GT element by element: the host side of k_gt_final_exp, k_miller_each, k_gt_check.  Callers hold the MSM lock: the slots
+// are the table workspace of the GtModule kernels. ---------------------------------------------------------------------------
+constexpr size_t GT_EACH_MAX = (size_t)1 << 20;  // elements per call: 1728 B of slots and 576 B of record each
+
+namespace {
+struct GtTmp {  // a device block of one call: nothing in flight reads it once it goes
+  Context* C;
+  uint8_t* p = nullptr;
+  explicit GtTmp(Context* c) : C(c) {}
+  ~GtTmp() {
+    if (!p) return;
+    (void)hipStreamSynchronize(C->stream);
+    (void)gm::raw_free(p);
+  }
+};
+}  // namespace
+
+static int gt_slots_ensure(Context* C, size_t n, size_t* blocks) {
+  GM_CHECK(n <= GT_EACH_MAX, GM_EINVAL, "gt: %zu elements in one call (at most 2^20)", n);
+  *blocks = (n + PAIR_BLOCK - 1) / PAIR_BLOCK;
+  return C->pairing.gt_tab.ensure(*blocks * GT_TAB_BLOCK * sizeof(uint32_t));
+}
+
+// out[i] = in[i]^((q^12 - 1) / r) over device records (in == out is fine), on C->stream without a wait
+int gt_final_exp_launch(Context* C, const uint8_t* in, size_t n, int conj, uint8_t* out) {
+  size_t blocks;
+  int rc = gt_slots_ensure(C, n, &blocks);
+  if (rc || n == 0) return rc;
+  C->prof.begin(PROF_REDUCE, C->stream);
+  hipLaunchKernelGGL(k_gt_final_exp, dim3((unsigned)blocks), dim3(PAIR_BLOCK), 0, C->stream, in, n, conj, C->pairing.gt_tab.as<uint32_t>(), out);
+  C->prof.end(PROF_REDUCE, C->stream);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+// n device records -> n x 72 host limbs (the records are converted in place); ends in a wait
+static int gt_to_host(Context* C, uint8_t* d, size_t n, uint64_t* out) {
+  const size_t ncoef = n * 12;
+  hipLaunchKernelGGL(k_gt_export, dim3((unsigned)((ncoef + 255) / 256)), dim3(256), 0, C->stream, d, ncoef);
+  GM_HIP(hipGetLastError());
+  GM_HIP(hipMemcpyAsync(out, d, n * GT_BYTES, hipMemcpyDeviceToHost, C->stream));
+  GM_HIP(hipStreamSynchronize(C->stream));
+  C->prof.collect();
+  return GM_OK;
+}
+
+// gm_gt_final_exp_many: host elements, no conjugation
+int gt_final_exp_many(Context* C, const uint64_t* in, size_t n, uint64_t* out) {
+  GM_CHECK(n <= GT_EACH_MAX, GM_EINVAL, "gt_final_exp_many: %zu elements in one call (at most 2^20)", n);
+  GM_MSM_LOCK(C);
+  GtTmp d(C);
+  int rc = gt_from_host(C, in, n, &d.p);
+  if (!rc) rc = gt_final_exp_launch(C, d.p, n, 0, d.p);
+  if (!rc) rc = gt_to_host(C, d.p, n, out);
+  return rc;
+}
+
+// out[i] = e(g1[first1 + step1 i], g2[first2 + step2 i]) over packed device records: one k_miller_each, one k_gt_final_exp
+int pairing_each_run(Context* C, const uint8_t* d_g1, int64_t first1, int64_t step1, const uint8_t* d_g2, int64_t first2, int64_t step2, size_t n, uint64_t* out_gt) {
+  GM_CHECK(n <= GT_EACH_MAX, GM_EINVAL, "pairing_each: %zu pairs in one call (at most 2^20)", n);
+  GM_MSM_LOCK(C);
+  GtTmp d(C);
+  GM_HIP(dev_malloc((void**)&d.p, n * GT_BYTES));
+  const PairRange r{d_g1, d_g2, (long long)first1, (long long)step1, (long long)first2, (long long)step2, (unsigned long long)n};
+  C->prof.begin(PROF_ACC0, C->stream);
+  hipLaunchKernelGGL(k_miller_each, dim3((unsigned)((n + PAIR_BLOCK - 1) / PAIR_BLOCK)), dim3(PAIR_BLOCK), 0, C->stream, r, d.p);
+  C->prof.end(PROF_ACC0, C->stream);
+  GM_HIP(hipGetLastError());
+  int rc = gt_final_exp_launch(C, d.p, n, 1, d.p);
+  if (!rc) rc = gt_to_host(C, d.p, n, out_gt);
+  return rc;
+}
+int pairing_each_host(Context* C, const void* g1, size_t stride1, const void* g2, size_t stride2, size_t n, uint64_t* out_gt) {
+  std::unique_ptr<Bases> b1;
+  std::unique_ptr<G2Bases> b2;
+  int rc = bases_from_host(C, g1, stride1, n, b1);
+  if (!rc) rc = g2_bases_from_host(C, g2, stride2, n, b2);
+  if (!rc) rc = pairing_each_run(C, b1->d, 0, 1, b2->d, 0, 1, n, out_gt);
+  if (b1 && b1->d) (void)gm::raw_free(b1->d);
+  if (b2 && b2->d) (void)gm::raw_free(b2->d);
+  return rc;
+}
+
+// k_gt_check over n records on the device (host_form: 72 x u64 of ark-ff's form as copied, else device records); *ok was cleared
+// by the entry.  n = 0 passes.
+int gt_check_run(Context* C, const uint8_t* d_src, int host_form, size_t n, uint8_t* status_or_null, size_t* first_bad, int* ok) {
+  if (n == 0) {
+    if (first_bad) *first_bad = 0;
+    *ok = 1;
+    return GM_OK;
+  }
+  size_t blocks;
+  int rc = gt_slots_ensure(C, n, &blocks);
+  if (rc) return rc;
+  const size_t st_bytes = (n + 15) & ~(size_t)15;  // status bytes, then one u32 per block
+  GtTmp rep(C);
+  GM_HIP(dev_malloc((void**)&rep.p, st_bytes + blocks * 4));
+  uint32_t* d_sum = reinterpret_cast<uint32_t*>(rep.p + st_bytes);
+  hipLaunchKernelGGL(k_gt_check, dim3((unsigned)blocks), dim3(PAIR_BLOCK), 0, C->stream, d_src, host_form, n, C->pairing.gt_tab.as<uint32_t>(), rep.p, d_sum);
+  GM_HIP(hipGetLastError());
+  std::vector<uint32_t> s(blocks);
+  GM_HIP(hipMemcpyAsync(s.data(), d_sum, blocks * 4, hipMemcpyDeviceToHost, C->stream));
+  if (status_or_null) GM_HIP(hipMemcpyAsync(status_or_null, rep.p, n, hipMemcpyDeviceToHost, C->stream));
+  GM_HIP(hipStreamSynchronize(C->stream));
+  size_t fb = n;
+  for (size_t b = 0; b < blocks; b++)
+    if (s[b] != GT_NO_BAD) {
+      fb = b * PAIR_BLOCK + s[b];
+      break;
+    }
+  if (first_bad) *first_bad = fb;
+  *ok = fb == n ? 1 : 0;
+  return GM_OK;
+}
+int gt_check_host(Context* C, const uint64_t* x, size_t n, uint8_t* status_or_null, size_t* first_bad, int* ok) {
+  GM_CHECK(n <= GT_EACH_MAX, GM_EINVAL, "gt_check: %zu elements in one call (at most 2^20)", n);
+  GM_MSM_LOCK(C);
+  GtTmp stage(C);
+  if (n) {
+    GM_HIP(dev_malloc((void**)&stage.p, n * GT_BYTES));
+    GM_HIP(hipMemcpyAsync(stage.p, x, n * GT_BYTES, hipMemcpyHostToDevice, C->stream));
+  }
+  return gt_check_run(C, stage.p, 1, n, status_or_null, first_bad, ok);
+}
+
+// gm_debug_gt_op
+int gt_debug_op(Context* C, int op, const uint64_t* in, size_t n, uint64_t* out) {
+  GM_CHECK(op >= GT_OP_FROBENIUS1 && op <= GT_OP_POW_X, GM_EINVAL, "debug_gt_op: unknown op %d", op);
+  GM_MSM_LOCK(C);
+  size_t blocks;
+  int rc = gt_slots_ensure(C, n, &blocks);
+  if (rc) return rc;
+  GtTmp d(C);
+  if ((rc = gt_from_host(C, in, n, &d.p))) return rc;
+  hipLaunchKernelGGL(k_gt_debug_op, dim3((unsigned)blocks), dim3(PAIR_BLOCK), 0, C->stream, op, d.p, n, C->pairing.gt_tab.as<uint32_t>(), d.p);
+  GM_HIP(hipGetLastError());
+  return gt_to_host(C, d.p, n, out);
 }
 
 }  // namespace gm

@@ -65,17 +65,6 @@ GM_DEV FqE pt_const(const uint32_t (&c)[12]) {
   return r;
 }
 GM_DEV FqE pt_four() { return fq_dbl(fq_dbl(fqe_one())); }
-// the limbs as an integer: >= q?
-GM_DEV bool pt_raw_ge_q(const Fq& a) {
-  uint32_t borrow = 0;
-#pragma unroll
-  for (int i = 0; i < 12; i++) {
-    uint32_t b;
-    (void)__builtin_subc(a.l[i], FqParams::MOD[i], borrow, &b);
-    borrow = b;
-  }
-  return borrow == 0;
-}
 // a > b as integers
 GM_DEV bool pt_raw_gt(const Fq& a, const Fq& b) {
   uint32_t borrow = 0;

@@ -129,3 +129,10 @@ class GtModuleTimeProver(_ModuleTimeProver):
         capi.check(capi.load().gm_hgt_new(capi.ptr(fg), C.c_size_t(len(fg)), capi.ptr(gm_), C.c_size_t(len(gm_)),
                                           capi.ptr(capi.u64(twist_mont).reshape(4)), C.byref(h)))
         self.handle = h.value
+
+    def check(self):
+        """gm_hgt_check: the GT membership test (pairing.gt_check) over the CURRENT f vector, where it lies on the device; a
+        points.ProofCheckResult (ok, first_bad = the smallest bad index, the length when all pass)"""
+        from .points import check_proof
+
+        return check_proof(capi.load().gm_hgt_check, C.c_uint64(self.handle))

@@ -260,10 +260,17 @@ class InnerProductProof:
 
     def check_points(self):
         """gm_ipa_check: every G1 and G2 element verify_transcript reads from the proof (the G1 ones first); a points.ProofCheckResult.
-        The GT elements of the messages are NOT checked for membership."""
+        The GT elements of the messages are checked by `check_messages`."""
         from .points import check_proof
 
         return check_proof(capi.load().gm_ipa_check, C.c_uint64(self.handle))
+
+    def check_messages(self):
+        """gm_ipa_check_gt: GT membership of the 2 rounds message elements (a of round i is index 2 i, b is 2 i + 1); a
+        points.ProofCheckResult"""
+        from .points import check_proof
+
+        return check_proof(capi.load().gm_ipa_check_gt, C.c_uint64(self.handle))
 
     def host_times(self) -> dict:
         """what gm_ipa_new spent on the host making this proof, ms (a measurement aid: tools/ipa_bench.py)"""

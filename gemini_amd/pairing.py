@@ -10,11 +10,13 @@ what herring calls "+" on GT is `gt_mul`.  The value is the reduced ate pairing 
 from __future__ import annotations
 
 import ctypes as C
+import enum
 
 import numpy as np
 
 from . import capi
 from .g2msm import G2Bases, _fq_int, _fq_limbs, _records as _g2_records
+from .points import CheckResult
 
 
 def gt_from_ints(coeffs) -> np.ndarray:
@@ -76,6 +78,45 @@ def gt_final_exp(f) -> np.ndarray:
     return out
 
 
+def gt_final_exp_many(f) -> np.ndarray:
+    """out[i] = f[i]^((q^12 - 1) / r) on the device (gm_gt_final_exp_many): (n, 72) limbs in and out, no conjugation; bit for bit
+    `gt_final_exp` element by element on any reduced coefficients"""
+    capi.ensure_init()
+    fs = capi.u64(f).reshape(-1, 72)
+    out = np.empty_like(fs)
+    capi.check(capi.load().gm_gt_final_exp_many(capi.ptr(fs), C.c_size_t(len(fs)), capi.ptr(out)))
+    return out
+
+
+class GtStatus(enum.IntEnum):
+    """the GM_PT_* values gm_gt_check reports: the FIRST test of an element that fails, in this order"""
+    OK = 0
+    NONCANONICAL = 2       # a coefficient >= q
+    NOT_CYCLOTOMIC = 5     # f = 0 or f^(q^4) f != f^(q^2)
+    NOT_IN_SUBGROUP = 4    # f^q != f^x
+
+
+def gt_check(x) -> CheckResult:
+    """gm_gt_check: is every element of x ((n, 72) limbs) a member of GT, the order-r subgroup of Fq12*?  A points.CheckResult whose
+    status holds GtStatus values; a bad element is a result, not an exception."""
+    capi.ensure_init()
+    xs = capi.u64(x).reshape(-1, 72)
+    status = np.zeros(len(xs), dtype=np.uint8)
+    first_bad, ok = C.c_size_t(0), C.c_int(0)
+    capi.check(capi.load().gm_gt_check(capi.ptr(xs), C.c_size_t(len(xs)), capi.ptr(status), C.byref(first_bad), C.byref(ok)))
+    return CheckResult(bool(ok.value), first_bad.value, status)
+
+
+def debug_gt_op(op: int, x) -> np.ndarray:
+    """gm_debug_gt_op, a test aid: ONE device function per element of x ((n, 72) limbs).  op 0: x^q, 1: x^(q^2), 2: 1 / x,
+    3: the cyclotomic squaring, 4: x^|x_BLS| by cyclotomic squarings (3 and 4 are valid on the cyclotomic subgroup only)"""
+    capi.ensure_init()
+    xs = capi.u64(x).reshape(-1, 72)
+    out = np.empty_like(xs)
+    capi.check(capi.load().gm_debug_gt_op(C.c_int(op), capi.ptr(xs), C.c_size_t(len(xs)), capi.ptr(out)))
+    return out
+
+
 def _g1_records(bases) -> np.ndarray:
     bases = capi.u64(bases)
     assert bases.ndim == 2 and bases.shape[1] in (12, 13)
@@ -99,4 +140,23 @@ def multi_pairing_h(g1_bases, g2_bases: G2Bases, n: int, off1: int = 0, step1: i
     out = np.empty(72, dtype=np.uint64)
     capi.check(capi.load().gm_pairing_multi_h(C.c_uint64(g1_bases.handle), C.c_size_t(off1), C.c_size_t(step1), C.c_uint64(g2_bases.handle),
                                               C.c_size_t(off2), C.c_size_t(step2), C.c_size_t(n), capi.ptr(out)))
+    return out
+
+
+def pairing_each(g1, g2, n: int | None = None, off1: int = 0, step1: int = 1, off2: int = 0, step2: int = 1) -> np.ndarray:
+    """out[i] = e(P_i, Q_i), (n, 72) limbs: one launch of Miller loops and one of final exponentiations (gm_pairing_each).  g1 / g2
+    are host records (zip: the shorter input ends the vector) or BOTH registered handles (G1Bases, G2Bases), then
+    out[i] = e(g1[off1 + step1 i], g2[off2 + step2 i]) for i < n (gm_pairing_each_h)."""
+    capi.ensure_init()
+    if isinstance(g2, G2Bases):
+        assert hasattr(g1, "handle") and n is not None, "handles on both sides, and n"
+        out = np.empty((n, 72), dtype=np.uint64)
+        capi.check(capi.load().gm_pairing_each_h(C.c_uint64(g1.handle), C.c_size_t(off1), C.c_size_t(step1), C.c_uint64(g2.handle), C.c_size_t(off2),
+                                                 C.c_size_t(step2), C.c_size_t(n), capi.ptr(out)))
+        return out
+    r1, r2 = _g1_records(g1), _g2_records(g2)
+    m = min(len(r1), len(r2)) if n is None else n
+    assert m <= min(len(r1), len(r2))
+    out = np.empty((m, 72), dtype=np.uint64)
+    capi.check(capi.load().gm_pairing_each(capi.ptr(r1), C.c_size_t(r1.shape[1] * 8), capi.ptr(r2), C.c_size_t(r2.shape[1] * 8), C.c_size_t(m), capi.ptr(out)))
     return out

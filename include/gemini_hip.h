@@ -575,6 +575,39 @@ int gm_hgt_rounds(uint64_t handle, size_t* tot_rounds, size_t* round);
 int gm_hgt_final(uint64_t handle, uint64_t f0_gt[72], uint64_t g0_mont[4], int* has);
 int gm_hgt_free(uint64_t handle);
 
+/* ---- GT element by element on the device: final exponentiation, pairings, membership (gemini_amd/csrc/pairing.hip) ------
+ * Vectors of GT elements: `BilinearModule::p` of PModule is P::pairing(a, b) (src/herring/module.rs:67), and the GtModule prover
+ * above consumes 2^10 .. 2^14 of them.  One lane per element, 64 lanes per block; a launch is milliseconds deep whatever n is
+ * (profiles/gt_device.md gives the n from which the device beats the host loop; calls that make ONE final exponentiation --
+ * gm_pairing_multi*, gm_hp_round, gm_ipa_new, gm_ipa_verify, the verifiers -- stay on the host function).  At most 2^20 elements
+ * per call.  Calls share the MSM lock.
+ * The final exponentiation splits (q^12 - 1) / r = (q^6 - 1)(q^2 + 1) h with, for x = -0xd201000000010000,
+ *   h = (q^4 - q^2 + 1) / r = ((x - 1)^2 / 3)(x + q)(x^2 + q^2 - 1) + 1,
+ * an exact identity: the value is gm_gt_final_exp's bit for bit on ANY 12 reduced Fq coefficients (0 gives 0), not its cube.
+ * gm_gt_final_exp_many: out[i] = in[i]^((q^12 - 1) / r), no conjugation; n = 0 is a no-op.
+ * gm_pairing_each / _h: out[i] = e(P_i, Q_i) -- ONE launch of Miller loops and ONE of final exponentiations, the Miller values
+ * never leave the device.  Records, ranges and steps as for gm_pairing_multi / gm_pairing_multi_h; a pair with a point at
+ * infinity gives 1.
+ * gm_gt_check / gm_hgt_check / gm_ipa_check_gt: is every element a member of GT, the subgroup of order r of Fq12*?  Conventions of
+ * the point-validation block below: *ok = 0 is written before anything else, a bad element is a result (GM_OK, *ok = 0, *first_bad
+ * the smallest bad index; all good: *ok = 1, *first_bad = n), negative codes are for misuse only.  One status per element, the FIRST
+ * test that fails:
+ *   GM_PT_NONCANONICAL      a coefficient >= q (host input only)
+ *   GM_PT_NOT_CYCLOTOMIC    f = 0 or f^(q^4) f != f^(q^2): not in the cyclotomic subgroup
+ *   GM_PT_NOT_IN_SUBGROUP   f^q != f^x
+ * The last two together give f^(x^4 - x^2 + 1) = f^r = 1 (r = x^4 - x^2 + 1 for BLS12).  1 is a member.
+ * gm_hgt_check: the CURRENT f vector of a GtModule prover (folded as far as the rounds went), where it lies, no copy.
+ * gm_ipa_check_gt: the 2 rounds message elements of a proof; a of round i is index 2 i, b is index 2 i + 1. */
+int gm_gt_final_exp_many(const uint64_t* in /* n x 72 */, size_t n, uint64_t* out /* n x 72 */);
+int gm_pairing_each(const void* g1, size_t g1_stride, const void* g2, size_t g2_stride, size_t n, uint64_t* out_gt /* n x 72 */);
+int gm_pairing_each_h(uint64_t g1_handle, size_t off1, size_t step1, uint64_t g2_handle, size_t off2, size_t step2, size_t n, uint64_t* out_gt /* n x 72 */);
+int gm_gt_check(const uint64_t* x /* n x 72 */, size_t n, uint8_t* status_or_null, size_t* first_bad, int* ok);
+int gm_hgt_check(uint64_t handle, size_t* first_bad, int* ok);
+int gm_ipa_check_gt(uint64_t proof, size_t* first_bad, int* ok);
+/* A test aid: ONE device function of gt.cuh per lane over n x 72 limbs.  op 0: in^q, 1: in^(q^2), 2: 1 / in (0 gives 0),
+ * 3: the cyclotomic squaring (in^2 on the cyclotomic subgroup ONLY), 4: in^|x| by cyclotomic squarings (likewise). */
+int gm_debug_gt_op(int op, const uint64_t* in, size_t n, uint64_t* out);
+
 /* ---- herring's inner-product argument: Crs, Vrs, InnerProductProof (gemini_amd/csrc/ipa.hip) -------------------------
  * src/herring/ipa.rs: InnerProductProof::new (:533-685) proves <a, b> = y together with comm_a = <a, crs.g1> and
  * comm_b = <b, crs.g2> in one batched sumcheck over GT; verify_transcript (:250-343) checks it against the Vrs of the CRS.
@@ -1074,7 +1107,7 @@ int gm_psnark_new_time_sharded(const gm_psnark_shard* shard, int g1_encoding, si
  * (GM_EINVAL), an unknown handle (GM_EHANDLE), no gm_init (GM_ENOTINIT).  Every entry writes *ok = 0 (and gm_g1_bases_from_bytes
  * *handle = 0) before it does anything else, gm_init or not, so a negative return value always comes with *ok = 0: the checks fail
  * closed.  Only status bytes and one word per block of points come back from the device.  The calls share the MSM lock of the Threading paragraph above. */
-enum { GM_PT_OK = 0, GM_PT_BAD_ENCODING = 1, GM_PT_NONCANONICAL = 2, GM_PT_NOT_ON_CURVE = 3, GM_PT_NOT_IN_SUBGROUP = 4 };
+enum { GM_PT_OK = 0, GM_PT_BAD_ENCODING = 1, GM_PT_NONCANONICAL = 2, GM_PT_NOT_ON_CURVE = 3, GM_PT_NOT_IN_SUBGROUP = 4, GM_PT_NOT_CYCLOTOMIC = 5 /* gm_gt_check only */ };
 /* Host records as gm_g1_bases_register / gm_g2_bases_register take them (ark-ff Montgomery limbs, stride >= 96 / 192 and a multiple
  * of 8, the infinity byte at 96 / 192 when the stride has room).  A record is the identity exactly when registration reads it as
  * the identity: the infinity byte is set (whatever the coordinates hold) or every coordinate limb is zero.  GM_PT_NONCANONICAL: the
@@ -1125,8 +1158,8 @@ int gm_vk_check(uint64_t vk, size_t* first_bad_g1, size_t* first_bad_g2, int* ok
  *            ralpha_star_acc_mu_proof, fold_commitments[0 .. nfold), evaluation_proof
  *   ipa      G1: foldings_fg1's lhs, the Lhs final foldings; then G2: foldings_fg2's rhs, the Rhs final foldings
  * The commitments a caller passes to gm_ipa_verify beside the proof are its own to check (gm_g1_check, gm_g2_check).  The GT
- * elements of an IPA proof (its messages) are NOT checked for membership: that needs a cyclotomic or order-r test this library does
- * not have. */
+ * elements of an IPA proof (its messages) are not checked here: gm_ipa_check_gt (the GT block above) runs the membership test
+ * over them. */
 int gm_snark_proof_check(const gm_snark_proof* proof, size_t* first_bad, int* ok);
 int gm_psnark_proof_check(const gm_psnark_proof* proof, size_t* first_bad, int* ok);
 int gm_ipa_check(uint64_t proof, size_t* first_bad, int* ok);

@@ -129,7 +129,7 @@ struct G1Affine {                          // Rust layout: x, y, infinity (104-b
 static_assert(sizeof(G1Affine) == 104, "G1Affine must match the 104-byte Rust record");
 
 // ---- point validation (the block of the same name in gemini_hip.h).  A bad point is a result, never an exception ---------------
-enum class PointStatus : uint8_t { Ok = GM_PT_OK, BadEncoding = GM_PT_BAD_ENCODING, NonCanonical = GM_PT_NONCANONICAL, NotOnCurve = GM_PT_NOT_ON_CURVE, NotInSubgroup = GM_PT_NOT_IN_SUBGROUP };
+enum class PointStatus : uint8_t { Ok = GM_PT_OK, BadEncoding = GM_PT_BAD_ENCODING, NonCanonical = GM_PT_NONCANONICAL, NotOnCurve = GM_PT_NOT_ON_CURVE, NotInSubgroup = GM_PT_NOT_IN_SUBGROUP, NotCyclotomic = GM_PT_NOT_CYCLOTOMIC /* check_gt only */ };
 struct PointCheck {
   bool ok = false;
   size_t first_bad = 0;         // the smallest bad index; n when every point passes
@@ -778,7 +778,42 @@ struct HerringGtModule {
   static constexpr auto free = gm_hgt_free;
 };
 }  // namespace detail
-using HerringGt = detail::HerringModuleProver<detail::HerringGtModule>;
+// check(): GT membership of the CURRENT f vector, where it lies on the device (gm_hgt_check); first_bad is its length when all pass
+class HerringGt : public detail::HerringModuleProver<detail::HerringGtModule> {
+ public:
+  using detail::HerringModuleProver<detail::HerringGtModule>::HerringModuleProver;
+  ProofCheck check() const {
+    ProofCheck r;
+    int ok = 0;
+    gm::check(gm_hgt_check(handle(), &r.first_bad, &ok));
+    r.ok = ok != 0;
+    return r;
+  }
+};
+
+// ---- GT element by element on the device (the block of the same name in gemini_hip.h) --------------------------------------------
+// out[i] = in[i]^((q^12 - 1) / r), no conjugation: gm_gt_final_exp's value bit for bit, on any reduced coefficients
+inline std::vector<Gt> gt_final_exp_many(const std::vector<Gt>& in) {
+  std::vector<Gt> out(in.size());
+  check(gm_gt_final_exp_many(in.empty() ? nullptr : in[0].data(), in.size(), out.empty() ? nullptr : out[0].data()));
+  return out;
+}
+// out[i] = e(g1[i], g2[i]) over the shorter input (zip): one launch of Miller loops, one of final exponentiations
+inline std::vector<Gt> pairing_each(const std::vector<G1Affine>& g1, const std::vector<G2Affine>& g2) {
+  std::vector<Gt> out(g1.size() < g2.size() ? g1.size() : g2.size());
+  check(gm_pairing_each(g1.data(), sizeof(G1Affine), g2.data(), sizeof(G2Affine), out.size(), out.empty() ? nullptr : out[0].data()));
+  return out;
+}
+// the same over registered bases: out[i] = e(g1[off1 + step1 i], g2[off2 + step2 i]), i < n
+inline std::vector<Gt> pairing_each(uint64_t g1_handle, size_t off1, size_t step1, const G2Bases& g2, size_t off2, size_t step2, size_t n) {
+  std::vector<Gt> out(n);
+  check(gm_pairing_each_h(g1_handle, off1, step1, g2.handle(), off2, step2, n, out.empty() ? nullptr : out[0].data()));
+  return out;
+}
+// gm_gt_check: is every element a member of GT?  status holds GM_PT_OK / GM_PT_NONCANONICAL / GM_PT_NOT_CYCLOTOMIC / GM_PT_NOT_IN_SUBGROUP
+inline PointCheck check_gt(const std::vector<Gt>& x) {
+  return detail::point_check(x.size(), [&](uint8_t* st, size_t* fb, int* ok) { return gm_gt_check(x.empty() ? nullptr : x[0].data(), x.size(), st, fb, ok); });
+}
 
 // merlin::Transcript + GeminiTranscript, src/transcript.rs
 class Transcript {
@@ -1005,11 +1040,19 @@ class InnerProductProof {  // ipa.rs:54-60
     check(gm_ipa_foldings_fg2(h_, r.first.data(), r.second.data()));
     return r;
   }
-  // every G1 and G2 element verify_transcript reads from the proof, the G1 ones first (gm_ipa_check); GT elements are NOT checked
+  // every G1 and G2 element verify_transcript reads from the proof, the G1 ones first (gm_ipa_check); the GT elements: check_messages
   ProofCheck check_points() const {
     ProofCheck r;
     int ok = 0;
     check(gm_ipa_check(h_, &r.first_bad, &ok));
+    r.ok = ok != 0;
+    return r;
+  }
+  // GT membership of the 2 rounds message elements (gm_ipa_check_gt): a of round i is index 2 i, b is 2 i + 1
+  ProofCheck check_messages() const {
+    ProofCheck r;
+    int ok = 0;
+    check(gm_ipa_check_gt(h_, &r.first_bad, &ok));
     r.ok = ok != 0;
     return r;
   }
