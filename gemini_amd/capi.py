@@ -54,6 +54,8 @@ SYMBOLS = [
     "gm_ipa_new", "gm_ipa_rounds", "gm_ipa_messages", "gm_ipa_challenges", "gm_ipa_batch_challenges", "gm_ipa_final_foldings", "gm_ipa_foldings_ff",
     "gm_spm_bilinear_pm", "gm_vk_new", "gm_vk_from_trapdoor", "gm_vk_free", "gm_vk_len", "gm_vk_g2_bytes", "gm_kzg_verify", "gm_kzg_verify_multi_points",
     "gm_sumcheck_subclaim", "gm_sumcheck_subclaim_batch", "gm_tensorcheck_verify", "gm_snark_verify", "gm_psnark_verify",
+    "gm_g1_lincomb_many", "gm_pairing_multi_many", "gm_pairing_multi_many_h", "gm_set_verify_many_min", "gm_kzg_verify_multi_points_many", "gm_snark_verify_many",
+    "gm_psnark_verify_many",
     "gm_g1_check", "gm_g2_check", "gm_g1_bases_check", "gm_g2_bases_check", "gm_g1_bases_from_bytes", "gm_g1_powers_check",
     "gm_g2_bases_from_bytes", "gm_g1_bases_to_bytes", "gm_g2_bases_to_bytes", "gm_crs_from_bases", "gm_crs_check", "gm_vk_check",
     "gm_snark_proof_check", "gm_psnark_proof_check", "gm_ipa_check", "gm_debug_fq2_sqrt",

@@ -430,6 +430,9 @@ void gm_shutdown(void) {
   for (auto& kv : C->g2_bases)
     if (kv.second->d) (void)gm::raw_free(kv.second->d);
   for (auto& kv : C->crs) crs_destroy(kv.second.get());
+  for (auto& kv : C->vks)
+    if (kv.second->d_g2) (void)gm::raw_free(kv.second->d_g2);
+  C->lincomb.release();
   C->partial_bufs.release_all();
   for (auto& kv : C->indices)
     if (kv.second->d) (void)gm::raw_free(kv.second->d);
@@ -505,6 +508,12 @@ int gm_prof_read(double* ms_out, uint64_t* count_out, int n) {
 int gm_set_msm_table_min(size_t n) {
   GM_CTX();
   C->msm_table_min = n;
+  return GM_OK;
+}
+
+int gm_set_verify_many_min(size_t checks) {
+  GM_CTX();
+  C->verify_many_min = checks;
   return GM_OK;
 }
 
@@ -928,6 +937,15 @@ int gm_g1_msm(const void* bases, size_t base_stride, const uint64_t* scalars, si
   rc = msm_host_scalars(C, b.get(), 0, 0, scalars, n, out_jac);
   if (b->d) (void)gm::raw_free(b->d);
   return rc;
+}
+
+// S short linear combinations in a fixed number of launches (msm.hip: k_g1_term_mul, k_g1_seg_sum)
+int gm_g1_lincomb_many(const void* points, size_t stride, const uint64_t* scalars_canonical, const size_t* offsets, size_t S, uint64_t* out_jac) {
+  GM_CTX();
+  if (S == 0) return GM_OK;
+  GM_CHECK(offsets != nullptr && out_jac != nullptr, GM_EINVAL, "lincomb_many: null pointer");
+  GM_CHECK((points != nullptr && scalars_canonical != nullptr) || offsets[S] == 0, GM_EINVAL, "lincomb_many: null pointer");
+  return g1_lincomb_many_host(C, points, stride, scalars_canonical, offsets, S, out_jac);
 }
 
 int gm_g1_msm_h(uint64_t handle, size_t offset, int reversed, const uint64_t* scalars, size_t n, uint64_t out_jac[18]) {
@@ -1989,6 +2007,41 @@ int gm_pairing_multi_h(uint64_t g1_handle, size_t off1, size_t step1, uint64_t g
   GM_CHECK(off2 < b2->n && (n - 1) <= (b2->n - 1 - off2) / step2, GM_EINVAL, "pairing_multi_h: G2 range %zu + %zu * [0, %zu) outside %zu bases", off2, step2, n,
            b2->n);
   return pairing_run(C, b1->d, (int64_t)off1, (int64_t)step1, b2->d, (int64_t)off2, (int64_t)step2, n, out_gt);
+}
+// S independent products in one call (pairing.hip: pairing_products): one k_miller_seg, the k_gt_reduce_seg levels of products
+// longer than a block, one k_gt_final_exp and one wait, whatever S is
+int gm_pairing_multi_many(const void* g1, size_t g1_stride, const void* g2, size_t g2_stride, const size_t* offsets, size_t S, uint64_t* out_gt) {
+  GM_CTX();
+  if (S == 0) return GM_OK;
+  GM_CHECK(offsets != nullptr && out_gt != nullptr, GM_EINVAL, "pairing_multi_many: null pointer");
+  GM_CHECK((g1 != nullptr && g2 != nullptr) || offsets[S] == 0, GM_EINVAL, "pairing_multi_many: null pointer");
+  return pairing_products_host(C, g1, g1_stride, g2, g2_stride, offsets, S, out_gt);
+}
+// product s over the pairs (g1[off1 + t], g2[off2 + t]), offsets[s] <= t < offsets[s + 1], of registered bases
+int gm_pairing_multi_many_h(uint64_t g1_handle, size_t off1, uint64_t g2_handle, size_t off2, const size_t* offsets, size_t S, uint64_t* out_gt) {
+  GM_CTX();
+  Bases* b1 = find_bases(g1_handle);
+  GM_CHECK(b1 != nullptr, GM_EHANDLE, "pairing_multi_many_h: unknown G1 bases handle %llu", (unsigned long long)g1_handle);
+  GM_G2B(b2, g2_handle, "pairing_multi_many_h");
+  if (S == 0) return GM_OK;
+  GM_CHECK(offsets != nullptr && out_gt != nullptr, GM_EINVAL, "pairing_multi_many_h: null pointer");
+  GM_CHECK(offsets[0] == 0, GM_EINVAL, "pairing_multi_many_h: offsets[0] = %zu, the first product starts at 0", offsets[0]);
+  for (size_t s = 0; s < S; s++)
+    GM_CHECK(offsets[s] <= offsets[s + 1], GM_EINVAL, "pairing_multi_many_h: offsets[%zu] = %zu is above offsets[%zu] = %zu", s, offsets[s], s + 1, offsets[s + 1]);
+  const size_t n = offsets[S];
+  GM_CHECK(off1 <= b1->n && n <= b1->n - off1, GM_EINVAL, "pairing_multi_many_h: G1 range [%zu, %zu) outside %zu bases", off1, off1 + n, b1->n);
+  GM_CHECK(off2 <= b2->n && n <= b2->n - off2, GM_EINVAL, "pairing_multi_many_h: G2 range [%zu, %zu) outside %zu bases", off2, off2 + n, b2->n);
+  std::vector<PairProduct> prods(S);
+  for (size_t s = 0; s < S; s++) {
+    PairSpan& p = prods[s].s0;
+    p.g1 = b1->d;
+    p.g2 = b2->d;
+    p.first1 = (int64_t)(off1 + offsets[s]);
+    p.first2 = (int64_t)(off2 + offsets[s]);
+    p.n = offsets[s + 1] - offsets[s];
+  }
+  GM_MSM_LOCK(C);
+  return pairing_products(C, prods.data(), S, out_gt);
 }
 int gm_gt_one(uint64_t out_gt[72]) {
   GM_CHECK(out_gt != nullptr, GM_EINVAL, "gt_one: null pointer");

@@ -194,6 +194,7 @@ struct VerifierKey {
   std::vector<uint64_t> g1;  // n1 x 12 limbs: the first max_eval_points powers of g
   std::vector<uint64_t> g2;  // n2 x 24 limbs: max_eval_points + 1 powers of g2
   size_t n1 = 0, n2 = 0;
+  uint8_t* d_g2 = nullptr;  // the same n2 powers of g2 resident on the device (192-byte records): the batched checks pair against them
 };
 
 // G2 bases (g2msm.hip): n x 192 bytes, x.c0 | x.c1 | y.c0 | y.c1 in the device form of g1.cuh; identity = all zero
@@ -370,6 +371,8 @@ struct Context {
   hipStream_t part_tail[2 + MSM_SMALL_LANES] = {};
   hipEvent_t start_ev;  // recorded on `stream` when an MSM call starts: its other streams wait for the producer of the scalars
   bool have_start_ev = false;
+  DevBuf lincomb;  // gm_g1_lincomb_many and the batched KZG checks: staged terms, their multiples and the sums of a call (under msm_mu)
+  size_t verify_many_min = 3;  // fewer stated KZG checks than this take the per-check path (gm_set_verify_many_min); 2 is a tie: profiles/verify_many.md
   DevBuf fr_scratch;
   uint64_t* host_small = nullptr;  // pinned, 64 KiB, for small results
   // the descriptor arrays of k_sc_round_multi: a RING of SC_DESC_SLOTS slots of SC_DESC_SLOT bytes, one per launch, pinned on the host
@@ -506,6 +509,12 @@ int bases_from_host(Context* C, const void* bases, size_t stride, size_t n, std:
 // out[i] = in[2i] + s in[2i+1] over packed affine records (an odd tail folds against the identity), s at d_s8 (canonical, 8 x u32), on C->stream
 int g1_split_fold_launch(Context* C, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out);
 
+// S short linear combinations out[s] = sum_{offsets[s] <= t < offsets[s+1]} scalar[t] P[t] (k_g1_term_mul, k_g1_seg_sum,
+// k_xyzz_to_affine_batch): host records of `stride` bytes and canonical scalars in, S packed affine device records at *d_aff (a
+// region of C->lincomb), on C->stream without a wait.  Caller holds the MSM lock and keeps the three host arrays until it has waited.
+int g1_lincomb_many_launch(Context* C, const void* points, size_t stride, const uint64_t* scalars_canonical, const size_t* offsets, size_t S, uint8_t** d_aff);
+int g1_lincomb_many_host(Context* C, const void* points, size_t stride, const uint64_t* scalars_canonical, const size_t* offsets, size_t S, uint64_t* out_jac);
+
 // Fr vectors (fr.hip), on C->stream without a wait
 int fr_stride_raw(Context* C, const uint8_t* in, size_t start, size_t stride, size_t count, uint8_t* out);
 int fr_fold_raw(Context* C, const uint8_t* f, size_t n, const uint64_t r[4], uint8_t* out);  // r is read by an asynchronous copy: the caller waits
@@ -536,6 +545,13 @@ struct PairProduct {
 int miller_products(Context* C, const PairProduct* prods, size_t S, gmh::Fq12* out);
 // the same S products as GT elements (S x 72 limbs): conjugation and ONE k_gt_final_exp launch over the Miller values on the device
 int pairing_products(Context* C, const PairProduct* prods, size_t S, uint64_t* out_gt);
+// gm_pairing_multi_many: product s is over the host pairs [offsets[s], offsets[s + 1])
+int pairing_products_host(Context* C, const void* g1, size_t stride1, const void* g2, size_t stride2, const size_t* offsets, size_t S, uint64_t* out_gt);
+// The batched KZG checks (verifier.cpp): one g1_lincomb_many_launch over all segments, then check s is the product of the pairs
+// (sum[check_seg[s] + j], d_g2[j == 0 ? 0 : j - 1]), j < check_seg[s + 1] - check_seg[s]: ONE k_miller_seg, ONE k_gt_final_exp, one wait.
+// ok[s] = the product is 1.
+int kzg_checks_run(Context* C, const uint8_t* d_g2, const void* points, size_t stride, const uint64_t* scalars_canonical, const size_t* seg_offsets,
+                   size_t nseg, const size_t* check_seg, size_t S, int* ok);
 // Miller product -> GT: conjugation (the loop parameter is negative), then the one final exponentiation
 void pairing_finish(const gmh::Fq12& miller, uint64_t out_gt[72]);
 

@@ -232,6 +232,24 @@ GM_DEV void xyzz_add(G1Xyzz& acc, const G1Xyzz& q) {
   acc.y = y3;
 }
 
+// k * p for the 256-bit integer k at s8 (8 x u32, least significant first), most significant bit first.  Nothing here is secret:
+// the doublings in front of the first set bit return at once (the identity), so a short scalar is a short loop.  k = 0 and the
+// identity give the identity; the additions are xyzz_madd's, complete.
+GM_DEV G1Xyzz xyzz_scalar_mul(const G1Affine& p, const uint32_t* __restrict__ s8) {
+  G1Xyzz acc = G1Xyzz::identity();
+  if (p.is_identity()) return acc;
+#pragma unroll 1
+  for (int w = 7; w >= 0; w--) {
+    const uint32_t word = s8[w];
+#pragma unroll 1
+    for (int bit = 31; bit >= 0; bit--) {
+      acc = xyzz_dbl(acc);
+      if ((word >> bit) & 1u) xyzz_madd(acc, p);
+    }
+  }
+  return acc;
+}
+
 // 96-byte affine / 192-byte XYZZ memory images (AoS, 16-byte aligned -> dwordx4 accesses); values at
 // rest are fully reduced
 GM_DEV G1Affine g1_load_affine(const void* p) {

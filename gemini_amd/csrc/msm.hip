@@ -1690,6 +1690,29 @@ __global__ __launch_bounds__(256) void k_g1_split_fold(const uint8_t* __restrict
   g1_store_affine(out + i * AFF_BYTES, a);
 }
 
+// ---- many short linear combinations (gm_g1_lincomb_many, the batched KZG checks): segments of tens of terms, thousands of them.
+// One lane per TERM makes the multiple (the latency of the call: ~255 doublings and ~128 additions, whatever the number of terms up
+// to one wave per SIMD), then one lane per SEGMENT adds its terms up, and k_xyzz_to_affine_batch normalises the sums.  Three
+// launches for any number of segments.
+__global__ __launch_bounds__(256) void k_g1_term_mul(const uint8_t* __restrict__ points, const uint32_t* __restrict__ scalars, size_t nterms,
+                                                     uint8_t* __restrict__ out_xyzz) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nterms) return;
+  const G1Affine p = g1_load_affine(points + t * AFF_BYTES);
+  g1_store_xyzz(out_xyzz + t * XYZZ_BYTES, xyzz_scalar_mul(p, scalars + 8 * t));
+}
+// out[s] = the sum of the terms [offsets[s], offsets[s + 1]); an empty segment is the identity.  xyzz_add is complete: two equal
+// terms double, opposite ones cancel.
+__global__ __launch_bounds__(256) void k_g1_seg_sum(const uint8_t* __restrict__ terms_xyzz, const unsigned long long* __restrict__ offsets, size_t nseg,
+                                                    uint8_t* __restrict__ out_xyzz) {
+  const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= nseg) return;
+  G1Xyzz acc = G1Xyzz::identity();
+#pragma unroll 1
+  for (unsigned long long t = offsets[s]; t < offsets[s + 1]; t++) xyzz_add(acc, g1_load_xyzz(terms_xyzz + (size_t)t * XYZZ_BYTES));
+  g1_store_xyzz(out_xyzz + s * XYZZ_BYTES, acc);
+}
+
 // table[(w + 1) * n + i] = 2^c * table[w * n + i]: c doublings and one normalisation per point
 __global__ __launch_bounds__(256) void k_table_next(const uint8_t* __restrict__ prev, uint8_t* __restrict__ next_xyzz, size_t n, int c) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -3312,6 +3335,62 @@ int g1_split_fold_launch(Context* C, const uint8_t* in, size_t n, const uint32_t
 }
 
 // table[w * n + i] = 2^(c w) * d[i], w < ceil(256 / c); row 0 is a copy of d
+// ---- gm_g1_lincomb_many ------------------------------------------------------------------------
+int g1_lincomb_many_launch(Context* C, const void* points, size_t stride, const uint64_t* scalars_canonical, const size_t* offsets, size_t S, uint8_t** d_aff) {
+  *d_aff = nullptr;
+  if (S == 0) return GM_OK;
+  GM_CHECK(stride >= 96 && (stride % 8) == 0, GM_EINVAL, "lincomb_many: stride %zu must be >= 96 and a multiple of 8", stride);
+  GM_CHECK(offsets[0] == 0, GM_EINVAL, "lincomb_many: offsets[0] = %zu, the first segment starts at 0", offsets[0]);
+  for (size_t s = 0; s < S; s++)
+    GM_CHECK(offsets[s] <= offsets[s + 1], GM_EINVAL, "lincomb_many: offsets[%zu] = %zu is above offsets[%zu] = %zu", s, offsets[s], s + 1, offsets[s + 1]);
+  const size_t T = offsets[S];
+  GM_CHECK(T <= ((size_t)1 << 28) && S <= ((size_t)1 << 28), GM_EINVAL, "lincomb_many: %zu terms in %zu segments (at most 2^28 of either)", T, S);
+  static_assert(sizeof(size_t) == sizeof(unsigned long long), "the offsets are copied as they are");
+  auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
+  const size_t o_raw = 0, o_pts = o_raw + up(T * stride), o_sc = o_pts + up(T * AFF_BYTES), o_off = o_sc + up(T * 32), o_terms = o_off + up((S + 1) * 8),
+               o_sums = o_terms + T * XYZZ_BYTES, o_aff = o_sums + S * XYZZ_BYTES, total = o_aff + S * AFF_BYTES;
+  int rc = C->lincomb.ensure(total);
+  if (rc) return rc;
+  uint8_t* w = C->lincomb.as<uint8_t>();
+  hipStream_t st = C->stream;
+  GM_HIP(hipMemcpyAsync(w + o_off, offsets, (S + 1) * 8, hipMemcpyHostToDevice, st));
+  if (T) {
+    GM_HIP(hipMemcpyAsync(w + o_raw, points, T * stride, hipMemcpyHostToDevice, st));
+    GM_HIP(hipMemcpyAsync(w + o_sc, scalars_canonical, T * 32, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_pack_bases, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, w + o_raw, stride, T, w + o_pts);
+    C->prof.begin(PROF_DIGITS, st);  // the stages a pairing does not use, so that one call reports all its kernels: term, sum, normalise
+    hipLaunchKernelGGL(k_g1_term_mul, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, w + o_pts, reinterpret_cast<const uint32_t*>(w + o_sc), T, w + o_terms);
+    C->prof.end(PROF_DIGITS, st);
+  }
+  C->prof.begin(PROF_SCAN, st);
+  hipLaunchKernelGGL(k_g1_seg_sum, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, w + o_terms, reinterpret_cast<const unsigned long long*>(w + o_off), S, w + o_sums);
+  C->prof.end(PROF_SCAN, st);
+  C->prof.begin(PROF_SCATTER, st);
+  hipLaunchKernelGGL(k_xyzz_to_affine_batch, dim3((unsigned)(((S + NORM_K - 1) / NORM_K + 255) / 256)), dim3(256), 0, st, w + o_sums, S, w + o_aff);
+  C->prof.end(PROF_SCATTER, st);
+  GM_HIP(hipGetLastError());
+  *d_aff = w + o_aff;
+  return GM_OK;
+}
+
+int g1_lincomb_many_host(Context* C, const void* points, size_t stride, const uint64_t* scalars_canonical, const size_t* offsets, size_t S, uint64_t* out_jac) {
+  if (S == 0) return GM_OK;
+  GM_MSM_LOCK(C);
+  uint8_t* d_aff = nullptr;
+  int rc = g1_lincomb_many_launch(C, points, stride, scalars_canonical, offsets, S, &d_aff);
+  std::vector<uint64_t> aff(12 * S);
+  if (!rc) {
+    hipError_t e = hipMemcpyAsync(aff.data(), d_aff, S * AFF_BYTES, hipMemcpyDeviceToHost, C->stream);
+    if (e != hipSuccess) rc = gm::hip_fail(e, "hipMemcpyAsync", __FILE__, __LINE__);
+  }
+  const hipError_t e = hipStreamSynchronize(C->stream);  // the host arrays are read by their copies until here
+  if (rc) return rc;
+  GM_HIP(e);
+  C->prof.collect();
+  for (size_t s = 0; s < S; s++) gmh::g1_affine_to_jac_dev(aff.data() + 12 * s).to_limbs(out_jac + 18 * s);
+  return GM_OK;
+}
+
 static int build_window_table(Context* C, const uint8_t* d, size_t n, int c, uint8_t** out) {
   const int W = (256 + c - 1) / c;
   uint8_t* t = nullptr;

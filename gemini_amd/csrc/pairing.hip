@@ -830,6 +830,65 @@ int pairing_products(Context* C, const PairProduct* prods, size_t S, uint64_t* o
   return GM_OK;
 }
 
+// gm_pairing_multi_many: host records on both sides, product s over the pairs [offsets[s], offsets[s + 1])
+int pairing_products_host(Context* C, const void* g1, size_t stride1, const void* g2, size_t stride2, const size_t* offsets, size_t S, uint64_t* out_gt) {
+  GM_CHECK(offsets[0] == 0, GM_EINVAL, "pairing_multi_many: offsets[0] = %zu, the first product starts at 0", offsets[0]);
+  for (size_t s = 0; s < S; s++)
+    GM_CHECK(offsets[s] <= offsets[s + 1], GM_EINVAL, "pairing_multi_many: offsets[%zu] = %zu is above offsets[%zu] = %zu", s, offsets[s], s + 1, offsets[s + 1]);
+  const size_t n = offsets[S];
+  std::unique_ptr<Bases> b1;
+  std::unique_ptr<G2Bases> b2;
+  int rc = bases_from_host(C, g1, stride1, n, b1);
+  if (!rc) rc = g2_bases_from_host(C, g2, stride2, n, b2);
+  if (!rc) {
+    std::vector<PairProduct> prods(S);
+    for (size_t s = 0; s < S; s++) {
+      PairSpan& p = prods[s].s0;
+      p.g1 = b1->d;
+      p.g2 = b2->d;
+      p.first1 = p.first2 = (int64_t)offsets[s];
+      p.n = offsets[s + 1] - offsets[s];
+    }
+    GM_MSM_LOCK(C);
+    rc = pairing_products(C, prods.data(), S, out_gt);
+  }
+  if (b1 && b1->d) (void)gm::raw_free(b1->d);
+  if (b2 && b2->d) (void)gm::raw_free(b2->d);
+  return rc;
+}
+
+// The batched KZG checks (ctx.hpp).  Everything is enqueued on C->stream behind the copies of the caller's arrays; the one wait is
+// pairing_products'.
+int kzg_checks_run(Context* C, const uint8_t* d_g2, const void* points, size_t stride, const uint64_t* scalars_canonical, const size_t* seg_offsets,
+                   size_t nseg, const size_t* check_seg, size_t S, int* ok) {
+  if (S == 0) return GM_OK;
+  GM_MSM_LOCK(C);
+  uint8_t* d_aff = nullptr;
+  int rc = g1_lincomb_many_launch(C, points, stride, scalars_canonical, seg_offsets, nseg, &d_aff);
+  if (rc) {
+    (void)hipStreamSynchronize(C->stream);
+    return rc;
+  }
+  std::vector<PairProduct> prods(S);
+  for (size_t s = 0; s < S; s++) {
+    const size_t first = check_seg[s], n = check_seg[s + 1] - first;
+    if (n == 0) continue;
+    PairSpan &a = prods[s].s0, &b = prods[s].s1;
+    a.g1 = b.g1 = d_aff;
+    a.g2 = b.g2 = d_g2;
+    a.first1 = (int64_t)first;  // L against g2
+    a.n = 1;
+    b.first1 = (int64_t)first + 1;  // the multiples of the proof element against the powers of tau
+    b.n = n - 1;
+  }
+  std::vector<uint64_t> gt(72 * S), one(72);
+  rc = pairing_products(C, prods.data(), S, gt.data());
+  if (rc) return rc;
+  gmh::Fq12::one().to_limbs(one.data());
+  for (size_t s = 0; s < S; s++) ok[s] = memcmp(gt.data() + 72 * s, one.data(), GT_BYTES) == 0 ? 1 : 0;
+  return GM_OK;
+}
+
 // Miller product -> GT: conjugation (the loop parameter is negative), then the one final exponentiation
 void pairing_finish(const gmh::Fq12& miller, uint64_t out_gt[72]) { gmh::gt_final_exponentiation(miller.conj()).to_limbs(out_gt); }
 

@@ -68,10 +68,30 @@ int pack_records(const void* src, size_t stride, size_t n, size_t bytes, std::ve
 // ---- the ONE KZG check ---------------------------------------------------------------------------------------------------
 // e(sum_i scalars[i] C_i - [I(tau)] g, g2) * e(-proof, [Z(tau)] g2) == 1 with Z the vanishing polynomial of `points` and I the
 // polynomial the claimed evaluations interpolate to (src/kzg/mod.rs:155-175 is the case of one commitment and one point)
+// A check as it is STATED: what kzg_check takes.  The *_many entries collect the checks of all their proofs (kzg_check with a
+// list answers *ok = 1 for the time being) and run_stated runs them together.
+struct StatedCheck {
+  std::vector<uint64_t> commitments_jac;  // 18 limbs per commitment
+  std::vector<Fr> scalars, i_poly, points;
+  uint64_t proof_jac[18];
+};
+using CheckList = std::vector<StatedCheck>;
+
 int kzg_check(const VerifierKey& vk, const uint64_t* commitments_jac, const std::vector<Fr>& scalars, const std::vector<Fr>& i_poly,
-              const std::vector<Fr>& points, const uint64_t proof_jac[18], int* ok) {
+              const std::vector<Fr>& points, const uint64_t proof_jac[18], int* ok, CheckList* defer = nullptr) {
   SC_CHECK(points.size() + 1 <= vk.n2 && i_poly.size() <= vk.n1, GM_EINVAL, "kzg verify: %zu evaluation points, the key holds %zu G1 and %zu G2 powers",
            points.size(), vk.n1, vk.n2);
+  if (defer) {
+    defer->emplace_back();
+    StatedCheck& c = defer->back();
+    c.commitments_jac.assign(commitments_jac, commitments_jac + 18 * scalars.size());
+    c.scalars = scalars;
+    c.i_poly = i_poly;
+    c.points = points;
+    memcpy(c.proof_jac, proof_jac, sizeof c.proof_jac);
+    *ok = 1;
+    return GM_OK;
+  }
   const std::vector<Fr> zeros = vanishing(points);
   std::vector<uint64_t> zc(4 * zeros.size());
   for (size_t d = 0; d < zeros.size(); d++) zeros[d].to_canonical(zc.data() + 4 * d);
@@ -102,6 +122,57 @@ int kzg_check(const VerifierKey& vk, const uint64_t* commitments_jac, const std:
   return GM_OK;
 }
 
+// The stated checks together, ok[i] for check i.  With Z(X) = sum_d z_d X^d the vanishing polynomial of the check's m points (monic),
+//   e(L, g2) e(-proof, [Z(tau)] g2) = e(L, g2) prod_{d <= m} e((r - z_d) proof, [tau^d] g2):
+// m + 2 pairs against the key's G2 powers as they stand, no G2 arithmetic.  Every G1 point of every check -- L and the m + 1
+// multiples of the proof element -- is one segment of ONE gm_g1_lincomb_many launch group; then one segmented Miller launch, one
+// final-exponentiation launch and one wait for the whole list (pairing.hip: kzg_checks_run).  A zero z_d, an identity proof element
+// or L = identity is an identity record, which k_miller_seg skips.  Fewer checks than gm_set_verify_many_min take kzg_check one by one:
+// the verdicts are the same (both sides compute the same element of GT), only the time differs.
+int run_stated(const VerifierKey& vk, const CheckList& checks, int* ok) {
+  GM_CTX();
+  if (checks.size() < C->verify_many_min || vk.d_g2 == nullptr) {
+    for (size_t i = 0; i < checks.size(); i++) {
+      const StatedCheck& c = checks[i];
+      RC(kzg_check(vk, c.commitments_jac.data(), c.scalars, c.i_poly, c.points, c.proof_jac, &ok[i]));
+    }
+    return GM_OK;
+  }
+  size_t nterms = 0, nsegs = 0;
+  for (const StatedCheck& c : checks) {
+    nterms += c.scalars.size() + c.i_poly.size() + c.points.size() + 1;
+    nsegs += c.points.size() + 2;
+  }
+  std::vector<uint64_t> bases(12 * nterms), sc(4 * nterms);
+  std::vector<size_t> seg_offsets, check_seg;
+  seg_offsets.reserve(nsegs + 1);
+  check_seg.reserve(checks.size() + 1);
+  size_t t = 0;
+  seg_offsets.push_back(0);
+  check_seg.push_back(0);
+  for (const StatedCheck& c : checks) {
+    for (size_t i = 0; i < c.scalars.size(); i++, t++) {
+      g1_record(c.commitments_jac.data() + 18 * i, bases.data() + 12 * t);
+      c.scalars[i].to_canonical(sc.data() + 4 * t);
+    }
+    for (size_t d = 0; d < c.i_poly.size(); d++, t++) {
+      memcpy(bases.data() + 12 * t, vk.g1.data() + 12 * d, 96);
+      c.i_poly[d].neg().to_canonical(sc.data() + 4 * t);
+    }
+    seg_offsets.push_back(t);  // L
+    const std::vector<Fr> zeros = vanishing(c.points);
+    uint64_t proof[12];
+    g1_record(c.proof_jac, proof);
+    for (size_t d = 0; d < zeros.size(); d++, t++) {
+      memcpy(bases.data() + 12 * t, proof, 96);
+      zeros[d].neg().to_canonical(sc.data() + 4 * t);
+      seg_offsets.push_back(t + 1);
+    }
+    check_seg.push_back(seg_offsets.size() - 1);
+  }
+  return gm::kzg_checks_run(C, vk.d_g2, bases.data(), 96, sc.data(), seg_offsets.data(), seg_offsets.size() - 1, check_seg.data(), checks.size(), ok);
+}
+
 int find_vk(uint64_t h, const VerifierKey** vk) {
   GM_CTX();
   *vk = gm::find_in(C, C->vks, h);
@@ -110,7 +181,8 @@ int find_vk(uint64_t h, const VerifierKey** vk) {
 }
 
 int verify_multi_points(const VerifierKey& vk, const uint64_t* commitments_jac, size_t ncommitments, const std::vector<Fr>& points,
-                        const std::vector<Fr>& evaluations, size_t nrows, const uint64_t proof_jac[18], const Fr& open_chal, int* ok) {
+                        const std::vector<Fr>& evaluations, size_t nrows, const uint64_t proof_jac[18], const Fr& open_chal, int* ok,
+                        CheckList* defer = nullptr) {
   SC_CHECK(points.size() + 1 <= vk.n2 && points.size() <= vk.n1, GM_EINVAL, "verify_multi_points: %zu evaluation points, the key holds %zu G1 and %zu G2 powers",
            points.size(), vk.n1, vk.n2);
   if (ncommitments != nrows) REJECT();  // G::msm(..).unwrap() fails on a length mismatch (:236)
@@ -120,7 +192,7 @@ int verify_multi_points(const VerifierKey& vk, const uint64_t* commitments_jac, 
     etas[i] = eta;
     eta = eta * open_chal;
   }
-  return kzg_check(vk, commitments_jac, etas, interpolate_combination(points, evaluations.data(), nrows, open_chal), points, proof_jac, ok);
+  return kzg_check(vk, commitments_jac, etas, interpolate_combination(points, evaluations.data(), nrows, open_chal), points, proof_jac, ok, defer);
 }
 
 std::vector<Fr> fr_vector(const uint64_t* mont, size_t n) {
@@ -182,7 +254,7 @@ struct TensorInstance {
   Fr direct_base_evals[2];
 };
 int tensorcheck_verify(uint64_t transcript, const VerifierKey& vk, const gm_tensorcheck_proof* P, const uint64_t* base_commitments_jac, size_t ncommitments,
-                       const std::vector<TensorInstance>& instances, const Fr& eval_chal, const Fr& batch_challenge, int* ok) {
+                       const std::vector<TensorInstance>& instances, const Fr& eval_chal, const Fr& batch_challenge, int* ok, CheckList* defer = nullptr) {
   const Fr two_inv = fr_u64(2).inv(), two_beta_inv = eval_chal.dbl().inv();
   std::vector<Fr> evaluations = fr_vector(P->base_evaluations, 3 * P->nbase);
   size_t offset = 0;
@@ -215,7 +287,7 @@ int tensorcheck_verify(uint64_t transcript, const VerifierKey& vk, const gm_tens
   if (ncommitments) memcpy(all.data(), base_commitments_jac, 144 * ncommitments);
   if (P->nfold) memcpy(all.data() + 18 * ncommitments, P->fold_commitments, 144 * P->nfold);
   return verify_multi_points(vk, all.data(), ncommitments + P->nfold, {eval_chal.sqr(), eval_chal, eval_chal.neg()}, evaluations, evaluations.size() / 3,
-                             P->evaluation_proof, open_chal, ok);
+                             P->evaluation_proof, open_chal, ok, defer);
 }
 
 // x(beta) + beta^|x| w(beta) and the same at -beta: z = x || w                                  src/snark/verifier.rs:91-104
@@ -258,6 +330,11 @@ extern "C" int gm_vk_new(const void* g1, size_t g1_stride, size_t n1, const void
   RC(pack_records(g2, g2_stride, n2, 192, K->g2));
   K->n1 = n1;
   K->n2 = n2;
+  {  // the G2 powers stay on the device with the key: the batched checks pair against them as they stand
+    std::unique_ptr<gm::G2Bases> d;
+    RC(gm::g2_bases_from_host(C, K->g2.data(), 192, n2, d));
+    K->d_g2 = d->d;
+  }
   *vk = gm::put_in(C, C->vks, std::move(K));
   return GM_OK;
 }
@@ -286,7 +363,9 @@ extern "C" int gm_vk_from_trapdoor(const uint64_t g1_affine[12], const uint64_t 
 
 extern "C" int gm_vk_free(uint64_t vk) {
   GM_CTX();
-  SC_CHECK(gm::take_from(C, C->vks, vk) != nullptr, GM_EHANDLE, "vk_free: unknown verifier key handle %llu", (unsigned long long)vk);
+  std::unique_ptr<VerifierKey> K = gm::take_from(C, C->vks, vk);
+  SC_CHECK(K != nullptr, GM_EHANDLE, "vk_free: unknown verifier key handle %llu", (unsigned long long)vk);
+  if (K->d_g2) (void)gm::raw_free(K->d_g2);
   return GM_OK;
 }
 
@@ -400,10 +479,8 @@ extern "C" int gm_tensorcheck_verify(uint64_t transcript, uint64_t vk, const gm_
   return tensorcheck_verify(transcript, *K, proof, base_commitments_jac, ncommitments, inst, Fr::from_limbs(eval_chal_mont), Fr::from_limbs(batch_challenge_mont), ok);
 }
 
-// snark::Proof::verify (src/snark/verifier.rs:19-119)
-extern "C" int gm_snark_verify(const uint64_t matrices[3], uint64_t x_vec, uint64_t vk, int g1_encoding, const gm_snark_proof* P, int* ok) {
-  const VerifierKey* K;
-  RC(find_vk(vk, &K));
+// snark::Proof::verify (src/snark/verifier.rs:19-119); with `defer` the KZG check at the end is stated, not run
+static int snark_verify_one(const uint64_t matrices[3], uint64_t x_vec, const VerifierKey* K, int g1_encoding, const gm_snark_proof* P, int* ok, CheckList* defer) {
   SC_CHECK(matrices && P && ok && (P->messages[0] || !P->rounds[0]) && (P->messages[1] || !P->rounds[1]), GM_EINVAL, "snark_verify: null pointer");
   SC_CHECK((P->fold_commitments && P->fold_evaluations) || !P->nfold, GM_EINVAL, "snark_verify: null folding arrays");
   size_t n = 0;
@@ -473,14 +550,18 @@ extern "C" int gm_snark_verify(const uint64_t matrices[3], uint64_t x_vec, uint6
   inst[0].fold_randomness = ch2;
   inst[0].direct_base_evals[0] = m_pos + gamma * z_pos;
   inst[0].direct_base_evals[1] = m_neg + gamma * z_neg;
-  return tensorcheck_verify(T.h, *K, &tc, P->witness_commitment, 1, inst, beta, gamma, ok);
+  return tensorcheck_verify(T.h, *K, &tc, P->witness_commitment, 1, inst, beta, gamma, ok, defer);
 }
-
-// psnark::Proof::verify (src/psnark/verifier.rs:88-565): O(log n) field arithmetic around two KZG checks
-extern "C" int gm_psnark_verify(uint64_t x_vec, size_t num_variables, size_t nnz, const uint64_t* index_commitments, uint64_t vk, int g1_encoding,
-                                const gm_psnark_proof* P, int* ok) {
+extern "C" int gm_snark_verify(const uint64_t matrices[3], uint64_t x_vec, uint64_t vk, int g1_encoding, const gm_snark_proof* P, int* ok) {
   const VerifierKey* K;
   RC(find_vk(vk, &K));
+  return snark_verify_one(matrices, x_vec, K, g1_encoding, P, ok, nullptr);
+}
+
+// psnark::Proof::verify (src/psnark/verifier.rs:88-565): O(log n) field arithmetic around two KZG checks.  With `defer` both are
+// stated: the replay behind the first does not depend on its verdict (the prover's data is absorbed either way).
+static int psnark_verify_one(uint64_t x_vec, size_t num_variables, size_t nnz, const uint64_t* index_commitments, uint64_t vk, const VerifierKey* K, int g1_encoding,
+                             const gm_psnark_proof* P, int* ok, CheckList* defer) {
   SC_CHECK(index_commitments && P && ok && num_variables >= 1 && nnz >= 1, GM_EINVAL, "psnark_verify: null pointer or an empty instance");
   for (int k = 0; k < 3; k++) SC_CHECK(P->messages[k] || !P->rounds[k], GM_EINVAL, "psnark_verify: null messages");
   SC_CHECK((P->fold_commitments && P->fold_evaluations) || !P->nfold, GM_EINVAL, "psnark_verify: null folding arrays");
@@ -532,7 +613,7 @@ extern "C" int gm_psnark_verify(uint64_t x_vec, size_t num_variables, size_t nnz
     uint64_t commitments[10 * 18];
     memcpy(commitments, P->r_star_commitments[0], 144);
     memcpy(commitments + 18, P->acc_v_commitments, 9 * 144);
-    RC(verify_multi_points(*K, commitments, 10, {mu}, fr_vector(&P->ralpha_star_acc_mu_evals[0][0], 10), 10, P->ralpha_star_acc_mu_proof, open_chal, &good));
+    RC(verify_multi_points(*K, commitments, 10, {mu}, fr_vector(&P->ralpha_star_acc_mu_evals[0][0], 10), 10, P->ralpha_star_acc_mu_proof, open_chal, &good, defer));
     if (!good) REJECT();
   }
   for (int k = 0; k < 10; k++) RC(absorb_fr(T.h, "ralpha_star_acc_mu", P->ralpha_star_acc_mu_evals[k]));
@@ -633,5 +714,107 @@ extern "C" int gm_psnark_verify(uint64_t x_vec, size_t num_variables, size_t nnz
   memcpy(tc.evaluation_proof, P->evaluation_proof, sizeof tc.evaluation_proof);
   tc.nbase = 22;
   tc.base_evaluations = const_cast<uint64_t*>(&P->base_evaluations[0][0]);
-  return tensorcheck_verify(T.h, *K, &tc, base_commitments, 22, inst, beta, bc, ok);
+  return tensorcheck_verify(T.h, *K, &tc, base_commitments, 22, inst, beta, bc, ok, defer);
+}
+extern "C" int gm_psnark_verify(uint64_t x_vec, size_t num_variables, size_t nnz, const uint64_t* index_commitments, uint64_t vk, int g1_encoding,
+                                const gm_psnark_proof* P, int* ok) {
+  const VerifierKey* K;
+  RC(find_vk(vk, &K));
+  return psnark_verify_one(x_vec, num_variables, nnz, index_commitments, vk, K, g1_encoding, P, ok, nullptr);
+}
+
+// ==== many proofs in one call ==================================================================================================
+// One proof of a batch: its host part ran to `rc` / `ok` and stated the checks [first, first + count).  What the single entry would
+// have answered follows from the verdicts of those checks IN ORDER: it stops at the first one that fails (ok = 0, GM_OK, whatever
+// came behind it -- an error code included, which the single entry never reaches), and behind checks that all pass it answers what
+// the host part answered.
+namespace {
+struct ProofRun {
+  int rc = GM_OK, ok = 0;
+  size_t first = 0, count = 0;
+};
+int settle(const VerifierKey& K, const CheckList& checks, const std::vector<ProofRun>& runs, int* ok) {
+  std::vector<int> verdict(checks.size(), 0);
+  RC(run_stated(K, checks, verdict.data()));
+  for (size_t s = 0; s < runs.size(); s++) {
+    const ProofRun& r = runs[s];
+    bool pass = true;
+    for (size_t i = 0; i < r.count && pass; i++) pass = verdict[r.first + i] != 0;
+    if (!pass) {
+      ok[s] = 0;
+      continue;
+    }
+    if (r.rc != GM_OK) return r.rc;  // the code is that proof's; gm_last_error may hold the text of a later proof's failure
+    ok[s] = r.ok;
+  }
+  return GM_OK;
+}
+}  // namespace
+
+extern "C" int gm_kzg_verify_multi_points_many(uint64_t vk, size_t S, const uint64_t* commitments_jac, const size_t* commitment_offsets, const uint64_t* eval_points_mont,
+                                               const size_t* point_offsets, const uint64_t* evaluations_mont, const size_t* row_offsets, const uint64_t* proofs_jac,
+                                               const uint64_t* open_chals_mont, int* ok) {
+  const VerifierKey* K;
+  RC(find_vk(vk, &K));
+  if (S == 0) return GM_OK;
+  SC_CHECK(commitment_offsets && point_offsets && row_offsets && eval_points_mont && proofs_jac && open_chals_mont && ok, GM_EINVAL,
+           "kzg_verify_multi_points_many: null pointer");
+  SC_CHECK(commitment_offsets[0] == 0 && point_offsets[0] == 0 && row_offsets[0] == 0, GM_EINVAL, "kzg_verify_multi_points_many: the offset arrays start at 0");
+  size_t eval_at = 0;
+  std::vector<size_t> eval_offsets(S);
+  for (size_t s = 0; s < S; s++) {
+    SC_CHECK(commitment_offsets[s] <= commitment_offsets[s + 1] && point_offsets[s] < point_offsets[s + 1] && row_offsets[s] <= row_offsets[s + 1], GM_EINVAL,
+             "kzg_verify_multi_points_many: offsets of check %zu descend, or it has no evaluation point", s);
+    eval_offsets[s] = eval_at;
+    eval_at += (row_offsets[s + 1] - row_offsets[s]) * (point_offsets[s + 1] - point_offsets[s]);
+  }
+  SC_CHECK((commitments_jac || !commitment_offsets[S]) && (evaluations_mont || !eval_at), GM_EINVAL, "kzg_verify_multi_points_many: null pointer");
+  CheckList checks;
+  std::vector<ProofRun> runs(S);
+  for (size_t s = 0; s < S; s++) {
+    const size_t nc = commitment_offsets[s + 1] - commitment_offsets[s], np = point_offsets[s + 1] - point_offsets[s], nr = row_offsets[s + 1] - row_offsets[s];
+    ProofRun& r = runs[s];
+    r.first = checks.size();
+    r.rc = verify_multi_points(*K, commitments_jac + 18 * commitment_offsets[s], nc, fr_vector(eval_points_mont + 4 * point_offsets[s], np),
+                               fr_vector(evaluations_mont + 4 * eval_offsets[s], nr * np), nr, proofs_jac + 18 * s, Fr::from_limbs(open_chals_mont + 4 * s), &r.ok,
+                               &checks);
+    r.count = checks.size() - r.first;
+    if (r.rc != GM_OK) return r.rc;  // the one check of an entry: nothing in front of it could have rejected
+  }
+  return settle(*K, checks, runs, ok);
+}
+
+extern "C" int gm_snark_verify_many(const uint64_t matrices[3], const uint64_t* x_vecs, uint64_t vk, int g1_encoding, const gm_snark_proof* proofs, size_t S, int* ok) {
+  const VerifierKey* K;
+  RC(find_vk(vk, &K));
+  if (S == 0) return GM_OK;
+  SC_CHECK(matrices && x_vecs && proofs && ok, GM_EINVAL, "snark_verify_many: null pointer");
+  CheckList checks;
+  std::vector<ProofRun> runs(S);
+  for (size_t s = 0; s < S; s++) {
+    ProofRun& r = runs[s];
+    r.first = checks.size();
+    r.rc = snark_verify_one(matrices, x_vecs[s], K, g1_encoding, &proofs[s], &r.ok, &checks);
+    r.count = checks.size() - r.first;
+    if (r.rc != GM_OK && r.count == 0) return r.rc;
+  }
+  return settle(*K, checks, runs, ok);
+}
+
+extern "C" int gm_psnark_verify_many(const uint64_t* x_vecs, size_t num_variables, size_t nnz, const uint64_t* index_commitments, uint64_t vk, int g1_encoding,
+                                     const gm_psnark_proof* proofs, size_t S, int* ok) {
+  const VerifierKey* K;
+  RC(find_vk(vk, &K));
+  if (S == 0) return GM_OK;
+  SC_CHECK(x_vecs && proofs && ok, GM_EINVAL, "psnark_verify_many: null pointer");
+  CheckList checks;
+  std::vector<ProofRun> runs(S);
+  for (size_t s = 0; s < S; s++) {
+    ProofRun& r = runs[s];
+    r.first = checks.size();
+    r.rc = psnark_verify_one(x_vecs[s], num_variables, nnz, index_commitments, vk, K, g1_encoding, &proofs[s], &r.ok, &checks);
+    r.count = checks.size() - r.first;
+    if (r.rc != GM_OK && r.count == 0) return r.rc;  // before any check was stated the single entry fails in the same way
+  }
+  return settle(*K, checks, runs, ok);
 }

@@ -272,12 +272,51 @@ class VerifierKey:
         if not ok.value:
             raise VerificationError("verify_multi_points: pairing check failed")
 
+    def verify_multi_points_many(self, checks) -> list:
+        """gm_kzg_verify_multi_points_many: `checks` is a sequence of (commitments, eval_points_mont, evaluations_mont, proof,
+        open_chal_mont) as verify_multi_points takes them; a list of bools, one verdict per check, from ONE batch of device work.
+        A check whose numbers of commitments and evaluation rows differ is False."""
+        import ctypes as C
+
+        S = len(checks)
+        cms, pts, evs, prs, chs = [], [], [], [], []
+        co, po, ro = [0], [0], [0]
+        for commitments, eval_points_mont, evaluations_mont, proof, open_chal_mont in checks:
+            cm = np.asarray(commitments, dtype=np.uint64).reshape(-1, 18)
+            pt = np.asarray(eval_points_mont, dtype=np.uint64).reshape(-1, 4)
+            ev = np.asarray(evaluations_mont, dtype=np.uint64).reshape(-1, len(pt), 4)
+            cms.append(cm)
+            pts.append(pt)
+            evs.append(ev.reshape(-1, 4))
+            prs.append(np.asarray(proof, dtype=np.uint64).reshape(18))
+            chs.append(np.asarray(open_chal_mont, dtype=np.uint64).reshape(4))
+            co.append(co[-1] + len(cm))
+            po.append(po[-1] + len(pt))
+            ro.append(ro[-1] + len(ev))
+        cat = lambda xs, w: capi.u64(np.concatenate(xs).reshape(-1, w)) if xs else np.zeros((0, w), dtype=np.uint64)  # noqa: E731
+        off = lambda o: np.ascontiguousarray(o, dtype=np.uintp)  # noqa: E731
+        ok = np.zeros(max(S, 1), dtype=np.int32)
+        co, po, ro = off(co), off(po), off(ro)
+        capi.check(capi.load().gm_kzg_verify_multi_points_many(C.c_uint64(self.handle), C.c_size_t(S), capi.ptr(cat(cms, 18)), capi.ptr(co), capi.ptr(cat(pts, 4)),
+                                                               capi.ptr(po), capi.ptr(cat(evs, 4)), capi.ptr(ro), capi.ptr(cat(prs, 18)), capi.ptr(cat(chs, 4)),
+                                                               capi.ptr(ok)))
+        return [bool(v) for v in ok[:S]]
+
     def free(self):
         import ctypes as C
 
         if self.handle:
             capi.check(capi.load().gm_vk_free(C.c_uint64(self.handle)))
             self.handle = 0
+
+
+def set_verify_many_min(checks: int):
+    """gm_set_verify_many_min: fewer stated KZG checks than this run one by one, as the single verifiers run them.  Verdicts do not
+    depend on it."""
+    import ctypes as C
+
+    capi.ensure_init()
+    capi.check(capi.load().gm_set_verify_many_min(C.c_size_t(checks)))
 
 
 class FoldedPolynomialTree:

@@ -168,6 +168,22 @@ def g1_sum(points: np.ndarray) -> np.ndarray:
     return out
 
 
+def g1_lincomb_many(points: np.ndarray, scalars_canonical: np.ndarray, offsets) -> np.ndarray:
+    """gm_g1_lincomb_many: out[s] = sum of scalars[t] * points[t] over offsets[s] <= t < offsets[s + 1], for S = len(offsets) - 1
+    short segments in a fixed number of launches; (S, 18) normalised Jacobian limbs.  Records and canonical scalars as for
+    VariableBaseMSM.msm_bigint; an empty segment is the identity."""
+    capi.ensure_init()
+    pts = capi.u64(points)
+    assert pts.ndim == 2 and pts.shape[1] in (12, 13)
+    sc = capi.u64(scalars_canonical).reshape(-1, 4)
+    off = np.ascontiguousarray(offsets, dtype=np.uintp)
+    S = len(off) - 1
+    assert S >= 0 and (S == 0 or int(off[-1]) <= min(len(pts), len(sc)))
+    out = np.empty((max(S, 0), 18), dtype=np.uint64)
+    capi.check(capi.load().gm_g1_lincomb_many(capi.ptr(pts), C.c_size_t(pts.shape[1] * 8), capi.ptr(sc), capi.ptr(off), C.c_size_t(S), capi.ptr(out)))
+    return out
+
+
 G1_ZERO = None
 
 

@@ -135,6 +135,32 @@ def multi_pairing(g1_records, g2_records) -> np.ndarray:
     return out
 
 
+def multi_pairing_many(g1_records, g2_records, offsets) -> np.ndarray:
+    """gm_pairing_multi_many: S = len(offsets) - 1 independent products, out[s] = prod e(P_t, Q_t) over offsets[s] <= t < offsets[s + 1],
+    (S, 72) limbs; each equals `multi_pairing` on that slice bit for bit, an empty product is 1.  One segmented Miller launch and one
+    launch of final exponentiations whatever S is."""
+    capi.ensure_init()
+    g1 = _g1_records(g1_records)
+    g2 = _g2_records(g2_records)
+    off = np.ascontiguousarray(offsets, dtype=np.uintp)
+    S = len(off) - 1
+    assert S >= 0 and (S == 0 or int(off[-1]) <= min(len(g1), len(g2)))
+    out = np.empty((max(S, 0), 72), dtype=np.uint64)
+    capi.check(capi.load().gm_pairing_multi_many(capi.ptr(g1), C.c_size_t(g1.shape[1] * 8), capi.ptr(g2), C.c_size_t(g2.shape[1] * 8), capi.ptr(off),
+                                                 C.c_size_t(S), capi.ptr(out)))
+    return out
+
+
+def multi_pairing_many_h(g1_bases, g2_bases: G2Bases, offsets, off1: int = 0, off2: int = 0) -> np.ndarray:
+    """the same over registered bases: product s pairs g1[off1 + t] with g2[off2 + t], offsets[s] <= t < offsets[s + 1]"""
+    off = np.ascontiguousarray(offsets, dtype=np.uintp)
+    S = len(off) - 1
+    out = np.empty((max(S, 0), 72), dtype=np.uint64)
+    capi.check(capi.load().gm_pairing_multi_many_h(C.c_uint64(g1_bases.handle), C.c_size_t(off1), C.c_uint64(g2_bases.handle), C.c_size_t(off2), capi.ptr(off),
+                                                   C.c_size_t(S), capi.ptr(out)))
+    return out
+
+
 def multi_pairing_h(g1_bases, g2_bases: G2Bases, n: int, off1: int = 0, step1: int = 1, off2: int = 0, step2: int = 1) -> np.ndarray:
     """prod_i e(g1[off1 + step1 i], g2[off2 + step2 i]), i < n, over registered bases (gemini_amd.msm.G1Bases, g2msm.G2Bases)"""
     out = np.empty(72, dtype=np.uint64)

@@ -263,6 +263,35 @@ class Proof:
         if not ok.value:
             raise VerificationError("psnark: rejected")
 
+    @staticmethod
+    def verify_many(proofs, r1cs: R1cs, vk, index: list, num_non_zero: int | None = None, x_vecs=None) -> list:
+        """gm_psnark_verify_many: the proofs under one index and one key, each with its own public input (x_vecs: FrVec or None per
+        proof; default r1cs.x for all).  A list of bools -- what verify decides for each; the two KZG checks of every proof run in ONE
+        batch."""
+        import ctypes as C
+
+        from . import capi
+        from .transcript import default_group_encoding
+
+        proofs = list(proofs)
+        if not proofs:
+            return []
+        xs = [r1cs.x] * len(proofs) if x_vecs is None else list(x_vecs)
+        assert len(xs) == len(proofs)
+        if num_non_zero is None:
+            num_non_zero = len(_joint_device(r1cs).row_index)
+        packed = [_pack_proof(p) for p in proofs]
+        size = C.sizeof(packed[0][0])  # (every _pack_proof call makes the record type anew: the records are copied as bytes)
+        recs = (C.c_char * (size * len(proofs)))()
+        for i, (P, _) in enumerate(packed):
+            C.memmove(C.addressof(recs) + i * size, C.addressof(P), size)
+        xh = (C.c_uint64 * len(proofs))(*[x.handle if x is not None else 0 for x in xs])
+        idx = np.ascontiguousarray(np.stack(index), dtype=np.uint64).reshape(5, 18)
+        ok = (C.c_int * len(proofs))()
+        capi.check(capi.load().gm_psnark_verify_many(xh, C.c_size_t(len(r1cs.z)), C.c_size_t(num_non_zero), capi.ptr(idx), C.c_uint64(vk.handle),
+                                                     C.c_int(int(default_group_encoding())), recs, C.c_size_t(len(proofs)), ok))
+        return [bool(v) for v in ok]
+
     def check_points(self):
         """gm_psnark_proof_check: every G1 element the verifier reads is canonical, on the curve and in G1; a points.ProofCheckResult
         (the order of first_bad: include/gemini_hip.h).  verify() does not call it."""

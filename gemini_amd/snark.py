@@ -178,6 +178,32 @@ def _proof_verify(self, r1cs: R1cs, vk) -> None:
         raise VerificationError("snark: rejected")
 
 
+def verify_many(proofs, r1cs: R1cs, vk, x_vecs=None) -> list:
+    """gm_snark_verify_many: the proofs under one set of matrices and one key, each with its own public input (x_vecs: FrVec or None
+    per proof; default r1cs.x for all).  A list of bools -- what Proof.verify decides for each, from ONE batch of KZG checks."""
+    import ctypes as C
+
+    from . import capi
+    from .transcript import default_group_encoding
+
+    proofs = list(proofs)
+    xs = [r1cs.x] * len(proofs) if x_vecs is None else list(x_vecs)
+    assert len(xs) == len(proofs)
+    live = [i for i, p in enumerate(proofs) if len(p.tensorcheck_proof.base_polynomials_evaluations) == 1]
+    out = [False] * len(proofs)
+    if not live:
+        return out
+    packed = [_pack_native(proofs[i]) for i in live]
+    recs = (_GmSnarkProof * len(live))(*[P for P, _ in packed])
+    xh = (C.c_uint64 * len(live))(*[xs[i].handle if xs[i] is not None else 0 for i in live])
+    mats = (C.c_uint64 * 3)(r1cs.a.handle, r1cs.b.handle, r1cs.c.handle)
+    ok = (C.c_int * len(live))()
+    capi.check(capi.load().gm_snark_verify_many(mats, xh, C.c_uint64(vk.handle), C.c_int(int(default_group_encoding())), recs, C.c_size_t(len(live)), ok))
+    for k, i in enumerate(live):
+        out[i] = bool(ok[k])
+    return out
+
+
 def _proof_check_points(self):
     """gm_snark_proof_check: every G1 element the verifier reads is canonical, on the curve and in G1; a points.ProofCheckResult whose
     first_bad counts witness_commitment, the folded commitments, evaluation_proof.  verify() does not call it."""
@@ -192,6 +218,7 @@ def _proof_check_points(self):
 
 
 Proof.verify = _proof_verify
+Proof.verify_many = staticmethod(verify_many)
 Proof.check_points = _proof_check_points
 
 

@@ -73,6 +73,12 @@ int gm_abi_version(void);
  * algorithm statement src/kzg/msm/variable_base.rs:99-176).
  * scalars: n x 4 u64 canonical (< r).  Like msm_unchecked, the caller passes n = min(lengths). */
 int gm_g1_msm(const void* bases, size_t base_stride, const uint64_t* scalars, size_t n, uint64_t out_jac[18]);
+/* S independent SHORT linear combinations (tens of terms each, where an MSM has millions): out[s] = sum over
+ * offsets[s] <= t < offsets[s + 1] of scalars[t] * points[t]; records and canonical scalars as for gm_g1_msm, offsets[0] = 0, S + 1
+ * entries, out_jac: S x 18 limbs, normalised.  One lane per term, then one per segment: three launches and one wait whatever S is.
+ * The additions are complete (equal terms double, opposite ones cancel); an empty segment, a zero scalar and the all-zero record
+ * give the identity. */
+int gm_g1_lincomb_many(const void* points, size_t stride, const uint64_t* scalars_canonical, const size_t* offsets, size_t S, uint64_t* out_jac);
 
 /* SRS resident in HBM: replaces the `powers_of_g: Vec<G1Affine>` field of CommitterKey
  * (src/kzg/time.rs:24-27) as the MSM operand.  The bases are copied; `handle` is opaque.  Cost: one upload and one
@@ -529,6 +535,12 @@ int gm_hg2_free(uint64_t handle);
 int gm_pairing_multi(const void* g1, size_t g1_stride, const void* g2, size_t g2_stride, size_t n, uint64_t out_gt[72]);
 /* prod_i e(g1[off1 + step1 i], g2[off2 + step2 i]), i < n, over registered bases (steps >= 1: Vrs::from pairs
  * step_by(2) against take(size)).  A range outside the bases or a zero step gives GM_EINVAL, an unknown handle GM_EHANDLE. */
+/* S independent products in one call: product s is over the pairs [offsets[s], offsets[s + 1]) (offsets[0] = 0, S + 1 entries), an
+ * empty one is 1; out_gt: S x 72 limbs, each bit-identical to gm_pairing_multi on that product.  ONE segmented Miller launch, the
+ * reduction levels of products longer than a block, ONE final-exponentiation launch and one wait, whatever S is.  The _h form
+ * pairs (g1[off1 + t], g2[off2 + t]) of registered bases. */
+int gm_pairing_multi_many(const void* g1, size_t g1_stride, const void* g2, size_t g2_stride, const size_t* offsets, size_t S, uint64_t* out_gt);
+int gm_pairing_multi_many_h(uint64_t g1_handle, size_t off1, uint64_t g2_handle, size_t off2, const size_t* offsets, size_t S, uint64_t* out_gt);
 int gm_pairing_multi_h(uint64_t g1_handle, size_t off1, size_t step1, uint64_t g2_handle, size_t off2, size_t step2, size_t n,
                        uint64_t out_gt[72]);
 /* GT on the host (no GPU needed, like gm_g2_sum): a b, a^s for a canonical 256-bit integer s, 1 */
@@ -908,6 +920,29 @@ int gm_snark_verify(const uint64_t matrices[3], uint64_t x_vec, uint64_t vk, int
  * 5 x 18 limbs (gm_psnark_index).  The key must hold max_eval_points >= 3. */
 int gm_psnark_verify(uint64_t x_vec, size_t num_variables, size_t nnz, const uint64_t* index_commitments, uint64_t vk, int g1_encoding,
                      const gm_psnark_proof* proof, int* ok);
+
+/* ---- Many proofs in one call.  Every *_many entry answers ok[s] = what the single entry answers for proof s, for every s, and fails
+ * as a whole (a negative code) exactly where one of the single calls, made in order, would fail.  The KZG checks of all proofs are
+ * STATED by the host part of each proof and run together: with Z(X) = sum_d z_d X^d the monic vanishing polynomial of a check's m points,
+ *   e(L, g2) e(-proof, [Z(tau)] g2) = e(L, g2) prod_{d <= m} e((r - z_d) proof, [tau^d] g2),
+ * m + 2 pairs against the key's G2 powers as they stand.  Every G1 point of every check comes out of one gm_g1_lincomb_many launch
+ * group, then ONE segmented Miller launch, ONE final-exponentiation launch and one wait for all of them: the number of launches and
+ * waits does not depend on S.  (Equal verdicts need proof elements ON the curve, as everything here does: the identity above is the
+ * pairing's bilinearity.)  Below gm_set_verify_many_min stated checks (default 3, the measured break-even: profiles/verify_many.md) the checks run one by
+ * one as the single entries run them: one host final exponentiation is cheaper than the device's launch.  Verdicts never depend on that knob. */
+int gm_set_verify_many_min(size_t checks);
+/* S checks of gm_kzg_verify_multi_points: check s has the commitments [commitment_offsets[s], commitment_offsets[s + 1]) of
+ * commitments_jac (18 limbs each), the points [point_offsets[s], point_offsets[s + 1]) of eval_points_mont (at least one) and the
+ * evaluation rows [row_offsets[s], row_offsets[s + 1]); evaluations_mont is the concatenation of the checks' row-major nrows x npoints
+ * blocks.  proofs_jac: S x 18, open_chals_mont: S x 4.  A check whose commitment and row counts differ is ok[s] = 0. */
+int gm_kzg_verify_multi_points_many(uint64_t vk, size_t S, const uint64_t* commitments_jac, const size_t* commitment_offsets, const uint64_t* eval_points_mont,
+                                    const size_t* point_offsets, const uint64_t* evaluations_mont, const size_t* row_offsets, const uint64_t* proofs_jac,
+                                    const uint64_t* open_chals_mont, int* ok);
+/* S proofs under one set of matrices / one index and one key, each with its own public input x_vecs[s] (0 = empty).  The host part
+ * of every proof runs as in the single entry; a proof it rejects states no further check. */
+int gm_snark_verify_many(const uint64_t matrices[3], const uint64_t* x_vecs, uint64_t vk, int g1_encoding, const gm_snark_proof* proofs, size_t S, int* ok);
+int gm_psnark_verify_many(const uint64_t* x_vecs, size_t num_variables, size_t nnz, const uint64_t* index_commitments, uint64_t vk, int g1_encoding,
+                          const gm_psnark_proof* proofs, size_t S, int* ok);
 
 /* ---- Multi-GPU: the collective layer (gemini_amd/csrc/dist.cpp) ------------------------------------------------------
  * One process per GPU (gm_init(LOCAL_RANK)).  The reference has no multi-device code: what shards is its own loop structure --

@@ -187,6 +187,16 @@ inline G1Projective g1_add(const G1Projective& a, const G1Projective& b) {
   return r;
 }
 
+// S short linear combinations in a fixed number of launches (gm_g1_lincomb_many): out[s] = sum of bigints[t] * points[t] over
+// offsets[s] <= t < offsets[s + 1]; offsets has S + 1 entries and starts at 0; an empty segment is the identity
+inline std::vector<G1Projective> g1_lincomb_many(const std::vector<G1Affine>& points, const std::vector<BigInt>& bigints, const std::vector<size_t>& offsets) {
+  if (offsets.size() < 2) return {};
+  if (offsets.back() > points.size() || offsets.back() > bigints.size()) throw Error(GM_EINVAL, "g1_lincomb_many: the offsets run past the terms");
+  std::vector<G1Projective> out(offsets.size() - 1);
+  check(gm_g1_lincomb_many(points.data(), sizeof(G1Affine), bigints.empty() ? nullptr : bigints[0].data(), offsets.data(), out.size(), out[0].data()));
+  return out;
+}
+
 struct VariableBaseMSM {
   static G1Projective msm_bigint(const std::vector<G1Affine>& bases, const std::vector<BigInt>& bigints) {
     size_t n = bases.size() < bigints.size() ? bases.size() : bigints.size();
@@ -730,6 +740,17 @@ inline Gt multi_pairing(uint64_t g1_handle, size_t off1, size_t step1, const G2B
   check(gm_pairing_multi_h(g1_handle, off1, step1, g2.handle(), off2, step2, n, r.data()));
   return r;
 }
+// S independent products in one segmented launch (gm_pairing_multi_many): out[s] = prod e(g1[t], g2[t]) over offsets[s] <= t < offsets[s + 1],
+// each bit-identical to multi_pairing on that slice; an empty product is 1
+inline std::vector<Gt> multi_pairing_many(const std::vector<G1Affine>& g1, const std::vector<G2Affine>& g2, const std::vector<size_t>& offsets) {
+  if (offsets.size() < 2) return {};
+  if (offsets.back() > g1.size() || offsets.back() > g2.size()) throw Error(GM_EINVAL, "multi_pairing_many: the offsets run past the pairs");
+  std::vector<Gt> out(offsets.size() - 1);
+  check(gm_pairing_multi_many(g1.data(), sizeof(G1Affine), g2.data(), sizeof(G2Affine), offsets.data(), out.size(), out[0].data()));
+  return out;
+}
+// fewer stated KZG checks than this run one by one, as the single verifiers run them (gm_set_verify_many_min); verdicts do not depend on it
+inline void set_verify_many_min(size_t checks) { check(gm_set_verify_many_min(checks)); }
 
 struct GtRoundMsg {
   Gt a, b;
@@ -1392,6 +1413,35 @@ class VerifierKey {
                                      eval_points.size(), flat.empty() ? nullptr : flat[0].data(), evaluations.size(), proof.data(), open_chal.data(), &ok));
     return ok != 0;
   }
+  // one verify_multi_points per entry, all of them in ONE batch of device work (gm_kzg_verify_multi_points_many): a verdict per check
+  struct MultiPointsCheck {
+    std::vector<G1Projective> commitments;
+    std::vector<Fr> eval_points;
+    std::vector<std::vector<Fr>> evaluations;
+    G1Projective proof;
+    Fr open_chal;
+  };
+  std::vector<bool> verify_multi_points_many(const std::vector<MultiPointsCheck>& checks) const {
+    std::vector<uint64_t> cm, pts, ev, pr, ch;
+    std::vector<size_t> co{0}, po{0}, ro{0};
+    for (const MultiPointsCheck& c : checks) {
+      for (auto& x : c.commitments) cm.insert(cm.end(), x.begin(), x.end());
+      for (auto& x : c.eval_points) pts.insert(pts.end(), x.begin(), x.end());
+      for (auto& row : c.evaluations) {
+        if (row.size() != c.eval_points.size()) throw Error(GM_EINVAL, "verify_multi_points_many: one value per evaluation point in every row");
+        for (auto& x : row) ev.insert(ev.end(), x.begin(), x.end());
+      }
+      pr.insert(pr.end(), c.proof.begin(), c.proof.end());
+      ch.insert(ch.end(), c.open_chal.begin(), c.open_chal.end());
+      co.push_back(co.back() + c.commitments.size());
+      po.push_back(po.back() + c.eval_points.size());
+      ro.push_back(ro.back() + c.evaluations.size());
+    }
+    std::vector<int> ok(checks.size() + 1, 0);
+    cm.push_back(0), pts.push_back(0), ev.push_back(0), pr.push_back(0), ch.push_back(0);  // never null
+    gm::check(gm_kzg_verify_multi_points_many(h_, checks.size(), cm.data(), co.data(), pts.data(), po.data(), ev.data(), ro.data(), pr.data(), ch.data(), ok.data()));
+    return std::vector<bool>(ok.begin(), ok.begin() + checks.size());
+  }
 
  private:
   VerifierKey() = default;
@@ -1464,42 +1514,78 @@ struct SnarkProof {
 
   // Proof::verify(&r1cs, &vk) (src/snark/verifier.rs:19-119): true = accepted.  The proof may come from a prover or from its fields
   bool verify(const R1cs& r1cs, const VerifierKey& vk, int g1_encoding = 0) const {
-    if (tensorcheck_proof.base_polynomials_evaluations.size() != 1) return false;
-    const auto& tc = tensorcheck_proof;
-    const size_t nf = tc.folded_polynomials_commitments.size();
-    if (tc.folded_polynomials_evaluations.size() != nf) return false;
-    gm_snark_proof p;
-    memset(&p, 0, sizeof p);
-    memcpy(p.witness_commitment, witness_commitment.data(), 144);
-    memcpy(p.zc_alpha, zc_alpha.data(), 32);
-    std::vector<uint64_t> m[2], fc(18 * nf + 1), fe(8 * nf + 1);
-    const std::vector<RoundMsg>* msgs[2] = {&first_sumcheck_msgs, &second_sumcheck_msgs};
-    for (int k = 0; k < 2; k++) {
-      m[k].resize(8 * msgs[k]->size() + 1);
-      for (size_t i = 0; i < msgs[k]->size(); i++) {
-        memcpy(m[k].data() + 8 * i, (*msgs[k])[i].a.data(), 32);
-        memcpy(m[k].data() + 8 * i + 4, (*msgs[k])[i].b.data(), 32);
-      }
-      p.rounds[k] = msgs[k]->size();
-      p.messages[k] = m[k].data();
-    }
-    memcpy(p.final_foldings[0], first_final_foldings.data(), 64);
-    memcpy(p.final_foldings[1], second_final_foldings.data(), 64);
-    for (size_t i = 0; i < nf; i++) {
-      memcpy(fc.data() + 18 * i, tc.folded_polynomials_commitments[i].data(), 144);
-      memcpy(fe.data() + 8 * i, tc.folded_polynomials_evaluations[i].data(), 64);
-    }
-    p.nfold = nf;
-    p.fold_commitments = fc.data();
-    p.fold_evaluations = fe.data();
-    memcpy(p.evaluation_proof, tc.evaluation_proof.data(), 144);
-    memcpy(p.base_evaluations, tc.base_polynomials_evaluations[0].data(), 96);
+    Packed P;
+    if (!P.pack(*this)) return false;
     const PublicInput x(r1cs);
     const uint64_t mats[3] = {r1cs.a_.handle(), r1cs.b_.handle(), r1cs.c_.handle()};
     int ok = 0;
-    check(gm_snark_verify(mats, x.h, vk.handle(), g1_encoding, &p, &ok));
+    check(gm_snark_verify(mats, x.h, vk.handle(), g1_encoding, &P.p, &ok));
     return ok != 0;
   }
+
+  // The proofs under one set of matrices and one key in ONE call (gm_snark_verify_many): a verdict per proof, what verify() answers for
+  // each.  x_vecs: the public input of every proof as a vector handle (0 = empty); empty = the instance's own for all of them
+  static std::vector<bool> verify_many(const std::vector<const SnarkProof*>& proofs, const R1cs& r1cs, const VerifierKey& vk, const std::vector<uint64_t>& x_vecs = {},
+                                       int g1_encoding = 0) {
+    if (!x_vecs.empty() && x_vecs.size() != proofs.size()) throw Error(GM_EINVAL, "verify_many: one public input per proof");
+    std::vector<bool> out(proofs.size(), false);
+    std::vector<Packed> packed(proofs.size());
+    std::vector<gm_snark_proof> recs;
+    std::vector<uint64_t> xs;
+    std::vector<size_t> live;
+    const PublicInput x(r1cs);
+    for (size_t i = 0; i < proofs.size(); i++) {
+      if (!packed[i].pack(*proofs[i])) continue;  // verify() rejects these without a call
+      live.push_back(i);
+      recs.push_back(packed[i].p);
+      xs.push_back(x_vecs.empty() ? x.h : x_vecs[i]);
+    }
+    if (live.empty()) return out;
+    const uint64_t mats[3] = {r1cs.a_.handle(), r1cs.b_.handle(), r1cs.c_.handle()};
+    std::vector<int> ok(live.size(), 0);
+    check(gm_snark_verify_many(mats, xs.data(), vk.handle(), g1_encoding, recs.data(), live.size(), ok.data()));
+    for (size_t k = 0; k < live.size(); k++) out[live[k]] = ok[k] != 0;
+    return out;
+  }
+
+  // the gm_snark_proof record of a proof and the arrays it points into
+  struct Packed {
+    gm_snark_proof p;
+    std::vector<uint64_t> m[2], fc, fe;
+    bool pack(const SnarkProof& s) {
+      if (s.tensorcheck_proof.base_polynomials_evaluations.size() != 1) return false;
+      const auto& tc = s.tensorcheck_proof;
+      const size_t nf = tc.folded_polynomials_commitments.size();
+      if (tc.folded_polynomials_evaluations.size() != nf) return false;
+      memset(&p, 0, sizeof p);
+      memcpy(p.witness_commitment, s.witness_commitment.data(), 144);
+      memcpy(p.zc_alpha, s.zc_alpha.data(), 32);
+      fc.assign(18 * nf + 1, 0);
+      fe.assign(8 * nf + 1, 0);
+      const std::vector<RoundMsg>* msgs[2] = {&s.first_sumcheck_msgs, &s.second_sumcheck_msgs};
+      for (int k = 0; k < 2; k++) {
+        m[k].assign(8 * msgs[k]->size() + 1, 0);
+        for (size_t i = 0; i < msgs[k]->size(); i++) {
+          memcpy(m[k].data() + 8 * i, (*msgs[k])[i].a.data(), 32);
+          memcpy(m[k].data() + 8 * i + 4, (*msgs[k])[i].b.data(), 32);
+        }
+        p.rounds[k] = msgs[k]->size();
+        p.messages[k] = m[k].data();
+      }
+      memcpy(p.final_foldings[0], s.first_final_foldings.data(), 64);
+      memcpy(p.final_foldings[1], s.second_final_foldings.data(), 64);
+      for (size_t i = 0; i < nf; i++) {
+        memcpy(fc.data() + 18 * i, tc.folded_polynomials_commitments[i].data(), 144);
+        memcpy(fe.data() + 8 * i, tc.folded_polynomials_evaluations[i].data(), 64);
+      }
+      p.nfold = nf;
+      p.fold_commitments = fc.data();
+      p.fold_evaluations = fe.data();
+      memcpy(p.evaluation_proof, tc.evaluation_proof.data(), 144);
+      memcpy(p.base_evaluations, tc.base_polynomials_evaluations[0].data(), 96);
+      return true;
+    }
+  };
 
   // x = the entries of z in front of the witness (src/circuit.rs: z = x || w), as a vector of its own for the verifiers
   struct PublicInput {
@@ -1703,50 +1789,85 @@ struct PsnarkProof {
 
   // Proof::verify(&r1cs, &vk, &index, num_non_zero) (src/psnark/verifier.rs:88-565): true = accepted.  The key needs max_eval_points >= 3
   bool verify(const R1cs& r1cs, const VerifierKey& vk, const std::array<G1Projective, 5>& index, size_t num_non_zero, int g1_encoding = 0) const {
-    const TensorcheckProof& tc = tensorcheck_proof;
-    const size_t nf = tc.folded_polynomials_commitments.size();
-    if (tc.base_polynomials_evaluations.size() != 22 || tc.folded_polynomials_evaluations.size() != nf) return false;
-    gm_psnark_proof p;
-    memset(&p, 0, sizeof p);
-    std::vector<uint64_t> m[3], fc(18 * nf + 1), fe(8 * nf + 1);
-    const std::vector<RoundMsg>* msgs[3] = {&first_sumcheck_msgs, &second_sumcheck_msgs, &third_sumcheck_msgs};
-    for (int k = 0; k < 3; k++) {
-      m[k].resize(8 * msgs[k]->size() + 1);
-      for (size_t i = 0; i < msgs[k]->size(); i++) {
-        memcpy(m[k].data() + 8 * i, (*msgs[k])[i].a.data(), 32);
-        memcpy(m[k].data() + 8 * i + 4, (*msgs[k])[i].b.data(), 32);
-      }
-      p.rounds[k] = msgs[k]->size();
-      p.messages[k] = m[k].data();
-    }
-    memcpy(p.witness_commitment, witness_commitment.data(), 144);
-    memcpy(p.zc_alpha, zc_alpha.data(), 32);
-    memcpy(p.final_foldings[0], first_final_foldings.data(), 64);
-    memcpy(p.final_foldings[1], second_final_foldings.data(), 64);
-    memcpy(p.third_final_foldings, third_final_foldings.data(), sizeof p.third_final_foldings);
-    memcpy(p.r_star_commitments, r_star_commitments.data(), sizeof p.r_star_commitments);
-    memcpy(p.z_star_commitment, z_star_commitment.data(), 144);
-    memcpy(p.sorted_commitments, sorted_commitments.data(), sizeof p.sorted_commitments);
-    memcpy(p.products, products.data(), sizeof p.products);
-    memcpy(p.acc_v_commitments, acc_v_commitments.data(), sizeof p.acc_v_commitments);
-    memcpy(p.claimed_sumchecks, claimed_sumchecks.data(), sizeof p.claimed_sumchecks);
-    memcpy(p.ralpha_star_acc_mu_evals, ralpha_star_acc_mu_evals.data(), sizeof p.ralpha_star_acc_mu_evals);
-    memcpy(p.ralpha_star_acc_mu_proof, ralpha_star_acc_mu_proof.data(), 144);
-    memcpy(p.rstars_vals, rstars_vals.data(), sizeof p.rstars_vals);
-    for (size_t i = 0; i < nf; i++) {
-      memcpy(fc.data() + 18 * i, tc.folded_polynomials_commitments[i].data(), 144);
-      memcpy(fe.data() + 8 * i, tc.folded_polynomials_evaluations[i].data(), 64);
-    }
-    p.nfold = p.cap_folds = nf;
-    p.fold_commitments = fc.data();
-    p.fold_evaluations = fe.data();
-    memcpy(p.evaluation_proof, tc.evaluation_proof.data(), 144);
-    memcpy(p.base_evaluations, tc.base_polynomials_evaluations[0].data(), sizeof p.base_evaluations);
+    Packed P;
+    if (!P.pack(*this)) return false;
     const SnarkProof::PublicInput x(r1cs);
     int ok = 0;
-    check(gm_psnark_verify(x.h, r1cs.nz_, num_non_zero, index[0].data(), vk.handle(), g1_encoding, &p, &ok));
+    check(gm_psnark_verify(x.h, r1cs.nz_, num_non_zero, index[0].data(), vk.handle(), g1_encoding, &P.p, &ok));
     return ok != 0;
   }
+
+  // The proofs under one index and one key in ONE call (gm_psnark_verify_many): a verdict per proof, what verify() answers for each; the two
+  // KZG checks of every proof run in one batch.  x_vecs as for SnarkProof::verify_many
+  static std::vector<bool> verify_many(const std::vector<const PsnarkProof*>& proofs, const R1cs& r1cs, const VerifierKey& vk, const std::array<G1Projective, 5>& index,
+                                       size_t num_non_zero, const std::vector<uint64_t>& x_vecs = {}, int g1_encoding = 0) {
+    if (!x_vecs.empty() && x_vecs.size() != proofs.size()) throw Error(GM_EINVAL, "verify_many: one public input per proof");
+    std::vector<bool> out(proofs.size(), false);
+    std::vector<Packed> packed(proofs.size());
+    std::vector<gm_psnark_proof> recs;
+    std::vector<uint64_t> xs;
+    std::vector<size_t> live;
+    const SnarkProof::PublicInput x(r1cs);
+    for (size_t i = 0; i < proofs.size(); i++) {
+      if (!packed[i].pack(*proofs[i])) continue;
+      live.push_back(i);
+      recs.push_back(packed[i].p);
+      xs.push_back(x_vecs.empty() ? x.h : x_vecs[i]);
+    }
+    if (live.empty()) return out;
+    std::vector<int> ok(live.size(), 0);
+    check(gm_psnark_verify_many(xs.data(), r1cs.nz_, num_non_zero, index[0].data(), vk.handle(), g1_encoding, recs.data(), live.size(), ok.data()));
+    for (size_t k = 0; k < live.size(); k++) out[live[k]] = ok[k] != 0;
+    return out;
+  }
+
+  // the gm_psnark_proof record of a proof and the arrays it points into
+  struct Packed {
+    gm_psnark_proof p;
+    std::vector<uint64_t> m[3], fc, fe;
+    bool pack(const PsnarkProof& s) {
+      const TensorcheckProof& tc = s.tensorcheck_proof;
+      const size_t nf = tc.folded_polynomials_commitments.size();
+      if (tc.base_polynomials_evaluations.size() != 22 || tc.folded_polynomials_evaluations.size() != nf) return false;
+      memset(&p, 0, sizeof p);
+        fc.assign(18 * nf + 1, 0);
+        fe.assign(8 * nf + 1, 0);
+      const std::vector<RoundMsg>* msgs[3] = {&s.first_sumcheck_msgs, &s.second_sumcheck_msgs, &s.third_sumcheck_msgs};
+      for (int k = 0; k < 3; k++) {
+        m[k].assign(8 * msgs[k]->size() + 1, 0);
+        for (size_t i = 0; i < msgs[k]->size(); i++) {
+          memcpy(m[k].data() + 8 * i, (*msgs[k])[i].a.data(), 32);
+          memcpy(m[k].data() + 8 * i + 4, (*msgs[k])[i].b.data(), 32);
+        }
+        p.rounds[k] = msgs[k]->size();
+        p.messages[k] = m[k].data();
+      }
+      memcpy(p.witness_commitment, s.witness_commitment.data(), 144);
+      memcpy(p.zc_alpha, s.zc_alpha.data(), 32);
+      memcpy(p.final_foldings[0], s.first_final_foldings.data(), 64);
+      memcpy(p.final_foldings[1], s.second_final_foldings.data(), 64);
+      memcpy(p.third_final_foldings, s.third_final_foldings.data(), sizeof p.third_final_foldings);
+      memcpy(p.r_star_commitments, s.r_star_commitments.data(), sizeof p.r_star_commitments);
+      memcpy(p.z_star_commitment, s.z_star_commitment.data(), 144);
+      memcpy(p.sorted_commitments, s.sorted_commitments.data(), sizeof p.sorted_commitments);
+      memcpy(p.products, s.products.data(), sizeof p.products);
+      memcpy(p.acc_v_commitments, s.acc_v_commitments.data(), sizeof p.acc_v_commitments);
+      memcpy(p.claimed_sumchecks, s.claimed_sumchecks.data(), sizeof p.claimed_sumchecks);
+      memcpy(p.ralpha_star_acc_mu_evals, s.ralpha_star_acc_mu_evals.data(), sizeof p.ralpha_star_acc_mu_evals);
+      memcpy(p.ralpha_star_acc_mu_proof, s.ralpha_star_acc_mu_proof.data(), 144);
+      memcpy(p.rstars_vals, s.rstars_vals.data(), sizeof p.rstars_vals);
+      for (size_t i = 0; i < nf; i++) {
+        memcpy(fc.data() + 18 * i, tc.folded_polynomials_commitments[i].data(), 144);
+        memcpy(fe.data() + 8 * i, tc.folded_polynomials_evaluations[i].data(), 64);
+      }
+      p.nfold = p.cap_folds = nf;
+      p.fold_commitments = fc.data();
+      p.fold_evaluations = fe.data();
+      memcpy(p.evaluation_proof, tc.evaluation_proof.data(), 144);
+      memcpy(p.base_evaluations, tc.base_polynomials_evaluations[0].data(), sizeof p.base_evaluations);
+      return true;
+    }
+  };
 };
 
 }  // namespace gm
