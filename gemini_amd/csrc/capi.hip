@@ -786,6 +786,25 @@ int gm_debug_msm_sort_path(int* out) {
   return GM_OK;
 }
 
+int gm_set_msm_optimistic(int sort_bins, int boundary_pass) {
+  GM_CTX();
+  GM_CHECK((sort_bins == 0 || sort_bins == 1) && (boundary_pass == 0 || boundary_pass == 1), GM_EINVAL,
+           "gm_set_msm_optimistic: sort_bins = %d, boundary_pass = %d not in {0, 1}", sort_bins, boundary_pass);
+  std::lock_guard<std::recursive_mutex> lk(C->msm_mu);
+  C->msm_opt = (sort_bins ? MSM_OPT_BINS : 0) | (boundary_pass ? MSM_OPT_BOUNDARY : 0);
+  C->msm_opt_k = 0;
+  C->msm_opt_skip = 0;
+  return GM_OK;
+}
+
+int gm_debug_msm_optimistic(int out[5]) {
+  GM_CTX();
+  GM_CHECK(out != nullptr, GM_EINVAL, "gm_debug_msm_optimistic: null output");
+  std::lock_guard<std::recursive_mutex> lk(C->msm_mu);
+  for (int i = 0; i < 5; i++) out[i] = C->msm_opt_last[i];
+  return GM_OK;
+}
+
 int gm_set_msm_split(int on) {
   GM_CTX();
 #ifndef GM_EXPERIMENTS

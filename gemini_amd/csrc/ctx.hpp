@@ -241,7 +241,12 @@ struct MsmPending {
   int multi_levels = 0;  // > 0: several small MSMs in ONE pass (msm.hip: MsmMulti); bucket sets [l W, (l + 1) W) belong to call l
   int multi_W = 0;
   bool sort_compact = false;  // the block sort took the 4-byte pass-1 entries + k_sort2_group (gm_debug_msm_sort_path)
+  int opt = 0;                // parts of the optimistic one-call path this enqueue took (MSM_OPT_*), checked by the flags of its trailer
+  uint32_t L = 0;             // chunk length of k_acc0
 };
+// the optimistic one-call path (gm_set_msm_optimistic): pass 1 of the block sort into fixed-capacity bins, one boundary pass in
+// place of the merge levels; the same values name the flag a failed attempt raised
+enum { MSM_OPT_BINS = 1, MSM_OPT_BOUNDARY = 2 };
 struct MsmStreamSlot {
   uint8_t *raw = nullptr, *packed = nullptr, *scalars = nullptr;  // staged records, device-form bases, scalars
   size_t raw_cap = 0, packed_cap = 0, scalars_cap = 0;
@@ -395,6 +400,13 @@ struct Context {
   int msm_sort_group = 1;
   size_t msm_sort_group_cap = 0;
   int msm_sort_path_last = 0;  // what the last finished call took: 0 old, 1 compact, 2 compact with a chunked group
+  // the optimistic path of an unsplit one-call MSM (msm.hip: msm_run_one; gm_set_msm_optimistic): MSM_OPT_* bits that are switched on,
+  // the back-off after failed attempts (the next `msm_opt_skip` one-calls go straight to the general path; 2^msm_opt_k after the next
+  // failure), and the read-out of the last finished one-call (gm_debug_msm_optimistic)
+  int msm_opt = MSM_OPT_BINS | MSM_OPT_BOUNDARY;
+  int msm_opt_k = 0;
+  uint32_t msm_opt_skip = 0;
+  int msm_opt_last[5] = {0, 0, 0, 0, 0};
   size_t msm_table_min = (size_t)1 << 17;  // smallest MSM that uses fixed-base tables when present
   // small results (per-block partial sums, the bit-plane sums of an MSM) are written by their kernels straight into pinned host
   // memory instead of a device buffer that a blit kernel then copies (GM_ZERO_COPY=0 restores the copies; bit 0 field paths, bit 1 MSM planes.  Two A/B runs on one box: snark -i 20 14.9 -> 14.5 ms, -i 24 117.8 -> 117.0, psnark -i 20 129 -> 127, same proof bytes: profiles/r4_zero_copy_probe.txt)

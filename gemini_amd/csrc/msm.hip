@@ -28,6 +28,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdlib>
 #include <cstring>
@@ -599,8 +600,13 @@ GM_DEV uint64_t sort_entry_expand(uint32_t v, uint32_t g, uint32_t FB) {
 // k_sort1_staged for those entries: the same 1024 scalars per block, the LDS image is 4 bytes per entry (2048 scalars per block,
 // which would keep the byte length of the runs, measured the same: profiles/msm_group_sort.md).  Plain calls only (no levels,
 // tables or GLV).  The image leaves by coarse bin, one half-wave per bin, as one contiguous run.
+// bin > 0 (the optimistic one-call path): group g owns the fixed bin tmp[g bin .. (g + 1) bin) and gcursor[g], zero from the call's
+// memset, counts its entries -- no coarse count, no coarse scan in front of this kernel.  A run that would end past its bin is not
+// written and raises *ovf (the call is then repeated through the counting passes); the scalar-range check of the coarse count
+// (*err) is made here.
 __global__ __launch_bounds__(1024) void k_sort1_staged_c(const uint32_t* __restrict__ scalars, uint32_t n, int mont, SortGeom sg,
-                                                         uint32_t* __restrict__ gcursor, uint32_t* __restrict__ tmp) {
+                                                         uint32_t* __restrict__ gcursor, uint32_t* __restrict__ tmp, uint32_t bin,
+                                                         uint32_t* __restrict__ ovf, uint32_t* __restrict__ err) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   uint32_t* buf = reinterpret_cast<uint32_t*>(smem);
   uint32_t* cnt = buf + (size_t)SORT_TS * sg.Wg;
@@ -626,6 +632,7 @@ __global__ __launch_bounds__(1024) void k_sort1_staged_c(const uint32_t* __restr
       ks[j] = k;
       wave_atomic_inc(cnt, k != ~0u ? (k & 0x7fffffffu) >> sg.FB : KEY_INV);
     }
+    if (bin && it.bad) atomicOr(err, 1u);  // a scalar >= 2^255 (not an Fr image): the call fails with GM_EINVAL
   }
   __syncthreads();
   const uint32_t per = (sg.G + 1023u) / 1024u;
@@ -634,7 +641,16 @@ __global__ __launch_bounds__(1024) void k_sort1_staged_c(const uint32_t* __restr
     const uint32_t g = tid * per + k;
     if (g < sg.G) {
       const uint32_t c = cnt[g];
-      base[g] = c ? atomicAdd(gcursor + g, c) : 0u;
+      uint32_t b = c ? atomicAdd(gcursor + g, c) : 0u;
+      if (bin && c) {
+        if (b + c > bin) {
+          atomicOr(ovf, 1u);
+          b = KEY_INV;  // this run stays in LDS
+        } else {
+          b += g * bin;
+        }
+      }
+      base[g] = b;
       s += c;
     }
   }
@@ -673,7 +689,8 @@ __global__ __launch_bounds__(1024) void k_sort1_staged_c(const uint32_t* __restr
   for (uint32_t k = 0; k * 32u < sg.G; k++) {
     const uint32_t g = k * 32u + ((hw + k) & 31u);
     if (g >= sg.G) continue;
-    const uint32_t c = cnt[g], l0 = lst[g], b0 = base[g];
+    const uint32_t l0 = lst[g], b0 = base[g];
+    const uint32_t c = b0 != KEY_INV ? cnt[g] : 0u;
     for (uint32_t o = hl; o < c; o += 32u) tmp[b0 + o] = buf[l0 + o];
   }
 }
@@ -699,6 +716,9 @@ GM_DEV uint32_t block_inclusive_scan_1024(uint32_t v, uint32_t* wsum /* 16 */) {
 // entries -- lane j writes entries[goff[g] + j].  A larger group (n near 2^21, skewed or all-equal scalars) takes the same block
 // two sweeps: a counting sweep over the whole group, then the chunks of `cap` entries one after the other, each to its bins'
 // next free ranges.  The block writes counts[] and offsets[] of its 2^FB buckets; blocks do not depend on one another.
+// bin > 0 (fixed bins, G <= 1024, bin <= cap): the group is tmp[g bin .. g bin + gcur[g]) and its output offset the sum of the
+// gcur[] in front of it, which every block scans for itself; block 0 writes the entry count k_acc0 reads.  If pass 1 raised *ovf the
+// bins are incomplete: the count becomes 0 and nothing else is written.
 // Dynamic LDS: three arrays of 1024 counters, 16 wave sums, cap entries.
 constexpr uint32_t SORT2G_QPT = 10;  // 16-byte loads per thread: 40 Ki entries >= MSM_SORT_GROUP_CAP_MAX + 3
 static_assert(SORT2G_QPT * 4096 >= MSM_SORT_GROUP_CAP_MAX + 3, "k_sort2_group: a chunk must fit the registers of its block");
@@ -740,7 +760,8 @@ struct Sort2gChunk {
 };
 __global__ __launch_bounds__(1024) void k_sort2_group(const uint32_t* __restrict__ tmp, const uint32_t* __restrict__ goff, SortGeom sg, uint32_t cap,
                                                       uint32_t* __restrict__ counts, uint32_t* __restrict__ offsets, uint64_t* __restrict__ entries,
-                                                      uint32_t* __restrict__ chunked) {
+                                                      uint32_t* __restrict__ chunked, uint32_t bin, const uint32_t* __restrict__ gcur,
+                                                      const uint32_t* __restrict__ ovf, uint32_t* __restrict__ total_out) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   uint32_t* ccnt = reinterpret_cast<uint32_t*>(smem);  // counts of the chunk per fine bin
   uint32_t* clst = ccnt + 1024;                        // ... and their exclusive scan
@@ -749,7 +770,29 @@ __global__ __launch_bounds__(1024) void k_sort2_group(const uint32_t* __restrict
   uint32_t* buf = wsum + 16;
   const uint32_t tid = threadIdx.x, g = blockIdx.x;
   const uint32_t nf = 1u << sg.FB, fsh = 32u - sg.FB, b0 = g << sg.FB;
-  const uint32_t lo = goff[g], m = goff[g + 1] - lo;
+  uint32_t lo, m, src;  // the group's place in entries[], its length, its place in tmp[]
+  if (bin) {
+    if (*ovf) {  // block-uniform
+      if (g == 0 && tid == 0) *total_out = 0u;
+      return;
+    }
+    const uint32_t mine = tid < sg.G ? gcur[tid] : 0u;
+    const uint32_t inc = block_inclusive_scan_1024(mine, wsum);
+    if (tid == g) {
+      glst[0] = inc - mine;
+      glst[1] = mine;
+    }
+    if (g == 0 && tid == 1023) *total_out = inc;
+    __syncthreads();
+    lo = glst[0];
+    m = glst[1];
+    src = g * bin;
+    __syncthreads();
+  } else {
+    lo = goff[g];
+    m = goff[g + 1] - lo;
+    src = lo;
+  }
   if (m == 0) {  // counts[] are zero from the call's memset
     if (tid < nf) offsets[b0 + tid] = lo;
     return;
@@ -761,7 +804,7 @@ __global__ __launch_bounds__(1024) void k_sort2_group(const uint32_t* __restrict
     constexpr uint32_t CQ = 4;  // (steps of 16 Ki entries: the chunks' 40 registers per thread here as well would spill)
     for (uint32_t c0 = 0; c0 < m; c0 += CQ * 4096 - 3) {
       Sort2gChunk<CQ> ch;
-      ch.load(tmp, lo + c0, min(CQ * 4096 - 3, m - c0));
+      ch.load(tmp, src + c0, min(CQ * 4096 - 3, m - c0));
       ch.count(glst, fsh);
     }
     __syncthreads();
@@ -779,7 +822,7 @@ __global__ __launch_bounds__(1024) void k_sort2_group(const uint32_t* __restrict
     ccnt[tid] = 0;
     __syncthreads();
     Sort2gChunk<SORT2G_QPT> ch;
-    ch.load(tmp, lo + c0, mc);
+    ch.load(tmp, src + c0, mc);
     ch.count(ccnt, fsh);
     __syncthreads();
     const uint32_t c = ccnt[tid];
@@ -1405,6 +1448,46 @@ __global__ __launch_bounds__(64) void k_merge(const uint32_t* __restrict__ keys_
   }
 }
 
+// The chunk boundaries of k_acc0 in ONE full-width pass (the optimistic one-call path), in place of the merge levels: thread t
+// looks at lane t's keyed partials and at its two neighbours' keys.  While no bucket is longer than L + 1 entries every bucket
+// that crosses a lane boundary is exactly (last partial of lane t) + (head of lane t + 1): thread t owns its lane's LAST partial
+// -- the tail, or the head of a lane with a single run --, adds the next lane's head if that has the same key and stores the
+// bucket; a head that does not continue the previous lane's last run is a whole bucket and is stored by its own thread.  A lane
+// with a single run whose key is also the previous lane's last key and the next lane's head key is the middle of a run of three
+// or more partials: its thread raises *long_run and the call is repeated through k_merge.  No LDS, no dependency between threads.
+__global__ __launch_bounds__(256) void k_boundary(const uint32_t* __restrict__ pk, const uint8_t* __restrict__ pp, uint32_t T,
+                                                  uint8_t* __restrict__ buckets, uint32_t* __restrict__ long_run) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= T) return;
+  const uint32_t hk = pk[2 * (size_t)t], tk = pk[2 * (size_t)t + 1];
+  if (hk == KEY_INV) return;  // a lane beyond the entries
+  uint32_t prev_last = KEY_INV;
+  if (t > 0) {
+    const uint32_t ptk = pk[2 * (size_t)t - 1];
+    prev_last = ptk != KEY_INV ? ptk : pk[2 * (size_t)t - 2];
+  }
+  const uint32_t nhk = t + 1 < T ? pk[2 * (size_t)t + 2] : KEY_INV;
+  const bool single = tk == KEY_INV, continued = prev_last == hk;
+  if (single && continued) {  // the previous lane's thread adds this partial to its own
+    if (nhk == hk) atomicOr(long_run, 1u);
+    return;
+  }
+  if (!single && !continued) {
+    Acc30 h;
+    acc30_load(h, pp + (2 * (size_t)t) * XYZZ30_BYTES);
+    acc30_store(buckets + (size_t)hk * XYZZ30_BYTES, h);
+  }
+  const uint32_t lk = single ? hk : tk;
+  Acc30 a;
+  acc30_load(a, pp + (2 * (size_t)t + (single ? 0u : 1u)) * XYZZ30_BYTES);
+  if (nhk == lk) {
+    Acc30 o;
+    acc30_load(o, pp + (2 * (size_t)t + 2) * XYZZ30_BYTES);
+    acc30_add(a, o);
+  }
+  acc30_store(buckets + (size_t)lk * XYZZ30_BYTES, a);
+}
+
 // ------------------------------------------------------------------------------------------
 // bucket reduction by plain sums, several lanes per output element
 //
@@ -1439,6 +1522,7 @@ struct GroupSumJobs {
   uint32_t* err_dst;         // ... and the clock readings of the call's k_acc0 (two 64-bit words at err_dst + 2)
   const unsigned long long* clk_src;
   const uint32_t* chunked_src;  // ... and k_sort2_group's "a group was chunked" word, to err_dst[1]
+  const uint32_t* opt_src;      // ... and the two flag words of the optimistic path (bin overflow, long run), to err_dst[6], [7]
 };
 
 // up to three independent jobs per launch so that passes of the same level overlap instead of
@@ -1453,6 +1537,8 @@ __global__ __launch_bounds__(256) void k_group_sum(GroupSumJobs J) {
       d[0] = J.clk_src[0];
       d[1] = J.clk_src[1];
     }
+    J.err_dst[6] = J.opt_src ? J.opt_src[0] : 0u;
+    J.err_dst[7] = J.opt_src ? J.opt_src[1] : 0u;
   }
   const int job = blockIdx.x < J.blk_end[0] ? 0 : (blockIdx.x < J.blk_end[1] ? 1 : 2);
   const GroupSumArgs& a = J.j[job];
@@ -1830,14 +1916,15 @@ struct MsmMulti {
 constexpr size_t MSM_MULTI_MAX_N = (size_t)1 << 13;  // calls this small (c = 8 on their own as well) are fused
 constexpr size_t MSM_MULTI_BLOCK_MAX_N = (size_t)1 << 20;  // and the mid-size ones above them, up to this, as the levels of a block-sorted pass
 static int msm_enqueue(Context* C, MsmWorkspace& ws, MsmStreams sts, const Bases* bases, int64_t first, int64_t step, const void* d_scalars,
-                       int mont, size_t n, int slot, MsmPending* P, int part = 0, int nparts = 1, const MsmMulti* multi = nullptr);
+                       int mont, size_t n, int slot, MsmPending* P, int part = 0, int nparts = 1, const MsmMulti* multi = nullptr, int opt = 0);
 static int msm_finish_parts(Context* C, const MsmPending* parts, int nparts, bool normalize, uint64_t out_jac[18], bool use_pool = true,
-                            uint64_t* const* multi_out = nullptr);
+                            uint64_t* const* multi_out = nullptr, int* opt_failed = nullptr);
 // the helper threads of the host tail (class HornerPool, below)
 static void horner_pool_prewake();
 static void horner_pool_run(int n, const std::function<void(int)>& fn);
-static int msm_finish(Context* C, const MsmPending& P, bool normalize, uint64_t out_jac[18], bool use_pool = true) {
-  return msm_finish_parts(C, &P, 1, normalize, out_jac, use_pool);
+// opt_failed: the MSM_OPT_* parts of an optimistic enqueue whose flag the device raised; then there is no result (GM_OK all the same)
+static int msm_finish(Context* C, const MsmPending& P, bool normalize, uint64_t out_jac[18], bool use_pool = true, int* opt_failed = nullptr) {
+  return msm_finish_parts(C, &P, 1, normalize, out_jac, use_pool, nullptr, opt_failed);
 }
 
 // Calls larger than 2^26 pairs are split into 2^26-pair MSMs whose results are added on the host --
@@ -1881,10 +1968,42 @@ static int msm_run_one(Context* C, const Bases* bases, int64_t first, int64_t st
                       n < ((size_t)1 << ENTRY_W_SHIFT);
   const bool split = GM_GLV(1) && C->msm_split && n >= MSM_SPLIT_MIN_N && !tables && C->msm_affine_levels == 0 && C->stream_b && C->small_stream[0];
   if (!split) {
+    // The optimistic path (gm_set_msm_optimistic): fixed sort bins and one boundary pass are right only while every coarse group
+    // fits its bin and no bucket spans three lanes of k_acc0.  The device checks both and says so in the trailer of the plane
+    // sums; a call whose attempt failed is enqueued again with the failed part switched off.  So that a stream of skewed calls
+    // (the reference's elastic benchmark: all scalars equal) does not pay twice each time, the next 2^k one-calls after a failed
+    // one go straight to the general path, k = 0, 1, .. 10 growing with every consecutive failure and reset by a success.
+    int want = C->msm_opt;
+    if (want && C->msm_opt_skip > 0) {
+      C->msm_opt_skip--;
+      want = 0;
+    }
+    const bool tried = want != 0;
+    int failed = 0, took = 0;
     MsmPending P;
-    int rc = msm_enqueue(C, C->msm, MsmStreams{C->stream, C->stream, C->stream}, bases, first, step, d_scalars, mont, n, 0, &P);
-    if (rc) return rc;
-    return msm_finish(C, P, normalize, out_jac);
+    for (;;) {
+      int rc = msm_enqueue(C, C->msm, MsmStreams{C->stream, C->stream, C->stream}, bases, first, step, d_scalars, mont, n, 0, &P, 0, 1, nullptr, want);
+      if (rc) return rc;
+      int f = 0;
+      rc = msm_finish(C, P, normalize, out_jac, true, &f);
+      if (rc) return rc;
+      if (!failed) took = P.opt;  // what the first attempt took
+      if (!f) break;
+      failed |= f;
+      want &= ~f;
+    }
+    if (failed) {
+      C->msm_opt_skip = 1u << C->msm_opt_k;
+      if (C->msm_opt_k < 10) C->msm_opt_k++;
+      C->msm_opt_last[3]++;
+    } else if (tried && took) {
+      C->msm_opt_k = 0;
+    }
+    C->msm_opt_last[0] = (P.opt & MSM_OPT_BINS) ? 1 : 0;  // of the attempt that gave the result
+    C->msm_opt_last[1] = (P.opt & MSM_OPT_BOUNDARY) ? 1 : 0;
+    C->msm_opt_last[2] = failed;
+    C->msm_opt_last[4] = (int)P.L;
+    return GM_OK;
   }
   if (!C->have_start_ev) {
     GM_HIP(hipEventCreateWithFlags(&C->start_ev, hipEventDisableTiming));
@@ -2234,13 +2353,16 @@ int msm_run_batch_at(Context* C, const Bases* bases, int64_t first, int64_t step
 }
 
 static int msm_enqueue(Context* C, MsmWorkspace& ws, MsmStreams sts, const Bases* bases, int64_t first, int64_t step, const void* d_scalars,
-                       int mont, size_t n, int slot, MsmPending* P, int part, int nparts, const MsmMulti* multi) {
+                       int mont, size_t n, int slot, MsmPending* P, int part, int nparts, const MsmMulti* multi, int opt) {
   hipStream_t st = sts.sort;  // memsets + sort; the accumulation runs on sts.acc, everything after it on sts.tail
   const size_t nbases = bases->n;
   P->ws = &ws;
   P->slot = slot;
   P->multi_levels = 0;
   P->sort_compact = false;
+  P->opt = 0;
+  P->L = 0;
+  if (multi || nparts != 1) opt = 0;  // the optimistic path is the unsplit one-call's (msm_run_one)
   if (multi) {
     GM_CHECK(multi->levels >= 1 && multi->levels <= MULTI_MAX_LEVELS && nparts == 1, GM_EINVAL, "msm: %d fused calls (1 .. %d)", multi->levels, MULTI_MAX_LEVELS);
     // the entries of a fused pass carry ABSOLUTE base indices in 30 bits (bit 30: the GLV half, bit 31: the sign)
@@ -2362,11 +2484,12 @@ static int msm_enqueue(Context* C, MsmWorkspace& ws, MsmStreams sts, const Bases
   const uint64_t T0 = (Nacc + L - 1) / L;
   const uint64_t T0pad = (T0 + 255) / 256 * 256;
   const uint64_t E1 = 2 * T0pad;
+  P->L = L;
 
   int rc;
   // [nbuckets + 1] = scalar-range flag; behind it the coarse-bin counters of the block sort and the word k_sort2_group sets when
-  // it chunks a group, so that ONE memset clears them all
-  const size_t counts_words = (nbuckets + 2 + SORT_GMAX + 2 + 63) / 64 * 64;
+  // it chunks a group, then the two flag words of the optimistic path, so that ONE memset clears them all
+  const size_t counts_words = (nbuckets + 2 + SORT_GMAX + 4 + 63) / 64 * 64;
   if ((rc = ws.counts.ensure(counts_words * 4))) return rc;
   if ((rc = ws.offsets.ensure((nbuckets + 1) * 4))) return rc;
   if ((rc = ws.cursor.ensure((nbuckets + 1) * 4))) return rc;
@@ -2383,6 +2506,7 @@ static int msm_enqueue(Context* C, MsmWorkspace& ws, MsmStreams sts, const Bases
   GM_HIP(hipMemsetAsync(ws.counts.p, 0, counts_words * 4, st));
   uint32_t* d_err = ws.counts.as<uint32_t>() + nbuckets + 1;
   uint32_t* d_chunked = ws.counts.as<uint32_t>() + nbuckets + 2 + SORT_GMAX + 1;
+  uint32_t* d_opt = d_chunked + 1;  // [0]: a run of pass 1 did not fit its fixed bin, [1]: k_boundary met a bucket of three or more partials
   // levels (an experiment build) rewrite the entry lists, so the counts no longer say which buckets get written: clear there
   const bool bucket_counts_valid = levels == 0;
   if (!bucket_counts_valid) GM_HIP(hipMemsetAsync(ws.buckets.p, 0, nbuckets * bucket_bytes, st));
@@ -2508,12 +2632,29 @@ static int msm_enqueue(Context* C, MsmWorkspace& ws, MsmStreams sts, const Bases
                               sg.FB <= 10 && ceil_log2_sz(n) + (int)sg.FB + 1 <= 32 && sort1_staged_env && sort_staged &&
                               sg.Wg <= SORT1_STAGE_WMAX && stage1c_lds <= 160 * 1024;
     P->sort_compact = sort_compact;
+    const uint32_t cap = (uint32_t)(C->msm_sort_group_cap ? C->msm_sort_group_cap : MSM_SORT_GROUP_CAP_MAX);
+    // The optimistic path: pass 1 straight into one fixed bin per coarse group, no coarse count and no coarse scan.  The bin is
+    // sized from n: the mean group size + 25 % + 1024 entries (uniform scalars put 32 / 29 of the mean into the groups of the top
+    // window, whose digits end at 0x73ED), a multiple of 4 so that chunk loads stay aligned, never above what a block of pass 2
+    // loads at once -- and only taken if that leaves the top window's groups room (mean x 9 / 8).
+    uint32_t bin = 0;
+    if (sort_compact && (opt & MSM_OPT_BINS) && sg.G <= 1024) {
+      const uint64_t mean = (N + sg.G - 1) / sg.G;
+      const uint64_t want = std::min<uint64_t>((mean + mean / 4 + 1024 + 3) & ~(uint64_t)3, cap & ~3u);
+      if (mean + mean / 8 <= want) bin = (uint32_t)want;
+    }
+    if (bin) {
+      P->opt |= MSM_OPT_BINS;
+      if ((rc = ws.tmp_entries.ensure((size_t)sg.G * bin * 4 + 16))) return rc;
+    }
     uint32_t* tmp32 = ws.tmp_entries.as<uint32_t>();
     pf.begin(part, PROF_DIGITS, st);
-    hipLaunchKernelGGL(k_sort1<false>, dim3(b1), dim3(256), 0, st, sc, (uint32_t)n, mont, sg, lg, gcount, (uint64_t*)nullptr, d_err);
-    // (k_sort2_group writes the buckets' offsets itself: the entry count k_acc0 reads behind them comes from the coarse scan)
-    hipLaunchKernelGGL(k_sort1_scan, dim3(1), dim3(1024), 0, st, gcount, sg.G, goff, gcursor, blkoff,
-                       sort_compact ? ws.offsets.as<uint32_t>() + nbuckets : (uint32_t*)nullptr);
+    if (!bin) {
+      hipLaunchKernelGGL(k_sort1<false>, dim3(b1), dim3(256), 0, st, sc, (uint32_t)n, mont, sg, lg, gcount, (uint64_t*)nullptr, d_err);
+      // (k_sort2_group writes the buckets' offsets itself: the entry count k_acc0 reads behind them comes from the coarse scan)
+      hipLaunchKernelGGL(k_sort1_scan, dim3(1), dim3(1024), 0, st, gcount, sg.G, goff, gcursor, blkoff,
+                         sort_compact ? ws.offsets.as<uint32_t>() + nbuckets : (uint32_t*)nullptr);
+    }
     const size_t stage1_lds = (size_t)SORT_TS * sg.Wg * (use_glv ? 2 : 1) * 8 + (size_t)3 * sg.G * 4 + 1024 * 4;
     if (sort_compact) {
       static bool attr_set = false;
@@ -2522,7 +2663,9 @@ static int msm_enqueue(Context* C, MsmWorkspace& ws, MsmStreams sts, const Bases
         GM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sort2_group), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set = true;
       }
-      hipLaunchKernelGGL(k_sort1_staged_c, dim3(b1), dim3(1024), stage1c_lds, st, sc, (uint32_t)n, mont, sg, gcursor, tmp32);
+      // (fixed bins: the zeroed coarse counters are the cursors, relative to each bin)
+      hipLaunchKernelGGL(k_sort1_staged_c, dim3(b1), dim3(1024), stage1c_lds, st, sc, (uint32_t)n, mont, sg, bin ? gcount : gcursor, tmp32, bin, d_opt,
+                         d_err);
     } else if (sort1_staged_env && sg.Wg * (use_glv ? 2 : 1) <= SORT1_STAGE_WMAX && stage1_lds <= 160 * 1024) {
       static bool attr_set = false;
       if (!attr_set) {
@@ -2536,9 +2679,8 @@ static int msm_enqueue(Context* C, MsmWorkspace& ws, MsmStreams sts, const Bases
     pf.end(part, PROF_DIGITS, st);
     pf.begin(part, PROF_SCATTER, st);
     if (sort_compact) {
-      const uint32_t cap = (uint32_t)(C->msm_sort_group_cap ? C->msm_sort_group_cap : MSM_SORT_GROUP_CAP_MAX);
       hipLaunchKernelGGL(k_sort2_group, dim3(sg.G), dim3(1024), (size_t)(3 * 1024 + 16 + cap) * 4, st, tmp32, goff, sg, cap, ws.counts.as<uint32_t>(),
-                         ws.offsets.as<uint32_t>(), ws.entries.as<uint64_t>(), d_chunked);
+                         ws.offsets.as<uint32_t>(), ws.entries.as<uint64_t>(), d_chunked, bin, gcount, d_opt, ws.offsets.as<uint32_t>() + nbuckets);
     } else {
       hipLaunchKernelGGL(k_sort2<false>, dim3(b2), dim3(256), 0, st, ws.tmp_entries.as<uint64_t>(), goff, blkoff, sg,
                          ws.counts.as<uint32_t>(), (uint64_t*)nullptr);
@@ -2598,7 +2740,19 @@ static int msm_enqueue(Context* C, MsmWorkspace& ws, MsmStreams sts, const Bases
   }
   st = sts.tail;
   pf.begin(part, PROF_MERGE, st);
-  {
+  // The boundary pass is tried only where uniform scalars make a bucket of L + 2 entries (the shortest that can span three lanes)
+  // unlikely: buckets x the Chernoff bound of the Poisson tail P(X >= k) <= e^-m (e m / k)^k, m = entries per bucket, stays below
+  // 1 (0.54 at 2^20 pairs: m = 32, L = 64; small calls run with L = 4 and m up to 30 and keep the merge levels)
+  bool boundary = false;
+  if (opt & MSM_OPT_BOUNDARY) {
+    const double mean = (double)N / (double)nbuckets, k = (double)L + 2.0;
+    boundary = mean < k && (double)nbuckets * std::exp(k - mean + k * std::log(mean / k)) <= 1.0;
+  }
+  if (boundary) {
+    P->opt |= MSM_OPT_BOUNDARY;
+    hipLaunchKernelGGL(k_boundary, dim3((uint32_t)(T0pad / 256)), dim3(256), 0, st, ws.pk[0].as<uint32_t>(), ws.pp[0].as<uint8_t>(), (uint32_t)T0pad,
+                       ws.buckets.as<uint8_t>(), d_opt + 1);
+  } else {
     uint64_t E = E1;
     int src = 0;
     for (;;) {
@@ -2677,6 +2831,7 @@ static int msm_enqueue(Context* C, MsmWorkspace& ws, MsmStreams sts, const Bases
       J.err_dst = reinterpret_cast<uint32_t*>(planes + plane_count * XYZZ_BYTES);
       J.clk_src = ws.clk.as<unsigned long long>();
       J.chunked_src = d_chunked;
+      J.opt_src = d_opt;
     }
     uint32_t tot = 0;
     int k = 0;
@@ -2695,7 +2850,8 @@ static int msm_enqueue(Context* C, MsmWorkspace& ws, MsmStreams sts, const Bases
     plane_off[k] = plane_count;
     plane_count += (size_t)Wb * (wf[k] + 1);
   }
-  const size_t plane_bytes = plane_count * XYZZ_BYTES + 24;  // + the scalar-range flag, the sort's chunked word + k_acc0's clock readings
+  // + the scalar-range flag, the sort's chunked word, k_acc0's clock readings + the two flag words of the optimistic path
+  const size_t plane_bytes = plane_count * XYZZ_BYTES + 32;
   if (ws.host_planes_cap[slot] < plane_bytes) {
     if (ws.host_planes[slot]) (void)hipHostFree(ws.host_planes[slot]);
     ws.host_planes[slot] = nullptr;
@@ -2907,7 +3063,9 @@ static void horner_pool_run(int n, const std::function<void(int)>& fn) { HornerP
 
 // use_pool = false: the whole tail on the calling thread (the batch finishes several small calls side by side, ONE per helper
 // thread -- a small call's tail is 256 dependent doublings that no pool can split, and a batch of twenty of them was HOST-bound)
-static int msm_finish_parts(Context* C, const MsmPending* parts, int nparts, bool normalize, uint64_t out_jac[18], bool use_pool, uint64_t* const* multi_out) {
+static int msm_finish_parts(Context* C, const MsmPending* parts, int nparts, bool normalize, uint64_t out_jac[18], bool use_pool, uint64_t* const* multi_out,
+                            int* opt_failed) {
+  if (opt_failed) *opt_failed = 0;
   gmh::G1 result = gmh::G1::identity();
   // Horner over bit positions, window groups and bucket sets high -> low (variable_base.rs:168-175 with the
   // weighted bucket sum unrolled into its bit-planes): total = sum_w 2^(cw) * (sum_j 2^j Z_{w,j} + Tot_w).
@@ -2928,6 +3086,15 @@ static int msm_finish_parts(Context* C, const MsmPending* parts, int nparts, boo
       continue;
     }
     if (rc) continue;
+    if (P.opt) {  // an optimistic one-call (one part): a raised flag means the planes are not the result
+      const uint64_t fl = hp[P.plane_count * 24 + 3];
+      const int failed = P.opt & (((uint32_t)fl != 0 ? MSM_OPT_BINS : 0) | ((fl >> 32) != 0 ? MSM_OPT_BOUNDARY : 0));
+      if (failed) {
+        if (use_pool) C->prof.collect();
+        if (opt_failed) *opt_failed = failed;
+        return opt_failed ? GM_OK : GM_ESTATE;
+      }
+    }
     auto plane_at = [&](int w, int field, uint32_t j) {
       return gmh::xyzz_to_jac_dev(hp + (P.plane_off[field] + (size_t)w * (P.wf[field] + 1) + j) * 24);
     };

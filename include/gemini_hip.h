@@ -252,6 +252,19 @@ int gm_set_msm_sort_group(int mode, size_t cap);
 /* Which sort the last finished MSM call took: 0 = the 8-byte passes (or no block sort at all), 1 = 4-byte entries with every
  * coarse group loaded once, 2 = 4-byte entries with at least one group chunked.  Travels with the call's result: no extra sync. */
 int gm_debug_msm_sort_path(int* out);
+/* The optimistic path of an unsplit one-call MSM (batches, fused passes, streams and G2 do not take it).  sort_bins (default 1):
+ * where gm_set_msm_sort_group's 4-byte sort applies and the mean coarse group leaves room, its first pass writes into one
+ * fixed-capacity bin per group, without the counting pass and the scan in front of it.  boundary_pass (default 1): the buckets
+ * that cross a chunk boundary of the accumulation are finished by one full-width pass in place of the merge levels.  The device
+ * checks what each part relies on (every group fits its bin; no bucket is spread over three or more chunks); a call whose check
+ * fails is run again without that part, and the next 2^k one-calls (k = 0 .. 10, one more per consecutive failure, reset by a
+ * success) go straight to the general path.  The result does not depend on either.  Setting resets the back-off.  GM_EINVAL for
+ * values outside {0, 1}.  Test / A-B knob. */
+int gm_set_msm_optimistic(int sort_bins, int boundary_pass);
+/* The last finished one-call MSM: out[0] = fixed bins gave the result, out[1] = the boundary pass gave the result, out[2] = 0 or
+ * the parts whose check failed and made the call run again (1 = a bin overflowed, 2 = a bucket of three or more chunks, 3 = both),
+ * out[3] = calls run again since gm_init, out[4] = the chunk length L of the accumulation. */
+int gm_debug_msm_optimistic(int out[5]);
 /* Tuning knob (default 0): run one-call MSMs of >= 2^17 pairs as two window groups pipelined over three streams.
  * Same results; slower on MI355X as measured.  Builds with -DGM_EXPERIMENTS only; otherwise on != 0 returns GM_EINVAL. */
 int gm_set_msm_split(int on);

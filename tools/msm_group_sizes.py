@@ -9,7 +9,9 @@ the carry of the last window folded back in.
     python tools/msm_group_sizes.py [--logn 20]          # no GPU needed
 
 prints, for each of the two seeded scalar sets of bench.py, the largest group, the largest group outside the top window, the
-number of non-empty groups of the top window and how many groups exceed the capacity (profiles/msm_group_sort.md quotes it)."""
+number of non-empty groups of the top window and how many groups exceed the capacity (profiles/msm_group_sort.md quotes it), and
+the largest BUCKET against L + 2, L the chunk length of k_acc0: a bucket of at least L + 2 entries can span three lanes, which
+the boundary pass of the optimistic one-call path (k_boundary) hands back to the merge levels (profiles/msm_optimistic_tail.md)."""
 import argparse
 import os
 import sys
@@ -42,6 +44,13 @@ def coarse_group_sizes(scalars: np.ndarray, c: int = C_WINDOW, fb: int = FB) -> 
     return sizes
 
 
+def chunk_length(n: int, W: int = 16) -> int:
+    """msm_enqueue's chunk length L of k_acc0 for a plain call of n pairs"""
+    N = n * W
+    lanes = 262144 if N >= 1 << 24 else 131072
+    return (min(256, max(4, -(-N // lanes))) + 1) & ~1
+
+
 def main():
     import bench
 
@@ -55,10 +64,17 @@ def main():
     print(f"n = 2^{args.logn}, c = {C_WINDOW}, FB = {FB}: {16 * gpw} coarse groups, capacity of one block {CAP_MAX} entries")
     print("| scalar set | entries | largest group | largest outside the top window | non-empty groups of the top window | groups over the capacity |")
     print("|---|---:|---:|---:|---:|---:|")
+    largest = []
     for k in range(2):
-        s = coarse_group_sizes(bench.uniform_fr(rng, n))
+        sc = bench.uniform_fr(rng, n)
+        s = coarse_group_sizes(sc)
         top = s[-gpw:]
         print(f"| {k} | {s.sum()} | {s.max()} | {s[:-gpw].max()} | {(top > 0).sum()} | {(s > CAP_MAX).sum()} |")
+        largest.append(int(coarse_group_sizes(sc, fb=0).max()))  # FB = 0: one group per bucket
+    L = chunk_length(n)
+    for k, b in enumerate(largest):
+        print(f"scalar set {k}: largest bucket {b} entries against L + 2 = {L + 2} (L = {L}): "
+              + ("no bucket spans three lanes" if b < L + 2 else "a bucket may span three lanes"))
 
 
 if __name__ == "__main__":
