@@ -59,6 +59,7 @@ SYMBOLS = [
     "gm_g1_check", "gm_g2_check", "gm_g1_bases_check", "gm_g2_bases_check", "gm_g1_bases_from_bytes", "gm_g1_powers_check",
     "gm_g2_bases_from_bytes", "gm_g1_bases_to_bytes", "gm_g2_bases_to_bytes", "gm_crs_from_bases", "gm_crs_check", "gm_vk_check",
     "gm_snark_proof_check", "gm_psnark_proof_check", "gm_ipa_check", "gm_debug_fq2_sqrt",
+    "gm_debug_fq_op", "gm_debug_fq30_op", "gm_debug_fq2_op", "gm_debug_g1_op", "gm_debug_g2_op", "gm_debug_acc30_op",
     "gm_g2_fixed_base_register", "gm_g2_srs_register", "gm_g1_bases_from_candidates", "gm_g2_bases_from_candidates",
     "gm_crs_truncate", "gm_crs_halve", "gm_crs_fold", "gm_crs_to_bases",
     "gm_ipa_foldings_fg1", "gm_ipa_foldings_fg2", "gm_ipa_free", "gm_ipa_host_times", "gm_ipa_from_fields", "gm_ipa_verify", "gm_transcript_append_gt",

@@ -1214,6 +1214,49 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, WAVE
 #endif
 }
 
+// gm_debug_acc30_op, a test aid: ONE of the two Acc30 statements per lane, records in and records out, under k_acc0's launch
+// attributes.  op 0: acc = g1_madd30_asm(acc, base, neg), `other` n x 24 canonical words; op 1: acc30_add(acc, other), `other`
+// n x 52 loose limbs.  out: the 52 limbs the statement leaves; canon: acc30_to_canonical of them (4 x 12 words, as returned).
+// A lane beyond n runs the ordinary law on (1, 1, 1, 1) + (2, 1[, 1, 1]) -- field arithmetic only, p = 1 -- so the statement sees
+// a full EXEC mask in a partial block, as it does in k_acc0.
+enum { ACC30_OP_MADD = 0, ACC30_OP_ADD = 1 };
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_debug_acc30(int op, const uint32_t* __restrict__ acc, const uint32_t* __restrict__ other,
+                                                                                                const uint32_t* __restrict__ neg, size_t n, uint32_t* __restrict__ out,
+                                                                                                uint32_t* __restrict__ canon) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = i < n;
+  const FqE one = fqe_one(), two = fq_dbl(one);
+  G1Xyzz h;
+  h.x = h.y = h.zz = h.zzz = one;
+  Acc30 A;
+  if (live) acc30_load(A, acc + i * 52);
+  else acc30_from_canonical(A, h);
+  if (op == ACC30_OP_MADD) {
+    gm_u4v x0 = {two.l[0], two.l[1], two.l[2], two.l[3]}, x1 = {two.l[4], two.l[5], two.l[6], two.l[7]}, x2 = {two.l[8], two.l[9], two.l[10], two.l[11]};
+    gm_u4v y0 = {one.l[0], one.l[1], one.l[2], one.l[3]}, y1 = {one.l[4], one.l[5], one.l[6], one.l[7]}, y2 = {one.l[8], one.l[9], one.l[10], one.l[11]};
+    uint32_t sgn = 0;
+    if (live) {
+      const gm_u4v* bp = reinterpret_cast<const gm_u4v*>(other + i * 24);
+      x0 = bp[0]; x1 = bp[1]; x2 = bp[2]; y0 = bp[3]; y1 = bp[4]; y2 = bp[5];
+      sgn = neg[i];
+    }
+    (void)g1_madd30_asm(A, x0, x1, x2, y0, y1, y2, sgn);
+  } else {
+    Acc30 O;
+    h.x = two;
+    if (live) acc30_load(O, other + i * 52);
+    else acc30_from_canonical(O, h);
+    acc30_add(A, O);
+  }
+  if (!live) return;
+  acc30_store(out + i * 52, A);
+  const G1Xyzz c = acc30_to_canonical(A);
+  fqe_store(canon + i * 48, c.x);
+  fqe_store(canon + i * 48 + 12, c.y);
+  fqe_store(canon + i * 48 + 24, c.zz);
+  fqe_store(canon + i * 48 + 36, c.zzz);
+}
+
 // The same accumulation with the gather of entry i + 1 IN FLIGHT during the addition of entry i (24 more registers).  On the
 // plain path the 96 B x n bases sit in the Infinity Cache and the wait is short; the fixed-base tables are 13 x that (1.3 GB
 // at 2^20 points, 38 GB at 2^25) and every gather is a random HBM access of ~1-2 us, a tenth of the addition it feeds.
@@ -3690,6 +3733,35 @@ int fixed_base_generate(Context* C, const uint64_t base_affine[12], const void* 
 }
 
 }  // namespace gm
+
+int gm_debug_acc30_op(int op, const uint32_t* acc, const uint32_t* other, const uint32_t* neg, size_t n, uint32_t* out, uint32_t* out_canonical) {
+  using namespace gm;
+  GM_CTX();
+  GM_CHECK((acc && other && out && out_canonical && (neg || op != ACC30_OP_MADD)) || n == 0, GM_EINVAL, "debug_acc30_op: null pointer");
+  if (n == 0) return GM_OK;
+  GM_CHECK(op == ACC30_OP_MADD || op == ACC30_OP_ADD, GM_EINVAL, "debug_acc30_op: unknown op %d", op);
+  GM_CHECK(n <= (size_t)1 << 20, GM_EINVAL, "debug_acc30_op: %zu elements in one call (at most 2^20)", n);
+  GM_MSM_LOCK(C);
+  const size_t ow = op == ACC30_OP_MADD ? 24 : 52;
+  // acc | other | neg | out | canon, every part a multiple of 16 bytes after n is rounded up to 4
+  const size_t np = (n + 3) & ~(size_t)3;
+  uint32_t* d = nullptr;
+  GM_HIP(dev_malloc((void**)&d, np * (52 + ow + 1 + 52 + 48) * 4));
+  uint32_t *d_acc = d, *d_other = d_acc + np * 52, *d_neg = d_other + np * ow, *d_out = d_neg + np, *d_canon = d_out + np * 52;
+  hipError_t e = hipMemcpyAsync(d_acc, acc, n * 52 * 4, hipMemcpyHostToDevice, C->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_other, other, n * ow * 4, hipMemcpyHostToDevice, C->stream);
+  if (e == hipSuccess && op == ACC30_OP_MADD) e = hipMemcpyAsync(d_neg, neg, n * 4, hipMemcpyHostToDevice, C->stream);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_debug_acc30, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, C->stream, op, d_acc, d_other, d_neg, n, d_out, d_canon);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, n * 52 * 4, hipMemcpyDeviceToHost, C->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(out_canonical, d_canon, n * 48 * 4, hipMemcpyDeviceToHost, C->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(C->stream);
+  (void)raw_free(d);
+  GM_HIP(e);
+  return GM_OK;
+}
 
 #ifdef GM_ACC0_CYCLES
 // development build only (make EXTRA=-DGM_ACC0_CYCLES): shader cycles / 100 MHz ticks / waves summed over the k_acc0 launches

@@ -933,6 +933,209 @@ int candidates_run(Context* C, int group, const uint8_t* cand, size_t m, size_t 
   return GM_OK;
 }
 
+// ---- test aids: ONE device function of field.cuh / field30.cuh / g1.cuh / g2.cuh per lane (gm_debug_fq_op and its kin) -------------
+// Records in, records out, no conversion at the boundary: the caller chooses the exact limbs the function sees and reads the exact
+// limbs it leaves.  64 lanes per block; a lane beyond n runs the function on the device one (2 where two operands must differ), so
+// the asm statements behind fq_mul see a full wave in a partial block.
+constexpr int DBG_BLOCK = 64;
+enum { FQ_OP_MUL = 0, FQ_OP_SQR, FQ_OP_ADD, FQ_OP_SUB, FQ_OP_DBL, FQ_OP_NEG, FQ_OP_IMPORT, FQ_OP_EXPORT, FQ_OP_INV, FQ_OP_RAW_GE_Q, FQ_OP_PACK_UNPACK, FQ_OP_END };
+enum { FQ30_OP_MUL_ASM = 0, FQ30_OP_SQR_ASM, FQ30_OP_MUL_C, FQ30_OP_LOOSE_TO_CANONICAL, FQ30_OP_CANONICAL_TAIL, FQ30_OP_END };
+enum { FQ2_OP_MUL = 0, FQ2_OP_SQR, FQ2_OP_ADD, FQ2_OP_SUB, FQ2_OP_NEG, FQ2_OP_INV, FQ2_OP_END };
+enum { G1_OP_MADD = 0, G1_OP_ADD, G1_OP_DBL, G1_OP_DBL_AFFINE, G1_OP_STORE_LOAD30, G1_OP_END };
+enum { G2_OP_MADD = 0, G2_OP_ADD, G2_OP_DBL, G2_OP_DBL_AFFINE, G2_OP_TO_AFFINE, G2_OP_END };
+
+GM_DEV Fq dbg_load_fq(const uint32_t* p) {
+  Fq r;
+#pragma unroll
+  for (int i = 0; i < 12; i++) r.l[i] = p[i];
+  return r;
+}
+GM_DEV void dbg_store_fq(uint32_t* p, const Fq& a) {
+#pragma unroll
+  for (int i = 0; i < 12; i++) p[i] = a.l[i];
+}
+GM_DEV Fq2 dbg_load_fq2(const uint32_t* p) {
+  Fq2 r;
+  r.c0 = dbg_load_fq(p);
+  r.c1 = dbg_load_fq(p + 12);
+  return r;
+}
+GM_DEV void dbg_store_fq2(uint32_t* p, const Fq2& a) {
+  dbg_store_fq(p, a.c0);
+  dbg_store_fq(p + 12, a.c1);
+}
+
+__global__ __launch_bounds__(DBG_BLOCK) void k_debug_fq(int op, const uint32_t* __restrict__ a_in, const uint32_t* __restrict__ b_in, size_t n, uint32_t* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * DBG_BLOCK + threadIdx.x;
+  const bool live = i < n;
+  const bool binary = op == FQ_OP_MUL || op == FQ_OP_ADD || op == FQ_OP_SUB;
+  const Fq a = live ? dbg_load_fq(a_in + i * 12) : fqe_one();
+  const Fq b = live && binary ? dbg_load_fq(b_in + i * 12) : fq_dbl(fqe_one());
+  Fq r = Fq::zero();
+  if (op == FQ_OP_MUL) r = fq_mul(a, b);
+  else if (op == FQ_OP_SQR) r = fq_sqr(a);
+  else if (op == FQ_OP_ADD) r = fq_add(a, b);
+  else if (op == FQ_OP_SUB) r = fq_sub(a, b);
+  else if (op == FQ_OP_DBL) r = fq_dbl(a);
+  else if (op == FQ_OP_NEG) r = fq_neg_canonical(a);
+  else if (op == FQ_OP_IMPORT) r = fqe_import(a);
+  else if (op == FQ_OP_EXPORT) r = fqe_export(a);
+  else if (op == FQ_OP_INV) r = g2_fq_inv(a);
+  else if (op == FQ_OP_RAW_GE_Q) r.l[0] = pt_raw_ge_q(a) ? 1u : 0u;
+  else r = fq30_pack(fq30_unpack(a));
+  if (live) dbg_store_fq(out + i * 12, r);
+}
+
+__global__ __launch_bounds__(DBG_BLOCK) void k_debug_fq30(int op, const uint32_t* __restrict__ a_in, const uint32_t* __restrict__ b_in, size_t n, uint32_t* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * DBG_BLOCK + threadIdx.x;
+  const bool live = i < n;
+  const bool binary = op == FQ30_OP_MUL_ASM || op == FQ30_OP_MUL_C;
+  Fq30 a = fq30_const(Fq30Consts::ONE), b = fq30_const(Fq30Consts::ONE);
+  if (live) {
+#pragma unroll
+    for (int k = 0; k < 13; k++) a.l[k] = a_in[i * 13 + k];
+    if (binary) {
+#pragma unroll
+      for (int k = 0; k < 13; k++) b.l[k] = b_in[i * 13 + k];
+    }
+  }
+  Fq30 r = Fq30::zero();
+  if (op == FQ30_OP_MUL_ASM) {
+    r = fq30_mul_asm(a.l[0], a.l[1], a.l[2], a.l[3], a.l[4], a.l[5], a.l[6], a.l[7], a.l[8], a.l[9], a.l[10], a.l[11], a.l[12],
+                     b.l[0], b.l[1], b.l[2], b.l[3], b.l[4], b.l[5], b.l[6], b.l[7], b.l[8], b.l[9], b.l[10], b.l[11], b.l[12]);
+  } else if (op == FQ30_OP_SQR_ASM) {
+    r = fq30_sqr_asm(a.l[0], a.l[1], a.l[2], a.l[3], a.l[4], a.l[5], a.l[6], a.l[7], a.l[8], a.l[9], a.l[10], a.l[11], a.l[12]);
+  } else if (op == FQ30_OP_MUL_C) {
+    r = fq30_mul(a, b);
+  } else if (op == FQ30_OP_LOOSE_TO_CANONICAL) {
+    const Fq c = fq30_loose_to_canonical(a);
+#pragma unroll
+    for (int k = 0; k < 12; k++) r.l[k] = c.l[k];  // 12 words and a zero
+  } else {
+    r = fq30_canonical_tail(a);
+  }
+  if (live) {
+#pragma unroll
+    for (int k = 0; k < 13; k++) out[i * 13 + k] = r.l[k];
+  }
+}
+
+__global__ __launch_bounds__(DBG_BLOCK) void k_debug_fq2(int op, const uint32_t* __restrict__ a_in, const uint32_t* __restrict__ b_in, size_t n, uint32_t* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * DBG_BLOCK + threadIdx.x;
+  const bool live = i < n;
+  const bool binary = op == FQ2_OP_MUL || op == FQ2_OP_ADD || op == FQ2_OP_SUB;
+  const Fq2 a = live ? dbg_load_fq2(a_in + i * 24) : fq2_one();
+  const Fq2 b = live && binary ? dbg_load_fq2(b_in + i * 24) : fq2_dbl(fq2_one());
+  Fq2 r;
+  if (op == FQ2_OP_MUL) r = fq2_mul(a, b);
+  else if (op == FQ2_OP_SQR) r = fq2_sqr(a);
+  else if (op == FQ2_OP_ADD) r = fq2_add(a, b);
+  else if (op == FQ2_OP_SUB) r = fq2_sub(a, b);
+  else if (op == FQ2_OP_NEG) r = fq2_neg_canonical(a);
+  else r = fq2_inv(a);
+  if (live) dbg_store_fq2(out + i * 24, r);
+}
+
+// p: XYZZ records (4 x 12 words; G1_OP_DBL_AFFINE reads the affine point from the first 24 and ignores the rest); q: 24 words (affine)
+// for G1_OP_MADD, 48 for G1_OP_ADD, not read otherwise.  out: x | y | zz | zzz as the function returns them.
+__global__ __launch_bounds__(DBG_BLOCK) void k_debug_g1(int op, const uint32_t* __restrict__ p_in, const uint32_t* __restrict__ q_in, size_t n, uint32_t* __restrict__ out) {
+  __shared__ __attribute__((aligned(16))) uint8_t rec[DBG_BLOCK * XYZZ30_BYTES];
+  const size_t i = (size_t)blockIdx.x * DBG_BLOCK + threadIdx.x;
+  const bool live = i < n;
+  const FqE one = fqe_one();
+  G1Xyzz P, Q;
+  P.x = P.y = P.zz = P.zzz = one;
+  Q = P;
+  Q.x = fq_dbl(one);
+  if (live) {
+    const uint32_t* s = p_in + i * 48;
+    P.x = dbg_load_fq(s); P.y = dbg_load_fq(s + 12); P.zz = dbg_load_fq(s + 24); P.zzz = dbg_load_fq(s + 36);
+    if (op == G1_OP_MADD) {
+      Q.x = dbg_load_fq(q_in + i * 24); Q.y = dbg_load_fq(q_in + i * 24 + 12);
+    } else if (op == G1_OP_ADD) {
+      const uint32_t* t = q_in + i * 48;
+      Q.x = dbg_load_fq(t); Q.y = dbg_load_fq(t + 12); Q.zz = dbg_load_fq(t + 24); Q.zzz = dbg_load_fq(t + 36);
+    }
+  }
+  G1Affine qa, pa;
+  qa.x = Q.x; qa.y = Q.y;
+  pa.x = P.x; pa.y = P.y;
+  G1Xyzz r = P;
+  if (op == G1_OP_MADD) {
+    xyzz_madd(r, qa);
+  } else if (op == G1_OP_ADD) {
+    xyzz_add(r, Q);
+  } else if (op == G1_OP_DBL) {
+    r = xyzz_dbl(P);
+  } else if (op == G1_OP_DBL_AFFINE) {
+    r = xyzz_dbl_affine(pa);
+  } else {
+    g1_store_xyzz30(rec + threadIdx.x * XYZZ30_BYTES, P);
+    r = g1_load_xyzz30(rec + threadIdx.x * XYZZ30_BYTES);
+  }
+  if (live) {
+    uint32_t* o = out + i * 48;
+    dbg_store_fq(o, r.x); dbg_store_fq(o + 12, r.y); dbg_store_fq(o + 24, r.zz); dbg_store_fq(o + 36, r.zzz);
+  }
+}
+
+// The same over Fq2: p 4 x 24 words (G2_OP_DBL_AFFINE reads the first 48); q 48 words for G2_OP_MADD, 96 for G2_OP_ADD.  out: 96 words;
+// G2_OP_TO_AFFINE writes x | y into the first 48 and zeroes behind them.
+__global__ __launch_bounds__(DBG_BLOCK) void k_debug_g2(int op, const uint32_t* __restrict__ p_in, const uint32_t* __restrict__ q_in, size_t n, uint32_t* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * DBG_BLOCK + threadIdx.x;
+  const bool live = i < n;
+  G2Xyzz P, Q;
+  P.x = P.y = P.zz = P.zzz = fq2_one();
+  Q = P;
+  Q.x = fq2_dbl(fq2_one());
+  if (live) {
+    const uint32_t* s = p_in + i * 96;
+    P.x = dbg_load_fq2(s); P.y = dbg_load_fq2(s + 24); P.zz = dbg_load_fq2(s + 48); P.zzz = dbg_load_fq2(s + 72);
+    if (op == G2_OP_MADD) {
+      Q.x = dbg_load_fq2(q_in + i * 48); Q.y = dbg_load_fq2(q_in + i * 48 + 24);
+    } else if (op == G2_OP_ADD) {
+      const uint32_t* t = q_in + i * 96;
+      Q.x = dbg_load_fq2(t); Q.y = dbg_load_fq2(t + 24); Q.zz = dbg_load_fq2(t + 48); Q.zzz = dbg_load_fq2(t + 72);
+    }
+  }
+  G2Affine qa, pa;
+  qa.x = Q.x; qa.y = Q.y;
+  pa.x = P.x; pa.y = P.y;
+  G2Xyzz r = P;
+  if (op == G2_OP_MADD) {
+    g2_madd(r, qa);
+  } else if (op == G2_OP_ADD) {
+    g2_add(r, Q);
+  } else if (op == G2_OP_DBL) {
+    r = g2_dbl(P);
+  } else if (op == G2_OP_DBL_AFFINE) {
+    r = g2_dbl_affine(pa);
+  } else {
+    const G2Affine a = g2_to_affine(P);
+    r.x = a.x; r.y = a.y; r.zz = fq2_zero(); r.zzz = fq2_zero();
+  }
+  if (live) {
+    uint32_t* o = out + i * 96;
+    dbg_store_fq2(o, r.x); dbg_store_fq2(o + 24, r.y); dbg_store_fq2(o + 48, r.zz); dbg_store_fq2(o + 72, r.zzz);
+  }
+}
+
+// host side of the five entries above: a (aw words per element), b (bw words, 0: not read) -> out (ow words)
+template <class K>
+int debug_op_run(Context* C, K kernel, int op, const uint32_t* a, size_t aw, const uint32_t* b, size_t bw, size_t n, uint32_t* out, size_t ow) {
+  GM_MSM_LOCK(C);
+  DevTmp d;
+  GM_HIP(dev_malloc(&d.p, n * (aw + bw + ow) * 4));
+  uint32_t *d_a = static_cast<uint32_t*>(d.p), *d_b = d_a + n * aw, *d_out = d_b + n * bw;
+  GM_HIP(hipMemcpyAsync(d_a, a, n * aw * 4, hipMemcpyHostToDevice, C->stream));
+  if (bw) GM_HIP(hipMemcpyAsync(d_b, b, n * bw * 4, hipMemcpyHostToDevice, C->stream));
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((n + DBG_BLOCK - 1) / DBG_BLOCK)), dim3(DBG_BLOCK), 0, C->stream, op, (const uint32_t*)d_a, (const uint32_t*)d_b, n, d_out);
+  GM_HIP(hipGetLastError());
+  GM_HIP(hipMemcpyAsync(out, d_out, n * ow * 4, hipMemcpyDeviceToHost, C->stream));
+  GM_HIP(hipStreamSynchronize(C->stream));
+  return GM_OK;
+}
+
 }  // namespace
 }  // namespace gm
 
@@ -1225,6 +1428,37 @@ int gm_debug_fq2_sqrt(const uint64_t* a_mont, size_t n, uint64_t* root_mont, uin
   GM_HIP(hipStreamSynchronize(C->stream));
   return GM_OK;
 }
+
+// the element-wise test aids: `bw` is the second operand's width for this op, 0 when the op does not read it
+#define GM_DEBUG_OP(who, kernel, end, aw, bw, ow)                                                                 \
+  GM_CTX();                                                                                                       \
+  GM_CHECK((a && out && (b || (bw) == 0)) || n == 0, GM_EINVAL, who ": null pointer");                            \
+  if (n == 0) return GM_OK;                                                                                       \
+  GM_CHECK(op >= 0 && op < (end), GM_EINVAL, who ": unknown op %d", op);                                          \
+  GM_CHECK(n <= (size_t)1 << 20, GM_EINVAL, who ": %zu elements in one call (at most 2^20)", n);                  \
+  return debug_op_run(C, kernel, op, a, aw, b, bw, n, out, ow)
+
+int gm_debug_fq_op(int op, const uint32_t* a, const uint32_t* b, size_t n, uint32_t* out) {
+  const size_t bw = (op == FQ_OP_MUL || op == FQ_OP_ADD || op == FQ_OP_SUB) ? 12 : 0;
+  GM_DEBUG_OP("debug_fq_op", k_debug_fq, FQ_OP_END, 12, bw, 12);
+}
+int gm_debug_fq30_op(int op, const uint32_t* a, const uint32_t* b, size_t n, uint32_t* out) {
+  const size_t bw = (op == FQ30_OP_MUL_ASM || op == FQ30_OP_MUL_C) ? 13 : 0;
+  GM_DEBUG_OP("debug_fq30_op", k_debug_fq30, FQ30_OP_END, 13, bw, 13);
+}
+int gm_debug_fq2_op(int op, const uint32_t* a, const uint32_t* b, size_t n, uint32_t* out) {
+  const size_t bw = (op == FQ2_OP_MUL || op == FQ2_OP_ADD || op == FQ2_OP_SUB) ? 24 : 0;
+  GM_DEBUG_OP("debug_fq2_op", k_debug_fq2, FQ2_OP_END, 24, bw, 24);
+}
+int gm_debug_g1_op(int op, const uint32_t* a, const uint32_t* b, size_t n, uint32_t* out) {
+  const size_t bw = op == G1_OP_MADD ? 24 : op == G1_OP_ADD ? 48 : 0;
+  GM_DEBUG_OP("debug_g1_op", k_debug_g1, G1_OP_END, 48, bw, 48);
+}
+int gm_debug_g2_op(int op, const uint32_t* a, const uint32_t* b, size_t n, uint32_t* out) {
+  const size_t bw = op == G2_OP_MADD ? 48 : op == G2_OP_ADD ? 96 : 0;
+  GM_DEBUG_OP("debug_g2_op", k_debug_g2, G2_OP_END, 96, bw, 96);
+}
+#undef GM_DEBUG_OP
 
 int gm_g1_powers_check(uint64_t handle, size_t offset, size_t n, const uint64_t g2_affine[24], const uint64_t tau_g2_affine[24], const uint64_t rho_mont[4], int* ok) {
   if (ok) *ok = 0;

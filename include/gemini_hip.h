@@ -1214,6 +1214,33 @@ int gm_ipa_check(uint64_t proof, size_t* first_bad, int* ok);
 /* A test aid: the Fq2 square root of the G2 decoder, one lane per element, on inputs no curve point produces.  a_mont: n x 12 limbs
  * (c0 | c1, ark-ff Montgomery); root_mont the same; is_square[i] = 1 when a_i is a square, and then root_i^2 = a_i. */
 int gm_debug_fq2_sqrt(const uint64_t* a_mont, size_t n, uint64_t* root_mont, uint8_t* is_square);
+/* A test aid: the device's field and group arithmetic element by element.  Each call applies ONE device function per lane, 64 lanes
+ * per block, to records in DEVICE form -- 12 x u32 words holding a * 2^390 mod q, or 13 loose 30-bit limbs -- read and written as
+ * they are: no conversion at the boundary, so the caller controls the exact limbs the function sees.  Operands must be valid inputs
+ * of the function (canonical where it requires that; loose values normalised and below 2^386).  b is read only by the ops that take
+ * a second operand and may be null otherwise.  n = 0 gives GM_OK; an unknown op or a null pointer with n > 0 GM_EINVAL.
+ *   gm_debug_fq_op     n x 12 words.  0 fq_mul  1 fq_sqr  2 fq_add  3 fq_sub  4 fq_dbl  5 fq_neg_canonical  6 fqe_import  7 fqe_export
+ *                      8 g2_fq_inv (0 gives 0)  9 pt_raw_ge_q (0 / 1 in word 0, the others 0; the ONLY op that takes words >= q)
+ *                      10 fq30_pack(fq30_unpack(a))
+ *   gm_debug_fq30_op   n x 13 limbs.  0 fq30_mul_asm  1 fq30_sqr_asm  2 fq30_mul (plain C)  3 fq30_loose_to_canonical (12 words and a
+ *                      zero)  4 fq30_canonical_tail alone (a < 2 q)
+ *   gm_debug_fq2_op    n x 24 words (c0 | c1).  0 fq2_mul  1 fq2_sqr  2 fq2_add  3 fq2_sub  4 fq2_neg_canonical  5 fq2_inv (a != 0)
+ *   gm_debug_g1_op     a: n x 48 words, X | Y | ZZ | ZZZ canonical.  0 xyzz_madd (b: n x 24, affine)  1 xyzz_add (b: n x 48)  2 xyzz_dbl
+ *                      3 xyzz_dbl_affine (of the affine point in a's first 24 words)  4 g1_store_xyzz30 then g1_load_xyzz30.
+ *                      out: n x 48, the four coordinates as the function leaves them.
+ *   gm_debug_g2_op     the same over Fq2: a n x 96.  0 g2_madd (b: n x 48)  1 g2_add (b: n x 96)  2 g2_dbl  3 g2_dbl_affine
+ *                      4 g2_to_affine (x | y in the first 48 words of out, zeros behind)
+ *   gm_debug_acc30_op  the two statements of the bucket accumulator, under the hot kernel's launch attributes.  acc: n x 52 loose
+ *                      limbs (the 208-byte record; X < 7 q, Y, ZZ, ZZZ < 2 q; ZZ == 0 exactly marks the identity).  0 g1_madd30_asm:
+ *                      other n x 24 canonical words (an affine point, not the identity), neg n x u32 (!= 0 adds the negative)
+ *                      1 acc30_add: other n x 52 loose limbs, neg not read.  out: the 52 limbs the statement leaves;
+ *                      out_canonical: acc30_to_canonical of them, n x 48 words. */
+int gm_debug_fq_op(int op, const uint32_t* a, const uint32_t* b, size_t n, uint32_t* out);
+int gm_debug_fq30_op(int op, const uint32_t* a, const uint32_t* b, size_t n, uint32_t* out);
+int gm_debug_fq2_op(int op, const uint32_t* a, const uint32_t* b, size_t n, uint32_t* out);
+int gm_debug_g1_op(int op, const uint32_t* a, const uint32_t* b, size_t n, uint32_t* out);
+int gm_debug_g2_op(int op, const uint32_t* a, const uint32_t* b, size_t n, uint32_t* out);
+int gm_debug_acc30_op(int op, const uint32_t* acc, const uint32_t* other, const uint32_t* neg, size_t n, uint32_t* out, uint32_t* out_canonical);
 /* Do bases[offset .. offset + n) hold consecutive powers of ONE tau -- bases[offset + i + 1] = tau bases[offset + i] for i < n - 1 --,
  * the tau of (g2, tau g2)?  With A = sum rho^i P_i and B = sum rho^i P_{i+1} over i < n - 1 the test is e(A, tau g2) e(-B, g2) == 1:
  * gm_fr_powers, two gm_g1_msm_v and ONE two-pair multi-pairing.  g2_affine / tau_g2_affine: 192-byte records as

@@ -1,6 +1,9 @@
 // Unit checks of the Fq element layer of gemini_amd/csrc/g1.cuh against the host field arithmetic
 // (gemini_amd/csrc/host_field.hpp):
 //   hipcc -O2 -std=c++17 --offload-arch=gfx950 -I gemini_amd/csrc tools/fq30_check.hip -o /tmp/fq30_check && /tmp/fq30_check
+// NOT the test of this layer: tests/test_gpu_field_ops.py and tests/test_gpu_group_ops.py check every function here one by one
+// through the gm_debug_*_op entries of the library, against Python integers, at the edge operands (this program compares with the
+// host arithmetic on random inputs and knows only 0, 1 and q - 1).  Kept as a stand-alone probe for a compiler or flag change.
 // Field level: mul / sqr / add / dbl / sub chains, is_zero on differences that vanish and on ones that do not,
 // import / export.  Group level: xyzz_madd / xyzz_add / xyzz_dbl chains incl. P + P, P - P, identity
 // operands, stored through g1_store_xyzz and read back with the host's xyzz_to_jac_dev.

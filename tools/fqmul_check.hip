@@ -1,5 +1,8 @@
 // Device check + throughput of the radix-2^30 asm Fq multiplier / squarer (gen_field_mul30.py) against the
 // 32-bit-limb product-scanning multiplier (gen_field_mul.py).  Dev tool, not product.
+// Kept for the RATE measurement (profiles/r*_fqmul_check.txt).  The correctness check here is a differential against another device
+// multiplier on random inputs; the tests of the multiplier are tests/test_field_mul30_gen_cpu.py (the instruction list interpreted
+// against big integers, the .inc held to the generator) and tests/test_gpu_field_ops.py (the assembled code against Python integers).
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/fqmul_check.hip -o tools/_build/fqmul_check
 #include <hip/hip_runtime.h>
 #include <stdint.h>
