@@ -33,7 +33,7 @@ namespace gm {
 
 int bases_build_phi(Context* C, Bases* b);  // msm.hip
 
-constexpr int PT_BLOCK = 256;      // G1 kernels: amdgpu_waves_per_eu(2, 2) -- 96 / 112 bytes of scratch buy the second wave, 1.27 x against one wave (profiles/point_check.md)
+constexpr int PT_BLOCK = 256;      // G1 kernels: amdgpu_waves_per_eu(2, 2) -- 96 / 160 bytes of scratch buy the second wave, 1.27 x against one wave (profiles/point_check.md)
 constexpr int PT_G2_BLOCK = 64;    // G2: one wave per SIMD, the whole register file (as k_g2_acc)
 constexpr uint32_t PT_NO_BAD = 0xffffffffu;
 constexpr uint64_t BLS_X_ABS = 0xd201000000010000ull;  // the curve parameter is x = -BLS_X_ABS
@@ -153,90 +153,6 @@ GM_DEV uint8_t pt_g2_status(const G2Affine& Q, bool check_curve) {
   return same_x && neg_y ? GM_PT_OK : GM_PT_NOT_IN_SUBGROUP;
 }
 
-// ---- reporting: the status byte of the lane, and the block's first bad lane (every lane of the block arrives here) -------------
-GM_DEV void pt_report(size_t i, size_t n, uint8_t st, uint8_t* __restrict__ status, uint32_t* __restrict__ summary) {
-  __shared__ uint32_t first[PT_BLOCK / 64];
-  const bool bad = i < n && st != GM_PT_OK;
-  if (i < n) status[i] = st;
-  const unsigned long long m = __ballot(bad);
-  if ((threadIdx.x & 63u) == 0) first[threadIdx.x >> 6] = m ? (threadIdx.x + (uint32_t)__ffsll((long long)m) - 1u) : PT_NO_BAD;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t f = PT_NO_BAD;
-    for (unsigned w = 0; w < blockDim.x / 64; w++) f = first[w] < f ? first[w] : f;
-    summary[blockIdx.x] = f;
-  }
-}
-
-// host_form != 0: records as gm_g1_bases_register takes them (ark-ff Montgomery limbs, stride >= 96, the infinity byte at 96 when the
-// stride has room); 0: packed device records (stride 96), canonical by construction
-__global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_g1_check(const uint8_t* __restrict__ src, size_t stride, int host_form, size_t n, uint8_t* __restrict__ status,
-                                                       uint32_t* __restrict__ summary) {
-  const size_t i = (size_t)blockIdx.x * PT_BLOCK + threadIdx.x;
-  uint8_t st = GM_PT_OK;
-  if (i < n) {
-    const uint32_t* s = reinterpret_cast<const uint32_t*>(src + i * stride);
-    G1Affine P;
-#pragma unroll
-    for (int k = 0; k < 12; k++) {
-      P.x.l[k] = s[k];
-      P.y.l[k] = s[12 + k];
-    }
-    const bool inf = (host_form && stride >= 97 && src[i * stride + 96] != 0) || P.is_identity();  // what k_pack_bases reads as the identity
-    if (!inf) {
-      if (host_form && (pt_raw_ge_q(P.x) || pt_raw_ge_q(P.y))) {
-        st = GM_PT_NONCANONICAL;
-      } else {
-        if (host_form) {
-          P.x = fqe_import(P.x);
-          P.y = fqe_import(P.y);
-        }
-        st = pt_g1_status(P, true);
-      }
-    }
-  }
-  pt_report(i, n, st, status, summary);
-}
-
-__global__ __launch_bounds__(PT_G2_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_g2_check(const uint8_t* __restrict__ src, size_t stride, int host_form, size_t n,
-                                                                                                      uint8_t* __restrict__ status, uint32_t* __restrict__ summary) {
-  const size_t i = (size_t)blockIdx.x * PT_G2_BLOCK + threadIdx.x;
-  uint8_t st = GM_PT_OK;
-  if (i < n) {
-    const uint32_t* s = reinterpret_cast<const uint32_t*>(src + i * stride);
-    FqE c[4];
-    uint32_t any = 0;
-    bool canonical = true;
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-#pragma unroll
-      for (int k = 0; k < 12; k++) {
-        c[e].l[k] = s[12 * e + k];
-        any |= c[e].l[k];
-      }
-      canonical = canonical && !pt_raw_ge_q(c[e]);
-    }
-    const bool inf = (host_form && stride >= 193 && src[i * stride + 192] != 0) || any == 0;
-    if (!inf) {
-      if (host_form && !canonical) {
-        st = GM_PT_NONCANONICAL;
-      } else {
-        if (host_form) {
-#pragma unroll
-          for (int e = 0; e < 4; e++) c[e] = fqe_import(c[e]);
-        }
-        G2Affine Q;
-        Q.x.c0 = c[0];
-        Q.x.c1 = c[1];
-        Q.y.c0 = c[2];
-        Q.y.c1 = c[3];
-        st = pt_g2_status(Q, true);
-      }
-    }
-  }
-  pt_report(i, n, st, status, summary);
-}
-
 // a^((q + 1) / 4): the square root of a square (q = 3 mod 4).  Bit i of the exponent is bit i + 2 of q + 1, which differs from q in
 // bit 2 alone (q = ...1010 1011).  Plain square-and-multiply: 378 squares + 228 products; a 4-bit window would save ~120 of them
 // for a table of 16 x 12 VGPRs.
@@ -251,82 +167,6 @@ GM_DEV FqE pt_sqrt_candidate(const FqE& a) {
 }
 
 GM_DEV uint32_t pt_bswap(uint32_t v) { return __builtin_bswap32(v); }
-
-// 48- / 96-byte encodings -> packed device records (the layout k_pack_bases produces; the identity and every rejected point are the
-// all-zero record).  Acceptance and the order of the checks are those of wire.g1_deserialize(.., strict = True, validate).
-__global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_g1_decode(const uint8_t* __restrict__ bytes, size_t n, int compressed, int zcash, int validate, uint8_t* __restrict__ dst,
-                                                        uint8_t* __restrict__ status, uint32_t* __restrict__ summary) {
-  const size_t i = (size_t)blockIdx.x * PT_BLOCK + threadIdx.x;
-  uint8_t st = GM_PT_OK;
-  if (i < n) {
-    const size_t sz = compressed ? 48 : 96;
-    Fq x = fp_load<FqParams>(bytes + i * sz), y = Fq::zero();
-    if (!compressed) y = fp_load<FqParams>(bytes + i * sz + 48);
-    if (zcash) {  // big-endian: limb k is word 11 - k, byte-swapped
-      Fq t = x, u = y;
-#pragma unroll
-      for (int k = 0; k < 12; k++) {
-        x.l[k] = pt_bswap(t.l[11 - k]);
-        y.l[k] = pt_bswap(u.l[11 - k]);
-      }
-    }
-    bool inf, larger;
-    if (zcash) {  // flags in the three top bits of the first byte = the top bits of x
-      const uint32_t f = x.l[11] >> 29;
-      x.l[11] &= 0x1fffffffu;
-      inf = (f >> 1) & 1u;
-      larger = f & 1u;
-      if ((int)(f >> 2) != (compressed ? 1 : 0) || (larger && (!compressed || inf))) st = GM_PT_BAD_ENCODING;
-    } else {  // flags in the two top bits of the last byte = the top bits of the last coordinate
-      const uint32_t f = (compressed ? x.l[11] : y.l[11]) >> 30;
-      if (compressed) x.l[11] &= 0x3fffffffu;
-      else y.l[11] &= 0x3fffffffu;
-      inf = f == 1;
-      larger = f == 2;
-      if (f == 3) st = GM_PT_BAD_ENCODING;
-    }
-    G1Affine P;
-    P.x = fqe_zero();
-    P.y = fqe_zero();
-    if (st == GM_PT_OK) {
-      if (inf) {
-        if (!x.is_zero() || !y.is_zero()) st = GM_PT_BAD_ENCODING;  // infinity with non-zero coordinates
-      } else if (compressed) {
-        if (pt_raw_ge_q(x)) {
-          st = GM_PT_NONCANONICAL;
-        } else {
-          P.x = pt_from_int(x);
-          const FqE rhs = fq_add(fq_mul(fq_sqr(P.x), P.x), pt_four());
-          P.y = pt_sqrt_candidate(rhs);
-          if (!(fq_sqr(P.y) == rhs)) {
-            st = GM_PT_NOT_ON_CURVE;  // x^3 + 4 is no square
-          } else {
-            if (pt_y_is_larger(pt_to_int(P.y)) != larger) P.y = fq_neg_canonical(P.y);
-            if (validate) st = pt_g1_status(P, false);  // on the curve by construction
-          }
-        }
-      } else {
-        const bool y_ge = pt_raw_ge_q(y);
-        // wire.py compares the sign flag BEFORE the canonical check; for y >= q its `y > (q - y) mod q` is always true
-        if (!zcash && (y_ge || pt_y_is_larger(y)) != larger) {
-          st = GM_PT_BAD_ENCODING;
-        } else if (y_ge || pt_raw_ge_q(x)) {
-          st = GM_PT_NONCANONICAL;
-        } else {
-          P.x = pt_from_int(x);
-          P.y = pt_from_int(y);
-          if (validate) st = pt_g1_status(P, true);
-        }
-      }
-    }
-    if (st != GM_PT_OK) {
-      P.x = fqe_zero();
-      P.y = fqe_zero();
-    }
-    g1_store_affine(dst + i * 96, P);
-  }
-  pt_report(i, n, st, status, summary);
-}
 
 // ---- G2 from bytes: a square root in Fq2 ---------------------------------------------------------------------------------------
 // a^((q - 3) / 4): bit i of the exponent is bit i + 2 of q - 3, which is q with its two low bits cleared -- pt_sqrt_candidate's loop
@@ -373,9 +213,6 @@ GM_DEV Fq2 pt_fq2_sqrt(const Fq2& a, bool* is_square) {
   return r;
 }
 
-// ark-ff's QuadExtField order on fully reduced integers: y > -y compares c1 first, c0 when c1 = 0 (c = -c only for c = 0)
-GM_DEV bool pt_y2_is_larger(const Fq& y0_int, const Fq& y1_int) { return y1_int.is_zero() ? pt_y_is_larger(y0_int) : pt_y_is_larger(y1_int); }
-
 // one 48-byte coordinate of either framing -> the integer it spells (flag bits still in place)
 GM_DEV Fq pt_load_coord(const uint8_t* p, int zcash) {
   Fq v = fp_load<FqParams>(p);
@@ -395,126 +232,6 @@ GM_DEV void pt_store_coord(uint8_t* p, const Fq& v, int zcash) {
   fp_store<FqParams>(p, o);
 }
 
-// 96- / 192-byte encodings -> packed device records (192 bytes; the identity and every rejected point are the all-zero record).
-// Acceptance and the order of the checks are those of gemini_amd/g2.py: deserialize(.., strict = True, validate), the image of
-// k_g1_decode over Fq2.  On the wire enc 0 holds c0 | c1 and enc 1 c1 | c0; c[] below is x.c0, x.c1, y.c0, y.c1.
-__global__ __launch_bounds__(PT_G2_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_g2_decode(const uint8_t* __restrict__ bytes, size_t n, int compressed, int zcash, int validate,
-                                                                                                       uint8_t* __restrict__ dst, uint8_t* __restrict__ status, uint32_t* __restrict__ summary) {
-  const size_t i = (size_t)blockIdx.x * PT_G2_BLOCK + threadIdx.x;
-  uint8_t st = GM_PT_OK;
-  if (i < n) {
-    const int k = compressed ? 2 : 4;
-    const uint8_t* src = bytes + i * (size_t)(48 * k);
-    Fq c[4];
-#pragma unroll
-    for (int e = 0; e < 4; e++) c[e] = e < k ? pt_load_coord(src + 48 * (zcash ? e ^ 1 : e), zcash) : Fq::zero();
-    bool inf, larger;
-    if (zcash) {  // flags in the three top bits of the first byte = the top bits of x.c1
-      const uint32_t f = c[1].l[11] >> 29;
-      c[1].l[11] &= 0x1fffffffu;
-      inf = (f >> 1) & 1u;
-      larger = f & 1u;
-      if ((int)(f >> 2) != (compressed ? 1 : 0) || (larger && (!compressed || inf))) st = GM_PT_BAD_ENCODING;
-    } else {  // flags in the two top bits of the last byte = the top bits of the last coordinate's c1
-      const uint32_t f = (compressed ? c[1].l[11] : c[3].l[11]) >> 30;
-      if (compressed) c[1].l[11] &= 0x3fffffffu;
-      else c[3].l[11] &= 0x3fffffffu;
-      inf = f == 1;
-      larger = f == 2;
-      if (f == 3) st = GM_PT_BAD_ENCODING;
-    }
-    G2Affine P;
-    P.x = fq2_zero();
-    P.y = fq2_zero();
-    if (st == GM_PT_OK) {
-      const bool x_ge = pt_raw_ge_q(c[0]) || pt_raw_ge_q(c[1]);
-      if (inf) {
-        if (!c[0].is_zero() || !c[1].is_zero() || !c[2].is_zero() || !c[3].is_zero()) st = GM_PT_BAD_ENCODING;  // infinity with non-zero coordinates
-      } else if (compressed) {
-        if (x_ge) {
-          st = GM_PT_NONCANONICAL;
-        } else {
-          P.x.c0 = pt_from_int(c[0]);
-          P.x.c1 = pt_from_int(c[1]);
-          Fq2 rhs = fq2_mul(fq2_sqr(P.x), P.x);
-          rhs.c0 = fq_add(rhs.c0, pt_four());
-          rhs.c1 = fq_add(rhs.c1, pt_four());
-          bool square;
-          P.y = pt_fq2_sqrt(rhs, &square);
-          if (!square) {
-            st = GM_PT_NOT_ON_CURVE;  // x^3 + 4 (1 + u) is no square
-          } else {
-            if (pt_y2_is_larger(pt_to_int(P.y.c0), pt_to_int(P.y.c1)) != larger) P.y = fq2_neg_canonical(P.y);
-            if (validate) st = pt_g2_status(P, false);  // on the twist by construction
-          }
-        }
-      } else {
-        const bool y0_ge = pt_raw_ge_q(c[2]), y1_ge = pt_raw_ge_q(c[3]);
-        // g2.py compares the sign flag BEFORE the canonical check, against (-y) mod q: a component >= q is larger than its negative
-        const bool y_larger = y1_ge || (c[3].is_zero() ? (y0_ge || pt_y_is_larger(c[2])) : pt_y_is_larger(c[3]));
-        if (!zcash && y_larger != larger) {
-          st = GM_PT_BAD_ENCODING;
-        } else if (x_ge || y0_ge || y1_ge) {
-          st = GM_PT_NONCANONICAL;
-        } else {
-          P.x.c0 = pt_from_int(c[0]);
-          P.x.c1 = pt_from_int(c[1]);
-          P.y.c0 = pt_from_int(c[2]);
-          P.y.c1 = pt_from_int(c[3]);
-          if (validate) st = pt_g2_status(P, true);
-        }
-      }
-    }
-    if (st != GM_PT_OK) {
-      P.x = fq2_zero();
-      P.y = fq2_zero();
-    }
-    g2_store_affine(dst + i * G2_AFF_BYTES, P);
-  }
-  pt_report(i, n, st, status, summary);
-}
-
-// ---- resident records -> bytes: one Montgomery exit per coordinate and the y > -y compare, no inversion (the bases are affine) ------
-constexpr int PT_ENC_BLOCK = 256;
-__global__ __launch_bounds__(PT_ENC_BLOCK) void k_g1_encode(const uint8_t* __restrict__ src, size_t n, int compressed, int zcash, uint8_t* __restrict__ out) {
-  const size_t i = (size_t)blockIdx.x * PT_ENC_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  const G1Affine P = g1_load_affine(src + i * 96);
-  const bool inf = P.is_identity();
-  Fq x = pt_to_int(P.x), y = pt_to_int(P.y);  // 0 for the identity
-  const bool larger = !inf && pt_y_is_larger(y);
-  if (zcash) {
-    x.l[11] |= (compressed ? 0x80000000u : 0u) | (inf ? 0x40000000u : 0u) | (compressed && larger ? 0x20000000u : 0u);
-  } else {
-    const uint32_t f = (inf ? 0x40000000u : 0u) | (larger ? 0x80000000u : 0u);
-    if (compressed) x.l[11] |= f;
-    else y.l[11] |= f;
-  }
-  uint8_t* o = out + i * (size_t)(compressed ? 48 : 96);
-  pt_store_coord(o, x, zcash);
-  if (!compressed) pt_store_coord(o + 48, y, zcash);
-}
-__global__ __launch_bounds__(PT_ENC_BLOCK) void k_g2_encode(const uint8_t* __restrict__ src, size_t n, int compressed, int zcash, uint8_t* __restrict__ out) {
-  const size_t i = (size_t)blockIdx.x * PT_ENC_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  const G2Affine P = g2_load_affine(src + i * G2_AFF_BYTES);
-  const bool inf = P.is_identity();
-  Fq c[4] = {pt_to_int(P.x.c0), pt_to_int(P.x.c1), pt_to_int(P.y.c0), pt_to_int(P.y.c1)};
-  const bool larger = !inf && pt_y2_is_larger(c[2], c[3]);
-  if (zcash) {  // the first byte is the top of x.c1
-    c[1].l[11] |= (compressed ? 0x80000000u : 0u) | (inf ? 0x40000000u : 0u) | (compressed && larger ? 0x20000000u : 0u);
-  } else {  // the last byte is the top of the last coordinate's c1
-    const uint32_t f = (inf ? 0x40000000u : 0u) | (larger ? 0x80000000u : 0u);
-    if (compressed) c[1].l[11] |= f;
-    else c[3].l[11] |= f;
-  }
-  const int k = compressed ? 2 : 4;
-  uint8_t* o = out + i * (size_t)(48 * k);
-#pragma unroll
-  for (int e = 0; e < 4; e++)
-    if (e < k) pt_store_coord(o + 48 * (zcash ? e ^ 1 : e), c[e], zcash);
-}
-
 // gm_debug_fq2_sqrt: pt_fq2_sqrt on ark-ff Montgomery elements, one lane each
 __global__ __launch_bounds__(PT_G2_BLOCK) void k_fq2_sqrt(const uint8_t* __restrict__ src, size_t n, uint8_t* __restrict__ root, uint8_t* __restrict__ is_square) {
   const size_t i = (size_t)blockIdx.x * PT_G2_BLOCK + threadIdx.x;
@@ -528,57 +245,6 @@ __global__ __launch_bounds__(PT_G2_BLOCK) void k_fq2_sqrt(const uint8_t* __restr
   r.c1 = fqe_export(r.c1);
   fq2_store(root + i * 96, r);
   is_square[i] = square ? 1 : 0;
-}
-
-// ---- points without a known logarithm: candidates -> cofactor-cleared points (gm_g1_bases_from_candidates, gm_g2_...) -----------
-// A candidate is an x (and one bit that chooses between y and -y); it survives when its coordinates are < q, x^3 + b is a square and
-// the cleared point is not the identity (include/gemini_hip.h has the format; tests/keygen_ref.py states all of it on integers).
-// Three launches, dense lanes in each, the host compacting in between from status bytes (a wave runs as long as its slowest lane:
-// one kernel from bytes to cleared point took 2.4 x as long, every wave paying root AND clearing for its few survivors):
-//   root    one lane per candidate: rules 1 and 2, the curve point (affine) into slot i, one status byte
-//   clear   one lane per candidate ON THE CURVE, in order and only as many as the key still needs: the cleared point (XYZZ) over the
-//           slot, one status byte (rule 3)
-//   gather  the survivors normalised into the key, eight to an inversion
-// Fq products: root G1 5 + 606, G2 9 + 1 221; clearing G1 63 x 9 + 6 x 10 = 627, G2 2 x 63 x 24 + 6 x 28 (mixed) + 5 x 37 (full) +
-// 135 (the tail: one mixed and two full additions, psi three times, [2] P) = 3 512.
-constexpr uint8_t PT_CAND_OK = 0, PT_CAND_GE_Q = 1, PT_CAND_NO_SQUARE = 2, PT_CAND_IDENTITY = 3;
-constexpr uint32_t PT_CAND_X_MASK = 0x1fffffffu;  // bits 381 and 382 are ignored, bit 383 is the choice of y
-
-__global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_g1_cand_root(const uint8_t* __restrict__ cand, size_t m, uint8_t* __restrict__ slots,
-                                                                                                      uint8_t* __restrict__ status) {
-  const size_t i = (size_t)blockIdx.x * PT_BLOCK + threadIdx.x;
-  if (i >= m) return;
-  Fq x = fp_load<FqParams>(cand + i * 48);
-  const bool larger = (x.l[11] >> 31) != 0;
-  x.l[11] &= PT_CAND_X_MASK;
-  uint8_t st = PT_CAND_OK;
-  if (pt_raw_ge_q(x)) {
-    st = PT_CAND_GE_Q;
-  } else {
-    G1Affine P;
-    P.x = pt_from_int(x);
-    const FqE rhs = fq_add(fq_mul(fq_sqr(P.x), P.x), pt_four());
-    P.y = pt_sqrt_candidate(rhs);
-    if (!(fq_sqr(P.y) == rhs)) {
-      st = PT_CAND_NO_SQUARE;
-    } else {
-      if (pt_y_is_larger(pt_to_int(P.y)) != larger) P.y = fq_neg_canonical(P.y);
-      g1_store_affine(slots + i * 192, P);
-    }
-  }
-  status[i] = st;
-}
-// lane j clears the curve point in slot idx[j]: [1 - x] P = [|x|] P + P
-__global__ __launch_bounds__(PT_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_g1_cand_clear(uint8_t* __restrict__ slots, const uint32_t* __restrict__ idx, size_t n,
-                                                                                                       uint8_t* __restrict__ status) {
-  const size_t j = (size_t)blockIdx.x * PT_BLOCK + threadIdx.x;
-  if (j >= n) return;
-  uint8_t* slot = slots + (size_t)idx[j] * 192;
-  const G1Affine P = g1_load_affine(slot);
-  G1Xyzz T = pt_g1_mul_x(P);
-  xyzz_madd(T, P);
-  g1_store_xyzz(slot, T);
-  status[j] = T.is_identity() ? PT_CAND_IDENTITY : PT_CAND_OK;
 }
 
 // psi on XYZZ coordinates: conjugation is a field automorphism, so (X, Y, ZZ, ZZZ) -> (conj(X) c_x, conj(Y) c_y, conj(ZZ), conj(ZZZ))
@@ -604,7 +270,7 @@ GM_DEV G2Xyzz pt_g2_psi(const G2Xyzz& T) {
 }
 // [x^2 - x - 1] P + [x - 1] psi(P) + psi^2([2] P) (Budroni, Pintore: "Efficient hash maps to G2 on BLS curves"), x = -|x|: with
 // U = [|x| + 1] P it is [|x|] U - P - psi(U) + psi^2([2] P) -- two |x| ladders.  U waits in the lane's slot between the five
-// additions of the second ladder.  k_g2_cand_clear still spills: 560 bytes of scratch a lane at one wave per SIMD -- the accumulator,
+// additions of the second ladder.  k_pt_cand_clear<PtG2> still spills: 560 bytes of scratch a lane at one wave per SIMD -- the accumulator,
 // P and a full XYZZ + XYZZ addition over Fq2 are more than 512 registers, as in k_g2_reduce (profiles/keygen_kernel_resources.txt).
 GM_DEV G2Xyzz pt_g2_clear(const G2Affine& P, uint8_t* slot) {
   G2Xyzz acc = G2Xyzz::from_affine(P);
@@ -626,45 +292,6 @@ GM_DEV G2Xyzz pt_g2_clear(const G2Affine& P, uint8_t* slot) {
   g2_add(acc, pu);
   g2_add(acc, pt_g2_psi(pt_g2_psi(g2_dbl_affine(P))));
   return acc;
-}
-
-__global__ __launch_bounds__(PT_G2_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_g2_cand_root(const uint8_t* __restrict__ cand, size_t m, uint8_t* __restrict__ slots, uint8_t* __restrict__ status) {
-  const size_t i = (size_t)blockIdx.x * PT_G2_BLOCK + threadIdx.x;
-  if (i >= m) return;
-  Fq c0 = fp_load<FqParams>(cand + i * 96), c1 = fp_load<FqParams>(cand + i * 96 + 48);
-  const bool larger = (c1.l[11] >> 31) != 0;
-  c0.l[11] &= PT_CAND_X_MASK;
-  c1.l[11] &= PT_CAND_X_MASK;
-  uint8_t st = PT_CAND_OK;
-  if (pt_raw_ge_q(c0) || pt_raw_ge_q(c1)) {
-    st = PT_CAND_GE_Q;
-  } else {
-    G2Affine P;
-    P.x.c0 = pt_from_int(c0);
-    P.x.c1 = pt_from_int(c1);
-    Fq2 rhs = fq2_mul(fq2_sqr(P.x), P.x);
-    rhs.c0 = fq_add(rhs.c0, pt_four());
-    rhs.c1 = fq_add(rhs.c1, pt_four());
-    bool square;
-    P.y = pt_fq2_sqrt(rhs, &square);
-    if (!square) {
-      st = PT_CAND_NO_SQUARE;
-    } else {
-      if (pt_y2_is_larger(pt_to_int(P.y.c0), pt_to_int(P.y.c1)) != larger) P.y = fq2_neg_canonical(P.y);
-      g2_store_affine(slots + i * G2_XYZZ_BYTES, P);
-    }
-  }
-  status[i] = st;
-}
-// lane j clears the curve point in slot idx[j] (its first 192 bytes); the slot then serves pt_g2_clear, and takes the result
-__global__ __launch_bounds__(PT_G2_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_g2_cand_clear(uint8_t* slots, const uint32_t* __restrict__ idx, size_t n, uint8_t* __restrict__ status) {
-  const size_t j = (size_t)blockIdx.x * PT_G2_BLOCK + threadIdx.x;
-  if (j >= n) return;
-  uint8_t* slot = slots + (size_t)idx[j] * G2_XYZZ_BYTES;
-  const G2Affine P = g2_load_affine(slot);
-  const G2Xyzz R = pt_g2_clear(P, slot);
-  g2_store_xyzz(slot, R);
-  status[j] = R.is_identity() ? PT_CAND_IDENTITY : PT_CAND_OK;
 }
 
 // The slots idx[0 .. n) -> packed affine records, Montgomery's trick over eight points a lane; the prefix products wait in the
@@ -694,7 +321,350 @@ __global__ __launch_bounds__(PT_BLOCK) void k_g1_gather_affine(const uint8_t* __
   }
 }
 
+static int g1_normalise_launch(Context* C, const uint8_t* in, const uint32_t* d_idx, size_t n, uint8_t* out) {
+  const size_t groups = (n + PT_NORM_K - 1) / PT_NORM_K;
+  hipLaunchKernelGGL(k_g1_gather_affine, dim3((unsigned)((groups + PT_BLOCK - 1) / PT_BLOCK)), dim3(PT_BLOCK), 0, C->stream, in, d_idx, n, out);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
 int g2_normalise_launch(Context* C, const uint8_t* in, const uint32_t* d_idx, size_t n, uint8_t* out);  // g2msm.hip
+
+// ---- the two groups ------------------------------------------------------------------------------------------------------------
+// What the kernels and the entries below need to know of a group, by name: the types, the launch shape, the record sizes, and the
+// functions above that differ between the groups; the only arithmetic stated here is the curve's right-hand side.  A coordinate is
+// NC elements of Fq, c0 first; el() / parts() pass between an element and its NC components in the device form.  The host members
+// are the handle table, the step between decoding a key and registering it, and the two figures candidates_run needs.
+struct PtG1 {
+  using El = FqE;
+  using Affine = G1Affine;
+  using Xyzz = G1Xyzz;
+  using Held = Bases;  // what a handle names
+  static constexpr const char* NAME = "g1";
+  static constexpr int NC = 1, BLOCK = PT_BLOCK, WAVES = 2;
+  static constexpr size_t AFF_BYTES = 96, XYZZ_BYTES = 192;
+  static GM_DEV El zero() { return fqe_zero(); }
+  static GM_DEV El el(const FqE* c) { return c[0]; }
+  static GM_DEV void parts(const El& a, FqE* c) { c[0] = a; }
+  static GM_DEV El neg(const El& a) { return fq_neg_canonical(a); }
+  static GM_DEV El curve_rhs(const El& x) { return fq_add(fq_mul(fq_sqr(x), x), pt_four()); }  // x^3 + 4
+  static GM_DEV El sqrt(const El& a, bool* is_square) {
+    const El r = pt_sqrt_candidate(a);
+    *is_square = fq_sqr(r) == a;
+    return r;
+  }
+  static GM_DEV Affine load_affine(const void* p) { return g1_load_affine(p); }
+  static GM_DEV void store_affine(void* p, const Affine& a) { g1_store_affine(p, a); }
+  static GM_DEV void store_xyzz(void* p, const Xyzz& a) { g1_store_xyzz(p, a); }
+  static GM_DEV uint8_t status(const Affine& P, bool check_curve) { return pt_g1_status(P, check_curve); }
+  static GM_DEV Xyzz clear(const Affine& P, uint8_t*) {  // [1 - x] P = [|x|] P + P
+    Xyzz T = pt_g1_mul_x(P);
+    xyzz_madd(T, P);
+    return T;
+  }
+  static Held* find(Context*, uint64_t h) { return find_bases(h); }
+  static uint64_t put(Context*, std::unique_ptr<Held> b) { return put_bases(std::move(b)); }  // as gm_g1_bases_register: no tables
+  static int before_put(Context* C, Held* b) { return bases_build_phi(C, b); }
+  static size_t cand_piece(size_t want) { return want / 2 * 5 + 64; }  // candidates to read for `want` points: a little over 1 / p
+  static int normalise(Context* C, const uint8_t* in, const uint32_t* d_idx, size_t n, uint8_t* out) { return g1_normalise_launch(C, in, d_idx, n, out); }
+};
+struct PtG2 {
+  using El = Fq2;
+  using Affine = G2Affine;
+  using Xyzz = G2Xyzz;
+  using Held = G2Bases;
+  static constexpr const char* NAME = "g2";
+  static constexpr int NC = 2, BLOCK = PT_G2_BLOCK, WAVES = 1;
+  static constexpr size_t AFF_BYTES = G2_AFF_BYTES, XYZZ_BYTES = G2_XYZZ_BYTES;
+  static GM_DEV El zero() { return fq2_zero(); }
+  static GM_DEV El el(const FqE* c) {
+    El r;
+    r.c0 = c[0];
+    r.c1 = c[1];
+    return r;
+  }
+  static GM_DEV void parts(const El& a, FqE* c) {
+    c[0] = a.c0;
+    c[1] = a.c1;
+  }
+  static GM_DEV El neg(const El& a) { return fq2_neg_canonical(a); }
+  static GM_DEV El curve_rhs(const El& x) {  // x^3 + 4 (1 + u)
+    El r = fq2_mul(fq2_sqr(x), x);
+    r.c0 = fq_add(r.c0, pt_four());
+    r.c1 = fq_add(r.c1, pt_four());
+    return r;
+  }
+  static GM_DEV El sqrt(const El& a, bool* is_square) { return pt_fq2_sqrt(a, is_square); }
+  static GM_DEV Affine load_affine(const void* p) { return g2_load_affine(p); }
+  static GM_DEV void store_affine(void* p, const Affine& a) { g2_store_affine(p, a); }
+  static GM_DEV void store_xyzz(void* p, const Xyzz& a) { g2_store_xyzz(p, a); }
+  static GM_DEV uint8_t status(const Affine& P, bool check_curve) { return pt_g2_status(P, check_curve); }
+  static GM_DEV Xyzz clear(const Affine& P, uint8_t* slot) { return pt_g2_clear(P, slot); }
+  static Held* find(Context* C, uint64_t h) { return find_in(C, C->g2_bases, h); }
+  static uint64_t put(Context* C, std::unique_ptr<Held> b) { return put_in(C, C->g2_bases, std::move(b)); }
+  static int before_put(Context*, Held*) { return GM_OK; }
+  static size_t cand_piece(size_t want) { return want / 4 * 13 + 64; }
+  static int normalise(Context* C, const uint8_t* in, const uint32_t* d_idx, size_t n, uint8_t* out) { return g2_normalise_launch(C, in, d_idx, n, out); }
+};
+
+// NC canonical integers < q  <->  an element in the device form
+template <class G>
+GM_DEV typename G::El pt_el_from_int(const Fq* v) {
+  FqE c[G::NC];
+#pragma unroll
+  for (int e = 0; e < G::NC; e++) c[e] = pt_from_int(v[e]);
+  return G::el(c);
+}
+template <class G>
+GM_DEV void pt_el_to_int(const typename G::El& a, Fq* v) {
+  G::parts(a, v);
+#pragma unroll
+  for (int e = 0; e < G::NC; e++) v[e] = pt_to_int(v[e]);
+}
+// y > -y in ark-ff's order of an extension, on the NC integers of y: the top non-zero component decides, c0 when all above it are
+// zero (c = -c only for c = 0).  ge_q[e] (nullptr: all fully reduced) says that component e is >= q, which reads as larger than its negative.
+template <int NC>
+GM_DEV bool pt_is_larger(const Fq* y, const bool* ge_q = nullptr) {
+  bool r = (ge_q && ge_q[0]) || pt_y_is_larger(y[0]);
+#pragma unroll
+  for (int e = 1; e < NC; e++) r = (ge_q && ge_q[e]) || (y[e].is_zero() ? r : pt_y_is_larger(y[e]));
+  return r;
+}
+
+// ---- reporting: the status byte of the lane, and the block's first bad lane (every lane of the block arrives here) -------------
+template <int BLOCK>
+GM_DEV void pt_report(size_t i, size_t n, uint8_t st, uint8_t* __restrict__ status, uint32_t* __restrict__ summary) {
+  __shared__ uint32_t first[BLOCK / 64];
+  const bool bad = i < n && st != GM_PT_OK;
+  if (i < n) status[i] = st;
+  const unsigned long long m = __ballot(bad);
+  if ((threadIdx.x & 63u) == 0) first[threadIdx.x >> 6] = m ? (threadIdx.x + (uint32_t)__ffsll((long long)m) - 1u) : PT_NO_BAD;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t f = PT_NO_BAD;
+    for (unsigned w = 0; w < blockDim.x / 64; w++) f = first[w] < f ? first[w] : f;
+    summary[blockIdx.x] = f;
+  }
+}
+
+// The five kernels below are stated once for both groups.  They work on the 2 NC components of a point, c[] = x.c0 .. , y.c0 .. ;
+// G1 runs them at two waves per SIMD and blocks of 256, G2 at one wave and blocks of 64.
+//
+// k_pt_check.  host_form != 0: records as gm_g1_bases_register / gm_g2_bases_register take them (ark-ff Montgomery limbs, stride >= AFF_BYTES, the
+// infinity byte behind the coordinates when the stride has room); 0: packed device records, canonical by construction
+template <class G>
+__global__ __launch_bounds__(G::BLOCK) __attribute__((amdgpu_waves_per_eu(G::WAVES, G::WAVES))) void k_pt_check(const uint8_t* __restrict__ src, size_t stride, int host_form, size_t n, uint8_t* __restrict__ status, uint32_t* __restrict__ summary) {
+  constexpr int NC = G::NC;
+  const size_t i = (size_t)blockIdx.x * G::BLOCK + threadIdx.x;
+  uint8_t st = GM_PT_OK;
+  if (i < n) {
+    const uint32_t* s = reinterpret_cast<const uint32_t*>(src + i * stride);
+    FqE c[2 * NC];
+    uint32_t any = 0;
+    bool canonical = true;
+#pragma unroll
+    for (int e = 0; e < 2 * NC; e++) {
+#pragma unroll
+      for (int k = 0; k < 12; k++) {
+        c[e].l[k] = s[12 * e + k];
+        any |= c[e].l[k];
+      }
+      canonical = canonical && !pt_raw_ge_q(c[e]);
+    }
+    const bool inf = (host_form && stride > G::AFF_BYTES && src[i * stride + G::AFF_BYTES] != 0) || any == 0;  // what k_pack_bases reads as the identity
+    if (!inf) {
+      if (host_form && !canonical) {
+        st = GM_PT_NONCANONICAL;
+      } else {
+        if (host_form) {
+#pragma unroll
+          for (int e = 0; e < 2 * NC; e++) c[e] = fqe_import(c[e]);
+        }
+        typename G::Affine P;
+        P.x = G::el(c);
+        P.y = G::el(c + NC);
+        st = G::status(P, true);
+      }
+    }
+  }
+  pt_report<G::BLOCK>(i, n, st, status, summary);
+}
+
+// 48 NC- / 96 NC-byte encodings -> packed device records (the layout k_pack_bases produces; the identity and every rejected point
+// are the all-zero record).  Acceptance and the order of the checks are those of wire.g1_deserialize(.., strict = True, validate)
+// and of gemini_amd/g2.py: deserialize(.., strict = True, validate).  Component e sits in wire slot e (arkworks: c0 | c1,
+// little-endian) or e ^ (NC - 1) (zcash: c1 | c0, big-endian).
+template <class G>
+__global__ __launch_bounds__(G::BLOCK) __attribute__((amdgpu_waves_per_eu(G::WAVES, G::WAVES))) void k_pt_decode(const uint8_t* __restrict__ bytes, size_t n, int compressed, int zcash, int validate, uint8_t* __restrict__ dst, uint8_t* __restrict__ status,
+                         uint32_t* __restrict__ summary) {
+  constexpr int NC = G::NC;
+  const size_t i = (size_t)blockIdx.x * G::BLOCK + threadIdx.x;
+  uint8_t st = GM_PT_OK;
+  if (i < n) {
+    const int k = compressed ? NC : 2 * NC;
+    const uint8_t* src = bytes + i * (size_t)(48 * k);
+    Fq c[2 * NC];
+#pragma unroll
+    for (int e = 0; e < 2 * NC; e++) c[e] = e < k ? pt_load_coord(src + 48 * (zcash ? e ^ (NC - 1) : e), zcash) : Fq::zero();
+    uint32_t &x_top = c[NC - 1].l[11], &y_top = c[2 * NC - 1].l[11];
+    bool inf, larger;
+    if (zcash) {  // flags in the three top bits of the first byte = the top bits of x's last component
+      const uint32_t f = x_top >> 29;
+      x_top &= 0x1fffffffu;
+      inf = (f >> 1) & 1u;
+      larger = f & 1u;
+      if ((int)(f >> 2) != (compressed ? 1 : 0) || (larger && (!compressed || inf))) st = GM_PT_BAD_ENCODING;
+    } else {  // flags in the two top bits of the last byte = the top bits of the last coordinate's last component
+      const uint32_t f = (compressed ? x_top : y_top) >> 30;
+      if (compressed) x_top &= 0x3fffffffu;
+      else y_top &= 0x3fffffffu;
+      inf = f == 1;
+      larger = f == 2;
+      if (f == 3) st = GM_PT_BAD_ENCODING;
+    }
+    typename G::Affine P;
+    P.x = G::zero();
+    P.y = G::zero();
+    if (st == GM_PT_OK) {
+      bool x_ge = false;
+#pragma unroll
+      for (int e = 0; e < NC; e++) x_ge = x_ge || pt_raw_ge_q(c[e]);
+      if (inf) {
+        bool zero = true;
+#pragma unroll
+        for (int e = 0; e < 2 * NC; e++) zero = zero && c[e].is_zero();
+        if (!zero) st = GM_PT_BAD_ENCODING;  // infinity with non-zero coordinates
+      } else if (compressed) {
+        if (x_ge) {
+          st = GM_PT_NONCANONICAL;
+        } else {
+          P.x = pt_el_from_int<G>(c);
+          bool square;
+          P.y = G::sqrt(G::curve_rhs(P.x), &square);
+          if (!square) {
+            st = GM_PT_NOT_ON_CURVE;  // x^3 + b is no square
+          } else {
+            Fq y[NC];
+            pt_el_to_int<G>(P.y, y);
+            if (pt_is_larger<NC>(y) != larger) P.y = G::neg(P.y);
+            if (validate) st = G::status(P, false);  // on the curve by construction
+          }
+        }
+      } else {
+        bool ge[NC], y_ge = false;
+#pragma unroll
+        for (int e = 0; e < NC; e++) {
+          ge[e] = pt_raw_ge_q(c[NC + e]);
+          y_ge = y_ge || ge[e];
+        }
+        // wire.py and g2.py compare the sign flag BEFORE the canonical check, against (-y) mod q
+        if (!zcash && pt_is_larger<NC>(c + NC, ge) != larger) {
+          st = GM_PT_BAD_ENCODING;
+        } else if (x_ge || y_ge) {
+          st = GM_PT_NONCANONICAL;
+        } else {
+          P.x = pt_el_from_int<G>(c);
+          P.y = pt_el_from_int<G>(c + NC);
+          if (validate) st = G::status(P, true);
+        }
+      }
+    }
+    if (st != GM_PT_OK) {
+      P.x = G::zero();
+      P.y = G::zero();
+    }
+    G::store_affine(dst + i * G::AFF_BYTES, P);
+  }
+  pt_report<G::BLOCK>(i, n, st, status, summary);
+}
+
+// ---- resident records -> bytes: one Montgomery exit per coordinate and the y > -y compare, no inversion (the bases are affine) ------
+constexpr int PT_ENC_BLOCK = 256;
+template <class G>
+__global__ __launch_bounds__(PT_ENC_BLOCK) void k_pt_encode(const uint8_t* __restrict__ src, size_t n, int compressed, int zcash, uint8_t* __restrict__ out) {
+  constexpr int NC = G::NC;
+  const size_t i = (size_t)blockIdx.x * PT_ENC_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const typename G::Affine P = G::load_affine(src + i * G::AFF_BYTES);
+  const bool inf = P.is_identity();
+  Fq c[2 * NC];  // 0 for the identity
+  pt_el_to_int<G>(P.x, c);
+  pt_el_to_int<G>(P.y, c + NC);
+  const bool larger = !inf && pt_is_larger<NC>(c + NC);
+  uint32_t &x_top = c[NC - 1].l[11], &y_top = c[2 * NC - 1].l[11];
+  if (zcash) {  // the first byte is the top of x's last component
+    x_top |= (compressed ? 0x80000000u : 0u) | (inf ? 0x40000000u : 0u) | (compressed && larger ? 0x20000000u : 0u);
+  } else {  // the last byte is the top of the last coordinate's last component
+    const uint32_t f = (inf ? 0x40000000u : 0u) | (larger ? 0x80000000u : 0u);
+    if (compressed) x_top |= f;
+    else y_top |= f;
+  }
+  const int k = compressed ? NC : 2 * NC;
+  uint8_t* o = out + i * (size_t)(48 * k);
+#pragma unroll
+  for (int e = 0; e < 2 * NC; e++)
+    if (e < k) pt_store_coord(o + 48 * (zcash ? e ^ (NC - 1) : e), c[e], zcash);
+}
+
+// ---- points without a known logarithm: candidates -> cofactor-cleared points (gm_g1_bases_from_candidates, gm_g2_...) -----------
+// A candidate is an x (and one bit that chooses between y and -y); it survives when its coordinates are < q, x^3 + b is a square and
+// the cleared point is not the identity (include/gemini_hip.h has the format; tests/keygen_ref.py states all of it on integers).
+// Three launches, dense lanes in each, the host compacting in between from status bytes (a wave runs as long as its slowest lane:
+// one kernel from bytes to cleared point took 2.4 x as long, every wave paying root AND clearing for its few survivors):
+//   root    one lane per candidate: rules 1 and 2, the curve point (affine) into slot i, one status byte
+//   clear   one lane per candidate ON THE CURVE, in order and only as many as the key still needs: the cleared point (XYZZ) over the
+//           slot, one status byte (rule 3)
+//   gather  the survivors normalised into the key, eight to an inversion
+// Fq products: root G1 5 + 606, G2 9 + 1 221; clearing G1 63 x 9 + 6 x 10 = 627, G2 2 x 63 x 24 + 6 x 28 (mixed) + 5 x 37 (full) +
+// 135 (the tail: one mixed and two full additions, psi three times, [2] P) = 3 512.
+constexpr uint8_t PT_CAND_OK = 0, PT_CAND_GE_Q = 1, PT_CAND_NO_SQUARE = 2, PT_CAND_IDENTITY = 3;
+constexpr uint32_t PT_CAND_X_MASK = 0x1fffffffu;  // bits 381 and 382 are ignored, bit 383 (of the last component) is the choice of y
+
+template <class G>
+__global__ __launch_bounds__(G::BLOCK) __attribute__((amdgpu_waves_per_eu(G::WAVES, G::WAVES))) void k_pt_cand_root(const uint8_t* __restrict__ cand, size_t m, uint8_t* __restrict__ slots, uint8_t* __restrict__ status) {
+  constexpr int NC = G::NC;
+  const size_t i = (size_t)blockIdx.x * G::BLOCK + threadIdx.x;
+  if (i >= m) return;
+  Fq c[NC];
+#pragma unroll
+  for (int e = 0; e < NC; e++) c[e] = fp_load<FqParams>(cand + (i * NC + e) * 48);
+  const bool larger = (c[NC - 1].l[11] >> 31) != 0;
+  bool ge = false;
+#pragma unroll
+  for (int e = 0; e < NC; e++) {
+    c[e].l[11] &= PT_CAND_X_MASK;
+    ge = ge || pt_raw_ge_q(c[e]);
+  }
+  uint8_t st = PT_CAND_OK;
+  if (ge) {
+    st = PT_CAND_GE_Q;
+  } else {
+    typename G::Affine P;
+    P.x = pt_el_from_int<G>(c);
+    bool square;
+    P.y = G::sqrt(G::curve_rhs(P.x), &square);
+    if (!square) {
+      st = PT_CAND_NO_SQUARE;
+    } else {
+      Fq y[NC];
+      pt_el_to_int<G>(P.y, y);
+      if (pt_is_larger<NC>(y) != larger) P.y = G::neg(P.y);
+      G::store_affine(slots + i * G::XYZZ_BYTES, P);
+    }
+  }
+  status[i] = st;
+}
+// lane j clears the curve point in slot idx[j] (the affine record at its start); G2's clearing uses the slot on the way, and the
+// slot takes the result
+template <class G>
+__global__ __launch_bounds__(G::BLOCK) __attribute__((amdgpu_waves_per_eu(G::WAVES, G::WAVES))) void k_pt_cand_clear(uint8_t* slots, const uint32_t* __restrict__ idx, size_t n, uint8_t* __restrict__ status) {
+  const size_t j = (size_t)blockIdx.x * G::BLOCK + threadIdx.x;
+  if (j >= n) return;
+  uint8_t* slot = slots + (size_t)idx[j] * G::XYZZ_BYTES;
+  const typename G::Affine P = G::load_affine(slot);
+  const typename G::Xyzz R = G::clear(P, slot);
+  G::store_xyzz(slot, R);
+  status[j] = R.is_identity() ? PT_CAND_IDENTITY : PT_CAND_OK;
+}
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -742,36 +712,35 @@ struct Report {
   }
 };
 
-// group: 1 / 2.  d_src: device memory, `stride` bytes per record.  Caller holds the MSM lock.
-int check_run(Context* C, int group, const uint8_t* d_src, size_t stride, int host_form, size_t n, uint8_t* status_or_null, size_t* first_bad, int* ok) {
+// G: PtG1 / PtG2.  d_src: device memory, `stride` bytes per record.  Caller holds the MSM lock.
+template <class G>
+int check_run(Context* C, const uint8_t* d_src, size_t stride, int host_form, size_t n, uint8_t* status_or_null, size_t* first_bad, int* ok) {
   if (n == 0) {
     if (first_bad) *first_bad = 0;
     *ok = 1;
     return GM_OK;
   }
   Report rep;
-  int rc = rep.alloc(n, group == 1 ? PT_BLOCK : PT_G2_BLOCK);
+  int rc = rep.alloc(n, G::BLOCK);
   if (rc) return rc;
-  if (group == 1)
-    hipLaunchKernelGGL(k_g1_check, dim3((unsigned)rep.blocks), dim3(PT_BLOCK), 0, C->stream, d_src, stride, host_form, n, rep.status(), rep.summary());
-  else
-    hipLaunchKernelGGL(k_g2_check, dim3((unsigned)rep.blocks), dim3(PT_G2_BLOCK), 0, C->stream, d_src, stride, host_form, n, rep.status(), rep.summary());
+  hipLaunchKernelGGL(k_pt_check<G>, dim3((unsigned)rep.blocks), dim3(G::BLOCK), 0, C->stream, d_src, stride, host_form, n, rep.status(), rep.summary());
   return rep.read(C, status_or_null, first_bad, ok);
 }
 
-int check_host(int group, const void* points, size_t stride, size_t n, uint8_t* status_or_null, size_t* first_bad, int* ok) {
+template <class G>
+int check_host(const void* points, size_t stride, size_t n, uint8_t* status_or_null, size_t* first_bad, int* ok) {
+  if (ok) *ok = 0;  // every check entry fails closed: whatever the return value, *ok is 1 only after a pass that accepted every point
   GM_CTX();
-  const size_t rec = group == 1 ? 96 : 192;
-  GM_CHECK(ok != nullptr && (points != nullptr || n == 0), GM_EINVAL, "g%d_check: null pointer", group);
-  GM_CHECK(stride >= rec && stride % 8 == 0, GM_EINVAL, "g%d_check: stride %zu must be >= %zu and a multiple of 8", group, stride, rec);
-  GM_CHECK(n <= SIZE_MAX / stride, GM_EINVAL, "g%d_check: %zu records of %zu bytes do not fit a size_t", group, n, stride);
+  GM_CHECK(ok != nullptr && (points != nullptr || n == 0), GM_EINVAL, "%s_check: null pointer", G::NAME);
+  GM_CHECK(stride >= G::AFF_BYTES && stride % 8 == 0, GM_EINVAL, "%s_check: stride %zu must be >= %zu and a multiple of 8", G::NAME, stride, G::AFF_BYTES);
+  GM_CHECK(n <= SIZE_MAX / stride, GM_EINVAL, "%s_check: %zu records of %zu bytes do not fit a size_t", G::NAME, n, stride);
   GM_MSM_LOCK(C);
   DevTmp stage;
   if (n) {
     GM_HIP(dev_malloc(&stage.p, n * stride));
     GM_HIP(hipMemcpyAsync(stage.p, points, n * stride, hipMemcpyHostToDevice, C->stream));
   }
-  return check_run(C, group, static_cast<const uint8_t*>(stage.p), stride, 1, n, status_or_null, first_bad, ok);
+  return check_run<G>(C, static_cast<const uint8_t*>(stage.p), stride, 1, n, status_or_null, first_bad, ok);
 }
 
 // ---- the group elements of a proof: Jacobian, any representative -> host records for ONE check launch per group ----------------
@@ -779,7 +748,7 @@ bool limbs_lt_q(const uint64_t* p) {
   uint64_t t[6];
   return gmh::sub_n<6>(t, p, gmh::FqP::MOD) != 0;
 }
-// a coordinate >= q has no value to normalise: its record gets all-ones limbs, which k_g1_check / k_g2_check report as NONCANONICAL
+// a coordinate >= q has no value to normalise: its record gets all-ones limbs, which k_pt_check reports as NONCANONICAL
 void proof_g1_record(const uint64_t jac[18], uint64_t out[12]) {
   for (int c = 0; c < 3; c++)
     if (!limbs_lt_q(jac + 6 * c)) {
@@ -814,8 +783,8 @@ int check_records(Context* C, const std::vector<uint64_t>& r1, const std::vector
     if (n2) GM_HIP(hipMemcpyAsync(static_cast<uint8_t*>(stage.p) + n1 * 96, r2.data(), n2 * 192, hipMemcpyHostToDevice, C->stream));
   }
   int ok1 = 0, ok2 = 0;
-  int rc = check_run(C, 1, static_cast<const uint8_t*>(stage.p), 96, 1, n1, nullptr, bad1, &ok1);
-  if (!rc) rc = check_run(C, 2, static_cast<const uint8_t*>(stage.p) + n1 * 96, 192, 1, n2, nullptr, bad2, &ok2);
+  int rc = check_run<PtG1>(C, static_cast<const uint8_t*>(stage.p), 96, 1, n1, nullptr, bad1, &ok1);
+  if (!rc) rc = check_run<PtG2>(C, static_cast<const uint8_t*>(stage.p) + n1 * 96, 192, 1, n2, nullptr, bad2, &ok2);
   if (rc) return rc;
   *ok = ok1 && ok2;
   return GM_OK;
@@ -834,17 +803,15 @@ int proof_check(const std::vector<const uint64_t*>& g1, size_t* first_bad, int* 
 }
 
 // bases[offset .. offset + n) of either group -> bytes on the host
-int encode_run(Context* C, int group, const uint8_t* d_src, size_t n, int compressed, int encoding, uint8_t* out) {
+template <class G>
+int encode_run(Context* C, const uint8_t* d_src, size_t n, int compressed, int encoding, uint8_t* out) {
   if (n == 0) return GM_OK;
-  const size_t sz = (group == 1 ? 48 : 96) * (compressed ? 1 : 2);
+  const size_t sz = G::AFF_BYTES / (compressed ? 2 : 1);
   const size_t blocks = (n + PT_ENC_BLOCK - 1) / PT_ENC_BLOCK;
-  GM_CHECK(blocks <= 0x7fffffffu && n <= SIZE_MAX / sz, GM_EINVAL, "g%d_bases_to_bytes: %zu points in one call", group, n);
+  GM_CHECK(blocks <= 0x7fffffffu && n <= SIZE_MAX / sz, GM_EINVAL, "%s_bases_to_bytes: %zu points in one call", G::NAME, n);
   DevTmp tmp;
   GM_HIP(dev_malloc(&tmp.p, n * sz));
-  if (group == 1)
-    hipLaunchKernelGGL(k_g1_encode, dim3((unsigned)blocks), dim3(PT_ENC_BLOCK), 0, C->stream, d_src, n, compressed ? 1 : 0, encoding, static_cast<uint8_t*>(tmp.p));
-  else
-    hipLaunchKernelGGL(k_g2_encode, dim3((unsigned)blocks), dim3(PT_ENC_BLOCK), 0, C->stream, d_src, n, compressed ? 1 : 0, encoding, static_cast<uint8_t*>(tmp.p));
+  hipLaunchKernelGGL(k_pt_encode<G>, dim3((unsigned)blocks), dim3(PT_ENC_BLOCK), 0, C->stream, d_src, n, compressed ? 1 : 0, encoding, static_cast<uint8_t*>(tmp.p));
   GM_HIP(hipGetLastError());
   GM_HIP(hipMemcpyAsync(out, tmp.p, n * sz, hipMemcpyDeviceToHost, C->stream));
   GM_HIP(hipStreamSynchronize(C->stream));
@@ -858,15 +825,15 @@ int encode_run(Context* C, int group, const uint8_t* d_src, size_t n, int compre
 // (the slots of a piece: 192 / 384 MB).  Of a piece's curve points only as many as the key still needs are cleared, in order; one
 // that clears to the identity (rule 3) makes the loop take the next ones.  *found counts the survivors among the candidates [0, *used).
 constexpr size_t PT_CAND_PIECE = (size_t)1 << 20;
-size_t cand_piece(int group, size_t want) { return group == 1 ? want / 2 * 5 + 64 : want / 4 * 13 + 64; }
-int candidates_run(Context* C, int group, const uint8_t* cand, size_t m, size_t n, uint8_t** d_out, size_t* used, size_t* found) {
-  const size_t csz = group == 1 ? 48 : 96, xsz = group == 1 ? 192 : G2_XYZZ_BYTES, asz = group == 1 ? 96 : G2_AFF_BYTES;
-  const unsigned block = group == 1 ? PT_BLOCK : PT_G2_BLOCK;
+template <class G>
+int candidates_run(Context* C, const uint8_t* cand, size_t m, size_t n, uint8_t** d_out, size_t* used, size_t* found) {
+  const size_t csz = 48 * G::NC, xsz = G::XYZZ_BYTES, asz = G::AFF_BYTES;
+  const unsigned block = G::BLOCK;
   *d_out = nullptr;
   *used = m;
   *found = 0;
   GM_MSM_LOCK(C);
-  const size_t cap = std::min({m, PT_CAND_PIECE, cand_piece(group, n)});
+  const size_t cap = std::min({m, PT_CAND_PIECE, G::cand_piece(n)});
   DevTmp out, stage, slots_, st_, idx_;
   GM_HIP(dev_malloc(&out.p, n * asz));
   GM_HIP(dev_malloc(&stage.p, cap * csz));
@@ -879,12 +846,9 @@ int candidates_run(Context* C, int group, const uint8_t* cand, size_t m, size_t 
   std::vector<uint32_t> on_curve, good;
   size_t pos = 0, have = 0;
   while (have < n && pos < m) {
-    const size_t k = std::min({m - pos, cap, cand_piece(group, n - have)});
+    const size_t k = std::min({m - pos, cap, G::cand_piece(n - have)});
     GM_HIP(hipMemcpyAsync(stage.p, cand + pos * csz, k * csz, hipMemcpyHostToDevice, C->stream));
-    if (group == 1)
-      hipLaunchKernelGGL(k_g1_cand_root, dim3((unsigned)((k + block - 1) / block)), dim3(block), 0, C->stream, static_cast<const uint8_t*>(stage.p), k, slots, st);
-    else
-      hipLaunchKernelGGL(k_g2_cand_root, dim3((unsigned)((k + block - 1) / block)), dim3(block), 0, C->stream, static_cast<const uint8_t*>(stage.p), k, slots, st);
+    hipLaunchKernelGGL(k_pt_cand_root<G>, dim3((unsigned)((k + block - 1) / block)), dim3(block), 0, C->stream, static_cast<const uint8_t*>(stage.p), k, slots, st);
     GM_HIP(hipGetLastError());
     GM_HIP(hipMemcpyAsync(h_st.data(), st, k, hipMemcpyDeviceToHost, C->stream));
     GM_HIP(hipStreamSynchronize(C->stream));
@@ -895,10 +859,7 @@ int candidates_run(Context* C, int group, const uint8_t* cand, size_t m, size_t 
     for (size_t at = 0; at < on_curve.size() && have < n;) {
       const size_t c = std::min(on_curve.size() - at, n - have);
       GM_HIP(hipMemcpyAsync(idx, on_curve.data() + at, c * 4, hipMemcpyHostToDevice, C->stream));
-      if (group == 1)
-        hipLaunchKernelGGL(k_g1_cand_clear, dim3((unsigned)((c + block - 1) / block)), dim3(block), 0, C->stream, slots, idx, c, st);
-      else
-        hipLaunchKernelGGL(k_g2_cand_clear, dim3((unsigned)((c + block - 1) / block)), dim3(block), 0, C->stream, slots, idx, c, st);
+      hipLaunchKernelGGL(k_pt_cand_clear<G>, dim3((unsigned)((c + block - 1) / block)), dim3(block), 0, C->stream, slots, idx, c, st);
       GM_HIP(hipGetLastError());
       GM_HIP(hipMemcpyAsync(h_st.data(), st, c, hipMemcpyDeviceToHost, C->stream));
       GM_HIP(hipStreamSynchronize(C->stream));
@@ -908,14 +869,8 @@ int candidates_run(Context* C, int group, const uint8_t* cand, size_t m, size_t 
       if (!good.empty()) {
         uint8_t* dst = static_cast<uint8_t*>(out.p) + have * asz;
         if (good.size() != c) GM_HIP(hipMemcpyAsync(idx, good.data(), good.size() * 4, hipMemcpyHostToDevice, C->stream));  // else idx holds them already
-        if (group == 1) {
-          const size_t groups = (good.size() + PT_NORM_K - 1) / PT_NORM_K;
-          hipLaunchKernelGGL(k_g1_gather_affine, dim3((unsigned)((groups + PT_BLOCK - 1) / PT_BLOCK)), dim3(PT_BLOCK), 0, C->stream, slots, idx, good.size(), dst);
-          GM_HIP(hipGetLastError());
-        } else {
-          int rc = g2_normalise_launch(C, slots, idx, good.size(), dst);
-          if (rc) return rc;
-        }
+        int rc = G::normalise(C, slots, idx, good.size(), dst);
+        if (rc) return rc;
         GM_HIP(hipStreamSynchronize(C->stream));  // idx, the slots and the host lists are rewritten from here on
         have += good.size();
         if (have == n) end = (size_t)good.back() + 1;
@@ -930,6 +885,95 @@ int candidates_run(Context* C, int group, const uint8_t* cand, size_t m, size_t 
     *d_out = static_cast<uint8_t*>(out.p);
     out.p = nullptr;
   }
+  return GM_OK;
+}
+
+// ---- the gm_g1_bases_* / gm_g2_bases_* entries of this file, once for both groups --------------------------------------------------
+template <class G>
+int bases_check(uint64_t handle, size_t offset, size_t n, uint8_t* status_or_null, size_t* first_bad, int* ok) {
+  if (ok) *ok = 0;
+  GM_CTX();
+  typename G::Held* b = G::find(C, handle);
+  GM_CHECK(b != nullptr, GM_EHANDLE, "%s_bases_check: unknown handle %llu", G::NAME, (unsigned long long)handle);
+  GM_CHECK(ok != nullptr, GM_EINVAL, "%s_bases_check: null pointer", G::NAME);
+  GM_CHECK(offset <= b->n && n <= b->n - offset, GM_EINVAL, "%s_bases_check: range [%zu, %zu) outside %zu bases", G::NAME, offset, offset + n, b->n);
+  GM_MSM_LOCK(C);
+  return check_run<G>(C, b->d + offset * G::AFF_BYTES, G::AFF_BYTES, 0, n, status_or_null, first_bad, ok);
+}
+
+template <class G>
+int bases_from_bytes(const uint8_t* bytes, size_t n, int compressed, int encoding, int validate, uint64_t* handle, uint8_t* status_or_null, size_t* first_bad, int* ok) {
+  if (ok) *ok = 0;  // before anything can return: a negative code never comes with a stale 1 or a stale handle
+  if (handle) *handle = 0;
+  GM_CTX();
+  GM_CHECK(handle != nullptr && ok != nullptr && (bytes != nullptr || n == 0), GM_EINVAL, "%s_bases_from_bytes: null pointer", G::NAME);
+  GM_CHECK(encoding == 0 || encoding == 1, GM_EINVAL, "%s_bases_from_bytes: encoding %d (0 arkworks, 1 zcash)", G::NAME, encoding);
+  GM_CHECK(n <= SIZE_MAX / G::AFF_BYTES, GM_EINVAL, "%s_bases_from_bytes: %zu points do not fit a size_t", G::NAME, n);
+  auto b = std::make_unique<typename G::Held>();
+  b->n = n;
+  int rc = GM_OK;
+  if (first_bad) *first_bad = 0;
+  if (n) {
+    GM_MSM_LOCK(C);
+    const size_t sz = G::AFF_BYTES / (compressed ? 2 : 1);
+    DevTmp stage, out;
+    Report rep;
+    if ((rc = rep.alloc(n, G::BLOCK))) return rc;
+    GM_HIP(dev_malloc(&stage.p, n * sz));
+    GM_HIP(dev_malloc(&out.p, n * G::AFF_BYTES));
+    GM_HIP(hipMemcpyAsync(stage.p, bytes, n * sz, hipMemcpyHostToDevice, C->stream));
+    hipLaunchKernelGGL(k_pt_decode<G>, dim3((unsigned)rep.blocks), dim3(G::BLOCK), 0, C->stream, static_cast<const uint8_t*>(stage.p), n, compressed ? 1 : 0, encoding,
+                       validate ? 1 : 0, static_cast<uint8_t*>(out.p), rep.status(), rep.summary());
+    if ((rc = rep.read(C, status_or_null, first_bad, ok))) return rc;
+    if (!*ok) return GM_OK;  // a bad point is a result: nothing stays registered
+    b->d = static_cast<uint8_t*>(out.p);
+    out.p = nullptr;
+  }
+  if ((rc = G::before_put(C, b.get()))) {
+    if (b->d) (void)raw_free(b->d);
+    *ok = 0;
+    return rc;
+  }
+  *handle = G::put(C, std::move(b));
+  *ok = 1;
+  return GM_OK;
+}
+
+// A cyclic share (gm_g1_bases_set_cyclic) is encoded as it is held: the n points of the share, not the key they were cut from.
+template <class G>
+int bases_to_bytes(uint64_t handle, size_t offset, size_t n, int compressed, int encoding, uint8_t* out, size_t cap) {
+  GM_CTX();
+  typename G::Held* b = G::find(C, handle);
+  GM_CHECK(b != nullptr, GM_EHANDLE, "%s_bases_to_bytes: unknown handle %llu", G::NAME, (unsigned long long)handle);
+  GM_CHECK(out != nullptr || n == 0, GM_EINVAL, "%s_bases_to_bytes: null pointer", G::NAME);
+  GM_CHECK(encoding == 0 || encoding == 1, GM_EINVAL, "%s_bases_to_bytes: encoding %d (0 arkworks, 1 zcash)", G::NAME, encoding);
+  GM_CHECK(offset <= b->n && n <= b->n - offset, GM_EINVAL, "%s_bases_to_bytes: range [%zu, %zu) outside %zu bases", G::NAME, offset, offset + n, b->n);
+  GM_CHECK(cap / (G::AFF_BYTES / (compressed ? 2 : 1)) >= n, GM_EINVAL, "%s_bases_to_bytes: %zu bytes do not hold %zu points", G::NAME, cap, n);
+  GM_MSM_LOCK(C);
+  return encode_run<G>(C, b->d + offset * G::AFF_BYTES, n, compressed, encoding, out);
+}
+
+template <class G>
+int bases_from_candidates(const uint8_t* cand, size_t m, size_t n, uint64_t* handle, size_t* used, size_t* found) {
+  if (handle) *handle = 0;
+  GM_CTX();
+  GM_CHECK(handle && used && found && (cand || m == 0), GM_EINVAL, "%s_bases_from_candidates: null pointer", G::NAME);
+  GM_CHECK(m <= SIZE_MAX / (48 * G::NC) && n <= SIZE_MAX / G::XYZZ_BYTES, GM_EINVAL, "%s_bases_from_candidates: %zu candidates for %zu points do not fit a size_t", G::NAME, m,
+           n);
+  auto b = std::make_unique<typename G::Held>();
+  b->n = n;
+  *used = n == 0 ? 0 : m;
+  *found = 0;
+  int rc;
+  if (n && m) {
+    if ((rc = candidates_run<G>(C, cand, m, n, &b->d, used, found))) return rc;
+  }
+  if (*found < n) return GM_OK;  // a shortfall is a result: nothing stays registered
+  if ((rc = G::before_put(C, b.get()))) {
+    if (b->d) (void)raw_free(b->d);
+    return rc;
+  }
+  *handle = G::put(C, std::move(b));
   return GM_OK;
 }
 
@@ -1144,167 +1188,40 @@ using namespace gm;
 extern "C" {
 
 int gm_g1_check(const void* points, size_t stride, size_t n, uint8_t* status_or_null, size_t* first_bad, int* ok) {
-  if (ok) *ok = 0;  // every entry of this block fails closed: whatever the return value, *ok is 1 only after a pass that accepted every point
-  return check_host(1, points, stride, n, status_or_null, first_bad, ok);
+  return check_host<PtG1>(points, stride, n, status_or_null, first_bad, ok);
 }
 int gm_g2_check(const void* points, size_t stride, size_t n, uint8_t* status_or_null, size_t* first_bad, int* ok) {
-  if (ok) *ok = 0;
-  return check_host(2, points, stride, n, status_or_null, first_bad, ok);
+  return check_host<PtG2>(points, stride, n, status_or_null, first_bad, ok);
 }
 
 int gm_g1_bases_check(uint64_t handle, size_t offset, size_t n, uint8_t* status_or_null, size_t* first_bad, int* ok) {
-  if (ok) *ok = 0;
-  GM_CTX();
-  Bases* b = find_bases(handle);
-  GM_CHECK(b != nullptr, GM_EHANDLE, "g1_bases_check: unknown handle %llu", (unsigned long long)handle);
-  GM_CHECK(ok != nullptr, GM_EINVAL, "g1_bases_check: null pointer");
-  GM_CHECK(offset <= b->n && n <= b->n - offset, GM_EINVAL, "g1_bases_check: range [%zu, %zu) outside %zu bases", offset, offset + n, b->n);
-  GM_MSM_LOCK(C);
-  return check_run(C, 1, b->d + offset * 96, 96, 0, n, status_or_null, first_bad, ok);
+  return bases_check<PtG1>(handle, offset, n, status_or_null, first_bad, ok);
 }
 int gm_g2_bases_check(uint64_t handle, size_t offset, size_t n, uint8_t* status_or_null, size_t* first_bad, int* ok) {
-  if (ok) *ok = 0;
-  GM_CTX();
-  G2Bases* b = find_in(C, C->g2_bases, handle);
-  GM_CHECK(b != nullptr, GM_EHANDLE, "g2_bases_check: unknown G2 bases handle %llu", (unsigned long long)handle);
-  GM_CHECK(ok != nullptr, GM_EINVAL, "g2_bases_check: null pointer");
-  GM_CHECK(offset <= b->n && n <= b->n - offset, GM_EINVAL, "g2_bases_check: range [%zu, %zu) outside %zu bases", offset, offset + n, b->n);
-  GM_MSM_LOCK(C);
-  return check_run(C, 2, b->d + offset * G2_AFF_BYTES, G2_AFF_BYTES, 0, n, status_or_null, first_bad, ok);
+  return bases_check<PtG2>(handle, offset, n, status_or_null, first_bad, ok);
 }
 
 int gm_g1_bases_from_bytes(const uint8_t* bytes, size_t n, int compressed, int encoding, int validate, uint64_t* handle, uint8_t* status_or_null, size_t* first_bad,
                            int* ok) {
-  if (ok) *ok = 0;  // before anything can return: a negative code never comes with a stale 1 or a stale handle
-  if (handle) *handle = 0;
-  GM_CTX();
-  GM_CHECK(handle != nullptr && ok != nullptr && (bytes != nullptr || n == 0), GM_EINVAL, "g1_bases_from_bytes: null pointer");
-  GM_CHECK(encoding == 0 || encoding == 1, GM_EINVAL, "g1_bases_from_bytes: encoding %d (0 arkworks, 1 zcash)", encoding);
-  GM_CHECK(n <= SIZE_MAX / 96, GM_EINVAL, "g1_bases_from_bytes: %zu points do not fit a size_t", n);
-  auto b = std::make_unique<Bases>();
-  b->n = n;
-  int rc = GM_OK;
-  if (first_bad) *first_bad = 0;
-  if (n) {
-    GM_MSM_LOCK(C);
-    const size_t sz = compressed ? 48 : 96;
-    DevTmp stage, out;
-    Report rep;
-    if ((rc = rep.alloc(n, PT_BLOCK))) return rc;
-    GM_HIP(dev_malloc(&stage.p, n * sz));
-    GM_HIP(dev_malloc(&out.p, n * 96));
-    GM_HIP(hipMemcpyAsync(stage.p, bytes, n * sz, hipMemcpyHostToDevice, C->stream));
-    hipLaunchKernelGGL(k_g1_decode, dim3((unsigned)rep.blocks), dim3(PT_BLOCK), 0, C->stream, static_cast<const uint8_t*>(stage.p), n, compressed ? 1 : 0, encoding,
-                       validate ? 1 : 0, static_cast<uint8_t*>(out.p), rep.status(), rep.summary());
-    if ((rc = rep.read(C, status_or_null, first_bad, ok))) return rc;
-    if (!*ok) return GM_OK;  // a bad point is a result: nothing stays registered
-    b->d = static_cast<uint8_t*>(out.p);
-    out.p = nullptr;
-  }
-  if ((rc = bases_build_phi(C, b.get()))) {
-    if (b->d) (void)raw_free(b->d);
-    *ok = 0;
-    return rc;
-  }
-  *handle = put_bases(std::move(b));  // as gm_g1_bases_register: no tables here, gm_g1_bases_precompute(handle, -1) builds them
-  *ok = 1;
-  return GM_OK;
+  return bases_from_bytes<PtG1>(bytes, n, compressed, encoding, validate, handle, status_or_null, first_bad, ok);
 }
-
 int gm_g2_bases_from_bytes(const uint8_t* bytes, size_t n, int compressed, int encoding, int validate, uint64_t* handle, uint8_t* status_or_null, size_t* first_bad,
                            int* ok) {
-  if (ok) *ok = 0;
-  if (handle) *handle = 0;
-  GM_CTX();
-  GM_CHECK(handle != nullptr && ok != nullptr && (bytes != nullptr || n == 0), GM_EINVAL, "g2_bases_from_bytes: null pointer");
-  GM_CHECK(encoding == 0 || encoding == 1, GM_EINVAL, "g2_bases_from_bytes: encoding %d (0 arkworks, 1 zcash)", encoding);
-  GM_CHECK(n <= SIZE_MAX / G2_AFF_BYTES, GM_EINVAL, "g2_bases_from_bytes: %zu points do not fit a size_t", n);
-  auto b = std::make_unique<G2Bases>();
-  b->n = n;
-  int rc = GM_OK;
-  if (first_bad) *first_bad = 0;
-  if (n) {
-    GM_MSM_LOCK(C);
-    const size_t sz = compressed ? 96 : 192;
-    DevTmp stage, out;
-    Report rep;
-    if ((rc = rep.alloc(n, PT_G2_BLOCK))) return rc;
-    GM_HIP(dev_malloc(&stage.p, n * sz));
-    GM_HIP(dev_malloc(&out.p, n * G2_AFF_BYTES));
-    GM_HIP(hipMemcpyAsync(stage.p, bytes, n * sz, hipMemcpyHostToDevice, C->stream));
-    hipLaunchKernelGGL(k_g2_decode, dim3((unsigned)rep.blocks), dim3(PT_G2_BLOCK), 0, C->stream, static_cast<const uint8_t*>(stage.p), n, compressed ? 1 : 0, encoding,
-                       validate ? 1 : 0, static_cast<uint8_t*>(out.p), rep.status(), rep.summary());
-    if ((rc = rep.read(C, status_or_null, first_bad, ok))) return rc;
-    if (!*ok) return GM_OK;  // a bad point is a result: nothing stays registered
-    b->d = static_cast<uint8_t*>(out.p);
-    out.p = nullptr;
-  }
-  *handle = put_in(C, C->g2_bases, std::move(b));
-  *ok = 1;
-  return GM_OK;
+  return bases_from_bytes<PtG2>(bytes, n, compressed, encoding, validate, handle, status_or_null, first_bad, ok);
 }
 
-// A cyclic share (gm_g1_bases_set_cyclic) is encoded as it is held: the n points of the share, not the key they were cut from.
 int gm_g1_bases_to_bytes(uint64_t handle, size_t offset, size_t n, int compressed, int encoding, uint8_t* out, size_t cap) {
-  GM_CTX();
-  Bases* b = find_bases(handle);
-  GM_CHECK(b != nullptr, GM_EHANDLE, "g1_bases_to_bytes: unknown handle %llu", (unsigned long long)handle);
-  GM_CHECK(out != nullptr || n == 0, GM_EINVAL, "g1_bases_to_bytes: null pointer");
-  GM_CHECK(encoding == 0 || encoding == 1, GM_EINVAL, "g1_bases_to_bytes: encoding %d (0 arkworks, 1 zcash)", encoding);
-  GM_CHECK(offset <= b->n && n <= b->n - offset, GM_EINVAL, "g1_bases_to_bytes: range [%zu, %zu) outside %zu bases", offset, offset + n, b->n);
-  GM_CHECK(cap / (compressed ? 48 : 96) >= n, GM_EINVAL, "g1_bases_to_bytes: %zu bytes do not hold %zu points", cap, n);
-  GM_MSM_LOCK(C);
-  return encode_run(C, 1, b->d + offset * 96, n, compressed, encoding, out);
+  return bases_to_bytes<PtG1>(handle, offset, n, compressed, encoding, out, cap);
 }
 int gm_g2_bases_to_bytes(uint64_t handle, size_t offset, size_t n, int compressed, int encoding, uint8_t* out, size_t cap) {
-  GM_CTX();
-  G2Bases* b = find_in(C, C->g2_bases, handle);
-  GM_CHECK(b != nullptr, GM_EHANDLE, "g2_bases_to_bytes: unknown G2 bases handle %llu", (unsigned long long)handle);
-  GM_CHECK(out != nullptr || n == 0, GM_EINVAL, "g2_bases_to_bytes: null pointer");
-  GM_CHECK(encoding == 0 || encoding == 1, GM_EINVAL, "g2_bases_to_bytes: encoding %d (0 arkworks, 1 zcash)", encoding);
-  GM_CHECK(offset <= b->n && n <= b->n - offset, GM_EINVAL, "g2_bases_to_bytes: range [%zu, %zu) outside %zu bases", offset, offset + n, b->n);
-  GM_CHECK(cap / (compressed ? 96 : 192) >= n, GM_EINVAL, "g2_bases_to_bytes: %zu bytes do not hold %zu points", cap, n);
-  GM_MSM_LOCK(C);
-  return encode_run(C, 2, b->d + offset * G2_AFF_BYTES, n, compressed, encoding, out);
+  return bases_to_bytes<PtG2>(handle, offset, n, compressed, encoding, out, cap);
 }
 
 int gm_g1_bases_from_candidates(const uint8_t* cand, size_t m, size_t n, uint64_t* handle, size_t* used, size_t* found) {
-  if (handle) *handle = 0;
-  GM_CTX();
-  GM_CHECK(handle && used && found && (cand || m == 0), GM_EINVAL, "g1_bases_from_candidates: null pointer");
-  GM_CHECK(m <= SIZE_MAX / 48 && n <= SIZE_MAX / 192, GM_EINVAL, "g1_bases_from_candidates: %zu candidates for %zu points do not fit a size_t", m, n);
-  auto b = std::make_unique<Bases>();
-  b->n = n;
-  *used = n == 0 ? 0 : m;
-  *found = 0;
-  int rc;
-  if (n && m) {
-    if ((rc = candidates_run(C, 1, cand, m, n, &b->d, used, found))) return rc;
-  }
-  if (*found < n) return GM_OK;  // a shortfall is a result: nothing stays registered
-  if ((rc = bases_build_phi(C, b.get()))) {
-    if (b->d) (void)raw_free(b->d);
-    return rc;
-  }
-  *handle = put_bases(std::move(b));  // as gm_g1_bases_register: no tables here
-  return GM_OK;
+  return bases_from_candidates<PtG1>(cand, m, n, handle, used, found);
 }
 int gm_g2_bases_from_candidates(const uint8_t* cand, size_t m, size_t n, uint64_t* handle, size_t* used, size_t* found) {
-  if (handle) *handle = 0;
-  GM_CTX();
-  GM_CHECK(handle && used && found && (cand || m == 0), GM_EINVAL, "g2_bases_from_candidates: null pointer");
-  GM_CHECK(m <= SIZE_MAX / 96 && n <= SIZE_MAX / G2_XYZZ_BYTES, GM_EINVAL, "g2_bases_from_candidates: %zu candidates for %zu points do not fit a size_t", m, n);
-  auto b = std::make_unique<G2Bases>();
-  b->n = n;
-  *used = n == 0 ? 0 : m;
-  *found = 0;
-  if (n && m) {
-    int rc = candidates_run(C, 2, cand, m, n, &b->d, used, found);
-    if (rc) return rc;
-  }
-  if (*found < n) return GM_OK;
-  *handle = put_in(C, C->g2_bases, std::move(b));
-  return GM_OK;
+  return bases_from_candidates<PtG2>(cand, m, n, handle, used, found);
 }
 
 int gm_crs_from_bases(uint64_t g1_handle, uint64_t g2_handle, uint64_t* crs) {
@@ -1341,8 +1258,8 @@ int gm_crs_check(uint64_t crs, size_t* first_bad_g1, size_t* first_bad_g2, int* 
   GM_CHECK(ok != nullptr, GM_EINVAL, "crs_check: null pointer");
   GM_MSM_LOCK(C);
   int ok1 = 0, ok2 = 0;
-  int rc = check_run(C, 1, c->g1, 96, 0, c->n1, nullptr, first_bad_g1, &ok1);
-  if (!rc) rc = check_run(C, 2, c->g2, G2_AFF_BYTES, 0, c->n2, nullptr, first_bad_g2, &ok2);
+  int rc = check_run<PtG1>(C, c->g1, 96, 0, c->n1, nullptr, first_bad_g1, &ok1);
+  if (!rc) rc = check_run<PtG2>(C, c->g2, G2_AFF_BYTES, 0, c->n2, nullptr, first_bad_g2, &ok2);
   if (rc) return rc;
   *ok = ok1 && ok2;
   return GM_OK;

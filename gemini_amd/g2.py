@@ -160,7 +160,7 @@ def serialize_vec_uncompressed(points, enc: int | None = None) -> bytes:
 
 # ---- the canonical encodings, both framings and both modes ---------------------------------------------------------------------
 # The image of wire.g1_serialize / wire.g1_deserialize over Fq2: the same flag rules and the same ORDER of rejections.  This is the
-# definition k_g2_decode / k_g2_encode (gemini_amd/csrc/points.hip) follow point for point; a rejected encoding raises a WireError
+# definition k_pt_decode<PtG2> / k_pt_encode<PtG2> (gemini_amd/csrc/points.hip) follow point for point; a rejected encoding raises a WireError
 # whose `status` is the GM_PT_* value the device reports for it.
 PT_BAD_ENCODING, PT_NONCANONICAL, PT_NOT_ON_CURVE, PT_NOT_IN_SUBGROUP = 1, 2, 3, 4
 

@@ -85,5 +85,12 @@ def rejection_cases(compress: bool, enc: int) -> list:
         # the clear flag of the smaller y is a flag mismatch, not a non-canonical coordinate
         P = G if not g2._f2_gt(G[1], g2.f2_neg(G[1])) else (G[0], g2.f2_neg(G[1]))
         add("y.c1 >= q under a clear sign flag", with_coord(g2_bytes(P, False, 0), 3, 0, P[1][1] + pr.Q), BAD_ENCODING)
+        # y.c1 = 0 hands the comparison to y.c0, where the same rule holds: y.c0 + q reads as larger.  Both rejections come before the
+        # curve test, so y need not belong to x; 12345 + q < 2^382 leaves the flag bits free
+        b = with_coord(g2_bytes((G[0], (12345, 0)), False, 0), 2, 0, 12345 + pr.Q)
+        add("y.c1 = 0 and y.c0 >= q under a clear sign flag", b, BAD_ENCODING)
+        b = bytearray(b)
+        b[n - 1] |= 0x80
+        add("y.c1 = 0 and y.c0 >= q under a set sign flag", b, NONCANONICAL)
     add("not in the subgroup", g2_bytes(outside, compress, enc), NOT_IN_SUBGROUP)
     return cases

@@ -86,7 +86,7 @@ def g1_sigma(p):
 
 
 def g1_in_subgroup_endo(p) -> bool:
-    """what k_g1_check computes: sigma(P) == -[x^2] P as two multiplications by |x|; the identity is a member"""
+    """what k_pt_check<PtG1> computes: sigma(P) == -[x^2] P as two multiplications by |x|; the identity is a member"""
     if p is None:
         return True
     return g1_sigma(p) == g1_neg(g1_mul_raw(g1_mul_raw(p, X_ABS), X_ABS))
@@ -173,7 +173,7 @@ def g2_psi(p):
 
 
 def g2_in_subgroup_endo(p) -> bool:
-    """what k_g2_check computes: psi(Q) == -[|x|] Q; the identity is a member"""
+    """what k_pt_check<PtG2> computes: psi(Q) == -[|x|] Q; the identity is a member"""
     if p is None:
         return True
     return g2_psi(p) == g2_neg(g2_mul_raw(p, X_ABS))

@@ -1,6 +1,6 @@
 """The G2 encodings of gemini_amd/g2.py on Python integers: serialize_compressed / serialize_uncompressed / deserialize in both framings,
 the image of wire.g1_serialize / g1_deserialize over Fq2.  This is the definition the device decoder follows
-(tests/test_gpu_g2_bytes.py holds k_g2_decode against it); here it is held against a published vector, against its own inverse and
+(tests/test_gpu_g2_bytes.py holds k_pt_decode<PtG2> against it); here it is held against a published vector, against its own inverse and
 against the status each rejection class is assigned."""
 import random
 
@@ -28,7 +28,7 @@ def test_known_answer():
 
 
 def test_f2_sqrt_norm_method():
-    """the derivation k_g2_decode's square root rests on, against tests/points_ref.py's and against squaring"""
+    """the derivation the square root of k_pt_decode<PtG2> rests on, against tests/points_ref.py's and against squaring"""
     rng = random.Random(0xF2)
     sides = set()
     for _ in range(40):

@@ -35,7 +35,7 @@ from gemini_amd.kzg import g1_generator_mont  # noqa: E402
 TAU = 0x2F4E6D8C0B1A39587766554433221100FFEEDDCCBBAA9988776655443322110F % G2.R_ORDER
 # Fq products, read off the kernels' loops (a square counts as a product; Fq2 product 3, Fq2 square 2; G2 doubling 24, mixed
 # addition 28, full addition 37; G1 doubling 9, mixed addition 10)
-P_CHECK_G2 = 1674                                  # k_g2_check (points.hip)
+P_CHECK_G2 = 1674                                  # k_pt_check<PtG2> (points.hip)
 P_MADD_G2 = 28
 P_INV = 380 + 190 + 2 + 2 + 2                      # fq2_inv: two squares, the Fermat ladder, two products
 P_NORM_G2 = 6 + 3 + 6 + 6 + 6 + P_INV / 8          # k_g2_xyzz_to_affine_batch per point: prefix, 1 / (zz zzz), update, x, y; an inversion per 8
