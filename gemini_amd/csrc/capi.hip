@@ -2,7 +2,7 @@
 #include <cstring>
 #include <vector>
 
-#include "ctx.hpp"
+#include "groups.cuh"
 #include "host_field.hpp"
 
 namespace gm {
@@ -247,14 +247,9 @@ uint64_t put_prover(std::unique_ptr<Sumcheck> p) {
 }
 
 // implemented in msm.hip / fr.hip
-int fixed_base_generate(Context* C, const uint64_t base_affine[12], const void* d_scalars, int mont, size_t n,
-                        std::unique_ptr<Bases>& out);
-int g2_fixed_base_generate(Context* C, const uint64_t base_affine[24], const void* d_scalars, int mont, size_t n, std::unique_ptr<G2Bases>& out);
 int crs_fold(Context* C, const Crs* in, const uint64_t challenge_mont[4], Crs* out);  // ipa.hip
 int bases_precompute(Context* C, Bases* b, int c);
 void bases_free_tables(Bases* b);
-int bases_export(Context* C, const Bases* b, size_t offset, size_t n, void* out96);
-int bases_build_phi(Context* C, Bases* b);
 int sc_set_herring(Sumcheck* S, int on);
 int sc_create(Context* C, const void* f_src, size_t nf, const void* g_src, size_t ng, bool src_is_device,
               const uint64_t twist[4], uint64_t* handle, bool borrow = false);
@@ -312,6 +307,159 @@ int fr_shift_block(Context* C, FrVec* v, const uint64_t first[4], size_t nout, F
 }  // namespace gm
 
 using namespace gm;
+
+// ---- keys ----------------------------------------------------------------------------------
+// The entries that register, free, measure, download and generate a key, stated once over the group descriptions (groups.cuh;
+// the engine templates are bases.hip's).  The extern "C" names further down forward.  What a G1 key has beyond a G2 key -- GLV
+// images, window tables -- is in the two overload pairs.
+namespace {
+// Fixed-base window tables by default (gm_set_auto_tables): a registered key is resident for many MSMs -- the KZG key of a
+// prover (src/kzg/time.rs:49-72 builds a window table of its own to GENERATE the key) -- so when W x n x 96 bytes fit the
+// budget (default: 30 % of the device memory) the tables are built at registration, outside every prover span.
+int maybe_auto_tables(Context* C, Bases* b) {
+  if (!C->auto_tables || b->n < C->msm_table_min || b->n < ((size_t)1 << 17)) return GM_OK;
+  // 2^26: the pair-index field of a table entry (msm.hip: ENTRY_W_SHIFT).  Longer keys -- below 2^28 points: the key of `snark -i 26`; the provers at 2^27 / 2^28 constraints need the memory for their vectors --
+  // get tables over their first points only (bases_precompute); under memory pressure they are given back (release_spare_tables)
+  const bool prefix_only = b->n >= ((size_t)1 << 26);
+  if (prefix_only && b->n >= ((size_t)1 << 28)) return GM_OK;
+  const int c = b->n >= ((size_t)1 << 23) ? 22 : 20;
+  const size_t W = (256 + c - 1) / c;
+  const size_t bytes = (prefix_only ? (size_t)12 * 96 << 25 : W * b->n * 96) + (std::min<size_t>(b->n, (size_t)1 << 22) * 192) +
+                       (c >= 22 ? (size_t)13 * 96 << 22 : 0) + ((size_t)16 * 96 << 17);  // + the prefix tables
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return GM_OK;
+  const size_t budget = C->auto_tables_max ? C->auto_tables_max : total_b / 100 * 30;
+  size_t pooled = 0;
+  {
+    std::lock_guard<std::mutex> lk(C->pool.mu);
+    pooled = C->pool.pooled_bytes;
+  }
+  if (bytes > budget || bytes + ((size_t)2 << 30) > free_b + pooled) return GM_OK;  // no room: the plain path serves this key
+  const int rc = bases_precompute(C, b, 0);
+  return rc == GM_ENOMEM ? GM_OK : rc;
+}
+
+// after a key was generated on the device
+int after_generate(Context* C, Bases* b) {
+  const int rc = bases_build_phi(C, b);
+  return rc ? rc : maybe_auto_tables(C, b);
+}
+int after_generate(Context*, G2Bases*) { return GM_OK; }
+void free_extras(Bases* b) {
+  bases_free_tables(b);
+  if (b->phi) (void)gm::raw_free(b->phi);
+  b->phi = nullptr;
+}
+void free_extras(G2Bases*) {}
+template <class Held>
+int key_release(Held* b) {
+  free_extras(b);
+  if (b->d) GM_HIP(gm::raw_free(b->d));
+  return GM_OK;
+}
+// the last step of every constructor: `step` is what the group does to a new key; a key that fails it is released
+template <class G>
+int key_put(Context* C, std::unique_ptr<typename G::Held> b, int step, uint64_t* handle) {
+  if (step) {
+    (void)key_release(b.get());
+    return step;
+  }
+  *handle = G::put(C, std::move(b));
+  return GM_OK;
+}
+
+template <class G>
+int key_register(const void* bases, size_t base_stride, size_t n, uint64_t* handle) {
+  GM_CTX();
+  GM_CHECK(handle != nullptr && (bases != nullptr || n == 0), GM_EINVAL, "%sbases_register: null pointer", G::WHO);
+  std::unique_ptr<typename G::Held> b;
+  const int rc = bases_from_host<G>(C, bases, base_stride, n, b);
+  if (rc) return rc;
+  // no tables here: a plain registration may be one-shot (VariableBaseMSM::msm = register, one MSM, free) and a table build
+  // costs ~240 doublings per point; the key constructors (gm_g1_srs_register*, gm_g1_fixed_base_register) build them,
+  // and gm_g1_bases_precompute(handle, -1) does for a key uploaded from the host.
+  const int step = G::before_put(C, b.get());
+  return key_put<G>(C, std::move(b), step, handle);
+}
+template <class G>
+int key_free(uint64_t handle) {
+  GM_CTX();
+  std::unique_ptr<typename G::Held> b = G::take(C, handle);
+  GM_CHECK(b != nullptr, GM_EHANDLE, "%sbases_free: unknown handle %llu", G::WHO, (unsigned long long)handle);
+  return key_release(b.get());
+}
+template <class G>
+int key_len(uint64_t handle, size_t* n) {
+  GM_CTX();
+  typename G::Held* b = G::find(C, handle);
+  GM_CHECK(b != nullptr, GM_EHANDLE, "%sbases_len: unknown handle %llu", G::WHO, (unsigned long long)handle);
+  GM_CHECK(n != nullptr, GM_EINVAL, "%sbases_len: null pointer", G::WHO);
+  *n = b->n;
+  return GM_OK;
+}
+template <class G>
+int key_download(uint64_t handle, size_t offset, size_t n, void* out) {
+  GM_CTX();
+  typename G::Held* b = G::find(C, handle);
+  GM_CHECK(b != nullptr, GM_EHANDLE, "%sbases_download: unknown handle %llu", G::WHO, (unsigned long long)handle);
+  GM_CHECK(out != nullptr || n == 0, GM_EINVAL, "%sbases_download: null pointer", G::WHO);
+  GM_CHECK(offset <= b->n && n <= b->n - offset, GM_EINVAL, "%sbases_download: range [%zu, %zu + %zu) outside %zu bases", G::WHO, offset, offset, n, b->n);
+  GM_MSM_LOCK(C);
+  return bases_export<G>(C, b, offset, n, out);
+}
+// out[i] = scalars[i] * base (bases.hip: fixed_base_generate)
+template <class G>
+int key_fixed_base_register(const uint64_t* base_affine, const uint64_t* scalars, size_t n, uint64_t* handle) {
+  GM_CTX();
+  GM_CHECK(base_affine && handle && (scalars || n == 0), GM_EINVAL, "%sfixed_base_register: null pointer", G::WHO);
+  GM_CHECK(n <= SIZE_MAX / 32, GM_EINVAL, "%sfixed_base_register: %zu scalars do not fit a size_t", G::WHO, n);
+  std::unique_ptr<typename G::Held> b;
+  {
+    GM_MSM_LOCK(C);  // across the upload and the launches that read it -- and no further: the table build below takes it itself
+    DevTmp d_sc;
+    if (n) {
+      GM_HIP(dev_malloc(&d_sc.p, n * 32));
+      GM_HIP(hipMemcpyAsync(d_sc.p, scalars, n * 32, hipMemcpyHostToDevice, C->stream));
+    }
+    const int rc = fixed_base_generate<G>(C, base_affine, d_sc.p, 0, n, b);
+    if (rc) {
+      (void)hipStreamSynchronize(C->stream);  // the copy may still be in flight
+      return rc;
+    }
+  }
+  const int step = after_generate(C, b.get());
+  return key_put<G>(C, std::move(b), step, handle);
+}
+// out = base * tau^e for the exponents e of nseg segments [starts[s], starts[s] + counts[s]), back to back: the powers on the
+// device (Montgomery), then one fixed-base pass over all of them.  The plain SRS entries are the list of the one segment (0, n) and
+// so carry the segment bounds: more than 2^40 powers (or 2^39, fr_powers_at), which used to fail in the allocation, are GM_EINVAL
+template <class G>
+int key_srs_register(const char* who, const uint64_t* base_affine, const uint64_t tau[4], const size_t* starts, const size_t* counts, size_t nseg, uint64_t* handle) {
+  GM_CTX();
+  GM_CHECK(base_affine && tau && handle && (nseg == 0 || (starts && counts)), GM_EINVAL, "%s%s: null pointer", G::WHO, who);
+  size_t n = 0;
+  for (size_t s = 0; s < nseg; s++) {
+    GM_CHECK(counts[s] <= ((size_t)1 << 40) && n + counts[s] >= n, GM_EINVAL, "%s%s: segment %zu has %zu powers", G::WHO, who, s, counts[s]);
+    n += counts[s];
+  }
+  GM_CHECK(n <= SIZE_MAX / 32, GM_EINVAL, "%s%s: %zu powers do not fit a size_t", G::WHO, who, n);
+  DevTmp v;
+  if (n) GM_HIP(dev_malloc(&v.p, n * 32));
+  uint64_t tm[4];
+  gmh::Fr::from_canonical(tau).to_limbs(tm);
+  int rc = GM_OK;
+  size_t at = 0;
+  for (size_t s = 0; s < nseg && !rc; s++) {
+    rc = fr_powers_at(C, tm, starts[s], counts[s], v.u8() + at * 32);
+    at += counts[s];
+  }
+  std::unique_ptr<typename G::Held> b;
+  if (!rc) rc = fixed_base_generate<G>(C, base_affine, v.p, 1, n, b);
+  if (rc) return rc;
+  const int step = after_generate(C, b.get());
+  return key_put<G>(C, std::move(b), step, handle);
+}
+}  // namespace
 
 extern "C" {
 
@@ -825,61 +973,20 @@ int gm_set_msm_affine_levels(int levels) {
   return GM_OK;
 }
 
-// ---- bases ---------------------------------------------------------------------------------
-// Fixed-base window tables by default (gm_set_auto_tables): a registered key is resident for many MSMs -- the KZG key of a
-// prover (src/kzg/time.rs:49-72 builds a window table of its own to GENERATE the key) -- so when W x n x 96 bytes fit the
-// budget (default: 30 % of the device memory) the tables are built at registration, outside every prover span.
-static int maybe_auto_tables(Context* C, Bases* b) {
-  if (!C->auto_tables || b->n < C->msm_table_min || b->n < ((size_t)1 << 17)) return GM_OK;
-  // 2^26: the pair-index field of a table entry (msm.hip: ENTRY_W_SHIFT).  Longer keys -- below 2^28 points: the key of `snark -i 26`; the provers at 2^27 / 2^28 constraints need the memory for their vectors --
-  // get tables over their first points only (bases_precompute); under memory pressure they are given back (release_spare_tables)
-  const bool prefix_only = b->n >= ((size_t)1 << 26);
-  if (prefix_only && b->n >= ((size_t)1 << 28)) return GM_OK;
-  const int c = b->n >= ((size_t)1 << 23) ? 22 : 20;
-  const size_t W = (256 + c - 1) / c;
-  const size_t bytes = (prefix_only ? (size_t)12 * 96 << 25 : W * b->n * 96) + (std::min<size_t>(b->n, (size_t)1 << 22) * 192) +
-                       (c >= 22 ? (size_t)13 * 96 << 22 : 0) + ((size_t)16 * 96 << 17);  // + the prefix tables
-  size_t free_b = 0, total_b = 0;
-  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return GM_OK;
-  const size_t budget = C->auto_tables_max ? C->auto_tables_max : total_b / 100 * 30;
-  size_t pooled = 0;
-  {
-    std::lock_guard<std::mutex> lk(C->pool.mu);
-    pooled = C->pool.pooled_bytes;
-  }
-  if (bytes > budget || bytes + ((size_t)2 << 30) > free_b + pooled) return GM_OK;  // no room: the plain path serves this key
-  const int rc = bases_precompute(C, b, 0);
-  return rc == GM_ENOMEM ? GM_OK : rc;
+int gm_g1_bases_register(const void* bases, size_t base_stride, size_t n, uint64_t* handle) { return key_register<GrpG1>(bases, base_stride, n, handle); }
+int gm_g1_bases_free(uint64_t handle) { return key_free<GrpG1>(handle); }
+int gm_g1_bases_len(uint64_t handle, size_t* n) { return key_len<GrpG1>(handle, n); }
+int gm_g1_bases_download(uint64_t handle, size_t offset, size_t n, void* out96) { return key_download<GrpG1>(handle, offset, n, out96); }
+int gm_g1_fixed_base_register(const uint64_t base_affine[12], const uint64_t* scalars, size_t n, uint64_t* handle) {
+  return key_fixed_base_register<GrpG1>(base_affine, scalars, n, handle);
 }
-
-int gm_g1_bases_register(const void* bases, size_t base_stride, size_t n, uint64_t* handle) {
-  GM_CTX();
-  GM_CHECK(handle != nullptr && (bases != nullptr || n == 0), GM_EINVAL, "bases_register: null pointer");
-  std::unique_ptr<Bases> b;
-  int rc = bases_from_host(C, bases, base_stride, n, b);
-  if (rc) return rc;
-  if ((rc = bases_build_phi(C, b.get()))) return rc;
-  // no tables here: a plain registration may be one-shot (VariableBaseMSM::msm = register, one MSM, free) and a table build
-  // costs ~240 doublings per point; the key constructors (gm_g1_srs_register*, gm_g1_fixed_base_register) build them,
-  // and gm_g1_bases_precompute(handle, -1) does for a key uploaded from the host.
-  *handle = put_bases(std::move(b));
-  return GM_OK;
+int gm_g1_srs_register(const uint64_t base_affine[12], const uint64_t tau[4], size_t n, uint64_t* handle) {
+  const size_t start = 0;
+  return key_srs_register<GrpG1>("srs_register", base_affine, tau, &start, &n, 1, handle);
 }
-
-int gm_g1_bases_free(uint64_t handle) {
-  GM_CTX();
-  std::unique_ptr<Bases> b;
-  {
-    std::lock_guard<std::mutex> lk(C->mu);
-    auto it = C->bases.find(handle);
-    GM_CHECK(it != C->bases.end(), GM_EHANDLE, "bases_free: unknown handle %llu", (unsigned long long)handle);
-    b = std::move(it->second);
-    C->bases.erase(it);
-  }
-  bases_free_tables(b.get());
-  if (b->phi) (void)gm::raw_free(b->phi);
-  if (b->d) GM_HIP(gm::raw_free(b->d));
-  return GM_OK;
+int gm_g1_srs_register_segments(const uint64_t base_affine[12], const uint64_t tau[4], const size_t* starts, const size_t* counts, size_t nseg,
+                                uint64_t* handle) {
+  return key_srs_register<GrpG1>("srs_register_segments", base_affine, tau, starts, counts, nseg, handle);
 }
 
 int gm_g1_bases_precompute(uint64_t handle, int c) {
@@ -901,22 +1008,6 @@ int gm_g1_bases_table_info(uint64_t handle, int* c, size_t* bytes) {
     for (const auto& ts : b->extra) *bytes += (size_t)ts.W * ts.n * 96;  // prefix tables for the calls below the main table's range
   }
   return GM_OK;
-}
-
-int gm_g1_bases_len(uint64_t handle, size_t* n) {
-  GM_CTX();
-  Bases* b = find_bases(handle);
-  GM_CHECK(b != nullptr, GM_EHANDLE, "bases_len: unknown handle %llu", (unsigned long long)handle);
-  *n = b->n;
-  return GM_OK;
-}
-
-int gm_g1_bases_download(uint64_t handle, size_t offset, size_t n, void* out96) {
-  GM_CTX();
-  Bases* b = find_bases(handle);
-  GM_CHECK(b != nullptr, GM_EHANDLE, "bases_download: unknown handle %llu", (unsigned long long)handle);
-  GM_CHECK(offset + n <= b->n, GM_EINVAL, "bases_download: range [%zu, %zu) outside %zu bases", offset, offset + n, b->n);
-  return bases_export(C, b, offset, n, out96);
 }
 
 static int msm_host_scalars(Context* C, Bases* b, size_t offset, int reversed, const uint64_t* scalars, size_t n,
@@ -1116,78 +1207,6 @@ int gm_g1_sum(const uint64_t* points_jac, size_t k, uint64_t out_jac[18]) {
   gmh::G1 acc = gmh::G1::identity();
   for (size_t i = 0; i < k; i++) acc = acc.add(gmh::G1::from_limbs(points_jac + 18 * i));
   acc.normalized().to_limbs(out_jac);
-  return GM_OK;
-}
-
-int gm_g1_fixed_base_register(const uint64_t base_affine[12], const uint64_t* scalars, size_t n, uint64_t* handle) {
-  GM_CTX();
-  GM_CHECK(base_affine && handle && (scalars || n == 0), GM_EINVAL, "fixed_base_register: null pointer");
-  uint8_t* d_sc = nullptr;
-  if (n) {
-    GM_HIP(dev_malloc((void**)&d_sc, n * 32));
-    GM_HIP(hipMemcpyAsync(d_sc, scalars, n * 32, hipMemcpyHostToDevice, C->stream));
-  }
-  std::unique_ptr<Bases> b;
-  int rc = fixed_base_generate(C, base_affine, d_sc, 0, n, b);
-  if (d_sc) (void)gm::raw_free(d_sc);
-  if (rc) return rc;
-  if ((rc = bases_build_phi(C, b.get()))) return rc;
-  if ((rc = maybe_auto_tables(C, b.get()))) return rc;
-  *handle = put_bases(std::move(b));
-  return GM_OK;
-}
-
-int gm_g1_srs_register(const uint64_t base_affine[12], const uint64_t tau[4], size_t n, uint64_t* handle) {
-  GM_CTX();
-  GM_CHECK(base_affine && tau && handle, GM_EINVAL, "srs_register: null pointer");
-  // powers of tau on device (Montgomery), then fixed-base multiplication
-  auto v = std::make_unique<FrVec>();
-  v->cap = n;
-  if (n) GM_HIP(dev_malloc((void**)&v->d, n * 32));
-  gmh::Fr t = gmh::Fr::from_canonical(tau);
-  uint64_t tm[4];
-  t.to_limbs(tm);
-  int rc = fr_powers(C, tm, n, v.get());
-  std::unique_ptr<Bases> b;
-  if (!rc) rc = fixed_base_generate(C, base_affine, v->d, 1, n, b);
-  if (v->d) (void)gm::raw_free(v->d);
-  if (rc) return rc;
-  if ((rc = bases_build_phi(C, b.get()))) return rc;
-  if ((rc = maybe_auto_tables(C, b.get()))) return rc;
-  *handle = put_bases(std::move(b));
-  return GM_OK;
-}
-
-int gm_g1_srs_register_segments(const uint64_t base_affine[12], const uint64_t tau[4], const size_t* starts, const size_t* counts, size_t nseg,
-                                uint64_t* handle) {
-  GM_CTX();
-  GM_CHECK(base_affine && tau && handle && (nseg == 0 || (starts && counts)), GM_EINVAL, "srs_register_segments: null pointer");
-  size_t n = 0;
-  for (size_t s = 0; s < nseg; s++) {
-    GM_CHECK(counts[s] <= ((size_t)1 << 40) && n + counts[s] >= n, GM_EINVAL, "srs_register_segments: segment %zu has %zu powers", s, counts[s]);
-    n += counts[s];
-  }
-  // the exponents' images on device: segment s = tau^starts[s] * (1, tau, tau^2, ...), then one fixed-base pass over all of them
-  auto v = std::make_unique<FrVec>();
-  v->cap = n;
-  if (n) GM_HIP(dev_malloc((void**)&v->d, n * 32));
-  gmh::Fr t = gmh::Fr::from_canonical(tau);
-  uint64_t tm[4];
-  t.to_limbs(tm);
-  int rc = GM_OK;
-  size_t at = 0;
-  for (size_t s = 0; s < nseg && !rc; s++) {
-    rc = fr_powers_at(C, tm, starts[s], counts[s], v->d + at * 32);
-    at += counts[s];
-  }
-  std::unique_ptr<Bases> b;
-  if (!rc) rc = fixed_base_generate(C, base_affine, v->d, 1, n, b);
-  if (v->d) (void)gm::raw_free(v->d);
-  v->d = nullptr;
-  if (rc) return rc;
-  if ((rc = bases_build_phi(C, b.get()))) return rc;
-  if ((rc = maybe_auto_tables(C, b.get()))) return rc;
-  *handle = put_bases(std::move(b));
   return GM_OK;
 }
 
@@ -1839,11 +1858,6 @@ int gm_hg1_free(uint64_t handle) {
 }
 
 // ---- G2: MSM (g2msm.hip) and the herring G2Module prover ---------------------------------------------
-static G2Bases* find_g2_bases(Context* C, uint64_t h) {
-  std::lock_guard<std::mutex> lk(C->mu);
-  auto it = C->g2_bases.find(h);
-  return it == C->g2_bases.end() ? nullptr : it->second.get();
-}
 static int g2_msm_host_scalars(Context* C, const G2Bases* b, size_t offset, int reversed, const uint64_t* scalars, size_t n, uint64_t out_jac[36]) {
   int rc;
   GM_MSM_LOCK(C);  // held across the upload AND the MSM: another thread must not restage C->msm.scalars in between
@@ -1861,98 +1875,28 @@ int gm_g2_msm(const void* bases, size_t base_stride, const uint64_t* scalars, si
   if (b->d) (void)gm::raw_free(b->d);
   return rc;
 }
-int gm_g2_bases_register(const void* bases, size_t base_stride, size_t n, uint64_t* handle) {
-  GM_CTX();
-  GM_CHECK(handle != nullptr && (bases != nullptr || n == 0), GM_EINVAL, "g2_bases_register: null pointer");
-  std::unique_ptr<G2Bases> b;
-  int rc = g2_bases_from_host(C, bases, base_stride, n, b);
-  if (rc) return rc;
-  std::lock_guard<std::mutex> lk(C->mu);
-  *handle = C->next_handle++;
-  C->g2_bases[*handle] = std::move(b);
-  return GM_OK;
-}
-// the G2 twins of gm_g1_fixed_base_register / gm_g1_srs_register (g2msm.hip: g2_fixed_base_generate)
+int gm_g2_bases_register(const void* bases, size_t base_stride, size_t n, uint64_t* handle) { return key_register<GrpG2>(bases, base_stride, n, handle); }
+int gm_g2_bases_free(uint64_t handle) { return key_free<GrpG2>(handle); }
+int gm_g2_bases_len(uint64_t handle, size_t* n) { return key_len<GrpG2>(handle, n); }
+int gm_g2_bases_download(uint64_t handle, size_t offset, size_t n, void* out192) { return key_download<GrpG2>(handle, offset, n, out192); }
 int gm_g2_fixed_base_register(const uint64_t base_affine[24], const uint64_t* scalars, size_t n, uint64_t* handle) {
-  GM_CTX();
-  GM_CHECK(base_affine && handle && (scalars || n == 0), GM_EINVAL, "g2_fixed_base_register: null pointer");
-  GM_CHECK(n <= SIZE_MAX / 32, GM_EINVAL, "g2_fixed_base_register: %zu scalars do not fit a size_t", n);
-  GM_MSM_LOCK(C);  // across the upload and the launches that read it
-  uint8_t* d_sc = nullptr;
-  if (n) {
-    GM_HIP(dev_malloc((void**)&d_sc, n * 32));
-    GM_HIP(hipMemcpyAsync(d_sc, scalars, n * 32, hipMemcpyHostToDevice, C->stream));
-  }
-  std::unique_ptr<G2Bases> b;
-  int rc = g2_fixed_base_generate(C, base_affine, d_sc, 0, n, b);
-  if (d_sc) {
-    if (rc) (void)hipStreamSynchronize(C->stream);  // the copy may still be in flight
-    (void)gm::raw_free(d_sc);
-  }
-  if (rc) return rc;
-  *handle = put_in(C, C->g2_bases, std::move(b));
-  return GM_OK;
+  return key_fixed_base_register<GrpG2>(base_affine, scalars, n, handle);
 }
 int gm_g2_srs_register(const uint64_t base_affine[24], const uint64_t tau[4], size_t n, uint64_t* handle) {
-  GM_CTX();
-  GM_CHECK(base_affine && tau && handle, GM_EINVAL, "g2_srs_register: null pointer");
-  GM_CHECK(n <= SIZE_MAX / 32, GM_EINVAL, "g2_srs_register: %zu powers do not fit a size_t", n);
-  // powers of tau on the device (Montgomery), then the fixed-base multiplication
-  auto v = std::make_unique<FrVec>();
-  v->cap = n;
-  if (n) GM_HIP(dev_malloc((void**)&v->d, n * 32));
-  gmh::Fr t = gmh::Fr::from_canonical(tau);
-  uint64_t tm[4];
-  t.to_limbs(tm);
-  int rc = fr_powers(C, tm, n, v.get());
-  std::unique_ptr<G2Bases> b;
-  if (!rc) rc = g2_fixed_base_generate(C, base_affine, v->d, 1, n, b);
-  if (v->d) (void)gm::raw_free(v->d);
-  v->d = nullptr;
-  if (rc) return rc;
-  *handle = put_in(C, C->g2_bases, std::move(b));
-  return GM_OK;
-}
-int gm_g2_bases_free(uint64_t handle) {
-  GM_CTX();
-  std::unique_ptr<G2Bases> b;
-  {
-    std::lock_guard<std::mutex> lk(C->mu);
-    auto it = C->g2_bases.find(handle);
-    GM_CHECK(it != C->g2_bases.end(), GM_EHANDLE, "g2_bases_free: unknown handle %llu", (unsigned long long)handle);
-    b = std::move(it->second);
-    C->g2_bases.erase(it);
-  }
-  if (b->d) GM_HIP(gm::raw_free(b->d));
-  return GM_OK;
-}
-#define GM_G2B(var, h, who)                 \
-  G2Bases* var = find_g2_bases(C, h);       \
-  GM_CHECK(var != nullptr, GM_EHANDLE, who ": unknown G2 bases handle %llu", (unsigned long long)(h))
-int gm_g2_bases_len(uint64_t handle, size_t* n) {
-  GM_CTX();
-  GM_G2B(b, handle, "g2_bases_len");
-  GM_CHECK(n != nullptr, GM_EINVAL, "g2_bases_len: null pointer");
-  *n = b->n;
-  return GM_OK;
-}
-int gm_g2_bases_download(uint64_t handle, size_t offset, size_t n, void* out192) {
-  GM_CTX();
-  GM_G2B(b, handle, "g2_bases_download");
-  GM_CHECK(out192 != nullptr || n == 0, GM_EINVAL, "g2_bases_download: null pointer");
-  GM_CHECK(offset <= b->n && n <= b->n - offset, GM_EINVAL, "g2_bases_download: range [%zu, %zu) outside %zu bases", offset, offset + n, b->n);
-  GM_MSM_LOCK(C);
-  return g2_bases_export(C, b, offset, n, out192);
+  const size_t start = 0;
+  return key_srs_register<GrpG2>("srs_register", base_affine, tau, &start, &n, 1, handle);
 }
 int gm_g2_msm_h(uint64_t handle, size_t offset, int reversed, const uint64_t* scalars, size_t n, uint64_t out_jac[36]) {
   GM_CTX();
-  GM_G2B(b, handle, "g2_msm_h");
+  G2Bases* b = GrpG2::find(C, handle);
+  GM_CHECK(b != nullptr, GM_EHANDLE, "g2_msm_h: unknown G2 bases handle %llu", (unsigned long long)handle);
   GM_CHECK(out_jac != nullptr && (scalars != nullptr || n == 0), GM_EINVAL, "g2_msm_h: null pointer");
   return g2_msm_host_scalars(C, b, offset, reversed, scalars, n, out_jac);
 }
 int gm_g2_msm_v(uint64_t bases_handle, size_t offset, int reversed, uint64_t vec_handle, size_t voffset, size_t n, uint64_t out_jac[36]) {
   GM_CTX();
-  GM_G2B(b, bases_handle, "g2_msm_v");
+  G2Bases* b = GrpG2::find(C, bases_handle);
+  GM_CHECK(b != nullptr, GM_EHANDLE, "g2_msm_v: unknown G2 bases handle %llu", (unsigned long long)bases_handle);
   FrVec* v = find_vec(vec_handle);
   GM_CHECK(v != nullptr, GM_EHANDLE, "g2_msm_v: unknown vector handle %llu", (unsigned long long)vec_handle);
   GM_CHECK(out_jac != nullptr, GM_EINVAL, "g2_msm_v: null pointer");
@@ -1961,7 +1905,8 @@ int gm_g2_msm_v(uint64_t bases_handle, size_t offset, int reversed, uint64_t vec
 }
 int gm_g2_msm_d(uint64_t bases_handle, size_t offset, int reversed, const void* d_scalars, int mont, size_t n, uint64_t out_jac[36]) {
   GM_CTX();
-  GM_G2B(b, bases_handle, "g2_msm_d");
+  G2Bases* b = GrpG2::find(C, bases_handle);
+  GM_CHECK(b != nullptr, GM_EHANDLE, "g2_msm_d: unknown G2 bases handle %llu", (unsigned long long)bases_handle);
   GM_CHECK(out_jac != nullptr && (d_scalars != nullptr || n == 0), GM_EINVAL, "g2_msm_d: null pointer");
   return g2_msm_run(C, b, (int64_t)offset, reversed ? -1 : 1, d_scalars, mont, n, out_jac);
 }
@@ -2017,7 +1962,8 @@ int gm_pairing_multi_h(uint64_t g1_handle, size_t off1, size_t step1, uint64_t g
   GM_CTX();
   Bases* b1 = find_bases(g1_handle);
   GM_CHECK(b1 != nullptr, GM_EHANDLE, "pairing_multi_h: unknown G1 bases handle %llu", (unsigned long long)g1_handle);
-  GM_G2B(b2, g2_handle, "pairing_multi_h");
+  G2Bases* b2 = GrpG2::find(C, g2_handle);
+  GM_CHECK(b2 != nullptr, GM_EHANDLE, "pairing_multi_h: unknown G2 bases handle %llu", (unsigned long long)g2_handle);
   GM_CHECK(out_gt != nullptr, GM_EINVAL, "pairing_multi_h: null pointer");
   GM_CHECK(step1 >= 1 && step2 >= 1, GM_EINVAL, "pairing_multi_h: steps %zu / %zu must be >= 1", step1, step2);
   if (n == 0) return gm_gt_one(out_gt);
@@ -2041,7 +1987,8 @@ int gm_pairing_multi_many_h(uint64_t g1_handle, size_t off1, uint64_t g2_handle,
   GM_CTX();
   Bases* b1 = find_bases(g1_handle);
   GM_CHECK(b1 != nullptr, GM_EHANDLE, "pairing_multi_many_h: unknown G1 bases handle %llu", (unsigned long long)g1_handle);
-  GM_G2B(b2, g2_handle, "pairing_multi_many_h");
+  G2Bases* b2 = GrpG2::find(C, g2_handle);
+  GM_CHECK(b2 != nullptr, GM_EHANDLE, "pairing_multi_many_h: unknown G2 bases handle %llu", (unsigned long long)g2_handle);
   if (S == 0) return GM_OK;
   GM_CHECK(offsets != nullptr && out_gt != nullptr, GM_EINVAL, "pairing_multi_many_h: null pointer");
   GM_CHECK(offsets[0] == 0, GM_EINVAL, "pairing_multi_many_h: offsets[0] = %zu, the first product starts at 0", offsets[0]);
@@ -2172,7 +2119,8 @@ int gm_pairing_each_h(uint64_t g1_handle, size_t off1, size_t step1, uint64_t g2
   GM_CTX();
   Bases* b1 = find_bases(g1_handle);
   GM_CHECK(b1 != nullptr, GM_EHANDLE, "pairing_each_h: unknown G1 bases handle %llu", (unsigned long long)g1_handle);
-  GM_G2B(b2, g2_handle, "pairing_each_h");
+  G2Bases* b2 = GrpG2::find(C, g2_handle);
+  GM_CHECK(b2 != nullptr, GM_EHANDLE, "pairing_each_h: unknown G2 bases handle %llu", (unsigned long long)g2_handle);
   GM_CHECK(out_gt != nullptr || n == 0, GM_EINVAL, "pairing_each_h: null pointer");
   GM_CHECK(step1 >= 1 && step2 >= 1, GM_EINVAL, "pairing_each_h: steps %zu / %zu must be >= 1", step1, step2);
   if (n == 0) return GM_OK;

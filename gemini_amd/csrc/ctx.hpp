@@ -438,6 +438,13 @@ inline hipError_t raw_malloc(T** p, size_t bytes) {
 }
 hipError_t raw_free(void* p);
 hipError_t dev_malloc(void** p, size_t bytes);  // raw_malloc that gives the vector pool's freed blocks back on OOM
+struct DevTmp {  // device memory of one call, freed on every path out
+  void* p = nullptr;
+  ~DevTmp() {
+    if (p) (void)raw_free(p);
+  }
+  uint8_t* u8() const { return static_cast<uint8_t*>(p); }
+};
 // last resort of an allocation that failed twice: the PREFIX tables of every key (Bases::extra) go, the calls they served take the
 // plain path from then on.  False when nothing was freed or an MSM may be reading them (any open GM_MSM_LOCK scope).
 bool release_spare_tables(Context* C);
@@ -517,12 +524,19 @@ int msm_ceil_log2(size_t n);
 // firsts[j] (optional): call j starts at base firsts[j] instead of `first` (herring: even / odd halves of one array)
 int msm_run_batch_at(Context* C, const Bases* bases, int64_t first, int64_t step, const size_t* pair_offsets, const void* const* d_scalars,
                      int mont, const size_t* ns, size_t k, bool normalize, uint64_t* out_jac, const int64_t* firsts = nullptr);
+
+// keys of either group (bases.hip; stated once over the descriptions of groups.cuh, these are the instances the other files call)
 int bases_from_host(Context* C, const void* bases, size_t stride, size_t n, std::unique_ptr<Bases>& out);
+int g2_bases_from_host(Context* C, const void* bases, size_t stride, size_t n, std::unique_ptr<G2Bases>& out);
+int g1_pack_launch(hipStream_t st, const uint8_t* src, size_t stride, size_t n, uint8_t* dst);  // host records -> packed device records, no wait
+// n XYZZ records -> packed affine records, eight points per inversion, no wait; `out` must lie apart from `in`
+int g1_normalise_launch(hipStream_t st, const uint8_t* in, size_t n, uint8_t* out);
 // out[i] = in[2i] + s in[2i+1] over packed affine records (an odd tail folds against the identity), s at d_s8 (canonical, 8 x u32), on C->stream
 int g1_split_fold_launch(Context* C, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out);
+int g2_split_fold_launch(Context* C, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out);
 
 // S short linear combinations out[s] = sum_{offsets[s] <= t < offsets[s+1]} scalar[t] P[t] (k_g1_term_mul, k_g1_seg_sum,
-// k_xyzz_to_affine_batch): host records of `stride` bytes and canonical scalars in, S packed affine device records at *d_aff (a
+// k_normalise): host records of `stride` bytes and canonical scalars in, S packed affine device records at *d_aff (a
 // region of C->lincomb), on C->stream without a wait.  Caller holds the MSM lock and keeps the three host arrays until it has waited.
 int g1_lincomb_many_launch(Context* C, const void* points, size_t stride, const uint64_t* scalars_canonical, const size_t* offsets, size_t S, uint8_t** d_aff);
 int g1_lincomb_many_host(Context* C, const void* points, size_t stride, const uint64_t* scalars_canonical, const size_t* offsets, size_t S, uint64_t* out_jac);
@@ -532,11 +546,8 @@ int fr_stride_raw(Context* C, const uint8_t* in, size_t start, size_t stride, si
 int fr_fold_raw(Context* C, const uint8_t* f, size_t n, const uint64_t r[4], uint8_t* out);  // r is read by an asynchronous copy: the caller waits
 
 // G2 engine (g2msm.hip)
-int g2_bases_from_host(Context* C, const void* bases, size_t stride, size_t n, std::unique_ptr<G2Bases>& out);
-int g2_bases_export(Context* C, const G2Bases* b, size_t offset, size_t n, void* out192);
 int g2_msm_run(Context* C, const G2Bases* bases, int64_t first, int64_t step, const void* d_scalars, int mont, size_t n, uint64_t out_jac[36]);
 void g2_workspace_release(G2Workspace& w);
-int g2_split_fold_launch(Context* C, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out);  // as g1_split_fold_launch
 
 // pairings (pairing.hip): GT values are 72 limbs, 12 Fq in tower order, Montgomery
 int pairing_run(Context* C, const uint8_t* d_g1, int64_t first1, int64_t step1, const uint8_t* d_g2, int64_t first2, int64_t step2, size_t n, uint64_t out_gt[72]);

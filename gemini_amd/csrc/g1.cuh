@@ -62,6 +62,20 @@ GM_DEV void fqe_store(void* p, const FqE& a) { fp_store<FqParams>(p, a); }
 // ark-ff form (a * 2^384) <-> device form (a * 2^390)
 GM_DEV FqE fqe_import(const Fq& ark) { return fq_mul(ark, fq30_pack(fq30_const(Fq30Consts::CIN))); }
 GM_DEV Fq fqe_export(const FqE& dev) { return fq_mul(dev, fq30_pack(fq30_const(Fq30Consts::COUT))); }
+// Fq inversion by Fermat (a^(q-2)): one per normalised point or group of points
+GM_DEV FqE fq_inv(const FqE& a) {
+  // q - 2, little-endian 32-bit limbs
+  uint32_t e[12];
+#pragma unroll
+  for (int i = 0; i < 12; i++) e[i] = FqParams::MOD[i];
+  e[0] -= 2u;
+  FqE acc = fqe_one();
+  for (int i = 380; i >= 0; i--) {
+    acc = fq_sqr(acc);
+    if ((e[i >> 5] >> (i & 31)) & 1u) acc = fq_mul(acc, a);
+  }
+  return acc;
+}
 
 // ---- the bucket accumulator of k_acc0 lives in the product's own representation: 13 x 30-bit LOOSE limbs (field30.cuh),
 // the whole mixed addition one asm statement (gen_madd30.py).  Buckets and level-0 partials are written as 208-byte

@@ -69,23 +69,10 @@ GM_DEV Fq2 fq2_neg_canonical(const Fq2& a) {
   r.c1 = fq_neg_canonical(a.c1);
   return r;
 }
-// Fq inversion by Fermat (a^(q-2)); one per normalised point
-GM_DEV FqE g2_fq_inv(const FqE& a) {
-  uint32_t e[12];
-#pragma unroll
-  for (int i = 0; i < 12; i++) e[i] = FqParams::MOD[i];
-  e[0] -= 2u;
-  FqE acc = fqe_one();
-  for (int i = 380; i >= 0; i--) {
-    acc = fq_sqr(acc);
-    if ((e[i >> 5] >> (i & 31)) & 1u) acc = fq_mul(acc, a);
-  }
-  return acc;
-}
 // 1 / (a0 + a1 u) = (a0 - a1 u) / (a0^2 + a1^2), a non-zero
 GM_DEV Fq2 fq2_inv(const Fq2& a) {
   const FqE n = fq_add(fq_sqr(a.c0), fq_sqr(a.c1));
-  const FqE ni = g2_fq_inv(n);
+  const FqE ni = fq_inv(n);
   Fq2 r;
   r.c0 = fq_mul(a.c0, ni);
   r.c1 = fq_sub(fqe_zero(), fq_mul(a.c1, ni));
@@ -231,19 +218,6 @@ GM_DEV void g2_add(G2Xyzz& acc, const G2Xyzz& q) {
   acc.zzz = fq2_mul(fq2_mul(acc.zzz, q.zzz), ppp);
   acc.x = x3;
   acc.y = y3;
-}
-
-// (X / ZZ, Y / ZZZ) with one inversion of ZZ * ZZZ; the identity gives the all-zero record
-GM_DEV G2Affine g2_to_affine(const G2Xyzz& p) {
-  G2Affine a;
-  a.x = fq2_zero();
-  a.y = fq2_zero();
-  if (!p.is_identity()) {
-    const Fq2 ti = fq2_inv(fq2_mul(p.zz, p.zzz));
-    a.x = fq2_mul(p.x, fq2_mul(ti, p.zzz));
-    a.y = fq2_mul(p.y, fq2_mul(ti, p.zz));
-  }
-  return a;
 }
 
 // 192-byte affine / 384-byte XYZZ memory images (16-byte aligned); values at rest are fully reduced

@@ -18,8 +18,9 @@
 //                       8 x as much.  ceil((c - 1) / 3) launches instead of 2^(c-1) sequential additions per window
 //   5. host             window sums -> Jacobian, Horner over the windows (variable_base.rs:168-175), normalisation (host_field.hpp)
 //
-// Also here: the generation of a G2 key from scalars (gm_g2_fixed_base_register, gm_g2_srs_register; the `powers_of_g2` loop of
-// CommitterKey::new, src/kzg/time.rs:60-67) -- a fixed-base table of 32 x 256 multiples, one lane per scalar, batched normalisation.
+// Not here: import, export and generation of a G2 key, the G2 fold of the herring provers and the batched normalisation -- bases.hip
+// states them once for G1 and G2.  Deliberately not merged with msm.hip: k_g2_acc, k_g2_merge*, k_g2_reduce and the host composition
+// below (the G1 engine accumulates in the 30-bit loose form, with tables, GLV and batches).
 //
 // Out of scope here: fixed-base tables for the MSM, GLV, streams, batches, sharding.
 #include <algorithm>
@@ -31,30 +32,6 @@
 #include "host_field.hpp"
 
 namespace gm {
-
-// ------------------------------------------------------------------------------------------
-// bases import / export
-// ------------------------------------------------------------------------------------------
-// staging (stride >= 192, optional infinity flag at byte 192, ark-ff Montgomery form) -> packed 192-byte records in the
-// device form (g1.cuh: a * 2^390)
-__global__ void k_g2_pack_bases(const uint8_t* __restrict__ src, size_t stride, size_t n, uint8_t* __restrict__ dst) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t* s = reinterpret_cast<const uint32_t*>(src + i * stride);
-  const bool inf = stride >= 193 && src[i * stride + 192] != 0;
-  for (int e = 0; e < 4; e++) {
-    Fq v;
-#pragma unroll
-    for (int k = 0; k < 12; k++) v.l[k] = inf ? 0u : s[12 * e + k];
-    fqe_store(dst + i * G2_AFF_BYTES + 48 * e, fqe_import(v));
-  }
-}
-// device form -> ark-ff Montgomery form, 192-byte records (gm_g2_bases_download)
-__global__ void k_g2_export_bases(const uint8_t* __restrict__ src, size_t n, uint8_t* __restrict__ dst) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  for (int e = 0; e < 4; e++) fp_store<FqParams>(dst + i * G2_AFF_BYTES + 48 * e, fqe_export(fqe_load(src + i * G2_AFF_BYTES + 48 * e)));
-}
 
 // ------------------------------------------------------------------------------------------
 // k_g2_acc: chunk-per-lane accumulation of sorted entries
@@ -186,97 +163,6 @@ __global__ __launch_bounds__(64) void k_g2_reduce(const uint8_t* __restrict__ Ti
   g2_store_xyzz(Uout + ((size_t)w * Kp + s) * G2_XYZZ_BYTES, acc);
 }
 
-// herring split_fold over G2 (src/herring/time_prover.rs:72-76): out[i] = P[2i] + s * P[2i+1] (an odd tail: P[2i] alone), affine
-// out.  s: canonical scalar, 8 x u32.  One lane per output: 255-bit double-and-add, one addition, one inversion.
-__global__ __launch_bounds__(64) void k_g2_split_fold(const uint8_t* __restrict__ in, size_t n, const uint32_t* __restrict__ s8, uint8_t* __restrict__ out) {
-  const size_t m = (n + 1) / 2;
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= m) return;
-  G2Xyzz acc = G2Xyzz::identity();
-  if (2 * i + 1 < n) {
-    const G2Affine hi = g2_load_affine(in + (2 * i + 1) * G2_AFF_BYTES);
-    for (int bit = 254; bit >= 0; bit--) {
-      acc = g2_dbl(acc);
-      if ((s8[bit >> 5] >> (bit & 31)) & 1u) g2_madd(acc, hi);
-    }
-  }
-  g2_madd(acc, g2_load_affine(in + (2 * i) * G2_AFF_BYTES));
-  g2_store_affine(out + i * G2_AFF_BYTES, g2_to_affine(acc));
-}
-
-// ------------------------------------------------------------------------------------------
-// fixed-base generation: out[i] = k_i * base (gm_g2_fixed_base_register, gm_g2_srs_register) -- the twins of k_fixed_base_table,
-// k_fixed_base_mul and k_xyzz_to_affine_batch of msm.hip over Fq2.  Registers: profiles/keygen_kernel_resources.txt.
-// ------------------------------------------------------------------------------------------
-constexpr int G2_FB_BLOCK = 64;
-// table[w][d] = d * 2^(8 w) * base, one lane per (w, d): the bits of d from the top, then 8 w doublings
-__global__ __launch_bounds__(G2_FB_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_g2_fixed_base_table(const uint8_t* __restrict__ base, uint8_t* __restrict__ table) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= 32 * 256) return;
-  const uint32_t w = t >> 8, dgt = t & 255u;
-  const G2Affine b = g2_load_affine(base);
-  G2Xyzz acc = G2Xyzz::identity();
-  for (int bit = 7; bit >= 0; bit--) {
-    acc = g2_dbl(acc);
-    if ((dgt >> bit) & 1u) g2_madd(acc, b);
-  }
-  for (uint32_t k = 0; k < 8 * w; k++) acc = g2_dbl(acc);
-  g2_store_xyzz(table + (size_t)t * G2_XYZZ_BYTES, acc);
-}
-
-// one lane per scalar: at most 32 mixed additions against the affine table.  scalars canonical (mont = 0: any 256-bit value, taken as
-// that integer) or Montgomery
-__global__ __launch_bounds__(G2_FB_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_g2_fixed_base_mul(const uint32_t* __restrict__ scalars, int mont, size_t n,
-                                                                                                              const uint8_t* __restrict__ table_aff, uint8_t* __restrict__ out_xyzz) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  Fr s = fp_load<FrParams>(scalars + 8 * i);
-  if (mont) s = fp_from_mont<FrParams>(s);
-  G2Xyzz acc = G2Xyzz::identity();
-  for (int w = 0; w < 32; w++) {
-    const uint32_t dgt = (s.l[w >> 2] >> (8 * (w & 3))) & 255u;
-    if (dgt) g2_madd(acc, g2_load_affine(table_aff + ((size_t)w * 256 + dgt) * G2_AFF_BYTES));
-  }
-  g2_store_xyzz(out_xyzz + i * G2_XYZZ_BYTES, acc);  // normalised in groups by k_g2_xyzz_to_affine_batch
-}
-
-// Batched normalisation, Montgomery's trick inside a lane over Fq2: prefix products of t_k = zz_k zzz_k, ONE inversion -- in Fq, of the
-// norm (fq2_inv) -- and the back-substitution, per group of G2_NORM_K points.  Point k of the group is in[idx ? idx[i0 + k] : i0 + k];
-// identity records (zz = 0) stay out of the products and give the all-zero affine record.
-// The prefix products wait in the first 96 bytes of the group's own OUTPUT records -- record k is read back before record k + 1 is
-// written over --, not in a register array: eight Fq2 prefixes are 192 VGPRs a lane would hold across the inversion.
-constexpr int G2_NORM_K = 8;
-__global__ __launch_bounds__(G2_FB_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_g2_xyzz_to_affine_batch(const uint8_t* __restrict__ in, const uint32_t* __restrict__ idx, size_t n,
-                                                                                                                    uint8_t* out) {
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t i0 = t * G2_NORM_K;
-  if (i0 >= n) return;
-  const int m = (int)min((size_t)G2_NORM_K, n - i0);
-  Fq2 run = fq2_one();
-  for (int k = 0; k < m; k++) {
-    const uint8_t* rec = in + (size_t)(idx ? idx[i0 + k] : i0 + k) * G2_XYZZ_BYTES;
-    const Fq2 zz = fq2_load(rec + 192);
-    if (!fq2_is_zero(zz)) run = fq2_mul(run, fq2_mul(zz, fq2_load(rec + 288)));
-    fq2_store(out + (i0 + k) * G2_AFF_BYTES, run);
-  }
-  Fq2 inv = fq2_inv(run);
-  for (int k = m - 1; k >= 0; k--) {
-    const uint8_t* rec = in + (size_t)(idx ? idx[i0 + k] : i0 + k) * G2_XYZZ_BYTES;
-    const Fq2 zz = fq2_load(rec + 192);
-    G2Affine a;
-    a.x = fq2_zero();
-    a.y = fq2_zero();
-    if (!fq2_is_zero(zz)) {
-      const Fq2 zzz = fq2_load(rec + 288);
-      const Fq2 ti = k ? fq2_mul(inv, fq2_load(out + (i0 + k - 1) * G2_AFF_BYTES)) : inv;  // 1 / (zz zzz)
-      inv = fq2_mul(inv, fq2_mul(zz, zzz));
-      a.x = fq2_mul(fq2_load(rec), fq2_mul(ti, zzz));
-      a.y = fq2_mul(fq2_load(rec + 96), fq2_mul(ti, zz));
-    }
-    g2_store_affine(out + (i0 + k) * G2_AFF_BYTES, a);
-  }
-}
-
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
@@ -391,106 +277,6 @@ int g2_msm_run(Context* C, const G2Bases* bases, int64_t first, int64_t step, co
     acc = acc.add(part);
   }
   acc.normalized().to_limbs(out_jac);
-  return GM_OK;
-}
-
-// ---- bases management -----------------------------------------------------------------------
-int g2_bases_from_host(Context* C, const void* bases, size_t stride, size_t n, std::unique_ptr<G2Bases>& out) {
-  GM_CHECK(stride >= (size_t)G2_AFF_BYTES && (stride % 8) == 0, GM_EINVAL, "g2 bases: stride %zu must be >= 192 and a multiple of 8", stride);
-  auto b = std::make_unique<G2Bases>();
-  b->n = n;
-  if (n) {
-    uint8_t* stage = nullptr;
-    GM_HIP(dev_malloc((void**)&b->d, n * G2_AFF_BYTES));
-    hipError_t e = dev_malloc((void**)&stage, n * stride);
-    if (e == hipSuccess) e = hipMemcpyAsync(stage, bases, n * stride, hipMemcpyHostToDevice, C->stream);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(k_g2_pack_bases, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, C->stream, stage, stride, n, b->d);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(C->stream);
-    if (stage) (void)gm::raw_free(stage);
-    if (e != hipSuccess) {
-      (void)gm::raw_free(b->d);
-      return hip_fail(e, "g2 bases upload", __FILE__, __LINE__);
-    }
-  }
-  out = std::move(b);
-  return GM_OK;
-}
-
-int g2_bases_export(Context* C, const G2Bases* b, size_t offset, size_t n, void* out192) {
-  if (n == 0) return GM_OK;
-  uint8_t* tmp = nullptr;
-  GM_HIP(dev_malloc((void**)&tmp, n * G2_AFF_BYTES));
-  hipLaunchKernelGGL(k_g2_export_bases, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, C->stream, b->d + offset * G2_AFF_BYTES, n, tmp);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(out192, tmp, n * G2_AFF_BYTES, hipMemcpyDeviceToHost, C->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(C->stream);
-  (void)gm::raw_free(tmp);
-  return e == hipSuccess ? GM_OK : hip_fail(e, "g2 bases download", __FILE__, __LINE__);
-}
-
-// n XYZZ records (d_idx != nullptr: the records d_idx[0 .. n) of `in`) -> packed affine records, on C->stream without a wait
-int g2_normalise_launch(Context* C, const uint8_t* in, const uint32_t* d_idx, size_t n, uint8_t* out) {
-  if (n == 0) return GM_OK;
-  const size_t groups = (n + G2_NORM_K - 1) / G2_NORM_K;
-  hipLaunchKernelGGL(k_g2_xyzz_to_affine_batch, dim3((unsigned)((groups + G2_FB_BLOCK - 1) / G2_FB_BLOCK)), dim3(G2_FB_BLOCK), 0, C->stream, in, d_idx, n, out);
-  GM_HIP(hipGetLastError());
-  return GM_OK;
-}
-
-namespace {
-struct G2Tmp {  // device memory of one call, freed on every path out
-  uint8_t* p = nullptr;
-  ~G2Tmp() {
-    if (p) (void)gm::raw_free(p);
-  }
-};
-}  // namespace
-
-// out[i] = scalars[i] * base, i < n: the affine table (32 x 256 records, 1.5 MB), then slabs of at most 2^22 points -- a multiply
-// launch into an XYZZ slab and its normalisation into the key.  d_scalars: n x 32 bytes on the device, ordered on C->stream.
-int g2_fixed_base_generate(Context* C, const uint64_t base_affine[24], const void* d_scalars, int mont, size_t n, std::unique_ptr<G2Bases>& out) {
-  GM_CHECK(n <= SIZE_MAX / G2_XYZZ_BYTES, GM_EINVAL, "g2 fixed base: %zu points do not fit a size_t", n);
-  auto b = std::make_unique<G2Bases>();
-  b->n = n;
-  if (n) {
-    GM_MSM_LOCK(C);
-    G2Tmp base, stage, t_xyzz, table, xy, key;
-    const size_t T = (size_t)32 * 256;
-    GM_HIP(dev_malloc((void**)&base.p, G2_AFF_BYTES));
-    GM_HIP(dev_malloc((void**)&stage.p, G2_AFF_BYTES));
-    GM_HIP(dev_malloc((void**)&t_xyzz.p, T * G2_XYZZ_BYTES));
-    GM_HIP(dev_malloc((void**)&table.p, T * G2_AFF_BYTES));
-    GM_HIP(hipMemcpyAsync(stage.p, base_affine, G2_AFF_BYTES, hipMemcpyHostToDevice, C->stream));
-    hipLaunchKernelGGL(k_g2_pack_bases, dim3(1), dim3(64), 0, C->stream, stage.p, (size_t)G2_AFF_BYTES, (size_t)1, base.p);
-    hipLaunchKernelGGL(k_g2_fixed_base_table, dim3((unsigned)(T / G2_FB_BLOCK)), dim3(G2_FB_BLOCK), 0, C->stream, base.p, t_xyzz.p);
-    int rc = g2_normalise_launch(C, t_xyzz.p, nullptr, T, table.p);
-    if (rc) return rc;
-    const size_t slab = std::min<size_t>(n, (size_t)1 << 22);
-    GM_HIP(dev_malloc((void**)&key.p, n * G2_AFF_BYTES));
-    GM_HIP(dev_malloc((void**)&xy.p, slab * G2_XYZZ_BYTES));
-    for (size_t off = 0; off < n; off += slab) {
-      const size_t m = std::min(slab, n - off);
-      hipLaunchKernelGGL(k_g2_fixed_base_mul, dim3((unsigned)((m + G2_FB_BLOCK - 1) / G2_FB_BLOCK)), dim3(G2_FB_BLOCK), 0, C->stream,
-                         reinterpret_cast<const uint32_t*>(d_scalars) + 8 * off, mont, m, table.p, xy.p);
-      if ((rc = g2_normalise_launch(C, xy.p, nullptr, m, key.p + off * G2_AFF_BYTES))) return rc;
-    }
-    GM_HIP(hipGetLastError());
-    GM_HIP(hipStreamSynchronize(C->stream));
-    b->d = key.p;
-    key.p = nullptr;
-  }
-  out = std::move(b);
-  return GM_OK;
-}
-
-// the G2 fold of the herring provers (herring.hip): out[i] = in[2i] + s in[2i+1], s at d_s8 (canonical, 8 x u32), on C->stream
-int g2_split_fold_launch(Context* C, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out) {
-  const size_t m = (n + 1) / 2;
-  hipLaunchKernelGGL(k_g2_split_fold, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, C->stream, in, n, d_s8, out);
-  GM_HIP(hipGetLastError());
   return GM_OK;
 }
 

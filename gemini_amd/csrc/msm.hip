@@ -25,6 +25,11 @@
 //                     instead of the 2*2^(c-1) sequential additions of the CPU running sum).
 //   7. host           Horner over <= 256 bit positions on the (W x c) plane sums
 //                     (src/kzg/msm/variable_base.rs:168-175 is the window Horner).
+//
+// Keys: the window tables, the GLV images and the short linear combinations of a G1 key are here (k_table_next, k_phi_bases,
+// k_g1_term_mul, k_g1_seg_sum).  Import, export, generation from scalars, the herring fold and the batched normalisation are in
+// bases.hip, once for G1 and G2, and reached through ctx.hpp.  Deliberately not merged with G2: everything of msm_enqueue, and
+// the experiments build.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -1641,35 +1646,9 @@ __global__ __launch_bounds__(256) void k_group_sum(GroupSumJobs J) {
 }
 
 // ------------------------------------------------------------------------------------------
-// bases import / generation
+// what a G1 key has beyond its points (import, export, generation from scalars, the fold and the batched normalisation are
+// stated once for G1 and G2 in bases.hip)
 // ------------------------------------------------------------------------------------------
-// staging (stride >= 96, optional infinity flag at byte 96, ark-ff Montgomery form) -> packed 96-byte
-// records in the device form (see g1.cuh: a * 2^390)
-__global__ void k_pack_bases(const uint8_t* __restrict__ src, size_t stride, size_t n, uint8_t* __restrict__ dst) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t* s = reinterpret_cast<const uint32_t*>(src + i * stride);
-  bool inf = stride >= 97 && src[i * stride + 96] != 0;
-  Fq x, y;
-#pragma unroll
-  for (int k = 0; k < 12; k++) {
-    x.l[k] = inf ? 0u : s[k];
-    y.l[k] = inf ? 0u : s[12 + k];
-  }
-  G1Affine a;
-  a.x = fqe_import(x);
-  a.y = fqe_import(y);
-  g1_store_affine(dst + i * AFF_BYTES, a);
-}
-// device form -> ark-ff Montgomery form, 96-byte records (gm_g1_bases_download)
-__global__ void k_export_bases(const uint8_t* __restrict__ src, size_t n, uint8_t* __restrict__ dst) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  G1Affine a = g1_load_affine(src + i * AFF_BYTES);
-  fp_store<FqParams>(dst + i * AFF_BYTES, fqe_export(a.x));
-  fp_store<FqParams>(dst + i * AFF_BYTES + 48, fqe_export(a.y));
-}
-
 // phi(P) = (beta x, y): the image of every registered base under the GLV endomorphism (see glv_split)
 __global__ void k_phi_bases(const uint8_t* __restrict__ src, size_t n, uint8_t* __restrict__ dst) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1685,143 +1664,9 @@ __global__ void k_phi_bases(const uint8_t* __restrict__ src, size_t n, uint8_t* 
   g1_store_affine(dst + i * AFF_BYTES, a);  // the identity (0, 0) maps to itself
 }
 
-// out[i] = k_i * base via 32 windows of 8 bits against a (32 x 256)-entry affine table
-__global__ __launch_bounds__(256) void k_fixed_base_table(const uint8_t* __restrict__ base, uint8_t* __restrict__ table) {
-  // table[w][d] = d * 2^(8w) * base ; one thread per (w, d): double-and-add of the 13-bit... d*2^(8w)
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= 32 * 256) return;
-  const uint32_t w = t >> 8, dgt = t & 255u;
-  G1Affine b = g1_load_affine(base);
-  G1Xyzz acc = G1Xyzz::identity();
-  // scalar = dgt << (8w): process bits of dgt from the top, then 8w doublings
-  for (int bit = 7; bit >= 0; bit--) {
-    acc = xyzz_dbl(acc);
-    if ((dgt >> bit) & 1u) xyzz_madd(acc, b);
-  }
-  for (uint32_t k = 0; k < 8 * w; k++) acc = xyzz_dbl(acc);
-  g1_store_xyzz(table + (size_t)t * XYZZ_BYTES, acc);
-}
-
-// Fq inversion by Fermat (a^(q-2)); used once per generated point
-GM_DEV FqE fq_inv(const FqE& a) {
-  // q - 2, little-endian 32-bit limbs
-  uint32_t e[12];
-#pragma unroll
-  for (int i = 0; i < 12; i++) e[i] = FqParams::MOD[i];
-  e[0] -= 2u;
-  FqE acc = fqe_one();
-  for (int i = 380; i >= 0; i--) {
-    acc = fq_sqr(acc);
-    if ((e[i >> 5] >> (i & 31)) & 1u) acc = fq_mul(acc, a);
-  }
-  return acc;
-}
-
-__global__ __launch_bounds__(256) void k_xyzz_to_affine(const uint8_t* __restrict__ in, size_t n, uint8_t* __restrict__ out) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  G1Xyzz p = g1_load_xyzz(in + i * XYZZ_BYTES);
-  G1Affine a;
-  if (p.is_identity()) {
-    a.x = fqe_zero();
-    a.y = fqe_zero();
-  } else {
-    // x = X/ZZ, y = Y/ZZZ ; 1/ZZZ = inv, 1/ZZ = inv * ZZZ / ZZ ... use one inversion of ZZ*ZZZ
-    FqE t = fq_mul(p.zz, p.zzz);
-    FqE ti = fq_inv(t);
-    a.x = fq_mul(p.x, fq_mul(ti, p.zzz));
-    a.y = fq_mul(p.y, fq_mul(ti, p.zz));
-  }
-  g1_store_affine(out + i * AFF_BYTES, a);
-}
-
-// Batched normalisation: one Fermat inversion (~570 products) per NORM_K points instead of per point
-// (Montgomery's trick inside a thread: prefix products of t_k = zz_k * zzz_k, one inversion, back-substitution).
-// Identity records (zz = 0) are skipped in the products and written as the all-zero affine record.
-constexpr int NORM_K = 8;
-__global__ __launch_bounds__(256) void k_xyzz_to_affine_batch(const uint8_t* __restrict__ in, size_t n, uint8_t* __restrict__ out) {
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t i0 = t * NORM_K;
-  if (i0 >= n) return;
-  const int m = (int)min((size_t)NORM_K, n - i0);
-  FqE pre[NORM_K];
-  FqE run = fqe_one();
-  for (int k = 0; k < m; k++) {
-    const uint8_t* rec = in + (i0 + k) * XYZZ_BYTES;
-    const FqE zz = fqe_load(rec + 96);
-    if (!fq_is_zero(zz)) run = fq_mul(run, fq_mul(zz, fqe_load(rec + 144)));
-    pre[k] = run;
-  }
-  FqE inv = fq_inv(run);
-  for (int k = m - 1; k >= 0; k--) {
-    const uint8_t* rec = in + (i0 + k) * XYZZ_BYTES;
-    const FqE zz = fqe_load(rec + 96);
-    G1Affine a;
-    if (fq_is_zero(zz)) {
-      a.x = fqe_zero();
-      a.y = fqe_zero();
-    } else {
-      const FqE zzz = fqe_load(rec + 144);
-      const FqE ti = k ? fq_mul(inv, pre[k - 1]) : inv;  // 1 / (zz * zzz)
-      inv = fq_mul(inv, fq_mul(zz, zzz));
-      a.x = fq_mul(fqe_load(rec), fq_mul(ti, zzz));
-      a.y = fq_mul(fqe_load(rec + 48), fq_mul(ti, zz));
-    }
-    g1_store_affine(out + (i0 + k) * AFF_BYTES, a);
-  }
-}
-
-// scalars canonical (mont = 0) or Montgomery; table in XYZZ; output affine
-__global__ __launch_bounds__(256) void k_fixed_base_mul(const uint32_t* __restrict__ scalars, int mont, size_t n,
-                                                        const uint8_t* __restrict__ table_aff, uint8_t* __restrict__ out_xyzz) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  Fr s = fp_load<FrParams>(scalars + 8 * i);
-  if (mont) s = fp_from_mont<FrParams>(s);
-  G1Xyzz acc = G1Xyzz::identity();
-  for (int w = 0; w < 32; w++) {
-    uint32_t dgt = (s.l[w >> 2] >> (8 * (w & 3))) & 255u;
-    if (dgt) {
-      G1Affine p = g1_load_affine(table_aff + ((size_t)w * 256 + dgt) * AFF_BYTES);
-      xyzz_madd(acc, p);
-    }
-  }
-  g1_store_xyzz(out_xyzz + i * XYZZ_BYTES, acc);  // normalised in batches by k_xyzz_to_affine_batch
-}
-
-// herring split_fold over G1 (src/herring/time_prover.rs:72-76): out[i] = P[2i] + s * P[2i+1], affine out.
-// s: canonical scalar, 8 x u32.  One thread per output: double-and-add, then one inversion.
-__global__ __launch_bounds__(256) void k_g1_split_fold(const uint8_t* __restrict__ in, size_t n, const uint32_t* __restrict__ s8,
-                                                       uint8_t* __restrict__ out) {
-  const size_t m = (n + 1) / 2;
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= m) return;
-  G1Affine lo = g1_load_affine(in + (2 * i) * AFF_BYTES);
-  G1Xyzz acc = G1Xyzz::identity();
-  if (2 * i + 1 < n) {
-    G1Affine hi = g1_load_affine(in + (2 * i + 1) * AFF_BYTES);
-    for (int bit = 254; bit >= 0; bit--) {
-      acc = xyzz_dbl(acc);
-      if ((s8[bit >> 5] >> (bit & 31)) & 1u) xyzz_madd(acc, hi);
-    }
-  }
-  xyzz_madd(acc, lo);
-  G1Affine a;
-  if (acc.is_identity()) {
-    a.x = fqe_zero();
-    a.y = fqe_zero();
-  } else {
-    FqE t = fq_mul(acc.zz, acc.zzz);
-    FqE ti = fq_inv(t);
-    a.x = fq_mul(acc.x, fq_mul(ti, acc.zzz));
-    a.y = fq_mul(acc.y, fq_mul(ti, acc.zz));
-  }
-  g1_store_affine(out + i * AFF_BYTES, a);
-}
-
 // ---- many short linear combinations (gm_g1_lincomb_many, the batched KZG checks): segments of tens of terms, thousands of them.
 // One lane per TERM makes the multiple (the latency of the call: ~255 doublings and ~128 additions, whatever the number of terms up
-// to one wave per SIMD), then one lane per SEGMENT adds its terms up, and k_xyzz_to_affine_batch normalises the sums.  Three
+// to one wave per SIMD), then one lane per SEGMENT adds its terms up, and k_normalise (bases.hip) normalises the sums.  Three
 // launches for any number of segments.
 __global__ __launch_bounds__(256) void k_g1_term_mul(const uint8_t* __restrict__ points, const uint32_t* __restrict__ scalars, size_t nterms,
                                                      uint8_t* __restrict__ out_xyzz) {
@@ -1849,7 +1694,7 @@ __global__ __launch_bounds__(256) void k_table_next(const uint8_t* __restrict__ 
   G1Affine p = g1_load_affine(prev + i * AFF_BYTES);
   G1Xyzz acc = G1Xyzz::from_affine(p);
   for (int k = 0; k < c; k++) acc = xyzz_dbl(acc);
-  g1_store_xyzz(next_xyzz + i * XYZZ_BYTES, acc);  // normalised in batches by k_xyzz_to_affine_batch
+  g1_store_xyzz(next_xyzz + i * XYZZ_BYTES, acc);  // normalised in batches by k_normalise (bases.hip)
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3285,26 +3130,6 @@ int msm_sort_plain(Context* C, MsmWorkspace& ws, hipStream_t st, const void* d_s
 }
 
 // ---- bases management -----------------------------------------------------------------------
-int bases_from_host(Context* C, const void* bases, size_t stride, size_t n, std::unique_ptr<Bases>& out) {
-  GM_CHECK(stride >= 96 && (stride % 8) == 0, GM_EINVAL, "bases: stride %zu must be >= 96 and a multiple of 8", stride);
-  auto b = std::make_unique<Bases>();
-  b->n = n;
-  if (n) {
-    GM_HIP(dev_malloc((void**)&b->d, n * AFF_BYTES));
-    {
-      uint8_t* stage = nullptr;
-      GM_HIP(dev_malloc((void**)&stage, n * stride));
-      GM_HIP(hipMemcpyAsync(stage, bases, n * stride, hipMemcpyHostToDevice, C->stream));
-      hipLaunchKernelGGL(k_pack_bases, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, C->stream, stage, stride, n, b->d);
-      GM_HIP(hipStreamSynchronize(C->stream));
-      GM_HIP(gm::raw_free(stage));
-    }
-    GM_HIP(hipStreamSynchronize(C->stream));
-  }
-  out = std::move(b);
-  return GM_OK;
-}
-
 // gm_g1_bases_register / fixed_base_register / srs_register, when gm_set_msm_glv(1) is in force (off by default:
 // measured below): the GLV images next to the bases (one product per point, +96 bytes per point).  Calls on bases
 // without them take the one-string path.
@@ -3327,40 +3152,6 @@ int bases_build_phi(Context* C, Bases* b) {
   GM_HIP(hipStreamSynchronize(C->stream));
   return GM_OK;
 #endif
-}
-
-int bases_export(Context* C, const Bases* b, size_t offset, size_t n, void* out96) {
-  if (n == 0) return GM_OK;
-  uint8_t* tmp = nullptr;
-  GM_HIP(dev_malloc((void**)&tmp, n * AFF_BYTES));
-  hipLaunchKernelGGL(k_export_bases, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, C->stream, b->d + offset * AFF_BYTES, n, tmp);
-  GM_HIP(hipGetLastError());
-  GM_HIP(hipMemcpyAsync(out96, tmp, n * AFF_BYTES, hipMemcpyDeviceToHost, C->stream));
-  GM_HIP(hipStreamSynchronize(C->stream));
-  GM_HIP(gm::raw_free(tmp));
-  return GM_OK;
-}
-
-// fixed-base table (affine, 32 x 256 entries) for `base`
-static int build_fixed_table(Context* C, const uint64_t base_affine[12], uint8_t** table_aff) {
-  uint8_t *d_base = nullptr, *t_xyzz = nullptr;
-  GM_HIP(dev_malloc((void**)&d_base, AFF_BYTES));
-  GM_HIP(dev_malloc((void**)&t_xyzz, (size_t)32 * 256 * XYZZ_BYTES));
-  GM_HIP(dev_malloc((void**)table_aff, (size_t)32 * 256 * AFF_BYTES));
-  {
-    uint8_t* stage = nullptr;
-    GM_HIP(dev_malloc((void**)&stage, AFF_BYTES));
-    GM_HIP(hipMemcpyAsync(stage, base_affine, AFF_BYTES, hipMemcpyHostToDevice, C->stream));
-    hipLaunchKernelGGL(k_pack_bases, dim3(1), dim3(64), 0, C->stream, stage, (size_t)AFF_BYTES, (size_t)1, d_base);
-    GM_HIP(hipStreamSynchronize(C->stream));
-    GM_HIP(gm::raw_free(stage));
-  }
-  hipLaunchKernelGGL(k_fixed_base_table, dim3(32), dim3(256), 0, C->stream, d_base, t_xyzz);
-  hipLaunchKernelGGL(k_xyzz_to_affine, dim3(32), dim3(256), 0, C->stream, t_xyzz, (size_t)32 * 256, *table_aff);
-  GM_HIP(hipStreamSynchronize(C->stream));
-  GM_HIP(gm::raw_free(d_base));
-  GM_HIP(gm::raw_free(t_xyzz));
-  return GM_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3420,7 +3211,8 @@ static int msm_stream_flush(Context* C, MsmStream* S) {
     step = S->step;
     S->next_base += step * (int64_t)m;
   } else {
-    hipLaunchKernelGGL(k_pack_bases, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, S->copy, sl.raw, S->stride, m, sl.packed);
+    const int rc = g1_pack_launch(S->copy, sl.raw, S->stride, m, sl.packed);
+    if (rc) return rc;
     own.d = sl.packed;
     own.n = m;
   }
@@ -3536,14 +3328,6 @@ int msm_stream_finalize(Context* C, MsmStream* S, uint64_t out_jac[18], size_t* 
   return rc;
 }
 
-// the G1 fold of the herring provers (herring.hip): out[i] = in[2i] + s in[2i+1], s at d_s8 (canonical, 8 x u32), on C->stream
-int g1_split_fold_launch(Context* C, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out) {
-  const size_t m = (n + 1) / 2;
-  hipLaunchKernelGGL(k_g1_split_fold, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, C->stream, in, n, d_s8, out);
-  GM_HIP(hipGetLastError());
-  return GM_OK;
-}
-
 // table[w * n + i] = 2^(c w) * d[i], w < ceil(256 / c); row 0 is a copy of d
 // ---- gm_g1_lincomb_many ------------------------------------------------------------------------
 int g1_lincomb_many_launch(Context* C, const void* points, size_t stride, const uint64_t* scalars_canonical, const size_t* offsets, size_t S, uint8_t** d_aff) {
@@ -3567,7 +3351,7 @@ int g1_lincomb_many_launch(Context* C, const void* points, size_t stride, const 
   if (T) {
     GM_HIP(hipMemcpyAsync(w + o_raw, points, T * stride, hipMemcpyHostToDevice, st));
     GM_HIP(hipMemcpyAsync(w + o_sc, scalars_canonical, T * 32, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_pack_bases, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, w + o_raw, stride, T, w + o_pts);
+    if ((rc = g1_pack_launch(st, w + o_raw, stride, T, w + o_pts))) return rc;
     C->prof.begin(PROF_DIGITS, st);  // the stages a pairing does not use, so that one call reports all its kernels: term, sum, normalise
     hipLaunchKernelGGL(k_g1_term_mul, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, w + o_pts, reinterpret_cast<const uint32_t*>(w + o_sc), T, w + o_terms);
     C->prof.end(PROF_DIGITS, st);
@@ -3576,9 +3360,9 @@ int g1_lincomb_many_launch(Context* C, const void* points, size_t stride, const 
   hipLaunchKernelGGL(k_g1_seg_sum, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, w + o_terms, reinterpret_cast<const unsigned long long*>(w + o_off), S, w + o_sums);
   C->prof.end(PROF_SCAN, st);
   C->prof.begin(PROF_SCATTER, st);
-  hipLaunchKernelGGL(k_xyzz_to_affine_batch, dim3((unsigned)(((S + NORM_K - 1) / NORM_K + 255) / 256)), dim3(256), 0, st, w + o_sums, S, w + o_aff);
+  rc = g1_normalise_launch(st, w + o_sums, S, w + o_aff);  // o_aff lies behind o_sums: apart, as the kernel needs
   C->prof.end(PROF_SCATTER, st);
-  GM_HIP(hipGetLastError());
+  if (rc) return rc;  // (of any launch above: the error waits for the first one who asks)
   *d_aff = w + o_aff;
   return GM_OK;
 }
@@ -3606,7 +3390,7 @@ static int build_window_table(Context* C, const uint8_t* d, size_t n, int c, uin
   uint8_t* t = nullptr;
   GM_HIP(dev_malloc((void**)&t, (size_t)W * n * AFF_BYTES));
   GM_HIP(hipMemcpyAsync(t, d, n * AFF_BYTES, hipMemcpyDeviceToDevice, C->stream));
-  // one slab of XYZZ results at a time (192 B per point), normalised NORM_K points per inversion
+  // one slab of XYZZ results at a time (192 B per point), normalised eight points per inversion
   const size_t slab = std::min<size_t>(n, (size_t)1 << 22);
   uint8_t* xy = nullptr;
   {
@@ -3614,18 +3398,18 @@ static int build_window_table(Context* C, const uint8_t* d, size_t n, int c, uin
     if (e != hipSuccess) (void)gm::raw_free(t);
     GM_HIP(e);
   }
-  for (int w = 0; w + 1 < W; w++)
-    for (size_t off = 0; off < n; off += slab) {
+  int rc = GM_OK;
+  for (int w = 0; w + 1 < W && !rc; w++)
+    for (size_t off = 0; off < n && !rc; off += slab) {
       const size_t m = std::min(slab, n - off);
       hipLaunchKernelGGL(k_table_next, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, C->stream,
                          t + ((size_t)w * n + off) * AFF_BYTES, xy, m, c);
-      hipLaunchKernelGGL(k_xyzz_to_affine_batch, dim3((unsigned)(((m + NORM_K - 1) / NORM_K + 255) / 256)), dim3(256), 0, C->stream, xy, m,
-                         t + ((size_t)(w + 1) * n + off) * AFF_BYTES);
+      rc = g1_normalise_launch(C->stream, xy, m, t + ((size_t)(w + 1) * n + off) * AFF_BYTES);  // the slab into the next row: apart
     }
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipStreamSynchronize(C->stream);
+  const hipError_t e = hipStreamSynchronize(C->stream);
   (void)gm::raw_free(xy);
-  if (e != hipSuccess) (void)gm::raw_free(t);
+  if (rc || e != hipSuccess) (void)gm::raw_free(t);
+  if (rc) return rc;
   GM_HIP(e);
   *out = t;
   return GM_OK;
@@ -3701,34 +3485,6 @@ int bases_build_prefix_sets(Context* C, Bases* b) {
   static const int small_c = getenv("GM_SMALL_TABLE_C") ? atoi(getenv("GM_SMALL_TABLE_C")) : 16;
   static const int small_min_log = getenv("GM_SMALL_TABLE_MIN") ? atoi(getenv("GM_SMALL_TABLE_MIN")) : 11;
   if (small_c >= 8 && small_c <= 20 && (rc = add_set(small_c, (size_t)1 << 17, (size_t)1 << small_min_log, (size_t)1 << 17))) return rc;
-  return GM_OK;
-}
-
-int fixed_base_generate(Context* C, const uint64_t base_affine[12], const void* d_scalars, int mont, size_t n,
-                        std::unique_ptr<Bases>& out) {
-  auto b = std::make_unique<Bases>();
-  b->n = n;
-  if (n) {
-    uint8_t* table = nullptr;
-    int rc = build_fixed_table(C, base_affine, &table);
-    if (rc) return rc;
-    GM_HIP(dev_malloc((void**)&b->d, n * AFF_BYTES));
-    const size_t slab = std::min<size_t>(n, (size_t)1 << 22);
-    uint8_t* xy = nullptr;
-    GM_HIP(dev_malloc((void**)&xy, slab * XYZZ_BYTES));
-    for (size_t off = 0; off < n; off += slab) {
-      const size_t m = std::min(slab, n - off);
-      hipLaunchKernelGGL(k_fixed_base_mul, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, C->stream,
-                         reinterpret_cast<const uint32_t*>(d_scalars) + 8 * off, mont, m, table, xy);
-      hipLaunchKernelGGL(k_xyzz_to_affine_batch, dim3((unsigned)(((m + NORM_K - 1) / NORM_K + 255) / 256)), dim3(256), 0, C->stream, xy, m,
-                         b->d + off * AFF_BYTES);
-    }
-    GM_HIP(hipGetLastError());
-    GM_HIP(hipStreamSynchronize(C->stream));
-    GM_HIP(gm::raw_free(xy));
-    GM_HIP(gm::raw_free(table));
-  }
-  out = std::move(b);
   return GM_OK;
 }
 

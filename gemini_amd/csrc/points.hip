@@ -25,13 +25,10 @@
 #include <cstring>
 #include <vector>
 
-#include "ctx.hpp"
-#include "g2.cuh"
+#include "groups.cuh"
 #include "host_field.hpp"
 
 namespace gm {
-
-int bases_build_phi(Context* C, Bases* b);  // msm.hip
 
 constexpr int PT_BLOCK = 256;      // G1 kernels: amdgpu_waves_per_eu(2, 2) -- 96 / 160 bytes of scratch buy the second wave, 1.27 x against one wave (profiles/point_check.md)
 constexpr int PT_G2_BLOCK = 64;    // G2: one wave per SIMD, the whole register file (as k_g2_acc)
@@ -294,99 +291,28 @@ GM_DEV G2Xyzz pt_g2_clear(const G2Affine& P, uint8_t* slot) {
   return acc;
 }
 
-// The slots idx[0 .. n) -> packed affine records, Montgomery's trick over eight points a lane; the prefix products wait in the
-// group's own output records (k_g2_xyzz_to_affine_batch, g2msm.hip, is the same over Fq2).  No slot holds the identity.
-constexpr int PT_NORM_K = 8;
-__global__ __launch_bounds__(PT_BLOCK) void k_g1_gather_affine(const uint8_t* __restrict__ slots, const uint32_t* __restrict__ idx, size_t n, uint8_t* out) {
-  const size_t t = (size_t)blockIdx.x * PT_BLOCK + threadIdx.x;
-  const size_t i0 = t * PT_NORM_K;
-  if (i0 >= n) return;
-  const int m = (int)min((size_t)PT_NORM_K, n - i0);
-  FqE run = fqe_one();
-  for (int k = 0; k < m; k++) {
-    const uint8_t* rec = slots + (size_t)idx[i0 + k] * 192;
-    run = fq_mul(run, fq_mul(fqe_load(rec + 96), fqe_load(rec + 144)));
-    fqe_store(out + (i0 + k) * 96, run);
-  }
-  FqE inv = g2_fq_inv(run);
-  for (int k = m - 1; k >= 0; k--) {
-    const uint8_t* rec = slots + (size_t)idx[i0 + k] * 192;
-    const FqE zz = fqe_load(rec + 96), zzz = fqe_load(rec + 144);
-    const FqE ti = k ? fq_mul(inv, fqe_load(out + (i0 + k - 1) * 96)) : inv;  // 1 / (zz zzz)
-    inv = fq_mul(inv, fq_mul(zz, zzz));
-    G1Affine a;
-    a.x = fq_mul(fqe_load(rec), fq_mul(ti, zzz));
-    a.y = fq_mul(fqe_load(rec + 48), fq_mul(ti, zz));
-    g1_store_affine(out + (i0 + k) * 96, a);
-  }
-}
-
-static int g1_normalise_launch(Context* C, const uint8_t* in, const uint32_t* d_idx, size_t n, uint8_t* out) {
-  const size_t groups = (n + PT_NORM_K - 1) / PT_NORM_K;
-  hipLaunchKernelGGL(k_g1_gather_affine, dim3((unsigned)((groups + PT_BLOCK - 1) / PT_BLOCK)), dim3(PT_BLOCK), 0, C->stream, in, d_idx, n, out);
-  GM_HIP(hipGetLastError());
-  return GM_OK;
-}
-int g2_normalise_launch(Context* C, const uint8_t* in, const uint32_t* d_idx, size_t n, uint8_t* out);  // g2msm.hip
-
 // ---- the two groups ------------------------------------------------------------------------------------------------------------
-// What the kernels and the entries below need to know of a group, by name: the types, the launch shape, the record sizes, and the
-// functions above that differ between the groups; the only arithmetic stated here is the curve's right-hand side.  A coordinate is
-// NC elements of Fq, c0 first; el() / parts() pass between an element and its NC components in the device form.  The host members
-// are the handle table, the step between decoding a key and registering it, and the two figures candidates_run needs.
-struct PtG1 {
-  using El = FqE;
-  using Affine = G1Affine;
-  using Xyzz = G1Xyzz;
-  using Held = Bases;  // what a handle names
-  static constexpr const char* NAME = "g1";
-  static constexpr int NC = 1, BLOCK = PT_BLOCK, WAVES = 2;
-  static constexpr size_t AFF_BYTES = 96, XYZZ_BYTES = 192;
-  static GM_DEV El zero() { return fqe_zero(); }
-  static GM_DEV El el(const FqE* c) { return c[0]; }
-  static GM_DEV void parts(const El& a, FqE* c) { c[0] = a; }
-  static GM_DEV El neg(const El& a) { return fq_neg_canonical(a); }
+// What the kernels and the entries below need to know of a group beyond groups.cuh, by name: the launch shape of the point
+// kernels and the functions above that differ between the groups; the only arithmetic stated here is the curve's right-hand
+// side.  The host members are the two figures candidates_run needs.
+struct PtG1 : GrpG1 {
+  static constexpr int BLOCK = PT_BLOCK, WAVES = 2;
   static GM_DEV El curve_rhs(const El& x) { return fq_add(fq_mul(fq_sqr(x), x), pt_four()); }  // x^3 + 4
   static GM_DEV El sqrt(const El& a, bool* is_square) {
     const El r = pt_sqrt_candidate(a);
     *is_square = fq_sqr(r) == a;
     return r;
   }
-  static GM_DEV Affine load_affine(const void* p) { return g1_load_affine(p); }
-  static GM_DEV void store_affine(void* p, const Affine& a) { g1_store_affine(p, a); }
-  static GM_DEV void store_xyzz(void* p, const Xyzz& a) { g1_store_xyzz(p, a); }
   static GM_DEV uint8_t status(const Affine& P, bool check_curve) { return pt_g1_status(P, check_curve); }
   static GM_DEV Xyzz clear(const Affine& P, uint8_t*) {  // [1 - x] P = [|x|] P + P
     Xyzz T = pt_g1_mul_x(P);
     xyzz_madd(T, P);
     return T;
   }
-  static Held* find(Context*, uint64_t h) { return find_bases(h); }
-  static uint64_t put(Context*, std::unique_ptr<Held> b) { return put_bases(std::move(b)); }  // as gm_g1_bases_register: no tables
-  static int before_put(Context* C, Held* b) { return bases_build_phi(C, b); }
   static size_t cand_piece(size_t want) { return want / 2 * 5 + 64; }  // candidates to read for `want` points: a little over 1 / p
-  static int normalise(Context* C, const uint8_t* in, const uint32_t* d_idx, size_t n, uint8_t* out) { return g1_normalise_launch(C, in, d_idx, n, out); }
 };
-struct PtG2 {
-  using El = Fq2;
-  using Affine = G2Affine;
-  using Xyzz = G2Xyzz;
-  using Held = G2Bases;
-  static constexpr const char* NAME = "g2";
-  static constexpr int NC = 2, BLOCK = PT_G2_BLOCK, WAVES = 1;
-  static constexpr size_t AFF_BYTES = G2_AFF_BYTES, XYZZ_BYTES = G2_XYZZ_BYTES;
-  static GM_DEV El zero() { return fq2_zero(); }
-  static GM_DEV El el(const FqE* c) {
-    El r;
-    r.c0 = c[0];
-    r.c1 = c[1];
-    return r;
-  }
-  static GM_DEV void parts(const El& a, FqE* c) {
-    c[0] = a.c0;
-    c[1] = a.c1;
-  }
-  static GM_DEV El neg(const El& a) { return fq2_neg_canonical(a); }
+struct PtG2 : GrpG2 {
+  static constexpr int BLOCK = PT_G2_BLOCK, WAVES = 1;
   static GM_DEV El curve_rhs(const El& x) {  // x^3 + 4 (1 + u)
     El r = fq2_mul(fq2_sqr(x), x);
     r.c0 = fq_add(r.c0, pt_four());
@@ -394,16 +320,9 @@ struct PtG2 {
     return r;
   }
   static GM_DEV El sqrt(const El& a, bool* is_square) { return pt_fq2_sqrt(a, is_square); }
-  static GM_DEV Affine load_affine(const void* p) { return g2_load_affine(p); }
-  static GM_DEV void store_affine(void* p, const Affine& a) { g2_store_affine(p, a); }
-  static GM_DEV void store_xyzz(void* p, const Xyzz& a) { g2_store_xyzz(p, a); }
   static GM_DEV uint8_t status(const Affine& P, bool check_curve) { return pt_g2_status(P, check_curve); }
   static GM_DEV Xyzz clear(const Affine& P, uint8_t* slot) { return pt_g2_clear(P, slot); }
-  static Held* find(Context* C, uint64_t h) { return find_in(C, C->g2_bases, h); }
-  static uint64_t put(Context* C, std::unique_ptr<Held> b) { return put_in(C, C->g2_bases, std::move(b)); }
-  static int before_put(Context*, Held*) { return GM_OK; }
   static size_t cand_piece(size_t want) { return want / 4 * 13 + 64; }
-  static int normalise(Context* C, const uint8_t* in, const uint32_t* d_idx, size_t n, uint8_t* out) { return g2_normalise_launch(C, in, d_idx, n, out); }
 };
 
 // NC canonical integers < q  <->  an element in the device form
@@ -671,13 +590,6 @@ __global__ __launch_bounds__(G::BLOCK) __attribute__((amdgpu_waves_per_eu(G::WAV
 // ------------------------------------------------------------------------------------------
 namespace {
 
-struct DevTmp {  // freed on every path out
-  void* p = nullptr;
-  ~DevTmp() {
-    if (p) (void)raw_free(p);
-  }
-};
-
 // status bytes (n, padded to 16) followed by one u32 per block
 struct Report {
   DevTmp buf;
@@ -869,7 +781,7 @@ int candidates_run(Context* C, const uint8_t* cand, size_t m, size_t n, uint8_t*
       if (!good.empty()) {
         uint8_t* dst = static_cast<uint8_t*>(out.p) + have * asz;
         if (good.size() != c) GM_HIP(hipMemcpyAsync(idx, good.data(), good.size() * 4, hipMemcpyHostToDevice, C->stream));  // else idx holds them already
-        int rc = G::normalise(C, slots, idx, good.size(), dst);
+        int rc = normalise_launch<typename G::Grp>(C->stream, slots, idx, good.size(), dst);  // the slots into the key: apart
         if (rc) return rc;
         GM_HIP(hipStreamSynchronize(C->stream));  // idx, the slots and the host lists are rewritten from here on
         have += good.size();
@@ -1024,7 +936,7 @@ __global__ __launch_bounds__(DBG_BLOCK) void k_debug_fq(int op, const uint32_t* 
   else if (op == FQ_OP_NEG) r = fq_neg_canonical(a);
   else if (op == FQ_OP_IMPORT) r = fqe_import(a);
   else if (op == FQ_OP_EXPORT) r = fqe_export(a);
-  else if (op == FQ_OP_INV) r = g2_fq_inv(a);
+  else if (op == FQ_OP_INV) r = fq_inv(a);
   else if (op == FQ_OP_RAW_GE_Q) r.l[0] = pt_raw_ge_q(a) ? 1u : 0u;
   else r = fq30_pack(fq30_unpack(a));
   if (live) dbg_store_fq(out + i * 12, r);
@@ -1155,7 +1067,7 @@ __global__ __launch_bounds__(DBG_BLOCK) void k_debug_g2(int op, const uint32_t* 
   } else if (op == G2_OP_DBL_AFFINE) {
     r = g2_dbl_affine(pa);
   } else {
-    const G2Affine a = g2_to_affine(P);
+    const G2Affine a = grp_to_affine<GrpG2>(P);
     r.x = a.x; r.y = a.y; r.zz = fq2_zero(); r.zzz = fq2_zero();
   }
   if (live) {

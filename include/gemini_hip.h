@@ -1220,7 +1220,7 @@ int gm_debug_fq2_sqrt(const uint64_t* a_mont, size_t n, uint64_t* root_mont, uin
  * of the function (canonical where it requires that; loose values normalised and below 2^386).  b is read only by the ops that take
  * a second operand and may be null otherwise.  n = 0 gives GM_OK; an unknown op or a null pointer with n > 0 GM_EINVAL.
  *   gm_debug_fq_op     n x 12 words.  0 fq_mul  1 fq_sqr  2 fq_add  3 fq_sub  4 fq_dbl  5 fq_neg_canonical  6 fqe_import  7 fqe_export
- *                      8 g2_fq_inv (0 gives 0)  9 pt_raw_ge_q (0 / 1 in word 0, the others 0; the ONLY op that takes words >= q)
+ *                      8 fq_inv (0 gives 0)      9 pt_raw_ge_q (0 / 1 in word 0, the others 0; the ONLY op that takes words >= q)
  *                      10 fq30_pack(fq30_unpack(a))
  *   gm_debug_fq30_op   n x 13 limbs.  0 fq30_mul_asm  1 fq30_sqr_asm  2 fq30_mul (plain C)  3 fq30_loose_to_canonical (12 words and a
  *                      zero)  4 fq30_canonical_tail alone (a < 2 q)
@@ -1229,7 +1229,7 @@ int gm_debug_fq2_sqrt(const uint64_t* a_mont, size_t n, uint64_t* root_mont, uin
  *                      3 xyzz_dbl_affine (of the affine point in a's first 24 words)  4 g1_store_xyzz30 then g1_load_xyzz30.
  *                      out: n x 48, the four coordinates as the function leaves them.
  *   gm_debug_g2_op     the same over Fq2: a n x 96.  0 g2_madd (b: n x 48)  1 g2_add (b: n x 96)  2 g2_dbl  3 g2_dbl_affine
- *                      4 g2_to_affine (x | y in the first 48 words of out, zeros behind)
+ *                      4 grp_to_affine<GrpG2> (x | y in the first 48 words of out, zeros behind)
  *   gm_debug_acc30_op  the two statements of the bucket accumulator, under the hot kernel's launch attributes.  acc: n x 52 loose
  *                      limbs (the 208-byte record; X < 7 q, Y, ZZ, ZZZ < 2 q; ZZ == 0 exactly marks the identity).  0 g1_madd30_asm:
  *                      other n x 24 canonical words (an affine point, not the identity), neg n x u32 (!= 0 adds the negative)
@@ -1251,7 +1251,7 @@ int gm_debug_acc30_op(int op, const uint32_t* acc, const uint32_t* other, const 
 int gm_g1_powers_check(uint64_t handle, size_t offset, size_t n, const uint64_t g2_affine[24], const uint64_t tau_g2_affine[24],
                        const uint64_t rho_mont[4], int* ok);
 
-/* ---- key generation: G2 fixed-base keys, points without a known logarithm, Crs operations (g2msm.hip, points.hip, ipa.hip) --------
+/* ---- key generation: G2 fixed-base keys, points without a known logarithm, Crs operations (bases.hip, points.hip, ipa.hip) --------
  * The G2 twins of gm_g1_fixed_base_register / gm_g1_srs_register: out[i] = scalars[i] * base, resp. tau^i * base, i < n, through a
  * table of 32 windows x 256 affine multiples of the base, one lane per scalar (at most 32 mixed additions over Fq2), normalised by
  * Montgomery's trick over Fq2 -- one Fq inversion per 8 points -- in slabs of at most 2^22 points.  base_affine: a 192-byte record

@@ -122,7 +122,7 @@ assert all(0 <= v < 1 << 384 for _, v in RAW_GE_Q)
 
 
 def fq_inv_expected(a: int) -> int:
-    """g2_fq_inv: a^(q - 2) in the field, i.e. the inverse, and 0 for 0 (Fermat's ladder multiplies 0 in at its first step)"""
+    """fq_inv: a^(q - 2) in the field, i.e. the inverse, and 0 for 0 (Fermat's ladder multiplies 0 in at its first step)"""
     return dev(pow(val(a), Q - 2, Q))
 
 

@@ -134,7 +134,7 @@ def test_fq_square_is_the_product_with_itself(gm, fq_unary):
 
 
 def test_fq_inverse(gm):
-    """g2_fq_inv is Fermat's a^(q - 2): the inverse, and 0 for 0 (the ladder multiplies the operand in at its first step and
+    """fq_inv is Fermat's a^(q - 2): the inverse, and 0 for 0 (the ladder multiplies the operand in at its first step and
     0 stays 0) -- 0, 1, q - 1 and the rest of the list, a partial second block"""
     names = [n for n, _ in fc.FQ]
     a = D.rows_words(fc.FQ_VALUES)

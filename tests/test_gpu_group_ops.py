@@ -186,7 +186,7 @@ def test_g2_doublings_and_to_affine(gm, n):
     zero2 = ((0, 0), (0, 0))
     aff = g2_rows([(zero2 if c["B"] is None else (fc.f2d(c["B"][0]), fc.f2d(c["B"][1]))) + ((3, 0), (5, 0)) for c in cases])
     check_g2(D.g2_op(D.G2_DBL_AFFINE, aff), [g2_ref.add(c["B"], c["B"]) for c in cases], cases)
-    # g2_to_affine: the affine coordinates themselves, bit for bit; the identity is the all-zero record
+    # grp_to_affine<GrpG2>: the affine coordinates themselves, bit for bit; the identity is the all-zero record
     want = g2_rows([(zero2 if p is None else (fc.f2d(p[0]), fc.f2d(p[1]))) + zero2 for p in P])
     assert (D.g2_op(D.G2_TO_AFFINE, acc) == want).all()
 

@@ -1,9 +1,10 @@
-"""Key generation on the device: gm_g2_fixed_base_register / gm_g2_srs_register against gemini_amd/g2.py's integers,
-gm_g1_bases_from_candidates / gm_g2_bases_from_candidates point for point against tests/keygen_ref.py, and the Crs operations
+"""Key generation on the device: gm_g1_/gm_g2_fixed_base_register and gm_g1_/gm_g2_srs_register against the integers of
+oracle/pyref.py and gemini_amd/g2.py, the register -> download round trip of both groups, gm_g1_bases_from_candidates / gm_g2_bases_from_candidates point for point against tests/keygen_ref.py, and the Crs operations
 (gm_crs_truncate, gm_crs_halve, gm_crs_fold, gm_crs_to_bases) against the exponents of a Crs.from_scalars.
 
-Shapes: the normalisation kernels take 8 points a lane and 64 lanes a block, the multiply one lane a scalar -- n = 7, 8, 9 sit
-below, at and above a group, 257 above a block of the multiply and 2^12 + 3 spans 9 blocks of the normalisation with an odd tail.
+Shapes: the normalisation kernel takes 8 points a lane and 64 (G2) or 256 (G1) lanes a block, the multiply and the fold one lane a
+scalar or an output -- n = 7, 8, 9 sit below, at and above a group, 257 above a block of the multiply of either group, 514 folds
+to 257 outputs, and 2^12 + 3 spans 9 blocks of the G2 normalisation with an odd tail.
 The candidate streams are read in pieces (points.hip: cand_piece); the junk prefix of test_pieces makes the call take several.
 """
 import ctypes as C
@@ -22,6 +23,7 @@ from tests import points_ref as pr
 pytestmark = pytest.mark.gpu
 
 GM_EINVAL = -1
+GM_EHANDLE = -3
 Q, R = pr.Q, pr.R
 assert R == R_MOD
 LABEL = b"gemini-tests"
@@ -139,6 +141,116 @@ def test_fixed_base_g2_other_base_and_misuse(gm):
     assert lib.gm_g2_fixed_base_register(gm.capi.ptr(rec), None, C.c_size_t(1), C.byref(h)) == GM_EINVAL
     assert lib.gm_g2_fixed_base_register(gm.capi.ptr(rec), gm.capi.ptr(one), C.c_size_t(1), None) == GM_EINVAL
     assert lib.gm_g2_srs_register(gm.capi.ptr(rec), None, C.c_size_t(1), C.byref(h)) == GM_EINVAL
+
+
+# ---- fixed base G1: the mirror of the above, against oracle/pyref.py ---------------------------------------------------------------
+def g1_points_sum(pts):
+    return functools.reduce(P.g1_add, pts, None)
+
+
+@pytest.mark.parametrize("n", [0, 1, 7, 8, 9, 257])
+def test_fixed_base_g1(gm, n):
+    """gm_g1_fixed_base_register against pyref.g1_mul: every point for n <= 9; at 257 the same spots as G2 and the sum of all outputs"""
+    sc = fixed_base_scalars(n)
+    b = gm.G1Bases.fixed_base(g1_gen_record(), canon(sc))
+    assert b.handle != 0 and len(b) == n
+    ln = C.c_size_t(99)
+    gm.capi.check(gm.capi.load().gm_g1_bases_len(C.c_uint64(b.handle), C.byref(ln)))
+    assert ln.value == n
+    rec = b.download()
+    pts = g1_records_to_points(rec)
+    spots = range(n) if n <= 9 else [0, 1, 2, 3, 4, 5, 7, 8, 63, 64, 248, 254, 255, 256]
+    for i in spots:
+        assert pts[i] == P.g1_mul(P.G1_GEN, sc[i] % R), (i, hex(sc[i]))
+    if n:
+        assert not rec[0].any()  # a zero scalar: the all-zero identity record
+        assert g1_points_sum(pts) == P.g1_mul(P.G1_GEN, sum(sc) % R)
+    b.free()
+
+
+def test_srs_g1_against_integers(gm):
+    b = gm.G1Bases.srs(g1_gen_record(), canon([TAU]), 9)
+    assert g1_records_to_points(b.download()) == [P.g1_mul(P.G1_GEN, pow(TAU, i, R)) for i in range(9)]
+    b.free()
+    e = gm.G1Bases.srs(g1_gen_record(), canon([TAU]), 0)
+    assert e.handle != 0 and len(e.download()) == 0
+    e.free()
+
+
+# ---- both groups: what a description (groups.cuh) tells apart, by number --------------------------------------------------------------
+GROUPS = {
+    1: dict(cls="G1Bases", words=12, gen=g1_gen_record, point=lambda k: P.g1_mul(P.G1_GEN, k), record=pr.g1_record, points=g1_records_to_points),
+    2: dict(cls="G2Bases", words=24, gen=g2_gen_record, point=lambda k: G2.mul(G2.generator(), k), record=pr.g2_record, points=g2_affine_to_points),
+}
+
+
+@pytest.mark.parametrize("group", [1, 2])
+def test_normalisation_with_identities_at_every_position(gm, group):
+    """n = 17 is two full groups of the batched normalisation and one point: zero scalars -- identity records among the XYZZ results --
+    at the first and the last place of a group, in a group of their own and next to ordinary points; then every scalar zero (the
+    product that is inverted is the empty one)"""
+    g = GROUPS[group]
+    sc = [k + 2 for k in range(17)]
+    for i in (0, 7, 8, 15, 16):
+        sc[i] = 0
+    b = getattr(gm, g["cls"]).fixed_base(g["gen"](), canon(sc))
+    rec = b.download()
+    assert g["points"](rec) == [g["point"](k) if k else None for k in sc]
+    assert [i for i in range(17) if not rec[i].any()] == [0, 7, 8, 15, 16]
+    b.free()
+    z = getattr(gm, g["cls"]).fixed_base(g["gen"](), canon([0] * 17))
+    assert z.download().shape == (17, g["words"]) and not z.download().any()
+    z.free()
+
+
+@pytest.mark.parametrize("flagged", [False, True])
+@pytest.mark.parametrize("n", [1, 257])
+@pytest.mark.parametrize("group", [1, 2])
+def test_register_download_round_trip(gm, group, n, flagged):
+    """records of the plain stride (96 / 192 bytes) and of the flagged one (104 / 200: the infinity flag behind the coordinates) come
+    back limb for limb; a row whose flag is set comes back all-zero whatever its coordinates hold"""
+    g = GROUPS[group]
+    w = g["words"]
+    plain = np.array([g["record"](g["point"](k + 1)) for k in range(n)], dtype=np.uint64)
+    rec, want = plain, plain.copy()
+    if flagged:
+        rec = np.zeros((n, w + 1), dtype=np.uint64)
+        rec[:, :w] = plain
+        for i in ({0} if n == 1 else {1, n - 2}):  # two rows, each between unflagged neighbours; the single row of n = 1
+            rec[i, w] = 1
+            want[i] = 0
+    b = getattr(gm, g["cls"]).register(rec)
+    got = b.download()
+    assert got.shape == (n, w) and (got == want).all()
+    if n > 1:
+        assert (b.download(offset=n - 2, n=2) == want[n - 2:]).all()
+    b.free()
+
+
+def test_bases_misuse(gm):
+    """a range that overflows, a null length pointer; a handle of one group is unknown to the other group's entries, which free nothing"""
+    lib = gm.capi.load()
+    b1 = gm.G1Bases.fixed_base(g1_gen_record(), canon([1, 2, 3]))
+    b2 = gm.G2Bases.fixed_base(g2_gen_record(), canon([1, 2, 3]))
+    out = np.zeros((3, 24), dtype=np.uint64)
+    ln = C.c_size_t(0)
+    ops = {1: (lib.gm_g1_bases_free, lib.gm_g1_bases_len, lib.gm_g1_bases_download), 2: (lib.gm_g2_bases_free, lib.gm_g2_bases_len, lib.gm_g2_bases_download)}
+    for mine, other, b in ((1, 2, b1), (2, 1, b2)):
+        free, length, download = ops[mine]
+        h = C.c_uint64(b.handle)
+        assert download(h, C.c_size_t(2**64 - 1), C.c_size_t(2), gm.capi.ptr(out)) == GM_EINVAL
+        assert download(h, C.c_size_t(2), C.c_size_t(2), gm.capi.ptr(out)) == GM_EINVAL
+        assert download(h, C.c_size_t(0), C.c_size_t(1), None) == GM_EINVAL
+        assert length(h, None) == GM_EINVAL
+        o_free, o_length, o_download = ops[other]
+        assert o_length(h, C.byref(ln)) == GM_EHANDLE
+        assert o_download(h, C.c_size_t(0), C.c_size_t(1), gm.capi.ptr(out)) == GM_EHANDLE
+        assert o_free(h) == GM_EHANDLE
+        gm.capi.check(length(h, C.byref(ln)))  # still there
+        assert ln.value == 3 and len(b.download()) == 3
+    b1.free()
+    b2.free()
+    assert lib.gm_g1_bases_free(C.c_uint64(b1.handle)) == GM_EHANDLE and lib.gm_g2_bases_free(C.c_uint64(b2.handle)) == GM_EHANDLE
 
 
 # ---- SRS ---------------------------------------------------------------------------------------------------------------------------
@@ -398,8 +510,10 @@ def crs_points(crs):
     return out
 
 
-@pytest.mark.parametrize("n", [1, 2, 5, 8])
+@pytest.mark.parametrize("n", [1, 2, 3, 5, 8, 514])
 def test_crs_fold_against_integers(gm, n):
+    """n = 514 folds to 257 outputs, past a 256-lane block of the G1 fold and into the fifth 64-lane block of the G2 fold: there the outputs
+    at the block edges and the sum of all outputs are checked against the exponents, not every point"""
     a, b = scalars(50 + n, n), scalars(60 + n, n)
     if n >= 5:
         a[3], b[2] = 0, 0  # identities among the points
@@ -412,14 +526,23 @@ def test_crs_fold_against_integers(gm, n):
     assert (folded.n1, folded.n2) == (m, m) and folded.handle != crs.handle
     fold_exp = lambda v: [(v[2 * i] + (c * v[2 * i + 1] if 2 * i + 1 < n else 0)) % R for i in range(m)]  # noqa: E731
     g1s, g2s = crs_points(folded)
-    assert g1s == [pr.g1_mul_raw(pr.G1_GEN, e) for e in fold_exp(a)]
-    assert g2s == [G2.mul(G2.generator(), e) for e in fold_exp(b)]
+    spots = range(m) if n <= 8 else [0, 63, 64, 255, 256]
+    assert [g1s[i] for i in spots] == [pr.g1_mul_raw(pr.G1_GEN, fold_exp(a)[i]) for i in spots]
+    assert [g2s[i] for i in spots] == [G2.mul(G2.generator(), fold_exp(b)[i]) for i in spots]
+    if n > 8:
+        assert g1_points_sum(g1s) == P.g1_mul(P.G1_GEN, sum(fold_exp(a)) % R)
+        b1, b2 = folded.bases()
+        assert g2_records_sum(gm, b2.download()) == G2.mul(G2.generator(), sum(fold_exp(b)) % R)
+        b1.free()
+        b2.free()
     # the input is the caller's, unchanged
     assert (crs.n1, crs.n2) == (n, n)
     after = (crs.commit_g1(w), crs.commit_g2(w))
     assert (before[0] == after[0]).all() and (before[1] == after[1]).all()
     g1s, g2s = crs_points(crs)
-    assert g1s == [pr.g1_mul_raw(pr.G1_GEN, e) for e in a] and g2s == [G2.mul(G2.generator(), e) for e in b]
+    spots = range(n) if n <= 8 else [0, 1, 127, 128, 511, 512, 513]
+    assert [g1s[i] for i in spots] == [pr.g1_mul_raw(pr.G1_GEN, a[i]) for i in spots]
+    assert [g2s[i] for i in spots] == [G2.mul(G2.generator(), b[i]) for i in spots]
     folded.free()
     crs.free()
 

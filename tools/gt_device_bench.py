@@ -51,7 +51,7 @@ def pow_products(e: int) -> int:
 
 def fq_products():
     """Fq products per lane, counted from the kernels as written (gt.cuh, pairing.hip)"""
-    fq_inv = 381 + bin(Q - 2).count("1")          # g2_fq_inv: a squaring per bit, a product per set bit
+    fq_inv = 381 + bin(Q - 2).count("1")          # fq_inv (g1.cuh): a squaring per bit, a product per set bit
     fq2_inv = 2 + fq_inv + 2
     fq6_inv = 3 * (2 + 3) + 9 + fq2_inv + 9
     fq12_inv = 2 * 18 + fq6_inv + 2 * 18

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Key generation on the device (profiles/keygen.md, profiles/keygen_bench.jsonl): gm_g2_fixed_base_register, gm_g2_srs_register,
-gm_g1_bases_from_candidates and gm_g2_bases_from_candidates at 2^16 and 2^20 produced points, gm_crs_fold at 2^14 points.
+"""Key generation on the device (profiles/keygen.md, profiles/keygen_bench.jsonl): gm_g1_/gm_g2_fixed_base_register,
+gm_g1_/gm_g2_srs_register, gm_g1_bases_from_candidates and gm_g2_bases_from_candidates at 2^16 and 2^20 produced points,
+gm_g1_bases_precompute (the window tables, c = 20) on the 2^20 key, gm_crs_fold at 2^14 points.
 
   call time   host clock around the C call (each ends in a stream synchronise): one warm-up, then the median of `--calls` with min
               and max.  A call includes the upload of its scalars / candidates from pageable host memory and the allocation of the
@@ -38,14 +39,14 @@ TAU = 0x2F4E6D8C0B1A39587766554433221100FFEEDDCCBBAA9988776655443322110F % G2.R_
 P_CHECK_G2 = 1674                                  # k_pt_check<PtG2> (points.hip)
 P_MADD_G2 = 28
 P_INV = 380 + 190 + 2 + 2 + 2                      # fq2_inv: two squares, the Fermat ladder, two products
-P_NORM_G2 = 6 + 3 + 6 + 6 + 6 + P_INV / 8          # k_g2_xyzz_to_affine_batch per point: prefix, 1 / (zz zzz), update, x, y; an inversion per 8
+P_NORM_G2 = 6 + 3 + 6 + 6 + 6 + P_INV / 8          # k_normalise<GrpG2> (bases.hip) per point: prefix, 1 / (zz zzz), update, x, y; an inversion per 8
 P_FIXED_G2 = 31 * P_MADD_G2 + P_NORM_G2            # 32 non-zero digits: the first lands in an empty accumulator
 P_ROOT_G1, P_ROOT_G2 = 5 + 606, 9 + 1221           # candidate -> curve point (rules 1 and 2)
 P_CLEAR_G1 = 63 * 9 + 6 * 10                       # [|x|] P + P
 P_CLEAR_G2 = 2 * 63 * 24 + 6 * 28 + 5 * 37 + 135   # two ladders and the tail (points.hip: pt_g2_clear)
-P_NORM_G1 = 2 + 1 + 2 + 2 + 2 + (380 + 190) / 8    # k_g1_gather_affine per point
-P_FOLD_G1 = 255 * 9 + 127 * 10 + 10 + 575          # k_g1_split_fold per output: the ladder of an average scalar, one addition, one inversion
-P_FOLD_G2 = 255 * 24 + 127 * 28 + 28 + P_INV + 15  # k_g2_split_fold
+P_NORM_G1 = 2 + 1 + 2 + 2 + 2 + (380 + 190) / 8    # k_normalise<GrpG1> per point
+P_FOLD_G1 = 255 * 9 + 127 * 10 + 10 + 575          # k_split_fold<GrpG1> per output: the ladder of an average scalar, one addition, one inversion
+P_FOLD_G2 = 255 * 24 + 127 * 28 + 28 + P_INV + 15  # k_split_fold<GrpG2>
 
 
 def timed(fn, calls, after=None):
@@ -130,6 +131,13 @@ def main():
         return h1.value
 
     emit(what="gm_g2_fixed_base_register_one_point", **timed(fixed_one, a.calls, free_g2))
+    g1rec = g1_generator_mont()
+
+    def fixed_one_g1():
+        gm.capi.check(lib.gm_g1_fixed_base_register(gm.capi.ptr(g1rec), gm.capi.ptr(one), C.c_size_t(1), C.byref(h1)))
+        return h1.value
+
+    emit(what="gm_g1_fixed_base_register_one_point", **timed(fixed_one_g1, a.calls, free_g1))
 
     for logn in a.logn:
         n = 1 << logn
@@ -147,6 +155,21 @@ def main():
 
         emit(what="gm_g2_fixed_base_register", logn=logn, products_per_point=round(P_FIXED_G2, 1), **timed(fixed, a.calls, free_g2))
         emit(what="gm_g2_srs_register", logn=logn, products_per_point=round(P_FIXED_G2, 1), **timed(srs, a.calls, free_g2))
+
+        def fixed_g1():  # (the automatic window tables are off, above: the call is the generation alone)
+            gm.capi.check(lib.gm_g1_fixed_base_register(gm.capi.ptr(g1rec), gm.capi.ptr(sc), C.c_size_t(n), C.byref(h)))
+            return h.value
+
+        def srs_g1():
+            gm.capi.check(lib.gm_g1_srs_register(gm.capi.ptr(g1rec), gm.capi.ptr(tau), C.c_size_t(n), C.byref(h)))
+            return h.value
+
+        emit(what="gm_g1_fixed_base_register", logn=logn, **timed(fixed_g1, a.calls, free_g1))
+        emit(what="gm_g1_srs_register", logn=logn, **timed(srs_g1, a.calls, free_g1))
+        if logn == 20:  # 12 rows of 2^20 doublings-by-20 and their normalisation (msm.hip: build_window_table)
+            key1 = gm.G1Bases.fixed_base(g1rec, sc)
+            emit(what="gm_g1_bases_precompute", logn=logn, c=20, **timed(lambda: key1.precompute(20), a.calls))
+            key1.free()
 
         # the yardsticks, on a generated key
         key = gm.G2Bases.fixed_base(g2rec, sc)

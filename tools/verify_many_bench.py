@@ -33,9 +33,9 @@ from oracle import pyref as P  # noqa: E402
 E = 0x1D2C3B4A59687766554433221100FFEE % P.R_MOD
 TAU = 0x0123456789ABCDEF0FEDCBA987654321 % P.R_MOD
 # the profiler stages the batched path records (gemini_amd/csrc/msm.hip: g1_lincomb_many_launch, pairing.hip: pairing_products)
-STAGES = {0: "k_g1_term_mul", 1: "k_g1_seg_sum", 2: "k_xyzz_to_affine_batch", 3: "k_miller_seg", 5: "k_gt_final_exp"}
+STAGES = {0: "k_g1_term_mul", 1: "k_g1_seg_sum", 2: "k_normalise", 3: "k_miller_seg", 5: "k_gt_final_exp"}
 # what one batched KZG call enqueues, whatever S is (products of at most 64 pairs need no k_gt_reduce_seg level)
-LAUNCHES = ["k_pack_bases", "k_g1_term_mul", "k_g1_seg_sum", "k_xyzz_to_affine_batch", "k_miller_seg", "k_gt_final_exp", "k_gt_export"]
+LAUNCHES = ["k_pack_bases", "k_g1_term_mul", "k_g1_seg_sum", "k_normalise", "k_miller_seg", "k_gt_final_exp", "k_gt_export"]
 COPIES_IN, COPIES_OUT, WAITS = 5, 1, 1  # offsets, points, scalars, pair table, segment table; the S results; one stream wait
 
 
