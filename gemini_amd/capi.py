@@ -43,6 +43,7 @@ SYMBOLS = [
     "gm_hp_new", "gm_hp_round", "gm_hp_fold", "gm_hp_rounds", "gm_hp_final", "gm_hp_free",
     "gm_gt_multi_pow", "gm_hgt_new", "gm_hgt_round", "gm_hgt_fold", "gm_hgt_rounds", "gm_hgt_final", "gm_hgt_free",
     "gm_gt_final_exp_many", "gm_pairing_each", "gm_pairing_each_h", "gm_gt_check", "gm_hgt_check", "gm_ipa_check_gt", "gm_debug_gt_op",
+    "gm_debug_gt_op2", "gm_debug_miller_step", "gm_debug_miller_each",
     "gm_transcript_new", "gm_transcript_free", "gm_transcript_append_message", "gm_transcript_challenge_bytes",
     "gm_transcript_append_fr", "gm_transcript_append_g1", "gm_transcript_set_g1_encoding", "gm_transcript_challenge_fr", "gm_sumcheck_prove", "gm_sumcheck_prove_batch",
     "gm_dist_init_hook", "gm_dist_rccl_unique_id", "gm_dist_init_rccl", "gm_dist_init_shm", "gm_dist_init_rccl_node", "gm_dist_finalize", "gm_dist_abort", "gm_dist_info", "gm_dist_allgather_host",

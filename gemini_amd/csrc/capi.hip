@@ -2149,6 +2149,24 @@ int gm_debug_gt_op(int op, const uint64_t* in, size_t n, uint64_t* out) {
   if (n == 0) return GM_OK;
   return gt_debug_op(C, op, in, n, out);
 }
+int gm_debug_gt_op2(int op, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out) {
+  GM_CTX();
+  GM_CHECK((a != nullptr && out != nullptr) || n == 0, GM_EINVAL, "debug_gt_op2: null pointer");
+  if (n == 0) return GM_OK;
+  return gt_debug_op2(C, op, a, b, n, out);
+}
+int gm_debug_miller_step(int op, const uint64_t* in, size_t n, uint64_t* out) {
+  GM_CTX();
+  GM_CHECK((in != nullptr && out != nullptr) || n == 0, GM_EINVAL, "debug_miller_step: null pointer");
+  if (n == 0) return GM_OK;
+  return miller_debug_step(C, op, in, n, out);
+}
+int gm_debug_miller_each(const void* g1, size_t g1_stride, const void* g2, size_t g2_stride, size_t n, uint64_t* out) {
+  GM_CTX();
+  GM_CHECK((g1 != nullptr && g2 != nullptr && out != nullptr) || n == 0, GM_EINVAL, "debug_miller_each: null pointer");
+  if (n == 0) return GM_OK;
+  return miller_debug_each(C, g1, g1_stride, g2, g2_stride, n, out);
+}
 
 // ---- herring's inner-product argument: Crs, Vrs, InnerProductProof (ipa.hip) --------------------------------
 #define GM_IPA_FIND(var, table, h, who, what)  \

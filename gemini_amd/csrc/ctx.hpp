@@ -601,6 +601,10 @@ int pairing_each_host(Context* C, const void* g1, size_t stride1, const void* g2
 int gt_check_run(Context* C, const uint8_t* d_src, int host_form, size_t n, uint8_t* status_or_null, size_t* first_bad, int* ok);
 int gt_check_host(Context* C, const uint64_t* x, size_t n, uint8_t* status_or_null, size_t* first_bad, int* ok);
 int gt_debug_op(Context* C, int op, const uint64_t* in, size_t n, uint64_t* out);
+// test aids for the Miller-loop half: one tower function, one step, one raw Miller value per lane
+int gt_debug_op2(Context* C, int op, const uint64_t* a, const uint64_t* b_or_null, size_t n, uint64_t* out);
+int miller_debug_step(Context* C, int op, const uint64_t* in, size_t n, uint64_t* out);
+int miller_debug_each(Context* C, const void* g1, size_t stride1, const void* g2, size_t stride2, size_t n, uint64_t* out);
 
 // herring module provers (herring.hip).  f / g are host arrays: Fr vectors in Montgomery form (the stride is ignored) or point
 // records of f_stride / g_stride bytes; messages and final foldings have the module's limb counts (include/gemini_hip.h).

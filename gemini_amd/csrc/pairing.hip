@@ -450,6 +450,77 @@ __global__ __launch_bounds__(PAIR_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1
   if (i < n) fq12_store(out + i * GT_BYTES, r);
 }
 
+// gm_debug_gt_op2: ONE of the Miller-loop functions of gt.cuh per lane, over device records a and b (b is read by the ops that
+// take a second operand only).  The Fq6 ops run on both halves (c0 with c0, c1 with c1), the Fq2 ops on each of the six Fq2 slots;
+// a line (l0, l1, l4) is the first three Fq2 slots of b, an Fq scalar the c0 of b's slot.
+enum {
+  GT_OP2_MUL = 0, GT_OP2_SQR = 1, GT_OP2_CONJ = 2, GT_OP2_MUL_014 = 3, GT_OP2_FQ6_MUL = 4, GT_OP2_FQ6_MUL_V = 5, GT_OP2_FQ6_MUL_01 = 6,
+  GT_OP2_FQ6_MUL_1 = 7, GT_OP2_FQ2_MUL_XI = 8, GT_OP2_FQ2_MUL12 = 9, GT_OP2_FQ2_MUL_FQ = 10, GT_OP2_FQ2_CONJ = 11, GT_OP2_END = 12
+};
+static bool gt_op2_is_binary(int op) {
+  return op == GT_OP2_MUL || op == GT_OP2_MUL_014 || op == GT_OP2_FQ6_MUL || op == GT_OP2_FQ6_MUL_01 || op == GT_OP2_FQ6_MUL_1 || op == GT_OP2_FQ2_MUL_FQ;
+}
+__global__ __launch_bounds__(PAIR_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_gt_debug_op2(int op, const uint8_t* a_in, const uint8_t* b_in, size_t n, uint8_t* out) {
+  const size_t i = (size_t)blockIdx.x * PAIR_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const Fq12 a = fq12_load(a_in + i * GT_BYTES);
+  const Fq12 b = b_in ? fq12_load(b_in + i * GT_BYTES) : fq12_one();
+  const Fq2* as = reinterpret_cast<const Fq2*>(&a);  // 6 Fq2 back to back, tower order
+  const Fq2* bs = reinterpret_cast<const Fq2*>(&b);
+  Fq12 r;
+  Fq2* rs = reinterpret_cast<Fq2*>(&r);
+  if (op == GT_OP2_MUL) {
+    r = fq12_mul(a, b);
+  } else if (op == GT_OP2_SQR) {
+    r = fq12_sqr(a);
+  } else if (op == GT_OP2_CONJ) {
+    r = fq12_conj(a);
+  } else if (op == GT_OP2_MUL_014) {
+    r = fq12_mul_014(a, bs[0], bs[1], bs[2]);
+  } else if (op == GT_OP2_FQ6_MUL) {
+    r.c0 = fq6_mul(a.c0, b.c0);
+    r.c1 = fq6_mul(a.c1, b.c1);
+  } else if (op == GT_OP2_FQ6_MUL_V) {
+    r.c0 = fq6_mul_v(a.c0);
+    r.c1 = fq6_mul_v(a.c1);
+  } else if (op == GT_OP2_FQ6_MUL_01) {
+    r.c0 = fq6_mul_01(a.c0, bs[0], bs[1]);
+    r.c1 = fq6_mul_01(a.c1, bs[0], bs[1]);
+  } else if (op == GT_OP2_FQ6_MUL_1) {
+    r.c0 = fq6_mul_1(a.c0, bs[0]);
+    r.c1 = fq6_mul_1(a.c1, bs[0]);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 6; k++)
+      rs[k] = op == GT_OP2_FQ2_MUL_XI ? fq2_mul_xi(as[k]) : op == GT_OP2_FQ2_MUL12 ? fq2_mul12(as[k]) : op == GT_OP2_FQ2_MUL_FQ ? fq2_mul_fq(as[k], bs[k].c0) : fq2_conj(as[k]);
+  }
+  fq12_store(out + i * GT_BYTES, r);
+}
+
+// gm_debug_miller_step: ONE step of the Miller loop per lane.  A record of 576 bytes in: T (X | Y | Z, any Z), Q (x | y), P (x | y, two
+// field elements as they are: the steps only multiply by them); out: the new T (X | Y | Z) and the line (l0 | l1 | l4).
+enum { MILLER_OP_DBL = 0, MILLER_OP_ADD = 1 };
+static_assert(3 * 96 + G2_AFF_BYTES + G1_AFF_BYTES == GT_BYTES, "T | Q | P is one GT record");
+__global__ __launch_bounds__(PAIR_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_miller_debug_step(int op, const uint8_t* in, size_t n, uint8_t* out) {
+  const size_t i = (size_t)blockIdx.x * PAIR_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const uint8_t* p = in + i * GT_BYTES;
+  G2Proj T;
+  T.x = fq2_load(p);
+  T.y = fq2_load(p + 96);
+  T.z = fq2_load(p + 192);
+  const G2Affine Q = g2_load_affine(p + 288);
+  const G1Affine P = g1_load_affine(p + 288 + G2_AFF_BYTES);
+  const Line l = op == MILLER_OP_DBL ? miller_dbl_step(T, P) : miller_add_step(T, Q, P);
+  uint8_t* o = out + i * GT_BYTES;
+  fq2_store(o, T.x);
+  fq2_store(o + 96, T.y);
+  fq2_store(o + 192, T.z);
+  fq2_store(o + 288, l.l0);
+  fq2_store(o + 384, l.l1);
+  fq2_store(o + 480, l.l4);
+}
+
 // ---- the segmented form: S independent products per launch ------------------------------------------------------------------
 // Segment s owns the lanes [start, start + count) of a level and writes its partials from index `out` on, one per block it touches.
 // The host (seg_levels) lays the segments out so that one of at most PAIR_BLOCK lanes never crosses a block; lanes between two
@@ -1059,6 +1130,57 @@ int gt_debug_op(Context* C, int op, const uint64_t* in, size_t n, uint64_t* out)
   hipLaunchKernelGGL(k_gt_debug_op, dim3((unsigned)blocks), dim3(PAIR_BLOCK), 0, C->stream, op, d.p, n, C->pairing.gt_tab.as<uint32_t>(), d.p);
   GM_HIP(hipGetLastError());
   return gt_to_host(C, d.p, n, out);
+}
+
+// gm_debug_gt_op2: b_or_null is read by the ops that take a second operand
+int gt_debug_op2(Context* C, int op, const uint64_t* a, const uint64_t* b_or_null, size_t n, uint64_t* out) {
+  GM_CHECK(op >= 0 && op < GT_OP2_END, GM_EINVAL, "debug_gt_op2: unknown op %d", op);
+  GM_CHECK(n <= GT_EACH_MAX, GM_EINVAL, "debug_gt_op2: %zu elements in one call (at most 2^20)", n);
+  const bool binary = gt_op2_is_binary(op);
+  GM_CHECK(!binary || b_or_null != nullptr, GM_EINVAL, "debug_gt_op2: op %d takes a second operand", op);
+  GM_MSM_LOCK(C);
+  GtTmp da(C), db(C);
+  int rc = gt_from_host(C, a, n, &da.p);
+  if (!rc && binary) rc = gt_from_host(C, b_or_null, n, &db.p);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_gt_debug_op2, dim3((unsigned)((n + PAIR_BLOCK - 1) / PAIR_BLOCK)), dim3(PAIR_BLOCK), 0, C->stream, op, da.p, db.p, n, da.p);
+  GM_HIP(hipGetLastError());
+  return gt_to_host(C, da.p, n, out);
+}
+
+// gm_debug_miller_step: n records T | Q | P in, n records T' | line out
+int miller_debug_step(Context* C, int op, const uint64_t* in, size_t n, uint64_t* out) {
+  GM_CHECK(op == MILLER_OP_DBL || op == MILLER_OP_ADD, GM_EINVAL, "debug_miller_step: unknown op %d", op);
+  GM_CHECK(n <= GT_EACH_MAX, GM_EINVAL, "debug_miller_step: %zu records in one call (at most 2^20)", n);
+  GM_MSM_LOCK(C);
+  GtTmp d(C);
+  int rc = gt_from_host(C, in, n, &d.p);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_miller_debug_step, dim3((unsigned)((n + PAIR_BLOCK - 1) / PAIR_BLOCK)), dim3(PAIR_BLOCK), 0, C->stream, op, d.p, n, d.p);
+  GM_HIP(hipGetLastError());
+  return gt_to_host(C, d.p, n, out);
+}
+
+// gm_debug_miller_each: out[i] = f_{|x|, Q_i}(P_i) as k_miller_each stores it -- no conjugation, no product, no final exponentiation
+static int miller_debug_each_run(Context* C, const uint8_t* d_g1, const uint8_t* d_g2, size_t n, uint64_t* out) {
+  GM_MSM_LOCK(C);
+  GtTmp d(C);
+  GM_HIP(dev_malloc((void**)&d.p, n * GT_BYTES));
+  const PairRange r{d_g1, d_g2, 0, 1, 0, 1, (unsigned long long)n};
+  hipLaunchKernelGGL(k_miller_each, dim3((unsigned)((n + PAIR_BLOCK - 1) / PAIR_BLOCK)), dim3(PAIR_BLOCK), 0, C->stream, r, d.p);
+  GM_HIP(hipGetLastError());
+  return gt_to_host(C, d.p, n, out);
+}
+int miller_debug_each(Context* C, const void* g1, size_t stride1, const void* g2, size_t stride2, size_t n, uint64_t* out) {
+  GM_CHECK(n <= GT_EACH_MAX, GM_EINVAL, "debug_miller_each: %zu pairs in one call (at most 2^20)", n);
+  std::unique_ptr<Bases> b1;
+  std::unique_ptr<G2Bases> b2;
+  int rc = bases_from_host(C, g1, stride1, n, b1);
+  if (!rc) rc = g2_bases_from_host(C, g2, stride2, n, b2);
+  if (!rc) rc = miller_debug_each_run(C, b1->d, b2->d, n, out);
+  if (b1 && b1->d) (void)gm::raw_free(b1->d);
+  if (b2 && b2->d) (void)gm::raw_free(b2->d);
+  return rc;
 }
 
 }  // namespace gm

@@ -117,6 +117,50 @@ def debug_gt_op(op: int, x) -> np.ndarray:
     return out
 
 
+(GT_OP2_MUL, GT_OP2_SQR, GT_OP2_CONJ, GT_OP2_MUL_014, GT_OP2_FQ6_MUL, GT_OP2_FQ6_MUL_V, GT_OP2_FQ6_MUL_01, GT_OP2_FQ6_MUL_1, GT_OP2_FQ2_MUL_XI,
+ GT_OP2_FQ2_MUL12, GT_OP2_FQ2_MUL_FQ, GT_OP2_FQ2_CONJ) = range(12)
+MILLER_OP_DBL, MILLER_OP_ADD = range(2)
+
+
+def debug_gt_op2(op: int, a, b=None) -> np.ndarray:
+    """gm_debug_gt_op2, a test aid: ONE tower function of gt.cuh per element of a ((n, 72) limbs); b ((n, 72)) is the second operand
+    of the GT_OP2_* that take one (include/gemini_hip.h: a line in its first three Fq2 slots, an Fq scalar in the c0 of a slot)"""
+    capi.ensure_init()
+    xs = capi.u64(a).reshape(-1, 72)
+    pb = None
+    if b is not None:
+        ys = capi.u64(b).reshape(-1, 72)
+        assert len(ys) == len(xs)
+        pb = capi.ptr(ys)
+    out = np.empty_like(xs)
+    capi.check(capi.load().gm_debug_gt_op2(C.c_int(op), capi.ptr(xs), pb, C.c_size_t(len(xs)), capi.ptr(out)))
+    return out
+
+
+def debug_miller_step(op: int, T, Q, P):
+    """gm_debug_miller_step, a test aid: ONE miller_dbl_step (op 0) or miller_add_step (op 1) per row.  T is (n, 36) limbs (X | Y | Z
+    over Fq2, any Z), Q (n, 24) (x | y over Fq2), P (n, 12) (two field elements, not checked against the curve) -> the new T (n, 36)
+    and the line (l0 | l1 | l4) (n, 36)"""
+    capi.ensure_init()
+    t, q, p = capi.u64(T).reshape(-1, 36), capi.u64(Q).reshape(-1, 24), capi.u64(P).reshape(-1, 12)
+    assert len(t) == len(q) == len(p)
+    rec = np.ascontiguousarray(np.concatenate([t, q, p], axis=1))
+    out = np.empty_like(rec)
+    capi.check(capi.load().gm_debug_miller_step(C.c_int(op), capi.ptr(rec), C.c_size_t(len(rec)), capi.ptr(out)))
+    return out[:, :36].copy(), out[:, 36:].copy()
+
+
+def debug_miller_each(g1, g2) -> np.ndarray:
+    """gm_debug_miller_each, a test aid: out[i] = the Miller value of pair i as the loop leaves it ((n, 72) limbs): no conjugation, no
+    product, no final exponentiation.  Records as for `pairing_each`; the shorter input ends the vector."""
+    capi.ensure_init()
+    r1, r2 = _g1_records(g1), _g2_records(g2)
+    m = min(len(r1), len(r2))
+    out = np.empty((m, 72), dtype=np.uint64)
+    capi.check(capi.load().gm_debug_miller_each(capi.ptr(r1), C.c_size_t(r1.shape[1] * 8), capi.ptr(r2), C.c_size_t(r2.shape[1] * 8), C.c_size_t(m), capi.ptr(out)))
+    return out
+
+
 def _g1_records(bases) -> np.ndarray:
     bases = capi.u64(bases)
     assert bases.ndim == 2 and bases.shape[1] in (12, 13)

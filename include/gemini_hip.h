@@ -632,6 +632,21 @@ int gm_ipa_check_gt(uint64_t proof, size_t* first_bad, int* ok);
 /* A test aid: ONE device function of gt.cuh per lane over n x 72 limbs.  op 0: in^q, 1: in^(q^2), 2: 1 / in (0 gives 0),
  * 3: the cyclotomic squaring (in^2 on the cyclotomic subgroup ONLY), 4: in^|x| by cyclotomic squarings (likewise). */
 int gm_debug_gt_op(int op, const uint64_t* in, size_t n, uint64_t* out);
+/* Test aids for the Miller-loop half of gt.cuh / pairing.hip, same conventions: records of 72 limbs (12 Fq in ark-ff's Montgomery
+ * form), one lane per record, 64 lanes per block, under the MSM lock; an unknown op or a missing operand is GM_EINVAL, n = 0 a no-op.
+ * gm_debug_gt_op2: ONE tower function per lane.  b is read by the ops marked (b) and may be NULL for the others.
+ *   0 fq12_mul(a, b) (b)   1 fq12_sqr(a)   2 fq12_conj(a)   3 fq12_mul_014(a, l0, l1, l4) (b: the line in its first three Fq2 slots)
+ *   4 fq6_mul (b)   5 fq6_mul_v   6 fq6_mul_01(., b0, b1) (b: its first two Fq2 slots)   7 fq6_mul_1(., b1) (b: its first Fq2 slot)
+ *     -- 4 .. 7 on both halves: out.c0 from a.c0 (and b.c0 for 4), out.c1 from a.c1 (and b.c1 for 4)
+ *   8 fq2_mul_xi   9 fq2_mul12   10 fq2_mul_fq(., s) (b: s is the c0 of b's Fq2 slot)   11 fq2_conj   -- 8 .. 11 on each of the six Fq2 slots
+ * gm_debug_miller_step: ONE step of the Miller loop per lane, op 0 miller_dbl_step, 1 miller_add_step.  in: T (X | Y | Z over Fq2,
+ *   homogeneous projective, any Z), Q (x | y over Fq2), P (x | y, two field elements taken as they are, not checked against the
+ *   curve) = 72 limbs; out: the new T (X | Y | Z) and the line (l0 | l1 | l4) = 72 limbs.  The addition step requires T != +-Q.
+ * gm_debug_miller_each: out[i] = f_{|x|, Q_i}(P_i), the lane's Miller value as the loop leaves it: no conjugation, no product, no
+ *   final exponentiation (1 when either point is the identity).  Records as for gm_pairing_each. */
+int gm_debug_gt_op2(int op, const uint64_t* a /* n x 72 */, const uint64_t* b /* n x 72 or NULL */, size_t n, uint64_t* out /* n x 72 */);
+int gm_debug_miller_step(int op, const uint64_t* in /* n x 72 */, size_t n, uint64_t* out /* n x 72 */);
+int gm_debug_miller_each(const void* g1, size_t g1_stride, const void* g2, size_t g2_stride, size_t n, uint64_t* out /* n x 72 */);
 
 /* ---- herring's inner-product argument: Crs, Vrs, InnerProductProof (gemini_amd/csrc/ipa.hip) -------------------------
  * src/herring/ipa.rs: InnerProductProof::new (:533-685) proves <a, b> = y together with comm_a = <a, crs.g1> and

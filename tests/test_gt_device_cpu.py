@@ -16,7 +16,8 @@ from tests.test_pairing_cpu import tower_to_w
 
 Q, R = OP.Q, OP.R
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gemini_amd", "csrc")
-NAMES = ("gm_gt_final_exp_many", "gm_pairing_each", "gm_pairing_each_h", "gm_gt_check", "gm_hgt_check", "gm_ipa_check_gt", "gm_debug_gt_op")
+NAMES = ("gm_gt_final_exp_many", "gm_pairing_each", "gm_pairing_each_h", "gm_gt_check", "gm_hgt_check", "gm_ipa_check_gt", "gm_debug_gt_op",
+         "gm_debug_gt_op2", "gm_debug_miller_step", "gm_debug_miller_each")
 
 
 def test_chain_identity_on_integers():
@@ -116,6 +117,10 @@ def test_entries_fail_closed_before_init():
     assert lib.gm_pairing_each(capi.ptr(x), C.c_size_t(96), capi.ptr(x), C.c_size_t(192), C.c_size_t(1), capi.ptr(out)) == NOTINIT
     assert lib.gm_pairing_each_h(C.c_uint64(1), C.c_size_t(0), C.c_size_t(1), C.c_uint64(2), C.c_size_t(0), C.c_size_t(1), C.c_size_t(1), capi.ptr(out)) == NOTINIT
     assert lib.gm_debug_gt_op(C.c_int(0), capi.ptr(x), C.c_size_t(2), capi.ptr(out)) == NOTINIT
+    assert lib.gm_debug_gt_op2(C.c_int(0), capi.ptr(x), capi.ptr(x), C.c_size_t(2), capi.ptr(out)) == NOTINIT
+    assert lib.gm_debug_gt_op2(C.c_int(99), None, None, C.c_size_t(0), None) == NOTINIT
+    assert lib.gm_debug_miller_step(C.c_int(0), capi.ptr(x), C.c_size_t(2), capi.ptr(out)) == NOTINIT
+    assert lib.gm_debug_miller_each(capi.ptr(x), C.c_size_t(96), capi.ptr(x), C.c_size_t(192), C.c_size_t(1), capi.ptr(out)) == NOTINIT
     for call in (lambda fb, ok: lib.gm_gt_check(capi.ptr(x), C.c_size_t(2), capi.ptr(st), fb, ok),
                  lambda fb, ok: lib.gm_hgt_check(C.c_uint64(1), fb, ok),
                  lambda fb, ok: lib.gm_ipa_check_gt(C.c_uint64(1), fb, ok)):
