@@ -41,7 +41,7 @@ SYMBOLS = [
     "gm_hg2_new", "gm_hg2_round", "gm_hg2_fold", "gm_hg2_rounds", "gm_hg2_final", "gm_hg2_free",
     "gm_pairing_multi", "gm_pairing_multi_h", "gm_gt_mul", "gm_gt_pow", "gm_gt_one", "gm_gt_final_exp",
     "gm_hp_new", "gm_hp_round", "gm_hp_fold", "gm_hp_rounds", "gm_hp_final", "gm_hp_free",
-    "gm_gt_multi_pow", "gm_hgt_new", "gm_hgt_round", "gm_hgt_fold", "gm_hgt_rounds", "gm_hgt_final", "gm_hgt_free",
+    "gm_gt_multi_pow", "gm_gt_multi_pow_many", "gm_hgt_new", "gm_hgt_round", "gm_hgt_fold", "gm_hgt_rounds", "gm_hgt_final", "gm_hgt_free",
     "gm_gt_final_exp_many", "gm_pairing_each", "gm_pairing_each_h", "gm_gt_check", "gm_hgt_check", "gm_ipa_check_gt", "gm_debug_gt_op",
     "gm_debug_gt_op2", "gm_debug_miller_step", "gm_debug_miller_each",
     "gm_transcript_new", "gm_transcript_free", "gm_transcript_append_message", "gm_transcript_challenge_bytes",
@@ -63,7 +63,7 @@ SYMBOLS = [
     "gm_debug_fq_op", "gm_debug_fq30_op", "gm_debug_fq2_op", "gm_debug_g1_op", "gm_debug_g2_op", "gm_debug_acc30_op",
     "gm_g2_fixed_base_register", "gm_g2_srs_register", "gm_g1_bases_from_candidates", "gm_g2_bases_from_candidates",
     "gm_crs_truncate", "gm_crs_halve", "gm_crs_fold", "gm_crs_to_bases",
-    "gm_ipa_foldings_fg1", "gm_ipa_foldings_fg2", "gm_ipa_free", "gm_ipa_host_times", "gm_ipa_from_fields", "gm_ipa_verify", "gm_transcript_append_gt",
+    "gm_ipa_foldings_fg1", "gm_ipa_foldings_fg2", "gm_ipa_free", "gm_ipa_host_times", "gm_ipa_from_fields", "gm_ipa_verify", "gm_ipa_verify_many", "gm_set_ipa_verify_many_min", "gm_debug_ipa_verify_many_path", "gm_debug_ipa_stated_terms", "gm_transcript_append_gt",
 ]
 
 

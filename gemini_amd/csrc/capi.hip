@@ -2069,6 +2069,12 @@ int gm_gt_multi_pow(const uint64_t* x, size_t n, const uint64_t* scalars_canonic
   if (n == 0) return gm_gt_one(out_gt);
   return gt_multi_pow_host(C, x, scalars_canonical, n, out_gt);
 }
+int gm_gt_multi_pow_many(const uint64_t* x, const uint64_t* scalars_canonical, const size_t* offsets, size_t S, uint64_t* out_gt) {
+  GM_CTX();
+  if (S == 0) return GM_OK;
+  GM_CHECK(offsets != nullptr && out_gt != nullptr, GM_EINVAL, "gt_multi_pow_many: null pointer");
+  return gt_multi_pow_many_host(C, x, scalars_canonical, offsets, S, out_gt);
+}
 int gm_hgt_new(const uint64_t* f_gt, size_t nf, const uint64_t* g_mont, size_t ng, const uint64_t twist_mont[4], uint64_t* handle) {
   GM_CTX();
   GM_CHECK(f_gt && g_mont && twist_mont && handle, GM_EINVAL, "hgt_new: null pointer");
@@ -2434,6 +2440,47 @@ int gm_ipa_verify(uint64_t proof, uint64_t vrs, const uint64_t comm_a_jac[18], c
   GM_IPA_FIND(v, vrs, vrs, "ipa_verify", "Vrs");
   GM_CHECK(comm_a_jac && comm_b_jac && y_mont && ok, GM_EINVAL, "ipa_verify: null pointer");
   return ipa_verify(C, p, v, comm_a_jac, comm_b_jac, y_mont, ok);
+}
+int gm_ipa_verify_many(const uint64_t* proofs, uint64_t vrs, const uint64_t* comm_a_jac, const uint64_t* comm_b_jac, const uint64_t* y_mont, size_t S, int* ok) {
+  GM_CTX();
+  if (S == 0) {  // no single call would be made
+    GM_MSM_LOCK(C);
+    C->ipa_verify_many_last[0] = C->ipa_verify_many_last[1] = 0;
+    return GM_OK;
+  }
+  GM_CHECK(proofs != nullptr, GM_EINVAL, "ipa_verify_many: null pointer");
+  std::vector<const IpaProof*> ps(S);
+  const Vrs* v = nullptr;
+  for (size_t s = 0; s < S; s++) {  // the codes of the single calls, in their order
+    GM_IPA_FIND(p, ipa, proofs[s], "ipa_verify_many", "proof");
+    ps[s] = p;
+    if (s == 0) {
+      GM_IPA_FIND(v0, vrs, vrs, "ipa_verify_many", "Vrs");
+      v = v0;
+      GM_CHECK(comm_a_jac && comm_b_jac && y_mont && ok, GM_EINVAL, "ipa_verify_many: null pointer");
+    }
+  }
+  return ipa_verify_many(C, ps.data(), v, comm_a_jac, comm_b_jac, y_mont, S, ok);
+}
+int gm_set_ipa_verify_many_min(size_t proofs) {
+  GM_CTX();
+  GM_MSM_LOCK(C);
+  C->ipa_verify_many_min = proofs;
+  return GM_OK;
+}
+int gm_debug_ipa_verify_many_path(size_t counts[2]) {
+  GM_CTX();
+  GM_CHECK(counts != nullptr, GM_EINVAL, "gm_debug_ipa_verify_many_path: null output");
+  GM_MSM_LOCK(C);
+  counts[0] = C->ipa_verify_many_last[0];
+  counts[1] = C->ipa_verify_many_last[1];
+  return GM_OK;
+}
+int gm_debug_ipa_stated_terms(uint64_t proof, const uint64_t y_mont[4], uint64_t* gt_exponents, uint64_t* pairing_exponents) {
+  GM_CTX();
+  GM_IPA_FIND(p, ipa, proof, "debug_ipa_stated_terms", "proof");
+  GM_CHECK(y_mont && gt_exponents && pairing_exponents, GM_EINVAL, "debug_ipa_stated_terms: null pointer");
+  return ipa_stated_terms(p, y_mont, gt_exponents, pairing_exponents);
 }
 
 // ---- space prover --------------------------------------------------------------------------------

@@ -378,6 +378,10 @@ struct Context {
   bool have_start_ev = false;
   DevBuf lincomb;  // gm_g1_lincomb_many and the batched KZG checks: staged terms, their multiples and the sums of a call (under msm_mu)
   size_t verify_many_min = 3;  // fewer stated KZG checks than this take the per-check path (gm_set_verify_many_min); 2 is a tie: profiles/verify_many.md
+  // gm_ipa_verify_many: fewer proofs than this take ipa_verify one by one (gm_set_ipa_verify_many_min); what the last call did
+  // (gm_debug_ipa_verify_many_path): proofs on the batched path, proofs on the per-proof path
+  size_t ipa_verify_many_min = 2;  // S = 1 is a tie (69.6 against 71.2 ms), S = 2 wins 66 against 140 ms: profiles/ipa_verify_many.md
+  size_t ipa_verify_many_last[2] = {0, 0};
   DevBuf fr_scratch;
   uint64_t* host_small = nullptr;  // pinned, 64 KiB, for small results
   // the descriptor arrays of k_sc_round_multi: a RING of SC_DESC_SLOTS slots of SC_DESC_SLOT bytes, one per launch, pinned on the host
@@ -589,6 +593,18 @@ struct GtSpan {  // n terms x[first_x + step_x i] ^ e[first_e + step_e i]: 576-b
 // form (the canonical integer is taken on the device); else 8 canonical words as they are, not reduced.  Caller holds the MSM lock.
 int gt_multi_pow(Context* C, const GtSpan spans[3], int mont, gmh::Fq12* out);
 int gt_multi_pow_host(Context* C, const uint64_t* x, const uint64_t* scalars_canonical, size_t n, uint64_t out_gt[72]);
+// The segmented form (k_gt_multi_pow_seg): S independent products in one launch per level.  A term names a row of a table of 576-byte
+// elements and a row of a table of 32-byte canonical exponents, so many terms may raise the same element.
+struct GtTerm {
+  uint32_t x, e;
+};
+// gm_gt_multi_pow_many: product s is over the host terms [offsets[s], offsets[s + 1])
+int gt_multi_pow_many_host(Context* C, const uint64_t* x, const uint64_t* scalars_canonical, const size_t* offsets, size_t S, uint64_t* out_gt);
+// The two halves of S batched inner-product checks (ipa.hip) in one launch group and one wait: out_gt[s] = FE(conj(Miller product of
+// prods[s])), out_gt[S + s] = the product of the terms [offsets[s], offsets[s + 1]) over the device tables d_x (rows < nx) and d_e
+// (rows < ne).  Every product is non-empty.  Caller holds the MSM lock.
+int gt_checks_run(Context* C, const PairProduct* prods, const uint8_t* d_x, size_t nx, const uint8_t* d_e, size_t ne, const GtTerm* terms, const size_t* offsets, size_t S,
+                  uint64_t* out_gt);
 int gt_from_host(Context* C, const uint64_t* x, size_t n, uint8_t** d);  // n x 72 limbs -> a dev_malloc block of device records
 // out[i] = in[2i] in[2i+1]^s (an odd tail is in[2i]), s at d_s8 (canonical, 8 x u32), on C->stream; caller holds the MSM lock
 int gt_split_fold_launch(Context* C, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out);
@@ -624,5 +640,13 @@ int crs_commit(Context* C, const Crs* crs, int group, const uint64_t* scalars_mo
 int vrs_from_crs(Context* C, const Crs* crs, Vrs* out);
 int ipa_prove(Context* C, uint64_t transcript, const Crs* crs, const uint64_t* a_mont, const uint64_t* b_mont, size_t d, IpaProof* proof);
 int ipa_verify(Context* C, const IpaProof* proof, const Vrs* vrs, const uint64_t comm_a[18], const uint64_t comm_b[36], const uint64_t y_mont[4], int* ok);
+// S proofs in one launch group; ok[s] is ipa_verify's answer for every input
+int ipa_verify_many(Context* C, const IpaProof* const* proofs, const Vrs* vrs, const uint64_t* comm_a /* S x 18 */, const uint64_t* comm_b /* S x 36 */,
+                    const uint64_t* y_mont /* S x 4 */, size_t S, int* ok);
+// gm_debug_ipa_stated_terms: the canonical exponents of the stated form of one proof, 6 R - 4 GT terms then 2 R + 4 pairing terms
+int ipa_stated_terms(const IpaProof* proof, const uint64_t y_mont[4], uint64_t* gt_exp, uint64_t* pair_exp);
+// Jacobian points of both groups -> the host records of the proof checks and a GM_PT_* status byte each (points.hip), one launch per group
+int jac_points_status(Context* C, const std::vector<const uint64_t*>& g1, const std::vector<const uint64_t*>& g2, std::vector<uint64_t>& r1, std::vector<uint64_t>& r2,
+                      std::vector<uint8_t>& st1, std::vector<uint8_t>& st2);
 
 }  // namespace gm

@@ -531,4 +531,243 @@ int ipa_verify(Context* C, const IpaProof* pr, const Vrs* vrs, const uint64_t co
   return GM_OK;
 }
 
+// ---- many proofs in one call ----------------------------------------------------------------------------------------------------
+// verify_transcript is linear in the claim: every round maps claim -> a^(1 - ch^2) b^ch claim^(ch^2) times the folded verifier key.
+// Unrolled over the R rounds, with w[i] = prod_{j > i} ch[j]^2 and W = w[0] ch[0]^2, "claim == expected" is ONE product in GT,
+//
+//   prod_j x_j^(e_j) * FE(conj(prod_t Miller(P_t, Q_t))) == 1
+//
+// over GT elements the verifier is handed (the proof's messages, the Vrs entries) with exponents the host computes from the
+// challenges, and pairs whose exponent has moved onto the G1 side.  The terms, in the order ipa_state lists them (R rounds):
+//
+//   GT, 6 R - 4      a_i^((1 - ch_i^2) w_i), b_i^(ch_i w_i) for every round i; then for every round i < R - 1, level l = R - 2 - i:
+//                    vk1_even[l]^(bch[3+2i] w_i), vk1_odd[l]^(bch[3+2i] w_i ch_i), vk2_even[l]^(bch[4+2i] w_i), vk2_odd[l]^(bch[4+2i] w_i ch_i)
+//   pairs, 2 R + 4   e(G1, G2)^(y bch0 W), e(comm_a, G2)^(bch1 W), e(G1, comm_b)^(bch2 W); then the expected side, negated:
+//                    e(G1, G2)^(-ff.lhs ff.rhs bch0), e(fg1.f0, G2)^(-fg1.g0 bch1), e(G1, fg2.g0)^(-fg2.f0 bch2), e(lhs_p, rhs_p)^(-bch[3+p])
+//
+// tests/ipa_flat_ref.py states the same on Python integers.  The unrolling holds for MEMBERS only (exponents are taken mod r, and
+// e(s P, Q) = e(P, Q)^s needs P in G1 and Q in G2), so ipa_verify_many first runs the membership tests over every element a proof or the
+// caller supplies and gives every proof that fails one to ipa_verify above: its answer is ipa_verify's for every input.
+namespace {
+
+void ipa_state(const IpaProof* pr, const uint64_t y_mont[4], std::vector<gmh::Fr>& gt, std::vector<gmh::Fr>& pair) {
+  const size_t R = pr->rounds, k = 2 * (R - 1);
+  auto fr = [](const uint64_t* p) { return gmh::Fr::from_limbs(p); };
+  std::vector<gmh::Fr> bch(3 + k), ch(R), w(R);
+  for (size_t i = 0; i < 3 + k; i++) bch[i] = fr(pr->batch_challenges.data() + 4 * i);
+  for (size_t i = 0; i < R; i++) ch[i] = fr(pr->challenges.data() + 4 * i);
+  w[R - 1] = gmh::Fr::one();
+  for (size_t i = R - 1; i > 0; i--) w[i - 1] = w[i] * ch[i].sqr();
+  const gmh::Fr W = w[0] * ch[0].sqr();
+  gt.clear();
+  pair.clear();
+  for (size_t i = 0; i < R; i++) {
+    gt.push_back((gmh::Fr::one() - ch[i].sqr()) * w[i]);
+    gt.push_back(ch[i] * w[i]);
+  }
+  for (size_t i = 0; i + 1 < R; i++)
+    for (size_t v = 0; v < 2; v++) {
+      const gmh::Fr e = bch[3 + 2 * i + v] * w[i];
+      gt.push_back(e);
+      gt.push_back(e * ch[i]);
+    }
+  pair.push_back(fr(y_mont) * bch[0] * W);
+  pair.push_back(bch[1] * W);
+  pair.push_back(bch[2] * W);
+  pair.push_back((fr(pr->foldings_ff) * fr(pr->foldings_ff + 4) * bch[0]).neg());
+  pair.push_back((fr(pr->foldings_fg1 + 18) * bch[1]).neg());
+  pair.push_back((fr(pr->foldings_fg2) * bch[2]).neg());
+  for (size_t p = 0; p < k; p++) pair.push_back(bch[3 + p].neg());
+}
+
+// the lengths ipa_verify asks of a proof and of the Vrs, with its codes
+int ipa_shape(const IpaProof* pr, const Vrs* vrs, const char* who) {
+  const size_t R = pr->rounds, k = R >= 1 ? 2 * (R - 1) : 0;
+  GM_CHECK(R >= 1 && pr->messages.size() == R * 144 && pr->challenges.size() == R * 4 && pr->batch_challenges.size() == (3 + k) * 4 && pr->final_g1.size() == k * 18 &&
+               pr->final_g2.size() == k * 36,
+           GM_EINVAL, "%s: the proof's fields do not have the lengths of %zu rounds", who, R);
+  GM_CHECK(!vrs || vrs->levels + 1 >= R, GM_EINVAL, "%s: a proof of %zu rounds needs %zu levels of the Vrs, it has %zu", who, R, R - 1, vrs ? vrs->levels : 0);
+  return GM_OK;
+}
+
+bool fr_reduced(const uint64_t* p) {
+  uint64_t t[4];
+  return gmh::sub_n<4>(t, p, gmh::FrP::MOD) != 0;
+}
+// every scalar the stated form multiplies is a reduced residue (the per-proof path takes limbs as they are)
+bool ipa_scalars_reduced(const IpaProof* pr, const uint64_t y_mont[4]) {
+  bool ok = fr_reduced(y_mont) && fr_reduced(pr->foldings_ff) && fr_reduced(pr->foldings_ff + 4) && fr_reduced(pr->foldings_fg1 + 18) && fr_reduced(pr->foldings_fg2);
+  for (size_t i = 0; i < pr->challenges.size(); i += 4) ok = ok && fr_reduced(pr->challenges.data() + i);
+  for (size_t i = 0; i < pr->batch_challenges.size(); i += 4) ok = ok && fr_reduced(pr->batch_challenges.data() + i);
+  return ok;
+}
+
+// an affine host record (ark-ff's Montgomery form, the identity all zero) -> the packed record of the device
+void g2_record_to_device(const uint64_t in[24], uint64_t out[24]) {
+  for (int c = 0; c < 4; c++) gmh::fq_to_device(gmh::Fq::from_limbs(in + 6 * c), out + 6 * c);
+}
+
+}  // namespace
+
+int ipa_stated_terms(const IpaProof* pr, const uint64_t y_mont[4], uint64_t* gt_exp, uint64_t* pair_exp) {
+  int rc = ipa_shape(pr, nullptr, "ipa_stated_terms");
+  if (rc) return rc;
+  std::vector<gmh::Fr> gt, pair;
+  ipa_state(pr, y_mont, gt, pair);
+  for (size_t i = 0; i < gt.size(); i++) gt[i].to_canonical(gt_exp + 4 * i);
+  for (size_t i = 0; i < pair.size(); i++) pair[i].to_canonical(pair_exp + 4 * i);
+  return GM_OK;
+}
+
+// Launches and waits of the batched path, whatever S is: one k_pt_check per group and one k_gt_check over every element the proofs
+// and the caller supply (a wait each: their verdicts decide which proofs go on), the upload of the GT table (a wait), then ONE
+// launch group -- k_g1_term_mul, k_g1_seg_sum, k_normalise for every G1 point of every proof, k_miller_seg with one segment per
+// proof, k_gt_final_exp over the S Miller values, k_gt_multi_pow_seg over all GT terms, the reduction levels of the longest proof --
+// and its wait.  The batched kernels see members only: no element that failed a test reaches them, and none of them addresses memory
+// by the value of an element (pairing.hip: k_gt_multi_pow_seg).
+int ipa_verify_many(Context* C, const IpaProof* const* proofs, const Vrs* vrs, const uint64_t* comm_a, const uint64_t* comm_b, const uint64_t* y_mont, size_t S, int* ok) {
+  int rc;
+  for (size_t s = 0; s < S; s++)
+    if ((rc = ipa_shape(proofs[s], vrs, "ipa_verify_many"))) return rc;
+  for (size_t s = 0; s < S; s++) ok[s] = 0;
+  GM_MSM_LOCK(C);
+  C->ipa_verify_many_last[0] = C->ipa_verify_many_last[1] = 0;
+  std::vector<char> clean(S, 0);
+  size_t nclean = 0;
+  if (S >= C->ipa_verify_many_min && S > 0) {
+    // membership: G1 = comm_a, fg1.f0, the Lhs final foldings; G2 = comm_b, fg2.g0, the Rhs final foldings; GT = the messages
+    std::vector<const uint64_t*> j1, j2;
+    std::vector<size_t> pbase(S + 1, 0), mbase(S + 1, 0);  // first point / first message of proof s
+    for (size_t s = 0; s < S; s++) {
+      const IpaProof* pr = proofs[s];
+      const size_t k = 2 * (pr->rounds - 1);
+      j1.push_back(comm_a + 18 * s);
+      j1.push_back(pr->foldings_fg1);
+      j2.push_back(comm_b + 36 * s);
+      j2.push_back(pr->foldings_fg2 + 4);
+      for (size_t p = 0; p < k; p++) {
+        j1.push_back(pr->final_g1.data() + 18 * p);
+        j2.push_back(pr->final_g2.data() + 36 * p);
+      }
+      pbase[s + 1] = pbase[s] + 2 + k;
+      mbase[s + 1] = mbase[s] + 2 * pr->rounds;
+    }
+    std::vector<uint64_t> r1, r2, msgs(mbase[S] * 72);
+    std::vector<uint8_t> st1, st2, stg(mbase[S]);
+    for (size_t s = 0; s < S; s++) memcpy(msgs.data() + 72 * mbase[s], proofs[s]->messages.data(), proofs[s]->messages.size() * 8);
+    int all = 0;
+    if ((rc = jac_points_status(C, j1, j2, r1, r2, st1, st2))) return rc;
+    if ((rc = gt_check_host(C, msgs.data(), mbase[S], stg.data(), nullptr, &all))) return rc;
+    for (size_t s = 0; s < S; s++) {
+      bool good = ipa_scalars_reduced(proofs[s], y_mont + 4 * s);
+      for (size_t i = pbase[s]; i < pbase[s + 1]; i++) good = good && st1[i] == GM_PT_OK && st2[i] == GM_PT_OK;
+      for (size_t i = mbase[s]; i < mbase[s + 1]; i++) good = good && stg[i] == GM_PT_OK;
+      clean[s] = good;
+      nclean += good;
+    }
+    if (nclean) {
+      // the tables of the clean proofs.  G1 terms (host records) and their segments: per proof [G1 y.., comm_a, G1 -ff.., fg1.f0]
+      // against G2, [G1] against comm_b, [G1] against fg2.g0, [lhs_p] against rhs_p; the G2 side lists one record per segment
+      uint64_t gen1[12], gen2[24];
+      g1_generator().x.to_limbs(gen1);
+      g1_generator().y.to_limbs(gen1 + 6);
+      g2_to_record(g2_generator(), gen2);
+      const size_t nv = 4 * vrs->levels;
+      std::vector<uint64_t> pts, sc, q2, gtx(nv * 72), gte;
+      std::vector<size_t> seg_off(1, 0), term_off(1, 0);
+      std::vector<GtTerm> terms;
+      std::vector<PairProduct> prods;
+      std::vector<size_t> who;
+      for (size_t l = 0; l < vrs->levels; l++) {  // rows 4 l ..: vk1 even, vk1 odd, vk2 even, vk2 odd
+        memcpy(gtx.data() + 72 * (4 * l), vrs->vk1.data() + 144 * l, 144 * 8);
+        memcpy(gtx.data() + 72 * (4 * l + 2), vrs->vk2.data() + 144 * l, 144 * 8);
+      }
+      std::vector<gmh::Fr> eg, ep;
+      auto term1 = [&](const uint64_t* rec, const gmh::Fr& e) {
+        pts.insert(pts.end(), rec, rec + 12);
+        const Scalar c = canonical(e);
+        sc.insert(sc.end(), c.begin(), c.end());
+      };
+      auto seg_end = [&](const uint64_t* rec2_dev) {
+        seg_off.push_back(pts.size() / 12);
+        q2.insert(q2.end(), rec2_dev, rec2_dev + 24);
+      };
+      for (size_t s = 0; s < S; s++) {
+        if (!clean[s]) continue;
+        const IpaProof* pr = proofs[s];
+        const size_t R = pr->rounds, k = 2 * (R - 1);
+        ipa_state(pr, y_mont + 4 * s, eg, ep);
+        const uint64_t *a1 = r1.data() + 12 * pbase[s], *a2 = r2.data() + 24 * pbase[s];
+        uint64_t rec2[24];
+        const size_t seg0 = seg_off.size() - 1;
+        term1(gen1, ep[0]);
+        term1(a1, ep[1]);
+        term1(gen1, ep[3]);
+        term1(a1 + 12, ep[4]);
+        seg_end(gen2);
+        term1(gen1, ep[2]);
+        g2_record_to_device(a2, rec2);
+        seg_end(rec2);
+        term1(gen1, ep[5]);
+        g2_record_to_device(a2 + 24, rec2);
+        seg_end(rec2);
+        for (size_t p = 0; p < k; p++) {
+          term1(a1 + 12 * (2 + p), ep[6 + p]);
+          g2_record_to_device(a2 + 24 * (2 + p), rec2);
+          seg_end(rec2);
+        }
+        PairProduct pp;
+        pp.s0 = span(nullptr, seg0, 1, nullptr, seg0, 1, 3 + k);  // the two arrays are known once they are on the device
+        prods.push_back(pp);
+        // GT terms: the messages of this proof follow the Vrs rows
+        const size_t m0 = gtx.size() / 72, e0 = gte.size() / 4;
+        gtx.insert(gtx.end(), pr->messages.begin(), pr->messages.end());
+        for (size_t i = 0; i < eg.size(); i++) {
+          const Scalar c = canonical(eg[i]);
+          gte.insert(gte.end(), c.begin(), c.end());
+          uint32_t row;
+          if (i < 2 * R) {
+            row = (uint32_t)(m0 + i);
+          } else {
+            const size_t j = i - 2 * R, round = j / 4;
+            row = (uint32_t)(4 * (R - 2 - round) + j % 4);
+          }
+          terms.push_back(GtTerm{row, (uint32_t)(e0 + i)});
+        }
+        term_off.push_back(terms.size());
+        who.push_back(s);
+      }
+      const size_t nx = gtx.size() / 72, ne = gte.size() / 4, nseg = seg_off.size() - 1;
+      Scratch mem;
+      uint8_t *d_x = nullptr, *d_e = nullptr, *d_q2 = nullptr, *d_aff = nullptr;
+      if ((rc = gt_from_host(C, gtx.data(), nx, &d_x))) return rc;  // ends in a wait
+      mem.p.push_back(d_x);
+      if ((rc = mem.get(ne * 32, &d_e)) || (rc = mem.get(nseg * 192, &d_q2))) return rc;
+      std::vector<uint64_t> out(2 * nclean * 72);
+      rc = GM_OK;
+      hipError_t e = hipMemcpyAsync(d_e, gte.data(), ne * 32, hipMemcpyHostToDevice, C->stream);
+      if (e == hipSuccess) e = hipMemcpyAsync(d_q2, q2.data(), nseg * 192, hipMemcpyHostToDevice, C->stream);
+      if (e != hipSuccess) rc = gm::hip_fail(e, "hipMemcpyAsync", __FILE__, __LINE__);
+      if (!rc) rc = g1_lincomb_many_launch(C, pts.data(), 96, sc.data(), seg_off.data(), nseg, &d_aff);
+      if (!rc) {
+        for (PairProduct& pp : prods) {
+          pp.s0.g1 = d_aff;
+          pp.s0.g2 = d_q2;
+        }
+        rc = gt_checks_run(C, prods.data(), d_x, nx, d_e, ne, terms.data(), term_off.data(), nclean, out.data());  // ends in the wait
+      }
+      (void)hipStreamSynchronize(C->stream);  // the host tables are read by their copies until here, the device ones by the kernels
+      if (rc) return rc;
+      const gmh::Fq12 one = gmh::Fq12::one();
+      for (size_t c = 0; c < nclean; c++)
+        ok[who[c]] = gmh::Fq12::from_limbs(out.data() + 72 * c) * gmh::Fq12::from_limbs(out.data() + 72 * (nclean + c)) == one ? 1 : 0;
+    }
+  }
+  for (size_t s = 0; s < S; s++)
+    if (!clean[s] && (rc = ipa_verify(C, proofs[s], vrs, comm_a + 18 * s, comm_b + 36 * s, y_mont + 4 * s, ok + s))) return rc;
+  C->ipa_verify_many_last[0] = nclean;
+  C->ipa_verify_many_last[1] = S - nclean;
+  return GM_OK;
+}
+
 }  // namespace gm

@@ -21,7 +21,8 @@
 // (ipa.hip), and Vrs::from asks for 4 (log2 len - 1) products.  Lanes map to (segment, pair) through a table of segment starts,
 // the per-lane loop is k_miller's, the block product multiplies only neighbours of the same segment and every segment that
 // touches a block writes one partial.  Partials of a segment are consecutive, so the next level is the same reduction over a
-// table of its own; the launch count depends on the longest segment only, never on S.
+// table of its own; the launch count depends on the longest segment only, never on S.  k_gt_multi_pow_seg is GtModule's power in
+// the same form: S independent multi-exponentiations in one launch (gm_gt_multi_pow_many; the GT half of ipa.hip's batched verifier).
 //
 // ELEMENT BY ELEMENT (k_miller_each, k_gt_final_exp, k_gt_check; "GT element by element" below): one lane per element and no block
 // product -- out[i] = e(P_i, Q_i) as one launch of Miller loops and one of final exponentiations by an exact x-chain over the
@@ -600,6 +601,35 @@ __global__ __launch_bounds__(PAIR_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1
   gt_block_product_seg(sh, seg, lane, sid, map, out);
 }
 
+// k_gt_multi_pow over a table of products: lane -> (segment, term), the power of gt_pow_lane, one partial per (block, segment).
+// Term t names a row of x (576-byte device records) and a row of e (32 bytes: 8 canonical words as they are), so many terms may
+// raise the same element; first[s] is the first term of segment s.  Both indices come from the host, which has checked them; the
+// only address a lane forms from the VALUE of an exponent is the 2-bit digit that picks one of the three table entries of its own
+// slice (gt_tab_load), and none from the value of an element.  (GtTerm: ctx.hpp)
+__global__ __launch_bounds__(PAIR_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_gt_multi_pow_seg(const uint8_t* __restrict__ x, const uint8_t* __restrict__ e,
+                                                                                                               const GtTerm* __restrict__ terms,
+                                                                                                               const unsigned long long* __restrict__ first,
+                                                                                                               const SegMap* __restrict__ map, unsigned nseg, uint32_t* __restrict__ tab,
+                                                                                                               uint8_t* __restrict__ partials) {
+  __shared__ uint32_t sh[GT_WORDS * PAIR_BLOCK];
+  __shared__ uint32_t seg[PAIR_BLOCK];
+  const int lane = threadIdx.x;
+  const unsigned long long i = (unsigned long long)blockIdx.x * PAIR_BLOCK + lane;
+  const uint32_t sid = seg_find(map, nseg, i);
+  const bool live = sid != NO_SEG;
+  Fq12 f = fq12_one();
+  uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (live) {
+    const GtTerm t = terms[first[sid] + (i - map[sid].start)];
+    f = fq12_load(x + (size_t)t.x * GT_BYTES);
+    const Fr s = fp_load<FrParams>(e + (size_t)t.e * 32);
+#pragma unroll
+    for (int j = 0; j < 8; j++) w[j] = s.l[j];
+  }
+  gt_pow_lane(sh, tab + (size_t)blockIdx.x * GT_TAB_BLOCK, lane, live, f, w);
+  gt_block_product_seg(sh, seg, lane, sid, map, partials);
+}
+
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
@@ -781,6 +811,28 @@ static unsigned long long seg_level(std::vector<unsigned long long>& counts, con
   return lane;
 }
 
+// Every level of the layout for segments of counts[s] >= 1 lanes: `maps` gets one table of counts.size() entries per level (level
+// 0 maps the terms, the others the partials of the level below), the last level leaves one partial per segment, back to back.
+struct SegLevel {
+  unsigned long long lanes, partials;
+};
+static int seg_levels(std::vector<unsigned long long>& counts, std::vector<SegMap>& maps, std::vector<SegLevel>& levels) {
+  const size_t nseg = counts.size();
+  std::vector<unsigned long long> starts;
+  for (;;) {
+    maps.resize(maps.size() + nseg);
+    SegMap* m = maps.data() + maps.size() - nseg;
+    SegLevel l;
+    l.lanes = seg_level(counts, starts, m, &l.partials);
+    levels.push_back(l);
+    GM_CHECK(l.lanes <= ((unsigned long long)1 << 37), GM_EINVAL, "pairing: %llu lanes in one segmented launch (at most 2^37)", l.lanes);
+    if (l.partials == nseg) break;  // one partial per segment, back to back
+    starts.resize(nseg);
+    for (size_t s = 0; s < nseg; s++) starts[s] = m[s].out;
+  }
+  return GM_OK;
+}
+
 // The launches of S independent Miller products, one per level (NOT conjugated, not exponentiated), on C->stream without a wait:
 // the products of the non-empty prods[idx[k]], k < idx.size(), end as consecutive device records at *d_out (a level buffer of the
 // workspace).  Caller holds the MSM lock and keeps `t` until it has waited for the stream: the copies of the tables read it.
@@ -808,26 +860,12 @@ static int miller_products_launch(Context* C, const PairProduct* prods, size_t S
   if (nseg == 0) return GM_OK;
   GM_CHECK(nseg < ((size_t)1 << 24), GM_EINVAL, "pairing: %zu products in one call (at most 2^24)", nseg);
   // every level's table, then ONE copy: level 0 maps pairs, the others the partials of the level below
-  struct Level {
-    unsigned long long lanes, partials;
-  };
-  std::vector<Level> levels;
-  std::vector<unsigned long long> starts;
-  for (;;) {
-    maps.resize(maps.size() + nseg);
-    SegMap* m = maps.data() + maps.size() - nseg;
-    Level l;
-    l.lanes = seg_level(counts, starts, m, &l.partials);
-    levels.push_back(l);
-    GM_CHECK(l.lanes <= ((unsigned long long)1 << 37), GM_EINVAL, "pairing: %llu lanes in one segmented launch (at most 2^37)", l.lanes);
-    if (l.partials == nseg) break;  // one partial per segment, back to back
-    starts.resize(nseg);
-    for (size_t s = 0; s < nseg; s++) starts[s] = m[s].out;
-  }
+  std::vector<SegLevel> levels;
+  int rc = seg_levels(counts, maps, levels);
+  if (rc) return rc;
   hipStream_t st = C->stream;
   PairingWorkspace& ws = C->pairing;
   Profiler& pf = C->prof;
-  int rc;
   const size_t span_bytes = nseg * sizeof(PairSeg), map_bytes = maps.size() * sizeof(SegMap);
   if ((rc = ws.seg_tab.ensure(span_bytes + map_bytes))) return rc;
   for (size_t l = 0; l < levels.size(); l++)  // level l writes its partials into part[l & 1]
@@ -1116,6 +1154,121 @@ int gt_check_host(Context* C, const uint64_t* x, size_t n, uint8_t* status_or_nu
     GM_HIP(hipMemcpyAsync(stage.p, x, n * GT_BYTES, hipMemcpyHostToDevice, C->stream));
   }
   return gt_check_run(C, stage.p, 1, n, status_or_null, first_bad, ok);
+}
+
+// ---- S independent GT multi-exponentiations (k_gt_multi_pow_seg and the levels of k_gt_reduce_seg) ---------------------------------
+// The launches on C->stream without a wait: the products of the non-empty term ranges [offsets[s], offsets[s + 1]) end as
+// consecutive device records at *d_out (a level buffer of the workspace), in the order of t.idx.  The caller has checked the
+// offsets and every term's rows against the two tables, holds the MSM lock and keeps `t` and `terms` until it has waited.
+struct GtSegTables {
+  std::vector<size_t> idx;
+  std::vector<unsigned long long> first;
+  std::vector<SegMap> maps;
+};
+static int gt_multi_pow_seg_launch(Context* C, const uint8_t* d_x, const uint8_t* d_e, const GtTerm* terms, const size_t* offsets, size_t S, GtSegTables& t, uint8_t** d_out) {
+  *d_out = nullptr;
+  std::vector<unsigned long long> counts;
+  for (size_t s = 0; s < S; s++) {
+    if (offsets[s + 1] == offsets[s]) continue;
+    t.idx.push_back(s);
+    t.first.push_back(offsets[s]);
+    counts.push_back(offsets[s + 1] - offsets[s]);
+  }
+  const size_t nseg = t.idx.size(), T = offsets[S];
+  if (nseg == 0) return GM_OK;
+  std::vector<SegLevel> levels;
+  int rc = seg_levels(counts, t.maps, levels);
+  if (rc) return rc;
+  hipStream_t st = C->stream;
+  PairingWorkspace& ws = C->pairing;
+  Profiler& pf = C->prof;
+  const size_t blocks = (size_t)((levels[0].lanes + PAIR_BLOCK - 1) / PAIR_BLOCK);
+  if ((rc = ws.gt_tab.ensure(blocks * GT_TAB_BLOCK * sizeof(uint32_t)))) return rc;
+  const size_t first_bytes = nseg * sizeof(unsigned long long), map_bytes = t.maps.size() * sizeof(SegMap), term_bytes = T * sizeof(GtTerm);
+  if ((rc = ws.seg_tab.ensure(first_bytes + map_bytes + term_bytes))) return rc;
+  for (size_t l = 0; l < levels.size(); l++)  // level l writes its partials into part[l & 1]
+    if ((rc = ws.part[l & 1].ensure(levels[l].partials * GT_BYTES))) return rc;
+  uint8_t* d_tab = ws.seg_tab.as<uint8_t>();
+  GM_HIP(hipMemcpyAsync(d_tab, t.first.data(), first_bytes, hipMemcpyHostToDevice, st));
+  GM_HIP(hipMemcpyAsync(d_tab + first_bytes, t.maps.data(), map_bytes, hipMemcpyHostToDevice, st));
+  GM_HIP(hipMemcpyAsync(d_tab + first_bytes + map_bytes, terms, term_bytes, hipMemcpyHostToDevice, st));
+  const SegMap* d_map = reinterpret_cast<const SegMap*>(d_tab + first_bytes);
+  pf.begin(PROF_ACC0, st);
+  hipLaunchKernelGGL(k_gt_multi_pow_seg, dim3((unsigned)blocks), dim3(PAIR_BLOCK), 0, st, d_x, d_e, reinterpret_cast<const GtTerm*>(d_tab + first_bytes + map_bytes),
+                     reinterpret_cast<const unsigned long long*>(d_tab), d_map, (unsigned)nseg, ws.gt_tab.as<uint32_t>(), ws.part[0].as<uint8_t>());
+  pf.end(PROF_ACC0, st);
+  GM_HIP(hipGetLastError());
+  int cur = 0;
+  pf.begin(PROF_REDUCE, st);
+  for (size_t l = 1; l < levels.size(); l++) {
+    hipLaunchKernelGGL(k_gt_reduce_seg, dim3((unsigned)((levels[l].lanes + PAIR_BLOCK - 1) / PAIR_BLOCK)), dim3(PAIR_BLOCK), 0, st, ws.part[cur].as<uint8_t>(), d_map + l * nseg,
+                       (unsigned)nseg, ws.part[cur ^ 1].as<uint8_t>());
+    cur ^= 1;
+  }
+  pf.end(PROF_REDUCE, st);
+  GM_HIP(hipGetLastError());
+  *d_out = ws.part[cur].as<uint8_t>();
+  return GM_OK;
+}
+
+// gm_gt_multi_pow_many: host elements and canonical 256-bit exponents, term i raises x[i] to scalars[i]
+int gt_multi_pow_many_host(Context* C, const uint64_t* x, const uint64_t* scalars_canonical, const size_t* offsets, size_t S, uint64_t* out_gt) {
+  GM_CHECK(offsets[0] == 0, GM_EINVAL, "gt_multi_pow_many: offsets[0] = %zu, the first product starts at 0", offsets[0]);
+  for (size_t s = 0; s < S; s++)
+    GM_CHECK(offsets[s] <= offsets[s + 1], GM_EINVAL, "gt_multi_pow_many: offsets[%zu] = %zu is above offsets[%zu] = %zu", s, offsets[s], s + 1, offsets[s + 1]);
+  const size_t n = offsets[S];
+  GM_CHECK(n <= GT_EACH_MAX, GM_EINVAL, "gt_multi_pow_many: %zu terms in one call (at most 2^20)", n);
+  GM_CHECK(n == 0 || (x != nullptr && scalars_canonical != nullptr), GM_EINVAL, "gt_multi_pow_many: null pointer");
+  for (size_t s = 0; s < S; s++) gmh::Fq12::one().to_limbs(out_gt + 72 * s);
+  if (n == 0) return GM_OK;
+  GM_MSM_LOCK(C);
+  GtTmp d(C);  // the elements, then the exponents
+  GM_HIP(dev_malloc((void**)&d.p, n * (GT_BYTES + 32)));
+  GM_HIP(hipMemcpyAsync(d.p, x, n * GT_BYTES, hipMemcpyHostToDevice, C->stream));
+  GM_HIP(hipMemcpyAsync(d.p + n * GT_BYTES, scalars_canonical, n * 32, hipMemcpyHostToDevice, C->stream));
+  hipLaunchKernelGGL(k_gt_import, dim3((unsigned)((n * 12 + 255) / 256)), dim3(256), 0, C->stream, d.p, n * 12);
+  GM_HIP(hipGetLastError());
+  std::vector<GtTerm> terms(n);
+  for (size_t i = 0; i < n; i++) terms[i] = GtTerm{(uint32_t)i, (uint32_t)i};
+  GtSegTables t;
+  uint8_t* d_out = nullptr;
+  int rc = gt_multi_pow_seg_launch(C, d.p, d.p + n * GT_BYTES, terms.data(), offsets, S, t, &d_out);
+  const size_t nseg = t.idx.size();
+  std::vector<uint64_t> got(nseg * 72);
+  if (!rc) rc = gt_to_host(C, d_out, nseg, got.data());  // the one wait
+  if (rc) {
+    (void)hipStreamSynchronize(C->stream);  // the host arrays are read by their copies until here
+    return rc;
+  }
+  for (size_t s = 0; s < nseg; s++) memcpy(out_gt + 72 * t.idx[s], got.data() + 72 * s, GT_BYTES);
+  return GM_OK;
+}
+
+int gt_checks_run(Context* C, const PairProduct* prods, const uint8_t* d_x, size_t nx, const uint8_t* d_e, size_t ne, const GtTerm* terms, const size_t* offsets, size_t S,
+                  uint64_t* out_gt) {
+  if (S == 0) return GM_OK;
+  GM_CHECK(offsets[0] == 0, GM_EINVAL, "gt_checks: offsets[0] = %zu", offsets[0]);
+  for (size_t s = 0; s < S; s++) {
+    GM_CHECK(offsets[s] < offsets[s + 1] && prods[s].s0.n + prods[s].s1.n > 0, GM_EINVAL, "gt_checks: check %zu has an empty product", s);
+    for (size_t i = offsets[s]; i < offsets[s + 1]; i++)
+      GM_CHECK(terms[i].x < nx && terms[i].e < ne, GM_EINVAL, "gt_checks: term %zu names element %u of %zu, exponent %u of %zu", i, terms[i].x, nx, terms[i].e, ne);
+  }
+  GM_CHECK(offsets[S] <= GT_EACH_MAX && S <= GT_EACH_MAX / 2, GM_EINVAL, "gt_checks: %zu terms in %zu checks (at most 2^20 terms)", offsets[S], S);
+  GtTmp res(C);  // the S pairing values, then the S powers: the two launch groups share the level buffers of the workspace
+  GM_HIP(dev_malloc((void**)&res.p, 2 * S * GT_BYTES));
+  SegTables pt;
+  GtSegTables gt;
+  uint8_t* d = nullptr;
+  int rc = miller_products_launch(C, prods, S, pt, &d);
+  if (!rc) rc = gt_final_exp_launch(C, d, S, 1, res.p);
+  if (!rc) rc = gt_multi_pow_seg_launch(C, d_x, d_e, terms, offsets, S, gt, &d);
+  if (!rc) {
+    const hipError_t e = hipMemcpyAsync(res.p + S * GT_BYTES, d, S * GT_BYTES, hipMemcpyDeviceToDevice, C->stream);
+    if (e != hipSuccess) rc = gm::hip_fail(e, "hipMemcpyAsync", __FILE__, __LINE__);
+  }
+  if (!rc) rc = gt_to_host(C, res.p, 2 * S, out_gt);  // the one wait: the tables of `pt` and `gt` are read by their copies until here
+  if (rc) (void)hipStreamSynchronize(C->stream);
+  return rc;
 }
 
 // gm_debug_gt_op

@@ -1093,6 +1093,31 @@ int debug_op_run(Context* C, K kernel, int op, const uint32_t* a, size_t aw, con
 }
 
 }  // namespace
+
+// The group elements of many proofs at once (ipa.hip: ipa_verify_many): Jacobian points of both groups, any representative ->
+// the host records the proof checks build (r1: 12 limbs, r2: 24 limbs per point) and one GM_PT_* status byte per point, from ONE
+// k_pt_check launch per non-empty group.  Caller holds the MSM lock.
+int jac_points_status(Context* C, const std::vector<const uint64_t*>& g1, const std::vector<const uint64_t*>& g2, std::vector<uint64_t>& r1, std::vector<uint64_t>& r2,
+                      std::vector<uint8_t>& st1, std::vector<uint8_t>& st2) {
+  const size_t n1 = g1.size(), n2 = g2.size();
+  r1.assign(n1 * 12, 0);
+  r2.assign(n2 * 24, 0);
+  st1.assign(n1, 0);
+  st2.assign(n2, 0);
+  for (size_t i = 0; i < n1; i++) proof_g1_record(g1[i], r1.data() + 12 * i);
+  for (size_t i = 0; i < n2; i++) proof_g2_record(g2[i], r2.data() + 24 * i);
+  DevTmp stage;
+  if (n1 + n2) {
+    GM_HIP(dev_malloc(&stage.p, n1 * 96 + n2 * 192));
+    if (n1) GM_HIP(hipMemcpyAsync(stage.p, r1.data(), n1 * 96, hipMemcpyHostToDevice, C->stream));
+    if (n2) GM_HIP(hipMemcpyAsync(stage.u8() + n1 * 96, r2.data(), n2 * 192, hipMemcpyHostToDevice, C->stream));
+  }
+  int ok1 = 0, ok2 = 0;
+  int rc = check_run<PtG1>(C, stage.u8(), 96, 1, n1, st1.data(), nullptr, &ok1);
+  if (!rc) rc = check_run<PtG2>(C, stage.u8() + n1 * 96, 192, 1, n2, st2.data(), nullptr, &ok2);
+  if (rc) (void)hipStreamSynchronize(C->stream);  // nothing in flight reads the stage once it goes
+  return rc;
+}
 }  // namespace gm
 
 using namespace gm;

@@ -258,6 +258,31 @@ class InnerProductProof:
                                              capi.ptr(capi.u64(comm_b).reshape(36)), capi.ptr(capi.u64(y_mont).reshape(4)), C.byref(ok)))
         return bool(ok.value)
 
+    @staticmethod
+    def verify_many(proofs, vrs: Vrs, comm_as, comm_bs, ys) -> list:
+        """gm_ipa_verify_many: [proofs[s].verify_transcript(vrs, comm_as[s], comm_bs[s], ys[s]) for every s] from ONE launch
+        group, whatever the number of proofs; they may differ in their number of rounds.  A proof with an element outside its
+        group is answered by the per-proof path, so the list is the single entry's for every input."""
+        capi.ensure_init()
+        S = len(proofs)
+        hs = np.array([p.handle for p in proofs], dtype=np.uint64)
+        ca, cb, y = capi.u64(comm_as).reshape(S, 18), capi.u64(comm_bs).reshape(S, 36), capi.u64(ys).reshape(S, 4)
+        ok = np.zeros(max(S, 1), dtype=np.intc)
+        capi.check(capi.load().gm_ipa_verify_many(capi.ptr(hs) if S else None, C.c_uint64(vrs.handle), capi.ptr(ca) if S else None, capi.ptr(cb) if S else None,
+                                                  capi.ptr(y) if S else None, C.c_size_t(S), capi.ptr(ok)))
+        return [bool(v) for v in ok[:S]]
+
+    def stated_terms(self, y_mont):
+        """gm_debug_ipa_stated_terms, a test aid: the exponents of the one product in GT that verify_many states for this proof,
+        as integers -- (6 rounds - 4 for the GT terms, 2 rounds + 4 for the pairing terms), in the order of tests/ipa_flat_ref.py"""
+        n = C.c_size_t()
+        capi.check(capi.load().gm_ipa_rounds(C.c_uint64(self.handle), C.byref(n)))
+        r = n.value
+        g, p = np.zeros((max(6 * r - 4, 1), 4), dtype=np.uint64), np.zeros((2 * r + 4, 4), dtype=np.uint64)
+        capi.check(capi.load().gm_debug_ipa_stated_terms(C.c_uint64(self.handle), capi.ptr(capi.u64(y_mont).reshape(4)), capi.ptr(g), capi.ptr(p)))
+        to_int = lambda row: sum(int(v) << (64 * k) for k, v in enumerate(row))  # noqa: E731
+        return [to_int(e) for e in g[: 6 * r - 4]], [to_int(e) for e in p]
+
     def check_points(self):
         """gm_ipa_check: every G1 and G2 element verify_transcript reads from the proof (the G1 ones first); a points.ProofCheckResult.
         The GT elements of the messages are checked by `check_messages`."""
@@ -282,3 +307,18 @@ class InnerProductProof:
         if self.handle:
             capi.check(capi.load().gm_ipa_free(C.c_uint64(self.handle)))
             self.handle = 0
+
+
+def set_verify_many_min(proofs: int):
+    """gm_set_ipa_verify_many_min: fewer proofs than this make InnerProductProof.verify_many run them one by one, as
+    verify_transcript does.  Verdicts do not depend on it (profiles/ipa_verify_many.md has the measurement behind the default)."""
+    capi.ensure_init()
+    capi.check(capi.load().gm_set_ipa_verify_many_min(C.c_size_t(proofs)))
+
+
+def verify_many_path() -> tuple:
+    """gm_debug_ipa_verify_many_path: (proofs of the last verify_many call that took the batched path, proofs that took the per-proof path)"""
+    capi.ensure_init()
+    counts = (C.c_size_t * 2)()
+    capi.check(capi.load().gm_debug_ipa_verify_many_path(counts))
+    return int(counts[0]), int(counts[1])

@@ -71,6 +71,26 @@ def gt_multi_pow(x, scalars) -> np.ndarray:
     return out
 
 
+def gt_multi_pow_many(x, scalars, offsets) -> np.ndarray:
+    """S = len(offsets) - 1 independent products in one launch (gm_gt_multi_pow_many): out[s] = prod of x_i^scalars_i over
+    offsets[s] <= i < offsets[s + 1], an empty product is 1; -> (S, 72).  x and scalars as gt_multi_pow takes them.  Each row is bit
+    for bit gt_multi_pow on its range."""
+    capi.ensure_init()
+    xs = capi.u64(x).reshape(-1, 72)
+    if isinstance(scalars, np.ndarray) and scalars.dtype == np.uint64:
+        sc = capi.u64(scalars).reshape(-1, 4)
+    else:
+        ints = [int(s) for s in scalars]
+        assert all(0 <= s < (1 << 256) for s in ints)
+        sc = np.array([[(s >> (64 * k)) & 0xFFFFFFFFFFFFFFFF for k in range(4)] for s in ints], dtype=np.uint64).reshape(-1, 4)
+    off = np.ascontiguousarray(offsets, dtype=np.uintp)
+    S = len(off) - 1
+    assert S >= 0 and (S == 0 or int(off.max()) <= min(len(xs), len(sc))), "the offsets run past the terms"
+    out = np.empty((max(S, 0), 72), dtype=np.uint64)
+    capi.check(capi.load().gm_gt_multi_pow_many(capi.ptr(xs) if len(xs) else None, capi.ptr(sc) if len(sc) else None, capi.ptr(off), C.c_size_t(S), capi.ptr(out) if S else None))
+    return out
+
+
 def gt_final_exp(f) -> np.ndarray:
     """f^((q^12 - 1) / r) for any Fq12 element, no conjugation: a test and integration aid (gm_gt_final_exp)"""
     out = np.empty(72, dtype=np.uint64)

@@ -593,6 +593,12 @@ int gm_hp_free(uint64_t handle);
  * has_msg = 0 further rounds answer has_msg = 0 and folds are applied, as for gm_hg1_* / gm_hg2_*.  gm_hgt_final: f[0] (72 limbs)
  * and g[0] (4 limbs) once the rounds are done.  A handle of another module is GM_EHANDLE. */
 int gm_gt_multi_pow(const uint64_t* x /* n x 72 */, size_t n, const uint64_t* scalars_canonical /* n x 4 */, uint64_t out_gt[72]);
+/* S independent products: out[s] = prod_{i in [offsets[s], offsets[s+1])} x_i^e_i; offsets[0] = 0, S + 1 entries, an empty
+ * product is 1.  Each out[s] is bit for bit gm_gt_multi_pow on that range, on ANY 12 reduced Fq coefficients.  ONE
+ * exponentiation launch (k_gt_multi_pow_seg: one lane per term, the block multiplies per product), the reduction levels of the
+ * longest product, one wait, whatever S is.  S = 0 does nothing.  GM_EINVAL: descending offsets, offsets[0] != 0, null pointers with
+ * terms to read, more than 2^20 terms.  Shares the MSM lock. */
+int gm_gt_multi_pow_many(const uint64_t* x /* n x 72 */, const uint64_t* scalars_canonical /* n x 4 */, const size_t* offsets, size_t S, uint64_t* out_gt /* S x 72 */);
 int gm_hgt_new(const uint64_t* f_gt /* nf x 72 */, size_t nf, const uint64_t* g_mont, size_t ng, const uint64_t twist_mont[4], uint64_t* handle);
 int gm_hgt_round(uint64_t handle, const uint64_t* challenge_or_null, uint64_t a_gt[72], uint64_t b_gt[72], int* has_msg);
 int gm_hgt_fold(uint64_t handle, const uint64_t challenge_mont[4]);
@@ -706,6 +712,28 @@ int gm_ipa_from_fields(size_t rounds, const uint64_t* messages, const uint64_t* 
 /* InnerProductProof::verify_transcript(vrs, comm_a, comm_b, y): *ok = 1 iff the proof verifies.  Its pairings are one segmented
  * launch on the device.  A Vrs with fewer than rounds - 1 levels gives GM_EINVAL. */
 int gm_ipa_verify(uint64_t proof, uint64_t vrs, const uint64_t comm_a_jac[18], const uint64_t comm_b_jac[36], const uint64_t y_mont[4], int* ok);
+/* ok[s] = what gm_ipa_verify answers for proofs[s] with comm_a[s], comm_b[s], y[s] under `vrs`, for every s; fails as a whole
+ * (negative code) exactly where one of the single calls, made in order, would.  Proofs may differ in their number of rounds.
+ * verify_transcript is linear in the claim, so a proof of R rounds is ONE product in GT: 6 R - 4 powers of elements the verifier is
+ * handed (the messages, the Vrs entries) times the final exponentiation of 2 R + 1 pairs whose exponents have moved onto the G1 side
+ * (gemini_amd/csrc/ipa.hip states the terms, tests/ipa_flat_ref.py repeats them on integers).  All proofs share one launch group:
+ * one gm_g1_lincomb_many group, one segmented Miller launch with a segment per proof, one final-exponentiation launch, one
+ * k_gt_multi_pow_seg launch, the reduction levels of the longest proof; launches and waits do not depend on S.
+ * Equal verdicts hold for EVERY input: the unrolling is valid for members only, so the entry first runs the GT membership test over
+ * every message and the curve-and-subgroup tests over every G1 and G2 point the proofs and the caller supply (one launch each for
+ * all proofs), and a proof with a failing element, or a scalar that is not reduced, gets its verdict from gm_ipa_verify's own path.
+ * Only elements that passed reach the batched kernels, and none of those addresses memory by the value of an element.  The Vrs is
+ * the library's own (gm_vrs_from_crs) and is trusted, as gm_ipa_verify trusts it.
+ * gm_set_ipa_verify_many_min: fewer proofs than this run one by one; verdicts never depend on it.  Default 2, from
+ * profiles/ipa_verify_many.md at d = 2^10: S = 1 is a tie, 69.6 (66.4-71.3) ms batched against 71.2 (69.3-72.5) ms single; S = 2 is the
+ * first row where the batched call wins beyond the spread, 66.2 (66.1-67.3) ms against 140.5 (140.3-144.4) ms.  gm_debug_ipa_verify_many_path: counts[0] = proofs of the last call that took the batched path, counts[1] = proofs
+ * that took the per-proof path.  gm_debug_ipa_stated_terms, a test aid: the canonical exponents (4 limbs each) the host states for
+ * one proof, 6 R - 4 for the GT terms and 2 R + 4 for the pairing terms, in the order ipa.hip lists them; no kernel runs. */
+int gm_ipa_verify_many(const uint64_t* proofs /* S handles */, uint64_t vrs, const uint64_t* comm_a_jac /* S x 18 */, const uint64_t* comm_b_jac /* S x 36 */,
+                       const uint64_t* y_mont /* S x 4 */, size_t S, int* ok);
+int gm_set_ipa_verify_many_min(size_t proofs);
+int gm_debug_ipa_verify_many_path(size_t counts[2]);
+int gm_debug_ipa_stated_terms(uint64_t proof, const uint64_t y_mont[4], uint64_t* gt_exponents, uint64_t* pairing_exponents);
 
 /* ---- Fiat-Shamir transcript (host; no GPU needed) ------------------------------------------------ */
 /* merlin::Transcript::new(label) (merlin 3.0.0, Cargo.lock:606-608); the prover uses

@@ -782,6 +782,16 @@ inline Gt gt_multi_pow(const std::vector<Gt>& x, const std::vector<BigInt>& scal
   check(gm_gt_multi_pow(n ? x[0].data() : nullptr, n, n ? scalars[0].data() : nullptr, r.data()));
   return r;
 }
+// S = offsets.size() - 1 independent products in one launch (gm_gt_multi_pow_many): out[s] is over the terms offsets[s] <= i <
+// offsets[s + 1], bit for bit gt_multi_pow on that range; an empty product is 1
+inline std::vector<Gt> gt_multi_pow_many(const std::vector<Gt>& x, const std::vector<BigInt>& scalars, const std::vector<size_t>& offsets) {
+  if (offsets.empty()) throw Error(GM_EINVAL, "gt_multi_pow_many: offsets needs S + 1 entries");
+  if (offsets.back() > x.size() || offsets.back() > scalars.size()) throw Error(GM_EINVAL, "gt_multi_pow_many: the offsets run past the terms");
+  std::vector<Gt> out(offsets.size() - 1);
+  check(gm_gt_multi_pow_many(x.empty() ? nullptr : x[0].data(), scalars.empty() ? nullptr : scalars[0].data(), offsets.data(), out.size(),
+                             out.empty() ? nullptr : out[0].data()));
+  return out;
+}
 namespace detail {
 // TimeProver<GtModule>: f in GT, g in Fr, messages in GT
 struct HerringGtModule {
@@ -1082,6 +1092,20 @@ class InnerProductProof {  // ipa.rs:54-60
     int ok = 0;
     check(gm_ipa_verify(h_, vrs.handle(), comm_a.data(), comm_b.data(), y.data(), &ok));
     return ok != 0;
+  }
+  // [proofs[s]->verify_transcript(vrs, comm_a[s], comm_b[s], y[s]) for every s] from ONE launch group whatever their number
+  // (gm_ipa_verify_many); the proofs may differ in their rounds, and the answers are the single entry's for every input
+  static std::vector<bool> verify_many(const std::vector<const InnerProductProof*>& proofs, const Vrs& vrs, const std::vector<G1Projective>& comm_a,
+                                       const std::vector<G2Projective>& comm_b, const std::vector<Fr>& y) {
+    const size_t S = proofs.size();
+    if (comm_a.size() != S || comm_b.size() != S || y.size() != S) throw Error(GM_EINVAL, "InnerProductProof::verify_many: one commitment pair and one y per proof");
+    std::vector<uint64_t> h(S);
+    for (size_t s = 0; s < S; s++) h[s] = proofs[s]->handle();
+    std::vector<int> ok(S, 0);
+    check(gm_ipa_verify_many(h.data(), vrs.handle(), S ? comm_a[0].data() : nullptr, S ? comm_b[0].data() : nullptr, S ? y[0].data() : nullptr, S, ok.data()));
+    std::vector<bool> r(S);
+    for (size_t s = 0; s < S; s++) r[s] = ok[s] != 0;
+    return r;
   }
   uint64_t handle() const { return h_; }
 
