@@ -11,6 +11,7 @@
 #include <algorithm>
 
 #include "groups.cuh"
+#include "host_field.hpp"
 
 namespace gm {
 
@@ -90,6 +91,84 @@ __global__ __launch_bounds__(G::KEY_BLOCK) void k_split_fold(const uint8_t* __re
   G::store_affine(out + i * G::AFF_BYTES, grp_to_affine<G>(acc));
 }
 
+// The segmented form: lane i folds pair i % m of span i / m, m = (n + 1) / 2 -- the spans of many proofs in one launch, each under
+// the scalar its table entry names (row `ch` of s8).  Lanes of one wave may belong to spans with different scalars, so the scalar
+// is the lane's own (eight registers) and the bit test is per lane: the doublings run in step, an addition runs under the mask of
+// the lanes whose bit is set.  (FoldSpan: ctx.hpp.)
+template <class G>
+__global__ __launch_bounds__(G::KEY_BLOCK) void k_split_fold_seg(const FoldSpan* __restrict__ spans, size_t nspans, size_t n, const uint32_t* __restrict__ s8) {
+  const size_t m = (n + 1) / 2;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nspans * m) return;
+  const FoldSpan sp = spans[i / m];
+  const size_t k = i % m;
+  typename G::Xyzz acc = G::identity();
+  if (2 * k + 1 < n) {
+    uint32_t s[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) s[j] = s8[(size_t)sp.ch * 8 + j];
+    const typename G::Affine hi = G::load_affine(sp.in + (2 * k + 1) * G::AFF_BYTES);
+#pragma unroll 1
+    for (int w = 7; w >= 0; w--) {
+      uint32_t bits = s[7];  // the top word, then the scalar moves up by one word: no register is indexed by the loop counter
+#pragma unroll
+      for (int j = 7; j > 0; j--) s[j] = s[j - 1];
+#pragma unroll 1
+      for (int b = 0; b < 32; b++) {
+        acc = G::dbl(acc);
+        if (bits >> 31) G::madd(acc, hi);
+        bits <<= 1;
+      }
+    }
+  }
+  G::madd(acc, G::load_affine(sp.in + (2 * k) * G::AFF_BYTES));
+  G::store_affine(sp.out + k * G::AFF_BYTES, grp_to_affine<G>(acc));
+}
+
+// ---- short linear combinations over either group (gm_g2_lincomb_many; the module messages of ipa.hip's lockstep prover) -------
+// One lane per TERM makes the multiple by the loop of k_split_fold (one XYZZ accumulator and one affine point in the lane), one
+// lane per SEGMENT adds its terms up with the complete addition, k_normalise normalises the sums.  A term names its point and its
+// scalar through optional index tables, so the terms of many proofs can read vectors where they lie.  (G1's own pair for host
+// records, k_g1_term_mul / k_g1_seg_sum of msm.hip, stays as it is.)
+template <class G>
+__global__ __launch_bounds__(G::KEY_BLOCK) void k_term_mul(const uint8_t* __restrict__ points, const uint32_t* __restrict__ pidx, const uint8_t* __restrict__ scalars,
+                                                            const uint32_t* __restrict__ sidx, int mont, size_t nterms, uint8_t* __restrict__ out_xyzz) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nterms) return;
+  Fr sc = fp_load<FrParams>(reinterpret_cast<const uint32_t*>(scalars + (size_t)(sidx ? sidx[t] : t) * 32));
+  if (mont) sc = fp_from_mont<FrParams>(sc);
+  uint32_t s[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) s[j] = sc.l[j];
+  const typename G::Affine p = G::load_affine(points + (size_t)(pidx ? pidx[t] : t) * G::AFF_BYTES);
+  typename G::Xyzz acc = G::identity();
+#pragma unroll 1
+  for (int w = 7; w >= 0; w--) {
+    uint32_t bits = s[7];
+#pragma unroll
+    for (int j = 7; j > 0; j--) s[j] = s[j - 1];
+#pragma unroll 1
+    for (int b = 0; b < 32; b++) {
+      acc = G::dbl(acc);
+      if (bits >> 31) G::madd(acc, p);
+      bits <<= 1;
+    }
+  }
+  G::store_xyzz(out_xyzz + t * G::XYZZ_BYTES, acc);
+}
+// out[s] = the sum of the records [offsets[s], offsets[s + 1]); an empty segment is the identity.  G::add is complete: two equal
+// terms double, opposite ones cancel.
+template <class G>
+__global__ __launch_bounds__(G::KEY_BLOCK) void k_seg_sum(const uint8_t* __restrict__ terms_xyzz, const unsigned long long* __restrict__ offsets, size_t nseg,
+                                                           uint8_t* __restrict__ out_xyzz) {
+  const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= nseg) return;
+  typename G::Xyzz acc = G::identity();
+#pragma unroll 1
+  for (unsigned long long t = offsets[s]; t < offsets[s + 1]; t++) G::add(acc, G::load_xyzz(terms_xyzz + (size_t)t * G::XYZZ_BYTES));
+  G::store_xyzz(out_xyzz + s * G::XYZZ_BYTES, acc);
+}
+
 // Batched normalisation, Montgomery's trick inside a lane: prefix products of t_k = zz_k zzz_k, ONE inversion (over Fq2: in Fq, of
 // the norm) and the back-substitution, per group of `group` <= NORM_K points -- a Fermat inversion is ~570 products.  Point k of the group is
 // in[INDEXED ? idx[i0 + k] : i0 + k]; identity records (zz = 0) stay out of the products and give the all-zero affine record.
@@ -167,6 +246,72 @@ int normalise_launch(hipStream_t st, const uint8_t* in, const uint32_t* d_idx, s
   if (d_idx) hipLaunchKernelGGL((k_normalise<G, true>), grid, block, 0, st, in, d_idx, n, group, out);
   else hipLaunchKernelGGL((k_normalise<G, false>), grid, block, 0, st, in, d_idx, n, group, out);
   GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+template <class G>
+int split_fold_seg_launch(hipStream_t st, const FoldSpan* d_spans, size_t nspans, size_t n, const uint32_t* d_s8) {
+  const size_t lanes = nspans * ((n + 1) / 2);
+  if (lanes == 0) return GM_OK;
+  hipLaunchKernelGGL(k_split_fold_seg<G>, dim3((unsigned)((lanes + G::KEY_BLOCK - 1) / G::KEY_BLOCK)), dim3(G::KEY_BLOCK), 0, st, d_spans, nspans, n, d_s8);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+template <class G>
+int term_mul_launch(hipStream_t st, const uint8_t* d_points, const uint32_t* d_pidx, const uint8_t* d_scalars, const uint32_t* d_sidx, int mont, size_t T, uint8_t* d_out) {
+  if (T == 0) return GM_OK;
+  hipLaunchKernelGGL(k_term_mul<G>, dim3((unsigned)((T + G::KEY_BLOCK - 1) / G::KEY_BLOCK)), dim3(G::KEY_BLOCK), 0, st, d_points, d_pidx, d_scalars, d_sidx, mont, T, d_out);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+template <class G>
+int seg_sum_launch(hipStream_t st, const uint8_t* d_in, const unsigned long long* d_off, size_t S, uint8_t* d_out) {
+  if (S == 0) return GM_OK;
+  hipLaunchKernelGGL(k_seg_sum<G>, dim3((unsigned)((S + G::KEY_BLOCK - 1) / G::KEY_BLOCK)), dim3(G::KEY_BLOCK), 0, st, d_in, d_off, S, d_out);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+// gm_g2_lincomb_many: host records and canonical scalars staged in C->lincomb, three launches, one wait
+int g2_lincomb_many_host(Context* C, const void* points, size_t stride, const uint64_t* scalars_canonical, const size_t* offsets, size_t S, uint64_t* out_jac) {
+  using G = GrpG2;
+  if (S == 0) return GM_OK;
+  GM_CHECK(stride >= G::AFF_BYTES && (stride % 8) == 0, GM_EINVAL, "g2_lincomb_many: stride %zu must be >= %zu and a multiple of 8", stride, G::AFF_BYTES);
+  GM_CHECK(offsets[0] == 0, GM_EINVAL, "g2_lincomb_many: offsets[0] = %zu, the first segment starts at 0", offsets[0]);
+  for (size_t s = 0; s < S; s++)
+    GM_CHECK(offsets[s] <= offsets[s + 1], GM_EINVAL, "g2_lincomb_many: offsets[%zu] = %zu is above offsets[%zu] = %zu", s, offsets[s], s + 1, offsets[s + 1]);
+  const size_t T = offsets[S];
+  GM_CHECK(T <= ((size_t)1 << 28) && S <= ((size_t)1 << 28), GM_EINVAL, "g2_lincomb_many: %zu terms in %zu segments (at most 2^28 of either)", T, S);
+  static_assert(sizeof(size_t) == sizeof(unsigned long long), "the offsets are copied as they are");
+  auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
+  const size_t o_raw = 0, o_pts = o_raw + up(T * stride), o_sc = o_pts + up(T * G::AFF_BYTES), o_off = o_sc + up(T * 32), o_terms = o_off + up((S + 1) * 8),
+               o_sums = o_terms + T * G::XYZZ_BYTES, o_aff = o_sums + S * G::XYZZ_BYTES, total = o_aff + S * G::AFF_BYTES;
+  GM_MSM_LOCK(C);
+  int rc = C->lincomb.ensure(total);
+  if (rc) return rc;
+  uint8_t* w = C->lincomb.as<uint8_t>();
+  hipStream_t st = C->stream;
+  std::vector<uint64_t> aff(24 * S);
+  auto enqueue = [&]() -> int {
+    GM_HIP(hipMemcpyAsync(w + o_off, offsets, (S + 1) * 8, hipMemcpyHostToDevice, st));
+    if (T) {
+      GM_HIP(hipMemcpyAsync(w + o_raw, points, T * stride, hipMemcpyHostToDevice, st));
+      GM_HIP(hipMemcpyAsync(w + o_sc, scalars_canonical, T * 32, hipMemcpyHostToDevice, st));
+      int r = pack_launch<G>(st, w + o_raw, stride, T, w + o_pts);
+      if (!r) r = term_mul_launch<G>(st, w + o_pts, nullptr, w + o_sc, nullptr, 0, T, w + o_terms);
+      if (r) return r;
+    }
+    int r = seg_sum_launch<G>(st, w + o_terms, reinterpret_cast<const unsigned long long*>(w + o_off), S, w + o_sums);
+    if (!r) r = normalise_launch<G>(st, w + o_sums, nullptr, S, w + o_aff);  // o_aff lies behind o_sums: apart, as the kernel needs
+    if (r) return r;
+    GM_HIP(hipMemcpyAsync(aff.data(), w + o_aff, S * G::AFF_BYTES, hipMemcpyDeviceToHost, st));
+    return GM_OK;
+  };
+  rc = enqueue();
+  const hipError_t e = hipStreamSynchronize(st);  // the host arrays are read by their copies until here
+  if (rc) return rc;
+  GM_HIP(e);
+  for (size_t s = 0; s < S; s++) gmh::g2_affine_to_jac_dev(aff.data() + 24 * s).to_limbs(out_jac + 36 * s);
   return GM_OK;
 }
 
@@ -257,5 +402,16 @@ int g1_pack_launch(hipStream_t st, const uint8_t* src, size_t stride, size_t n, 
 int g1_normalise_launch(hipStream_t st, const uint8_t* in, size_t n, uint8_t* out) { return normalise_launch<GrpG1>(st, in, nullptr, n, out); }
 int g1_split_fold_launch(Context* C, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out) { return split_fold_launch<GrpG1>(C->stream, in, n, d_s8, out); }
 int g2_split_fold_launch(Context* C, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out) { return split_fold_launch<GrpG2>(C->stream, in, n, d_s8, out); }
+int g1_split_fold_seg_launch(Context* C, const FoldSpan* d_spans, size_t nspans, size_t n, const uint32_t* d_s8) { return split_fold_seg_launch<GrpG1>(C->stream, d_spans, nspans, n, d_s8); }
+int g2_split_fold_seg_launch(Context* C, const FoldSpan* d_spans, size_t nspans, size_t n, const uint32_t* d_s8) { return split_fold_seg_launch<GrpG2>(C->stream, d_spans, nspans, n, d_s8); }
+int g1_term_mul_launch(Context* C, const uint8_t* d_points, const uint32_t* d_pidx, const uint8_t* d_scalars, const uint32_t* d_sidx, int mont, size_t T, uint8_t* d_out_xyzz) {
+  return term_mul_launch<GrpG1>(C->stream, d_points, d_pidx, d_scalars, d_sidx, mont, T, d_out_xyzz);
+}
+int g2_term_mul_launch(Context* C, const uint8_t* d_points, const uint32_t* d_pidx, const uint8_t* d_scalars, const uint32_t* d_sidx, int mont, size_t T, uint8_t* d_out_xyzz) {
+  return term_mul_launch<GrpG2>(C->stream, d_points, d_pidx, d_scalars, d_sidx, mont, T, d_out_xyzz);
+}
+int g1_seg_sum_launch(Context* C, const uint8_t* d_in_xyzz, const unsigned long long* d_off, size_t S, uint8_t* d_out_xyzz) { return seg_sum_launch<GrpG1>(C->stream, d_in_xyzz, d_off, S, d_out_xyzz); }
+int g2_seg_sum_launch(Context* C, const uint8_t* d_in_xyzz, const unsigned long long* d_off, size_t S, uint8_t* d_out_xyzz) { return seg_sum_launch<GrpG2>(C->stream, d_in_xyzz, d_off, S, d_out_xyzz); }
+int g2_normalise_launch(hipStream_t st, const uint8_t* in, size_t n, uint8_t* out) { return normalise_launch<GrpG2>(st, in, nullptr, n, out); }
 
 }  // namespace gm

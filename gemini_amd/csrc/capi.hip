@@ -1057,6 +1057,14 @@ int gm_g1_lincomb_many(const void* points, size_t stride, const uint64_t* scalar
   GM_CHECK((points != nullptr && scalars_canonical != nullptr) || offsets[S] == 0, GM_EINVAL, "lincomb_many: null pointer");
   return g1_lincomb_many_host(C, points, stride, scalars_canonical, offsets, S, out_jac);
 }
+// the G2 twin (bases.hip: k_term_mul, k_seg_sum over the group description)
+int gm_g2_lincomb_many(const void* points, size_t stride, const uint64_t* scalars_canonical, const size_t* offsets, size_t S, uint64_t* out_jac) {
+  GM_CTX();
+  if (S == 0) return GM_OK;
+  GM_CHECK(offsets != nullptr && out_jac != nullptr, GM_EINVAL, "g2_lincomb_many: null pointer");
+  GM_CHECK((points != nullptr && scalars_canonical != nullptr) || offsets[S] == 0, GM_EINVAL, "g2_lincomb_many: null pointer");
+  return g2_lincomb_many_host(C, points, stride, scalars_canonical, offsets, S, out_jac);
+}
 
 int gm_g1_msm_h(uint64_t handle, size_t offset, int reversed, const uint64_t* scalars, size_t n, uint64_t out_jac[18]) {
   GM_CTX();
@@ -2461,6 +2469,44 @@ int gm_ipa_verify_many(const uint64_t* proofs, uint64_t vrs, const uint64_t* com
     }
   }
   return ipa_verify_many(C, ps.data(), v, comm_a_jac, comm_b_jac, y_mont, S, ok);
+}
+int gm_ipa_new_many(const uint64_t* transcripts, uint64_t crs, const uint64_t* a_mont, const uint64_t* b_mont, size_t d, size_t S, uint64_t* proofs) {
+  GM_CTX();
+  if (S == 0) {  // no single call would be made
+    GM_MSM_LOCK(C);
+    memset(C->ipa_new_many_last, 0, sizeof C->ipa_new_many_last);
+    return GM_OK;
+  }
+  GM_CHECK(transcripts && a_mont && b_mont && proofs, GM_EINVAL, "ipa_new_many: null pointer");
+  GM_IPA_FIND(c, crs, crs, "ipa_new_many", "CRS");
+  for (size_t s = 0; s < S; s++) {
+    GM_CHECK(transcript_exists(transcripts[s]), GM_EHANDLE, "ipa_new_many: unknown transcript handle %llu (proof %zu)", (unsigned long long)transcripts[s], s);
+    for (size_t t = 0; t < s; t++)
+      GM_CHECK(transcripts[t] != transcripts[s], GM_EINVAL, "ipa_new_many: proofs %zu and %zu name the same transcript; two proofs cannot share one", t, s);
+  }
+  std::vector<std::unique_ptr<IpaProof>> ps(S);
+  std::vector<IpaProof*> raw(S);
+  for (size_t s = 0; s < S; s++) {
+    ps[s] = std::make_unique<IpaProof>();
+    raw[s] = ps[s].get();
+  }
+  int rc = ipa_prove_many(C, transcripts, c, a_mont, b_mont, d, S, raw.data());
+  if (rc) return rc;  // no handle exists
+  for (size_t s = 0; s < S; s++) proofs[s] = put_in(C, C->ipa, std::move(ps[s]));
+  return GM_OK;
+}
+int gm_set_ipa_new_many_min(size_t proofs) {
+  GM_CTX();
+  GM_MSM_LOCK(C);
+  C->ipa_new_many_min = proofs;
+  return GM_OK;
+}
+int gm_debug_ipa_new_many_path(size_t counts[4]) {
+  GM_CTX();
+  GM_CHECK(counts != nullptr, GM_EINVAL, "gm_debug_ipa_new_many_path: null output");
+  GM_MSM_LOCK(C);
+  memcpy(counts, C->ipa_new_many_last, sizeof C->ipa_new_many_last);
+  return GM_OK;
 }
 int gm_set_ipa_verify_many_min(size_t proofs) {
   GM_CTX();

@@ -382,6 +382,11 @@ struct Context {
   // (gm_debug_ipa_verify_many_path): proofs on the batched path, proofs on the per-proof path
   size_t ipa_verify_many_min = 2;  // S = 1 is a tie (69.6 against 71.2 ms), S = 2 wins 66 against 140 ms: profiles/ipa_verify_many.md
   size_t ipa_verify_many_last[2] = {0, 0};
+  // gm_ipa_new_many: fewer proofs than this take ipa_prove one by one (gm_set_ipa_new_many_min); what the last call did
+  // (gm_debug_ipa_new_many_path): proofs on the lockstep path, proofs on the per-proof path, kernel launches and stream waits of
+  // the lockstep path
+  size_t ipa_new_many_min = 2;  // S = 1 loses (1004 against 670 ms), S = 2 wins 1014 (max 1017) against 1337 (min 1334) ms at d = 2^10: profiles/ipa_new_many.md
+  size_t ipa_new_many_last[4] = {0, 0, 0, 0};
   DevBuf fr_scratch;
   uint64_t* host_small = nullptr;  // pinned, 64 KiB, for small results
   // the descriptor arrays of k_sc_round_multi: a RING of SC_DESC_SLOTS slots of SC_DESC_SLOT bytes, one per launch, pinned on the host
@@ -538,6 +543,27 @@ int g1_normalise_launch(hipStream_t st, const uint8_t* in, size_t n, uint8_t* ou
 // out[i] = in[2i] + s in[2i+1] over packed affine records (an odd tail folds against the identity), s at d_s8 (canonical, 8 x u32), on C->stream
 int g1_split_fold_launch(Context* C, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out);
 int g2_split_fold_launch(Context* C, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out);
+// The segmented form (k_split_fold_seg): span k folds its n records at `in` to (n + 1) / 2 records at `out` by the canonical scalar
+// in row `ch` of the table d_s8 (8 x u32 a row) -- the spans of many proofs in one launch, every proof under its own challenge.
+// All spans of a launch have the same length n; the table of spans is on the device.  On C->stream without a wait.
+struct FoldSpan {
+  const uint8_t* in;
+  uint8_t* out;
+  uint32_t ch, pad;
+};
+int g1_split_fold_seg_launch(Context* C, const FoldSpan* d_spans, size_t nspans, size_t n, const uint32_t* d_s8);
+int g2_split_fold_seg_launch(Context* C, const FoldSpan* d_spans, size_t nspans, size_t n, const uint32_t* d_s8);
+// Short linear combinations over vectors that are on the device already (k_term_mul, k_seg_sum, k_normalise; bases.hip), each a
+// launch on C->stream without a wait.  term_mul: out[t] = scalar[sidx ? sidx[t] : t] * point[pidx ? pidx[t] : t] in XYZZ, the
+// scalars 32-byte records, Fr in Montgomery form when `mont`, else canonical.  seg_sum: out[s] = the sum of in[off[s] .. off[s + 1])
+// with the complete addition.  g2_normalise_launch: as g1_normalise_launch.
+int g1_term_mul_launch(Context* C, const uint8_t* d_points, const uint32_t* d_pidx, const uint8_t* d_scalars, const uint32_t* d_sidx, int mont, size_t T, uint8_t* d_out_xyzz);
+int g2_term_mul_launch(Context* C, const uint8_t* d_points, const uint32_t* d_pidx, const uint8_t* d_scalars, const uint32_t* d_sidx, int mont, size_t T, uint8_t* d_out_xyzz);
+int g1_seg_sum_launch(Context* C, const uint8_t* d_in_xyzz, const unsigned long long* d_off, size_t S, uint8_t* d_out_xyzz);
+int g2_seg_sum_launch(Context* C, const uint8_t* d_in_xyzz, const unsigned long long* d_off, size_t S, uint8_t* d_out_xyzz);
+int g2_normalise_launch(hipStream_t st, const uint8_t* in, size_t n, uint8_t* out);
+// gm_g2_lincomb_many: the G2 twin of g1_lincomb_many_host (192-byte records, 36-limb results); three launches and one wait
+int g2_lincomb_many_host(Context* C, const void* points, size_t stride, const uint64_t* scalars_canonical, const size_t* offsets, size_t S, uint64_t* out_jac);
 
 // S short linear combinations out[s] = sum_{offsets[s] <= t < offsets[s+1]} scalar[t] P[t] (k_g1_term_mul, k_g1_seg_sum,
 // k_normalise): host records of `stride` bytes and canonical scalars in, S packed affine device records at *d_aff (a
@@ -605,6 +631,12 @@ int gt_multi_pow_many_host(Context* C, const uint64_t* x, const uint64_t* scalar
 // (rows < ne).  Every product is non-empty.  Caller holds the MSM lock.
 int gt_checks_run(Context* C, const PairProduct* prods, const uint8_t* d_x, size_t nx, const uint8_t* d_e, size_t ne, const GtTerm* terms, const size_t* offsets, size_t S,
                   uint64_t* out_gt);
+// One round of many inner-product provers (ipa.hip: ipa_prove_many): the P non-empty Miller products stay on the device and are the
+// rows the terms name; out_gt[s] = FE(conj(prod over the terms [offsets[s], offsets[s + 1]) of Miller[t.x]^e[t.e])), e the ne host
+// rows of 4 canonical limbs.  One k_miller_seg, one k_gt_multi_pow_seg, their reduction levels, one k_gt_final_exp, one export and
+// ONE wait; *launches gets the number of kernels enqueued.  Every product and every term range is non-empty.  Caller holds the MSM lock.
+int miller_gt_products(Context* C, const PairProduct* prods, size_t P, const uint64_t* exps_canonical, size_t ne, const GtTerm* terms, const size_t* offsets, size_t S,
+                       uint64_t* out_gt, size_t* launches);
 int gt_from_host(Context* C, const uint64_t* x, size_t n, uint8_t** d);  // n x 72 limbs -> a dev_malloc block of device records
 // out[i] = in[2i] in[2i+1]^s (an odd tail is in[2i]), s at d_s8 (canonical, 8 x u32), on C->stream; caller holds the MSM lock
 int gt_split_fold_launch(Context* C, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out);
@@ -643,6 +675,10 @@ int ipa_verify(Context* C, const IpaProof* proof, const Vrs* vrs, const uint64_t
 // S proofs in one launch group; ok[s] is ipa_verify's answer for every input
 int ipa_verify_many(Context* C, const IpaProof* const* proofs, const Vrs* vrs, const uint64_t* comm_a /* S x 18 */, const uint64_t* comm_b /* S x 36 */,
                     const uint64_t* y_mont /* S x 4 */, size_t S, int* ok);
+// gm_ipa_new_many: proofs[s] = ipa_prove(transcripts[s], crs, a_s, b_s, d), the rounds of all proofs in lockstep (one launch group a
+// round) from C->ipa_new_many_min proofs on.  The caller has checked the handles; nothing is absorbed on a refusal.
+int ipa_prove_many(Context* C, const uint64_t* transcripts, const Crs* crs, const uint64_t* a_mont, const uint64_t* b_mont, size_t d, size_t S, IpaProof* const* proofs);
+bool transcript_exists(uint64_t handle);  // transcript.cpp
 // gm_debug_ipa_stated_terms: the canonical exponents of the stated form of one proof, 6 R - 4 GT terms then 2 R + 4 pairing terms
 int ipa_stated_terms(const IpaProof* proof, const uint64_t y_mont[4], uint64_t* gt_exp, uint64_t* pair_exp);
 // Jacobian points of both groups -> the host records of the proof checks and a GM_PT_* status byte each (points.hip), one launch per group

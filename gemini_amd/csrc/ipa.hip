@@ -457,6 +457,399 @@ int ipa_prove(Context* C, uint64_t transcript, const Crs* crs, const uint64_t* a
   return GM_OK;
 }
 
+// ---- many proofs in one call: the prover ----------------------------------------------------------------------------------------
+// The S proofs of gm_ipa_new_many run the rounds of ipa_prove above in lockstep.  Every proof keeps its own transcript, challenges
+// and batch challenges; what is shared is the launch group of a round.  All S proofs have the same d, so in every round every
+// point vector of every proof -- the live PModule vectors, the chopped CRS, the vectors of the G1Module and G2Module provers --
+// has the same length M, and the state of a proof is a list of references to spans of M records: into the CRS itself (the
+// module vectors before the first fold, the unfolded halves of the newest two provers) or into the current one of two
+// ping-pong buffers per group.  No span is copied: a fold reads spans where they lie and writes the halves into the other buffer.
+//
+//   fold      k_split_fold_seg (bases.hip), one launch per group over S (live + 2) spans, a challenge per proof
+//   Fr side   the vectors a and b of a proof are the FModule prover's and, with twist 1 and one challenge for all three claims,
+//             also the Rhs of the G1Module and the Lhs of the G2Module prover.  Fold and messages are 5 n products per proof and
+//             round and run on the host (sc_round_begin_many folds all its provers by ONE challenge; here every proof has its own)
+//   messages  the G1Module / G2Module messages are the same (scalar, point) index pairs in both groups: a = sum a[2i] F[2i],
+//             b = sum a[2i+1] F[2i] + a[2i] F[2i+1].  One lane per term (k_term_mul), the sums in two levels of k_seg_sum (chunks of
+//             LC_CHUNK terms, then the chunks of a segment), k_normalise: 4 launches per group whatever S is.  There is no switch
+//             to per-proof bucket MSMs at large term counts: the crossing lies near 48 000 terms a proof (profiles/ipa_new_many.md)
+//   GT        miller_gt_products (pairing.hip): the Miller values stay on the device, the products of the 2 S message halves are
+//             ONE k_gt_multi_pow_seg launch and ONE k_gt_final_exp launch; one download and the round's one wait
+//
+// Device memory of a call, per proof with F = 2^rounds: ping-pong buffers 2 F (96 + 192), the multiples of at most 1.5 F terms
+// in XYZZ 1.5 F (192 + 384), their chunk sums, 64 d of scalars and 12 F of index tables: about 1480 F + 64 d bytes.
+namespace {
+
+constexpr size_t LC_CHUNK = 32;  // terms to a lane of the first level of sums
+
+struct SpanRef {  // a span of the current length: records from `off` of the CRS or of the current ping-pong buffer
+  bool crs = true;
+  size_t off = 0;
+};
+struct LockstepProof {
+  std::vector<gmh::Fr> a, b;  // the folded scalar vectors
+  std::vector<gmh::Fr> bch;
+  std::vector<SpanRef> lhs, rhs;  // PModule prover p: Lhs in G1, Rhs in G2
+  SpanRef mod;                    // the G1Module's points and the G2Module's points: the same offsets in both groups
+  gmh::Fr fa, fb;                 // the FModule message of the round
+};
+
+bool fr_is_reduced(const uint64_t* p) {
+  uint64_t t[4];
+  return gmh::sub_n<4>(t, p, gmh::FrP::MOD) != 0;
+}
+
+void fr_fold(std::vector<gmh::Fr>& v, const gmh::Fr& c) {
+  const size_t n = v.size(), m = (n + 1) / 2;
+  for (size_t i = 0; i < m; i++) v[i] = 2 * i + 1 < n ? v[2 * i] + c * v[2 * i + 1] : v[2 * i];
+  v.resize(m);
+}
+
+size_t lockstep_bytes(size_t d, size_t rounds, size_t S) {
+  const size_t F = (size_t)1 << rounds, T = d + (d + 1) / 2, nch = T / LC_CHUNK + 4;
+  return S * (2 * F * (96 + 192) + T * (192 + 384) + nch * (192 + 384) + 2 * d * 32 + 2 * T * 4 + (nch + 3) * 8 + 2 * (2 * rounds + 1) * sizeof(FoldSpan) + 32 + 4 * (192 + 384) +
+              2 * (96 + 192)) +
+         4096;
+}
+
+int ipa_prove_lockstep(Context* C, const uint64_t* transcripts, const Crs* crs, const uint64_t* a_mont, const uint64_t* b_mont, size_t d, size_t S, IpaProof* const* proofs,
+                       size_t* launches, size_t* waits) {
+  typedef std::chrono::steady_clock Clock;
+  const Clock::time_point t_start = Clock::now();
+  const size_t rounds = (size_t)msm_ceil_log2(d), F = (size_t)1 << rounds;
+  const size_t Tmax = S * (d + (d + 1) / 2), NCmax = Tmax / LC_CHUNK + 4 * S;
+  int rc;
+  // the arena, before any transcript is touched
+  {
+    size_t free_b = 0, total_b = 0;
+    GM_HIP(hipMemGetInfo(&free_b, &total_b));
+    const size_t need = lockstep_bytes(d, rounds, S);
+    GM_CHECK(need <= free_b, GM_ENOMEM, "ipa_new_many: %zu proofs of d = %zu need an arena of %zu bytes, the device has %zu free", S, d, need, free_b);
+  }
+  Scratch mem;
+  uint8_t *P1[2], *P2[2], *T1, *T2, *CS1, *CS2, *SUM1, *SUM2, *A1, *A2, *d_sc, *d_pidx, *d_sidx, *d_off1, *d_off2, *d_ch, *d_sp1, *d_sp2;
+  const size_t max_spans = S * (2 * rounds + 1);
+  for (int i = 0; i < 2; i++)
+    if ((rc = mem.get(S * F * 96, &P1[i])) || (rc = mem.get(S * F * 192, &P2[i]))) return rc;
+  if ((rc = mem.get(Tmax * 192, &T1)) || (rc = mem.get(Tmax * 384, &T2)) || (rc = mem.get(NCmax * 192, &CS1)) || (rc = mem.get(NCmax * 384, &CS2)) ||
+      (rc = mem.get(2 * S * 192, &SUM1)) || (rc = mem.get(2 * S * 384, &SUM2)) || (rc = mem.get((1 + 2 * S) * 96, &A1)) || (rc = mem.get((1 + 2 * S) * 192, &A2)) ||
+      (rc = mem.get(S * 2 * d * 32, &d_sc)) || (rc = mem.get(Tmax * 4, &d_pidx)) || (rc = mem.get(Tmax * 4, &d_sidx)) || (rc = mem.get((NCmax + 1) * 8, &d_off1)) ||
+      (rc = mem.get((2 * S + 1) * 8, &d_off2)) || (rc = mem.get(S * 32, &d_ch)) || (rc = mem.get(max_spans * sizeof(FoldSpan), &d_sp1)) ||
+      (rc = mem.get(max_spans * sizeof(FoldSpan), &d_sp2)))
+    return rc;
+
+  std::vector<LockstepProof> L(S);
+  for (size_t s = 0; s < S; s++) {
+    L[s].a.resize(d);
+    L[s].b.resize(d);
+    for (size_t i = 0; i < d; i++) {
+      L[s].a[i] = gmh::Fr::from_limbs(a_mont + 4 * (s * d + i));
+      L[s].b[i] = gmh::Fr::from_limbs(b_mont + 4 * (s * d + i));
+    }
+    IpaProof* pr = proofs[s];
+    pr->rounds = rounds;
+    pr->messages.assign(rounds * 144, 0);
+    pr->challenges.assign(rounds * 4, 0);
+    pr->batch_challenges.clear();
+    pr->host_ms[0] = pr->host_ms[1] = pr->host_ms[2] = 0;
+  }
+  auto push_bch = [&](size_t s, const gmh::Fr& x) {
+    L[s].bch.push_back(x);
+    uint64_t l[4];
+    x.to_limbs(l);
+    proofs[s]->batch_challenges.insert(proofs[s]->batch_challenges.end(), l, l + 4);
+  };
+  int cur = 0;
+  size_t M = F, live = 0;
+  auto ptr1 = [&](const SpanRef& r) -> uint8_t* { return (r.crs ? crs->g1 : P1[cur]) + r.off * 96; };
+  auto ptr2 = [&](const SpanRef& r) -> uint8_t* { return (r.crs ? crs->g2 : P2[cur]) + r.off * 192; };
+  uint64_t gen1[12], gen2[24];
+  g1_to_record(g1_generator(), gen1);
+  g2_to_record(g2_generator(), gen2);
+  bool gens_up = false;
+
+  // host tables of the round in flight: read by their copies until the round's wait
+  std::vector<uint64_t> h_ch, h_sc, h_exp;
+  std::vector<FoldSpan> h_sp1, h_sp2;
+  std::vector<uint32_t> h_pidx, h_sidx;
+  std::vector<unsigned long long> h_off1, h_off2;
+
+  // every span of every proof folds by the proof's challenge ch[s]: one launch per group.  with_crs: the first M points of the CRS
+  // fold as one more span and become, with their unfolded first half, the vectors of two new provers.  Enqueues only.
+  auto fold_all = [&](const std::vector<gmh::Fr>& ch, bool with_crs) -> int {
+    const size_t m = M / 2;
+    h_ch.resize(4 * S);
+    h_sp1.clear();
+    h_sp2.clear();
+    for (size_t s = 0; s < S; s++) {
+      ch[s].to_canonical(h_ch.data() + 4 * s);
+      LockstepProof& p = L[s];
+      size_t at = s * F;  // the proof's region of the other buffer, in records
+      auto put = [&](const uint8_t* in1, const uint8_t* in2) {
+        h_sp1.push_back(FoldSpan{in1, P1[cur ^ 1] + at * 96, (uint32_t)s, 0});
+        h_sp2.push_back(FoldSpan{in2, P2[cur ^ 1] + at * 192, (uint32_t)s, 0});
+        const size_t was = at;
+        at += m;
+        return was;
+      };
+      for (size_t k = 0; k < live; k++) {
+        const size_t o = put(ptr1(p.lhs[k]), ptr2(p.rhs[k]));
+        p.lhs[k] = p.rhs[k] = SpanRef{false, o};
+      }
+      if (with_crs) {
+        const size_t o = put(crs->g1, crs->g2);
+        p.lhs.push_back(SpanRef{false, o});  // g1fold: the folded G1 half against the unfolded G2 half
+        p.rhs.push_back(SpanRef{true, 0});
+        p.lhs.push_back(SpanRef{true, 0});   // g2fold
+        p.rhs.push_back(SpanRef{false, o});
+      }
+      const size_t o = put(ptr1(p.mod), ptr2(p.mod));
+      p.mod = SpanRef{false, o};
+    }
+    const size_t nsp = h_sp1.size();
+    GM_HIP(hipMemcpyAsync(d_ch, h_ch.data(), S * 32, hipMemcpyHostToDevice, C->stream));
+    GM_HIP(hipMemcpyAsync(d_sp1, h_sp1.data(), nsp * sizeof(FoldSpan), hipMemcpyHostToDevice, C->stream));
+    GM_HIP(hipMemcpyAsync(d_sp2, h_sp2.data(), nsp * sizeof(FoldSpan), hipMemcpyHostToDevice, C->stream));
+    int r;
+    if ((r = g1_split_fold_seg_launch(C, reinterpret_cast<const FoldSpan*>(d_sp1), nsp, M, reinterpret_cast<const uint32_t*>(d_ch)))) return r;
+    if ((r = g2_split_fold_seg_launch(C, reinterpret_cast<const FoldSpan*>(d_sp2), nsp, M, reinterpret_cast<const uint32_t*>(d_ch)))) return r;
+    *launches += 2;
+    cur ^= 1;
+    M = m;
+    if (with_crs) live += 2;
+    return GM_OK;
+  };
+
+  // the message of every proof for the current vectors, into proofs[s]->messages at round j.  Enqueues, then the round's wait.
+  auto messages_all = [&](size_t j) -> int {
+    const size_t n = L[0].a.size(), ce = (n + 1) / 2, fl = n / 2;
+    int r;
+    if (!gens_up) {
+      GM_HIP(hipMemcpyAsync(A1, gen1, 96, hipMemcpyHostToDevice, C->stream));
+      GM_HIP(hipMemcpyAsync(A2, gen2, 192, hipMemcpyHostToDevice, C->stream));
+      gens_up = true;
+    }
+    // scalars: a_s at rows 2 s n, b_s at rows (2 s + 1) n; the terms of both groups are the same (scalar, point) index pairs
+    h_sc.resize(S * 2 * n * 4);
+    h_pidx.clear();
+    h_sidx.clear();
+    h_off1.clear();
+    h_off2.clear();
+    const bool in_crs = L[0].mod.crs;  // before the first fold every module vector is the CRS itself
+    auto seg_end = [&](size_t t0) {    // the segment [t0, now) in chunks
+      h_off2.push_back(h_off1.size());
+      for (size_t t = t0; t < h_pidx.size(); t += LC_CHUNK) h_off1.push_back(t);
+    };
+    for (size_t s = 0; s < S; s++) {
+      const LockstepProof& p = L[s];
+      for (size_t i = 0; i < n; i++) {
+        p.a[i].to_limbs(h_sc.data() + 4 * (2 * s * n + i));
+        p.b[i].to_limbs(h_sc.data() + 4 * ((2 * s + 1) * n + i));
+      }
+      const uint32_t sb = (uint32_t)(2 * s * n), pb = (uint32_t)p.mod.off;
+      size_t t0 = h_pidx.size();
+      for (size_t i = 0; i < ce; i++) {
+        h_sidx.push_back(sb + 2 * i);
+        h_pidx.push_back(pb + 2 * i);
+      }
+      seg_end(t0);
+      t0 = h_pidx.size();
+      for (size_t i = 0; i < fl; i++) {
+        h_sidx.push_back(sb + 2 * i + 1);
+        h_pidx.push_back(pb + 2 * i);
+      }
+      for (size_t i = 0; i < ce; i++) {
+        h_sidx.push_back(sb + 2 * i);
+        h_pidx.push_back(pb + 2 * i + 1);
+      }
+      seg_end(t0);
+    }
+    const size_t T = h_pidx.size(), nch = h_off1.size();
+    h_off1.push_back(T);
+    h_off2.push_back(nch);
+    GM_CHECK(T <= Tmax && nch <= NCmax, GM_ESTATE, "ipa_new_many: %zu terms in %zu chunks do not fit the arena (%zu, %zu)", T, nch, Tmax, NCmax);
+    GM_HIP(hipMemcpyAsync(d_sc, h_sc.data(), S * 2 * n * 32, hipMemcpyHostToDevice, C->stream));
+    GM_HIP(hipMemcpyAsync(d_pidx, h_pidx.data(), T * 4, hipMemcpyHostToDevice, C->stream));
+    GM_HIP(hipMemcpyAsync(d_sidx, h_sidx.data(), T * 4, hipMemcpyHostToDevice, C->stream));
+    GM_HIP(hipMemcpyAsync(d_off1, h_off1.data(), (nch + 1) * 8, hipMemcpyHostToDevice, C->stream));
+    GM_HIP(hipMemcpyAsync(d_off2, h_off2.data(), (2 * S + 1) * 8, hipMemcpyHostToDevice, C->stream));
+    const uint32_t *pi = reinterpret_cast<const uint32_t*>(d_pidx), *si = reinterpret_cast<const uint32_t*>(d_sidx);
+    const unsigned long long *o1 = reinterpret_cast<const unsigned long long*>(d_off1), *o2 = reinterpret_cast<const unsigned long long*>(d_off2);
+    if ((r = g1_term_mul_launch(C, in_crs ? crs->g1 : P1[cur], pi, d_sc, si, 1, T, T1)) || (r = g1_seg_sum_launch(C, T1, o1, nch, CS1)) ||
+        (r = g1_seg_sum_launch(C, CS1, o2, 2 * S, SUM1)) || (r = g1_normalise_launch(C->stream, SUM1, 2 * S, A1 + 96)))
+      return r;
+    if ((r = g2_term_mul_launch(C, in_crs ? crs->g2 : P2[cur], pi, d_sc + n * 32, si, 1, T, T2)) || (r = g2_seg_sum_launch(C, T2, o1, nch, CS2)) ||
+        (r = g2_seg_sum_launch(C, CS2, o2, 2 * S, SUM2)) || (r = g2_normalise_launch(C->stream, SUM2, 2 * S, A2 + 192)))
+      return r;
+    *launches += 8;
+    // Miller segments of proof s: e(G1, G2); (fg1.a, G2), (fg1.b, G2), (G1, fg2.a), (G1, fg2.b); then a_p, b_p of every PModule prover
+    const size_t per = 5 + 2 * live, eper = 4 + live, h = M / 2;
+    std::vector<PairProduct> prods(S * per);
+    std::vector<GtTerm> terms;
+    std::vector<size_t> toff(1, 0);
+    h_exp.resize(S * eper * 4);
+    for (size_t s = 0; s < S; s++) {
+      const LockstepProof& p = L[s];
+      PairProduct* q = prods.data() + s * per;
+      q[0].s0 = span(A1, 0, 1, A2, 0, 1, 1);
+      q[1].s0 = span(A1, 1 + 2 * s, 1, A2, 0, 1, 1);
+      q[2].s0 = span(A1, 2 + 2 * s, 1, A2, 0, 1, 1);
+      q[3].s0 = span(A1, 0, 1, A2, 1 + 2 * s, 1, 1);
+      q[4].s0 = span(A1, 0, 1, A2, 2 + 2 * s, 1, 1);
+      for (size_t k = 0; k < live; k++) {
+        const uint8_t *f = ptr1(p.lhs[k]), *g = ptr2(p.rhs[k]);
+        q[5 + 2 * k].s0 = span(f, 0, 2, g, 0, 2, h);      // a = ip(f_even, g_even)
+        q[5 + 2 * k + 1].s0 = span(f, 0, 2, g, 1, 2, h);  // b = ip(f_even, g_odd) + ip(f_odd, g_even)
+        q[5 + 2 * k + 1].s1 = span(f, 1, 2, g, 0, 2, h);
+      }
+      // SumcheckMsg::ip(messages, batch_challenges): exponents [fa bch0, fb bch0, bch1, bch2, bch3 ..] of the proof
+      uint64_t* e = h_exp.data() + 4 * s * eper;
+      (p.fa * p.bch[0]).to_canonical(e);
+      (p.fb * p.bch[0]).to_canonical(e + 4);
+      for (size_t k = 1; k < 3 + live; k++) p.bch[k].to_canonical(e + 4 * (k + 1));
+      const uint32_t x0 = (uint32_t)(s * per), e0 = (uint32_t)(s * eper);
+      for (uint32_t half = 0; half < 2; half++) {
+        terms.push_back(GtTerm{x0, e0 + half});
+        terms.push_back(GtTerm{x0 + 1 + half, e0 + 2});
+        terms.push_back(GtTerm{x0 + 3 + half, e0 + 3});
+        for (size_t k = 0; k < live; k++) terms.push_back(GtTerm{(uint32_t)(x0 + 5 + 2 * k + half), (uint32_t)(e0 + 4 + k)});
+        toff.push_back(terms.size());
+      }
+    }
+    std::vector<uint64_t> out(2 * S * 72);
+    r = miller_gt_products(C, prods.data(), prods.size(), h_exp.data(), S * eper, terms.data(), toff.data(), 2 * S, out.data(), launches);
+    *waits += 1;
+    if (r) return r;
+    for (size_t s = 0; s < S; s++) memcpy(proofs[s]->messages.data() + 144 * j, out.data() + 144 * s, 144 * 8);
+    return GM_OK;
+  };
+  // the FModule message of every proof, on the host
+  auto fr_messages = [&]() {
+    for (size_t s = 0; s < S; s++) {
+      LockstepProof& p = L[s];
+      const size_t n = p.a.size();
+      gmh::Fr a = gmh::Fr::zero(), b = gmh::Fr::zero();
+      for (size_t i = 0; 2 * i < n; i++) {
+        a = a + p.a[2 * i] * p.b[2 * i];
+        if (2 * i + 1 < n) b = b + p.a[2 * i] * p.b[2 * i + 1] + p.b[2 * i] * p.a[2 * i + 1];
+      }
+      p.fa = a;
+      p.fb = b;
+    }
+  };
+  // a failure between the launches and the wait: nothing of this call may still be read when its tables and its arena go
+  auto fail = [&](int r) {
+    (void)hipStreamSynchronize(C->stream);
+    return r;
+  };
+
+  uint64_t ch[4];
+  for (size_t s = 0; s < S; s++) {
+    if ((rc = gm_transcript_challenge_fr(transcripts[s], (const uint8_t*)"batch-chal", 10, ch))) return rc;
+    const gmh::Fr bc = gmh::Fr::from_limbs(ch);
+    push_bch(s, gmh::Fr::one());
+    push_bch(s, bc);
+    push_bch(s, bc.sqr());
+  }
+  fr_messages();
+  {
+    GM_MSM_LOCK(C);
+    if ((rc = messages_all(0))) return fail(rc);
+  }
+  for (size_t s = 0; s < S; s++)
+    if ((rc = gm_transcript_append_gt(transcripts[s], (const uint8_t*)"prover_message", 14, proofs[s]->messages.data(), 2))) return rc;
+
+  std::vector<gmh::Fr> cs(S);
+  for (size_t j = 0; j + 1 < rounds; j++) {
+    for (size_t s = 0; s < S; s++) {
+      uint64_t* c = proofs[s]->challenges.data() + 4 * j;
+      if ((rc = gm_transcript_challenge_fr(transcripts[s], (const uint8_t*)"sumcheck-chal", 13, c))) return rc;
+      if ((rc = gm_transcript_challenge_fr(transcripts[s], (const uint8_t*)"batch-chal", 10, ch))) return rc;
+      const gmh::Fr b = gmh::Fr::from_limbs(ch);
+      push_bch(s, b);
+      push_bch(s, b.sqr());
+      cs[s] = gmh::Fr::from_limbs(c);
+      fr_fold(L[s].a, cs[s]);
+      fr_fold(L[s].b, cs[s]);
+    }
+    fr_messages();
+    {
+      GM_MSM_LOCK(C);
+      if ((rc = fold_all(cs, true)) || (rc = messages_all(j + 1))) return fail(rc);
+    }
+    for (size_t s = 0; s < S; s++)
+      if ((rc = gm_transcript_append_gt(transcripts[s], (const uint8_t*)"sumcheck-round", 14, proofs[s]->messages.data() + 144 * (j + 1), 2))) return rc;
+  }
+
+  for (size_t s = 0; s < S; s++) {
+    uint64_t* last = proofs[s]->challenges.data() + 4 * (rounds - 1);
+    if ((rc = gm_transcript_challenge_fr(transcripts[s], (const uint8_t*)"sumcheck-chal", 13, last))) return rc;
+    cs[s] = gmh::Fr::from_limbs(last);
+    fr_fold(L[s].a, cs[s]);
+    fr_fold(L[s].b, cs[s]);
+  }
+  // final foldings: every PModule prover and the two module vectors fold once more, to length 1 -- one more segmented fold per
+  // group and ONE download: proof s has its live + 1 records back to back from record s F of the buffers
+  const size_t k = live, per = k + 1;
+  std::vector<uint64_t> f(S * per * 12), g(S * per * 24);
+  {
+    GM_MSM_LOCK(C);
+    if ((rc = fold_all(cs, false))) return fail(rc);
+    hipError_t e = hipMemcpy2DAsync(f.data(), per * 96, P1[cur], F * 96, per * 96, S, hipMemcpyDeviceToHost, C->stream);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(g.data(), per * 192, P2[cur], F * 192, per * 192, S, hipMemcpyDeviceToHost, C->stream);
+    const hipError_t e2 = hipStreamSynchronize(C->stream);
+    *waits += 1;
+    GM_HIP(e);
+    GM_HIP(e2);
+  }
+  const double ms = std::chrono::duration<double, std::milli>(Clock::now() - t_start).count();
+  for (size_t s = 0; s < S; s++) {
+    IpaProof* pr = proofs[s];
+    const LockstepProof& p = L[s];
+    pr->final_g1.assign(k * 18, 0);
+    pr->final_g2.assign(k * 36, 0);
+    const uint64_t *fs = f.data() + s * per * 12, *gs = g.data() + s * per * 24;
+    for (size_t q = 0; q < k; q++) {  // the spans were written in the order of the provers, the module vector last
+      gmh::g1_affine_to_jac_dev(fs + 12 * q).to_limbs(pr->final_g1.data() + 18 * q);
+      gmh::g2_affine_to_jac_dev(gs + 24 * q).to_limbs(pr->final_g2.data() + 36 * q);
+    }
+    p.a[0].to_limbs(pr->foldings_ff);
+    p.b[0].to_limbs(pr->foldings_ff + 4);
+    gmh::g1_affine_to_jac_dev(fs + 12 * k).to_limbs(pr->foldings_fg1);
+    p.a[0].to_limbs(pr->foldings_fg1 + 18);
+    p.b[0].to_limbs(pr->foldings_fg2);
+    gmh::g2_affine_to_jac_dev(gs + 24 * k).to_limbs(pr->foldings_fg2 + 4);
+    pr->host_ms[2] = ms;  // of the whole call: the proofs were made together
+  }
+  return GM_OK;
+}
+
+}  // namespace
+
+int ipa_prove_many(Context* C, const uint64_t* transcripts, const Crs* crs, const uint64_t* a_mont, const uint64_t* b_mont, size_t d, size_t S, IpaProof* const* proofs) {
+  GM_CHECK(d >= 2, GM_EINVAL, "ipa_new_many: d = %zu; the argument needs at least two scalars (the reference's round loop underflows at rounds - 1, ipa.rs:584)", d);
+  const size_t rounds = (size_t)msm_ceil_log2(d), need = std::max(d + 1, (size_t)1 << rounds);
+  GM_CHECK(crs->n1 >= need && crs->n2 >= need, GM_EINVAL, "ipa_new_many: d = %zu needs a CRS of max(d + 1, 2^rounds) = %zu points, it has %zu / %zu", d, need, crs->n1, crs->n2);
+  GM_CHECK(S <= ((size_t)1 << 16) && d <= ((size_t)1 << 24) && S * d <= ((size_t)1 << 28), GM_EINVAL, "ipa_new_many: %zu proofs of d = %zu (at most 2^28 scalars a side)", S, d);
+  // the lockstep path computes with reduced residues; the per-proof path takes limbs as they are
+  bool lockstep = S >= C->ipa_new_many_min && S > 0;
+  for (size_t i = 0; lockstep && i < S * d; i++) lockstep = fr_is_reduced(a_mont + 4 * i) && fr_is_reduced(b_mont + 4 * i);
+  size_t counts[4] = {0, 0, 0, 0};
+  int rc = GM_OK;
+  if (lockstep) {
+    counts[0] = S;
+    rc = ipa_prove_lockstep(C, transcripts, crs, a_mont, b_mont, d, S, proofs, &counts[2], &counts[3]);
+  } else {
+    counts[1] = S;
+    for (size_t s = 0; s < S && !rc; s++) rc = ipa_prove(C, transcripts[s], crs, a_mont + 4 * s * d, b_mont + 4 * s * d, d, proofs[s]);
+  }
+  {
+    GM_MSM_LOCK(C);
+    memcpy(C->ipa_new_many_last, counts, sizeof counts);
+  }
+  return rc;
+}
+
 // InnerProductProof::verify_transcript (ipa.rs:250-343), GT written multiplicatively.  Its pairings -- the two commitments, the
 // foldings of the three claims and every PModule final folding -- are the 1-pair segments of ONE segmented launch; the claim and the
 // expected value take one final exponentiation each.

@@ -1244,6 +1244,39 @@ int gt_multi_pow_many_host(Context* C, const uint64_t* x, const uint64_t* scalar
   return GM_OK;
 }
 
+int miller_gt_products(Context* C, const PairProduct* prods, size_t P, const uint64_t* exps_canonical, size_t ne, const GtTerm* terms, const size_t* offsets, size_t S,
+                       uint64_t* out_gt, size_t* launches) {
+  if (S == 0) return GM_OK;
+  GM_CHECK(offsets[0] == 0, GM_EINVAL, "miller_gt_products: offsets[0] = %zu", offsets[0]);
+  for (size_t p = 0; p < P; p++) GM_CHECK(prods[p].s0.n + prods[p].s1.n > 0, GM_EINVAL, "miller_gt_products: product %zu is empty", p);
+  for (size_t s = 0; s < S; s++) {
+    GM_CHECK(offsets[s] < offsets[s + 1], GM_EINVAL, "miller_gt_products: segment %zu is empty", s);
+    for (size_t i = offsets[s]; i < offsets[s + 1]; i++)
+      GM_CHECK(terms[i].x < P && terms[i].e < ne, GM_EINVAL, "miller_gt_products: term %zu names product %u of %zu, exponent %u of %zu", i, terms[i].x, P, terms[i].e, ne);
+  }
+  GM_CHECK(offsets[S] <= GT_EACH_MAX && P <= GT_EACH_MAX && S <= GT_EACH_MAX, GM_EINVAL, "miller_gt_products: %zu terms over %zu products in %zu segments (at most 2^20 of each)",
+           offsets[S], P, S);
+  GtTmp res(C);  // the P Miller values, the ne exponents, then the S results: the launch groups share the level buffers of the workspace
+  const size_t o_e = P * GT_BYTES, o_out = o_e + ((ne * 32 + 63) & ~(size_t)63);
+  GM_HIP(dev_malloc((void**)&res.p, o_out + S * GT_BYTES));
+  SegTables pt;
+  GtSegTables gt;
+  uint8_t* d = nullptr;
+  auto enqueue = [&]() -> int {
+    GM_HIP(hipMemcpyAsync(res.p + o_e, exps_canonical, ne * 32, hipMemcpyHostToDevice, C->stream));
+    int r = miller_products_launch(C, prods, P, pt, &d);
+    if (r) return r;
+    GM_HIP(hipMemcpyAsync(res.p, d, P * GT_BYTES, hipMemcpyDeviceToDevice, C->stream));
+    if ((r = gt_multi_pow_seg_launch(C, res.p, res.p + o_e, terms, offsets, S, gt, &d))) return r;
+    if ((r = gt_final_exp_launch(C, d, S, 1, res.p + o_out))) return r;
+    return gt_to_host(C, res.p + o_out, S, out_gt);  // the one wait: the tables of `pt` and `gt` are read by their copies until here
+  };
+  const int rc = enqueue();
+  if (rc) (void)hipStreamSynchronize(C->stream);
+  else if (launches) *launches += pt.maps.size() / P + gt.maps.size() / S + 2;  // a launch per level of either group, k_gt_final_exp, k_gt_export
+  return rc;
+}
+
 int gt_checks_run(Context* C, const PairProduct* prods, const uint8_t* d_x, size_t nx, const uint8_t* d_e, size_t ne, const GtTerm* terms, const size_t* offsets, size_t S,
                   uint64_t* out_gt) {
   if (S == 0) return GM_OK;

@@ -98,6 +98,22 @@ def _records(bases) -> np.ndarray:
     return bases
 
 
+def g2_lincomb_many(points: np.ndarray, scalars_canonical: np.ndarray, offsets) -> np.ndarray:
+    """gm_g2_lincomb_many, the G2 twin of msm.g1_lincomb_many: out[s] = sum of scalars[t] * points[t] over
+    offsets[s] <= t < offsets[s + 1], for S = len(offsets) - 1 short segments in a fixed number of launches; (S, 36) normalised
+    Jacobian limbs.  Records (n, 24) / (n, 25) and canonical scalars as for G2VariableBaseMSM.msm_bigint; an empty segment is
+    the identity."""
+    capi.ensure_init()
+    pts = _records(points)
+    sc = capi.u64(scalars_canonical).reshape(-1, 4)
+    off = np.ascontiguousarray(offsets, dtype=np.uintp)
+    S = len(off) - 1
+    assert S >= 0 and (S == 0 or int(off[-1]) <= min(len(pts), len(sc)))
+    out = np.empty((max(S, 0), 36), dtype=np.uint64)
+    capi.check(capi.load().gm_g2_lincomb_many(capi.ptr(pts), C.c_size_t(pts.shape[1] * 8), capi.ptr(sc), capi.ptr(off), C.c_size_t(S), capi.ptr(out)))
+    return out
+
+
 class G2Bases:
     """G2 points resident in HBM (the `g2s` of herring's Crs, src/herring/ipa.rs:86-96)."""
 

@@ -218,6 +218,25 @@ class InnerProductProof:
         return cls(h.value)
 
     @classmethod
+    def new_many(cls, transcripts, crs: Crs, a_monts, b_monts) -> list:
+        """gm_ipa_new_many: [InnerProductProof.new(transcripts[s], crs, a_monts[s], b_monts[s]) for every s], byte for byte, with
+        the rounds of all proofs in lockstep -- one launch group per round whatever the number of proofs.  All vectors have
+        the same length d; every proof needs a transcript of its own, which is left as the single call leaves it."""
+        capi.ensure_init()
+        S = len(transcripts)
+        assert len(a_monts) == S and len(b_monts) == S
+        if S == 0:
+            capi.check(capi.load().gm_ipa_new_many(None, C.c_uint64(crs.handle), None, None, C.c_size_t(0), C.c_size_t(0), None))
+            return []
+        a = np.ascontiguousarray(np.stack([capi.u64(x).reshape(-1, 4) for x in a_monts]))
+        b = np.ascontiguousarray(np.stack([capi.u64(x).reshape(-1, 4) for x in b_monts]))
+        assert a.shape == b.shape
+        ts = np.array([t.handle for t in transcripts], dtype=np.uint64)
+        hs = np.zeros(S, dtype=np.uint64)
+        capi.check(capi.load().gm_ipa_new_many(capi.ptr(ts), C.c_uint64(crs.handle), capi.ptr(a), capi.ptr(b), C.c_size_t(a.shape[1]), C.c_size_t(S), capi.ptr(hs)))
+        return [cls(int(h)) for h in hs]
+
+    @classmethod
     def from_fields(cls, f: IpaFields) -> "InnerProductProof":
         capi.ensure_init()
         k = 2 * (f.rounds - 1)
@@ -307,6 +326,22 @@ class InnerProductProof:
         if self.handle:
             capi.check(capi.load().gm_ipa_free(C.c_uint64(self.handle)))
             self.handle = 0
+
+
+def set_new_many_min(proofs: int):
+    """gm_set_ipa_new_many_min: fewer proofs than this make InnerProductProof.new_many run them one by one, as `new` does.  The
+    bytes do not depend on it (profiles/ipa_new_many.md has the measurement behind the default)."""
+    capi.ensure_init()
+    capi.check(capi.load().gm_set_ipa_new_many_min(C.c_size_t(proofs)))
+
+
+def new_many_path() -> tuple:
+    """gm_debug_ipa_new_many_path, for the last new_many call: (proofs on the lockstep path, proofs on the per-proof path, kernel
+    launches the lockstep path enqueued, stream waits it made)"""
+    capi.ensure_init()
+    counts = (C.c_size_t * 4)()
+    capi.check(capi.load().gm_debug_ipa_new_many_path(counts))
+    return tuple(int(c) for c in counts)
 
 
 def set_verify_many_min(proofs: int):

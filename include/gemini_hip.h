@@ -79,6 +79,11 @@ int gm_g1_msm(const void* bases, size_t base_stride, const uint64_t* scalars, si
  * The additions are complete (equal terms double, opposite ones cancel); an empty segment, a zero scalar and the all-zero record
  * give the identity. */
 int gm_g1_lincomb_many(const void* points, size_t stride, const uint64_t* scalars_canonical, const size_t* offsets, size_t S, uint64_t* out_jac);
+/* The G2 twin: records of at least 192 bytes as for gm_g2_msm, out_jac: S x 36 limbs, normalised.  The same contract -- complete
+ * additions, so equal terms double and opposite terms cancel; an empty segment, a zero scalar and the all-zero record give the
+ * identity -- and the same three launches (one lane per term, one per segment, the batched normalisation) and one wait whatever
+ * S is. */
+int gm_g2_lincomb_many(const void* points, size_t stride, const uint64_t* scalars_canonical, const size_t* offsets, size_t S, uint64_t* out_jac);
 
 /* SRS resident in HBM: replaces the `powers_of_g: Vec<G1Affine>` field of CommitterKey
  * (src/kzg/time.rs:24-27) as the MSM operand.  The bases are copied; `handle` is opaque.  Cost: one upload and one
@@ -610,7 +615,8 @@ int gm_hgt_free(uint64_t handle);
  * Vectors of GT elements: `BilinearModule::p` of PModule is P::pairing(a, b) (src/herring/module.rs:67), and the GtModule prover
  * above consumes 2^10 .. 2^14 of them.  One lane per element, 64 lanes per block; a launch is milliseconds deep whatever n is
  * (profiles/gt_device.md gives the n from which the device beats the host loop; calls that make ONE final exponentiation --
- * gm_pairing_multi*, gm_hp_round, gm_ipa_new, gm_ipa_verify, the verifiers -- stay on the host function).  At most 2^20 elements
+ * gm_pairing_multi*, gm_hp_round, gm_ipa_new, gm_ipa_verify, the verifiers -- stay on the host function; gm_ipa_new_many does
+ * not: the 2 S products of a round of S proofs go through one k_gt_final_exp launch).  At most 2^20 elements
  * per call.  Calls share the MSM lock.
  * The final exponentiation splits (q^12 - 1) / r = (q^6 - 1)(q^2 + 1) h with, for x = -0xd201000000010000,
  *   h = (q^4 - q^2 + 1) / r = ((x - 1)^2 / 3)(x + q)(x^2 + q^2 - 1) + 1,
@@ -688,6 +694,41 @@ int gm_vrs_free(uint64_t vrs);
  * GM_EINVAL for d < 2 (the reference's round loop underflows at rounds - 1) and for a CRS with fewer than max(d + 1, 2^rounds)
  * points in either group (commitments need d + 1, the truncation of ipa.rs:581 needs 2^rounds). */
 int gm_ipa_new(uint64_t transcript, uint64_t crs, const uint64_t* a_mont, const uint64_t* b_mont, size_t d, uint64_t* proof);
+/* S proofs against one CRS in one call: proofs[s] is what gm_ipa_new(transcripts[s], crs, a_s, b_s, d, .) returns, every field of
+ * every proof byte for byte, and transcript s is left in the state the single call leaves it in.  One d per call (callers group
+ * their work by length); a_mont / b_mont: S x d x 4 limbs.  S = 0 does nothing.
+ * Refused with nothing absorbed by any transcript and no proof handle created: GM_EINVAL for what gm_ipa_new refuses (d < 2, a
+ * CRS shorter than max(d + 1, 2^rounds) in either group), for null pointers with S > 0 and for a transcript handle named twice in
+ * one call (two proofs cannot share a transcript); GM_EHANDLE for a stale transcript or CRS handle; GM_ENOMEM when the arena does
+ * not fit the free device memory (the message has both numbers).  On a failure AFTER the first challenge (an allocation failure,
+ * say) no proof handle is returned and the states of the transcripts are unspecified.
+ * The S proofs run their rounds in lockstep.  Every proof draws its own challenges from its own transcript, in the single entry's
+ * order and under its labels, and the device work of one round of ALL proofs is one launch group: one segmented split-fold per
+ * group of the curve over every point vector of every proof (the PModule arena, the chopped CRS, the vectors of the G1Module and
+ * G2Module provers; k_split_fold_seg reads each span's challenge through a table and tests its bits lane by lane, so one wave may
+ * hold several proofs), the G1Module and G2Module messages of all proofs as segments of one short-linear-combination group per
+ * group of the curve (one lane per term, the sums in two levels), one k_miller_seg launch over the 5 + 2 live segments of every
+ * proof with the message points where the combinations left them, one k_gt_multi_pow_seg launch for the 2 S products of the round
+ * messages on the Miller values, one k_gt_final_exp launch, one download of S x 144 limbs and one stream wait.  The number of
+ * launches and waits does not depend on S.  The Fr side of a round -- the fold and the two inner products of the FModule prover,
+ * whose vectors are also the scalars of the other two -- is 5 d / 2^j products per proof and runs on the host between the
+ * challenges and the launches: the multi-prover sumcheck launch folds all its provers by ONE challenge, and here every proof has
+ * its own.  Values are exact group and field elements normalised on the way out, so the bytes are the host path's.
+ * Memory: one arena for all proofs, taken when the call starts and given back when it ends; its peak is
+ * about S x (1480 x 2^rounds + 64 d) bytes plus tables of a few KiB per proof, checked against the free memory before the first
+ * transcript is touched.  The MSM lock is taken per round, as gm_ipa_new takes it, so other threads' calls interleave.
+ * gm_set_ipa_new_many_min: fewer proofs than this are made one by one by gm_ipa_new's own code; the bytes never depend on it.
+ * Default 2, from profiles/ipa_new_many.md at d = 2^10: a lockstep call takes one proof's launch groups whatever S is, about a
+ * second, so S = 1 loses, 1004.0 (991.0-1016.3) ms against 669.9 (669.0-674.5) ms for gm_ipa_new; S = 2 is the first measured row
+ * where the slowest lockstep call beats the fastest loop, 1013.9 (1008.9-1017.3) ms against 1337.2 (1334.0-1339.7) ms; at S = 16
+ * it is 1007.4 (1001.8-1011.2) ms against 10700.6 (10673.7-10723.8) ms.  gm_debug_ipa_new_many_path, for the last call on the context: counts[0] = proofs that
+ * took the lockstep path, counts[1] = proofs that took the per-proof path, counts[2] = kernel launches the lockstep path enqueued,
+ * counts[3] = stream waits it made, both counted where they are issued.  Scalars that are not reduced residues send the call to
+ * the per-proof path, which takes limbs as they are. */
+int gm_ipa_new_many(const uint64_t* transcripts /* S handles */, uint64_t crs, const uint64_t* a_mont /* S x d x 4 */, const uint64_t* b_mont /* S x d x 4 */, size_t d,
+                    size_t S, uint64_t* proofs /* S handles out */);
+int gm_set_ipa_new_many_min(size_t proofs);
+int gm_debug_ipa_new_many_path(size_t counts[4]);
 /* The fields of the proof.  messages: rounds x (a || b) = 144 limbs; challenges: rounds x 4; batch_challenges: (2 rounds + 1) x 4;
  * final_foldings (Sumcheck::final_foldings): 2 (rounds - 1) x 18 limbs (Lhs, G1) and x 36 limbs (Rhs, G2);
  * foldings_ff: lhs || rhs; foldings_fg1: (G1, Fr); foldings_fg2: (Fr, G2). */

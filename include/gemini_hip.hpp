@@ -544,6 +544,15 @@ inline G2Projective g2_add(const G2Projective& a, const G2Projective& b) {
   return r;
 }
 
+// the G2 twin of g1_lincomb_many (gm_g2_lincomb_many): S short linear combinations in a fixed number of launches, an empty segment is the identity
+inline std::vector<G2Projective> g2_lincomb_many(const std::vector<G2Affine>& points, const std::vector<BigInt>& bigints, const std::vector<size_t>& offsets) {
+  if (offsets.size() < 2) return {};
+  if (offsets.back() > points.size() || offsets.back() > bigints.size()) throw Error(GM_EINVAL, "g2_lincomb_many: the offsets run past the terms");
+  std::vector<G2Projective> out(offsets.size() - 1);
+  check(gm_g2_lincomb_many(points.data(), sizeof(G2Affine), bigints.empty() ? nullptr : bigints[0].data(), offsets.data(), out.size(), out[0].data()));
+  return out;
+}
+
 // G2 points resident in HBM (the `g2s` of herring's Crs); commit_g2 is msm_unchecked against them
 class G2Bases {
  public:
@@ -1107,9 +1116,38 @@ class InnerProductProof {  // ipa.rs:54-60
     for (size_t s = 0; s < S; s++) r[s] = ok[s] != 0;
     return r;
   }
+  // [InnerProductProof(*transcripts[s], crs, a[s], b[s]) for every s], byte for byte, the rounds of all proofs in lockstep: one
+  // launch group per round whatever their number (gm_ipa_new_many).  One length for all vectors; a transcript per proof
+  static std::vector<InnerProductProof> new_many(const std::vector<Transcript*>& transcripts, const Crs& crs, const std::vector<std::vector<Fr>>& a,
+                                                 const std::vector<std::vector<Fr>>& b) {
+    const size_t S = transcripts.size(), d = S ? a.at(0).size() : 0;
+    if (a.size() != S || b.size() != S) throw Error(GM_EINVAL, "InnerProductProof::new_many: one pair of vectors per transcript");
+    std::vector<uint64_t> t(S), h(S, 0);
+    std::vector<Fr> fa, fb;
+    for (size_t s = 0; s < S; s++) {
+      if (a[s].size() != d || b[s].size() != d) throw Error(GM_EINVAL, "InnerProductProof::new_many: the vectors of one call have one length");
+      t[s] = transcripts[s]->handle();
+      fa.insert(fa.end(), a[s].begin(), a[s].end());
+      fb.insert(fb.end(), b[s].begin(), b[s].end());
+    }
+    check(gm_ipa_new_many(t.data(), crs.handle(), fa.empty() ? nullptr : fa[0].data(), fb.empty() ? nullptr : fb[0].data(), d, S, h.data()));
+    std::vector<InnerProductProof> out;
+    out.reserve(S);
+    for (size_t s = 0; s < S; s++) out.push_back(InnerProductProof(h[s]));
+    return out;
+  }
+  // fewer proofs than this are made one by one (gm_set_ipa_new_many_min); the bytes do not depend on it
+  static void set_new_many_min(size_t proofs) { check(gm_set_ipa_new_many_min(proofs)); }
+  // of the last new_many call: proofs on the lockstep path, on the per-proof path, kernel launches and stream waits of the lockstep path
+  static std::array<size_t, 4> new_many_path() {
+    std::array<size_t, 4> c{};
+    check(gm_debug_ipa_new_many_path(c.data()));
+    return c;
+  }
   uint64_t handle() const { return h_; }
 
  private:
+  explicit InnerProductProof(uint64_t h) : h_(h) {}
   uint64_t h_ = 0;
 };
 
