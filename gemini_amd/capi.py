@@ -65,6 +65,7 @@ SYMBOLS = [
     "gm_crs_truncate", "gm_crs_halve", "gm_crs_fold", "gm_crs_to_bases",
     "gm_ipa_foldings_fg1", "gm_ipa_foldings_fg2", "gm_ipa_free", "gm_ipa_host_times", "gm_ipa_from_fields", "gm_ipa_verify", "gm_ipa_verify_many", "gm_set_ipa_verify_many_min", "gm_debug_ipa_verify_many_path", "gm_debug_ipa_stated_terms", "gm_transcript_append_gt",
     "gm_ipa_new_many", "gm_set_ipa_new_many_min", "gm_debug_ipa_new_many_path", "gm_g2_lincomb_many",
+    "gm_ipa_new_batch", "gm_ipa_claims", "gm_ipa_foldings_batch", "gm_ipa_from_fields_batch", "gm_ipa_verify_batch", "gm_debug_ipa_new_batch_path",
 ]
 
 

@@ -2410,6 +2410,7 @@ int gm_ipa_final_foldings(uint64_t proof, uint64_t* lhs_jac, uint64_t* rhs_jac) 
 int gm_ipa_foldings_ff(uint64_t proof, uint64_t lhs_rhs_mont[8]) {
   GM_CTX();
   GM_IPA_FIND(p, ipa, proof, "ipa_foldings_ff", "proof");
+  GM_CHECK(p->K == 1, GM_EINVAL, "ipa_foldings_ff: a proof for %zu claims; gm_ipa_foldings_batch reads the foldings of all of them", p->K);
   GM_CHECK(lhs_rhs_mont != nullptr, GM_EINVAL, "ipa_foldings_ff: null pointer");
   memcpy(lhs_rhs_mont, p->foldings_ff, sizeof p->foldings_ff);
   return GM_OK;
@@ -2417,6 +2418,7 @@ int gm_ipa_foldings_ff(uint64_t proof, uint64_t lhs_rhs_mont[8]) {
 int gm_ipa_foldings_fg1(uint64_t proof, uint64_t lhs_jac[18], uint64_t rhs_mont[4]) {
   GM_CTX();
   GM_IPA_FIND(p, ipa, proof, "ipa_foldings_fg1", "proof");
+  GM_CHECK(p->K == 1, GM_EINVAL, "ipa_foldings_fg1: a proof for %zu claims; gm_ipa_foldings_batch reads the foldings of all of them", p->K);
   GM_CHECK(lhs_jac && rhs_mont, GM_EINVAL, "ipa_foldings_fg1: null pointer");
   memcpy(lhs_jac, p->foldings_fg1, 18 * 8);
   memcpy(rhs_mont, p->foldings_fg1 + 18, 4 * 8);
@@ -2425,6 +2427,7 @@ int gm_ipa_foldings_fg1(uint64_t proof, uint64_t lhs_jac[18], uint64_t rhs_mont[
 int gm_ipa_foldings_fg2(uint64_t proof, uint64_t lhs_mont[4], uint64_t rhs_jac[36]) {
   GM_CTX();
   GM_IPA_FIND(p, ipa, proof, "ipa_foldings_fg2", "proof");
+  GM_CHECK(p->K == 1, GM_EINVAL, "ipa_foldings_fg2: a proof for %zu claims; gm_ipa_foldings_batch reads the foldings of all of them", p->K);
   GM_CHECK(lhs_mont && rhs_jac, GM_EINVAL, "ipa_foldings_fg2: null pointer");
   memcpy(lhs_mont, p->foldings_fg2, 4 * 8);
   memcpy(rhs_jac, p->foldings_fg2 + 4, 36 * 8);
@@ -2433,6 +2436,7 @@ int gm_ipa_foldings_fg2(uint64_t proof, uint64_t lhs_mont[4], uint64_t rhs_jac[3
 int gm_ipa_host_times(uint64_t proof, double ms[3]) {
   GM_CTX();
   GM_IPA_FIND(p, ipa, proof, "ipa_host_times", "proof");
+  GM_CHECK(p->K == 1, GM_EINVAL, "ipa_host_times: a proof for %zu claims", p->K);
   GM_CHECK(ms != nullptr, GM_EINVAL, "ipa_host_times: null pointer");
   memcpy(ms, p->host_ms, sizeof p->host_ms);
   return GM_OK;
@@ -2527,6 +2531,81 @@ int gm_debug_ipa_stated_terms(uint64_t proof, const uint64_t y_mont[4], uint64_t
   GM_IPA_FIND(p, ipa, proof, "debug_ipa_stated_terms", "proof");
   GM_CHECK(y_mont && gt_exponents && pairing_exponents, GM_EINVAL, "debug_ipa_stated_terms: null pointer");
   return ipa_stated_terms(p, y_mont, gt_exponents, pairing_exponents);
+}
+
+// ---- one proof for many claims (ipa.hip: ipa_prove_batch, ipa_verify_batch) ------------------------------------------------------
+int gm_ipa_new_batch(uint64_t transcript, uint64_t crs, const uint64_t* a_mont, const uint64_t* b_mont, size_t d, size_t K, uint64_t* proof) {
+  GM_CTX();
+  GM_CHECK(a_mont && b_mont && proof, GM_EINVAL, "ipa_new_batch: null pointer");
+  GM_IPA_FIND(c, crs, crs, "ipa_new_batch", "CRS");
+  auto p = std::make_unique<IpaProof>();
+  int rc = ipa_prove_batch(C, transcript, c, a_mont, b_mont, d, K, p.get());
+  if (rc) return rc;  // no handle exists
+  *proof = put_in(C, C->ipa, std::move(p));
+  return GM_OK;
+}
+int gm_ipa_claims(uint64_t proof, size_t* K) {
+  GM_CTX();
+  GM_IPA_FIND(p, ipa, proof, "ipa_claims", "proof");
+  GM_CHECK(K != nullptr, GM_EINVAL, "ipa_claims: null pointer");
+  *K = p->K;
+  return GM_OK;
+}
+int gm_ipa_foldings_batch(uint64_t proof, uint64_t* ff, uint64_t* fg1, uint64_t* fg2) {
+  GM_CTX();
+  GM_IPA_FIND(p, ipa, proof, "ipa_foldings_batch", "proof");
+  GM_CHECK(ff && fg1 && fg2, GM_EINVAL, "ipa_foldings_batch: null pointer");
+  if (p->K == 1) {  // a single-claim proof keeps its foldings in the fixed fields
+    memcpy(ff, p->foldings_ff, sizeof p->foldings_ff);
+    memcpy(fg1, p->foldings_fg1, sizeof p->foldings_fg1);
+    memcpy(fg2, p->foldings_fg2, sizeof p->foldings_fg2);
+    return GM_OK;
+  }
+  memcpy(ff, p->batch_ff.data(), p->batch_ff.size() * 8);
+  memcpy(fg1, p->batch_fg1.data(), p->batch_fg1.size() * 8);
+  memcpy(fg2, p->batch_fg2.data(), p->batch_fg2.size() * 8);
+  return GM_OK;
+}
+int gm_ipa_from_fields_batch(size_t rounds, size_t K, const uint64_t* messages, const uint64_t* challenges, const uint64_t* batch_challenges, const uint64_t* final_lhs_jac,
+                             const uint64_t* final_rhs_jac, const uint64_t* ff, const uint64_t* fg1, const uint64_t* fg2, uint64_t* proof) {
+  GM_CTX();
+  GM_CHECK(rounds >= 1 && rounds <= 64, GM_EINVAL, "ipa_from_fields_batch: %zu rounds", rounds);
+  GM_CHECK(K >= 1 && K <= ((size_t)1 << 28), GM_EINVAL, "ipa_from_fields_batch: %zu claims", K);
+  const size_t k = 2 * (rounds - 1);
+  GM_CHECK(messages && challenges && batch_challenges && (k == 0 || (final_lhs_jac && final_rhs_jac)) && ff && fg1 && fg2 && proof, GM_EINVAL, "ipa_from_fields_batch: null pointer");
+  auto p = std::make_unique<IpaProof>();
+  p->rounds = rounds;
+  p->K = K;
+  p->messages.assign(messages, messages + rounds * 144);
+  p->challenges.assign(challenges, challenges + rounds * 4);
+  p->batch_challenges.assign(batch_challenges, batch_challenges + (3 * K + k) * 4);
+  if (k) {
+    p->final_g1.assign(final_lhs_jac, final_lhs_jac + k * 18);
+    p->final_g2.assign(final_rhs_jac, final_rhs_jac + k * 36);
+  }
+  p->batch_ff.assign(ff, ff + K * 8);
+  p->batch_fg1.assign(fg1, fg1 + K * 22);
+  p->batch_fg2.assign(fg2, fg2 + K * 40);
+  memcpy(p->foldings_ff, ff, sizeof p->foldings_ff);
+  memcpy(p->foldings_fg1, fg1, sizeof p->foldings_fg1);
+  memcpy(p->foldings_fg2, fg2, sizeof p->foldings_fg2);
+  *proof = put_in(C, C->ipa, std::move(p));
+  return GM_OK;
+}
+int gm_ipa_verify_batch(uint64_t proof, uint64_t vrs, const uint64_t* comm_a_jac, const uint64_t* comm_b_jac, const uint64_t* y_mont, size_t K, int* ok) {
+  if (ok) *ok = 0;
+  GM_CTX();
+  GM_IPA_FIND(p, ipa, proof, "ipa_verify_batch", "proof");
+  GM_IPA_FIND(v, vrs, vrs, "ipa_verify_batch", "Vrs");
+  GM_CHECK(comm_a_jac && comm_b_jac && y_mont && ok, GM_EINVAL, "ipa_verify_batch: null pointer");
+  return ipa_verify_batch(C, p, v, comm_a_jac, comm_b_jac, y_mont, K, ok);
+}
+int gm_debug_ipa_new_batch_path(size_t counts[3]) {
+  GM_CTX();
+  GM_CHECK(counts != nullptr, GM_EINVAL, "gm_debug_ipa_new_batch_path: null output");
+  GM_MSM_LOCK(C);
+  memcpy(counts, C->ipa_new_batch_last, sizeof C->ipa_new_batch_last);
+  return GM_OK;
 }
 
 // ---- space prover --------------------------------------------------------------------------------

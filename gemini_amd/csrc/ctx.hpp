@@ -185,7 +185,11 @@ struct IpaProof {
   std::vector<uint64_t> challenges;        // rounds x 4, Montgomery
   std::vector<uint64_t> batch_challenges;  // (2 rounds + 1) x 4
   std::vector<uint64_t> final_g1, final_g2;  // 2 (rounds - 1) x 18 / x 36: Sumcheck::final_foldings
-  uint64_t foldings_ff[8], foldings_fg1[22], foldings_fg2[40];  // (lhs || rhs) of the three initial provers
+  uint64_t foldings_ff[8], foldings_fg1[22], foldings_fg2[40];  // (lhs || rhs) of the three initial provers (of claim 0 of a batch proof)
+  // a batch proof (gm_ipa_new_batch, gm_ipa_from_fields_batch): K claims, batch_challenges (3 K + 2 (rounds - 1)) x 4 and the
+  // foldings of all claims, K x 8 / K x 22 / K x 40.  Every other proof has K = 1 and leaves the three vectors empty
+  size_t K = 1;
+  std::vector<uint64_t> batch_ff, batch_fg1, batch_fg2;
   double host_ms[3] = {0, 0, 0};  // of gm_ipa_new: host GT multi-exponentiations, host final exponentiations, the whole call (gm_ipa_host_times)
 };
 
@@ -387,6 +391,8 @@ struct Context {
   // the lockstep path
   size_t ipa_new_many_min = 2;  // S = 1 loses (1004 against 670 ms), S = 2 wins 1014 (max 1017) against 1337 (min 1334) ms at d = 2^10: profiles/ipa_new_many.md
   size_t ipa_new_many_last[4] = {0, 0, 0, 0};
+  // gm_ipa_new_batch: what the last call issued (gm_debug_ipa_new_batch_path): split-fold launches, MSM calls, Miller launches
+  size_t ipa_new_batch_last[3] = {0, 0, 0};
   DevBuf fr_scratch;
   uint64_t* host_small = nullptr;  // pinned, 64 KiB, for small results
   // the descriptor arrays of k_sc_round_multi: a RING of SC_DESC_SLOTS slots of SC_DESC_SLOT bytes, one per launch, pinned on the host
@@ -574,6 +580,8 @@ int g1_lincomb_many_host(Context* C, const void* points, size_t stride, const ui
 // Fr vectors (fr.hip), on C->stream without a wait
 int fr_stride_raw(Context* C, const uint8_t* in, size_t start, size_t stride, size_t count, uint8_t* out);
 int fr_fold_raw(Context* C, const uint8_t* f, size_t n, const uint64_t r[4], uint8_t* out);  // r is read by an asynchronous copy: the caller waits
+// out[i] = sum_j c_j v_j[i], v_j = base + j * pitch_bytes, k vectors of n elements; launches only, the caller waits
+int fr_lincomb_raw(Context* C, const uint8_t* base, size_t pitch_bytes, size_t n, const uint64_t* coeffs_mont, size_t k, uint8_t* out);
 
 // G2 engine (g2msm.hip)
 int g2_msm_run(Context* C, const G2Bases* bases, int64_t first, int64_t step, const void* d_scalars, int mont, size_t n, uint64_t out_jac[36]);
@@ -679,6 +687,11 @@ int ipa_verify_many(Context* C, const IpaProof* const* proofs, const Vrs* vrs, c
 // round) from C->ipa_new_many_min proofs on.  The caller has checked the handles; nothing is absorbed on a refusal.
 int ipa_prove_many(Context* C, const uint64_t* transcripts, const Crs* crs, const uint64_t* a_mont, const uint64_t* b_mont, size_t d, size_t S, IpaProof* const* proofs);
 bool transcript_exists(uint64_t handle);  // transcript.cpp
+// gm_ipa_new_batch: ONE proof for K claims over the same CRS (InnerProductProof::generic, ipa.rs:345-531, every twist one, one d);
+// gm_ipa_verify_batch: verify_transcript with 3 K initial claims.  Nothing is absorbed on a refusal.
+int ipa_prove_batch(Context* C, uint64_t transcript, const Crs* crs, const uint64_t* a_mont /* K x d x 4 */, const uint64_t* b_mont, size_t d, size_t K, IpaProof* proof);
+int ipa_verify_batch(Context* C, const IpaProof* proof, const Vrs* vrs, const uint64_t* comm_a /* K x 18 */, const uint64_t* comm_b /* K x 36 */, const uint64_t* y_mont /* K x 4 */,
+                     size_t K, int* ok);
 // gm_debug_ipa_stated_terms: the canonical exponents of the stated form of one proof, 6 R - 4 GT terms then 2 R + 4 pairing terms
 int ipa_stated_terms(const IpaProof* proof, const uint64_t y_mont[4], uint64_t* gt_exp, uint64_t* pair_exp);
 // Jacobian points of both groups -> the host records of the proof checks and a GM_PT_* status byte each (points.hip), one launch per group

@@ -2051,6 +2051,30 @@ int fr_lincomb(Context* C, FrVec** polys, const uint64_t* coeffs, size_t k, FrVe
   return fr_trim(C, out);
 }
 
+// out[i] = sum_j c_j v_j[i] for k raw device vectors of the same length n, v_j = base + j * pitch_bytes (ipa.hip: the weighted sum
+// of the scalar vectors of a batch proof).  Launches only: the caller waits, and `out` is none of the inputs.
+int fr_lincomb_raw(Context* C, const uint8_t* base, size_t pitch_bytes, size_t n, const uint64_t* coeffs_mont, size_t k, uint8_t* out) {
+  GM_FR_LOCK(C);
+  GM_CHECK(k >= 1 && n >= 1, GM_EINVAL, "lincomb: %zu vectors of %zu elements", k, n);
+  for (size_t j0 = 0; j0 < k; j0 += LINCOMB_MAX) {
+    LincombArgs A;
+    memset(&A, 0, sizeof A);
+    const size_t cnt = k - j0 < LINCOMB_MAX ? k - j0 : LINCOMB_MAX;
+    A.k = (uint32_t)cnt;
+    for (size_t j = 0; j < cnt; j++) {
+      A.p[j] = base + (j0 + j) * pitch_bytes;
+      A.len[j] = n;
+      memcpy(A.c[j], coeffs_mont + 4 * (j0 + j), 32);
+    }
+    if (j0 == 0)
+      hipLaunchKernelGGL(k_lincomb, dim3(grid_for(n)), dim3(256), 0, C->stream, A, n, out);
+    else
+      hipLaunchKernelGGL(k_lincomb_acc, dim3(grid_for(n)), dim3(256), 0, C->stream, A, n, out);
+  }
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
 // out[offsets[j] + i] = c_j * in_j[i], i < len(in_j): several scaled vectors laid out in ONE vector at chosen offsets (the quotients
 // of the block-sharded opening against the back-to-back key slices: one division and one MSM instead of one per level).  k launches,
 // ONE wait.  The ranges must lie inside out's current length (they may not overlap each other: the launches are not ordered by data)

@@ -286,6 +286,48 @@ int arena_round(Context* C, const Crs* crs, Arena& A, const gmh::Fr& challenge, 
   return GM_OK;
 }
 
+// The Miller products of one round message.  aux1 holds (G1 message a, G1 message b, G1 generator), aux2 (G2 generator, G2 message
+// a, G2 message b).  Segments: e(G1, G2); (fg1.a, G2), (fg1.b, G2), (G1, fg2.a), (G1, fg2.b); then a_p, b_p of every PModule prover
+std::vector<PairProduct> round_products(const uint8_t* aux1, const uint8_t* aux2, const Arena& A) {
+  std::vector<PairProduct> prods(5 + 2 * A.live);
+  prods[0].s0 = span(aux1, 2, 1, aux2, 0, 1, 1);
+  prods[1].s0 = span(aux1, 0, 1, aux2, 0, 1, 1);
+  prods[2].s0 = span(aux1, 1, 1, aux2, 0, 1, 1);
+  prods[3].s0 = span(aux1, 2, 1, aux2, 1, 1, 1);
+  prods[4].s0 = span(aux1, 2, 1, aux2, 2, 1, 1);
+  const size_t h = A.m / 2;
+  for (size_t p = 0; p < A.live; p++) {
+    const uint8_t *f = A.g1[A.cur], *g = A.g2[A.cur];
+    const size_t f0 = p * A.m, g0 = (p ^ 1) * A.m;
+    prods[5 + 2 * p].s0 = span(f, f0, 2, g, g0, 2, h);          // a = ip(f_even, g_even)
+    prods[5 + 2 * p + 1].s0 = span(f, f0, 2, g, g0 + 1, 2, h);  // b = ip(f_even, g_odd) + ip(f_odd, g_even)
+    prods[5 + 2 * p + 1].s1 = span(f, f0 + 1, 2, g, g0, 2, h);
+  }
+  return prods;
+}
+
+// The final foldings of the PModule provers (ipa.rs:655-661): every live prover folds once more, to length 1
+int arena_finals(Context* C, const Crs* crs, Arena& A, const uint64_t last[4], IpaProof* proof) {
+  const size_t k = A.live;
+  proof->final_g1.assign(k * 18, 0);
+  proof->final_g2.assign(k * 36, 0);
+  if (!k) return GM_OK;
+  std::vector<uint64_t> f(k * 12), g(k * 24);
+  {
+    GM_MSM_LOCK(C);
+    int rc = arena_round(C, crs, A, gmh::Fr::from_limbs(last), false);
+    if (rc) return rc;
+    GM_HIP(hipMemcpyAsync(f.data(), A.g1[A.cur], k * 96, hipMemcpyDeviceToHost, C->stream));
+    GM_HIP(hipMemcpyAsync(g.data(), A.g2[A.cur], k * 192, hipMemcpyDeviceToHost, C->stream));
+    GM_HIP(hipStreamSynchronize(C->stream));
+  }
+  for (size_t p = 0; p < k; p++) {
+    gmh::g1_affine_to_jac_dev(f.data() + 12 * p).to_limbs(proof->final_g1.data() + 18 * p);
+    gmh::g2_affine_to_jac_dev(g.data() + 24 * (p ^ 1)).to_limbs(proof->final_g2.data() + 36 * p);
+  }
+  return GM_OK;
+}
+
 }  // namespace
 
 // InnerProductProof::new (ipa.rs:533-685)
@@ -354,21 +396,7 @@ int ipa_prove(Context* C, uint64_t transcript, const Crs* crs, const uint64_t* a
     g1_to_record(gmh::G1::from_limbs(g1b), rec1 + 12);
     g2_to_record(gmh::G2::from_limbs(g2a), rec2 + 24);
     g2_to_record(gmh::G2::from_limbs(g2b), rec2 + 48);
-    // segments: e(G1, G2); (fg1.a, G2), (fg1.b, G2), (G1, fg2.a), (G1, fg2.b); then a_p, b_p of every PModule prover
-    std::vector<PairProduct> prods(5 + 2 * A.live);
-    prods[0].s0 = span(aux1, 2, 1, aux2, 0, 1, 1);
-    prods[1].s0 = span(aux1, 0, 1, aux2, 0, 1, 1);
-    prods[2].s0 = span(aux1, 1, 1, aux2, 0, 1, 1);
-    prods[3].s0 = span(aux1, 2, 1, aux2, 1, 1, 1);
-    prods[4].s0 = span(aux1, 2, 1, aux2, 2, 1, 1);
-    const size_t h = A.m / 2;
-    for (size_t p = 0; p < A.live; p++) {
-      const uint8_t *f = A.g1[A.cur], *g = A.g2[A.cur];
-      const size_t f0 = p * A.m, g0 = (p ^ 1) * A.m;
-      prods[5 + 2 * p].s0 = span(f, f0, 2, g, g0, 2, h);          // a = ip(f_even, g_even)
-      prods[5 + 2 * p + 1].s0 = span(f, f0, 2, g, g0 + 1, 2, h);  // b = ip(f_even, g_odd) + ip(f_odd, g_even)
-      prods[5 + 2 * p + 1].s1 = span(f, f0 + 1, 2, g, g0, 2, h);
-    }
+    const std::vector<PairProduct> prods = round_products(aux1, aux2, A);
     std::vector<gmh::Fq12> m(prods.size());
     {
       GM_MSM_LOCK(C);
@@ -427,24 +455,7 @@ int ipa_prove(Context* C, uint64_t transcript, const Crs* crs, const uint64_t* a
 
   uint64_t* last = proof->challenges.data() + 4 * (rounds - 1);
   if ((rc = gm_transcript_challenge_fr(transcript, (const uint8_t*)"sumcheck-chal", 13, last))) return rc;
-  // final foldings: every PModule prover folds once more to length 1 (ipa.rs:655-661)
-  const size_t k = A.live;
-  proof->final_g1.assign(k * 18, 0);
-  proof->final_g2.assign(k * 36, 0);
-  if (k) {
-    std::vector<uint64_t> f(k * 12), g(k * 24);
-    {
-      GM_MSM_LOCK(C);
-      if ((rc = arena_round(C, crs, A, gmh::Fr::from_limbs(last), false))) return rc;
-      GM_HIP(hipMemcpyAsync(f.data(), A.g1[A.cur], k * 96, hipMemcpyDeviceToHost, C->stream));
-      GM_HIP(hipMemcpyAsync(g.data(), A.g2[A.cur], k * 192, hipMemcpyDeviceToHost, C->stream));
-      GM_HIP(hipStreamSynchronize(C->stream));
-    }
-    for (size_t p = 0; p < k; p++) {
-      gmh::g1_affine_to_jac_dev(f.data() + 12 * p).to_limbs(proof->final_g1.data() + 18 * p);
-      gmh::g2_affine_to_jac_dev(g.data() + 24 * (p ^ 1)).to_limbs(proof->final_g2.data() + 36 * p);
-    }
-  }
+  if ((rc = arena_finals(C, crs, A, last, proof))) return rc;
   int has = 0;
   if ((rc = gm_sc_fold(P.ff, last)) || (rc = herring_fold(C, P.h1, last)) || (rc = herring_fold(C, P.h2, last))) return rc;
   if ((rc = gm_sc_final(P.ff, proof->foldings_ff, proof->foldings_ff + 4, &has))) return rc;
@@ -851,27 +862,36 @@ int ipa_prove_many(Context* C, const uint64_t* transcripts, const Crs* crs, cons
 }
 
 // InnerProductProof::verify_transcript (ipa.rs:250-343), GT written multiplicatively.  Its pairings -- the two commitments, the
-// foldings of the three claims and every PModule final folding -- are the 1-pair segments of ONE segmented launch; the claim and the
+// foldings of the initial claims and every PModule final folding -- are the 1-pair segments of ONE segmented launch; the claim and the
 // expected value take one final exponentiation each.
-int ipa_verify(Context* C, const IpaProof* pr, const Vrs* vrs, const uint64_t comm_a[18], const uint64_t comm_b[36], const uint64_t y_mont[4], int* ok) {
-  const size_t R = pr->rounds, k = R >= 1 ? 2 * (R - 1) : 0;
-  GM_CHECK(R >= 1 && pr->messages.size() == R * 144 && pr->challenges.size() == R * 4 && pr->batch_challenges.size() == (3 + k) * 4 && pr->final_g1.size() == k * 18 &&
-               pr->final_g2.size() == k * 36,
-           GM_EINVAL, "ipa_verify: the proof's fields do not have the lengths of %zu rounds", R);
-  GM_CHECK(vrs->levels + 1 >= R, GM_EINVAL, "ipa_verify: a proof of %zu rounds needs %zu levels of the Vrs, it has %zu", R, R - 1, vrs->levels);
+namespace {
+
+// What the initial claims put into the check: the points paired with a generator and the exponents of the six terms.  One claim
+// (ipa_verify): the commitments and the fg1 / fg2 points of the proof, y bch0, bch1, bch2 and ff.lhs ff.rhs bch0, fg1.rhs bch1,
+// fg2.lhs bch2.  K claims (ipa_verify_batch): the four weighted sums over the claims, with exponent one.
+struct InitialTerms {
+  gmh::G1 comm_a, fg1;
+  gmh::G2 comm_b, fg2;
+  Scalar e_y, e_comm_a, e_comm_b;  // claim_0 = E^e_y e(comm_a, G2)^e_comm_a e(G1, comm_b)^e_comm_b   (:284-290)
+  Scalar e_ff, e_fg1, e_fg2;       // expected = E^e_ff e(fg1, G2)^e_fg1 e(G1, fg2)^e_fg2 prod_p e(lhs_p, rhs_p)^bch[first + p]
+  size_t first;                    // of the PModule provers' batch challenges: 3 K
+};
+
+int ipa_verify_terms(Context* C, const IpaProof* pr, const Vrs* vrs, const InitialTerms& T, int* ok) {
+  const size_t R = pr->rounds, k = 2 * (R - 1), n0 = T.first;
   auto fr = [](const uint64_t* p) { return gmh::Fr::from_limbs(p); };
-  std::vector<gmh::Fr> bch(3 + k), ch(R);
-  for (size_t i = 0; i < 3 + k; i++) bch[i] = fr(pr->batch_challenges.data() + 4 * i);
+  std::vector<gmh::Fr> bch(n0 + k), ch(R);
+  for (size_t i = 0; i < n0 + k; i++) bch[i] = fr(pr->batch_challenges.data() + 4 * i);
   for (size_t i = 0; i < R; i++) ch[i] = fr(pr->challenges.data() + 4 * i);
 
   // records: G1 = generator, comm_a, fg1's f0, the Lhs final foldings; G2 = generator, comm_b, fg2's g0, the Rhs final foldings
   std::vector<uint64_t> r1((3 + k) * 12), r2((3 + k) * 24);
   g1_to_record(g1_generator(), r1.data());
-  g1_to_record(gmh::G1::from_limbs(comm_a), r1.data() + 12);
-  g1_to_record(gmh::G1::from_limbs(pr->foldings_fg1), r1.data() + 24);
+  g1_to_record(T.comm_a, r1.data() + 12);
+  g1_to_record(T.fg1, r1.data() + 24);
   g2_to_record(g2_generator(), r2.data());
-  g2_to_record(gmh::G2::from_limbs(comm_b), r2.data() + 24);
-  g2_to_record(gmh::G2::from_limbs(pr->foldings_fg2 + 4), r2.data() + 48);
+  g2_to_record(T.comm_b, r2.data() + 24);
+  g2_to_record(T.fg2, r2.data() + 48);
   for (size_t p = 0; p < k; p++) {
     g1_to_record(gmh::G1::from_limbs(pr->final_g1.data() + 18 * p), r1.data() + 12 * (3 + p));
     g2_to_record(gmh::G2::from_limbs(pr->final_g2.data() + 36 * p), r2.data() + 24 * (3 + p));
@@ -895,8 +915,7 @@ int ipa_verify(Context* C, const IpaProof* pr, const Vrs* vrs, const uint64_t co
     GM_HIP(hipMemcpyAsync(d2, r2.data(), r2.size() * 8, hipMemcpyHostToDevice, C->stream));
     if ((rc = miller_products(C, prods.data(), prods.size(), m.data()))) return rc;
   }
-  // reduced_claim = ip([E^y, e(comm_a, G2), e(G1, comm_b)], batch_challenges[..3])   (:284-290)
-  gmh::Fq12 claim = gt_finish(gt_multi_pow({m[0], m[1], m[2]}, {canonical(fr(y_mont) * bch[0]), canonical(bch[1]), canonical(bch[2])}));
+  gmh::Fq12 claim = gt_finish(gt_multi_pow({m[0], m[1], m[2]}, {T.e_y, T.e_comm_a, T.e_comm_b}));
   auto step = [&](size_t i) {  // a + b challenge + (claim - a) challenge^2   (:302-303, :311-312)
     const gmh::Fq12 a = gmh::Fq12::from_limbs(pr->messages.data() + 144 * i), b = gmh::Fq12::from_limbs(pr->messages.data() + 144 * i + 72);
     const gmh::Fq12 c = claim * a.inv();
@@ -909,19 +928,44 @@ int ipa_verify(Context* C, const IpaProof* pr, const Vrs* vrs, const uint64_t co
     const uint64_t* l2 = vrs->vk2.data() + 144 * (R - 2 - i);
     const gmh::Fq12 g1c = gmh::Fq12::from_limbs(l1) * gt_pow(gmh::Fq12::from_limbs(l1 + 72), ch[i]);
     const gmh::Fq12 g2c = gmh::Fq12::from_limbs(l2) * gt_pow(gmh::Fq12::from_limbs(l2 + 72), ch[i]);
-    claim = step(i) * gt_pow(g1c, bch[3 + 2 * i]) * gt_pow(g2c, bch[3 + 2 * i + 1]);
+    claim = step(i) * gt_pow(g1c, bch[n0 + 2 * i]) * gt_pow(g2c, bch[n0 + 2 * i + 1]);
   }
   claim = step(R - 1);
-  // expected = ip(final_foldings, batch_challenges)   (:314-336); p(f0, g0) of the three claims moves g0 / f0 into the exponent
+  // expected = ip(final_foldings, batch_challenges)   (:314-336); p(f0, g0) of the initial claims moves g0 / f0 into the exponent
   std::vector<gmh::Fq12> x = {m[0], m[3], m[4]};
-  std::vector<Scalar> e = {canonical(fr(pr->foldings_ff) * fr(pr->foldings_ff + 4) * bch[0]), canonical(fr(pr->foldings_fg1 + 18) * bch[1]),
-                           canonical(fr(pr->foldings_fg2) * bch[2])};
+  std::vector<Scalar> e = {T.e_ff, T.e_fg1, T.e_fg2};
   for (size_t p = 0; p < k; p++) {
     x.push_back(m[5 + p]);
-    e.push_back(canonical(bch[3 + p]));
+    e.push_back(canonical(bch[n0 + p]));
   }
   *ok = claim == gt_finish(gt_multi_pow(x, e)) ? 1 : 0;
   return GM_OK;
+}
+
+}  // namespace
+
+int ipa_verify(Context* C, const IpaProof* pr, const Vrs* vrs, const uint64_t comm_a[18], const uint64_t comm_b[36], const uint64_t y_mont[4], int* ok) {
+  const size_t R = pr->rounds, k = R >= 1 ? 2 * (R - 1) : 0;
+  GM_CHECK(pr->K == 1, GM_EINVAL, "ipa_verify: a proof for %zu claims goes to gm_ipa_verify_batch", pr->K);
+  GM_CHECK(R >= 1 && pr->messages.size() == R * 144 && pr->challenges.size() == R * 4 && pr->batch_challenges.size() == (3 + k) * 4 && pr->final_g1.size() == k * 18 &&
+               pr->final_g2.size() == k * 36,
+           GM_EINVAL, "ipa_verify: the proof's fields do not have the lengths of %zu rounds", R);
+  GM_CHECK(vrs->levels + 1 >= R, GM_EINVAL, "ipa_verify: a proof of %zu rounds needs %zu levels of the Vrs, it has %zu", R, R - 1, vrs->levels);
+  auto fr = [](const uint64_t* p) { return gmh::Fr::from_limbs(p); };
+  const gmh::Fr b0 = fr(pr->batch_challenges.data()), b1 = fr(pr->batch_challenges.data() + 4), b2 = fr(pr->batch_challenges.data() + 8);
+  InitialTerms T;
+  T.comm_a = gmh::G1::from_limbs(comm_a);
+  T.comm_b = gmh::G2::from_limbs(comm_b);
+  T.fg1 = gmh::G1::from_limbs(pr->foldings_fg1);
+  T.fg2 = gmh::G2::from_limbs(pr->foldings_fg2 + 4);
+  T.e_y = canonical(fr(y_mont) * b0);
+  T.e_comm_a = canonical(b1);
+  T.e_comm_b = canonical(b2);
+  T.e_ff = canonical(fr(pr->foldings_ff) * fr(pr->foldings_ff + 4) * b0);
+  T.e_fg1 = canonical(fr(pr->foldings_fg1 + 18) * b1);
+  T.e_fg2 = canonical(fr(pr->foldings_fg2) * b2);
+  T.first = 3;
+  return ipa_verify_terms(C, pr, vrs, T, ok);
 }
 
 // ---- many proofs in one call ----------------------------------------------------------------------------------------------------
@@ -976,6 +1020,7 @@ void ipa_state(const IpaProof* pr, const uint64_t y_mont[4], std::vector<gmh::Fr
 // the lengths ipa_verify asks of a proof and of the Vrs, with its codes
 int ipa_shape(const IpaProof* pr, const Vrs* vrs, const char* who) {
   const size_t R = pr->rounds, k = R >= 1 ? 2 * (R - 1) : 0;
+  GM_CHECK(pr->K == 1, GM_EINVAL, "%s: a proof for %zu claims goes to gm_ipa_verify_batch", who, pr->K);
   GM_CHECK(R >= 1 && pr->messages.size() == R * 144 && pr->challenges.size() == R * 4 && pr->batch_challenges.size() == (3 + k) * 4 && pr->final_g1.size() == k * 18 &&
                pr->final_g2.size() == k * 36,
            GM_EINVAL, "%s: the proof's fields do not have the lengths of %zu rounds", who, R);
@@ -1161,6 +1206,304 @@ int ipa_verify_many(Context* C, const IpaProof* const* proofs, const Vrs* vrs, c
   C->ipa_verify_many_last[0] = nclean;
   C->ipa_verify_many_last[1] = S - nclean;
   return GM_OK;
+}
+
+// ---- one proof for many claims ----------------------------------------------------------------------------------------------------
+// InnerProductProof::generic (ipa.rs:345-531) for K claims <a_i, b_i> = y_i, <a_i, crs.g1> = comm_a_i, <b_i, crs.g2> = comm_b_i with
+// every twist one and every vector of length d: ONE batched sumcheck, one set of round messages and one set of CRS-fold provers.
+// Run literally that is 3 K initial provers.  The batch weights of the initial provers are powers(bc, 3 K) of the first batch
+// challenge and stay fixed for the whole proof, and fold and message of a module prover are linear in its scalar side, so
+//
+//   the K G1Module provers over crs.g1 are ONE G1Module prover over ca = sum_i bc^(K+i) a_i, its messages entering with weight 1
+//   the K G2Module provers over crs.g2 are ONE G2Module prover over cb = sum_i bc^(2K+i) b_i, likewise
+//   the final scalar of G1Module prover i is the final lhs of FModule prover i (the same vector, the same challenges, twist 1), the
+//   final point is the folded CRS for every i; the same holds for G2 with rhs
+//
+// and only the K FModule provers stay per claim: they step together (gm_sc_round_begin_many, one challenge for all).  The PModule
+// arena, its fold and the segmented Miller launch of a round are those of ipa_prove.  tests/ipa_batch_ref.py states both forms on
+// Python integers and holds them equal field for field.  No witness takes a twist: the reference's TimeProver uses the twist in
+// `fold` and not in the message (time_prover.rs:83-123), so a proof with another twist cannot satisfy the verifier.
+namespace {
+
+struct BatchProvers {
+  Context* C;
+  std::vector<uint64_t> ff;
+  uint64_t fg1 = 0, fg2 = 0;
+  HerringProver *h1 = nullptr, *h2 = nullptr;
+  ~BatchProvers() {
+    for (uint64_t h : ff) (void)gm_sc_free(h);
+    if (fg1) (void)gm_hg1_free(fg1);
+    if (fg2) (void)gm_hg2_free(fg2);
+  }
+};
+
+}  // namespace
+
+int ipa_prove_batch(Context* C, uint64_t transcript, const Crs* crs, const uint64_t* a_mont, const uint64_t* b_mont, size_t d, size_t K, IpaProof* proof) {
+  // every refusal comes before the first challenge
+  GM_CHECK(K >= 1, GM_EINVAL, "ipa_new_batch: no claims");
+  GM_CHECK(d >= 2, GM_EINVAL, "ipa_new_batch: d = %zu; the argument needs at least two scalars (the reference's round loop underflows at rounds - 1, ipa.rs:420)", d);
+  const size_t rounds = (size_t)msm_ceil_log2(d), full = (size_t)1 << rounds;
+  const size_t need = std::max(d + 1, full);
+  GM_CHECK(crs->n1 >= need && crs->n2 >= need, GM_EINVAL, "ipa_new_batch: d = %zu needs a CRS of max(d + 1, 2^rounds) = %zu points, it has %zu / %zu", d, need, crs->n1, crs->n2);
+  GM_CHECK(transcript_exists(transcript), GM_EHANDLE, "ipa_new_batch: unknown transcript handle %llu", (unsigned long long)transcript);
+  {
+    // the PModule arena and the message records, then the scalars: a_i and b_i in their FModule prover and once more for the sums
+    const size_t arena = (rounds > 1 ? 4 * full * (96 + 192) : 0) + 3 * (96 + 192) + 2 * d * 32;
+    size_t free_b = 0, total_b = 0;
+    GM_HIP(hipMemGetInfo(&free_b, &total_b));
+    const bool fits = K <= (SIZE_MAX - arena) / (4 * d * 32) && arena + 4 * K * d * 32 <= free_b;
+    GM_CHECK(fits, GM_ENOMEM, "ipa_new_batch: %zu claims of d = %zu need an arena of %zu bytes and 4 K d 32 bytes of scalars, the device has %zu free", K, d, arena, free_b);
+  }
+  uint64_t one[4];
+  gmh::Fr::one().to_limbs(one);
+  size_t counts[3] = {0, 0, 0};  // split-fold launches, MSM calls, Miller launches, where they are issued
+  typedef std::chrono::steady_clock Clock;
+  auto ms_since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
+  const Clock::time_point t_start = Clock::now();
+
+  BatchProvers P{C};
+  int rc;
+  P.ff.reserve(K);
+  for (size_t i = 0; i < K; i++) {
+    uint64_t h = 0;
+    if ((rc = gm_sc_new(a_mont + 4 * i * d, d, b_mont + 4 * i * d, d, one, &h))) return rc;
+    P.ff.push_back(h);
+    if ((rc = gm_sc_set_herring(h, 1))) return rc;
+  }
+  Scratch mem;
+  Arena A;
+  uint8_t *aux1 = nullptr, *aux2 = nullptr, *d_ab = nullptr, *d_c = nullptr;  // d_ab: a_0 .. a_{K-1}, b_0 .. b_{K-1}; d_c: ca, cb
+  if ((rc = mem.get(3 * 96, &aux1)) || (rc = mem.get(3 * 192, &aux2)) || (rc = mem.get(2 * K * d * 32, &d_ab)) || (rc = mem.get(2 * d * 32, &d_c))) return rc;
+  if (rounds > 1) {
+    for (int i = 0; i < 2; i++)
+      if ((rc = mem.get(2 * full * 96, &A.g1[i])) || (rc = mem.get(2 * full * 192, &A.g2[i]))) return rc;
+  }
+  A.m = full;
+  GM_HIP(hipMemcpyAsync(d_ab, a_mont, K * d * 32, hipMemcpyHostToDevice, C->stream));
+  GM_HIP(hipMemcpyAsync(d_ab + K * d * 32, b_mont, K * d * 32, hipMemcpyHostToDevice, C->stream));
+  GM_HIP(hipStreamSynchronize(C->stream));
+  uint64_t rec1[36], rec2[72];
+  g1_to_record(g1_generator(), rec1 + 24);
+  g2_to_record(g2_generator(), rec2);
+
+  proof->rounds = rounds;
+  proof->K = K;
+  proof->messages.assign(rounds * 144, 0);
+  proof->challenges.assign(rounds * 4, 0);
+  proof->batch_challenges.clear();
+  proof->host_ms[0] = proof->host_ms[1] = proof->host_ms[2] = 0;
+  std::vector<gmh::Fr> bch;
+  auto push_bch = [&](const gmh::Fr& x) {
+    bch.push_back(x);
+    uint64_t l[4];
+    x.to_limbs(l);
+    proof->batch_challenges.insert(proof->batch_challenges.end(), l, l + 4);
+  };
+
+  // the first batch challenge fixes the weights of the 3 K initial provers: the sums, then the two module provers over them
+  uint64_t ch[4];
+  if ((rc = gm_transcript_challenge_fr(transcript, (const uint8_t*)"batch-chal", 10, ch))) return rc;
+  {
+    const gmh::Fr bc = gmh::Fr::from_limbs(ch);
+    gmh::Fr w = gmh::Fr::one();
+    for (size_t i = 0; i < 3 * K; i++, w = w * bc) push_bch(w);
+  }
+  if ((rc = fr_lincomb_raw(C, d_ab, d * 32, d, proof->batch_challenges.data() + 4 * K, K, d_c))) return rc;
+  if ((rc = fr_lincomb_raw(C, d_ab + K * d * 32, d * 32, d, proof->batch_challenges.data() + 8 * K, K, d_c + d * 32))) return rc;
+  GM_HIP(hipStreamSynchronize(C->stream));
+  // the G1 / G2 provers get the first 2^rounds points, as in ipa_prove; both sides are on the device and are copied
+  if ((rc = herring_create(C, HERRING_G1, crs->g1, 96, full, d_c, 32, d, one, &P.fg1, 3))) return rc;
+  if ((rc = herring_create(C, HERRING_G2, d_c + d * 32, 32, d, crs->g2, 192, full, one, &P.fg2, 3))) return rc;
+  {
+    std::lock_guard<std::mutex> lk(C->mu);
+    P.h1 = C->herring[P.fg1].get();
+    P.h2 = C->herring[P.fg2].get();
+  }
+
+  // One message of the batched sumcheck: the K FModule provers step in one launch group, the two module provers as in ipa_prove,
+  // then ONE segmented Miller launch and the two GT multi-exponentiations E^(sum_i bc^i fa_i) m_g1 m_g2 prod_p m_p^bch[3K+p]
+  std::vector<int> has_many(K);
+  auto round_message = [&](const uint64_t* vm, uint64_t* out144) -> int {
+    uint64_t fa[4], fb[4], g1a[18], g1b[18], g2a[36], g2b[36];
+    int has = 0, r;
+    if ((r = gm_sc_round_begin_many(P.ff.data(), K, vm, has_many.data()))) return r;
+    gmh::Fr sa = gmh::Fr::zero(), sb = gmh::Fr::zero();
+    int all = 1;
+    for (size_t i = 0; i < K; i++) {
+      if (!has_many[i]) {
+        all = 0;
+        continue;
+      }
+      if ((r = gm_sc_round_end(P.ff[i], fa, fb))) return r;
+      sa = sa + gmh::Fr::from_limbs(fa) * bch[i];
+      sb = sb + gmh::Fr::from_limbs(fb) * bch[i];
+    }
+    GM_CHECK(all, GM_ESTATE, "ipa_new_batch: an FModule prover has no message");
+    if ((r = herring_round(C, P.h1, vm, g1a, g1b, &has))) return r;
+    GM_CHECK(has, GM_ESTATE, "ipa_new_batch: the G1Module prover has no message");
+    if ((r = herring_round(C, P.h2, vm, g2a, g2b, &has))) return r;
+    GM_CHECK(has, GM_ESTATE, "ipa_new_batch: the G2Module prover has no message");
+    counts[0] += vm ? 2 : 0;  // the point side of either module prover folds in one launch
+    counts[1] += 1 + 3;       // g1_message: one batch of three strided MSMs; g2_message: three MSMs
+    g1_to_record(gmh::G1::from_limbs(g1a), rec1);
+    g1_to_record(gmh::G1::from_limbs(g1b), rec1 + 12);
+    g2_to_record(gmh::G2::from_limbs(g2a), rec2 + 24);
+    g2_to_record(gmh::G2::from_limbs(g2b), rec2 + 48);
+    const std::vector<PairProduct> prods = round_products(aux1, aux2, A);
+    std::vector<gmh::Fq12> m(prods.size());
+    {
+      GM_MSM_LOCK(C);
+      GM_HIP(hipMemcpyAsync(aux1, rec1, sizeof rec1, hipMemcpyHostToDevice, C->stream));
+      GM_HIP(hipMemcpyAsync(aux2, rec2, sizeof rec2, hipMemcpyHostToDevice, C->stream));
+      if ((r = miller_products(C, prods.data(), prods.size(), m.data()))) return r;
+      counts[2] += 1;
+    }
+    const Scalar unit = canonical(gmh::Fr::one());
+    for (int half = 0; half < 2; half++) {
+      std::vector<gmh::Fq12> x = {m[0], m[1 + half], m[3 + half]};
+      std::vector<Scalar> e = {canonical(half ? sb : sa), unit, unit};
+      for (size_t p = 0; p < A.live; p++) {
+        x.push_back(m[5 + 2 * p + half]);
+        e.push_back(canonical(bch[3 * K + p]));
+      }
+      Clock::time_point t0 = Clock::now();
+      const gmh::Fq12 prod = gt_multi_pow(x, e);
+      proof->host_ms[0] += ms_since(t0);
+      t0 = Clock::now();
+      gt_finish(prod).to_limbs(out144 + 72 * half);
+      proof->host_ms[1] += ms_since(t0);
+    }
+    return GM_OK;
+  };
+
+  if ((rc = round_message(nullptr, proof->messages.data()))) return rc;
+  if ((rc = gm_transcript_append_gt(transcript, (const uint8_t*)"prover_message", 14, proof->messages.data(), 2))) return rc;
+  for (size_t j = 0; j + 1 < rounds; j++) {
+    uint64_t* c = proof->challenges.data() + 4 * j;
+    if ((rc = gm_transcript_challenge_fr(transcript, (const uint8_t*)"sumcheck-chal", 13, c))) return rc;
+    if ((rc = gm_transcript_challenge_fr(transcript, (const uint8_t*)"batch-chal", 10, ch))) return rc;
+    const gmh::Fr b = gmh::Fr::from_limbs(ch);
+    push_bch(b);
+    push_bch(b.sqr());
+    {
+      GM_MSM_LOCK(C);
+      if ((rc = arena_round(C, crs, A, gmh::Fr::from_limbs(c), true))) return rc;
+      counts[0] += 2;
+    }
+    uint64_t* msg = proof->messages.data() + 144 * (j + 1);
+    if ((rc = round_message(c, msg))) return rc;
+    if ((rc = gm_transcript_append_gt(transcript, (const uint8_t*)"sumcheck-round", 14, msg, 2))) return rc;
+  }
+  uint64_t* last = proof->challenges.data() + 4 * (rounds - 1);
+  if ((rc = gm_transcript_challenge_fr(transcript, (const uint8_t*)"sumcheck-chal", 13, last))) return rc;
+  counts[0] += A.live ? 2 : 0;
+  if ((rc = arena_finals(C, crs, A, last, proof))) return rc;
+
+  // final foldings: ff_i from prover i; fg1_i = (the folded CRS point, ff_i.lhs); fg2_i = (ff_i.rhs, the folded CRS point)
+  int has = 0;
+  uint64_t p1[18 + 4], p2[4 + 36];
+  if ((rc = herring_fold(C, P.h1, last)) || (rc = herring_fold(C, P.h2, last))) return rc;
+  counts[0] += 2;
+  if ((rc = herring_final(C, P.h1, p1, p1 + 18, &has))) return rc;
+  GM_CHECK(has, GM_ESTATE, "ipa_new_batch: the G1Module prover has no final foldings");
+  if ((rc = herring_final(C, P.h2, p2, p2 + 4, &has))) return rc;
+  GM_CHECK(has, GM_ESTATE, "ipa_new_batch: the G2Module prover has no final foldings");
+  proof->batch_ff.assign(K * 8, 0);
+  proof->batch_fg1.assign(K * 22, 0);
+  proof->batch_fg2.assign(K * 40, 0);
+  for (size_t i = 0; i < K; i++) {
+    uint64_t* ff = proof->batch_ff.data() + 8 * i;
+    if ((rc = gm_sc_fold(P.ff[i], last)) || (rc = gm_sc_final(P.ff[i], ff, ff + 4, &has))) return rc;
+    GM_CHECK(has, GM_ESTATE, "ipa_new_batch: FModule prover %zu has no final foldings", i);
+    memcpy(proof->batch_fg1.data() + 22 * i, p1, 18 * 8);
+    memcpy(proof->batch_fg1.data() + 22 * i + 18, ff, 4 * 8);
+    memcpy(proof->batch_fg2.data() + 40 * i, ff + 4, 4 * 8);
+    memcpy(proof->batch_fg2.data() + 40 * i + 4, p2 + 4, 36 * 8);
+  }
+  memcpy(proof->foldings_ff, proof->batch_ff.data(), sizeof proof->foldings_ff);
+  memcpy(proof->foldings_fg1, proof->batch_fg1.data(), sizeof proof->foldings_fg1);
+  memcpy(proof->foldings_fg2, proof->batch_fg2.data(), sizeof proof->foldings_fg2);
+  proof->host_ms[2] = ms_since(t_start);
+  {
+    GM_MSM_LOCK(C);
+    memcpy(C->ipa_new_batch_last, counts, sizeof counts);
+  }
+  return GM_OK;
+}
+
+// verify_transcript (ipa.rs:250-343) with 3 K initial claims.  claim_0 = ip([E^y_i] ++ [e(comm_a_i, G2)] ++ [e(G1, comm_b_i)], bch[..3K])
+// and the initial part of the expected value, ip over (ff_i, fg1_i, fg2_i), are bilinear in the points, so the 4 K pairings are four:
+// sum_i bch[K+i] comm_a_i and sum_i bch[K+i] fg1_i.rhs fg1_i.lhs in G1, sum_i bch[2K+i] comm_b_i and sum_i bch[2K+i] fg2_i.lhs
+// fg2_i.rhs in G2, each of K terms through the short linear combinations (k_term_mul, k_seg_sum with the complete addition: a hostile
+// proof can make terms equal or opposite).  The FModule terms are one exponent of E each.  Launches do not depend on K.  As
+// ipa_verify, it takes the points as members (gm_ipa_check says whether they are).
+int ipa_verify_batch(Context* C, const IpaProof* pr, const Vrs* vrs, const uint64_t* comm_a, const uint64_t* comm_b, const uint64_t* y_mont, size_t K, int* ok) {
+  GM_CHECK(K >= 1 && K == pr->K, GM_EINVAL, "ipa_verify_batch: %zu claims for a proof of %zu", K, pr->K);
+  const size_t R = pr->rounds, k = R >= 1 ? 2 * (R - 1) : 0;
+  const uint64_t *ff = K == 1 && pr->batch_ff.empty() ? pr->foldings_ff : pr->batch_ff.data(), *fg1 = K == 1 && pr->batch_fg1.empty() ? pr->foldings_fg1 : pr->batch_fg1.data(),
+                 *fg2 = K == 1 && pr->batch_fg2.empty() ? pr->foldings_fg2 : pr->batch_fg2.data();
+  GM_CHECK(R >= 1 && pr->messages.size() == R * 144 && pr->challenges.size() == R * 4 && pr->batch_challenges.size() == (3 * K + k) * 4 && pr->final_g1.size() == k * 18 &&
+               pr->final_g2.size() == k * 36 && (K == 1 || (pr->batch_ff.size() == K * 8 && pr->batch_fg1.size() == K * 22 && pr->batch_fg2.size() == K * 40)),
+           GM_EINVAL, "ipa_verify_batch: the proof's fields do not have the lengths of %zu rounds and %zu claims", R, K);
+  GM_CHECK(vrs->levels + 1 >= R, GM_EINVAL, "ipa_verify_batch: a proof of %zu rounds needs %zu levels of the Vrs, it has %zu", R, R - 1, vrs->levels);
+  bool reduced = true;
+  for (size_t i = 0; i < K; i++)
+    reduced = reduced && fr_reduced(y_mont + 4 * i) && fr_reduced(ff + 8 * i) && fr_reduced(ff + 8 * i + 4) && fr_reduced(fg1 + 22 * i + 18) && fr_reduced(fg2 + 40 * i);
+  for (size_t i = 0; i < pr->batch_challenges.size(); i += 4) reduced = reduced && fr_reduced(pr->batch_challenges.data() + i);
+  GM_CHECK(reduced, GM_EINVAL, "ipa_verify_batch: a y, a folding scalar or a batch challenge is not a reduced residue");
+  if (K == 1) return ipa_verify(C, pr, vrs, comm_a, comm_b, y_mont, ok);  // gm_ipa_verify's verdict on every input
+
+  auto fr = [](const uint64_t* p) { return gmh::Fr::from_limbs(p); };
+  const uint64_t* bch = pr->batch_challenges.data();
+  // affine host records (ark-ff's Montgomery form, the identity all zero) and canonical scalars; segments: comm_a, fg1 / comm_b, fg2
+  std::vector<uint64_t> pts1(2 * K * 12, 0), pts2(2 * K * 24, 0), sc1(2 * K * 4), sc2(2 * K * 4);
+  auto put1 = [&](size_t t, const uint64_t* jac, const gmh::Fr& e) {
+    const gmh::G1 p = gmh::G1::from_limbs(jac);
+    if (!p.is_identity()) {
+      const gmh::G1 q = p.normalized();
+      q.x.to_limbs(pts1.data() + 12 * t);
+      q.y.to_limbs(pts1.data() + 12 * t + 6);
+    }
+    e.to_canonical(sc1.data() + 4 * t);
+  };
+  auto put2 = [&](size_t t, const uint64_t* jac, const gmh::Fr& e) {
+    const gmh::G2 p = gmh::G2::from_limbs(jac);
+    if (!p.is_identity()) {
+      const gmh::G2 q = p.normalized();
+      q.x.c0.to_limbs(pts2.data() + 24 * t);
+      q.x.c1.to_limbs(pts2.data() + 24 * t + 6);
+      q.y.c0.to_limbs(pts2.data() + 24 * t + 12);
+      q.y.c1.to_limbs(pts2.data() + 24 * t + 18);
+    }
+    e.to_canonical(sc2.data() + 4 * t);
+  };
+  gmh::Fr ey = gmh::Fr::zero(), eff = gmh::Fr::zero();
+  for (size_t i = 0; i < K; i++) {
+    const gmh::Fr w0 = fr(bch + 4 * i), w1 = fr(bch + 4 * (K + i)), w2 = fr(bch + 4 * (2 * K + i));
+    ey = ey + w0 * fr(y_mont + 4 * i);
+    eff = eff + w0 * fr(ff + 8 * i) * fr(ff + 8 * i + 4);
+    put1(i, comm_a + 18 * i, w1);
+    put1(K + i, fg1 + 22 * i, w1 * fr(fg1 + 22 * i + 18));
+    put2(i, comm_b + 36 * i, w2);
+    put2(K + i, fg2 + 40 * i + 4, w2 * fr(fg2 + 40 * i));
+  }
+  const size_t offsets[3] = {0, K, 2 * K};
+  uint64_t sum1[2 * 18], sum2[2 * 36];
+  int rc;
+  if ((rc = g1_lincomb_many_host(C, pts1.data(), 96, sc1.data(), offsets, 2, sum1))) return rc;
+  if ((rc = g2_lincomb_many_host(C, pts2.data(), 192, sc2.data(), offsets, 2, sum2))) return rc;
+  const Scalar unit = canonical(gmh::Fr::one());
+  InitialTerms T;
+  T.comm_a = gmh::G1::from_limbs(sum1);
+  T.fg1 = gmh::G1::from_limbs(sum1 + 18);
+  T.comm_b = gmh::G2::from_limbs(sum2);
+  T.fg2 = gmh::G2::from_limbs(sum2 + 36);
+  T.e_y = canonical(ey);
+  T.e_ff = canonical(eff);
+  T.e_comm_a = T.e_comm_b = T.e_fg1 = T.e_fg2 = unit;
+  T.first = 3 * K;
+  return ipa_verify_terms(C, pr, vrs, T, ok);
 }
 
 }  // namespace gm

@@ -202,6 +202,9 @@ class IpaFields:
     foldings_ff: np.ndarray       # (2, 4)
     foldings_fg1: tuple           # ((18,), (4,))
     foldings_fg2: tuple           # ((4,), (36,))
+    # a proof for K claims (InnerProductProof.new_batch): batch_challenges (3 K + 2 (rounds - 1), 4) and K-long foldings,
+    # foldings_ff (K, 2, 4), foldings_fg1 ((K, 18), (K, 4)), foldings_fg2 ((K, 4), (K, 36))
+    claims: int = 1
 
 
 class InnerProductProof:
@@ -237,6 +240,70 @@ class InnerProductProof:
         return [cls(int(h)) for h in hs]
 
     @classmethod
+    def new_batch(cls, transcript, crs: Crs, a_monts, b_monts) -> "InnerProductProof":
+        """gm_ipa_new_batch: ONE proof for the K claims <a_i, b_i> = y_i, <a_i, crs.g1> = comm_a_i, <b_i, crs.g2> = comm_b_i
+        (InnerProductProof::generic with every twist one): one transcript, one set of round messages.  All vectors have the same
+        length d.  K = 1 is `new` byte for byte."""
+        capi.ensure_init()
+        K = len(a_monts)
+        assert len(b_monts) == K and K >= 1
+        a = np.ascontiguousarray(np.stack([capi.u64(x).reshape(-1, 4) for x in a_monts]))
+        b = np.ascontiguousarray(np.stack([capi.u64(x).reshape(-1, 4) for x in b_monts]))
+        assert a.shape == b.shape
+        h = C.c_uint64()
+        capi.check(capi.load().gm_ipa_new_batch(C.c_uint64(transcript.handle), C.c_uint64(crs.handle), capi.ptr(a), capi.ptr(b), C.c_size_t(a.shape[1]), C.c_size_t(K),
+                                                C.byref(h)))
+        return cls(h.value)
+
+    @classmethod
+    def from_fields_batch(cls, f: IpaFields) -> "InnerProductProof":
+        """gm_ipa_from_fields_batch: a proof for f.claims claims from `batch_fields()`"""
+        capi.ensure_init()
+        K, k = f.claims, 2 * (f.rounds - 1)
+        fg1 = np.ascontiguousarray(np.concatenate([capi.u64(f.foldings_fg1[0]).reshape(K, 18), capi.u64(f.foldings_fg1[1]).reshape(K, 4)], axis=1))
+        fg2 = np.ascontiguousarray(np.concatenate([capi.u64(f.foldings_fg2[0]).reshape(K, 4), capi.u64(f.foldings_fg2[1]).reshape(K, 36)], axis=1))
+        lhs, rhs = capi.u64(f.final_lhs).reshape(k, 18), capi.u64(f.final_rhs).reshape(k, 36)
+        h = C.c_uint64()
+        capi.check(capi.load().gm_ipa_from_fields_batch(C.c_size_t(f.rounds), C.c_size_t(K), capi.ptr(capi.u64(f.messages).reshape(f.rounds, 144)),
+                                                        capi.ptr(capi.u64(f.challenges).reshape(f.rounds, 4)),
+                                                        capi.ptr(capi.u64(f.batch_challenges).reshape(3 * K + k, 4)), capi.ptr(lhs) if k else None,
+                                                        capi.ptr(rhs) if k else None, capi.ptr(capi.u64(f.foldings_ff).reshape(K, 8)), capi.ptr(fg1), capi.ptr(fg2),
+                                                        C.byref(h)))
+        return cls(h.value)
+
+    @property
+    def claims(self) -> int:
+        """gm_ipa_claims: K of a `new_batch` proof, 1 for every other"""
+        n = C.c_size_t()
+        capi.check(capi.load().gm_ipa_claims(C.c_uint64(self.handle), C.byref(n)))
+        return n.value
+
+    def batch_fields(self) -> IpaFields:
+        """the fields with K-long foldings, whatever K is (gm_ipa_foldings_batch)"""
+        lib, h = capi.load(), C.c_uint64(self.handle)
+        n = C.c_size_t()
+        capi.check(lib.gm_ipa_rounds(h, C.byref(n)))
+        r, K = n.value, self.claims
+        k = 2 * (r - 1)
+        msgs, ch, bch = np.empty((r, 2, 72), dtype=np.uint64), np.empty((r, 4), dtype=np.uint64), np.empty((3 * K + k, 4), dtype=np.uint64)
+        lhs, rhs = np.empty((k, 18), dtype=np.uint64), np.empty((k, 36), dtype=np.uint64)
+        ff, fg1, fg2 = np.empty((K, 2, 4), dtype=np.uint64), np.empty((K, 22), dtype=np.uint64), np.empty((K, 40), dtype=np.uint64)
+        capi.check(lib.gm_ipa_messages(h, capi.ptr(msgs)))
+        capi.check(lib.gm_ipa_challenges(h, capi.ptr(ch)))
+        capi.check(lib.gm_ipa_batch_challenges(h, capi.ptr(bch)))
+        capi.check(lib.gm_ipa_final_foldings(h, capi.ptr(lhs) if k else None, capi.ptr(rhs) if k else None))
+        capi.check(lib.gm_ipa_foldings_batch(h, capi.ptr(ff), capi.ptr(fg1), capi.ptr(fg2)))
+        return IpaFields(r, msgs, ch, bch, lhs, rhs, ff, (fg1[:, :18].copy(), fg1[:, 18:].copy()), (fg2[:, :4].copy(), fg2[:, 4:].copy()), K)
+
+    def verify_batch(self, vrs: Vrs, comm_as, comm_bs, ys) -> bool:
+        """gm_ipa_verify_batch: verify_transcript with 3 K initial claims; True for Ok(()).  K = len(ys) must be the proof's."""
+        K = len(ys)
+        ca, cb, y = capi.u64(comm_as).reshape(K, 18), capi.u64(comm_bs).reshape(K, 36), capi.u64(ys).reshape(K, 4)
+        ok = C.c_int()
+        capi.check(capi.load().gm_ipa_verify_batch(C.c_uint64(self.handle), C.c_uint64(vrs.handle), capi.ptr(ca), capi.ptr(cb), capi.ptr(y), C.c_size_t(K), C.byref(ok)))
+        return bool(ok.value)
+
+    @classmethod
     def from_fields(cls, f: IpaFields) -> "InnerProductProof":
         capi.ensure_init()
         k = 2 * (f.rounds - 1)
@@ -252,6 +319,9 @@ class InnerProductProof:
         return cls(h.value)
 
     def fields(self) -> IpaFields:
+        """the fields of the proof; one for K > 1 claims has K-long foldings (`batch_fields`)"""
+        if self.claims != 1:
+            return self.batch_fields()
         lib, h = capi.load(), C.c_uint64(self.handle)
         n = C.c_size_t()
         capi.check(lib.gm_ipa_rounds(h, C.byref(n)))
@@ -341,6 +411,14 @@ def new_many_path() -> tuple:
     capi.ensure_init()
     counts = (C.c_size_t * 4)()
     capi.check(capi.load().gm_debug_ipa_new_many_path(counts))
+    return tuple(int(c) for c in counts)
+
+
+def new_batch_path() -> tuple:
+    """gm_debug_ipa_new_batch_path, for the last new_batch call: (split-fold launches, MSM calls, Miller launches)"""
+    capi.ensure_init()
+    counts = (C.c_size_t * 3)()
+    capi.check(capi.load().gm_debug_ipa_new_batch_path(counts))
     return tuple(int(c) for c in counts)
 
 

@@ -671,8 +671,9 @@ int gm_debug_miller_each(const void* g1, size_t g1_stride, const void* g2, size_
  * gm_gt_mul / gm_gt_pow (tests/test_gpu_ipa_stepwise.py).
  * Scalars are Montgomery limbs, points normalised Jacobian, GT elements 72 limbs as in the pairing block.  The reference defines no
  * wire format for this proof and none is claimed: the getters return the fields.
- * OUT OF SCOPE: InnerProductProof::generic (pub(crate), called by one test of the reference only) and CrsStream (its fold is a
- * todo!() in the reference, ipa.rs:143-145). */
+ * InnerProductProof::generic (:345-531) is in as the CRS-shaped batch, gm_ipa_new_batch below: K claims over the same CRS, every
+ * twist one, one d.  OUT OF SCOPE: generic over witnesses whose point vectors are not the CRS, twists other than one, a different
+ * d per claim, and CrsStream (its fold is a todo!() in the reference, ipa.rs:143-145). */
 /* Crs over resident G1 and G2 arrays; records and strides as gm_g1_bases_register / gm_g2_bases_register take them */
 int gm_crs_new(const void* g1, size_t g1_stride, size_t n1, const void* g2, size_t g2_stride, size_t n2, uint64_t* handle);
 int gm_crs_free(uint64_t handle);
@@ -775,6 +776,56 @@ int gm_ipa_verify_many(const uint64_t* proofs /* S handles */, uint64_t vrs, con
 int gm_set_ipa_verify_many_min(size_t proofs);
 int gm_debug_ipa_verify_many_path(size_t counts[2]);
 int gm_debug_ipa_stated_terms(uint64_t proof, const uint64_t y_mont[4], uint64_t* gt_exponents, uint64_t* pairing_exponents);
+/* ONE proof for K claims <a_i, b_i> = y_i, comm_a_i = <a_i, crs.g1>, comm_b_i = <b_i, crs.g2>: InnerProductProof::generic
+ * (ipa.rs:345-531) with f_ip = [Witness(a_i, b_i, 1)], g1_ip = [Witness(crs.g1s, a_i, 1)], g2_ip = [Witness(b_i, crs.g2s, 1)] and
+ * every vector of length d -- one batched sumcheck, one set of round messages and one set of CRS-fold provers, where S calls of
+ * gm_ipa_new (or gm_ipa_new_many) make S proofs and S transcripts.  a_mont / b_mont: K x d x 4 limbs.
+ * Labels and their order are gm_ipa_new's.  batch_challenges = powers(bc, 3 K) of the first batch challenge, then (c, c^2) per
+ * round: 3 K + 2 (rounds - 1) entries, the weights in the order ff_0 .. ff_{K-1}, fg1_0 .., fg2_0 .., then the PModule provers in
+ * push order.  The other fields keep their meaning; foldings_ff / _fg1 / _fg2 have K entries each.  K = 1 is gm_ipa_new byte for
+ * byte and leaves the transcript in the same state.
+ * No entry takes a twist.  The reference's Witness carries one, but its TimeProver uses it in `fold` and not in the message
+ * (time_prover.rs:83-123): a proof with another twist cannot satisfy the verifier's a + b c + (claim - a) c^2.  `generic` unwraps a
+ * message from every prover in every round, so all claims need the same number of rounds in any case; here they have the same d.
+ * Only the scalar side grows with K.  The batch weights of the initial provers are fixed for the whole proof, and fold and message
+ * of a module prover are linear in its scalars: the K G1Module provers over the CRS are ONE over sum_i bc^(K+i) a_i, the K
+ * G2Module provers ONE over sum_i bc^(2K+i) b_i (both sums are formed on the device after the first challenge), their messages
+ * enter the round message with weight one, the final scalar of G1Module prover i is the final lhs of FModule prover i and its final
+ * point the folded CRS for every i.  The K FModule provers step together (gm_sc_round_begin_many: one launch per 22 provers); the
+ * PModule arena, its two fold launches and the one segmented Miller launch of a round are gm_ipa_new's.  The numbers of split-fold
+ * launches, MSM calls and Miller launches do not depend on K: gm_debug_ipa_new_batch_path gives them for the last call on the
+ * context, counted where they are issued.  The MSM lock is taken per round.  tests/ipa_batch_ref.py states the literal 3 K-prover
+ * form and this one on Python integers and holds them equal; tests/stepwise/ipa_generic.py composes the literal form from the
+ * single provers of this library.
+ * Refused before the first challenge, with nothing absorbed and no handle made: GM_EINVAL for K = 0, d < 2, a CRS shorter than
+ * max(d + 1, 2^rounds) in either group and null pointers; GM_EHANDLE for a stale transcript or CRS; GM_ENOMEM (the message has both
+ * numbers) when the arena plus 4 K d 32 bytes of scalars does not fit the free device memory.
+ * gm_ipa_claims: K (1 for every proof made by another entry).  gm_ipa_foldings_batch: the layouts of the single-claim getters
+ * repeated K times, ff K x 8, fg1 K x (lhs_jac || rhs_mont) = K x 22, fg2 K x (lhs_mont || rhs_jac) = K x 40.  gm_ipa_rounds,
+ * _messages, _challenges, _final_foldings, _free and _check_gt work on a batch proof as they are; gm_ipa_batch_challenges writes
+ * 3 K + 2 (rounds - 1) entries; gm_ipa_check visits the fg1 and fg2 points of claims 0 .. K - 1 where it visits those of the one
+ * claim.  gm_ipa_verify, gm_ipa_verify_many, gm_ipa_foldings_ff / _fg1 / _fg2, gm_debug_ipa_stated_terms and gm_ipa_host_times
+ * answer GM_EINVAL for a proof with K > 1 and are unchanged for K = 1.
+ * gm_ipa_from_fields_batch: a proof object from its fields, laid out as the getters return them.
+ * gm_ipa_verify_batch: verify_transcript (ipa.rs:250-343) with the constant 3 replaced by 3 K -- claim_0 = ip([E^y_i] ++
+ * [e(comm_a_i, G2)] ++ [e(G1, comm_b_i)], batch_challenges[..3K]), the round loop reads batch_challenges[3K + 2i] and [3K + 2i + 1],
+ * the final foldings are all ff, all fg1, all fg2, then the PModule pairs.  The reference has no verifier for `generic`; this
+ * generalisation is the library's own.  The 4 K pairings of the initial claims are four: sum_i w_i comm_a_i, sum_i w_i comm_b_i,
+ * sum_i w_i rhs_i P_i and sum_i w_i lhs_i Q_i go through the short linear combinations of both groups (complete addition: a hostile
+ * proof can make terms equal or opposite), the FModule terms are one exponent of E each, and one segmented pairing launch follows;
+ * launches do not depend on K.  *ok = 0 for a proof that fails.  GM_EINVAL when K differs from the proof's, for a Vrs with fewer
+ * than rounds - 1 levels, and for a y, a folding scalar or a batch challenge that is not a reduced residue.  For K = 1 the verdict is
+ * gm_ipa_verify's on every input.  Like gm_ipa_verify it takes points as members: gm_ipa_check tests the proof's. */
+int gm_ipa_new_batch(uint64_t transcript, uint64_t crs, const uint64_t* a_mont /* K x d x 4 */, const uint64_t* b_mont /* K x d x 4 */, size_t d, size_t K,
+                     uint64_t* proof);
+int gm_ipa_claims(uint64_t proof, size_t* K);
+int gm_ipa_foldings_batch(uint64_t proof, uint64_t* ff /* K x 8 */, uint64_t* fg1 /* K x 22 */, uint64_t* fg2 /* K x 40 */);
+int gm_ipa_from_fields_batch(size_t rounds, size_t K, const uint64_t* messages, const uint64_t* challenges, const uint64_t* batch_challenges /* (3 K + 2 (rounds - 1)) x 4 */,
+                             const uint64_t* final_lhs_jac, const uint64_t* final_rhs_jac, const uint64_t* ff /* K x 8 */, const uint64_t* fg1 /* K x 22 */,
+                             const uint64_t* fg2 /* K x 40 */, uint64_t* proof);
+int gm_ipa_verify_batch(uint64_t proof, uint64_t vrs, const uint64_t* comm_a_jac /* K x 18 */, const uint64_t* comm_b_jac /* K x 36 */, const uint64_t* y_mont /* K x 4 */,
+                        size_t K, int* ok);
+int gm_debug_ipa_new_batch_path(size_t counts[3]);
 
 /* ---- Fiat-Shamir transcript (host; no GPU needed) ------------------------------------------------ */
 /* merlin::Transcript::new(label) (merlin 3.0.0, Cargo.lock:606-608); the prover uses

@@ -1048,8 +1048,8 @@ class InnerProductProof {  // ipa.rs:54-60
     check(gm_ipa_challenges(h_, c[0].data()));
     return c;
   }
-  std::vector<Fr> batch_challenges() const {
-    std::vector<Fr> c(2 * rounds() + 1);
+  std::vector<Fr> batch_challenges() const {  // 3 K + 2 (rounds - 1): 2 rounds + 1 for one claim
+    std::vector<Fr> c(3 * claims() + 2 * (rounds() - 1));
     check(gm_ipa_batch_challenges(h_, c[0].data()));
     return c;
   }
@@ -1135,6 +1135,67 @@ class InnerProductProof {  // ipa.rs:54-60
     out.reserve(S);
     for (size_t s = 0; s < S; s++) out.push_back(InnerProductProof(h[s]));
     return out;
+  }
+  // ONE proof for the K claims <a[i], b[i]> = y[i], <a[i], crs.g1> = comm_a[i], <b[i], crs.g2> = comm_b[i] (gm_ipa_new_batch:
+  // InnerProductProof::generic, ipa.rs:345-531, over the CRS with every twist one): one transcript, one set of round messages.
+  // One length for all vectors.  K = 1 is the constructor's proof byte for byte
+  static InnerProductProof new_batch(Transcript& transcript, const Crs& crs, const std::vector<std::vector<Fr>>& a, const std::vector<std::vector<Fr>>& b) {
+    const size_t K = a.size(), d = K ? a[0].size() : 0;
+    if (b.size() != K) throw Error(GM_EINVAL, "InnerProductProof::new_batch: one b per a");
+    std::vector<Fr> fa, fb;
+    for (size_t i = 0; i < K; i++) {
+      if (a[i].size() != d || b[i].size() != d) throw Error(GM_EINVAL, "InnerProductProof::new_batch: the vectors of one proof have one length");
+      fa.insert(fa.end(), a[i].begin(), a[i].end());
+      fb.insert(fb.end(), b[i].begin(), b[i].end());
+    }
+    uint64_t h = 0;
+    Fr none{};  // K = 0 or d = 0 is refused by the library, which wants pointers to say so
+    check(gm_ipa_new_batch(transcript.handle(), crs.handle(), fa.empty() ? none.data() : fa[0].data(), fb.empty() ? none.data() : fb[0].data(), d, K, &h));
+    return InnerProductProof(h);
+  }
+  // K of a new_batch proof, 1 for every other (gm_ipa_claims)
+  size_t claims() const {
+    size_t K = 0;
+    check(gm_ipa_claims(h_, &K));
+    return K;
+  }
+  // the foldings of all K claims (gm_ipa_foldings_batch); foldings_ff / _fg1 / _fg2 above are for proofs of one claim
+  struct BatchFoldings {
+    std::vector<std::pair<Fr, Fr>> ff;
+    std::vector<std::pair<G1Projective, Fr>> fg1;
+    std::vector<std::pair<Fr, G2Projective>> fg2;
+  };
+  BatchFoldings foldings_batch() const {
+    const size_t K = claims();
+    std::vector<uint64_t> ff(K * 8), fg1(K * 22), fg2(K * 40);
+    check(gm_ipa_foldings_batch(h_, ff.data(), fg1.data(), fg2.data()));
+    BatchFoldings r;
+    r.ff.resize(K);
+    r.fg1.resize(K);
+    r.fg2.resize(K);
+    for (size_t i = 0; i < K; i++) {
+      memcpy(r.ff[i].first.data(), ff.data() + 8 * i, 32);
+      memcpy(r.ff[i].second.data(), ff.data() + 8 * i + 4, 32);
+      memcpy(r.fg1[i].first.data(), fg1.data() + 22 * i, 18 * 8);
+      memcpy(r.fg1[i].second.data(), fg1.data() + 22 * i + 18, 32);
+      memcpy(r.fg2[i].first.data(), fg2.data() + 40 * i, 32);
+      memcpy(r.fg2[i].second.data(), fg2.data() + 40 * i + 4, 36 * 8);
+    }
+    return r;
+  }
+  // verify_transcript with 3 K initial claims (gm_ipa_verify_batch): true for Ok(()); K = y.size() must be the proof's
+  bool verify_batch(const Vrs& vrs, const std::vector<G1Projective>& comm_a, const std::vector<G2Projective>& comm_b, const std::vector<Fr>& y) const {
+    const size_t K = y.size();
+    if (K == 0 || comm_a.size() != K || comm_b.size() != K) throw Error(GM_EINVAL, "InnerProductProof::verify_batch: one commitment pair and one y per claim");
+    int ok = 0;
+    check(gm_ipa_verify_batch(h_, vrs.handle(), comm_a[0].data(), comm_b[0].data(), y[0].data(), K, &ok));
+    return ok != 0;
+  }
+  // of the last new_batch call: split-fold launches, MSM calls, Miller launches (gm_debug_ipa_new_batch_path); none depends on K
+  static std::array<size_t, 3> new_batch_path() {
+    std::array<size_t, 3> c{};
+    check(gm_debug_ipa_new_batch_path(c.data()));
+    return c;
   }
   // fewer proofs than this are made one by one (gm_set_ipa_new_many_min); the bytes do not depend on it
   static void set_new_many_min(size_t proofs) { check(gm_set_ipa_new_many_min(proofs)); }
