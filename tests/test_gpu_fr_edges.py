@@ -15,6 +15,7 @@ import pytest
 
 from gemini_amd import fr as F
 from oracle import pyref
+from tests.fr_cases import EDGE, EDGE_CANON, EDGE_LIMBS, R_MINUS_1, Vec, canon, edge_limbs, limbs, mont, vectors  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -30,60 +31,6 @@ def gm():
 
     gemini_amd.capi.init()
     return gemini_amd
-
-
-def edge_limbs():
-    """Montgomery limb patterns, every one a valid element (< r)"""
-    top = R >> 224
-    out = [0, 1, R - 1, R - 2, (1 << 224) - 1, (top << 224) - 1, top << 224, (R - 1) // 2, (R + 1) // 2, (1 << 256) % R]
-    out += [1 << (32 * k) for k in range(1, 8)] + [0xFFFFFFFF << (32 * k) for k in range(7)]
-    assert all(0 <= v < R for v in out) and len(set(out)) == len(out)
-    return tuple(out)
-
-
-EDGE = edge_limbs()
-
-
-def limbs(ms) -> np.ndarray:
-    """Montgomery integers -> (n, 4) uint64, as they are"""
-    return np.array([[(m >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)] for m in ms], dtype=np.uint64).reshape(len(ms), 4)
-
-
-def canon(ms):
-    """the field elements the limbs stand for"""
-    return [m * RINV % R for m in ms]
-
-
-def mont(vs) -> np.ndarray:
-    """field elements -> the limbs the device must give"""
-    return limbs([v * (1 << 256) % R for v in vs])
-
-
-EDGE_LIMBS, EDGE_CANON = limbs(EDGE), canon(EDGE)
-
-
-class Vec:
-    """a vector drawn from EDGE by index: the limbs for the device, the field elements for the reference"""
-
-    def __init__(self, idx):
-        self.idx = np.asarray(idx, dtype=np.int64) % len(EDGE)
-
-    @property
-    def limbs(self) -> np.ndarray:
-        return EDGE_LIMBS[self.idx]
-
-    @property
-    def canon(self):
-        return [EDGE_CANON[i] for i in self.idx.tolist()]
-
-
-def vectors(n: int, shift: int):
-    """two vectors cycling through the list with different strides, so every pair of edge values meets within 24^2 elements"""
-    i = np.arange(n, dtype=np.int64)
-    return Vec(i + shift), Vec(i // len(EDGE) + 3 * i + 2 * shift)
-
-
-R_MINUS_1 = EDGE.index(R - 1)
 
 
 CASES = [(n, s) for n in LENGTHS for s in (0, 2)] + [(len(EDGE) ** 2, 1)]  # the last: every value against every value
