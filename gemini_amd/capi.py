@@ -66,6 +66,9 @@ SYMBOLS = [
     "gm_ipa_foldings_fg1", "gm_ipa_foldings_fg2", "gm_ipa_free", "gm_ipa_host_times", "gm_ipa_from_fields", "gm_ipa_verify", "gm_ipa_verify_many", "gm_set_ipa_verify_many_min", "gm_debug_ipa_verify_many_path", "gm_debug_ipa_stated_terms", "gm_transcript_append_gt",
     "gm_ipa_new_many", "gm_set_ipa_new_many_min", "gm_debug_ipa_new_many_path", "gm_g2_lincomb_many",
     "gm_ipa_new_batch", "gm_ipa_claims", "gm_ipa_foldings_batch", "gm_ipa_from_fields_batch", "gm_ipa_verify_batch", "gm_debug_ipa_new_batch_path",
+    "gm_hsp1_new_borrow", "gm_hsp1_new", "gm_hsp1_round", "gm_hsp1_fold", "gm_hsp1_rounds", "gm_hsp1_final", "gm_hsp1_to_time", "gm_hsp1_free",
+    "gm_hsp2_new_borrow", "gm_hsp2_new", "gm_hsp2_round", "gm_hsp2_fold", "gm_hsp2_rounds", "gm_hsp2_final", "gm_hsp2_to_time", "gm_hsp2_free",
+    "gm_debug_hsp_path",
 ]
 
 

@@ -74,21 +74,31 @@ __global__ __launch_bounds__(G::KEY_BLOCK) __attribute__((amdgpu_waves_per_eu(G:
 
 // herring split_fold: out[i] = P[2i] + s * P[2i+1] (an odd tail: P[2i] alone), affine out.  s: canonical scalar, 8 x u32.  One lane
 // per output: 255-bit double-and-add, one addition, one inversion.
-template <class G>
+template <class G, bool REV = false>
 __global__ __launch_bounds__(G::KEY_BLOCK) void k_split_fold(const uint8_t* __restrict__ in, size_t n, const uint32_t* __restrict__ s8, uint8_t* __restrict__ out) {
   const size_t m = (n + 1) / 2;
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= m) return;
+  // REV: record j of the vector is in[n - 1 - j] (a big-endian stream read as the little-endian vector it stands for)
+  const auto at = [&](size_t j) { return in + (REV ? n - 1 - j : j) * G::AFF_BYTES; };
   typename G::Xyzz acc = G::identity();
   if (2 * i + 1 < n) {
-    const typename G::Affine hi = G::load_affine(in + (2 * i + 1) * G::AFF_BYTES);
+    const typename G::Affine hi = G::load_affine(at(2 * i + 1));
     for (int bit = 254; bit >= 0; bit--) {
       acc = G::dbl(acc);
       if ((s8[bit >> 5] >> (bit & 31)) & 1u) G::madd(acc, hi);
     }
   }
-  G::madd(acc, G::load_affine(in + (2 * i) * G::AFF_BYTES));
+  G::madd(acc, G::load_affine(at(2 * i)));
   G::store_affine(out + i * G::AFF_BYTES, grp_to_affine<G>(acc));
+}
+
+// out[i] = in[n - 1 - i] over records of 16 q bytes, one lane per 16 bytes
+__global__ __launch_bounds__(256) void k_records_reverse(const uint4* __restrict__ in, size_t n, uint32_t q, uint4* __restrict__ out) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n * q) return;
+  const size_t i = t / q, c = t % q;
+  out[t] = in[(n - 1 - i) * q + c];
 }
 
 // The segmented form: lane i folds pair i % m of span i / m, m = (n + 1) / 2 -- the spans of many proofs in one launch, each under
@@ -233,6 +243,14 @@ template <class G>
 int split_fold_launch(hipStream_t st, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out) {
   const size_t m = (n + 1) / 2;
   hipLaunchKernelGGL(k_split_fold<G>, dim3((unsigned)((m + G::KEY_BLOCK - 1) / G::KEY_BLOCK)), dim3(G::KEY_BLOCK), 0, st, in, n, d_s8, out);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+// the same with the records read backwards (k_split_fold<G, true>)
+template <class G>
+static int split_fold_rev_launch(hipStream_t st, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out) {
+  const size_t m = (n + 1) / 2;
+  hipLaunchKernelGGL((k_split_fold<G, true>), dim3((unsigned)((m + G::KEY_BLOCK - 1) / G::KEY_BLOCK)), dim3(G::KEY_BLOCK), 0, st, in, n, d_s8, out);
   GM_HIP(hipGetLastError());
   return GM_OK;
 }
@@ -402,6 +420,16 @@ int g1_pack_launch(hipStream_t st, const uint8_t* src, size_t stride, size_t n, 
 int g1_normalise_launch(hipStream_t st, const uint8_t* in, size_t n, uint8_t* out) { return normalise_launch<GrpG1>(st, in, nullptr, n, out); }
 int g1_split_fold_launch(Context* C, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out) { return split_fold_launch<GrpG1>(C->stream, in, n, d_s8, out); }
 int g2_split_fold_launch(Context* C, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out) { return split_fold_launch<GrpG2>(C->stream, in, n, d_s8, out); }
+int g1_split_fold_rev_launch(Context* C, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out) { return split_fold_rev_launch<GrpG1>(C->stream, in, n, d_s8, out); }
+int g2_split_fold_rev_launch(Context* C, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out) { return split_fold_rev_launch<GrpG2>(C->stream, in, n, d_s8, out); }
+int records_reverse_launch(Context* C, const uint8_t* in, size_t n, size_t rec_bytes, uint8_t* out) {
+  const size_t lanes = n * (rec_bytes / 16);
+  if (lanes == 0) return GM_OK;
+  hipLaunchKernelGGL(k_records_reverse, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, C->stream, reinterpret_cast<const uint4*>(in), n,
+                     (uint32_t)(rec_bytes / 16), reinterpret_cast<uint4*>(out));
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
 int g1_split_fold_seg_launch(Context* C, const FoldSpan* d_spans, size_t nspans, size_t n, const uint32_t* d_s8) { return split_fold_seg_launch<GrpG1>(C->stream, d_spans, nspans, n, d_s8); }
 int g2_split_fold_seg_launch(Context* C, const FoldSpan* d_spans, size_t nspans, size_t n, const uint32_t* d_s8) { return split_fold_seg_launch<GrpG2>(C->stream, d_spans, nspans, n, d_s8); }
 int g1_term_mul_launch(Context* C, const uint8_t* d_points, const uint32_t* d_pidx, const uint8_t* d_scalars, const uint32_t* d_sidx, int mont, size_t T, uint8_t* d_out_xyzz) {

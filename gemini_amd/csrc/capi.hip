@@ -575,6 +575,7 @@ void gm_shutdown(void) {
   for (auto& kv : C->provers) sc_destroy(kv.second.get());
   for (auto& kv : C->space_provers) sp_destroy(C, kv.second.get());
   for (auto& kv : C->herring) herring_destroy(C, kv.second.get());
+  for (auto& kv : C->herring_space) hsp_destroy(C, kv.second.get());
   for (auto& kv : C->g2_bases)
     if (kv.second->d) (void)gm::raw_free(kv.second->d);
   for (auto& kv : C->crs) crs_destroy(kv.second.get());
@@ -1957,6 +1958,137 @@ int gm_hg2_final(uint64_t handle, uint64_t f0_mont[4], uint64_t g0_jac[36], int*
 int gm_hg2_free(uint64_t handle) {
   GM_CTX();
   return herring_free(C, handle, HERRING_G2, "hg2_free");
+}
+
+// ---- herring: space prover over G1Module / G2Module (herring.hip: hsp_*) ------------------------------
+// one handle table for both modules; a handle of the other module is unknown to this one's calls
+static HerringSpace* find_hsp(Context* C, uint64_t h, int module) {  // module < 0: either
+  std::lock_guard<std::mutex> lk(C->mu);
+  auto it = C->herring_space.find(h);
+  return it == C->herring_space.end() || (module >= 0 && it->second->module != module) ? nullptr : it->second.get();
+}
+#define GM_HSP(var, h, M, who)                      \
+  HerringSpace* var = find_hsp(C, h, HERRING_##M);  \
+  GM_CHECK(var != nullptr, GM_EHANDLE, who ": unknown herring " #M " space prover handle %llu", (unsigned long long)(h))
+static int hsp_rounds(const HerringSpace* H, size_t* tot_rounds, size_t* round) {
+  if (tot_rounds) *tot_rounds = H->tot_rounds;
+  if (round) *round = H->round;
+  return GM_OK;
+}
+static int hsp_free(Context* C, uint64_t handle, HerringModule module, const char* who) {
+  std::unique_ptr<HerringSpace> p;
+  {
+    std::lock_guard<std::mutex> lk(C->mu);
+    auto it = C->herring_space.find(handle);
+    GM_CHECK(it != C->herring_space.end() && it->second->module == module, GM_EHANDLE, "%s: unknown handle %llu", who, (unsigned long long)handle);
+    p = std::move(it->second);
+    C->herring_space.erase(it);
+  }
+  hsp_destroy(C, p.get());
+  return GM_OK;
+}
+int gm_hsp1_new_borrow(uint64_t g1_bases_handle, size_t offset, size_t nf, uint64_t g_stream_vec, const uint64_t twist_mont[4], uint64_t* handle) {
+  GM_CTX();
+  GM_CHECK(twist_mont && handle, GM_EINVAL, "hsp1_new_borrow: null pointer");
+  Bases* b = find_bases(g1_bases_handle);
+  GM_CHECK(b != nullptr, GM_EHANDLE, "hsp1_new_borrow: unknown bases handle %llu", (unsigned long long)g1_bases_handle);
+  GM_VEC(vg, g_stream_vec, "hsp1_new_borrow");
+  return hsp_create(C, HERRING_G1, b, offset, nullptr, 0, nf, vg->d, vg->len, true, twist_mont, handle);
+}
+int gm_hsp1_new(const void* f_bases, size_t base_stride, size_t nf, const uint64_t* g_stream_mont, size_t ng, const uint64_t twist_mont[4],
+                uint64_t* handle) {
+  GM_CTX();
+  GM_CHECK(f_bases && g_stream_mont && twist_mont && handle, GM_EINVAL, "hsp1_new: null pointer");
+  return hsp_create(C, HERRING_G1, nullptr, 0, f_bases, base_stride, nf, g_stream_mont, ng, false, twist_mont, handle);
+}
+int gm_hsp1_round(uint64_t handle, const uint64_t* challenge_or_null, uint64_t a_jac[18], uint64_t b_jac[18], int* has_msg) {
+  GM_CTX();
+  GM_HSP(H, handle, G1, "hsp1_round");
+  GM_CHECK(a_jac && b_jac && has_msg, GM_EINVAL, "hsp1_round: null pointer");
+  return hsp_round(C, H, challenge_or_null, a_jac, b_jac, has_msg);
+}
+int gm_hsp1_fold(uint64_t handle, const uint64_t challenge_mont[4]) {
+  GM_CTX();
+  GM_HSP(H, handle, G1, "hsp1_fold");
+  GM_CHECK(challenge_mont != nullptr, GM_EINVAL, "hsp1_fold: null pointer");
+  return hsp_fold(C, H, challenge_mont);
+}
+int gm_hsp1_rounds(uint64_t handle, size_t* tot_rounds, size_t* round) {
+  GM_CTX();
+  GM_HSP(H, handle, G1, "hsp1_rounds");
+  return hsp_rounds(H, tot_rounds, round);
+}
+int gm_hsp1_final(uint64_t handle, uint64_t f0_jac[18], uint64_t g0_mont[4], int* has) {
+  GM_CTX();
+  GM_HSP(H, handle, G1, "hsp1_final");
+  GM_CHECK(f0_jac && g0_mont && has, GM_EINVAL, "hsp1_final: null pointer");
+  return hsp_final(C, H, f0_jac, g0_mont, has);
+}
+int gm_hsp1_to_time(uint64_t handle, uint64_t* hg1_handle) {
+  GM_CTX();
+  GM_HSP(H, handle, G1, "hsp1_to_time");
+  GM_CHECK(hg1_handle != nullptr, GM_EINVAL, "hsp1_to_time: null pointer");
+  return hsp_to_time(C, H, hg1_handle);
+}
+int gm_hsp1_free(uint64_t handle) {
+  GM_CTX();
+  return hsp_free(C, handle, HERRING_G1, "hsp1_free");
+}
+int gm_hsp2_new_borrow(uint64_t f_stream_vec, uint64_t g2_bases_handle, size_t offset, size_t ng, const uint64_t twist_mont[4], uint64_t* handle) {
+  GM_CTX();
+  GM_CHECK(twist_mont && handle, GM_EINVAL, "hsp2_new_borrow: null pointer");
+  G2Bases* b = GrpG2::find(C, g2_bases_handle);
+  GM_CHECK(b != nullptr, GM_EHANDLE, "hsp2_new_borrow: unknown G2 bases handle %llu", (unsigned long long)g2_bases_handle);
+  GM_VEC(vf, f_stream_vec, "hsp2_new_borrow");
+  return hsp_create(C, HERRING_G2, b, offset, nullptr, 0, ng, vf->d, vf->len, true, twist_mont, handle);
+}
+int gm_hsp2_new(const uint64_t* f_stream_mont, size_t nf, const void* g_bases, size_t base_stride, size_t ng, const uint64_t twist_mont[4],
+                uint64_t* handle) {
+  GM_CTX();
+  GM_CHECK(f_stream_mont && g_bases && twist_mont && handle, GM_EINVAL, "hsp2_new: null pointer");
+  return hsp_create(C, HERRING_G2, nullptr, 0, g_bases, base_stride, ng, f_stream_mont, nf, false, twist_mont, handle);
+}
+int gm_hsp2_round(uint64_t handle, const uint64_t* challenge_or_null, uint64_t a_jac[36], uint64_t b_jac[36], int* has_msg) {
+  GM_CTX();
+  GM_HSP(H, handle, G2, "hsp2_round");
+  GM_CHECK(a_jac && b_jac && has_msg, GM_EINVAL, "hsp2_round: null pointer");
+  return hsp_round(C, H, challenge_or_null, a_jac, b_jac, has_msg);
+}
+int gm_hsp2_fold(uint64_t handle, const uint64_t challenge_mont[4]) {
+  GM_CTX();
+  GM_HSP(H, handle, G2, "hsp2_fold");
+  GM_CHECK(challenge_mont != nullptr, GM_EINVAL, "hsp2_fold: null pointer");
+  return hsp_fold(C, H, challenge_mont);
+}
+int gm_hsp2_rounds(uint64_t handle, size_t* tot_rounds, size_t* round) {
+  GM_CTX();
+  GM_HSP(H, handle, G2, "hsp2_rounds");
+  return hsp_rounds(H, tot_rounds, round);
+}
+int gm_hsp2_final(uint64_t handle, uint64_t f0_mont[4], uint64_t g0_jac[36], int* has) {
+  GM_CTX();
+  GM_HSP(H, handle, G2, "hsp2_final");
+  GM_CHECK(f0_mont && g0_jac && has, GM_EINVAL, "hsp2_final: null pointer");
+  return hsp_final(C, H, g0_jac, f0_mont, has);
+}
+int gm_hsp2_to_time(uint64_t handle, uint64_t* hg2_handle) {
+  GM_CTX();
+  GM_HSP(H, handle, G2, "hsp2_to_time");
+  GM_CHECK(hg2_handle != nullptr, GM_EINVAL, "hsp2_to_time: null pointer");
+  return hsp_to_time(C, H, hg2_handle);
+}
+int gm_hsp2_free(uint64_t handle) {
+  GM_CTX();
+  return hsp_free(C, handle, HERRING_G2, "hsp2_free");
+}
+int gm_debug_hsp_path(uint64_t handle, size_t out[4]) {
+  GM_CTX();
+  GM_CHECK(out != nullptr, GM_EINVAL, "gm_debug_hsp_path: null output");
+  HerringSpace* H = find_hsp(C, handle, -1);
+  GM_CHECK(H != nullptr, GM_EHANDLE, "gm_debug_hsp_path: unknown herring space prover handle %llu", (unsigned long long)handle);
+  std::lock_guard<std::mutex> lk(H->mu);
+  for (int i = 0; i < 4; i++) out[i] = H->path[i];
+  return GM_OK;
 }
 
 // ---- pairings: multi-Miller loop and GT helpers (pairing.hip), the herring PModule prover ----------------

@@ -206,6 +206,46 @@ struct G2Bases {
   uint8_t* d = nullptr;
   size_t n = 0;
 };
+// herring SpaceProver over G1Module / G2Module (src/herring/space_prover.rs:39-276; herring.hip): the point side is `np` points of a
+// key, read where they lie as the big-endian stream key[offset + i] and never written or copied; the scalar side is kept folded,
+// little-endian, in two ping-pong blocks of the vector pool.  A message is one launch of k_hsp_scalars and two MSMs over the key
+struct HerringSpace {
+  HerringModule module = HERRING_G1;  // HERRING_G1 (points are the Lhs) or HERRING_G2 (points are the Rhs)
+  const Bases* g1 = nullptr;          // the key: the caller's registered handle, or own_g1 / own_g2 (gm_hsp1_new / gm_hsp2_new)
+  const G2Bases* g2 = nullptr;
+  std::unique_ptr<Bases> own_g1;
+  std::unique_ptr<G2Bases> own_g2;
+  size_t offset = 0, np = 0;  // the points key[offset .. offset + np)
+  size_t ns = 0;              // length of the scalar stream
+  uint8_t* s[2] = {nullptr, nullptr};  // the folded scalar vector S (little-endian, Montgomery) and the block the next fold writes
+  size_t scap[2] = {0, 0};
+  int cur = 0;
+  size_t ls = 0;              // current length of S: ceil(ns / 2^k)
+  uint8_t* work = nullptr;    // the expanded scalars of a message (2 x np x 32 B, canonical), the half tensor tables, the challenges
+  size_t work_cap = 0;
+  std::vector<uint64_t> pt_ch;        // the challenges that fold the point side, 4 limbs each, Montgomery (twisted for G1Module)
+  std::vector<uint64_t> pt_ch_canon;  // the same as canonical integers, for split_fold (gm_hsp*_to_time)
+  uint64_t twist[4];
+  size_t round = 0, tot_rounds = 0;
+  size_t path[4] = {0, 0, 0, 0};  // gm_debug_hsp_path: MSM calls, expansion launches, point bytes allocated, scalar bytes allocated
+  std::mutex mu;
+};
+// what one launch of k_hsp_scalars is told (fr.hip: hsp_scalars_raw).  Lane t serves the point key[offset + t], whose little-endian
+// index is i = np - 1 - t, block m = i >> k, place u = i & (2^k - 1) inside it
+struct HspArgs {
+  const uint8_t* S = nullptr;  // folded scalars, little-endian, Montgomery; entries at and past `ls` count as zero
+  size_t ls = 0;
+  const uint8_t *lo = nullptr, *hi = nullptr;  // tensor(point-side challenges) = lo[u & (2^klo - 1)] hi[u >> klo]
+  uint32_t k = 0, klo = 0;
+  size_t np = 0;      // points of the stream
+  size_t lanes = 0;   // lanes of the launch: the first `lanes` points of the stream
+  size_t npairs = 0;  // blocks 2j and 2j + 1 with j >= npairs carry zero scalars
+  uint64_t twist[4];  // Montgomery
+  int rhs_points = 0;  // G2Module: the points are the Rhs, so the twist factor of b sits on the even block
+  int final_only = 0;  // out_a[t] = the weight of point t alone (final_foldings: the caller launches the lanes of the top block only)
+  uint8_t *out_a = nullptr, *out_b = nullptr;  // np x 32 B each, canonical
+};
+
 // What a G2 MSM holds beyond the sort buffers it shares with G1 (MsmWorkspace counts / offsets / cursor / entries / ...):
 // buckets and chunk partials in 384-byte XYZZ records, the two ping-pong levels of the bucket reduction, the pinned window sums
 struct G2Workspace {
@@ -352,6 +392,7 @@ struct Context {
   std::unordered_map<uint64_t, std::unique_ptr<SparseMatrix>> matrices;
   std::unordered_map<uint64_t, std::unique_ptr<SpaceProver>> space_provers;
   std::unordered_map<uint64_t, std::unique_ptr<HerringProver>> herring;
+  std::unordered_map<uint64_t, std::unique_ptr<HerringSpace>> herring_space;
   std::unordered_map<uint64_t, std::unique_ptr<Crs>> crs;
   std::unordered_map<uint64_t, std::unique_ptr<Vrs>> vrs;
   std::unordered_map<uint64_t, std::unique_ptr<IpaProof>> ipa;
@@ -549,6 +590,11 @@ int g1_normalise_launch(hipStream_t st, const uint8_t* in, size_t n, uint8_t* ou
 // out[i] = in[2i] + s in[2i+1] over packed affine records (an odd tail folds against the identity), s at d_s8 (canonical, 8 x u32), on C->stream
 int g1_split_fold_launch(Context* C, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out);
 int g2_split_fold_launch(Context* C, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out);
+// the same over records read backwards, in[n - 1 - j] in place of in[j]: the first level over a key that holds a big-endian stream
+int g1_split_fold_rev_launch(Context* C, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out);
+int g2_split_fold_rev_launch(Context* C, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out);
+// out[i] = in[n - 1 - i] over records of rec_bytes (a multiple of 16), `out` apart from `in`
+int records_reverse_launch(Context* C, const uint8_t* in, size_t n, size_t rec_bytes, uint8_t* out);
 // The segmented form (k_split_fold_seg): span k folds its n records at `in` to (n + 1) / 2 records at `out` by the canonical scalar
 // in row `ch` of the table d_s8 (8 x u32 a row) -- the spans of many proofs in one launch, every proof under its own challenge.
 // All spans of a launch have the same length n; the table of spans is on the device.  On C->stream without a wait.
@@ -580,6 +626,10 @@ int g1_lincomb_many_host(Context* C, const void* points, size_t stride, const ui
 // Fr vectors (fr.hip), on C->stream without a wait
 int fr_stride_raw(Context* C, const uint8_t* in, size_t start, size_t stride, size_t count, uint8_t* out);
 int fr_fold_raw(Context* C, const uint8_t* f, size_t n, const uint64_t r[4], uint8_t* out);  // r is read by an asynchronous copy: the caller waits
+int fr_reverse_raw(Context* C, const uint8_t* in, size_t n, uint8_t* out);                  // out[i] = in[n - 1 - i]
+// the half tables of tensor(challenges): lo over the first klo of the k challenges at d_ch (Montgomery, 32 B each), hi over the rest
+int fr_tensor_tables_raw(Context* C, const uint8_t* d_ch, uint32_t k, uint32_t klo, uint8_t* lo, uint8_t* hi);
+int hsp_scalars_raw(Context* C, const HspArgs& A);  // k_hsp_scalars: the scalars of a message of the module space prover
 // out[i] = sum_j c_j v_j[i], v_j = base + j * pitch_bytes, k vectors of n elements; launches only, the caller waits
 int fr_lincomb_raw(Context* C, const uint8_t* base, size_t pitch_bytes, size_t n, const uint64_t* coeffs_mont, size_t k, uint8_t* out);
 
@@ -672,6 +722,16 @@ int herring_fold(Context* C, HerringProver* H, const uint64_t r[4]);
 int herring_round(Context* C, HerringProver* H, const uint64_t* challenge, uint64_t* a, uint64_t* b, int* has_msg);
 int herring_final(Context* C, HerringProver* H, uint64_t* f0, uint64_t* g0, int* has);
 int herring_gt_check(Context* C, HerringProver* H, size_t* first_bad, int* ok);  // GtModule: k_gt_check over the current f
+// the space prover of G1Module / G2Module (herring.hip).  `key` is a Bases (HERRING_G1) or a G2Bases (HERRING_G2) that outlives the
+// prover, or nullptr with host records `host_points` of `stride` bytes, which become a key of the prover's own; the scalar stream
+// is a device vector (on_device) or a host array, Montgomery, big-endian like the points
+int hsp_create(Context* C, HerringModule module, const void* key, size_t offset, const void* host_points, size_t stride, size_t np,
+               const void* scalars, size_t ns, bool on_device, const uint64_t twist[4], uint64_t* handle);
+void hsp_destroy(Context* C, HerringSpace* H);
+int hsp_fold(Context* C, HerringSpace* H, const uint64_t r[4]);
+int hsp_round(Context* C, HerringSpace* H, const uint64_t* challenge, uint64_t* a, uint64_t* b, int* has_msg);
+int hsp_final(Context* C, HerringSpace* H, uint64_t* point0, uint64_t* scalar0, int* has);
+int hsp_to_time(Context* C, HerringSpace* H, uint64_t* time_handle);
 
 // herring's inner-product argument (ipa.hip)
 int crs_create(Context* C, const void* g1, size_t stride1, size_t n1, const void* g2, size_t stride2, size_t n2, uint64_t* handle);

@@ -934,6 +934,50 @@ __global__ __launch_bounds__(256) void k_sp_materialize(const uint8_t* __restric
 }
 
 // ------------------------------------------------------------------------------------------
+// herring's space prover over G1Module / G2Module (src/herring/space_prover.rs:118-250; herring.hip: hsp_round).  p(point, scalar) =
+// scalar * point is linear, so with F[m] = sum_u w_u P_le[m 2^k + u] the sums of a message
+//   a = sum_j tau^(2j) p(F[2j], S[2j]),   b = sum_j tau^(2j) (p(F[2j], S[2j+1]) + tau p(F[2j+1], S[2j]))      (points on the left)
+// are MSMs over the ORIGINAL points: the point of block m, place u carries w_u S[m] tau^m in a (even m only) and w_u S[m ^ 1] tau^m
+// in b.  With the points on the right (G2Module) the twist factor of b moves to the even block: tau^(m ^ 1).  One lane per point
+// writes both scalars, canonical, at the point's own place in the key, so the MSMs read the key where it lies.  S is the folded
+// scalar vector (looked up, not recomputed), w the tensor of the point side's challenges from its two half tables.
+// ------------------------------------------------------------------------------------------
+struct HspKernelArgs {
+  HspArgs a;
+  PowTable tau2;  // powers of twist^2
+};
+__global__ __launch_bounds__(256) void k_hsp_scalars(HspKernelArgs K) {
+  const HspArgs& A = K.a;
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= A.lanes) return;
+  const size_t i = A.np - 1 - t;  // the stream is big-endian
+  const size_t m = i >> A.k, u = i & (((size_t)1 << A.k) - 1), j = m >> 1;
+  Fr w = Fr::one();
+  if (A.k > 0) {
+    w = fp_load<FrParams>(A.lo + (u & (((size_t)1 << A.klo) - 1)) * FR_BYTES);
+    if (A.k > A.klo) w = fr_mul(w, fp_load<FrParams>(A.hi + (u >> A.klo) * FR_BYTES));
+  }
+  if (A.final_only) {
+    fp_store<FrParams>(A.out_a + t * FR_BYTES, fp_from_mont<FrParams>(w));
+    return;
+  }
+  Fr sa = Fr::zero(), sb = Fr::zero();
+  if (j < A.npairs) {
+    Fr tw = fr_mul(w, pow_from_table(K.tau2, j));  // w tau^(2j)
+    if ((m & 1) == 0) sa = fr_mul(tw, fr_load_or_zero(A.S, m, A.ls));
+    if (((m & 1) != 0) != (A.rhs_points != 0)) {
+      Fr tau;
+#pragma unroll
+      for (int q = 0; q < 8; q++) tau.l[q] = reinterpret_cast<const uint32_t*>(A.twist)[q];
+      tw = fr_mul(tw, tau);
+    }
+    sb = fr_mul(tw, fr_load_or_zero(A.S, m ^ 1, A.ls));
+  }
+  fp_store<FrParams>(A.out_a + t * FR_BYTES, fp_from_mont<FrParams>(sa));
+  fp_store<FrParams>(A.out_b + t * FR_BYTES, fp_from_mont<FrParams>(sb));
+}
+
+// ------------------------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------------------------
 static void make_pow_table(const gmh::Fr& x, PowTable& t) {
@@ -1719,6 +1763,31 @@ int fr_fold_raw(Context* C, const uint8_t* f, size_t n, const uint64_t r[4], uin
   if (m) hipLaunchKernelGGL(k_fold, dim3(grid_for(m)), dim3(256), 0, C->stream, f, n, (const uint32_t*)dr, out);
   GM_HIP(hipGetLastError());
   return GM_OK;  // no wait: `r` is the caller's until the copy has run (herring.hip: fold_locked waits once for both sides)
+}
+
+int fr_reverse_raw(Context* C, const uint8_t* in, size_t n, uint8_t* out) {
+  GM_FR_LOCK(C);
+  if (n) hipLaunchKernelGGL(k_reverse, dim3(grid_for(n)), dim3(256), 0, C->stream, in, n, out);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+int fr_tensor_tables_raw(Context* C, const uint8_t* d_ch, uint32_t k, uint32_t klo, uint8_t* lo, uint8_t* hi) {
+  GM_FR_LOCK(C);
+  hipLaunchKernelGGL(k_tensor_table, dim3(grid_for((size_t)1 << klo)), dim3(256), 0, C->stream, (const uint32_t*)d_ch, klo, lo);
+  if (k > klo)
+    hipLaunchKernelGGL(k_tensor_table, dim3(grid_for((size_t)1 << (k - klo))), dim3(256), 0, C->stream, (const uint32_t*)(d_ch + (size_t)klo * 32), k - klo, hi);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+int hsp_scalars_raw(Context* C, const HspArgs& A) {
+  GM_FR_LOCK(C);
+  if (A.lanes == 0) return GM_OK;
+  HspKernelArgs K;
+  K.a = A;
+  make_pow_table(gmh::Fr::from_limbs(A.twist).sqr(), K.tau2);
+  hipLaunchKernelGGL(k_hsp_scalars, dim3((unsigned)((A.lanes + 255) / 256)), dim3(256), 0, C->stream, K);
+  GM_HIP(hipGetLastError());
+  return GM_OK;
 }
 
 // ---- vector helper entry points (called from capi.hip) ---------------------------------------

@@ -16,6 +16,7 @@
 #include <cstring>
 
 #include "ctx.hpp"
+#include "herring_space_plan.hpp"
 #include "host_field.hpp"
 
 namespace gm {
@@ -323,6 +324,291 @@ int herring_final(Context* C, HerringProver* H, uint64_t* f0, uint64_t* g0, int*
   M.lhs->read0(ef, f0);
   M.rhs->read0(eg, g0);
   *has = 1;
+  return GM_OK;
+}
+
+// ---- the space prover of G1Module and G2Module ---------------------------------------------------------------------------
+// src/herring/space_prover.rs:39-316 for the two modules whose p(point, scalar) = scalar * point is linear in the point.  The
+// prover owns no point: the key is read where it lies as the big-endian stream key[offset + i].  After k folds the folded vectors
+// are F[m] = sum_u w_u x_le[m 2^k + u] (streams.rs:209-249; x_le[i] = stream[n - 1 - i], zero past the end as init_stack pads), so
+// every sum of a message is an MSM over the original points whose scalars one launch of k_hsp_scalars (fr.hip) expands.
+//   fold(r)          the challenge is stored, r twist on the Lhs and r on the Rhs, the twist is squared (:255-259); the scalar side,
+//                    32 bytes an element, is kept folded: S <- fold(S, its challenge)
+//   next_message(c)  an optional fold; pair j is (block 2j, block 2j + 1) of both sides, as many pairs as the shorter side has, and
+//                    a = sum_j twist^(2j) p(F[2j], G[2j]), b = sum_j twist^(2j) (p(F[2j], G[2j+1]) + twist p(F[2j+1], G[2j])):
+//                    what :150-207 computes with twist_runner = twist^(2 pairs) stepping down by twist^-2 -- on the first pair it
+//                    multiplies p, in the loop the Rhs, which is the same value
+//   final_foldings   the FIRST item of each folded stream (:270-276): the block of the highest index, not element 0.  The two are
+//                    one when the streams have equal lengths
+//   to_time          TimeProver::from(&SpaceProver) (:279-316): the point side folded k times out of place by split_fold
+// The reference's alignment (:152-164) adds the parity of the shorter length to the skip where it has to be subtracted: when the
+// folded lengths differ and the shorter one is odd its assertion f_pairs == g_pairs fails.  Everywhere else its pairs are the
+// ones above, which are also the TimeProver's (the zip of the even and odd halves).
+struct HspModuleDesc {
+  const char* name;
+  HerringModule module;
+  const HerringSide* point;  // G1_SIDE / G2_SIDE
+  bool rhs_points;           // G2Module: the points are the Rhs (folded by r, and the twist factor of b sits on the even block)
+  int (*split_fold_rev)(Context* C, const uint8_t* in, size_t n, const uint32_t* d_s8, uint8_t* out);
+};
+static const HspModuleDesc HSP_G1 = {"G1", HERRING_G1, &G1_SIDE, false, g1_split_fold_rev_launch};
+static const HspModuleDesc HSP_G2 = {"G2", HERRING_G2, &G2_SIDE, true, g2_split_fold_rev_launch};
+static const HspModuleDesc& hsp_desc(const HerringSpace* H) { return H->module == HERRING_G1 ? HSP_G1 : HSP_G2; }
+static const uint8_t* hsp_key(const HerringSpace* H) {  // the first point of the stream
+  return H->module == HERRING_G1 ? H->g1->d + H->offset * 96 : H->g2->d + H->offset * 192;
+}
+
+void hsp_destroy(Context* C, HerringSpace* H) {
+  for (int i = 0; i < 2; i++) {
+    C->pool.free(H->s[i], H->scap[i]);
+    H->s[i] = nullptr;
+  }
+  C->pool.free(H->work, H->work_cap);
+  H->work = nullptr;
+  if (H->own_g1 && H->own_g1->d) (void)gm::raw_free(H->own_g1->d);
+  if (H->own_g2 && H->own_g2->d) (void)gm::raw_free(H->own_g2->d);
+  H->own_g1.reset();
+  H->own_g2.reset();
+}
+
+// the work block holds the tables of `k` challenges (it is made for tot_rounds; folds past the last round make it grow)
+static int hsp_ensure_work(Context* C, HerringSpace* H, uint32_t k) {
+  const size_t need = hsp_work_bytes(H->np, k);
+  if (H->work_cap >= need) return GM_OK;
+  C->pool.free(H->work, H->work_cap);
+  H->work = nullptr;
+  H->work_cap = 0;
+  int rc = C->pool.alloc(need, (void**)&H->work, &H->work_cap);
+  if (!rc) H->path[3] += need;
+  return rc;
+}
+
+int hsp_create(Context* C, HerringModule module, const void* key, size_t offset, const void* host_points, size_t stride, size_t np,
+               const void* scalars, size_t ns, bool on_device, const uint64_t twist[4], uint64_t* handle) {
+  const HspModuleDesc& M = module == HERRING_G1 ? HSP_G1 : HSP_G2;
+  GM_CHECK(np >= 1 && ns >= 1, GM_EINVAL, "herring %s space prover: empty streams", M.name);
+  auto H = std::make_unique<HerringSpace>();
+  H->module = module;
+  H->np = np;
+  H->ns = H->ls = ns;
+  H->offset = offset;
+  int rc;
+  if (key) {
+    const size_t have = module == HERRING_G1 ? static_cast<const Bases*>(key)->n : static_cast<const G2Bases*>(key)->n;
+    GM_CHECK(offset <= have && np <= have - offset, GM_EINVAL, "herring %s space prover: points [%zu, %zu) outside a key of %zu", M.name, offset,
+             offset + np, have);
+    if (module == HERRING_G1) H->g1 = static_cast<const Bases*>(key);
+    else H->g2 = static_cast<const G2Bases*>(key);
+  } else {  // host records: a key of the prover's own
+    H->offset = 0;
+    if (module == HERRING_G1) {
+      if ((rc = bases_from_host(C, host_points, stride, np, H->own_g1))) return rc;
+      H->g1 = H->own_g1.get();
+    } else {
+      if ((rc = g2_bases_from_host(C, host_points, stride, np, H->own_g2))) return rc;
+      H->g2 = H->own_g2.get();
+    }
+    H->path[2] += np * M.point->elem;
+  }
+  memcpy(H->twist, twist, 32);
+  H->tot_rounds = hsp_ceil_log2(std::min(np, ns));  // WitnessStream::required_rounds (:77-80)
+  std::vector<uint64_t> rev;
+  if ((rc = C->pool.alloc(ns * 32, (void**)&H->s[0], &H->scap[0])) || (rc = C->pool.alloc(((ns + 1) / 2) * 32, (void**)&H->s[1], &H->scap[1])) ||
+      (rc = hsp_ensure_work(C, H.get(), (uint32_t)H->tot_rounds))) {
+    hsp_destroy(C, H.get());
+    return rc;
+  }
+  H->path[3] += ns * 32 + ((ns + 1) / 2) * 32;
+  // S = the scalar stream as the little-endian vector it stands for
+  if (on_device) {
+    rc = fr_reverse_raw(C, static_cast<const uint8_t*>(scalars), ns, H->s[0]);
+  } else {
+    rev.resize(ns * 4);
+    for (size_t i = 0; i < ns; i++) memcpy(&rev[4 * i], static_cast<const uint64_t*>(scalars) + 4 * (ns - 1 - i), 32);
+    rc = hipMemcpyAsync(H->s[0], rev.data(), ns * 32, hipMemcpyHostToDevice, C->stream) == hipSuccess ? GM_OK : GM_EHIP;
+  }
+  if (!rc && hipStreamSynchronize(C->stream) != hipSuccess) rc = GM_EHIP;
+  if (rc) {
+    hsp_destroy(C, H.get());
+    if (rc == GM_EHIP) set_error("herring %s space prover: the copy of the scalar stream failed", M.name);
+    return rc;
+  }
+  std::lock_guard<std::mutex> lk(C->mu);
+  *handle = C->next_handle++;
+  C->herring_space[*handle] = std::move(H);
+  return GM_OK;
+}
+
+// Prover::fold (:255-259)
+static int hsp_push(Context* C, HerringSpace* H, const uint64_t r[4]) {
+  const HspModuleDesc& M = hsp_desc(H);
+  const gmh::Fr rr = gmh::Fr::from_limbs(r), tw = gmh::Fr::from_limbs(H->twist), rt = rr * tw;
+  const gmh::Fr& pc = M.rhs_points ? rr : rt;  // the point side's challenge: the Lhs folds by r twist, the Rhs by r
+  const gmh::Fr& sc = M.rhs_points ? rt : rr;
+  uint64_t limbs[4], s_mont[4];
+  sc.to_limbs(s_mont);
+  int rc = fr_fold_raw(C, H->s[H->cur], H->ls, s_mont, H->s[H->cur ^ 1]);
+  if (rc) return rc;
+  GM_HIP(hipStreamSynchronize(C->stream));  // s_mont is read by a copy until here
+  H->cur ^= 1;
+  H->ls = (H->ls + 1) / 2;
+  pc.to_limbs(limbs);
+  H->pt_ch.insert(H->pt_ch.end(), limbs, limbs + 4);
+  pc.to_canonical(limbs);
+  H->pt_ch_canon.insert(H->pt_ch_canon.end(), limbs, limbs + 4);
+  tw.sqr().to_limbs(H->twist);
+  return GM_OK;
+}
+
+int hsp_fold(Context* C, HerringSpace* H, const uint64_t r[4]) {
+  std::lock_guard<std::mutex> lk(H->mu);
+  return hsp_push(C, H, r);
+}
+
+// the tensor tables of the point side's challenges and one launch of k_hsp_scalars, on C->stream without a wait
+static int hsp_expand(Context* C, HerringSpace* H, const HspPlan& P, bool final_only, const HspWork& W) {
+  int rc;
+  if (P.k) {
+    GM_HIP(hipMemcpyAsync(H->work + W.ch, H->pt_ch.data(), (size_t)P.k * 32, hipMemcpyHostToDevice, C->stream));
+    if ((rc = fr_tensor_tables_raw(C, H->work + W.ch, P.k, P.klo, H->work + W.lo, H->work + W.hi))) return rc;
+  }
+  HspArgs A;
+  A.S = H->s[H->cur];
+  A.ls = H->ls;
+  A.lo = H->work + W.lo;
+  A.hi = H->work + W.hi;
+  A.k = P.k;
+  A.klo = P.klo;
+  A.np = H->np;
+  A.lanes = final_only ? P.top_points : H->np;
+  A.npairs = P.npairs;
+  memcpy(A.twist, H->twist, 32);
+  A.rhs_points = hsp_desc(H).rhs_points ? 1 : 0;
+  A.final_only = final_only ? 1 : 0;
+  A.out_a = H->work + W.a;
+  A.out_b = H->work + W.b;
+  if ((rc = hsp_scalars_raw(C, A))) return rc;
+  H->path[1] += 1;
+  return GM_OK;
+}
+
+// k MSMs of n points each from the start of the stream, scalars at sc[j] (canonical), results normalised Jacobian, `limbs` apart
+static int hsp_msm(Context* C, HerringSpace* H, const void* const* sc, size_t n, size_t k, uint64_t* out, size_t limbs) {
+  int rc;
+  H->path[0] += k;
+  if (H->module == HERRING_G1) {  // G1 calls of one message go as one batch
+    const size_t ns[2] = {n, n};
+    return msm_run_batch(C, H->g1, (int64_t)H->offset, 1, sc, 0, ns, k, true, out);
+  }
+  for (size_t j = 0; j < k; j++)
+    if ((rc = g2_msm_run(C, H->g2, (int64_t)H->offset, 1, sc[j], 0, n, out + j * limbs))) return rc;
+  return GM_OK;
+}
+
+// SpaceProver::next_message (:118-250)
+int hsp_round(Context* C, HerringSpace* H, const uint64_t* challenge, uint64_t* a, uint64_t* b, int* has_msg) {
+  const HspModuleDesc& M = hsp_desc(H);
+  std::lock_guard<std::mutex> lk(H->mu);
+  GM_CHECK(H->round <= H->tot_rounds, GM_ESTATE, "More rounds than needed.");
+  int rc;
+  if (challenge && (rc = hsp_push(C, H, challenge))) return rc;
+  if (H->round == H->tot_rounds) {
+    *has_msg = 0;
+    return GM_OK;
+  }
+  const size_t k = H->pt_ch.size() / 4;
+  GM_CHECK(k == H->round, GM_ESTATE, "herring %s space prover: %zu challenges at round %zu (at the i-th round, randomness.len() = i)", M.name, k, H->round);
+  GM_MSM_LOCK(C);
+  const HspPlan P = hsp_plan(H->np, H->ns, (uint32_t)k);
+  const HspWork W = hsp_work_layout(H->np, (uint32_t)H->tot_rounds);
+  if ((rc = hsp_expand(C, H, P, false, W))) return rc;
+  const size_t limbs = M.point->elem / 96 * 18;  // 18 for G1, 36 for G2
+  uint64_t res[2 * 36];
+  const void* sc[2] = {H->work + W.a, H->work + W.b};
+  if ((rc = hsp_msm(C, H, sc, H->np, 2, res, limbs))) return rc;
+  memcpy(a, res, limbs * 8);
+  memcpy(b, res + limbs, limbs * 8);
+  H->round += 1;
+  *has_msg = 1;
+  return GM_OK;
+}
+
+// final_foldings (:270-276): the first item of each folded stream
+int hsp_final(Context* C, HerringSpace* H, uint64_t* point0, uint64_t* scalar0, int* has) {
+  const HspModuleDesc& M = hsp_desc(H);
+  std::lock_guard<std::mutex> lk(H->mu);
+  if (H->round != H->tot_rounds) {
+    *has = 0;
+    return GM_OK;
+  }
+  GM_MSM_LOCK(C);
+  const uint32_t k = (uint32_t)(H->pt_ch.size() / 4);
+  int rc = hsp_ensure_work(C, H, std::max<uint32_t>(k, (uint32_t)H->tot_rounds));
+  if (rc) return rc;
+  const HspPlan P = hsp_plan(H->np, H->ns, k);
+  const HspWork W = hsp_work_layout(H->np, std::max<uint32_t>(k, (uint32_t)H->tot_rounds));
+  if ((rc = hsp_expand(C, H, P, true, W))) return rc;
+  const void* sc[1] = {H->work + W.a};
+  if ((rc = hsp_msm(C, H, sc, P.top_points, 1, point0, M.point->elem / 96 * 18))) return rc;
+  GM_HIP(hipMemcpyAsync(scalar0, H->s[H->cur] + (H->ls - 1) * 32, 32, hipMemcpyDeviceToHost, C->stream));
+  GM_HIP(hipStreamSynchronize(C->stream));
+  *has = 1;
+  return GM_OK;
+}
+
+// TimeProver::from(&SpaceProver) (:279-316): a herring_* prover of the same module at the same round, twist and tot_rounds, whose
+// vectors are the folded streams in allocations of its own
+int hsp_to_time(Context* C, HerringSpace* H, uint64_t* time_handle) {
+  const HspModuleDesc& M = hsp_desc(H);
+  const HerringModuleDesc& T = MODULES[H->module];
+  std::lock_guard<std::mutex> lk(H->mu);
+  const uint32_t k = (uint32_t)(H->pt_ch.size() / 4);
+  const HspPlan P = hsp_plan(H->np, H->ns, k);
+  const HspTimeBuffers B = hsp_time_buffers(H->np, k);
+  auto TP = std::make_unique<HerringProver>();
+  TP->module = H->module;
+  uint8_t** pt = M.rhs_points ? TP->g : TP->f;  // the point side and the scalar side of the time prover
+  size_t* ptcap = M.rhs_points ? TP->gcap : TP->fcap;
+  uint8_t** sv = M.rhs_points ? TP->f : TP->g;
+  size_t* svcap = M.rhs_points ? TP->fcap : TP->gcap;
+  const int cur = B.result_in;
+  int rc;
+  if ((rc = M.point->alloc(C, B.first, &pt[0], &ptcap[0])) || (rc = M.point->alloc(C, B.second, &pt[1], &ptcap[1])) ||
+      (rc = FR_SIDE.alloc(C, P.ls, &sv[cur], &svcap[cur])) || (rc = FR_SIDE.alloc(C, (P.ls + 1) / 2, &sv[cur ^ 1], &svcap[cur ^ 1])) ||
+      (rc = C->pool.alloc(T.tmp_slots * (((P.ls + 1) / 2 + 1) * 32), (void**)&TP->tmp, &TP->tmpcap))) {
+    herring_destroy(C, TP.get());
+    return rc;
+  }
+  H->path[2] += (B.first + B.second) * M.point->elem;
+  H->path[3] += (P.ls + (P.ls + 1) / 2) * 32;
+  {
+    GM_MSM_LOCK(C);  // the canonical challenges are staged in the MSM workspace (C->msm.misc), as fold_locked stages its two
+    rc = C->msm.misc.ensure((size_t)k * 32 + 32);
+    if (!rc && k) rc = hipMemcpyAsync(C->msm.misc.p, H->pt_ch_canon.data(), (size_t)k * 32, hipMemcpyHostToDevice, C->stream) == hipSuccess ? GM_OK : GM_EHIP;
+    if (!rc && k == 0) rc = records_reverse_launch(C, hsp_key(H), H->np, M.point->elem, pt[0]);
+    size_t n = H->np;
+    for (uint32_t l = 0; l < k && !rc; l++) {  // level l reads the key (backwards: it is a big-endian stream), then the last level's output
+      const uint32_t* s8 = C->msm.misc.as<uint32_t>() + 8 * (size_t)l;
+      rc = l == 0 ? M.split_fold_rev(C, hsp_key(H), n, s8, pt[0]) : M.point->split_fold(C, pt[(l - 1) & 1], n, nullptr, s8, pt[l & 1]);
+      n = (n + 1) / 2;
+    }
+    if (!rc) rc = hipMemcpyAsync(sv[cur], H->s[H->cur], P.ls * 32, hipMemcpyDeviceToDevice, C->stream) == hipSuccess ? GM_OK : GM_EHIP;
+    if (hipStreamSynchronize(C->stream) != hipSuccess && !rc) rc = GM_EHIP;
+  }
+  if (rc) {
+    herring_destroy(C, TP.get());
+    if (rc == GM_EHIP) set_error("herring %s space prover: to_time failed on the device", M.name);
+    return rc;
+  }
+  TP->cur = cur;
+  (M.rhs_points ? TP->ng : TP->nf) = P.lp;
+  (M.rhs_points ? TP->nf : TP->ng) = P.ls;
+  memcpy(TP->twist, H->twist, 32);
+  TP->round = H->round;
+  TP->tot_rounds = H->tot_rounds;
+  std::lock_guard<std::mutex> lkc(C->mu);
+  *time_handle = C->next_handle++;
+  C->herring[*time_handle] = std::move(TP);
   return GM_OK;
 }
 

@@ -1,7 +1,8 @@
 """Host mirror of herring's sumcheck over a bilinear module (src/herring): the TimeProver of
 src/herring/time_prover.rs:42-137 for the five module instances of src/herring/module.rs:
 FModule (F x F -> F), G1Module (G1 x F -> G1), G2Module (F x G2 -> G2), PModule (G1 x G2 -> GT; pairings are
-gemini_amd/pairing.py) and GtModule (GT x F -> GT; the device multi-exponentiation is pairing.gt_multi_pow).  The inner-product
+gemini_amd/pairing.py) and GtModule (GT x F -> GT; the device multi-exponentiation is pairing.gt_multi_pow), and the SpaceProver of
+src/herring/space_prover.rs:39-316 for G1Module and G2Module over a registered key (G1ModuleSpaceProver, G2ModuleSpaceProver).  The inner-product
 argument built on them is gemini_amd/ipa.py (its PModule provers are batched inside the library, not instances of the classes here, and
 its GT multi-exponentiations stay on the host); InnerProductProof::generic and CrsStream are out of scope."""
 from __future__ import annotations
@@ -136,3 +137,88 @@ class GtModuleTimeProver(_ModuleTimeProver):
         from .points import check_proof
 
         return check_proof(capi.load().gm_hgt_check, C.c_uint64(self.handle))
+
+
+class _ModuleSpaceProver(_ModuleTimeProver):
+    """what the two module space provers share: the TimeProver's calls under the gm_hsp*_ names, to_time and path.  The key and the
+    Fr vector a prover was made from stay alive and unmodified until free()"""
+
+    _time_class = None
+
+    def to_time(self):
+        """TimeProver::from(&SpaceProver): a time prover of the same module at the same round, twist and number of rounds, its point
+        vector the folded points in an allocation of its own; this prover stays valid"""
+        h = C.c_uint64()
+        self._call("to_time", C.byref(h))
+        t = self._time_class.__new__(self._time_class)
+        t.handle = h.value
+        return t
+
+    def path(self):
+        """gm_debug_hsp_path: (MSM calls, launches of k_hsp_scalars, point bytes allocated, scalar bytes allocated) so far"""
+        out = (C.c_size_t * 4)()
+        capi.check(capi.load().gm_debug_hsp_path(C.c_uint64(self.handle), out))
+        return tuple(out)
+
+
+class G1ModuleSpaceProver(_ModuleSpaceProver):
+    """SpaceProver<G1Module>: the Lhs is the big-endian stream bases[offset + i], i < n, of a msm.G1Bases key, read where it lies;
+    the Rhs an fr.FrVec holding the big-endian Fr stream.  Messages and the final f are (18,) normalised Jacobian.  The messages
+    carry the twist (space_prover.rs:188-207), a TimeProver's do not: the two agree at twist = 1"""
+
+    _prefix, _msg, _final_f, _final_g = "hsp1", 18, 18, 4
+    _time_class = G1ModuleTimeProver
+
+    def __init__(self, bases, g_stream, twist_mont, offset: int = 0, n: int | None = None):
+        capi.ensure_init()
+        n = bases.n - offset if n is None else n
+        h = C.c_uint64()
+        capi.check(capi.load().gm_hsp1_new_borrow(C.c_uint64(bases.handle), C.c_size_t(offset), C.c_size_t(n), C.c_uint64(g_stream.handle),
+                                                  capi.ptr(capi.u64(twist_mont).reshape(4)), C.byref(h)))
+        self.handle = h.value
+        self._keep = (bases, g_stream)
+
+    @classmethod
+    def from_host(cls, f_points, g_stream, twist_mont):
+        """gm_hsp1_new: host records ((n, 12) or (n, 13)) and a host stream; the prover registers a key of its own"""
+        capi.ensure_init()
+        fp = capi.u64(f_points)
+        gm_ = capi.u64(g_stream).reshape(-1, 4)
+        h = C.c_uint64()
+        capi.check(capi.load().gm_hsp1_new(capi.ptr(fp), C.c_size_t(fp.shape[1] * 8), C.c_size_t(len(fp)), capi.ptr(gm_), C.c_size_t(len(gm_)),
+                                           capi.ptr(capi.u64(twist_mont).reshape(4)), C.byref(h)))
+        self = cls.__new__(cls)
+        self.handle = h.value
+        self._keep = ()
+        return self
+
+
+class G2ModuleSpaceProver(_ModuleSpaceProver):
+    """SpaceProver<G2Module>: the Lhs is an fr.FrVec holding the big-endian Fr stream, the Rhs the stream bases[offset + i], i < n, of
+    a g2msm.G2Bases key.  Messages and the final g are (36,) normalised Jacobian"""
+
+    _prefix, _msg, _final_f, _final_g = "hsp2", 36, 4, 36
+    _time_class = G2ModuleTimeProver
+
+    def __init__(self, f_stream, bases, twist_mont, offset: int = 0, n: int | None = None):
+        capi.ensure_init()
+        n = bases.n - offset if n is None else n
+        h = C.c_uint64()
+        capi.check(capi.load().gm_hsp2_new_borrow(C.c_uint64(f_stream.handle), C.c_uint64(bases.handle), C.c_size_t(offset), C.c_size_t(n),
+                                                  capi.ptr(capi.u64(twist_mont).reshape(4)), C.byref(h)))
+        self.handle = h.value
+        self._keep = (f_stream, bases)
+
+    @classmethod
+    def from_host(cls, f_stream, g_points, twist_mont):
+        """gm_hsp2_new: a host stream and host records ((n, 24) or (n, 25))"""
+        capi.ensure_init()
+        fm = capi.u64(f_stream).reshape(-1, 4)
+        gp = capi.u64(g_points)
+        h = C.c_uint64()
+        capi.check(capi.load().gm_hsp2_new(capi.ptr(fm), C.c_size_t(len(fm)), capi.ptr(gp), C.c_size_t(gp.shape[1] * 8), C.c_size_t(len(gp)),
+                                           capi.ptr(capi.u64(twist_mont).reshape(4)), C.byref(h)))
+        self = cls.__new__(cls)
+        self.handle = h.value
+        self._keep = ()
+        return self

@@ -611,6 +611,62 @@ int gm_hgt_rounds(uint64_t handle, size_t* tot_rounds, size_t* round);
 int gm_hgt_final(uint64_t handle, uint64_t f0_gt[72], uint64_t g0_mont[4], int* has);
 int gm_hgt_free(uint64_t handle);
 
+/* ---- herring: space prover over G1Module / G2Module (gemini_amd/csrc/herring.hip) ------------------------------------------
+ * The streaming SpaceProver of src/herring/space_prover.rs:39-316 for the two modules whose p(point, scalar) = scalar * point
+ * is linear in the point.  The point side is a run of a REGISTERED key, read where it lies and never written or copied: the
+ * nf points bases[offset .. offset + nf) are the big-endian stream the reference consumes, stream item i = bases[offset + i],
+ * so f_le[i] = bases[offset + nf - 1 - i].  After k folds the folded vectors are F[m] = sum_{u < 2^k} w_u f_le[m 2^k + u]
+ * with w the tensor of the side's challenges (twisted on the Lhs; past the end of the stream f_le is zero, streams.rs:79-95),
+ * and every sum of a message is ONE multi-scalar multiplication over the original points: a kernel (k_hsp_scalars) expands
+ * the scalars, the MSMs are the engine's (with the fixed-base tables of a G1 key that has them).  Two MSM calls a message,
+ * one more for final_foldings; no folded point vector exists until gm_hsp*_to_time.  The scalar side, 32 bytes an element,
+ * is copied once (as the little-endian vector) and kept folded.
+ *   gm_hsp1_new_borrow  G1Module: Lhs = points of a gm_g1_bases_* handle, Rhs = a gm_fr_vec_* vector holding the big-endian
+ *                       stream.  Key and vector stay alive and unmodified until gm_hsp1_free
+ *   gm_hsp1_new         the same from host records (as gm_hg1_new takes them) and a host stream: a key of the prover's own
+ *   gm_hsp1_round       next_message: an optional fold, then (a, b); has_msg = 0 after log2(min(nf, ng)) messages (ark-std's
+ *                       ceiling log, as gm_sp_new).  Pair j is (F[2j], F[2j+1]) against (G[2j], G[2j+1]), as many pairs as the
+ *                       shorter folded side has, a missing odd element is zero:
+ *                         a = sum_j t^(2j) p(F[2j], G[2j]),  b = sum_j t^(2j) (p(F[2j], G[2j+1]) + t p(F[2j+1], G[2j])),
+ *                       t the current twist -- space_prover.rs:188-207 (twist_runner = t^(2 pairs) stepping by t^-2; on the
+ *                       first pair it multiplies p, in the loop the Rhs: the same value).  The reference's own alignment
+ *                       (:152-164) fails its assertion f_pairs == g_pairs when the folded lengths differ and the shorter one
+ *                       is odd; everywhere else its pairs are these.  GM_ESTATE when folds and rounds are out of step.
+ *   gm_hsp1_fold        Prover::fold: stores r (Rhs) and r t (Lhs), t <- t^2
+ *   gm_hsp1_final       final_foldings: the FIRST item of each folded stream (:270-276), i.e. the block of the HIGHEST index
+ *                       -- element 0 only when that side has folded down to one element, as both have for equal lengths
+ *   gm_hsp1_to_time     TimeProver::from(&SpaceProver) (:279-316): an ordinary gm_hg1_* prover at the same round, twist and
+ *                       tot_rounds; its f is the folded points in an allocation of its own (k out-of-place split-folds, the
+ *                       first one reading the key), its g the folded scalars.  The space prover stays valid
+ *   gm_hsp2_*           G2Module: Lhs = the Fr stream, Rhs = points of a gm_g2_bases_* handle; points are jac[36]
+ * Outputs are normalised Jacobian, as gm_hg1_* / gm_hg2_* give them.  herring's TimeProver uses the twist when it folds only
+ * (time_prover.rs:83-123), the SpaceProver also in its messages: the two agree at twist = 1 and nowhere else, in the reference
+ * and here; a prover from to_time goes on as a TimeProver.  Null pointers or a bad stride: GM_EINVAL; nf = 0 or ng = 0:
+ * GM_EINVAL; an unknown handle: GM_EHANDLE; rounds past the end and further folds as gm_hg1_round / gm_hg1_fold take them.
+ * Not covered: PModule and GtModule (their p is no scalar multiple, so a message is no MSM), FModule under this twist
+ * placement, the space prover inside gm_ipa_new, CrsStream. */
+int gm_hsp1_new_borrow(uint64_t g1_bases_handle, size_t offset, size_t nf, uint64_t g_stream_vec, const uint64_t twist_mont[4], uint64_t* handle);
+int gm_hsp1_new(const void* f_bases, size_t base_stride, size_t nf, const uint64_t* g_stream_mont, size_t ng, const uint64_t twist_mont[4],
+                uint64_t* handle);
+int gm_hsp1_round(uint64_t handle, const uint64_t* challenge_or_null, uint64_t a_jac[18], uint64_t b_jac[18], int* has_msg);
+int gm_hsp1_fold(uint64_t handle, const uint64_t challenge_mont[4]);
+int gm_hsp1_rounds(uint64_t handle, size_t* tot_rounds, size_t* round);
+int gm_hsp1_final(uint64_t handle, uint64_t f0_jac[18], uint64_t g0_mont[4], int* has);
+int gm_hsp1_to_time(uint64_t handle, uint64_t* hg1_handle);
+int gm_hsp1_free(uint64_t handle);
+int gm_hsp2_new_borrow(uint64_t f_stream_vec, uint64_t g2_bases_handle, size_t offset, size_t ng, const uint64_t twist_mont[4], uint64_t* handle);
+int gm_hsp2_new(const uint64_t* f_stream_mont, size_t nf, const void* g_bases, size_t base_stride, size_t ng, const uint64_t twist_mont[4],
+                uint64_t* handle);
+int gm_hsp2_round(uint64_t handle, const uint64_t* challenge_or_null, uint64_t a_jac[36], uint64_t b_jac[36], int* has_msg);
+int gm_hsp2_fold(uint64_t handle, const uint64_t challenge_mont[4]);
+int gm_hsp2_rounds(uint64_t handle, size_t* tot_rounds, size_t* round);
+int gm_hsp2_final(uint64_t handle, uint64_t f0_mont[4], uint64_t g0_jac[36], int* has);
+int gm_hsp2_to_time(uint64_t handle, uint64_t* hg2_handle);
+int gm_hsp2_free(uint64_t handle);
+/* of a gm_hsp1_* or gm_hsp2_* prover so far: MSM calls, launches of k_hsp_scalars, point bytes the prover allocated (0 for the
+ * borrow forms until to_time), scalar bytes it allocated */
+int gm_debug_hsp_path(uint64_t handle, size_t out[4]);
+
 /* ---- GT element by element on the device: final exponentiation, pairings, membership (gemini_amd/csrc/pairing.hip) ------
  * Vectors of GT elements: `BilinearModule::p` of PModule is P::pairing(a, b) (src/herring/module.rs:67), and the GtModule prover
  * above consumes 2^10 .. 2^14 of them.  One lane per element, 64 lanes per block; a launch is milliseconds deep whatever n is

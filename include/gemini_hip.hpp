@@ -697,9 +697,33 @@ class HerringModuleProver {
     return ff;
   }
   uint64_t handle() const { return h_; }
+  static HerringModuleProver from_handle(uint64_t handle) {  // a prover the library created (a space prover's to_time); owned from here
+    HerringModuleProver p;
+    p.h_ = handle;
+    return p;
+  }
 
  private:
+  HerringModuleProver() = default;
   uint64_t h_ = 0;
+};
+// TimeProver<G1Module> (module.rs:81-102): f in G1, g in Fr
+struct G1ModuleRoundMsg {
+  G1Projective a, b;
+};
+struct HerringG1Module {
+  using Lhs = std::vector<G1Affine>;
+  using Rhs = std::vector<Fr>;
+  using Msg = G1ModuleRoundMsg;
+  using Final = std::pair<G1Projective, Fr>;
+  static int create(const Lhs& f, const Rhs& g, const Fr& twist, uint64_t* h) {
+    return gm_hg1_new(f.data(), sizeof(G1Affine), f.size(), g.empty() ? nullptr : g[0].data(), g.size(), twist.data(), h);
+  }
+  static constexpr auto round = gm_hg1_round;
+  static constexpr auto fold = gm_hg1_fold;
+  static constexpr auto rounds = gm_hg1_rounds;
+  static constexpr auto final_foldings = gm_hg1_final;
+  static constexpr auto free = gm_hg1_free;
 };
 // TimeProver<G2Module> (module.rs:104-125): f in Fr, g in G2
 struct HerringG2Module {
@@ -717,6 +741,7 @@ struct HerringG2Module {
   static constexpr auto free = gm_hg2_free;
 };
 }  // namespace detail
+using HerringG1 = detail::HerringModuleProver<detail::HerringG1Module>;
 using HerringG2 = detail::HerringModuleProver<detail::HerringG2Module>;
 
 // ---- pairings: `P::multi_pairing` behind PModule::ip (src/herring/module.rs:60-79) and TimeProver<PModule> ----------------------
@@ -1368,6 +1393,89 @@ class DeviceVec {
   DeviceVec() = default;
   uint64_t h_ = 0;
 };
+// ---- herring: SpaceProver over G1Module / G2Module (src/herring/space_prover.rs:39-316; the block of the same name in gemini_hip.h) ----
+// The point side is a run of a registered key, read where it lies; the Fr side a DeviceVec holding the big-endian stream.  Key and
+// vector outlive the prover.  The messages carry the twist, a TimeProver's do not: the two agree at twist = 1
+namespace detail {
+template <class T>
+class HerringModuleSpaceProver {
+ public:
+  // the points key[offset .. offset + n) of a key handle (CommitterKey::handle / G2Bases::handle) and an Fr stream
+  HerringModuleSpaceProver(uint64_t key_handle, size_t offset, size_t n, const DeviceVec& fr_stream, const Fr& twist) {
+    check(T::create(key_handle, offset, n, fr_stream.handle(), twist.data(), &h_));
+  }
+  HerringModuleSpaceProver(HerringModuleSpaceProver&& o) noexcept : h_(o.h_) { o.h_ = 0; }
+  ~HerringModuleSpaceProver() {
+    if (h_) T::free(h_);
+  }
+  HerringModuleSpaceProver(const HerringModuleSpaceProver&) = delete;
+  HerringModuleSpaceProver& operator=(const HerringModuleSpaceProver&) = delete;
+  std::optional<typename T::Time::Msg> next_message(const std::optional<Fr>& verifier_message) {
+    typename T::Time::Msg m;
+    int has = 0;
+    check(T::round(h_, verifier_message ? verifier_message->data() : nullptr, m.a.data(), m.b.data(), &has));
+    if (!has) return std::nullopt;
+    return m;
+  }
+  void fold(const Fr& challenge) { check(T::fold(h_, challenge.data())); }
+  size_t rounds() const {
+    size_t t = 0;
+    check(T::rounds(h_, &t, nullptr));
+    return t;
+  }
+  size_t round() const {
+    size_t r = 0;
+    check(T::rounds(h_, nullptr, &r));
+    return r;
+  }
+  std::optional<typename T::Time::Final> final_foldings() const {
+    typename T::Time::Final ff;
+    int has = 0;
+    check(T::final_foldings(h_, ff.first.data(), ff.second.data(), &has));
+    if (!has) return std::nullopt;
+    return ff;
+  }
+  // TimeProver::from(&SpaceProver): the folded points in an allocation of its own; this prover stays valid
+  HerringModuleProver<typename T::Time> to_time() const {
+    uint64_t t = 0;
+    check(T::to_time(h_, &t));
+    return HerringModuleProver<typename T::Time>::from_handle(t);
+  }
+  // MSM calls, launches of k_hsp_scalars, point bytes allocated, scalar bytes allocated, so far (gm_debug_hsp_path)
+  std::array<size_t, 4> path() const {
+    std::array<size_t, 4> c{};
+    check(gm_debug_hsp_path(h_, c.data()));
+    return c;
+  }
+  uint64_t handle() const { return h_; }
+
+ private:
+  uint64_t h_ = 0;
+};
+struct HerringG1SpaceModule {
+  using Time = HerringG1Module;
+  static int create(uint64_t key, size_t offset, size_t n, uint64_t vec, const uint64_t* twist, uint64_t* h) { return gm_hsp1_new_borrow(key, offset, n, vec, twist, h); }
+  static constexpr auto round = gm_hsp1_round;
+  static constexpr auto fold = gm_hsp1_fold;
+  static constexpr auto rounds = gm_hsp1_rounds;
+  static constexpr auto final_foldings = gm_hsp1_final;
+  static constexpr auto to_time = gm_hsp1_to_time;
+  static constexpr auto free = gm_hsp1_free;
+};
+struct HerringG2SpaceModule {
+  using Time = HerringG2Module;
+  static int create(uint64_t key, size_t offset, size_t n, uint64_t vec, const uint64_t* twist, uint64_t* h) { return gm_hsp2_new_borrow(vec, key, offset, n, twist, h); }
+  static constexpr auto round = gm_hsp2_round;
+  static constexpr auto fold = gm_hsp2_fold;
+  static constexpr auto rounds = gm_hsp2_rounds;
+  static constexpr auto final_foldings = gm_hsp2_final;
+  static constexpr auto to_time = gm_hsp2_to_time;
+  static constexpr auto free = gm_hsp2_free;
+};
+}  // namespace detail
+using HerringG1Space = detail::HerringModuleSpaceProver<detail::HerringG1SpaceModule>;
+using HerringG2Space = detail::HerringModuleSpaceProver<detail::HerringG2SpaceModule>;
+
 class IdxVec {
  public:
   explicit IdxVec(const std::vector<uint32_t>& index) { check(gm_idx_register(index.data(), index.size(), &h_)); }
