@@ -2470,27 +2470,33 @@ int gm_ipa_new(uint64_t transcript, uint64_t crs, const uint64_t* a_mont, const 
   *proof = put_in(C, C->ipa, std::move(p));
   return GM_OK;
 }
-int gm_ipa_from_fields(size_t rounds, const uint64_t* messages, const uint64_t* challenges, const uint64_t* batch_challenges, const uint64_t* final_lhs_jac,
-                       const uint64_t* final_rhs_jac, const uint64_t foldings_ff[8], const uint64_t foldings_fg1[22], const uint64_t foldings_fg2[40], uint64_t* proof) {
+// a proof for K claims from its fields, laid out as the getters return them
+static int ipa_from_fields(const char* who, size_t rounds, size_t K, const uint64_t* messages, const uint64_t* challenges, const uint64_t* batch_challenges,
+                           const uint64_t* final_lhs_jac, const uint64_t* final_rhs_jac, const uint64_t* ff, const uint64_t* fg1, const uint64_t* fg2, uint64_t* proof) {
   GM_CTX();
-  GM_CHECK(rounds >= 1 && rounds <= 64, GM_EINVAL, "ipa_from_fields: %zu rounds", rounds);
+  GM_CHECK(rounds >= 1 && rounds <= 64, GM_EINVAL, "%s: %zu rounds", who, rounds);
+  GM_CHECK(K >= 1 && K <= ((size_t)1 << 28), GM_EINVAL, "%s: %zu claims", who, K);
   const size_t k = 2 * (rounds - 1);
-  GM_CHECK(messages && challenges && batch_challenges && (k == 0 || (final_lhs_jac && final_rhs_jac)) && foldings_ff && foldings_fg1 && foldings_fg2 && proof, GM_EINVAL,
-           "ipa_from_fields: null pointer");
+  GM_CHECK(messages && challenges && batch_challenges && (k == 0 || (final_lhs_jac && final_rhs_jac)) && ff && fg1 && fg2 && proof, GM_EINVAL, "%s: null pointer", who);
   auto p = std::make_unique<IpaProof>();
   p->rounds = rounds;
+  p->K = K;
   p->messages.assign(messages, messages + rounds * 144);
   p->challenges.assign(challenges, challenges + rounds * 4);
-  p->batch_challenges.assign(batch_challenges, batch_challenges + (3 + k) * 4);
+  p->batch_challenges.assign(batch_challenges, batch_challenges + (3 * K + k) * 4);
   if (k) {
     p->final_g1.assign(final_lhs_jac, final_lhs_jac + k * 18);
     p->final_g2.assign(final_rhs_jac, final_rhs_jac + k * 36);
   }
-  memcpy(p->foldings_ff, foldings_ff, sizeof p->foldings_ff);
-  memcpy(p->foldings_fg1, foldings_fg1, sizeof p->foldings_fg1);
-  memcpy(p->foldings_fg2, foldings_fg2, sizeof p->foldings_fg2);
+  p->foldings_ff.assign(ff, ff + K * 8);
+  p->foldings_fg1.assign(fg1, fg1 + K * 22);
+  p->foldings_fg2.assign(fg2, fg2 + K * 40);
   *proof = put_in(C, C->ipa, std::move(p));
   return GM_OK;
+}
+int gm_ipa_from_fields(size_t rounds, const uint64_t* messages, const uint64_t* challenges, const uint64_t* batch_challenges, const uint64_t* final_lhs_jac,
+                       const uint64_t* final_rhs_jac, const uint64_t foldings_ff[8], const uint64_t foldings_fg1[22], const uint64_t foldings_fg2[40], uint64_t* proof) {
+  return ipa_from_fields("ipa_from_fields", rounds, 1, messages, challenges, batch_challenges, final_lhs_jac, final_rhs_jac, foldings_ff, foldings_fg1, foldings_fg2, proof);
 }
 // the 2 rounds GT messages of a proof through k_gt_check: a of round i is index 2 i, b is 2 i + 1 (the layout of `messages`)
 int gm_ipa_check_gt(uint64_t proof, size_t* first_bad, int* ok) {
@@ -2544,7 +2550,7 @@ int gm_ipa_foldings_ff(uint64_t proof, uint64_t lhs_rhs_mont[8]) {
   GM_IPA_FIND(p, ipa, proof, "ipa_foldings_ff", "proof");
   GM_CHECK(p->K == 1, GM_EINVAL, "ipa_foldings_ff: a proof for %zu claims; gm_ipa_foldings_batch reads the foldings of all of them", p->K);
   GM_CHECK(lhs_rhs_mont != nullptr, GM_EINVAL, "ipa_foldings_ff: null pointer");
-  memcpy(lhs_rhs_mont, p->foldings_ff, sizeof p->foldings_ff);
+  memcpy(lhs_rhs_mont, p->foldings_ff.data(), 8 * 8);
   return GM_OK;
 }
 int gm_ipa_foldings_fg1(uint64_t proof, uint64_t lhs_jac[18], uint64_t rhs_mont[4]) {
@@ -2552,8 +2558,8 @@ int gm_ipa_foldings_fg1(uint64_t proof, uint64_t lhs_jac[18], uint64_t rhs_mont[
   GM_IPA_FIND(p, ipa, proof, "ipa_foldings_fg1", "proof");
   GM_CHECK(p->K == 1, GM_EINVAL, "ipa_foldings_fg1: a proof for %zu claims; gm_ipa_foldings_batch reads the foldings of all of them", p->K);
   GM_CHECK(lhs_jac && rhs_mont, GM_EINVAL, "ipa_foldings_fg1: null pointer");
-  memcpy(lhs_jac, p->foldings_fg1, 18 * 8);
-  memcpy(rhs_mont, p->foldings_fg1 + 18, 4 * 8);
+  memcpy(lhs_jac, p->foldings_fg1.data(), 18 * 8);
+  memcpy(rhs_mont, p->foldings_fg1.data() + 18, 4 * 8);
   return GM_OK;
 }
 int gm_ipa_foldings_fg2(uint64_t proof, uint64_t lhs_mont[4], uint64_t rhs_jac[36]) {
@@ -2561,8 +2567,8 @@ int gm_ipa_foldings_fg2(uint64_t proof, uint64_t lhs_mont[4], uint64_t rhs_jac[3
   GM_IPA_FIND(p, ipa, proof, "ipa_foldings_fg2", "proof");
   GM_CHECK(p->K == 1, GM_EINVAL, "ipa_foldings_fg2: a proof for %zu claims; gm_ipa_foldings_batch reads the foldings of all of them", p->K);
   GM_CHECK(lhs_mont && rhs_jac, GM_EINVAL, "ipa_foldings_fg2: null pointer");
-  memcpy(lhs_mont, p->foldings_fg2, 4 * 8);
-  memcpy(rhs_jac, p->foldings_fg2 + 4, 36 * 8);
+  memcpy(lhs_mont, p->foldings_fg2.data(), 4 * 8);
+  memcpy(rhs_jac, p->foldings_fg2.data() + 4, 36 * 8);
   return GM_OK;
 }
 int gm_ipa_host_times(uint64_t proof, double ms[3]) {
@@ -2687,42 +2693,14 @@ int gm_ipa_foldings_batch(uint64_t proof, uint64_t* ff, uint64_t* fg1, uint64_t*
   GM_CTX();
   GM_IPA_FIND(p, ipa, proof, "ipa_foldings_batch", "proof");
   GM_CHECK(ff && fg1 && fg2, GM_EINVAL, "ipa_foldings_batch: null pointer");
-  if (p->K == 1) {  // a single-claim proof keeps its foldings in the fixed fields
-    memcpy(ff, p->foldings_ff, sizeof p->foldings_ff);
-    memcpy(fg1, p->foldings_fg1, sizeof p->foldings_fg1);
-    memcpy(fg2, p->foldings_fg2, sizeof p->foldings_fg2);
-    return GM_OK;
-  }
-  memcpy(ff, p->batch_ff.data(), p->batch_ff.size() * 8);
-  memcpy(fg1, p->batch_fg1.data(), p->batch_fg1.size() * 8);
-  memcpy(fg2, p->batch_fg2.data(), p->batch_fg2.size() * 8);
+  memcpy(ff, p->foldings_ff.data(), p->foldings_ff.size() * 8);
+  memcpy(fg1, p->foldings_fg1.data(), p->foldings_fg1.size() * 8);
+  memcpy(fg2, p->foldings_fg2.data(), p->foldings_fg2.size() * 8);
   return GM_OK;
 }
 int gm_ipa_from_fields_batch(size_t rounds, size_t K, const uint64_t* messages, const uint64_t* challenges, const uint64_t* batch_challenges, const uint64_t* final_lhs_jac,
                              const uint64_t* final_rhs_jac, const uint64_t* ff, const uint64_t* fg1, const uint64_t* fg2, uint64_t* proof) {
-  GM_CTX();
-  GM_CHECK(rounds >= 1 && rounds <= 64, GM_EINVAL, "ipa_from_fields_batch: %zu rounds", rounds);
-  GM_CHECK(K >= 1 && K <= ((size_t)1 << 28), GM_EINVAL, "ipa_from_fields_batch: %zu claims", K);
-  const size_t k = 2 * (rounds - 1);
-  GM_CHECK(messages && challenges && batch_challenges && (k == 0 || (final_lhs_jac && final_rhs_jac)) && ff && fg1 && fg2 && proof, GM_EINVAL, "ipa_from_fields_batch: null pointer");
-  auto p = std::make_unique<IpaProof>();
-  p->rounds = rounds;
-  p->K = K;
-  p->messages.assign(messages, messages + rounds * 144);
-  p->challenges.assign(challenges, challenges + rounds * 4);
-  p->batch_challenges.assign(batch_challenges, batch_challenges + (3 * K + k) * 4);
-  if (k) {
-    p->final_g1.assign(final_lhs_jac, final_lhs_jac + k * 18);
-    p->final_g2.assign(final_rhs_jac, final_rhs_jac + k * 36);
-  }
-  p->batch_ff.assign(ff, ff + K * 8);
-  p->batch_fg1.assign(fg1, fg1 + K * 22);
-  p->batch_fg2.assign(fg2, fg2 + K * 40);
-  memcpy(p->foldings_ff, ff, sizeof p->foldings_ff);
-  memcpy(p->foldings_fg1, fg1, sizeof p->foldings_fg1);
-  memcpy(p->foldings_fg2, fg2, sizeof p->foldings_fg2);
-  *proof = put_in(C, C->ipa, std::move(p));
-  return GM_OK;
+  return ipa_from_fields("ipa_from_fields_batch", rounds, K, messages, challenges, batch_challenges, final_lhs_jac, final_rhs_jac, ff, fg1, fg2, proof);
 }
 int gm_ipa_verify_batch(uint64_t proof, uint64_t vrs, const uint64_t* comm_a_jac, const uint64_t* comm_b_jac, const uint64_t* y_mont, size_t K, int* ok) {
   if (ok) *ok = 0;

@@ -183,13 +183,10 @@ struct IpaProof {
   size_t rounds = 0;
   std::vector<uint64_t> messages;          // rounds x (a || b), 144 limbs each
   std::vector<uint64_t> challenges;        // rounds x 4, Montgomery
-  std::vector<uint64_t> batch_challenges;  // (2 rounds + 1) x 4
+  size_t K = 1;                            // claims: 1 for every proof but one of gm_ipa_new_batch / gm_ipa_from_fields_batch
+  std::vector<uint64_t> batch_challenges;  // (3 K + 2 (rounds - 1)) x 4
   std::vector<uint64_t> final_g1, final_g2;  // 2 (rounds - 1) x 18 / x 36: Sumcheck::final_foldings
-  uint64_t foldings_ff[8], foldings_fg1[22], foldings_fg2[40];  // (lhs || rhs) of the three initial provers (of claim 0 of a batch proof)
-  // a batch proof (gm_ipa_new_batch, gm_ipa_from_fields_batch): K claims, batch_challenges (3 K + 2 (rounds - 1)) x 4 and the
-  // foldings of all claims, K x 8 / K x 22 / K x 40.  Every other proof has K = 1 and leaves the three vectors empty
-  size_t K = 1;
-  std::vector<uint64_t> batch_ff, batch_fg1, batch_fg2;
+  std::vector<uint64_t> foldings_ff, foldings_fg1, foldings_fg2;  // K x 8 / K x 22 / K x 40: (lhs || rhs) of the three initial provers of every claim
   double host_ms[3] = {0, 0, 0};  // of gm_ipa_new: host GT multi-exponentiations, host final exponentiations, the whole call (gm_ipa_host_times)
 };
 

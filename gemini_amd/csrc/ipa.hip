@@ -20,6 +20,14 @@
 // Launches per round: 2 folds, 1 segmented Miller kernel and its reduction levels (none while m_j / 2 <= 64, then one per factor
 // 64), whatever the number of live provers.
 //
+// One claim (ipa_prove, InnerProductProof::new) and K claims in one proof (ipa_prove_batch, ::generic) are ONE round loop,
+// ipa_prove_rounds, over an InitialClaims the entry fills.  The entries differ in four places only: the K FModule provers that
+// step; the scalars the G1Module / G2Module provers run over -- a and b from the host, limbs as they are, or the weighted sums
+// ca / cb formed on the device, for every K including 1; the exponent the module messages enter with -- bch[1] and bch[2], or
+// one; and where the PModule batch challenges start, 3 or 3 K.  Which of the two a call takes is the entry's, never K == 1's.
+// A proof object holds K rows of foldings whichever entry made it.  ipa_prove_lockstep (many proofs in one call) is another
+// algorithm and shares only the argument checks (ipa_prover_sizes).
+//
 // Locks: the MSM lock around every stretch that stages in C->msm.misc or uses the pairing workspace; the module provers take their own.
 #include <algorithm>
 #include <array>
@@ -64,6 +72,27 @@ void g2_to_record(const gmh::G2& p, uint64_t out[24]) {
   gmh::fq_to_device(a.x.c1, out + 6);
   gmh::fq_to_device(a.y.c0, out + 12);
   gmh::fq_to_device(a.y.c1, out + 18);
+}
+// Jacobian limbs -> the affine host record (ark-ff's Montgomery form) the short linear combinations take; `out` arrives all zero,
+// which is the identity
+void g1_to_host_record(const uint64_t jac[18], uint64_t out[12]) {
+  const gmh::G1 p = gmh::G1::from_limbs(jac);
+  if (p.is_identity()) return;
+  const gmh::G1 a = p.normalized();
+  a.x.to_limbs(out);
+  a.y.to_limbs(out + 6);
+}
+void g2_to_host_record(const uint64_t jac[36], uint64_t out[24]) {
+  const gmh::G2 p = gmh::G2::from_limbs(jac);
+  if (p.is_identity()) return;
+  const gmh::G2 a = p.normalized();
+  a.x.to_limbs(out);
+  a.y.to_limbs(out + 12);
+}
+
+bool fr_reduced(const uint64_t* p) {
+  uint64_t t[4];
+  return gmh::sub_n<4>(t, p, gmh::FrP::MOD) != 0;
 }
 
 Scalar canonical(const gmh::Fr& x) {
@@ -237,17 +266,52 @@ int vrs_from_crs(Context* C, const Crs* crs, Vrs* out) {
 
 namespace {
 
-// The three initial provers of InnerProductProof::new, freed with the call
-struct InitialProvers {
-  Context* C;
-  uint64_t ff = 0, fg1 = 0, fg2 = 0;
+// What the initial claims bring to the batched sumcheck (ipa_prove_rounds), as InitialTerms does for the verifier: the provers an
+// entry has made, freed with the call, and how their messages enter a round message.
+struct InitialClaims {
+  const char* who;
+  std::vector<uint64_t> ff;  // the FModule prover of every claim; its message enters as E^(weights[i] a)
+  uint64_t fg1 = 0, fg2 = 0;  // the G1Module and the G2Module prover
   HerringProver *h1 = nullptr, *h2 = nullptr;
-  ~InitialProvers() {
-    if (ff) (void)gm_sc_free(ff);
+  // the batch challenge the G1 / G2 module messages enter with, as an index into `weights`, or -1 for exponent one: the module
+  // provers run over sums the entry has weighted already, and their final scalars are no claim's
+  int e_g1 = -1, e_g2 = -1;
+  std::vector<gmh::Fr> weights;  // the batch challenges of the initial claims; the PModule provers' start at first = weights.size()
+  ~InitialClaims() {
+    for (uint64_t h : ff) (void)gm_sc_free(h);
     if (fg1) (void)gm_hg1_free(fg1);
     if (fg2) (void)gm_hg2_free(fg2);
   }
+  int add_ff(const uint64_t* a_mont, const uint64_t* b_mont, size_t d, const uint64_t one[4]) {
+    uint64_t h = 0;
+    int rc = gm_sc_new(a_mont, d, b_mont, d, one, &h);
+    if (rc) return rc;
+    ff.push_back(h);
+    return gm_sc_set_herring(h, 1);
+  }
+  // the G1 / G2 provers get the first 2^rounds points: their messages zip against d scalars and their final folding is a
+  // combination of exactly those points, so the rest of a longer CRS never enters (and need not be folded).  The points are on the
+  // device and are copied; so are the scalars when `on_device` says they are there
+  int add_modules(Context* C, const Crs* crs, size_t full, const void* a, const void* b, size_t d, const uint64_t one[4], bool on_device) {
+    int rc;
+    if ((rc = herring_create(C, HERRING_G1, crs->g1, 96, full, a, 32, d, one, &fg1, on_device ? 3 : 1))) return rc;
+    if ((rc = herring_create(C, HERRING_G2, b, 32, d, crs->g2, 192, full, one, &fg2, on_device ? 3 : 2))) return rc;
+    std::lock_guard<std::mutex> lk(C->mu);
+    h1 = C->herring[fg1].get();
+    h2 = C->herring[fg2].get();
+    return GM_OK;
+  }
 };
+
+// what every prover entry asks of d and the CRS; `line` is the round loop of the reference the entry restates
+int ipa_prover_sizes(size_t d, const Crs* crs, const char* who, int line, size_t* rounds, size_t* full) {
+  GM_CHECK(d >= 2, GM_EINVAL, "%s: d = %zu; the argument needs at least two scalars (the reference's round loop underflows at rounds - 1, ipa.rs:%d)", who, d, line);
+  *rounds = (size_t)msm_ceil_log2(d);
+  *full = (size_t)1 << *rounds;
+  const size_t need = std::max(d + 1, *full);
+  GM_CHECK(crs->n1 >= need && crs->n2 >= need, GM_EINVAL, "%s: d = %zu needs a CRS of max(d + 1, 2^rounds) = %zu points, it has %zu / %zu", who, d, need, crs->n1, crs->n2);
+  return GM_OK;
+}
 
 // The PModule provers of one proof.  Prover p (in the order ipa.rs pushes them: g1fold and g2fold of round 0, of round 1, ...) keeps
 // its Lhs vector in slot p of the G1 arena and its Rhs vector in slot p ^ 1 of the G2 arena: the fold of the chopped CRS lands in
@@ -328,34 +392,15 @@ int arena_finals(Context* C, const Crs* crs, Arena& A, const uint64_t last[4], I
   return GM_OK;
 }
 
-}  // namespace
+typedef std::chrono::steady_clock Clock;
+double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
 
-// InnerProductProof::new (ipa.rs:533-685)
-int ipa_prove(Context* C, uint64_t transcript, const Crs* crs, const uint64_t* a_mont, const uint64_t* b_mont, size_t d, IpaProof* proof) {
-  GM_CHECK(d >= 2, GM_EINVAL, "ipa_new: d = %zu; the argument needs at least two scalars (the reference's round loop underflows at rounds - 1, ipa.rs:584)", d);
-  const size_t rounds = (size_t)msm_ceil_log2(d), full = (size_t)1 << rounds;
-  const size_t need = std::max(d + 1, full);
-  GM_CHECK(crs->n1 >= need && crs->n2 >= need, GM_EINVAL, "ipa_new: d = %zu needs a CRS of max(d + 1, 2^rounds) = %zu points, it has %zu / %zu", d, need, crs->n1, crs->n2);
-  uint64_t one[4];
-  gmh::Fr::one().to_limbs(one);
-  typedef std::chrono::steady_clock Clock;
-  auto ms_since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
-  const Clock::time_point t_start = Clock::now();
-  proof->host_ms[0] = proof->host_ms[1] = proof->host_ms[2] = 0;
-
-  // the three claims.  The G1 / G2 provers get the first 2^rounds points: their messages zip against d scalars and their final
-  // folding is a combination of exactly those points, so the rest of a longer CRS never enters (and need not be folded)
-  InitialProvers P{C};
+// The batched sumcheck of InnerProductProof::new and ::generic (ipa.rs:584-685, 420-531) from the first message on: the entry has
+// made the initial provers and drawn the first batch challenge (T.weights).  counts: split-fold launches, MSM calls, Miller
+// launches, where they are issued (gm_debug_ipa_new_batch_path).
+int ipa_prove_rounds(Context* C, uint64_t transcript, const Crs* crs, size_t rounds, const InitialClaims& T, IpaProof* proof, size_t counts[3]) {
+  const size_t K = T.ff.size(), first = T.weights.size(), full = (size_t)1 << rounds;
   int rc;
-  if ((rc = gm_sc_new(a_mont, d, b_mont, d, one, &P.ff)) || (rc = gm_sc_set_herring(P.ff, 1))) return rc;
-  if ((rc = herring_create(C, HERRING_G1, crs->g1, 96, full, a_mont, 32, d, one, &P.fg1, 1))) return rc;
-  if ((rc = herring_create(C, HERRING_G2, b_mont, 32, d, crs->g2, 192, full, one, &P.fg2, 2))) return rc;
-  {
-    std::lock_guard<std::mutex> lk(C->mu);
-    P.h1 = C->herring[P.fg1].get();
-    P.h2 = C->herring[P.fg2].get();
-  }
-
   Scratch mem;
   Arena A;
   uint8_t *aux1 = nullptr, *aux2 = nullptr;  // G1: message a, message b, generator; G2: generator, message a, message b
@@ -370,9 +415,11 @@ int ipa_prove(Context* C, uint64_t transcript, const Crs* crs, const uint64_t* a
   g2_to_record(g2_generator(), rec2);
 
   proof->rounds = rounds;
+  proof->K = K;
   proof->messages.assign(rounds * 144, 0);
   proof->challenges.assign(rounds * 4, 0);
   proof->batch_challenges.clear();
+  proof->host_ms[0] = proof->host_ms[1] = proof->host_ms[2] = 0;
   std::vector<gmh::Fr> bch;  // batch_challenges
   auto push_bch = [&](const gmh::Fr& x) {
     bch.push_back(x);
@@ -380,18 +427,35 @@ int ipa_prove(Context* C, uint64_t transcript, const Crs* crs, const uint64_t* a
     x.to_limbs(l);
     proof->batch_challenges.insert(proof->batch_challenges.end(), l, l + 4);
   };
+  for (const gmh::Fr& w : T.weights) push_bch(w);
 
-  // One message of the batched sumcheck: the three initial provers step (folding by `vm` first when there is one), then every
-  // PModule prover's products and the carriers of the first three in one segmented launch, then the two GT multi-exponentiations
+  // One message of the batched sumcheck: the K FModule provers step in one launch group (folding by `vm` first when there is
+  // one), then the two module provers, then every PModule prover's products and the carriers of the initial messages in ONE
+  // segmented Miller launch, then the two GT multi-exponentiations E^(sum_i weights[i] fa_i) m_g1^e_g1 m_g2^e_g2 prod_p m_p^bch[first + p]
+  std::vector<int> has_many(K);
+  const Scalar unit = canonical(gmh::Fr::one());
   auto round_message = [&](const uint64_t* vm, uint64_t* out144) -> int {
     uint64_t fa[4], fb[4], g1a[18], g1b[18], g2a[36], g2b[36];
     int has = 0, r;
-    if ((r = gm_sc_round(P.ff, vm, fa, fb, &has))) return r;
-    GM_CHECK(has, GM_ESTATE, "ipa_new: the FModule prover has no message");
-    if ((r = herring_round(C, P.h1, vm, g1a, g1b, &has))) return r;
-    GM_CHECK(has, GM_ESTATE, "ipa_new: the G1Module prover has no message");
-    if ((r = herring_round(C, P.h2, vm, g2a, g2b, &has))) return r;
-    GM_CHECK(has, GM_ESTATE, "ipa_new: the G2Module prover has no message");
+    if ((r = gm_sc_round_begin_many(T.ff.data(), K, vm, has_many.data()))) return r;
+    gmh::Fr sa = gmh::Fr::zero(), sb = gmh::Fr::zero();
+    int all = 1;
+    for (size_t i = 0; i < K; i++) {
+      if (!has_many[i]) {
+        all = 0;
+        continue;
+      }
+      if ((r = gm_sc_round_end(T.ff[i], fa, fb))) return r;
+      sa = sa + gmh::Fr::from_limbs(fa) * bch[i];
+      sb = sb + gmh::Fr::from_limbs(fb) * bch[i];
+    }
+    GM_CHECK(all, GM_ESTATE, "%s: an FModule prover has no message", T.who);
+    if ((r = herring_round(C, T.h1, vm, g1a, g1b, &has))) return r;
+    GM_CHECK(has, GM_ESTATE, "%s: the G1Module prover has no message", T.who);
+    if ((r = herring_round(C, T.h2, vm, g2a, g2b, &has))) return r;
+    GM_CHECK(has, GM_ESTATE, "%s: the G2Module prover has no message", T.who);
+    counts[0] += vm ? 2 : 0;  // the point side of either module prover folds in one launch
+    counts[1] += 1 + 3;       // g1_message: one batch of three strided MSMs; g2_message: three MSMs
     g1_to_record(gmh::G1::from_limbs(g1a), rec1);
     g1_to_record(gmh::G1::from_limbs(g1b), rec1 + 12);
     g2_to_record(gmh::G2::from_limbs(g2a), rec2 + 24);
@@ -403,20 +467,15 @@ int ipa_prove(Context* C, uint64_t transcript, const Crs* crs, const uint64_t* a
       GM_HIP(hipMemcpyAsync(aux1, rec1, sizeof rec1, hipMemcpyHostToDevice, C->stream));
       GM_HIP(hipMemcpyAsync(aux2, rec2, sizeof rec2, hipMemcpyHostToDevice, C->stream));
       if ((r = miller_products(C, prods.data(), prods.size(), m.data()))) return r;
+      counts[2] += 1;
     }
-    // SumcheckMsg::ip(messages, batch_challenges) (ipa.rs:636-644): E^(ff bch_0), the G1 and G2 messages by bch_1, bch_2, prover p by bch_{3 + p}
+    // SumcheckMsg::ip(messages, batch_challenges) (ipa.rs:636-644)
     for (int half = 0; half < 2; half++) {
-      std::vector<gmh::Fq12> x;
-      std::vector<Scalar> e;
-      x.push_back(m[0]);
-      e.push_back(canonical(gmh::Fr::from_limbs(half ? fb : fa) * bch[0]));
-      x.push_back(m[1 + half]);
-      e.push_back(canonical(bch[1]));
-      x.push_back(m[3 + half]);
-      e.push_back(canonical(bch[2]));
+      std::vector<gmh::Fq12> x = {m[0], m[1 + half], m[3 + half]};
+      std::vector<Scalar> e = {canonical(half ? sb : sa), T.e_g1 < 0 ? unit : canonical(bch[T.e_g1]), T.e_g2 < 0 ? unit : canonical(bch[T.e_g2])};
       for (size_t p = 0; p < A.live; p++) {
         x.push_back(m[5 + 2 * p + half]);
-        e.push_back(canonical(bch[3 + p]));
+        e.push_back(canonical(bch[first + p]));
       }
       Clock::time_point t0 = Clock::now();
       const gmh::Fq12 prod = gt_multi_pow(x, e);
@@ -428,17 +487,11 @@ int ipa_prove(Context* C, uint64_t transcript, const Crs* crs, const uint64_t* a
     return GM_OK;
   };
 
-  uint64_t ch[4];
-  if ((rc = gm_transcript_challenge_fr(transcript, (const uint8_t*)"batch-chal", 10, ch))) return rc;
-  const gmh::Fr bc = gmh::Fr::from_limbs(ch);
-  push_bch(gmh::Fr::one());
-  push_bch(bc);
-  push_bch(bc.sqr());
   if ((rc = round_message(nullptr, proof->messages.data()))) return rc;
   if ((rc = gm_transcript_append_gt(transcript, (const uint8_t*)"prover_message", 14, proof->messages.data(), 2))) return rc;
 
   for (size_t j = 0; j + 1 < rounds; j++) {
-    uint64_t* c = proof->challenges.data() + 4 * j;
+    uint64_t *c = proof->challenges.data() + 4 * j, ch[4];
     if ((rc = gm_transcript_challenge_fr(transcript, (const uint8_t*)"sumcheck-chal", 13, c))) return rc;
     if ((rc = gm_transcript_challenge_fr(transcript, (const uint8_t*)"batch-chal", 10, ch))) return rc;
     const gmh::Fr b = gmh::Fr::from_limbs(ch);
@@ -447,6 +500,7 @@ int ipa_prove(Context* C, uint64_t transcript, const Crs* crs, const uint64_t* a
     {
       GM_MSM_LOCK(C);
       if ((rc = arena_round(C, crs, A, gmh::Fr::from_limbs(c), true))) return rc;
+      counts[0] += 2;
     }
     uint64_t* msg = proof->messages.data() + 144 * (j + 1);
     if ((rc = round_message(c, msg))) return rc;
@@ -455,15 +509,56 @@ int ipa_prove(Context* C, uint64_t transcript, const Crs* crs, const uint64_t* a
 
   uint64_t* last = proof->challenges.data() + 4 * (rounds - 1);
   if ((rc = gm_transcript_challenge_fr(transcript, (const uint8_t*)"sumcheck-chal", 13, last))) return rc;
+  counts[0] += A.live ? 2 : 0;
   if ((rc = arena_finals(C, crs, A, last, proof))) return rc;
+
+  // final foldings, a row per claim: ff_i from prover i; fg1_i = (the folded CRS point, a scalar), fg2_i = (a scalar, the folded CRS
+  // point).  The scalars are the module provers' own where those ran over the claim's a and b (limbs as they came), and else
+  // ff_i.lhs and ff_i.rhs: the same vector under the same challenges with twist 1
   int has = 0;
-  if ((rc = gm_sc_fold(P.ff, last)) || (rc = herring_fold(C, P.h1, last)) || (rc = herring_fold(C, P.h2, last))) return rc;
-  if ((rc = gm_sc_final(P.ff, proof->foldings_ff, proof->foldings_ff + 4, &has))) return rc;
-  GM_CHECK(has, GM_ESTATE, "ipa_new: the FModule prover has no final foldings");
-  if ((rc = herring_final(C, P.h1, proof->foldings_fg1, proof->foldings_fg1 + 18, &has))) return rc;
-  GM_CHECK(has, GM_ESTATE, "ipa_new: the G1Module prover has no final foldings");
-  if ((rc = herring_final(C, P.h2, proof->foldings_fg2, proof->foldings_fg2 + 4, &has))) return rc;
-  GM_CHECK(has, GM_ESTATE, "ipa_new: the G2Module prover has no final foldings");
+  uint64_t p1[18 + 4], p2[4 + 36];
+  if ((rc = herring_fold(C, T.h1, last)) || (rc = herring_fold(C, T.h2, last))) return rc;
+  counts[0] += 2;
+  if ((rc = herring_final(C, T.h1, p1, p1 + 18, &has))) return rc;
+  GM_CHECK(has, GM_ESTATE, "%s: the G1Module prover has no final foldings", T.who);
+  if ((rc = herring_final(C, T.h2, p2, p2 + 4, &has))) return rc;
+  GM_CHECK(has, GM_ESTATE, "%s: the G2Module prover has no final foldings", T.who);
+  proof->foldings_ff.assign(K * 8, 0);
+  proof->foldings_fg1.assign(K * 22, 0);
+  proof->foldings_fg2.assign(K * 40, 0);
+  for (size_t i = 0; i < K; i++) {
+    uint64_t *ff = proof->foldings_ff.data() + 8 * i, *fg1 = proof->foldings_fg1.data() + 22 * i, *fg2 = proof->foldings_fg2.data() + 40 * i;
+    if ((rc = gm_sc_fold(T.ff[i], last)) || (rc = gm_sc_final(T.ff[i], ff, ff + 4, &has))) return rc;
+    GM_CHECK(has, GM_ESTATE, "%s: FModule prover %zu has no final foldings", T.who, i);
+    memcpy(fg1, p1, 18 * 8);
+    memcpy(fg1 + 18, T.e_g1 < 0 ? ff : p1 + 18, 4 * 8);
+    memcpy(fg2, T.e_g2 < 0 ? ff + 4 : p2, 4 * 8);
+    memcpy(fg2 + 4, p2 + 4, 36 * 8);
+  }
+  return GM_OK;
+}
+
+}  // namespace
+
+// InnerProductProof::new (ipa.rs:533-685): the module provers run over a and b as the host hands them, limbs as they are, and
+// their messages enter with the batch challenges bc and bc^2
+int ipa_prove(Context* C, uint64_t transcript, const Crs* crs, const uint64_t* a_mont, const uint64_t* b_mont, size_t d, IpaProof* proof) {
+  size_t rounds, full;
+  int rc = ipa_prover_sizes(d, crs, "ipa_new", 584, &rounds, &full);
+  if (rc) return rc;
+  uint64_t one[4], ch[4];
+  gmh::Fr::one().to_limbs(one);
+  const Clock::time_point t_start = Clock::now();
+
+  InitialClaims T{"ipa_new"};
+  if ((rc = T.add_ff(a_mont, b_mont, d, one)) || (rc = T.add_modules(C, crs, full, a_mont, b_mont, d, one, false))) return rc;
+  if ((rc = gm_transcript_challenge_fr(transcript, (const uint8_t*)"batch-chal", 10, ch))) return rc;
+  const gmh::Fr bc = gmh::Fr::from_limbs(ch);
+  T.weights = {gmh::Fr::one(), bc, bc.sqr()};
+  T.e_g1 = 1;
+  T.e_g2 = 2;
+  size_t counts[3] = {0, 0, 0};
+  if ((rc = ipa_prove_rounds(C, transcript, crs, rounds, T, proof, counts))) return rc;
   proof->host_ms[2] = ms_since(t_start);
   return GM_OK;
 }
@@ -504,11 +599,6 @@ struct LockstepProof {
   SpanRef mod;                    // the G1Module's points and the G2Module's points: the same offsets in both groups
   gmh::Fr fa, fb;                 // the FModule message of the round
 };
-
-bool fr_is_reduced(const uint64_t* p) {
-  uint64_t t[4];
-  return gmh::sub_n<4>(t, p, gmh::FrP::MOD) != 0;
-}
 
 void fr_fold(std::vector<gmh::Fr>& v, const gmh::Fr& c) {
   const size_t n = v.size(), m = (n + 1) / 2;
@@ -824,12 +914,15 @@ int ipa_prove_lockstep(Context* C, const uint64_t* transcripts, const Crs* crs, 
       gmh::g1_affine_to_jac_dev(fs + 12 * q).to_limbs(pr->final_g1.data() + 18 * q);
       gmh::g2_affine_to_jac_dev(gs + 24 * q).to_limbs(pr->final_g2.data() + 36 * q);
     }
-    p.a[0].to_limbs(pr->foldings_ff);
-    p.b[0].to_limbs(pr->foldings_ff + 4);
-    gmh::g1_affine_to_jac_dev(fs + 12 * k).to_limbs(pr->foldings_fg1);
-    p.a[0].to_limbs(pr->foldings_fg1 + 18);
-    p.b[0].to_limbs(pr->foldings_fg2);
-    gmh::g2_affine_to_jac_dev(gs + 24 * k).to_limbs(pr->foldings_fg2 + 4);
+    pr->foldings_ff.assign(8, 0);
+    pr->foldings_fg1.assign(22, 0);
+    pr->foldings_fg2.assign(40, 0);
+    p.a[0].to_limbs(pr->foldings_ff.data());
+    p.b[0].to_limbs(pr->foldings_ff.data() + 4);
+    gmh::g1_affine_to_jac_dev(fs + 12 * k).to_limbs(pr->foldings_fg1.data());
+    p.a[0].to_limbs(pr->foldings_fg1.data() + 18);
+    p.b[0].to_limbs(pr->foldings_fg2.data());
+    gmh::g2_affine_to_jac_dev(gs + 24 * k).to_limbs(pr->foldings_fg2.data() + 4);
     pr->host_ms[2] = ms;  // of the whole call: the proofs were made together
   }
   return GM_OK;
@@ -838,15 +931,14 @@ int ipa_prove_lockstep(Context* C, const uint64_t* transcripts, const Crs* crs, 
 }  // namespace
 
 int ipa_prove_many(Context* C, const uint64_t* transcripts, const Crs* crs, const uint64_t* a_mont, const uint64_t* b_mont, size_t d, size_t S, IpaProof* const* proofs) {
-  GM_CHECK(d >= 2, GM_EINVAL, "ipa_new_many: d = %zu; the argument needs at least two scalars (the reference's round loop underflows at rounds - 1, ipa.rs:584)", d);
-  const size_t rounds = (size_t)msm_ceil_log2(d), need = std::max(d + 1, (size_t)1 << rounds);
-  GM_CHECK(crs->n1 >= need && crs->n2 >= need, GM_EINVAL, "ipa_new_many: d = %zu needs a CRS of max(d + 1, 2^rounds) = %zu points, it has %zu / %zu", d, need, crs->n1, crs->n2);
-  GM_CHECK(S <= ((size_t)1 << 16) && d <= ((size_t)1 << 24) && S * d <= ((size_t)1 << 28), GM_EINVAL, "ipa_new_many: %zu proofs of d = %zu (at most 2^28 scalars a side)", S, d);
+  size_t rounds, full;
+  int rc = ipa_prover_sizes(d, crs, "ipa_new_many", 584, &rounds, &full);
+  if (rc) return rc;
+  GM_CHECK(S <=((size_t)1 << 16) && d <= ((size_t)1 << 24) && S * d <= ((size_t)1 << 28), GM_EINVAL, "ipa_new_many: %zu proofs of d = %zu (at most 2^28 scalars a side)", S, d);
   // the lockstep path computes with reduced residues; the per-proof path takes limbs as they are
   bool lockstep = S >= C->ipa_new_many_min && S > 0;
-  for (size_t i = 0; lockstep && i < S * d; i++) lockstep = fr_is_reduced(a_mont + 4 * i) && fr_is_reduced(b_mont + 4 * i);
+  for (size_t i = 0; lockstep && i < S * d; i++) lockstep = fr_reduced(a_mont + 4 * i) && fr_reduced(b_mont + 4 * i);
   size_t counts[4] = {0, 0, 0, 0};
-  int rc = GM_OK;
   if (lockstep) {
     counts[0] = S;
     rc = ipa_prove_lockstep(C, transcripts, crs, a_mont, b_mont, d, S, proofs, &counts[2], &counts[3]);
@@ -876,6 +968,17 @@ struct InitialTerms {
   Scalar e_ff, e_fg1, e_fg2;       // expected = E^e_ff e(fg1, G2)^e_fg1 e(G1, fg2)^e_fg2 prod_p e(lhs_p, rhs_p)^bch[first + p]
   size_t first;                    // of the PModule provers' batch challenges: 3 K
 };
+
+// what a verifier of K claims asks of a proof and of the Vrs (none: the lengths alone)
+int ipa_shape(const IpaProof* pr, const Vrs* vrs, size_t K, const char* who) {
+  const size_t R = pr->rounds, k = R >= 1 ? 2 * (R - 1) : 0;
+  GM_CHECK(K >= 1 && K == pr->K, GM_EINVAL, "%s: %zu claims for a proof of %zu (gm_ipa_verify_batch takes a proof for several)", who, K, pr->K);
+  GM_CHECK(R >= 1 && pr->messages.size() == R * 144 && pr->challenges.size() == R * 4 && pr->batch_challenges.size() == (3 * K + k) * 4 && pr->final_g1.size() == k * 18 &&
+               pr->final_g2.size() == k * 36 && pr->foldings_ff.size() == K * 8 && pr->foldings_fg1.size() == K * 22 && pr->foldings_fg2.size() == K * 40,
+           GM_EINVAL, "%s: the proof's fields do not have the lengths of %zu rounds and %zu claims", who, R, K);
+  GM_CHECK(!vrs || vrs->levels + 1 >= R, GM_EINVAL, "%s: a proof of %zu rounds needs %zu levels of the Vrs, it has %zu", who, R, R - 1, vrs ? vrs->levels : 0);
+  return GM_OK;
+}
 
 int ipa_verify_terms(Context* C, const IpaProof* pr, const Vrs* vrs, const InitialTerms& T, int* ok) {
   const size_t R = pr->rounds, k = 2 * (R - 1), n0 = T.first;
@@ -945,25 +1048,22 @@ int ipa_verify_terms(Context* C, const IpaProof* pr, const Vrs* vrs, const Initi
 }  // namespace
 
 int ipa_verify(Context* C, const IpaProof* pr, const Vrs* vrs, const uint64_t comm_a[18], const uint64_t comm_b[36], const uint64_t y_mont[4], int* ok) {
-  const size_t R = pr->rounds, k = R >= 1 ? 2 * (R - 1) : 0;
-  GM_CHECK(pr->K == 1, GM_EINVAL, "ipa_verify: a proof for %zu claims goes to gm_ipa_verify_batch", pr->K);
-  GM_CHECK(R >= 1 && pr->messages.size() == R * 144 && pr->challenges.size() == R * 4 && pr->batch_challenges.size() == (3 + k) * 4 && pr->final_g1.size() == k * 18 &&
-               pr->final_g2.size() == k * 36,
-           GM_EINVAL, "ipa_verify: the proof's fields do not have the lengths of %zu rounds", R);
-  GM_CHECK(vrs->levels + 1 >= R, GM_EINVAL, "ipa_verify: a proof of %zu rounds needs %zu levels of the Vrs, it has %zu", R, R - 1, vrs->levels);
+  int rc = ipa_shape(pr, vrs, 1, "ipa_verify");
+  if (rc) return rc;
   auto fr = [](const uint64_t* p) { return gmh::Fr::from_limbs(p); };
   const gmh::Fr b0 = fr(pr->batch_challenges.data()), b1 = fr(pr->batch_challenges.data() + 4), b2 = fr(pr->batch_challenges.data() + 8);
+  const uint64_t *ff = pr->foldings_ff.data(), *fg1 = pr->foldings_fg1.data(), *fg2 = pr->foldings_fg2.data();
   InitialTerms T;
   T.comm_a = gmh::G1::from_limbs(comm_a);
   T.comm_b = gmh::G2::from_limbs(comm_b);
-  T.fg1 = gmh::G1::from_limbs(pr->foldings_fg1);
-  T.fg2 = gmh::G2::from_limbs(pr->foldings_fg2 + 4);
+  T.fg1 = gmh::G1::from_limbs(fg1);
+  T.fg2 = gmh::G2::from_limbs(fg2 + 4);
   T.e_y = canonical(fr(y_mont) * b0);
   T.e_comm_a = canonical(b1);
   T.e_comm_b = canonical(b2);
-  T.e_ff = canonical(fr(pr->foldings_ff) * fr(pr->foldings_ff + 4) * b0);
-  T.e_fg1 = canonical(fr(pr->foldings_fg1 + 18) * b1);
-  T.e_fg2 = canonical(fr(pr->foldings_fg2) * b2);
+  T.e_ff = canonical(fr(ff) * fr(ff + 4) * b0);
+  T.e_fg1 = canonical(fr(fg1 + 18) * b1);
+  T.e_fg2 = canonical(fr(fg2) * b2);
   T.first = 3;
   return ipa_verify_terms(C, pr, vrs, T, ok);
 }
@@ -1011,32 +1111,25 @@ void ipa_state(const IpaProof* pr, const uint64_t y_mont[4], std::vector<gmh::Fr
   pair.push_back(fr(y_mont) * bch[0] * W);
   pair.push_back(bch[1] * W);
   pair.push_back(bch[2] * W);
-  pair.push_back((fr(pr->foldings_ff) * fr(pr->foldings_ff + 4) * bch[0]).neg());
-  pair.push_back((fr(pr->foldings_fg1 + 18) * bch[1]).neg());
-  pair.push_back((fr(pr->foldings_fg2) * bch[2]).neg());
+  pair.push_back((fr(pr->foldings_ff.data()) * fr(pr->foldings_ff.data() + 4) * bch[0]).neg());
+  pair.push_back((fr(pr->foldings_fg1.data() + 18) * bch[1]).neg());
+  pair.push_back((fr(pr->foldings_fg2.data()) * bch[2]).neg());
   for (size_t p = 0; p < k; p++) pair.push_back(bch[3 + p].neg());
 }
 
-// the lengths ipa_verify asks of a proof and of the Vrs, with its codes
-int ipa_shape(const IpaProof* pr, const Vrs* vrs, const char* who) {
-  const size_t R = pr->rounds, k = R >= 1 ? 2 * (R - 1) : 0;
-  GM_CHECK(pr->K == 1, GM_EINVAL, "%s: a proof for %zu claims goes to gm_ipa_verify_batch", who, pr->K);
-  GM_CHECK(R >= 1 && pr->messages.size() == R * 144 && pr->challenges.size() == R * 4 && pr->batch_challenges.size() == (3 + k) * 4 && pr->final_g1.size() == k * 18 &&
-               pr->final_g2.size() == k * 36,
-           GM_EINVAL, "%s: the proof's fields do not have the lengths of %zu rounds", who, R);
-  GM_CHECK(!vrs || vrs->levels + 1 >= R, GM_EINVAL, "%s: a proof of %zu rounds needs %zu levels of the Vrs, it has %zu", who, R, R - 1, vrs ? vrs->levels : 0);
-  return GM_OK;
-}
-
-bool fr_reduced(const uint64_t* p) {
-  uint64_t t[4];
-  return gmh::sub_n<4>(t, p, gmh::FrP::MOD) != 0;
+// every scalar the verifier of K claims multiplies is a reduced residue, the challenges of the rounds apart
+bool ipa_claims_reduced(const IpaProof* pr, const uint64_t* y_mont, size_t K) {
+  bool ok = true;
+  for (size_t i = 0; i < K; i++)
+    ok = ok && fr_reduced(y_mont + 4 * i) && fr_reduced(pr->foldings_ff.data() + 8 * i) && fr_reduced(pr->foldings_ff.data() + 8 * i + 4) &&
+         fr_reduced(pr->foldings_fg1.data() + 22 * i + 18) && fr_reduced(pr->foldings_fg2.data() + 40 * i);
+  for (size_t i = 0; i < pr->batch_challenges.size(); i += 4) ok = ok && fr_reduced(pr->batch_challenges.data() + i);
+  return ok;
 }
 // every scalar the stated form multiplies is a reduced residue (the per-proof path takes limbs as they are)
 bool ipa_scalars_reduced(const IpaProof* pr, const uint64_t y_mont[4]) {
-  bool ok = fr_reduced(y_mont) && fr_reduced(pr->foldings_ff) && fr_reduced(pr->foldings_ff + 4) && fr_reduced(pr->foldings_fg1 + 18) && fr_reduced(pr->foldings_fg2);
+  bool ok = ipa_claims_reduced(pr, y_mont, 1);
   for (size_t i = 0; i < pr->challenges.size(); i += 4) ok = ok && fr_reduced(pr->challenges.data() + i);
-  for (size_t i = 0; i < pr->batch_challenges.size(); i += 4) ok = ok && fr_reduced(pr->batch_challenges.data() + i);
   return ok;
 }
 
@@ -1048,7 +1141,7 @@ void g2_record_to_device(const uint64_t in[24], uint64_t out[24]) {
 }  // namespace
 
 int ipa_stated_terms(const IpaProof* pr, const uint64_t y_mont[4], uint64_t* gt_exp, uint64_t* pair_exp) {
-  int rc = ipa_shape(pr, nullptr, "ipa_stated_terms");
+  int rc = ipa_shape(pr, nullptr, 1, "ipa_stated_terms");
   if (rc) return rc;
   std::vector<gmh::Fr> gt, pair;
   ipa_state(pr, y_mont, gt, pair);
@@ -1066,7 +1159,7 @@ int ipa_stated_terms(const IpaProof* pr, const uint64_t y_mont[4], uint64_t* gt_
 int ipa_verify_many(Context* C, const IpaProof* const* proofs, const Vrs* vrs, const uint64_t* comm_a, const uint64_t* comm_b, const uint64_t* y_mont, size_t S, int* ok) {
   int rc;
   for (size_t s = 0; s < S; s++)
-    if ((rc = ipa_shape(proofs[s], vrs, "ipa_verify_many"))) return rc;
+    if ((rc = ipa_shape(proofs[s], vrs, 1, "ipa_verify_many"))) return rc;
   for (size_t s = 0; s < S; s++) ok[s] = 0;
   GM_MSM_LOCK(C);
   C->ipa_verify_many_last[0] = C->ipa_verify_many_last[1] = 0;
@@ -1080,9 +1173,9 @@ int ipa_verify_many(Context* C, const IpaProof* const* proofs, const Vrs* vrs, c
       const IpaProof* pr = proofs[s];
       const size_t k = 2 * (pr->rounds - 1);
       j1.push_back(comm_a + 18 * s);
-      j1.push_back(pr->foldings_fg1);
+      j1.push_back(pr->foldings_fg1.data());
       j2.push_back(comm_b + 36 * s);
-      j2.push_back(pr->foldings_fg2 + 4);
+      j2.push_back(pr->foldings_fg2.data() + 4);
       for (size_t p = 0; p < k; p++) {
         j1.push_back(pr->final_g1.data() + 18 * p);
         j2.push_back(pr->final_g2.data() + 36 * p);
@@ -1219,33 +1312,16 @@ int ipa_verify_many(Context* C, const IpaProof* const* proofs, const Vrs* vrs, c
 //   the final scalar of G1Module prover i is the final lhs of FModule prover i (the same vector, the same challenges, twist 1), the
 //   final point is the folded CRS for every i; the same holds for G2 with rhs
 //
-// and only the K FModule provers stay per claim: they step together (gm_sc_round_begin_many, one challenge for all).  The PModule
-// arena, its fold and the segmented Miller launch of a round are those of ipa_prove.  tests/ipa_batch_ref.py states both forms on
+// and only the K FModule provers stay per claim: they step together (gm_sc_round_begin_many, one challenge for all).  The rounds
+// are ipa_prove_rounds, as for ipa_prove; this entry does the upload and the sums for every K, 1 included.  tests/ipa_batch_ref.py states both forms on
 // Python integers and holds them equal field for field.  No witness takes a twist: the reference's TimeProver uses the twist in
 // `fold` and not in the message (time_prover.rs:83-123), so a proof with another twist cannot satisfy the verifier.
-namespace {
-
-struct BatchProvers {
-  Context* C;
-  std::vector<uint64_t> ff;
-  uint64_t fg1 = 0, fg2 = 0;
-  HerringProver *h1 = nullptr, *h2 = nullptr;
-  ~BatchProvers() {
-    for (uint64_t h : ff) (void)gm_sc_free(h);
-    if (fg1) (void)gm_hg1_free(fg1);
-    if (fg2) (void)gm_hg2_free(fg2);
-  }
-};
-
-}  // namespace
-
 int ipa_prove_batch(Context* C, uint64_t transcript, const Crs* crs, const uint64_t* a_mont, const uint64_t* b_mont, size_t d, size_t K, IpaProof* proof) {
   // every refusal comes before the first challenge
   GM_CHECK(K >= 1, GM_EINVAL, "ipa_new_batch: no claims");
-  GM_CHECK(d >= 2, GM_EINVAL, "ipa_new_batch: d = %zu; the argument needs at least two scalars (the reference's round loop underflows at rounds - 1, ipa.rs:420)", d);
-  const size_t rounds = (size_t)msm_ceil_log2(d), full = (size_t)1 << rounds;
-  const size_t need = std::max(d + 1, full);
-  GM_CHECK(crs->n1 >= need && crs->n2 >= need, GM_EINVAL, "ipa_new_batch: d = %zu needs a CRS of max(d + 1, 2^rounds) = %zu points, it has %zu / %zu", d, need, crs->n1, crs->n2);
+  size_t rounds, full;
+  int rc = ipa_prover_sizes(d, crs, "ipa_new_batch", 420, &rounds, &full);
+  if (rc) return rc;
   GM_CHECK(transcript_exists(transcript), GM_EHANDLE, "ipa_new_batch: unknown transcript handle %llu", (unsigned long long)transcript);
   {
     // the PModule arena and the message records, then the scalars: a_i and b_i in their FModule prover and once more for the sums
@@ -1255,175 +1331,36 @@ int ipa_prove_batch(Context* C, uint64_t transcript, const Crs* crs, const uint6
     const bool fits = K <= (SIZE_MAX - arena) / (4 * d * 32) && arena + 4 * K * d * 32 <= free_b;
     GM_CHECK(fits, GM_ENOMEM, "ipa_new_batch: %zu claims of d = %zu need an arena of %zu bytes and 4 K d 32 bytes of scalars, the device has %zu free", K, d, arena, free_b);
   }
-  uint64_t one[4];
+  uint64_t one[4], ch[4];
   gmh::Fr::one().to_limbs(one);
-  size_t counts[3] = {0, 0, 0};  // split-fold launches, MSM calls, Miller launches, where they are issued
-  typedef std::chrono::steady_clock Clock;
-  auto ms_since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
   const Clock::time_point t_start = Clock::now();
 
-  BatchProvers P{C};
-  int rc;
-  P.ff.reserve(K);
-  for (size_t i = 0; i < K; i++) {
-    uint64_t h = 0;
-    if ((rc = gm_sc_new(a_mont + 4 * i * d, d, b_mont + 4 * i * d, d, one, &h))) return rc;
-    P.ff.push_back(h);
-    if ((rc = gm_sc_set_herring(h, 1))) return rc;
-  }
+  InitialClaims T{"ipa_new_batch"};
+  for (size_t i = 0; i < K; i++)
+    if ((rc = T.add_ff(a_mont + 4 * i * d, b_mont + 4 * i * d, d, one))) return rc;
   Scratch mem;
-  Arena A;
-  uint8_t *aux1 = nullptr, *aux2 = nullptr, *d_ab = nullptr, *d_c = nullptr;  // d_ab: a_0 .. a_{K-1}, b_0 .. b_{K-1}; d_c: ca, cb
-  if ((rc = mem.get(3 * 96, &aux1)) || (rc = mem.get(3 * 192, &aux2)) || (rc = mem.get(2 * K * d * 32, &d_ab)) || (rc = mem.get(2 * d * 32, &d_c))) return rc;
-  if (rounds > 1) {
-    for (int i = 0; i < 2; i++)
-      if ((rc = mem.get(2 * full * 96, &A.g1[i])) || (rc = mem.get(2 * full * 192, &A.g2[i]))) return rc;
-  }
-  A.m = full;
+  uint8_t *d_ab = nullptr, *d_c = nullptr;  // d_ab: a_0 .. a_{K-1}, b_0 .. b_{K-1}; d_c: ca, cb
+  if ((rc = mem.get(2 * K * d * 32, &d_ab)) || (rc = mem.get(2 * d * 32, &d_c))) return rc;
   GM_HIP(hipMemcpyAsync(d_ab, a_mont, K * d * 32, hipMemcpyHostToDevice, C->stream));
   GM_HIP(hipMemcpyAsync(d_ab + K * d * 32, b_mont, K * d * 32, hipMemcpyHostToDevice, C->stream));
   GM_HIP(hipStreamSynchronize(C->stream));
-  uint64_t rec1[36], rec2[72];
-  g1_to_record(g1_generator(), rec1 + 24);
-  g2_to_record(g2_generator(), rec2);
-
-  proof->rounds = rounds;
-  proof->K = K;
-  proof->messages.assign(rounds * 144, 0);
-  proof->challenges.assign(rounds * 4, 0);
-  proof->batch_challenges.clear();
-  proof->host_ms[0] = proof->host_ms[1] = proof->host_ms[2] = 0;
-  std::vector<gmh::Fr> bch;
-  auto push_bch = [&](const gmh::Fr& x) {
-    bch.push_back(x);
-    uint64_t l[4];
-    x.to_limbs(l);
-    proof->batch_challenges.insert(proof->batch_challenges.end(), l, l + 4);
-  };
 
   // the first batch challenge fixes the weights of the 3 K initial provers: the sums, then the two module provers over them
-  uint64_t ch[4];
   if ((rc = gm_transcript_challenge_fr(transcript, (const uint8_t*)"batch-chal", 10, ch))) return rc;
-  {
-    const gmh::Fr bc = gmh::Fr::from_limbs(ch);
-    gmh::Fr w = gmh::Fr::one();
-    for (size_t i = 0; i < 3 * K; i++, w = w * bc) push_bch(w);
+  const gmh::Fr bc = gmh::Fr::from_limbs(ch);
+  std::vector<uint64_t> w(3 * K * 4);
+  T.weights.assign(3 * K, gmh::Fr::one());
+  for (size_t i = 0; i < 3 * K; i++) {
+    if (i) T.weights[i] = T.weights[i - 1] * bc;
+    T.weights[i].to_limbs(w.data() + 4 * i);
   }
-  if ((rc = fr_lincomb_raw(C, d_ab, d * 32, d, proof->batch_challenges.data() + 4 * K, K, d_c))) return rc;
-  if ((rc = fr_lincomb_raw(C, d_ab + K * d * 32, d * 32, d, proof->batch_challenges.data() + 8 * K, K, d_c + d * 32))) return rc;
+  if ((rc = fr_lincomb_raw(C, d_ab, d * 32, d, w.data() + 4 * K, K, d_c))) return rc;
+  if ((rc = fr_lincomb_raw(C, d_ab + K * d * 32, d * 32, d, w.data() + 8 * K, K, d_c + d * 32))) return rc;
   GM_HIP(hipStreamSynchronize(C->stream));
-  // the G1 / G2 provers get the first 2^rounds points, as in ipa_prove; both sides are on the device and are copied
-  if ((rc = herring_create(C, HERRING_G1, crs->g1, 96, full, d_c, 32, d, one, &P.fg1, 3))) return rc;
-  if ((rc = herring_create(C, HERRING_G2, d_c + d * 32, 32, d, crs->g2, 192, full, one, &P.fg2, 3))) return rc;
-  {
-    std::lock_guard<std::mutex> lk(C->mu);
-    P.h1 = C->herring[P.fg1].get();
-    P.h2 = C->herring[P.fg2].get();
-  }
+  if ((rc = T.add_modules(C, crs, full, d_c, d_c + d * 32, d, one, true))) return rc;
 
-  // One message of the batched sumcheck: the K FModule provers step in one launch group, the two module provers as in ipa_prove,
-  // then ONE segmented Miller launch and the two GT multi-exponentiations E^(sum_i bc^i fa_i) m_g1 m_g2 prod_p m_p^bch[3K+p]
-  std::vector<int> has_many(K);
-  auto round_message = [&](const uint64_t* vm, uint64_t* out144) -> int {
-    uint64_t fa[4], fb[4], g1a[18], g1b[18], g2a[36], g2b[36];
-    int has = 0, r;
-    if ((r = gm_sc_round_begin_many(P.ff.data(), K, vm, has_many.data()))) return r;
-    gmh::Fr sa = gmh::Fr::zero(), sb = gmh::Fr::zero();
-    int all = 1;
-    for (size_t i = 0; i < K; i++) {
-      if (!has_many[i]) {
-        all = 0;
-        continue;
-      }
-      if ((r = gm_sc_round_end(P.ff[i], fa, fb))) return r;
-      sa = sa + gmh::Fr::from_limbs(fa) * bch[i];
-      sb = sb + gmh::Fr::from_limbs(fb) * bch[i];
-    }
-    GM_CHECK(all, GM_ESTATE, "ipa_new_batch: an FModule prover has no message");
-    if ((r = herring_round(C, P.h1, vm, g1a, g1b, &has))) return r;
-    GM_CHECK(has, GM_ESTATE, "ipa_new_batch: the G1Module prover has no message");
-    if ((r = herring_round(C, P.h2, vm, g2a, g2b, &has))) return r;
-    GM_CHECK(has, GM_ESTATE, "ipa_new_batch: the G2Module prover has no message");
-    counts[0] += vm ? 2 : 0;  // the point side of either module prover folds in one launch
-    counts[1] += 1 + 3;       // g1_message: one batch of three strided MSMs; g2_message: three MSMs
-    g1_to_record(gmh::G1::from_limbs(g1a), rec1);
-    g1_to_record(gmh::G1::from_limbs(g1b), rec1 + 12);
-    g2_to_record(gmh::G2::from_limbs(g2a), rec2 + 24);
-    g2_to_record(gmh::G2::from_limbs(g2b), rec2 + 48);
-    const std::vector<PairProduct> prods = round_products(aux1, aux2, A);
-    std::vector<gmh::Fq12> m(prods.size());
-    {
-      GM_MSM_LOCK(C);
-      GM_HIP(hipMemcpyAsync(aux1, rec1, sizeof rec1, hipMemcpyHostToDevice, C->stream));
-      GM_HIP(hipMemcpyAsync(aux2, rec2, sizeof rec2, hipMemcpyHostToDevice, C->stream));
-      if ((r = miller_products(C, prods.data(), prods.size(), m.data()))) return r;
-      counts[2] += 1;
-    }
-    const Scalar unit = canonical(gmh::Fr::one());
-    for (int half = 0; half < 2; half++) {
-      std::vector<gmh::Fq12> x = {m[0], m[1 + half], m[3 + half]};
-      std::vector<Scalar> e = {canonical(half ? sb : sa), unit, unit};
-      for (size_t p = 0; p < A.live; p++) {
-        x.push_back(m[5 + 2 * p + half]);
-        e.push_back(canonical(bch[3 * K + p]));
-      }
-      Clock::time_point t0 = Clock::now();
-      const gmh::Fq12 prod = gt_multi_pow(x, e);
-      proof->host_ms[0] += ms_since(t0);
-      t0 = Clock::now();
-      gt_finish(prod).to_limbs(out144 + 72 * half);
-      proof->host_ms[1] += ms_since(t0);
-    }
-    return GM_OK;
-  };
-
-  if ((rc = round_message(nullptr, proof->messages.data()))) return rc;
-  if ((rc = gm_transcript_append_gt(transcript, (const uint8_t*)"prover_message", 14, proof->messages.data(), 2))) return rc;
-  for (size_t j = 0; j + 1 < rounds; j++) {
-    uint64_t* c = proof->challenges.data() + 4 * j;
-    if ((rc = gm_transcript_challenge_fr(transcript, (const uint8_t*)"sumcheck-chal", 13, c))) return rc;
-    if ((rc = gm_transcript_challenge_fr(transcript, (const uint8_t*)"batch-chal", 10, ch))) return rc;
-    const gmh::Fr b = gmh::Fr::from_limbs(ch);
-    push_bch(b);
-    push_bch(b.sqr());
-    {
-      GM_MSM_LOCK(C);
-      if ((rc = arena_round(C, crs, A, gmh::Fr::from_limbs(c), true))) return rc;
-      counts[0] += 2;
-    }
-    uint64_t* msg = proof->messages.data() + 144 * (j + 1);
-    if ((rc = round_message(c, msg))) return rc;
-    if ((rc = gm_transcript_append_gt(transcript, (const uint8_t*)"sumcheck-round", 14, msg, 2))) return rc;
-  }
-  uint64_t* last = proof->challenges.data() + 4 * (rounds - 1);
-  if ((rc = gm_transcript_challenge_fr(transcript, (const uint8_t*)"sumcheck-chal", 13, last))) return rc;
-  counts[0] += A.live ? 2 : 0;
-  if ((rc = arena_finals(C, crs, A, last, proof))) return rc;
-
-  // final foldings: ff_i from prover i; fg1_i = (the folded CRS point, ff_i.lhs); fg2_i = (ff_i.rhs, the folded CRS point)
-  int has = 0;
-  uint64_t p1[18 + 4], p2[4 + 36];
-  if ((rc = herring_fold(C, P.h1, last)) || (rc = herring_fold(C, P.h2, last))) return rc;
-  counts[0] += 2;
-  if ((rc = herring_final(C, P.h1, p1, p1 + 18, &has))) return rc;
-  GM_CHECK(has, GM_ESTATE, "ipa_new_batch: the G1Module prover has no final foldings");
-  if ((rc = herring_final(C, P.h2, p2, p2 + 4, &has))) return rc;
-  GM_CHECK(has, GM_ESTATE, "ipa_new_batch: the G2Module prover has no final foldings");
-  proof->batch_ff.assign(K * 8, 0);
-  proof->batch_fg1.assign(K * 22, 0);
-  proof->batch_fg2.assign(K * 40, 0);
-  for (size_t i = 0; i < K; i++) {
-    uint64_t* ff = proof->batch_ff.data() + 8 * i;
-    if ((rc = gm_sc_fold(P.ff[i], last)) || (rc = gm_sc_final(P.ff[i], ff, ff + 4, &has))) return rc;
-    GM_CHECK(has, GM_ESTATE, "ipa_new_batch: FModule prover %zu has no final foldings", i);
-    memcpy(proof->batch_fg1.data() + 22 * i, p1, 18 * 8);
-    memcpy(proof->batch_fg1.data() + 22 * i + 18, ff, 4 * 8);
-    memcpy(proof->batch_fg2.data() + 40 * i, ff + 4, 4 * 8);
-    memcpy(proof->batch_fg2.data() + 40 * i + 4, p2 + 4, 36 * 8);
-  }
-  memcpy(proof->foldings_ff, proof->batch_ff.data(), sizeof proof->foldings_ff);
-  memcpy(proof->foldings_fg1, proof->batch_fg1.data(), sizeof proof->foldings_fg1);
-  memcpy(proof->foldings_fg2, proof->batch_fg2.data(), sizeof proof->foldings_fg2);
+  size_t counts[3] = {0, 0, 0};
+  if ((rc = ipa_prove_rounds(C, transcript, crs, rounds, T, proof, counts))) return rc;
   proof->host_ms[2] = ms_since(t_start);
   {
     GM_MSM_LOCK(C);
@@ -1439,43 +1376,21 @@ int ipa_prove_batch(Context* C, uint64_t transcript, const Crs* crs, const uint6
 // proof can make terms equal or opposite).  The FModule terms are one exponent of E each.  Launches do not depend on K.  As
 // ipa_verify, it takes the points as members (gm_ipa_check says whether they are).
 int ipa_verify_batch(Context* C, const IpaProof* pr, const Vrs* vrs, const uint64_t* comm_a, const uint64_t* comm_b, const uint64_t* y_mont, size_t K, int* ok) {
-  GM_CHECK(K >= 1 && K == pr->K, GM_EINVAL, "ipa_verify_batch: %zu claims for a proof of %zu", K, pr->K);
-  const size_t R = pr->rounds, k = R >= 1 ? 2 * (R - 1) : 0;
-  const uint64_t *ff = K == 1 && pr->batch_ff.empty() ? pr->foldings_ff : pr->batch_ff.data(), *fg1 = K == 1 && pr->batch_fg1.empty() ? pr->foldings_fg1 : pr->batch_fg1.data(),
-                 *fg2 = K == 1 && pr->batch_fg2.empty() ? pr->foldings_fg2 : pr->batch_fg2.data();
-  GM_CHECK(R >= 1 && pr->messages.size() == R * 144 && pr->challenges.size() == R * 4 && pr->batch_challenges.size() == (3 * K + k) * 4 && pr->final_g1.size() == k * 18 &&
-               pr->final_g2.size() == k * 36 && (K == 1 || (pr->batch_ff.size() == K * 8 && pr->batch_fg1.size() == K * 22 && pr->batch_fg2.size() == K * 40)),
-           GM_EINVAL, "ipa_verify_batch: the proof's fields do not have the lengths of %zu rounds and %zu claims", R, K);
-  GM_CHECK(vrs->levels + 1 >= R, GM_EINVAL, "ipa_verify_batch: a proof of %zu rounds needs %zu levels of the Vrs, it has %zu", R, R - 1, vrs->levels);
-  bool reduced = true;
-  for (size_t i = 0; i < K; i++)
-    reduced = reduced && fr_reduced(y_mont + 4 * i) && fr_reduced(ff + 8 * i) && fr_reduced(ff + 8 * i + 4) && fr_reduced(fg1 + 22 * i + 18) && fr_reduced(fg2 + 40 * i);
-  for (size_t i = 0; i < pr->batch_challenges.size(); i += 4) reduced = reduced && fr_reduced(pr->batch_challenges.data() + i);
-  GM_CHECK(reduced, GM_EINVAL, "ipa_verify_batch: a y, a folding scalar or a batch challenge is not a reduced residue");
+  int rc = ipa_shape(pr, vrs, K, "ipa_verify_batch");
+  if (rc) return rc;
+  GM_CHECK(ipa_claims_reduced(pr, y_mont, K), GM_EINVAL, "ipa_verify_batch: a y, a folding scalar or a batch challenge is not a reduced residue");
   if (K == 1) return ipa_verify(C, pr, vrs, comm_a, comm_b, y_mont, ok);  // gm_ipa_verify's verdict on every input
 
   auto fr = [](const uint64_t* p) { return gmh::Fr::from_limbs(p); };
-  const uint64_t* bch = pr->batch_challenges.data();
-  // affine host records (ark-ff's Montgomery form, the identity all zero) and canonical scalars; segments: comm_a, fg1 / comm_b, fg2
+  const uint64_t *bch = pr->batch_challenges.data(), *ff = pr->foldings_ff.data(), *fg1 = pr->foldings_fg1.data(), *fg2 = pr->foldings_fg2.data();
+  // affine host records and canonical scalars; segments: comm_a, fg1 / comm_b, fg2
   std::vector<uint64_t> pts1(2 * K * 12, 0), pts2(2 * K * 24, 0), sc1(2 * K * 4), sc2(2 * K * 4);
   auto put1 = [&](size_t t, const uint64_t* jac, const gmh::Fr& e) {
-    const gmh::G1 p = gmh::G1::from_limbs(jac);
-    if (!p.is_identity()) {
-      const gmh::G1 q = p.normalized();
-      q.x.to_limbs(pts1.data() + 12 * t);
-      q.y.to_limbs(pts1.data() + 12 * t + 6);
-    }
+    g1_to_host_record(jac, pts1.data() + 12 * t);
     e.to_canonical(sc1.data() + 4 * t);
   };
   auto put2 = [&](size_t t, const uint64_t* jac, const gmh::Fr& e) {
-    const gmh::G2 p = gmh::G2::from_limbs(jac);
-    if (!p.is_identity()) {
-      const gmh::G2 q = p.normalized();
-      q.x.c0.to_limbs(pts2.data() + 24 * t);
-      q.x.c1.to_limbs(pts2.data() + 24 * t + 6);
-      q.y.c0.to_limbs(pts2.data() + 24 * t + 12);
-      q.y.c1.to_limbs(pts2.data() + 24 * t + 18);
-    }
+    g2_to_host_record(jac, pts2.data() + 24 * t);
     e.to_canonical(sc2.data() + 4 * t);
   };
   gmh::Fr ey = gmh::Fr::zero(), eff = gmh::Fr::zero();
@@ -1490,7 +1405,6 @@ int ipa_verify_batch(Context* C, const IpaProof* pr, const Vrs* vrs, const uint6
   }
   const size_t offsets[3] = {0, K, 2 * K};
   uint64_t sum1[2 * 18], sum2[2 * 36];
-  int rc;
   if ((rc = g1_lincomb_many_host(C, pts1.data(), 96, sc1.data(), offsets, 2, sum1))) return rc;
   if ((rc = g2_lincomb_many_host(C, pts2.data(), 192, sc2.data(), offsets, 2, sum2))) return rc;
   const Scalar unit = canonical(gmh::Fr::one());

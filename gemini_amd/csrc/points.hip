@@ -1248,13 +1248,13 @@ int gm_ipa_check(uint64_t proof, size_t* first_bad, int* ok) {
   GM_CHECK(ok != nullptr, GM_EINVAL, "ipa_check: null pointer");
   const size_t k = p->final_g1.size() / 18;
   GM_CHECK(p->final_g2.size() == k * 36, GM_EINVAL, "ipa_check: %zu Lhs final foldings and %zu Rhs ones", k, p->final_g2.size() / 36);
-  // the fg1 / fg2 points of claims 0 .. K - 1 (one claim for every proof but a batch proof), then the final foldings
+  // the fg1 / fg2 points of claims 0 .. K - 1, then the final foldings
   const size_t K = p->K;
-  GM_CHECK(K >= 1 && (K == 1 || (p->batch_fg1.size() == K * 22 && p->batch_fg2.size() == K * 40)), GM_EINVAL, "ipa_check: the foldings of %zu claims are missing", K);
+  GM_CHECK(K >= 1 && p->foldings_fg1.size() == K * 22 && p->foldings_fg2.size() == K * 40, GM_EINVAL, "ipa_check: the foldings of %zu claims are missing", K);
   std::vector<uint64_t> r1((K + k) * 12), r2((K + k) * 24);
   for (size_t c = 0; c < K; c++) {
-    proof_g1_record(K == 1 ? p->foldings_fg1 : p->batch_fg1.data() + 22 * c, r1.data() + 12 * c);
-    proof_g2_record(K == 1 ? p->foldings_fg2 + 4 : p->batch_fg2.data() + 40 * c + 4, r2.data() + 24 * c);
+    proof_g1_record(p->foldings_fg1.data() + 22 * c, r1.data() + 12 * c);
+    proof_g2_record(p->foldings_fg2.data() + 40 * c + 4, r2.data() + 24 * c);
   }
   for (size_t i = 0; i < k; i++) {
     proof_g1_record(p->final_g1.data() + 18 * i, r1.data() + 12 * (K + i));

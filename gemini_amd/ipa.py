@@ -11,7 +11,7 @@ by one test of the reference) and `CrsStream` (its fold is a todo!() in the refe
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 
 import numpy as np
 
@@ -305,40 +305,15 @@ class InnerProductProof:
 
     @classmethod
     def from_fields(cls, f: IpaFields) -> "InnerProductProof":
-        capi.ensure_init()
-        k = 2 * (f.rounds - 1)
-        fg1 = np.concatenate([capi.u64(f.foldings_fg1[0]).reshape(18), capi.u64(f.foldings_fg1[1]).reshape(4)])
-        fg2 = np.concatenate([capi.u64(f.foldings_fg2[0]).reshape(4), capi.u64(f.foldings_fg2[1]).reshape(36)])
-        lhs, rhs = capi.u64(f.final_lhs).reshape(k, 18), capi.u64(f.final_rhs).reshape(k, 36)
-        h = C.c_uint64()
-        capi.check(capi.load().gm_ipa_from_fields(C.c_size_t(f.rounds), capi.ptr(capi.u64(f.messages).reshape(f.rounds, 144)),
-                                                  capi.ptr(capi.u64(f.challenges).reshape(f.rounds, 4)),
-                                                  capi.ptr(capi.u64(f.batch_challenges).reshape(2 * f.rounds + 1, 4)), capi.ptr(lhs) if k else None,
-                                                  capi.ptr(rhs) if k else None, capi.ptr(capi.u64(f.foldings_ff).reshape(8)), capi.ptr(fg1), capi.ptr(fg2),
-                                                  C.byref(h)))
-        return cls(h.value)
+        """a proof for one claim from `fields()`"""
+        return cls.from_fields_batch(replace(f, claims=1))
 
     def fields(self) -> IpaFields:
-        """the fields of the proof; one for K > 1 claims has K-long foldings (`batch_fields`)"""
-        if self.claims != 1:
-            return self.batch_fields()
-        lib, h = capi.load(), C.c_uint64(self.handle)
-        n = C.c_size_t()
-        capi.check(lib.gm_ipa_rounds(h, C.byref(n)))
-        r = n.value
-        k = 2 * (r - 1)
-        msgs, ch, bch = np.empty((r, 2, 72), dtype=np.uint64), np.empty((r, 4), dtype=np.uint64), np.empty((2 * r + 1, 4), dtype=np.uint64)
-        lhs, rhs = np.empty((k, 18), dtype=np.uint64), np.empty((k, 36), dtype=np.uint64)
-        ff = np.empty((2, 4), dtype=np.uint64)
-        g1f, g1s, g2s, g2g = (np.empty(w, dtype=np.uint64) for w in (18, 4, 4, 36))
-        capi.check(lib.gm_ipa_messages(h, capi.ptr(msgs)))
-        capi.check(lib.gm_ipa_challenges(h, capi.ptr(ch)))
-        capi.check(lib.gm_ipa_batch_challenges(h, capi.ptr(bch)))
-        capi.check(lib.gm_ipa_final_foldings(h, capi.ptr(lhs) if k else None, capi.ptr(rhs) if k else None))
-        capi.check(lib.gm_ipa_foldings_ff(h, capi.ptr(ff)))
-        capi.check(lib.gm_ipa_foldings_fg1(h, capi.ptr(g1f), capi.ptr(g1s)))
-        capi.check(lib.gm_ipa_foldings_fg2(h, capi.ptr(g2s), capi.ptr(g2g)))
-        return IpaFields(r, msgs, ch, bch, lhs, rhs, ff, (g1f, g1s), (g2s, g2g))
+        """`batch_fields()`, the foldings without the axis of the claims when there is one claim"""
+        f = self.batch_fields()
+        if f.claims == 1:
+            f.foldings_ff, f.foldings_fg1, f.foldings_fg2 = f.foldings_ff[0], tuple(x[0] for x in f.foldings_fg1), tuple(x[0] for x in f.foldings_fg2)
+        return f
 
     def verify_transcript(self, vrs: Vrs, comm_a, comm_b, y_mont) -> bool:
         """InnerProductProof::verify_transcript(vrs, comm_a, comm_b, y): True for Ok(())"""

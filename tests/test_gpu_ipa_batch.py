@@ -153,6 +153,79 @@ def test_one_claim_is_gm_ipa_new(gm, d, n):
         o.free()
 
 
+def _single_claim_getters(gm, proof):
+    """gm_ipa_foldings_ff / _fg1 / _fg2 -> their three return codes and (ff (8,), fg1 (22,), fg2 (40,))"""
+    lib, ptr, h = gm.capi.load(), gm.capi.ptr, C.c_uint64(proof.handle)
+    ff, fg1, fg2 = (np.zeros(w, dtype=np.uint64) for w in (8, 22, 40))
+    codes = (lib.gm_ipa_foldings_ff(h, ptr(ff)), lib.gm_ipa_foldings_fg1(h, ptr(fg1), ptr(fg1[18:])), lib.gm_ipa_foldings_fg2(h, ptr(fg2), ptr(fg2[4:])))
+    return codes, (ff, fg1, fg2)
+
+
+def _foldings_batch(gm, proof, K):
+    """gm_ipa_foldings_batch -> ff (K, 8), fg1 (K, 22), fg2 (K, 40)"""
+    out = tuple(np.zeros((K, w), dtype=np.uint64) for w in (8, 22, 40))
+    gm.capi.check(gm.capi.load().gm_ipa_foldings_batch(C.c_uint64(proof.handle), *(gm.capi.ptr(x) for x in out)))
+    return out
+
+
+@pytest.mark.parametrize("d,n", [(2, 4), (5, 16)])
+def test_one_claim_has_one_storage(gm, d, n):
+    """a proof of gm_ipa_new and one of gm_ipa_new_batch at K = 1, each rebuilt through from_fields(fields()) and through
+    from_fields_batch(batch_fields()): the same bytes from fields() and from batch_fields() whichever way a proof was made, the
+    single-claim getters are row 0 of gm_ipa_foldings_batch, and every verifier and check accepts every one.  d = 2 has one round,
+    no PModule prover and empty final foldings; d = 5 has three rounds and odd tails."""
+    from tests.test_gpu_ipa_new_many import fields_equal
+
+    p1, _, p2, _ = X.crs(n)
+    (a, b), = B.claims_for(1, d, seed=1200 + d)
+    crs = gm.Crs(g1_points_to_affine(p1), g2_points_to_affine(p2))
+    t1, t2 = gm.Transcript(LABEL), gm.Transcript(LABEL)
+    IP = gm.InnerProductProof
+    made = [IP.new(t1, crs, mont(a), mont(b)), IP.new_batch(t2, crs, [mont(a)], [mont(b)])]
+    rebuilt = [q for p in made for q in (IP.from_fields(p.fields()), IP.from_fields_batch(p.batch_fields()))]
+    f0, b0 = rebuilt[0].fields(), rebuilt[0].batch_fields()
+    k = 2 * (X.ceil_log2(d) - 1)
+    assert f0.rounds == X.ceil_log2(d) and f0.final_lhs.shape == (k, 18) and f0.final_rhs.shape == (k, 36) and f0.batch_challenges.shape == (3 + k, 4)
+    assert f0.foldings_ff.shape == (2, 4) and [x.shape for x in f0.foldings_fg1 + f0.foldings_fg2] == [(18,), (4,), (4,), (36,)]
+    assert b0.foldings_ff.shape == (1, 2, 4) and [x.shape for x in b0.foldings_fg1 + b0.foldings_fg2] == [(1, 18), (1, 4), (1, 4), (1, 36)]
+    vrs = gm.Vrs(crs)
+    ca, cb, y = crs.commit_g1(mont(a)), crs.commit_g2(mont(b)), fr_from_int(X.ip(a, b))
+    for i, p in enumerate(made + rebuilt):
+        assert p.claims == 1, i
+        assert fields_equal(p.fields(), f0) and fields_equal(p.batch_fields(), b0), i
+        codes, single = _single_claim_getters(gm, p)
+        assert codes == (0, 0, 0), i
+        for one, rows in zip(single, _foldings_batch(gm, p, 1)):
+            assert one.tobytes() == rows[0].tobytes(), i
+        assert single[0].tobytes() == f0.foldings_ff.tobytes() and single[1].tobytes() == np.concatenate(f0.foldings_fg1).tobytes(), i
+        assert single[2].tobytes() == np.concatenate(f0.foldings_fg2).tobytes(), i
+        assert p.verify_transcript(vrs, ca, cb, y) and p.verify_batch(vrs, [ca], [cb], [y]), i
+        assert p.check_points().ok and p.check_messages().ok, i
+    for o in made + rebuilt + [vrs, t1, t2, crs]:
+        o.free()
+
+
+def test_three_claims_round_trip(gm):
+    """K = 3 at d = 5 through from_fields_batch(batch_fields()): the same bytes, and the single-claim getters refuse both proofs"""
+    from tests.test_gpu_ipa_new_many import fields_equal
+
+    K = 3
+    ref = reference(K, 5, 16)
+    crs, tr = gm.Crs(ref["r1"], ref["r2"]), gm.Transcript(LABEL)
+    proof = gm.InnerProductProof.new_batch(tr, crs, ref["a_mont"], ref["b_mont"])
+    rebuilt = gm.InnerProductProof.from_fields_batch(proof.batch_fields())
+    f = proof.batch_fields()
+    assert f.claims == K and f.foldings_ff.shape == (K, 2, 4) and f.batch_challenges.shape == (3 * K + 4, 4)
+    for p in (proof, rebuilt):
+        assert p.claims == K
+        assert fields_equal(p.batch_fields(), f) and fields_equal(p.fields(), f)
+        assert _single_claim_getters(gm, p)[0] == (GM_EINVAL, GM_EINVAL, GM_EINVAL)
+        for rows, exp in zip(_foldings_batch(gm, p, K), (f.foldings_ff.reshape(K, 8), np.concatenate(f.foldings_fg1, axis=1), np.concatenate(f.foldings_fg2, axis=1))):
+            assert rows.tobytes() == exp.tobytes()
+    for o in (proof, rebuilt, tr, crs):
+        o.free()
+
+
 def _oracle_with(exp, **changes):
     bad = copy.deepcopy(exp)
     bad.update(changes)
